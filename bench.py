@@ -10,6 +10,12 @@ RCCL/xGMI and de-tiled into the full frame on every rank (strong scaling: the fr
 fixed, the ranks split it).
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task description).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, renders W warm-up frames, times K frames and prints the
+line (`value`, `ms_per_step` and the per-launch figures of the timed frames).  `--full` adds everything else the bench
+measures, each in timed regions or child processes of its own: `sustained`, `without_plane_tracking`, the small kernels'
+timings and the geometry chain alone, the `frames_4k` / `lights_1024` / `shadows` / `fused` sub-records and `cpu_baseline`.
+`--dump-outputs DIR` writes what the last timed frame computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -129,6 +135,29 @@ def ot_num_lods(size):
     return min(11, int(math.log2(size)))
 
 
+DUMP_SAMPLE_PX = 1 << 21        # at most this many pixels of an image are written (seeded sample): 32 MB of RGBA float32
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, images):
+    """Writes each (name, HxWxC array) of `images` as out_dir/<name>.npy in float32, one row per pixel.  An image of more
+    than DUMP_SAMPLE_PX pixels is reduced to the same fixed, seeded set of pixel indices (ascending) for every image of that
+    size, so two builds' files compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    picks = {}
+    for name, a in images:
+        a = a.reshape(a.shape[0] * a.shape[1], -1)
+        n = a.shape[0]
+        if n > DUMP_SAMPLE_PX:
+            if n not in picks:
+                picks[n] = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLE_PX, replace=False))
+            a = a[picks[n]]
+        if a.dtype == np.uint16:            # RGBA16F bits
+            a = a.view(np.float16)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -137,6 +166,10 @@ def main():
     ap.add_argument("--width", type=int, default=7680)
     ap.add_argument("--height", type=int, default=4320)
     ap.add_argument("--size", type=int, default=2048, help="heightmap / world size")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure (module docstring); a plain run only times the --steps frames")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write what the last one computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fixed-camera", action="store_true", help="reference default camera instead of the flythrough")
     ap.add_argument("--no-prepare", action="store_true",
@@ -561,9 +594,25 @@ def main():
     for c in side_ctxs:
         timings.update(c.timing_collect())
         c.timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        # the last timed frame as its caller receives it: HdrColor (packed tiles of the emulated rank's share, or the
+        # assembled frame of an N-rank run), with the depth plane of an unsplit frame beside it
+        if use_dist:
+            dump = [("ldr_color" if ldr else "hdr_color", frame.download())]
+        elif emu:
+            # the rank's owned pixels in packed order (the padding of partial and missing tiles is never written)
+            packed = (ldr_img.download(info["packed_bytes_ldr"]) if emu_ldr else
+                      emu_hdr[(args.warmup + args.steps - 1) % 2].download(info["packed_bytes"])).reshape(-1, 128, 128, 3)
+            px = []
+            for j, t in enumerate(pt.owned_tiles(W, H, args.emulate_rank, args.emulate_world)):
+                px.append(packed[j, :min(128, H - (t // tx_) * 128), :min(128, W - (t % tx_) * 128)].reshape(-1, 1, 3))
+            dump = [("ldr_tiles" if emu_ldr else "hdr_tiles", np.concatenate(px))]
+        else:
+            dump = [("hdr_color", hdr.download()), ("depth", rt.download("depth")[..., None])]
+        dump_outputs(args.dump_outputs, dump)
     # the same K frames once more after a further lap of load (clocks ramped): reported beside `value`, never instead of it
     sustained = None
-    if args.prewarm_laps == 0 and not args.no_sustained:
+    if args.full and args.prewarm_laps == 0 and not args.no_sustained:
         gc.collect(); gc.disable()
         for i in range(120):
             step(args.warmup + args.steps + i)
@@ -585,7 +634,7 @@ def main():
     # every pixel and the lighting pass reads them all, as a renderer without clear / constant metadata would.  Same frames, same
     # bits in the G-buffer and in HdrColor; reported beside `value` so that the tracking's share of it is on the page.
     untracked = None
-    if not args.no_sustained and not args.fused and not args.no_plane_tracking:
+    if args.full and not args.no_sustained and not args.fused and not args.no_plane_tracking:
         ctx.set_plane_tracking(False)
         gc.collect(); gc.disable()
         for i in range(20):
@@ -613,7 +662,7 @@ def main():
             step(args.warmup + i)
         sync()
     kernels_note = None
-    if timing_level == 2:
+    if args.full and timing_level == 2:
         # the small kernels (geometry chain, tone-map stage, de-tile), timed with events around every launch over a few
         # more frames OUTSIDE the timed region
         extra = min(args.steps, 20)
@@ -909,14 +958,14 @@ def main():
                                        "lighting of rank 0's tiles; overlap = share of the exchange hidden behind the next frame's rendering"}
         if verified is not None:
             out["frame_verified_against_unsplit"] = verified
-        if world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows:
+        if args.full and world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows:
             # the north star asks for 4K next to 8K: the same workload at 3840x2160, measured by a child process
             # (same code path, its own context) after this process has gone idle
             try:
                 import subprocess
                 ctx.synchronize()
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--width", "3840", "--height", "2160", "--steps", str(args.steps),
-                                    "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-4k", "--lights", str(args.lights)]
+                                    "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-4k", "--lights", str(args.lights)]
                                    + (["--fixed-camera"] if args.fixed_camera else []),
                                    capture_output=True, text=True, timeout=300)
                 j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -925,12 +974,12 @@ def main():
                                     "k_raster_avg_us": j["kernels"]["k_raster"]["avg_us"]}
             except Exception as e:
                 out["frames_4k"] = {"error": repr(e)}
-        if world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows and not tiled:
+        if args.full and world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows and not tiled:
             # BASELINE config 5 on one GPU: the same frame lit by 1 sun + 1023 point lights through the tiled pass (child process)
             try:
                 import subprocess
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--lights", "1024", "--steps", str(args.steps),
-                                    "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-4k"] + (["--fixed-camera"] if args.fixed_camera else []),
+                                    "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-4k"] + (["--fixed-camera"] if args.fixed_camera else []),
                                    capture_output=True, text=True, timeout=300)
                 j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                 pair_us = sum(j["kernels"][k]["avg_us"] for k in ("k_light_cull", "k_deferred_tiled") if k in j["kernels"])
@@ -945,13 +994,13 @@ def main():
                                       "note": "not bandwidth-bound (SURVEY 7): 1.6 lights reach a covered pixel on average, ~85 instructions each"}
             except Exception as e:
                 out["lights_1024"] = {"error": repr(e)}
-        if world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows and not tiled and not args.fused:
+        if args.full and world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows and not tiled and not args.fused:
             # row f1 (Renderer.cpp:333-372, :427): the same frame with the sun's terrain shadow map (2048^2, depth-only pass per frame)
             # and the 4x4 PCF term in the lighting pass (child process)
             try:
                 import subprocess
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shadows", "--steps", str(args.steps), "--warmup", str(args.warmup),
-                                    "--no-cpu-baseline", "--no-4k"] + (["--fixed-camera"] if args.fixed_camera else []),
+                                    "--full", "--no-cpu-baseline", "--no-4k"] + (["--fixed-camera"] if args.fixed_camera else []),
                                    capture_output=True, text=True, timeout=300)
                 j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                 out["shadows"] = {"value": j["value"], "unit": j["unit"], "ms_per_step": j["ms_per_step"],
@@ -971,12 +1020,12 @@ def main():
                                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(12 * owned_px / (ms_f / n_f * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                                          "avg_us": round(ms_f / n_f * 1e3, 2),
                                          "note": "depth 4 B + HdrColor 8 B written per pixel, nothing read back; bound by the tile pass's own work, not by HBM"}
-        if world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows and not tiled and not args.fused:
+        if args.full and world == 1 and not use_dist and not emu and (W, H) == (7680, 4320) and not args.no_4k and not args.shadows and not tiled and not args.fused:
             # the opt-in fused variant on the same workload (child process): reported beside the graded path, never instead of it
             try:
                 import subprocess
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--fused", "--steps", str(args.steps), "--warmup", str(args.warmup),
-                                    "--no-cpu-baseline", "--no-4k", "--verify"] + (["--fixed-camera"] if args.fixed_camera else []),
+                                    "--full", "--no-cpu-baseline", "--no-4k", "--verify"] + (["--fixed-camera"] if args.fixed_camera else []),
                                    capture_output=True, text=True, timeout=300)
                 j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                 out["fused"] = {"what": "vr_terrain_render_lit (opt-in, SURVEY 7 step 6): TerrainPass::Render + DeferredLightingPass::Render in one pass over the pixels; "
@@ -986,7 +1035,7 @@ def main():
                                 "kernels": {k: v["avg_us"] for k, v in j["kernels"].items() if k.startswith("k_raster")}}
             except Exception as e:
                 out["fused"] = {"error": repr(e)}
-        if world == 1 and not emu and not args.no_cpu_baseline:
+        if args.full and world == 1 and not emu and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(size, hm, al, params, (AMBIENT_TOP, AMBIENT_BOTTOM), camera)
                 # the device counterpart of the reference's (disabled) heightmap update, for the same heightmap

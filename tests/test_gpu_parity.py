@@ -1531,7 +1531,7 @@ def test_bench_n_rank_path_through_rccl_and_the_c_abi(mode):
         port = sock.getsockname()[1]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "3", "--warmup", "1", "--width", "1920", "--height", "1080",
-           "--verify", "--no-cpu-baseline", "--exchange", mode.split("-")[0]] + (["--no-overlap"] if mode.endswith("one-stream") else [])
+           "--full", "--verify", "--no-cpu-baseline", "--exchange", mode.split("-")[0]] + (["--no-overlap"] if mode.endswith("one-stream") else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=420, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1544,6 +1544,48 @@ def test_bench_n_rank_path_through_rccl_and_the_c_abi(mode):
     assert (x["allreduce_us"] > 0) == (mode != "hdr")
     assert "k_raster" in out["kernels"] and ("k_detile_ldr" if mode != "hdr" else "k_detile") in out["kernels"]
     assert out["sustained"]["value"] > 0
+
+
+def test_bench_plain_run_dumps_its_last_timed_frame(scene2048, gpu_ctx, tmp_path):
+    """A plain bench run (no --full) prints the headline line without the sub-records, and --dump-outputs writes the last
+    timed frame (flythrough view warmup + steps - 1): its HdrColor and depth equal the same frame rendered and lit here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from vrenderer_amd.scene import flythrough_camera
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W, H, steps, warmup = 640, 360, 4, 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--width", str(W), "--height", str(H), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["warmup"] == warmup and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "Gpixels/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["sustained"] is None and out["without_plane_tracking"] is None
+    assert not {"frames_4k", "lights_1024", "shadows", "fused", "cpu_baseline", "kernels_note"} & set(out)
+    assert sorted(os.listdir(tmp_path / "out")) == ["depth.npy", "hdr_color.npy"]
+    got_hdr = np.load(tmp_path / "out" / "hdr_color.npy")
+    got_depth = np.load(tmp_path / "out" / "depth.npy")
+    assert got_hdr.dtype == np.float32 and got_hdr.shape == (W * H, 4)
+    assert got_depth.dtype == np.float32 and got_depth.shape == (W * H, 1)
+
+    v = vr.make_view(*flythrough_camera(warmup + steps - 1), W, H)
+    rt = vr.RenderTargets(gpu_ctx).Init(W, H)
+    hdr = vr.HdrImage(gpu_ctx, W, H)
+    rt.Clear()
+    scene2048["tp"].Render(v, v, rt, vr.default_render_params(400.0))
+    vr.DeferredLightingPass(gpu_ctx).Render(v, rt, [vr.reference_sun()], AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+    want_hdr = hdr.download().reshape(-1, 4).view(np.float16).astype(np.float32)
+    want_depth = rt.download("depth").reshape(-1, 1)
+    hdr.close()
+    rt.close()
+    assert (want_depth < 1.0).any(), "the frame shows no terrain"
+    assert np.array_equal(got_depth, want_depth)
+    assert np.array_equal(got_hdr, want_hdr)
 
 
 @pytest.mark.parametrize("cross_stream", [False, True])

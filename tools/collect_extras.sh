@@ -5,9 +5,9 @@ TAG=$1
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-B="--no-cpu-baseline --no-4k"
+B="--full --no-cpu-baseline --no-4k"
 line() { grep '^{' $1 | tail -1; }
-python3 bench.py --steps 20 --warmup 5 > $OUT/driver_style.log 2>&1; line $OUT/driver_style.log > $OUT/bench_8k_driver_style.json
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/driver_style.log 2>&1; line $OUT/driver_style.log > $OUT/bench_8k_driver_style.json
 python3 bench.py $B --steps 120 --warmup 10 > $OUT/unprof.log 2>&1; line $OUT/unprof.log > $OUT/bench_8k_unprofiled.json
 python3 bench.py $B --steps 60 --warmup 10 --lights 1024 > $OUT/l.log 2>&1; line $OUT/l.log > $OUT/bench_8k_lights1024_unprofiled.json
 python3 bench.py $B --steps 60 --warmup 10 --shadows > $OUT/s.log 2>&1; line $OUT/s.log > $OUT/bench_8k_shadows_unprofiled.json

@@ -8,6 +8,6 @@ geo=sum(k.get(n,0) for n in ('k_select','k_vertex','k_setup','k_clip','k_scan','
 print('%.3f ms  %.1f Gpx/s  geometry sum %.0f us ' % (j['ms_per_step'], j['value'], geo), k)"; }
 for rep in 1 2; do for v in "$@"; do
   if [ "$v" = product ]; then cmd="python3 bench.py"; else cmd="python3 tools/ab_bench.py $v"; fi
-  echo -n "$v N=1: "; $cmd --steps 40 --warmup 5 --no-cpu-baseline --no-4k 2>/dev/null | show
-  echo -n "$v N=8 rank 0: "; $cmd --emulate-rank 0 --emulate-world 8 --steps 60 --warmup 10 --no-cpu-baseline --no-4k 2>/dev/null | show
+  echo -n "$v N=1: "; $cmd --full --steps 40 --warmup 5 --no-cpu-baseline --no-4k 2>/dev/null | show
+  echo -n "$v N=8 rank 0: "; $cmd --full --emulate-rank 0 --emulate-world 8 --steps 60 --warmup 10 --no-cpu-baseline --no-4k 2>/dev/null | show
 done; done
