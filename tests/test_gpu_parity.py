@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import vrenderer_amd as vr
+from tests import f64_shading
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
 
 pytestmark = pytest.mark.gpu
@@ -2080,6 +2081,10 @@ def test_deferred_fuzz_random_gbuffer_and_lights(scene256, oracle, gpu_ctx):
         assert (err <= 0.25 * np.abs(ref) + 1e-2).all(), trial
         assert (err > 1.5e-3 * np.abs(ref) + 1e-4).mean() < 1e-3, trial
         assert np.sqrt(np.mean((err / (np.abs(ref) + 1.0)) ** 2)) < 2e-4, trial
+        # and against the float64 model (tests/f64_shading.py): every value within its bound or in a named class
+        pix = f64_shading.Pixels.from_planes(gb)
+        f64_shading.check(got.reshape(-1, 3), f64_shading.reference(pix, v, lights, AMBIENT_TOP, AMBIENT_BOTTOM), pix,
+                          f"fuzz trial {trial}")
     hdr.close(); rt.close()
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import vrenderer_amd as vr
+from tests import f64_shading
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, DEFAULT_EYE, DEFAULT_TARGET, params, scaled_camera
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -232,81 +233,6 @@ def test_flat_terrain_known_answers(oracle):
     t.close()
 
 
-def _shade_numpy(view, gb, lights, amb_top, amb_bot, oracle):
-    """Independent float64 restatement of the deferred model (vectorised numpy)."""
-    h, w = gb.depth.shape
-    lut = np.array([oracle.lib().orc_srgb8_to_linear(c) for c in range(256)], np.float64)
-    alb = np.stack([lut[(gb.diffuse >> s) & 255] for s in (0, 8, 16)], -1)
-    f0 = np.stack([lut[(gb.specular >> s) & 255] for s in (0, 8, 16)], -1)
-    occ = (gb.specular >> 24).astype(np.float64) / 255.0
-    nn = np.maximum(gb.normals.view(np.int16).astype(np.float64) / 32767.0, -1.0)
-    N, rough = nn[..., :3], nn[..., 3]
-    E = gb.emissive.view(np.float16).astype(np.float64)[..., :3]
-    xs, ys = np.meshgrid(np.arange(w) + 0.5, np.arange(h) + 0.5)
-    clip = np.stack([xs * 2 / w - 1, 1 - ys * 2 / h, gb.depth.astype(np.float64), np.ones_like(xs)], -1)
-    wp4 = clip @ np.array(view.clip_to_world[:], np.float64).reshape(4, 4)
-    wp = wp4[..., :3] / wp4[..., 3:]
-    vi = wp - np.array(view.camera_pos[:3], np.float64)
-    vi /= np.linalg.norm(vi, axis=-1, keepdims=True)
-    V = -vi
-    R = vi - 2 * (vi * N).sum(-1, keepdims=True) * N
-    ndv = np.clip((N * V).sum(-1), 0, 1)
-    alpha = np.maximum(0.01, rough ** 2)
-    kk = (rough + 1) ** 2 / 8
-    dterm = np.zeros_like(alb)
-    sterm = np.zeros_like(alb)
-    for l in lights:
-        half = (0.5 * l.angular_size_or_inv_range if l.type == vr.VR_LIGHT_DIRECTIONAL else 0.0) * np.ones(wp.shape[:2])
-        if l.type == vr.VR_LIGHT_DIRECTIONAL:
-            L = -np.array(l.direction[:], np.float64) * np.ones_like(wp)
-            irr = l.intensity * np.ones(wp.shape[:2])
-        else:
-            lts = wp - np.array(l.position[:], np.float64)
-            dist = np.linalg.norm(lts, axis=-1)
-            L = -lts / dist[..., None]
-            att = np.ones_like(dist)
-            if l.angular_size_or_inv_range > 0:
-                att = np.clip(1 - (dist * l.angular_size_or_inv_range) ** 4, 0, 1) ** 2
-            spot = np.ones_like(dist)
-            if l.type == vr.VR_LIGHT_SPOT:
-                ang = np.arccos(np.clip((-L * np.array(l.direction[:], np.float64)).sum(-1), -1, 1))
-                ts = np.clip((ang - l.inner_angle) / (l.outer_angle - l.inner_angle), 0, 1)
-                spot = 1 - ts * ts * (3 - 2 * ts)
-            if l.radius > 0:
-                half = np.arctan(np.minimum(l.radius / dist, 1.0))
-                irr = l.intensity / l.radius ** 2 * half ** 2
-            else:
-                irr = l.intensity / dist ** 2
-            irr = irr * spot * att
-        kd = np.maximum((N * L).sum(-1), 0) / np.pi * irr
-        cosT = np.clip((R * L).sum(-1), -1, 1)
-        ang = np.arccos(cosT)
-        tsl = np.clip(np.where(ang > 0, half / np.maximum(ang, 1e-30), 1.0), 0, 1)
-        # slerp(L, R, t)
-        st = np.sin(np.maximum(ang, 1e-12))
-        wa = np.where(ang > 1e-9, np.sin((1 - tsl) * ang) / st, 1 - tsl)
-        wb = np.where(ang > 1e-9, np.sin(tsl * ang) / st, tsl)
-        CL = wa[..., None] * L + wb[..., None] * R
-        H = CL + V
-        hn = np.linalg.norm(H, axis=-1, keepdims=True)
-        H = np.where(hn > 0, H / np.maximum(hn, 1e-300), 0)
-        ndh = np.clip((N * H).sum(-1), 0, 1)
-        ndl = np.clip((N * CL).sum(-1), 0, 1)
-        vdh = np.clip((V * H).sum(-1), 0, 1)
-        ca = np.clip(alpha + 0.5 * np.tan(half), 0, 1)   # half may vary per pixel (spherical sources)
-        D = alpha ** 2 / (np.pi * (ndh ** 2 * (alpha ** 2 - 1) + 1) ** 2) * (alpha / ca) ** 2
-        G = 1 / ((ndl * (1 - kk) + kk) * (ndv * (1 - kk) + kk))
-        F = f0 + (1 - f0) * ((1 - vdh) ** 5)[..., None]
-        col = np.array(l.color[:], np.float64)
-        dterm += alb * kd[..., None] * col
-        sterm += F * (D * G * ndl / 4 * irr)[..., None] * col
-    t = N[..., 1] * 0.5 + 0.5
-    amb = np.array(amb_bot, np.float64) + (np.array(amb_top, np.float64) - np.array(amb_bot, np.float64)) * t[..., None]
-    dterm += amb * alb * occ[..., None]
-    sterm += amb * f0 * occ[..., None]
-    return dterm + sterm + E
-
-
 def test_deferred_matches_independent_float64_model(oracle):
     """The C oracle's closed-form area-light correction equals the slerp formulation (float64 numpy)."""
     g = np.load(os.path.join(GOLD, "frame_256x144.npz"))
@@ -321,7 +247,7 @@ def test_deferred_matches_independent_float64_model(oracle):
     got = oracle.deferred(v, gb, lights, AMBIENT_TOP, AMBIENT_BOTTOM, f32=True)[..., :3]
     only_sun = oracle.deferred(v, gb, lights[:1], AMBIENT_TOP, AMBIENT_BOTTOM, f32=True)[..., :3]
     assert np.abs(got - only_sun).max() > 1e-3, "the local lights must reach the terrain"
-    want = _shade_numpy(v, gb, lights, AMBIENT_TOP, AMBIENT_BOTTOM, oracle)
+    want = f64_shading.shade_frame(v, gb, lights, AMBIENT_TOP, AMBIENT_BOTTOM)
     assert np.abs(got - want).max() < 2e-5 * max(1.0, np.abs(want).max())
 
 
@@ -595,3 +521,54 @@ def test_oracle_under_address_and_undefined_behaviour_sanitizers(tmp_path):
             "print('sanitized frame ok', n)\n")
     r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "sanitized frame ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+
+
+EDGE_W, EDGE_H = 512, 128
+
+
+@pytest.mark.parametrize("lights_name", ["suns", "points", "extra", "max", "tiled"])
+def test_oracle_within_the_float64_bound_on_the_edge_case_frame(oracle, lights_name):
+    """The fp32 oracle's half output against the float64 model (tests/f64_shading.py) on the edge-case frame: every
+    unflagged value within its bound, flagged ones in their envelope, NaN / infinity where the model has them."""
+    view, planes, rows = f64_shading.edge_case_frame(vr, EDGE_W, EDGE_H)
+    lights = f64_shading.edge_lights(vr, view, planes, rows)[lights_name]
+    gb = oracle.GBufferHost(EDGE_W, EDGE_H)
+    for k, a in planes.items():
+        getattr(gb, k)[...] = a
+    got = oracle.half_to_float(oracle.deferred(view, gb, lights, AMBIENT_TOP, AMBIENT_BOTTOM))[..., :3]
+    pix = f64_shading.Pixels.from_planes(planes)
+    r = f64_shading.check(got.astype(np.float64).reshape(-1, 3),
+                          f64_shading.reference(pix, view, lights, AMBIENT_TOP, AMBIENT_BOTTOM), pix, f"oracle, {lights_name}",
+                          caps=f64_shading.EDGE_CAPS)
+    assert r["checked"] > 0.9 * got.size
+    if not any(l.type == vr.VR_LIGHT_DIRECTIONAL for l in lights):
+        return
+    y0, y1 = rows["far_plane"]
+    amb_only = f64_shading.reference(f64_shading.Pixels.from_planes(planes, np.arange(EDGE_W), np.full(EDGE_W, y0)), view, [],
+                                     AMBIENT_TOP, AMBIENT_BOTTOM)["ref"]
+    assert (np.abs(got[y0, :, :3] - amb_only) > 1e-3).mean() > 0.2, "texels at depth 1.0 with real planes are lit"
+
+
+@pytest.mark.parametrize("width,w_scale", [(2048, 1.0), (2048, 2.0), (2047, 1.0)])
+def test_oracle_shadowed_within_the_float64_bound(oracle, width, w_scale):
+    """The shadowed oracle on the PCF frame (tests/f64_shading.py: pcf_frame): receivers over the map's ramp,
+    checkerboard, constants 0 and 1 and exactly on a stored depth, footprints over every edge and corner, u / v / zc
+    exactly 0 and 1, an orthographic (w = 1) and a general (w = 2) light matrix; every pixel checked."""
+    cam, lv, smap, planes = f64_shading.pcf_frame(vr, w_scale, width)
+    sun = vr.reference_sun()
+    lights = [sun, vr.directional_light((0.3, -1.0, 0.2), 0.5, 0.0)]
+    gb = oracle.GBufferHost(width, f64_shading.PCF_H)
+    for k, a in planes.items():
+        getattr(gb, k)[...] = a
+    got = oracle.half_to_float(oracle.deferred(cam, gb, lights, AMBIENT_TOP, AMBIENT_BOTTOM,
+                                               shadow=(lv, smap, 0, f64_shading.PCF_BIAS)))[..., :3]
+    pix = f64_shading.Pixels.from_planes(planes)
+    sh = (lv, smap, 0, f64_shading.PCF_BIAS, sun.out_of_bounds_shadow)
+    r = f64_shading.reference(pix, cam, lights, AMBIENT_TOP, AMBIENT_BOTTOM, shadow=sh,
+                              exact_geometry=True if width == 2048 else "vz")
+    res = f64_shading.check(got, r, pix, f"oracle, PCF frame {width}, w = {w_scale}")
+    assert res["checked"] > 0.99 * got.size
+    cov = f64_shading.pcf_coverage(r["shadow_geo"], W=width)
+    for k in ("v0", "v1", "z0", "z1", "edge", "outside") + (("u0", "u1") if width == 2048 else ()):
+        assert cov[k] > 0, cov
+    assert cov["clamp_path"] > 1000 and cov["row_path"] > 1000, cov

@@ -401,7 +401,7 @@ __device__ __forceinline__ bool sphere_touches(const float* __restrict__ box, co
 // rows 30 KB apart.  The entries are consumed: reset to "none" for the next frame.
 template <bool RANGES>
 __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLight* __restrict__ lights, int num_lights,
-                                                     const float* __restrict__ g_depth, int macro_x,
+                                                     const float* __restrict__ g_depth, const uint2* __restrict__ g_nrm, int macro_x,
                                                      const int32_t* __restrict__ owned_tiles, uint32_t* __restrict__ lists, int stride,
                                                      int tiles32_x, int tiles32_y, uint32_t* __restrict__ overflow_flag,
                                                      uint32_t* __restrict__ macro_scratch, uint2* __restrict__ ranges)
@@ -436,7 +436,22 @@ __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLig
         const int py = y0 + r * 8 + (tid >> 5);
         const bool ok = py < a.h && px < a.w;                           // the frame width is a multiple of 4
         dv[r] = *reinterpret_cast<const float4*>(g_depth + (ok ? (size_t)py * a.w + px : (size_t)0));
-        if (!ok) dv[r] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+        if (!ok) dv[r] = make_float4(2.0f, 2.0f, 2.0f, 2.0f);
+    }
+    // A texel at depth 1.0 is a surface at the far plane unless its normal word is zero (a cleared texel, or one that no light
+    // can reach: with N = 0 and roughness 0 every light's term is +0).  Only quads that hold such a depth read the normals.
+#pragma unroll
+    for (int r = 0; r < kMacroTile / 8; r++) {
+        const float4 d = dv[r];
+        if (d.x == 1.0f || d.y == 1.0f || d.z == 1.0f || d.w == 1.0f) {
+            const int py = y0 + r * 8 + (tid >> 5);
+            const uint4* q = reinterpret_cast<const uint4*>(g_nrm + (size_t)py * a.w + px);
+            const uint4 n0 = q[0], n1 = q[1];
+            if (d.x == 1.0f && (n0.x | n0.y) == 0u) dv[r].x = 2.0f;
+            if (d.y == 1.0f && (n0.z | n0.w) == 0u) dv[r].y = 2.0f;
+            if (d.z == 1.0f && (n1.x | n1.y) == 0u) dv[r].z = 2.0f;
+            if (d.w == 1.0f && (n1.z | n1.w) == 0u) dv[r].w = 2.0f;
+        }
     }
 #pragma unroll
     for (int sub_y = 0; sub_y < kSubSide; sub_y++) {
@@ -445,7 +460,8 @@ __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLig
         for (int r = sub_y * 4; r < sub_y * 4 + 4; r++) {
             const float v[4] = { dv[r].x, dv[r].y, dv[r].z, dv[r].w };
 #pragma unroll
-            for (int k = 0; k < 4; k++) if (v[k] < 1.0f) { dmin = fmin1(dmin, v[k]); dmax = fmax1(dmax, v[k]); }
+            // depth 1.0 counts (a far-plane surface is lit); the texels that no light reaches were set to 2.0 above
+            for (int k = 0; k < 4; k++) if (v[k] <= 1.0f) { dmin = fmin1(dmin, v[k]); dmax = fmax1(dmax, v[k]); }
         }
 #pragma unroll
         for (int off = 1; off <= 4; off <<= 1) { dmin = fmin1(dmin, __shfl_xor(dmin, off)); dmax = fmax1(dmax, __shfl_xor(dmax, off)); }
@@ -678,6 +694,13 @@ __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const De
         na[0] = n0.x; na[1] = n0.y; na[2] = n0.z; na[3] = n0.w; na[4] = n1.x; na[5] = n1.y; na[6] = n1.z; na[7] = n1.w;
         ea[0] = e0.x; ea[1] = e0.y; ea[2] = e0.z; ea[3] = e0.w; ea[4] = e1.x; ea[5] = e1.y; ea[6] = e1.z; ea[7] = e1.w;
     }
+    // A texel that holds the clear values (sky) receives no light: with albedo, F0, the normal and the emissive term all zero
+    // every light's term is +0 (as in k_deferred's early-out).  Any other texel is lit - one at the far plane (depth 1.0, the
+    // raster's LessEqual accepts it) included.
+    bool bg[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        bg[k] = depth[k] == 1.0f && (dfa[k] | spa[k] | na[2 * k] | na[2 * k + 1] | ea[2 * k] | ea[2 * k + 1]) == 0u;
     uint32_t o[8];
     // The tile's lights go through LDS 256 at a time: one round - staged once, before the pixel loop - unless the tile
     // keeps more than that; then every pixel batch walks the rounds itself (barriers inside; n is workgroup-uniform).
@@ -698,7 +721,7 @@ __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const De
     __syncthreads();                                                 // (also publishes the decode table)
 #pragma unroll
     for (int kb = 0; kb < 4; kb += PXB) {
-        // (a background pixel's position is never used: albedo = F0 = N = 0 and it receives no light)
+        // (a background pixel's position is never used: it receives no light)
         Surface sv[PXB];
         float dT[PXB][3], sT[PXB][3];
 #pragma unroll
@@ -717,11 +740,11 @@ __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const De
                     const float tanH = t.inv_range * fast_rcp(t.w);
 #pragma unroll
                     for (int j = 0; j < PXB; j++)
-                        if (depth[kb + j] < 1.0f) add_light(sv[j], VR_LIGHT_DIRECTIONAL, t.vec, 0.0f, t.color, 1.0f, t.w, t.inv_range, tanH, dT[j], sT[j]);
+                        if (!bg[kb + j]) add_light(sv[j], VR_LIGHT_DIRECTIONAL, t.vec, 0.0f, t.color, 1.0f, t.w, t.inv_range, tanH, dT[j], sT[j]);
                 } else {
 #pragma unroll
                     for (int j = 0; j < PXB; j++)
-                        if (depth[kb + j] < 1.0f) add_light(sv[j], VR_LIGHT_POINT, t.vec, t.inv_range, t.color, 1.0f, 1.0f, 0.0f, 0.0f, dT[j], sT[j], nullptr, true);
+                        if (!bg[kb + j]) add_light(sv[j], VR_LIGHT_POINT, t.vec, t.inv_range, t.color, 1.0f, 1.0f, 0.0f, 0.0f, dT[j], sT[j], nullptr, true);
                 }
             }
         }
@@ -810,7 +833,7 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
         if (pt->num_owned > 0) {
             { VrKernelScope kc(ctx, VR_K_LIGHT_CULL);
               hipLaunchKernelGGL(use_ranges ? k_light_cull<true> : k_light_cull<false>, dim3((unsigned)pt->num_owned), dim3(256), 0, ctx->stream, a, ctx->d_lights,
-                                 num_lights, gb->depth, macro_x, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
+                                 num_lights, gb->depth, (const uint2*)gb->normals, macro_x, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
                                  gb->d_ranges); }
             VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
             VR_LAUNCH_TIMED(ks, (k_deferred_tiled<true, VR_TILED_PXB>), dim3((unsigned)pt->num_owned * kSubTiles), dim3(256), ctx->stream, a,
@@ -821,7 +844,7 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
         VR_REQUIRE((size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
         { VrKernelScope kc(ctx, VR_K_LIGHT_CULL);
           hipLaunchKernelGGL(use_ranges ? k_light_cull<true> : k_light_cull<false>, dim3((unsigned)(macro_x * macro_y)), dim3(256), 0, ctx->stream, a, ctx->d_lights,
-                             num_lights, gb->depth, macro_x, (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
+                             num_lights, gb->depth, (const uint2*)gb->normals, macro_x, (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
                              gb->d_ranges); }
         VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
         const bool nt = true;                                         // as in the streaming pass

@@ -1576,7 +1576,7 @@ __global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : V
     Rec nrec;                                                     // the NEXT pixel's record
     if (!depth_only) nrec = fetch_rec((uint32_t)nkeys[0]);
     else { nrec.g5 = (u32x4){ 0u, 0u, 0u, 0u }; nrec.g6 = (u3){ 0u, 0u, 0u }; nrec.g7 = nrec.g6; }
-    // RANGES: smallest / largest depth bits below 1.0 this lane has seen in the upper / lower 32 rows of the tile
+    // RANGES: smallest / largest depth bits of the covered pixels (1.0 included) this lane has seen in the upper / lower 32 rows of the tile
     uint32_t rmin0 = 0x7f800000u, rmax0 = 0u, rmin1 = 0x7f800000u, rmax1 = 0u;
     bool skip_all = false, skip_spec = false;                     // (wave-uniform)
     if constexpr (TRACK) {
@@ -1633,7 +1633,7 @@ __global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : V
             if (!cov && !a.assume_cleared) continue;               // keep what the target holds
             const uint32_t dep = (uint32_t)(key >> 32);
             uint32_t dif = 0, nn0 = 0, nn1 = 0;
-            if (RANGES && cov && dep < 0x3f800000u) {
+            if (RANGES && cov && dep <= 0x3f800000u) {
                 if (TILE == 64 && ly0 >= 32) { rmin1 = min(rmin1, dep); rmax1 = max(rmax1, dep); }       // (wave-uniform: a strip lies in one half)
                 else { rmin0 = min(rmin0, dep); rmax0 = max(rmax0, dep); }
             }
