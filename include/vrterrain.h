@@ -421,9 +421,19 @@ VR_API int    vr_frame_allgather_tiles(vr_context* ctx, void* nccl_comm, const v
 /* donut::render::ToneMappingPass as used by the reference: created with default CreateParameters
  * (Renderer.cpp:256-257), AdvanceFrame(seconds) (:188-189), SimpleRender(cmd, ToneMappingParameters(),
  * view, HdrColor) into LdrColor SRGBA8 (:430-431, Renderer.h:81-95).  [DONUT-RECOLLECTION: luminance
- * histogram (256 bins over log2 luminance, 6-bit fixed-point weights split over two bins) -> average
+ * histogram (256 bins over log2 luminance, fixed-point weights split over two bins) -> average
  * log luminance between two percentiles -> eye adaptation -> extended Reinhard on luminance.]
- * Integer results (histogram, SRGBA8 pixels) are bit-exact against the oracle. */
+ * Integer results (histogram, SRGBA8 pixels) are bit-exact against the oracle.
+ * Bin weights: a pixel adds Q = 64 >> s, split over two bins, where s is the smallest shift with Q * width * height
+ * <= 2^32 - 1 (the whole frame's width * height, also with a partition, so every rank uses the same Q and the bins summed
+ * over the ranks fit): Q = 64 below 2^26 pixels, and no 32-bit bin can wrap for ONE frame per reset_histogram (adding
+ * several frames without a reset can).  A frame of 2^32 pixels or more is VR_ERR_INVALID_ARGUMENT.
+ * Eye adaptation: adapted := old + (target - old)(1 - e^(-dt * speed)), speed = eye_adaptation_speed_up when target > old,
+ * else eye_adaptation_speed_down.  An adapted value <= 0 ("unset") jumps to the target, and so does a direction whose speed
+ * is <= 0 (it does not hold still).
+ * Operator: mapped / luminance is one fused division; where its denominator overflows it is evaluated in the written order
+ * (s (1 + s / wp^2) / (1 + s), then / luminance), so an extreme exposure saturates instead of giving inf / inf.  A pixel
+ * whose luminance is +inf is NaN through that formula and encodes to 0, as do NaN, zero and negative luminances. */
 typedef struct vr_tonemap_params {          /* ToneMappingParameters defaults + CreateParameters' log range */
     float histogram_low_percentile;         /* 0.8  */
     float histogram_high_percentile;        /* 0.95 */

@@ -37,6 +37,7 @@
  * the diff statistics against that float64 model in the commit.  A kernel optimisation is no reason for one. */
 #define ORC_MODEL_REVISION 3
 
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1391,6 +1392,12 @@ void orc_tonemap_histogram(const vr_tonemap_params* p, const uint16_t* hdr, int 
                            uint32_t hist[VR_TONEMAP_BINS])
 {
     const float scale = 1.0f / (p->max_log_luminance - p->min_log_luminance), bias = (0.0f - p->min_log_luminance) * scale;
+    /* bin weight quantum: 64 >> s, s the smallest shift with q * w * h <= 2^32 - 1 (the whole frame's w * h, also for a
+     * rank's share), so that no bin wraps; more pixels than that: nothing is counted (the product returns an error) */
+    const uint64_t npx = (uint64_t)w * (uint64_t)h;
+    uint32_t q = 64u;
+    while (q > 0u && (uint64_t)q * npx > 0xffffffffull) q >>= 1;
+    if (q == 0u) return;
     for (int y = 0; y < h; y++) for (int x = 0; x < w; x++) {
         if (!owns_pixel(part, x, y)) continue;
         const uint16_t* px = hdr + ((size_t)y * w + x) * 4;
@@ -1404,7 +1411,7 @@ void orc_tonemap_histogram(const vr_tonemap_params* p, const uint16_t* hdr, int 
         float hb = t * (float)(VR_TONEMAP_BINS - 1);
         float lf = floorf(hb);
         int left = (int)lf;
-        uint32_t rw = (uint32_t)((hb - lf) * 64.0f), lw = 64u - rw;   /* 6-bit fixed-point weights */
+        uint32_t rw = (uint32_t)((hb - lf) * (float)q), lw = q - rw;   /* fixed-point weights, q = 64 below 2^26 pixels */
         if (lw != 0u && left < VR_TONEMAP_BINS) hist[left] += lw;
         if (rw != 0u && left + 1 < VR_TONEMAP_BINS) hist[left + 1] += rw;
     }
@@ -1458,7 +1465,13 @@ void orc_tonemap_apply(const vr_tonemap_params* p, float adapted, const uint16_t
         if (src > 0.0f) {
             /* mapped = scaled (1 + scaled / white^2) / (1 + scaled);  k = mapped / src, as one division */
             float scaled = (exposure_scale * src) * inv_adapted;
-            k = (scaled * (1.0f + scaled * wp_inv2)) / ((1.0f + scaled) * src);
+            float num = scaled * (1.0f + scaled * wp_inv2), den = (1.0f + scaled) * src;
+            k = num / den;
+            if (!(den <= FLT_MAX) && src <= FLT_MAX) {
+                /* the denominator overflowed (k would be inf / inf = NaN, or 0): mapped / src in the written order, +inf
+                 * where that overflows; scaled itself is +inf only above fp32's range, where the exact mapped is too */
+                k = (scaled <= FLT_MAX ? num / (1.0f + scaled) : INFINITY) / src;
+            }
         }
         for (int ch = 0; ch < 3; ch++) ldr[i*4+ch] = orc_linear_to_srgb8(src > 0.0f ? c[ch] * k : 0.0f);   /* SRGBA8 target: saturate + OETF */
         ldr[i*4+3] = 255;

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import vrenderer_amd as vr
-from tests import f64_shading
+from tests import f64_shading, f64_tonemap
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, DEFAULT_EYE, DEFAULT_TARGET, params, scaled_camera
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -411,10 +411,14 @@ def test_tonemap_known_answers(oracle):
     assert abs((a1 - a0) / (target - a0) - (1 - np.exp(-1.0 / 60.0 * 1.0))) < 2e-3      # brighter: eyeAdaptationSpeedUp = 1
     tm.SimpleRender(p, frame([0.05], [1024])); a2 = tm.adapted
     assert abs((a1 - a2) / (a1 - a0) - (1 - np.exp(-1.0 / 60.0 * 0.5))) < 2e-2         # darker: speedDown = 0.5
-    # black pixels stay black, inf saturates
+    # black pixels stay black; an inf pixel has L = inf, s = inf and mapped = inf / inf = NaN in the written order (the
+    # float64 model, tests/f64_tonemap.py): it encodes to black
     img = np.zeros((1, 2, 4), np.float16); img[0, 1, :3] = np.inf
-    out = oracle.ToneMapper().SimpleRender(p, img.view(np.uint16))
-    assert out[0, 0].tolist() == [0, 0, 0, 255] and out[0, 1, 3] == 255
+    tm = oracle.ToneMapper()
+    out = tm.SimpleRender(p, img.view(np.uint16))
+    model = f64_tonemap.operator(img.view(np.uint16)[0, :, :3], tm.adapted, p)
+    assert model["lo"].tolist() == model["hi"].tolist() == [[0, 0, 0], [0, 0, 0]]
+    assert out[0, 0].tolist() == [0, 0, 0, 255] and out[0, 1].tolist() == [0, 0, 0, 255]
 
 
 def test_shadow_view_and_shadow_term_known_answers(oracle, t256):
@@ -572,3 +576,108 @@ def test_oracle_shadowed_within_the_float64_bound(oracle, width, w_scale):
     for k in ("v0", "v1", "z0", "z1", "edge", "outside") + (("u0", "u1") if width == 2048 else ()):
         assert cov[k] > 0, cov
     assert cov["clamp_path"] > 1000 and cov["row_path"] > 1000, cov
+
+
+# ---- the tone mapper against its float64 model (tests/f64_tonemap.py) ----------------------------------------------
+def _oracle_step(oracle, tm, p, frame, dt, what, old):
+    tm.AdvanceFrame(dt)
+    ldr = tm.SimpleRender(p, frame)
+    rgb = frame[..., :3].reshape(-1, 3)
+    return f64_tonemap.check_step(tm.hist, tm.adapted, ldr[..., :3].reshape(-1, 3), f64_tonemap.PixelSet.from_frame(frame), p, dt,
+                                  old, what, codes=rgb)
+
+
+@pytest.mark.parametrize("w", [512, 509])
+def test_oracle_tonemap_within_the_float64_bound_on_the_edge_frame(oracle, w):
+    """Bin boundaries k + j/Q and fp32 ulps around them, the range ends and beyond, every half code in each channel,
+    negative channels, OETF thresholds and the white point: histogram envelope, exposure bounds, LDR bytes."""
+    p = vr.default_tonemap_params()
+    frame = f64_tonemap.as_frame(f64_tonemap.edge_pixels(p), w)
+    r = _oracle_step(oracle, oracle.ToneMapper(), p, frame, 1 / 60, f"oracle edge frame, w {w}", 0.0)
+    print(r)
+    tm = oracle.ToneMapper(); tm.adapted = 0.18                  # the operator at the adapted value the frame was built for
+    ldr = tm.Render(p, frame)
+    worst, counts, checked = f64_tonemap.check_ldr(ldr[..., :3].reshape(-1, 3), frame[..., :3].reshape(-1, 3), 0.18, p, "oracle, A = 0.18")
+    print(worst, counts)
+    assert checked > 0.99 * frame[..., :3].size and counts["rounding"] > 0 and counts["saturated"] > 0 and counts["inf_nan"] > 0
+
+
+def test_oracle_tonemap_within_the_float64_bound_on_the_golden_frame(oracle):
+    p = vr.default_tonemap_params()
+    hdr = np.load(os.path.join(GOLD, "frame_256x144.npz"))["hdr"]
+    tm = oracle.ToneMapper()
+    old = 0.0
+    for i in range(3):                                          # the first frame jumps, the next two adapt from it
+        r = _oracle_step(oracle, tm, p, hdr, 1 / 60, f"golden frame, step {i}", old)
+        old = tm.adapted
+        print(r)
+
+
+@pytest.mark.parametrize("case", [c[0] for c in f64_tonemap.adaptation_cases()])
+def test_oracle_tonemap_adaptation_sequences(oracle, case):
+    """Each step from the oracle's own previous value; the two rules of the header (old <= 0 jumps, speed <= 0 jumps)."""
+    name, kw, steps = next(c for c in f64_tonemap.adaptation_cases() if c[0] == case)
+    p = vr.default_tonemap_params(**kw)
+    tm = oracle.ToneMapper()
+    old = 0.0
+    for i, (kind, dt) in enumerate(steps):
+        _oracle_step(oracle, tm, p, f64_tonemap.sequence_frame(kind, i), dt, f"{case} step {i}", old)
+        if dt == 0.0 and old > 0.0 and (kw.get("eye_adaptation_speed_up", 1.0) > 0.0 and kw.get("eye_adaptation_speed_down", 1.0) > 0.0):
+            assert tm.adapted == old, "dt = 0 holds the adapted value"
+        old = tm.adapted
+
+
+def test_oracle_tonemap_does_not_wrap_above_2_26_pixels(oracle):
+    """16384 x 4200 (68.8 M pixels): 4100 black rows, 100 rows at 0.3.  Q drops to 32; the black bin holds 32 * 67.2 M
+    (64 * 67.2 M wrapped to 4.2 M before, and the window landed in the bright band).  Closed-form model; also a world-2
+    share (the whole frame's Q)."""
+    w, h, rows = 16384, 4200, 100
+    p = vr.default_tonemap_params()
+    g = f64_tonemap._to_half(0.3)
+    frame = np.zeros((h, w, 4), np.uint16)
+    frame[h - rows:, :, :3] = g
+    tm = oracle.ToneMapper()
+    tm.AddFrameToHistogram(p, frame)
+    tm.ComputeExposure(p)
+    ps = f64_tonemap.banded(w, h, rows, 0.3)
+    hm = f64_tonemap.histogram_model(ps, p)
+    assert hm["q"] == 32
+    f64_tonemap.check_histogram(tm.hist, hm, "banded 16384x4200")
+    f64_tonemap.check_exposure(tm.adapted, tm.hist, hm, p, 0.0, 0.0, "banded 16384x4200")
+    assert tm.adapted == pytest.approx(0.02), "the 0.8..0.95 window lies in the black rows: minimum adapted luminance"
+    ldr = tm.Render(p, frame[h - rows - 2:h - rows + 2])
+    f64_tonemap.check_ldr(ldr[..., :3].reshape(-1, 3), frame[h - rows - 2:h - rows + 2, :, :3].reshape(-1, 3), tm.adapted, p, "banded LDR")
+    part = vr.Partition(1, 2)
+    tm2 = oracle.ToneMapper()
+    tm2.AddFrameToHistogram(p, frame, part)
+    share = f64_tonemap.banded_share(w, h, rows, 0.3, 1, 2)
+    f64_tonemap.check_histogram(tm2.hist, f64_tonemap.histogram_model(share, p, frame_pixels=w * h), "banded, rank 1 of 2")
+
+
+@pytest.mark.parametrize("how", ["reset_exposure", "min_adapted"])
+def test_oracle_tonemap_extreme_exposure_saturates(oracle, how):
+    """adapted = 1e-30: the fused mapped / src overflows (inf / inf); bright pixels must come out 255, not black."""
+    vals = [60000.0, 1.0, 1e-4, 0.0]
+    codes = [[f64_tonemap._to_half(v)] * 3 for v in vals] + [[f64_tonemap._to_half(0.5), 0, 0], [0, f64_tonemap._to_half(65504.0), 0]]
+    frame = f64_tonemap.as_frame(np.array(codes, np.uint16), len(codes))
+    p = vr.default_tonemap_params(**({"min_adapted_luminance": 1e-30, "max_adapted_luminance": 1e-30} if how == "min_adapted" else {}))
+    tm = oracle.ToneMapper()
+    if how == "reset_exposure":
+        tm.adapted = 1e-30
+    else:
+        tm.ComputeExposure(p)                                     # empty histogram: min_log -> clamp to [1e-30, 1e-30]
+        assert np.float32(tm.adapted) == np.float32(1e-30)
+    ldr = tm.Render(p, frame)[0, :, :3]
+    f64_tonemap.check_ldr(ldr, frame[0, :, :3], tm.adapted, p, f"extreme exposure ({how})")
+    assert ldr[:3].tolist() == [[255] * 3] * 3 and ldr[3].tolist() == [0, 0, 0]
+    assert ldr[4].tolist() == [255, 0, 0] and ldr[5].tolist() == [0, 255, 0]
+
+
+def test_tonemap_model_constants():
+    """The derived constants of tests/f64_tonemap.py: position delta over every fp32 luminance of the range, the exp2
+    cubic's error, the weight quantum."""
+    d = f64_tonemap.position_delta(-10.0, 4.0)
+    assert 0.005 < d < 0.03, d                                   # 1/64 of a bin is 0.0156: the split's resolution
+    assert 1e-5 < f64_tonemap.exp2_error() < 2e-4
+    assert f64_tonemap.quantum(2 ** 26 - 1) == 64 and f64_tonemap.quantum(2 ** 26) == 32
+    assert f64_tonemap.quantum(16384 * 4200) == 32 and f64_tonemap.quantum(2 ** 32 - 1) == 1 and f64_tonemap.quantum(2 ** 32) == 0

@@ -14,6 +14,7 @@
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
 
+#include <float.h>
 #include <math.h>
 #include <string.h>
 
@@ -29,7 +30,19 @@ struct TmArgs {
     int w, h, tiles_x;
     float scale, bias;                       // log-luminance -> [0, 1]
     float exposure_scale, wp_inv2, min_adapted;
+    uint32_t q;                              // bin weight quantum of one pixel (tm_bin_quantum)
 };
+
+// Q = 64 >> s, s the smallest shift with Q * pixels <= 2^32 - 1 (pixels of the whole frame, also for a rank's share): no
+// bin, LDS copy or per-workgroup sum can exceed Q * pixels, so the 32-bit bins never wrap, summed over the ranks included.
+// 0 = more than 2^32 - 1 pixels.
+static uint32_t tm_bin_quantum(int w, int h)
+{
+    const uint64_t n = (uint64_t)w * (uint64_t)h;
+    uint32_t q = 64u;
+    while (q > 0u && (uint64_t)q * n > 0xffffffffull) q >>= 1;
+    return q;
+}
 
 __device__ __forceinline__ float tm_luminance(float r, float g, float b) { return (r * 0.2126f + g * 0.7152f) + b * 0.0722f; }
 
@@ -73,7 +86,7 @@ __device__ __forceinline__ void tm_bin_pixel(uint32_t* __restrict__ s_hist, cons
     const float hb = t * (float)(VR_TONEMAP_BINS - 1);
     const float lf = floorf(hb);
     const int left = (int)lf;
-    const uint32_t rw = (uint32_t)((hb - lf) * 64.0f), lw = 64u - rw;
+    const uint32_t rw = (uint32_t)((hb - lf) * (float)a.q), lw = a.q - rw;     // a power of two: the product is exact
     if (lw != 0u && left < VR_TONEMAP_BINS) atomicAdd(&s_hist[left], lw);
     if (rw != 0u && left + 1 < VR_TONEMAP_BINS) atomicAdd(&s_hist[left + 1], rw);
 }
@@ -231,7 +244,13 @@ __device__ __forceinline__ uint32_t tm_pixel(const TmArgs& a, float inv_adapted,
     const float src = tm_luminance(c[0], c[1], c[2]);
     if (!(src > 0.0f)) return 0u;
     const float scaled = (a.exposure_scale * src) * inv_adapted;
-    const float k = (scaled * (1.0f + scaled * a.wp_inv2)) / ((1.0f + scaled) * src);     // mapped / src as one division
+    const float num = scaled * (1.0f + scaled * a.wp_inv2), den = (1.0f + scaled) * src;
+    float k = num / den;                                            // mapped / src as one division
+    if (!(den <= FLT_MAX) && src <= FLT_MAX) {
+        // the denominator overflowed (k would be inf / inf = NaN, or 0): mapped / src in the written order, +inf where
+        // that overflows; scaled itself is +inf only above fp32's range, where the exact mapped is too
+        k = (scaled <= FLT_MAX ? num / (1.0f + scaled) : INFINITY) / src;
+    }
     return vr_srgb_encode_fast(c[0] * k, thr, enc) | (vr_srgb_encode_fast(c[1] * k, thr, enc) << 8) | (vr_srgb_encode_fast(c[2] * k, thr, enc) << 16);
 }
 
@@ -379,6 +398,7 @@ static TmArgs make_args(const vr_tonemap_params* p, int w, int h)
     a.exposure_scale = exp2f(p->exposure_bias);
     a.wp_inv2 = 1.0f / (p->white_point * p->white_point);
     a.min_adapted = p->min_adapted_luminance;
+    a.q = tm_bin_quantum(w, h);
     return a;
 }
 
@@ -411,6 +431,7 @@ extern "C" VR_API int vr_tonemap_add_frame_to_histogram(vr_tonemap* tm, const vr
     const PartTables* pt = nullptr;
     if ((rc = source_blocks(ctx, hdr, w, h, part, &blocks, &pt))) return rc;
     const TmArgs a = make_args(p, w, h);
+    VR_REQUIRE(a.q != 0u, "frame has more than 2^32 - 1 pixels: the 32-bit histogram cannot count it");
     VrKernelScope ks(ctx, VR_K_TM_HISTOGRAM);
     if (part) {
         if (blocks > 0)
