@@ -182,8 +182,9 @@ VR_API uint32_t vr_build_experiments(void);
  * Renderer.cpp:326-437).  Kernel ids: */
 enum { VR_K_SELECT = 0, VR_K_VERTEX, VR_K_SETUP, VR_K_CLIP, VR_K_SCAN, VR_K_FILL, VR_K_RASTER,
        VR_K_DEFERRED, VR_K_DETILE, VR_K_CLEAR, VR_K_DEFERRED_TILED, VR_K_NODE_HEIGHTS,
-       VR_K_TM_HISTOGRAM, VR_K_TM_EXPOSURE, VR_K_TONEMAP, VR_K_DETILE_LDR, VR_K_RASTER_DEPTH, VR_K_LIGHT_CULL, VR_K_RASTER_LIT, VR_K_COUNT };
-/* (VR_K_COUNT grows when kernels are added - 16 in round 2, 18 in round 3, 19 now: size vr_timing_collect's arrays with the
+       VR_K_TM_HISTOGRAM, VR_K_TM_EXPOSURE, VR_K_TONEMAP, VR_K_DETILE_LDR, VR_K_RASTER_DEPTH, VR_K_LIGHT_CULL, VR_K_RASTER_LIT,
+       VR_K_QUERY_HEIGHTS, VR_K_QUERY_RAYS, VR_K_QUERY_PYRAMID, VR_K_COUNT };
+/* (VR_K_COUNT grows when kernels are added - 16 in round 2, 18 in round 3, 19 in round 4, 22 with the terrain queries: size vr_timing_collect's arrays with the
  * constant of the header the host is compiled against AND check vr_timing_kernel_count() at run time) */
 VR_API int  vr_timing_kernel_count(void);
 VR_API int  vr_timing_enable(vr_context* ctx, int enable);     /* also resets the samples; 1 = every kernel (two event records per
@@ -276,6 +277,47 @@ VR_API int  vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_gbuffer* g
                                const vr_partition* part);
 /* EditorParams::m_NumChunks of the last render/select (syncs the stream). */
 VR_API int  vr_terrain_num_chunks(vr_terrain* t, uint32_t* count);
+
+/* ---- terrain queries ------------------------------------------------------------- */
+/* The reference declares the seed of this and never grew it: QuadTree::GetHeightValue (QuadTree.h:84, QuadTree.cpp:153-162) is
+ * one nearest-texel lookup on the CPU.  Here the surface that is queried is the one the drawn vertices carry (terrain_vs.hlsl:27-33):
+ *   H(x, z) = SampleLevel(heightmap, linear-clamp, uv, 0.1).r * max_height,  uv = ((x, z) + world_size / 2) / world_size
+ * = 0.9 * bilinear(level 0) + 0.1 * bilinear(level 1), continuous and piecewise bilinear; like the vertex stage it does not
+ * depend on vr_terrain_params::location.  Outside uv in [0,1]^2 the clamp addressing holds for height queries; rays are clipped
+ * to the box x, z in [-world_size/2, world_size/2], y in [min(0, max_height), max(0, max_height)].
+ * Normal: normalize(-dH/dx, 1, -dH/dz) from the analytic partial derivatives of the two bilinear interpolants at the point
+ * (on a cell boundary: of the cell with the larger coordinate) - not main_ps's central difference, which depends on a
+ * screen-space LOD a query does not have.
+ * Arrays: device_pointers = 0 - the caller's host memory; the call copies in, runs, copies out and returns when the results are
+ * there (staging memory is kept with the terrain and grows by doubling).  device_pointers = 1 - device memory; the call is
+ * stream-ordered on the context's stream and synchronises nothing; xz must then be 8-byte aligned and rays / hits 16-byte aligned
+ * (the kernels move them as float2 / float4; anything else is VR_ERR_INVALID_ARGUMENT).  n = 0 is VR_OK and launches nothing; NULL arrays with n > 0
+ * and a max_height that is NaN or infinite are VR_ERR_INVALID_ARGUMENT.  A negative max_height is valid (the vertex stage
+ * multiplies by it as it is; the surface is then below y = 0). */
+typedef struct vr_ray     { float origin[3]; float t_max; float dir[3]; uint32_t reserved; } vr_ray;      /* 32 B; dir need not be unit length; t in units of |dir| */
+typedef struct vr_ray_hit { float t; float position[3]; float normal[3]; uint32_t status; } vr_ray_hit;   /* 32 B */
+enum { VR_RAY_MISS = 0, VR_RAY_HIT = 1, VR_RAY_INVALID = 2 /* NaN/Inf/zero dir, NaN/Inf origin (an infinite origin has no point on it to clip), t_max < 0 or NaN */, VR_RAY_STEP_LIMIT = 3 };
+
+/* QuadTree::GetHeightValue (QuadTree.h:84) for n points (x, z) -> H and, when out_normal != NULL, the normal (3 floats per
+ * point).  The heights are bit for bit what the vertex stage gives a vertex at (x, z). */
+VR_API int vr_terrain_query_heights(vr_terrain* t, const float* xz, uint32_t n, float max_height,
+                                    float* out_height, float* out_normal, int device_pointers);
+/* Ray casts against the same surface (grown from QuadTree.h:84): the first t in [max(0, t_enter), min(t_max, t_exit)] with
+ * origin.y + t dir.y <= H(origin.xz + t dir.xz); a ray that starts at or below the surface hits at its first t inside the box.
+ * hits[i] is written for every i: a hit has position.xz = origin.xz + t dir.xz, position.y = H there and the normal there;
+ * anything else has t = t_max, zero position and normal, and its status.  The first cast of a terrain builds a min / max
+ * pyramid over the surface on the context's stream (vr_terrain_memory_bytes counts it under textures); every loop of the walk
+ * has a hard iteration cap, and a ray that reaches it returns VR_RAY_STEP_LIMIT. */
+VR_API int vr_terrain_cast_rays(vr_terrain* t, const vr_ray* rays, uint32_t n, float max_height,
+                                vr_ray_hit* hits, int device_pointers);
+/* Host only (picking; QuadTree.h:84 is what the reference would have called with it): the ray through the centre of pixel
+ * (px, py) of view's viewport - screen point (px + 0.5, py + 0.5); fractional px, py are allowed.  The two ends are the
+ * points world_to_clip sends to (x, y, 0) and (x, y, 1), solved in double (the inverse of the matrix a renderer projects with;
+ * the fp32 clip_to_world is ill-conditioned at the far plane), so origin + t_max * dir lies on the far plane.  The origin is an
+ * fp32 point, and next to the eye one ulp of a coordinate is a visible angle (1e-3 NDC at coordinates near 1000, z_near 0.1): it
+ * is the fp32 point within 64 ulp of its largest coordinate behind the near plane, on the ray, that projects closest to the
+ * pixel's centre (within 5e-5 NDC where one exists).  Its clip z / w is therefore 0 only to that distance over z_near. */
+VR_API int vr_view_pixel_ray(const vr_view* view, float px, float py, vr_ray* out);
 
 /* ---- render targets ---------------------------------------------------------- */
 /* RenderTargets::Init / Clear (Renderer.h:60-101, Renderer.cpp:382).
@@ -534,9 +576,9 @@ VR_API int vr_debug_render_stats(vr_terrain* t, uint32_t out[8]);
  * longest bins first in eight classes (k_scan) - and each of those tiles' bin lengths, in that order.  `capacity` entries per
  * array; *out_count = number of tiles (0 if nothing was rendered).  Synchronises. */
 VR_API int vr_debug_tile_order(vr_terrain* t, int32_t* out_tiles, uint32_t* out_bin_lengths, int32_t capacity, int32_t* out_count);
-/* Device memory a terrain holds, in bytes: out[0] textures (chains + decoded tables), out[1] per-frame geometry scratch
- * (three rotating sets: instances, vertices, triangle records, bins - sized for params->max_instances), out[2] node
- * heights (after vr_terrain_update_heights), out[3] the sum. */
+/* Device memory a terrain holds, in bytes: out[0] textures (chains + decoded tables, and the query pyramid once a ray was cast), out[1] per-frame geometry scratch
+ * (three rotating sets: instances, vertices, triangle records, bins - sized for params->max_instances) plus the staging
+ * memory of host-pointer queries, out[2] node heights (after vr_terrain_update_heights), out[3] the sum. */
 VR_API int vr_terrain_memory_bytes(const vr_terrain* t, uint64_t out[4]);
 /* Test helper: the vertex stage's output (main_vs, terrain_vs.hlsl:35-62) of the last vr_terrain_render for `count`
  * vertices starting at vertex `first` of the instanced draw (vertex = instance * 1089 + row * 33 + column, rows = z):

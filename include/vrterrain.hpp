@@ -189,9 +189,27 @@ namespace vRenderer
             editorParams.m_NumChunks = n;
             return ok;
         }
+        // Terrain queries (grown from QuadTree::GetHeightValue, QuadTree.h:84) against the surface the last Render's max height
+        // draws; host arrays, synchronous.  xz: n pairs; heights: n floats; normals: optional, 3 n floats.
+        bool SampleHeights(const float* xz, uint32_t n, float* heights, float* normals = nullptr)
+        {
+            return Check(vr_terrain_query_heights(m_Terrain, xz, n, m_MaxHeight, heights, normals, 0), "vr_terrain_query_heights");
+        }
+        // first hit of each ray with the terrain (vr_ray_hit::status: VR_RAY_HIT / VR_RAY_MISS / VR_RAY_INVALID / VR_RAY_STEP_LIMIT)
+        bool CastRays(const vr_ray* rays, uint32_t n, vr_ray_hit* hits)
+        {
+            return Check(vr_terrain_cast_rays(m_Terrain, rays, n, m_MaxHeight, hits, 0), "vr_terrain_cast_rays");
+        }
+        void SetMaxHeight(float maxHeight) { m_MaxHeight = maxHeight; }      // for queries before the first Render
         const std::vector<std::shared_ptr<QuadTree>>& GetQuadTrees() const { return m_QuadTrees; }
         vr_terrain* Get() const { return m_Terrain; }
     };
+
+    // the ray through the centre of pixel (px, py) of the view's viewport, near plane to far plane (picking)
+    inline bool PixelRay(const vr_view& view, float px, float py, vr_ray& out)
+    {
+        return Check(vr_view_pixel_ray(&view, px, py, &out), "vr_view_pixel_ray");
+    }
 
     // donut::render::CascadedShadowMap with the one cascade the reference creates (Renderer.cpp:83-87)
     class CascadedShadowMap

@@ -1,0 +1,140 @@
+"""CPU tests of the terrain queries (include/vrterrain.h, "terrain queries"): struct layouts, argument checks that need no
+device, the host-only pixel ray, and self-checks of the float64 model the GPU tests measure against."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import vrenderer_amd as vr
+from vrenderer_amd import capi
+from tests.common import CAMERAS, params, scaled_camera
+from tests import queries_common as qc
+from tests.f64_queries import HIT, MISS, Surface64
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_ray_structs_are_32_bytes_like_the_header(tmp_path):
+    assert C.sizeof(capi.Ray) == 32 and C.sizeof(capi.RayHit) == 32
+    assert vr.RAY_DTYPE.itemsize == 32 and vr.RAY_HIT_DTYPE.itemsize == 32
+    assert [vr.RAY_DTYPE.fields[n][1] for n in ("origin", "t_max", "dir", "reserved")] == [0, 12, 16, 28]
+    assert [vr.RAY_HIT_DTYPE.fields[n][1] for n in ("t", "position", "normal", "status")] == [0, 4, 16, 28]
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include <vrterrain.h>\nint main(void) { printf("%zu %zu %zu %zu %d %d\\n", sizeof(vr_ray), '
+                   'sizeof(vr_ray_hit), offsetof(vr_ray, dir), offsetof(vr_ray_hit, status), VR_RAY_STEP_LIMIT, VR_K_COUNT); return 0; }\n')
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "sizes")],
+                   check=True, capture_output=True, text=True)
+    out = subprocess.run([str(tmp_path / "sizes")], capture_output=True, text=True, check=True).stdout.split()
+    assert out == ["32", "32", "16", "28", "3", "22"]
+    assert capi.VR_K_COUNT == 22 and (capi.VR_RAY_MISS, capi.VR_RAY_HIT, capi.VR_RAY_INVALID, capi.VR_RAY_STEP_LIMIT) == (0, 1, 2, 3)
+
+
+def test_kernel_table_names_the_query_kernels(product_lib):
+    assert product_lib.vr_timing_kernel_count() == 22
+    names = [product_lib.vr_kernel_name(i).decode() for i in range(22)]
+    assert names[19:] == ["k_query_heights", "k_query_rays", "k_query_pyramid (all levels)"] and "?" not in names
+    assert product_lib.vr_kernel_name(22) == b"?"
+
+
+def test_query_argument_checks_need_no_device(product_lib):
+    """The checks come before any use of the device or of the terrain: a block of zeros stands in for the handle."""
+    lib = product_lib
+    fake = C.create_string_buffer(8192)
+    buf = (C.c_float * 64)()
+    inv, ok = capi.VR_ERR_INVALID_ARGUMENT, capi.VR_OK
+    assert lib.vr_terrain_query_heights(None, buf, 4, 400.0, buf, None, 0) == inv
+    assert lib.vr_terrain_cast_rays(None, buf, 1, 400.0, buf, 0) == inv
+    for dev in (0, 1):
+        assert lib.vr_terrain_query_heights(fake, None, 0, 400.0, None, None, dev) == ok          # n = 0 launches nothing
+        assert lib.vr_terrain_cast_rays(fake, None, 0, -3.0, None, dev) == ok
+        assert lib.vr_terrain_query_heights(fake, None, 4, 400.0, buf, None, dev) == inv
+        assert lib.vr_terrain_query_heights(fake, buf, 4, 400.0, None, buf, dev) == inv
+        assert b"NULL" in lib.vr_last_error()
+        assert lib.vr_terrain_cast_rays(fake, None, 2, 400.0, buf, dev) == inv
+        assert lib.vr_terrain_cast_rays(fake, buf, 2, 400.0, None, dev) == inv
+        for bad in (float("nan"), float("inf"), float("-inf")):
+            assert lib.vr_terrain_query_heights(fake, buf, 4, bad, buf, None, dev) == inv
+            assert lib.vr_terrain_cast_rays(fake, buf, 2, bad, buf, dev) == inv
+            assert b"max_height" in lib.vr_last_error()
+    # device-pointer mode moves points as float2 and rays / hits as float4: under-aligned pointers are refused, host arrays are not
+    al = C.addressof(fake) + (-C.addressof(fake)) % 16
+    assert lib.vr_terrain_query_heights(fake, C.c_void_p(al + 4), 4, 400.0, C.c_void_p(al), None, 1) == inv
+    assert lib.vr_terrain_cast_rays(fake, C.c_void_p(al + 8), 2, 400.0, C.c_void_p(al), 1) == inv
+    assert lib.vr_terrain_cast_rays(fake, C.c_void_p(al), 2, 400.0, C.c_void_p(al + 4), 1) == inv and b"aligned" in lib.vr_last_error()
+    r = capi.Ray()
+    v = vr.make_view((0, 10, 0), (5, 0, 5), 64, 64)
+    assert lib.vr_view_pixel_ray(None, 0.0, 0.0, C.byref(r)) == inv and lib.vr_view_pixel_ray(C.byref(v), 0.0, 0.0, None) == inv
+    assert lib.vr_view_pixel_ray(C.byref(v), float("nan"), 0.0, C.byref(r)) == inv
+    assert lib.vr_view_pixel_ray(C.byref(vr.View()), 0.0, 0.0, C.byref(r)) == inv               # an empty viewport
+
+
+def test_pixel_ray_lands_on_the_pixel(product_lib):
+    """The ray through the centre of a pixel, taken through world_to_clip again, lands on that pixel's NDC within 1e-4 at
+    both ends; its origin lies on the near plane (clip z / w = 0), its end on the far plane."""
+    w, h = 640, 360
+    for cam in CAMERAS:
+        view = vr.make_view(cam[0], cam[1], w, h)
+        M = np.array(view.world_to_clip[:], np.float64).reshape(4, 4)
+        for px, py in ((0.0, 0.0), (319.5, 179.5), (639.0, 359.0)):
+            r = vr.pixel_ray(view, px, py)
+            assert r.t_max == 1.0 and r.reserved == 0
+            ndc = np.array([(px + 0.5) / w * 2.0 - 1.0, 1.0 - (py + 0.5) / h * 2.0])
+            o, d = np.array(r.origin[:], np.float64), np.array(r.dir[:], np.float64)
+            for t in (0.0, 1.0):
+                c = np.append(o + t * d, 1.0) @ M
+                assert np.abs(c[:2] / c[3] - ndc).max() <= 1e-4, (cam, px, py, t)
+                if t == 0.0:
+                    assert abs(c[2] / c[3]) <= 0.05, (cam, px, py, c[2] / c[3])       # the near plane, to the fp32 lattice the origin lives on (vr_view_pixel_ray)
+                else:
+                    assert abs(c[2] / c[3] - 1.0) <= 1e-2, (cam, px, py, c[2] / c[3])       # the far plane, to clip_to_world's fp32
+
+
+def test_model_heights_are_the_oracle_s_vertices(oracle):
+    """H64 at the oracle's vertex positions is within max_height 2^-18 of the fp32 height the oracle's vertex stage gives."""
+    size, mh = 256, 400.0
+    hm = oracle.synth_heightmap(size)
+    ot = oracle.OracleTerrain(params(size), hm, oracle.synth_albedo(size, hm))
+    surf = Surface64(ot.height_mip(0), ot.height_mip(1), size, mh)
+    eye, tgt = scaled_camera(CAMERAS[0], size)
+    view = vr.make_view(eye, tgt, 640, 360)
+    n, _, inst = ot.select(view, mh)
+    assert n >= 4
+    worst = 0.0
+    for i in range(min(n, 4)):
+        world = np.array([ot.vertex(view, mh, inst[i], vx, vz)[1] for vz in range(0, 33, 2) for vx in range(33)], np.float64)
+        worst = max(worst, float(np.abs(surf.H(world[:, 0], world[:, 2]) - world[:, 1]).max()))
+    assert worst <= mh * 2.0 ** -18, worst
+    ot.close()
+
+
+def test_model_first_hit_on_a_flat_map_is_the_plane_intersection():
+    flat = np.full((16, 16), 102, np.uint8)                                 # H = 0.4 max_height everywhere
+    surf = Surface64(flat, flat[::2, ::2], 64.0, 50.0)
+    o = np.array([[0.0, 60.0, 0.0], [-10.0, 45.0, 3.0], [0.0, 10.0, 0.0], [0.0, 60.0, 0.0], [100.0, 30.0, 0.0]])
+    d = np.array([[0.25, -1.0, 0.5], [0.5, -0.5, 0.0], [1.0, 0.0, 0.0], [0.0, 2.0, 0.0], [-1.0, 0.0, 0.0]])
+    m = surf.first_hit64(o, d)
+    assert m["status"].tolist() == [HIT, HIT, HIT, MISS, MISS]              # the third starts under the plane, the fifth flies over it
+    assert abs(m["t"][0] - 40.0) < 1e-6 and abs(m["t"][1] - 50.0) < 1e-6 and m["t"][2] == 0.0      # (the model calls g <= 1e-9 max_height a hit)
+    assert abs(m["gall"][4] - 10.0) < 1e-12 and m["gmin"][0] > 0.0
+    n = surf.normal(np.array([1.0]), np.array([2.0]))
+    assert np.allclose(n, [[0.0, 1.0, 0.0]])
+
+
+def test_seeds_keep_the_shares_the_gpu_tests_rely_on(oracle, product_lib):
+    """Fewer than 2 % of the height test's points lie within 2^-10 texel of a cell boundary, and fewer than 3 % of the ray
+    test's rays are grazing by the model's own measure (64^2 map; the 256^2 map is checked where the GPU test builds it)."""
+    size = 64
+    hm = oracle.synth_heightmap(size)
+    ot = oracle.OracleTerrain(params(size), hm, oracle.synth_albedo(size, hm))
+    surf = Surface64(ot.height_mip(0), ot.height_mip(1), size, qc.scaled_max_height(size))
+    for s in (64, 256):
+        grid = Surface64(np.zeros((s, s), np.uint8), np.zeros((s // 2, s // 2), np.uint8), s, 1.0)
+        pts = qc.uniform_points(s).astype(np.float64)
+        assert 1.0 - qc.away_from_cell_boundaries(grid, pts[:, 0], pts[:, 1]).mean() <= 0.02
+    o, d, tm = qc.make_rays(surf, size)
+    assert o.shape == (qc.N_RAYS, 3) and ((d == 0).sum(1) >= 1).sum() >= qc.N_RAYS // 5      # vertical and axis-parallel rays are exact
+    m = qc.model_of_rays(surf, o, d, tm)
+    assert m["grazing"].mean() <= 0.03, m["grazing"].mean()
+    assert 0.3 < (m["status"] == HIT).mean() < 0.9
+    ot.close()

@@ -20,13 +20,17 @@ VR_ERR_HIP = 6
 VR_LIGHT_DIRECTIONAL = 1
 VR_LIGHT_SPOT = 2
 VR_LIGHT_POINT = 3
-VR_K_COUNT = 19
+VR_K_COUNT = 22
 VR_TONEMAP_BINS = 256
 VR_OPT_ASYNC_GEOMETRY = 1
 VR_OPT_DISPATCH_EVENTS = 2
 VR_OPT_RASTER_TILE = 3
 VR_OPT_PLANE_TRACKING = 4
 VR_OPT_SCRATCH_WORST_CASE = 5
+VR_RAY_MISS = 0
+VR_RAY_HIT = 1
+VR_RAY_INVALID = 2
+VR_RAY_STEP_LIMIT = 3
 
 
 class TerrainParams(C.Structure):
@@ -132,6 +136,16 @@ class FrameDesc(C.Structure):
                 ("ldr_frame", C.c_void_p)]
 
 
+class Ray(C.Structure):
+    """vr_ray: dir need not be unit length; t is in units of |dir|."""
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("dir", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("position", C.c_float * 3), ("normal", C.c_float * 3), ("status", C.c_uint32)]
+
+
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -155,6 +169,7 @@ EXPORTS = [
     "vr_tonemap_default_params", "vr_tonemap_create", "vr_tonemap_destroy", "vr_tonemap_reset_exposure", "vr_tonemap_reset_histogram",
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
+    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray",
 ]
 
 _lib = None
@@ -270,6 +285,9 @@ def load_library():
         "vr_debug_tile_order": (C.c_int, [vp, vp, vp, C.c_int32, P(C.c_int32)]),
         "vr_debug_download_vertices": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
         "vr_terrain_memory_bytes": (C.c_int, [vp, P(C.c_uint64)]),
+        "vr_terrain_query_heights": (C.c_int, [vp, vp, C.c_uint32, C.c_float, vp, vp, C.c_int]),
+        "vr_terrain_cast_rays": (C.c_int, [vp, vp, C.c_uint32, C.c_float, vp, C.c_int]),
+        "vr_view_pixel_ray": (C.c_int, [P(View), C.c_float, C.c_float, P(Ray)]),
     }
     for name in EXPORTS:
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

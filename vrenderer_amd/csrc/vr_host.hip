@@ -239,7 +239,7 @@ extern "C" VR_API const char* vr_kernel_name(int id)
     static const char* names[VR_K_COUNT] = { "k_select", "k_vertex", "k_setup", "k_clip", "k_scan", "k_fill", "k_raster",
                                               "k_deferred", "k_detile", "k_fill_u32 (clear)", "k_deferred_tiled", "k_node_heights (all levels)",
                                               "k_tm_histogram", "k_tm_exposure", "k_tonemap", "k_detile_ldr", "k_raster (depth only)", "k_light_cull",
-                                              "k_raster (fused with lighting)" };
+                                              "k_raster (fused with lighting)", "k_query_heights", "k_query_rays", "k_query_pyramid (all levels)" };
     return (id >= 0 && id < VR_K_COUNT) ? names[id] : "?";
 }
 

@@ -372,7 +372,13 @@ struct vr_terrain {
     bool raster_begin_recorded = false;
     hipEvent_t start_hint = nullptr;        // vr_terrain_prepare starts its geometry behind this: ev_raster_begin, or the previous lighting pass's stop event
     uint64_t start_hint_epoch = 0;          // as GeoSet::raster_done_epoch
+    // Terrain queries (vr_query.hip): the min / max pyramid over the surface, built by the first ray cast on the context's stream and
+    // kept until vr_terrain_destroy, and the staging memory of the host-pointer mode (grown by doubling).
+    uchar2* d_pyramid = nullptr; uint64_t pyramid_bytes = 0;
+    hipEvent_t ev_pyramid = nullptr; hipStream_t pyramid_stream = nullptr;     // the build; a cast on another stream waits for it
+    void* d_query_stage = nullptr; size_t query_stage_bytes = 0;
 };
+void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
 
 struct vr_tonemap;
 vr_context* vr_tonemap_context(vr_tonemap* tm);

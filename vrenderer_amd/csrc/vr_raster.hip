@@ -69,24 +69,6 @@ struct RasterArgs {
 enum { C_COUNT = 0, C_FLAGS = 1, C_HARDTRIS = 2, C_XVERTS = 3, C_HARDLIST = 4, C_BINTOTAL = 5, C_CLASS0 = 8 };
 
 
-// One bilinear tap through the quad (footprint) table, split into address and filter so that the
-// loads of all taps of a pixel can be issued back to back before the first one is consumed.
-struct QuadTap { uint32_t idx; float fx, fy; };
-__device__ __forceinline__ QuadTap quad_tap(int w, int h, float u, float v)
-{
-    const float x = __builtin_fmaf(u, (float)w, -0.5f), y = __builtin_fmaf(v, (float)h, -0.5f);
-    float xf = floorf(x), yf = floorf(y);
-    QuadTap q; q.fx = x - xf; q.fy = y - yf;
-    xf = vr_min(vr_max(xf, -1.0f), (float)w); yf = vr_min(vr_max(yf, -1.0f), (float)h);
-    q.idx = (uint32_t)(__mul24((int)yf + 1, w + 2) + ((int)xf + 1));
-    return q;
-}
-__device__ __forceinline__ float quad_filter(uint32_t e, const QuadTap& q, const float* __restrict__ r8)
-{
-    const float t00 = r8[e & 255u], t10 = r8[(e >> 8) & 255u], t01 = r8[(e >> 16) & 255u], t11 = r8[e >> 24];
-    const float top = __builtin_fmaf(t10 - t00, q.fx, t00), bot = __builtin_fmaf(t11 - t01, q.fx, t01);   // the sampler's lerps are fused (oracle: tex_bilinear)
-    return __builtin_fmaf(bot - top, q.fy, top);
-}
 // ---------------------------------------------------------------------------------------
 // vertex stage (terrain_vs.hlsl:35-62)
 // ---------------------------------------------------------------------------------------

@@ -663,6 +663,7 @@ extern "C" VR_API void vr_terrain_destroy(vr_terrain* t)
         (void)hipFree(g.d_tile_count); (void)hipFree(g.d_tile_offset); (void)hipFree(g.d_tile_cursor); (void)hipFree(g.d_tile_order);
     }
     free_scratch(t);
+    vr_query_release(t);
     if (t->h_status) (void)hipHostFree(t->h_status);
     (void)hipFree(t->d_height); (void)hipFree(t->d_albedo); (void)hipFree(t->d_node_heights); (void)hipFree(t->d_minmax);
     delete t;
@@ -829,6 +830,6 @@ extern "C" VR_API int vr_terrain_memory_bytes(const vr_terrain* t, uint64_t out[
         const uint64_t nodes = ((((uint64_t)1 << (2 * (t->num_lods + 1))) - 1) / 3);
         heights = nodes * (uint64_t)(t->surfaces_per_side * t->surfaces_per_side) * sizeof(float2) + (t->d_minmax ? nodes * sizeof(uchar2) : 0);
     }
-    out[0] = t->bytes_textures; out[1] = t->bytes_scratch + tiles; out[2] = heights; out[3] = out[0] + out[1] + out[2];
+    out[0] = t->bytes_textures + t->pyramid_bytes; out[1] = t->bytes_scratch + tiles + t->query_stage_bytes; out[2] = heights; out[3] = out[0] + out[1] + out[2];
     return VR_OK;
 }

@@ -20,6 +20,20 @@ def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
 
+# numpy views of vr_ray / vr_ray_hit (32 bytes each)
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("dir", np.float32, 3), ("reserved", np.uint32)])
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("position", np.float32, 3), ("normal", np.float32, 3), ("status", np.uint32)])
+assert RAY_DTYPE.itemsize == C.sizeof(capi.Ray) == 32 and RAY_HIT_DTYPE.itemsize == C.sizeof(capi.RayHit) == 32
+
+
+def pixel_ray(view, px, py):
+    """vr_view_pixel_ray: the ray through the centre of pixel (px, py) of the view's viewport, near plane to far plane
+    (t in [0, 1]); returns a capi.Ray."""
+    r = capi.Ray()
+    check(capi.load_library().vr_view_pixel_ray(C.byref(view), px, py, C.byref(r)), "vr_view_pixel_ray")
+    return r
+
+
 class Context:
     """nvrhi device + the frame's single command list (main.cpp:57-61, Renderer.cpp:48)."""
 
@@ -439,6 +453,35 @@ class TerrainPass:
         check(self.ctx.lib.vr_debug_download_vertices(self.handle, int(first_instance) * 1089, n, out.ctypes.data_as(C.c_void_p)),
               "vr_debug_download_vertices")
         return out.reshape(int(num_instances), 1089, 6)
+
+    def SampleHeights(self, xz, max_height=400.0, normals=False):
+        """vr_terrain_query_heights (grown from QuadTree::GetHeightValue, QuadTree.h:84): (n, 2) float32 world (x, z) ->
+        (n,) float32 heights of the drawn surface, plus (n, 3) float32 normals with normals=True."""
+        p = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+        n = p.shape[0]
+        h = np.empty(n, np.float32)
+        nrm = np.empty((n, 3), np.float32) if normals else None
+        check(self.ctx.lib.vr_terrain_query_heights(self.handle, _vp(p), n, max_height, _vp(h), _vp(nrm) if normals else None, 0),
+              "vr_terrain_query_heights")
+        return (h, nrm) if normals else h
+
+    def CastRays(self, origins, dirs, t_max=np.inf, max_height=400.0):
+        """vr_terrain_cast_rays: (n, 3) origins and directions (any length; t is in units of |dir|), t_max a scalar or (n,) ->
+        structured array (RAY_HIT_DTYPE) with t, position, normal, status (capi.VR_RAY_*)."""
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        rays = np.zeros(n, RAY_DTYPE)
+        rays["origin"] = o
+        rays["dir"] = np.asarray(dirs, np.float32).reshape(-1, 3)
+        rays["t_max"] = t_max
+        return self.cast_ray_array(rays, max_height)
+
+    def cast_ray_array(self, rays, max_height=400.0):
+        """CastRays for rays already laid out as RAY_DTYPE (the C struct vr_ray)."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.zeros(rays.shape[0], RAY_HIT_DTYPE)
+        check(self.ctx.lib.vr_terrain_cast_rays(self.handle, _vp(rays), rays.shape[0], max_height, _vp(hits), 0), "vr_terrain_cast_rays")
+        return hits
 
     def Prepare(self, view, render_targets, render_params, partition=None):
         """Build the next frame's geometry ahead of time (overlaps the current frame's tile pass)."""
