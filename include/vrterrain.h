@@ -169,7 +169,15 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * by the high-water mark of the node counts its frames select - 1024 nodes to begin with (1.3 GB for the three sets), doubled before a
  * frame can exceed it - instead of for max_instances (4096: 5 GB).  1 (set BEFORE vr_terrain_create): worst case up front, no growth,
  * no frame can ever be truncated by the scratch. */
-enum { VR_OPT_ASYNC_GEOMETRY = 1, VR_OPT_DISPATCH_EVENTS = 2, VR_OPT_RASTER_TILE = 3, VR_OPT_PLANE_TRACKING = 4, VR_OPT_SCRATCH_WORST_CASE = 5 };
+/* VR_OPT_FRAME_FUSION (default 1; a context starts with 0 where the environment holds VR_FRAME_FUSION=0): vr_frame_submit shades
+ * the pixels in the tile pass itself and STILL writes the whole G-buffer - one kernel (timed as VR_K_RASTER_LIT) instead of tile pass +
+ * lighting pass, the same bits in all five planes, HdrColor, the region states and the plane knowledge.  Taken for: the whole frame
+ * (part == NULL), not tiled, no shadow, at most 16 directional / punctual point lights, the tile pass's fast variant on 32-pixel
+ * tiles, a target known cleared (assume_cleared = 1 or a pending vr_gbuffer_clear), shaded fill mode without depth ranges, a
+ * viewport that covers the target, a width that is a multiple of 4, and VR_OPT_PLANE_TRACKING with the emissive plane known zero.
+ * Any other frame - and every frame with 0 - queues the two passes as before. */
+enum { VR_OPT_ASYNC_GEOMETRY = 1, VR_OPT_DISPATCH_EVENTS = 2, VR_OPT_RASTER_TILE = 3, VR_OPT_PLANE_TRACKING = 4, VR_OPT_SCRATCH_WORST_CASE = 5,
+       VR_OPT_FRAME_FUSION = 6 };
 VR_API int  vr_context_set_option(vr_context* ctx, int option, int value);
 VR_API const char* vr_last_error(void);
 VR_API const char* vr_version(void);

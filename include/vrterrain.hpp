@@ -48,6 +48,8 @@ namespace vRenderer
         explicit operator bool() const { return m_Ctx != nullptr; }
         vr_context* Get() const { return m_Ctx; }
         void SetStream(void* hipStream) { vr_context_set_stream(m_Ctx, hipStream); }
+        void SetOption(int option, int value) { Check(vr_context_set_option(m_Ctx, option, value), "vr_context_set_option"); }   // VR_OPT_*
+        void SetFrameFusion(bool enable) { SetOption(VR_OPT_FRAME_FUSION, enable ? 1 : 0); }
         void WaitForIdle() { vr_context_synchronize(m_Ctx); }            // nvrhi::IDevice::waitForIdle
     };
 

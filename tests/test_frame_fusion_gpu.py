@@ -1,0 +1,292 @@
+"""VR_OPT_FRAME_FUSION: vr_frame_submit shading inside the tile pass (the KEEP flavour of k_raster) against the same frames
+with the option off - the unfused pair of passes, which is the reference.  Every comparison is exact: the five planes,
+depth, HdrColor, the region census and what the library knows about the emissive plane."""
+import numpy as np
+import pytest
+
+import vrenderer_amd as vr
+from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, flythrough_camera, params, scaled_camera
+
+pytestmark = pytest.mark.gpu
+
+FUSED, LIGHTING = "k_raster (fused with lighting)", "k_deferred"
+PLANES = ("depth", "diffuse", "specular", "normals", "emissive")
+
+
+@pytest.fixture(scope="module")
+def fx(product_lib):
+    """A context of this module's own (the option is per context) with a 256^2 terrain."""
+    ctx = vr.Context(0)
+    size = 256
+    h = vr.synth_heightmap(ctx, size)
+    a = vr.synth_albedo(ctx, size, h)
+    tp = vr.TerrainPass(ctx, params(size)).Init(h, a)
+    yield dict(ctx=ctx, tp=tp, h=h, size=size)
+    tp.close()
+    ctx.close()
+
+
+def _fly(i, w, h, size=256):
+    return vr.make_view(*scaled_camera(flythrough_camera(i), size), w, h)
+
+
+def _frames(fx, fusion, w, h, views, lights=None, clear=False, before=None, ahead=0, part=None, tiled=False, tile=0, **rpkw):
+    """Renders `views` one after the other into fresh targets through vr_frame_submit; per frame: everything the frame left
+    behind and which of the two kernels ran."""
+    ctx, tp = fx["ctx"], fx["tp"]
+    lights = [vr.reference_sun()] if lights is None else lights
+    rpkw.setdefault("assume_cleared", 1)
+    rp = vr.default_render_params(400.0, **rpkw)
+    ctx.set_frame_fusion(fusion)
+    ctx.set_raster_tile(tile)
+    rt = vr.RenderTargets(ctx).Init(w, h)
+    if part is None:
+        hdr, nbytes = vr.HdrImage(ctx, w, h), None
+    else:
+        from vrenderer_amd.passes import partition_info
+        info = partition_info(w, h, part.rank, part.world_size)
+        rows = (info["packed_bytes"] + vr.VR_OWNER_TILE * 8 - 1) // (vr.VR_OWNER_TILE * 8)
+        hdr, nbytes = vr.HdrImage(ctx, vr.VR_OWNER_TILE, rows), info["owned"] * 128 * 128 * 6
+    hdr.upload(np.zeros(hdr.width * hdr.height * 4, np.uint16))
+    fr = vr.Frame(tp, rt, rp, lights, AMBIENT_TOP, AMBIENT_BOTTOM, part, tiled)
+    out = []
+    try:
+        for i, v in enumerate(views):
+            if clear:
+                rt.Clear()
+            if before is not None:
+                before(i, rt)
+            ctx.timing_enable(2)
+            fr.submit(v, hdr, views[i + 1:i + 1 + ahead])
+            ctx.synchronize()
+            ran = ctx.timing_collect()
+            ctx.timing_enable(0)
+            f = {p: rt.download(p).copy() for p in PLANES}
+            f["hdr"] = hdr.download(nbytes).copy()
+            f["census"] = rt.region_census()
+            f["emissive_known_zero"] = rt.plane_known_zero("emissive")
+            f["fused"], f["lighting"] = FUSED in ran, LIGHTING in ran
+            assert not (f["fused"] and f["lighting"]), sorted(ran)
+            out.append(f)
+    finally:
+        ctx.set_frame_fusion(1)
+        ctx.set_raster_tile(0)
+        hdr.close()
+        rt.close()
+    return out
+
+
+def _same(want, got, what):
+    assert len(want) == len(got)
+    for i, (a, b) in enumerate(zip(want, got)):
+        for p in PLANES + ("hdr",):
+            x, y = a[p].view(np.uint32 if a[p].dtype == np.float32 else a[p].dtype), b[p].view(np.uint32 if b[p].dtype == np.float32 else b[p].dtype)
+            assert np.array_equal(x, y), f"{what}: frame {i}, {p} differs in {(x != y).sum()} elements"
+        assert a["census"] == b["census"], f"{what}: frame {i}, region census {a['census']} != {b['census']}"
+        assert a["emissive_known_zero"] == b["emissive_known_zero"], f"{what}: frame {i}, emissive plane knowledge"
+
+
+def _both(fx, what, expect_fused, *args, **kw):
+    """The same frames with the option off (reference) and on; expect_fused: per frame, or one value for all."""
+    off, on = _frames(fx, 0, *args, **kw), _frames(fx, 1, *args, **kw)
+    assert not any(f["fused"] for f in off), what + ": the option is off and a frame was fused"
+    exp = expect_fused if isinstance(expect_fused, (list, tuple)) else [expect_fused] * len(on)
+    assert [f["fused"] for f in on] == list(exp), what + f": fused frames {[f['fused'] for f in on]}"
+    if not kw.get("tiled"):         # a frame that is not fused launches the lighting pass
+        assert all(f["fused"] != f["lighting"] for f in off + on), what
+    _same(off, on, what)
+    return off, on
+
+
+@pytest.mark.parametrize("w,h", [(256, 144), (252, 132)])
+def test_small_frames_three_consecutive_views(fx, w, h):
+    """Three consecutive flythrough views (region states evolve from frame to frame); 252x132 has a partial last tile column
+    and row.  Every frame holds an all-sky tile, all-terrain regions and mixed regions."""
+    views = [_fly(i, w, h) for i in range(3)]
+    off, _ = _both(fx, f"{w}x{h}", True, w, h, views)
+    for i, f in enumerate(off):
+        cov = f["depth"] < 1.0
+        assert any(not cov[y:y + 32, x:x + 32].any() for y in range(0, h, 32) for x in range(0, w, 32)), f"frame {i}: no all-sky tile"
+        c = f["census"]
+        assert c["clear"] > 0 and c["specular_constant"] > 0 and c["unknown"] > 0, f"frame {i}: {c}"
+
+
+def test_clear_handling_and_state_changes_between_frames(fx):
+    w, h = 256, 144
+    views = [_fly(i, w, h) for i in range(3)]
+    # RenderTargets.Clear() before each frame: a lazy clear is pending, consumed by the whole-frame pass
+    _both(fx, "Clear before each frame", True, w, h, views, clear=True, assume_cleared=0)
+    # no clear, the caller's promise instead
+    _both(fx, "assume_cleared", True, w, h, [vr.make_view(*scaled_camera(CAMERAS[k], 256), w, h) for k in (0, 5, 3)])
+    # a foreign write into the specular plane: the region states drop to unknown, the specular plane is written again
+    rng = np.random.default_rng(5)
+    foreign = rng.integers(0, 1 << 32, (h, w), dtype=np.uint64).astype(np.uint32)
+
+    def spec_upload(i, rt):
+        if i == 1:
+            rt.upload("specular", foreign)
+    _both(fx, "specular upload", True, w, h, views, before=spec_upload)
+    # a non-zero emissive plane: nothing is known about it, the frame takes the two passes (and knows the plane again afterwards)
+    emi = rng.integers(1, 1 << 15, (h, w, 4), dtype=np.uint64).astype(np.uint16)
+
+    def emi_upload(i, rt):
+        if i == 1:
+            rt.upload("emissive", emi)
+    _both(fx, "emissive upload", [True, False, True], w, h, views, before=emi_upload)
+
+
+def test_light_lists(fx):
+    w, h = 256, 144
+    views = [_fly(0, w, h), _fly(7, w, h)]
+    sun = vr.reference_sun()
+    pts = vr.synthetic_point_lights(16, 256.0, fx["h"], 400.0, seed=9001)
+    _both(fx, "no light", True, w, h, views, lights=[])
+    _both(fx, "sun", True, w, h, views, lights=[sun])
+    _both(fx, "16 lights", True, w, h, views, lights=[sun] + pts[:15])
+    # more than the streaming pass's 16: only the tiled pass takes them
+    _both(fx, "17 lights (tiled)", False, w, h, views, lights=[sun] + pts, tiled=True)
+    for fusion in (0, 1):
+        with pytest.raises(Exception, match="16 lights"):
+            _frames(fx, fusion, w, h, views[:1], lights=[sun] + pts)
+    spot = vr.spot_light((-2.5, 7.5, 1.25), (0.3, -1.0, -0.2), 6000.0, 25.0, 12.0, 25.0, (0.2, 1.0, 0.4))
+    _both(fx, "spot light", False, w, h, views, lights=[sun, spot])
+
+
+def test_ineligible_render_params_fall_back(fx):
+    w, h = 256, 144
+    views = [_fly(0, w, h), _fly(1, w, h)]
+    _both(fx, "wireframe", False, w, h, views, wireframe=1)
+    _both(fx, "depth only", False, w, h, views, depth_only=1)
+    _both(fx, "depth ranges", False, w, h, views, depth_ranges=1)
+    _both(fx, "64-pixel tiles", False, w, h, views, tile=64)
+    # assume_cleared = 0 over what the first frame left (no clear in between): the second frame keeps what it does not cover
+    # (the frame's render parameters are read at submit time: the second frame changes them in place)
+    ctx, tp = fx["ctx"], fx["tp"]
+    outs = []
+    for fusion in (0, 1):
+        ctx.set_frame_fusion(fusion)
+        rt, hdr = vr.RenderTargets(ctx).Init(w, h), vr.HdrImage(ctx, w, h)
+        rp = vr.default_render_params(400.0, assume_cleared=1)
+        fr = vr.Frame(tp, rt, rp, [vr.reference_sun()], AMBIENT_TOP, AMBIENT_BOTTOM)
+        try:
+            fr.submit(views[0], hdr)
+            rp.assume_cleared = 0
+            ctx.timing_enable(2)
+            fr.submit(vr.make_view(*scaled_camera(CAMERAS[4], 256), w, h), hdr)
+            ctx.synchronize()
+            ran = ctx.timing_collect()
+            ctx.timing_enable(0)
+            assert LIGHTING in ran and FUSED not in ran, sorted(ran)
+            f = {p: rt.download(p).copy() for p in PLANES}
+            f.update(hdr=hdr.download().copy(), census=rt.region_census(), emissive_known_zero=rt.plane_known_zero("emissive"))
+            outs.append([f])
+        finally:
+            ctx.set_frame_fusion(1)
+            hdr.close()
+            rt.close()
+    _same(outs[0], outs[1], "assume_cleared = 0 over a drawn target")
+
+
+@pytest.mark.parametrize("w,h", [(256, 144), (1024, 576)])
+def test_tonemap_stage_on_a_second_stream(fx, w, h):
+    """The tone-map stage on another context's stream, two HdrImages rotating over six frames without a host synchronisation
+    in between: the fused tile pass waits for the reader of the image it overwrites, and the stage waits for the fused
+    launch's own stop event (two frames are prepared ahead after every launch)."""
+    import torch
+    ctx, tp = fx["ctx"], fx["tp"]
+    views = [_fly(3 * i, w, h) for i in range(6)]
+    tmp = vr.default_tonemap_params()
+    side = torch.cuda.Stream()
+    tctx = vr.Context(0)
+    tctx.set_stream(side.cuda_stream)
+
+    def run(fusion):
+        ctx.set_frame_fusion(fusion)
+        rt = vr.RenderTargets(ctx).Init(w, h)
+        hdrs = [vr.HdrImage(ctx, w, h) for _ in range(2)]
+        ldrs = [vr.LdrImage(tctx, w, h) for _ in range(2)]
+        tm = vr.ToneMappingPass(tctx)
+        tm.AdvanceFrame(1.0 / 60.0)
+        fr = vr.Frame(tp, rt, vr.default_render_params(400.0, assume_cleared=1), [vr.reference_sun()], AMBIENT_TOP, AMBIENT_BOTTOM,
+                      tonemap=tm, tonemap_params=tmp, ldr=ldrs[0])
+        outs = []
+        try:
+            for i, v in enumerate(views):
+                b = i % 2
+                if i >= 2:                                   # the host reads a buffer back before its slot is used again
+                    ctx.synchronize(); tctx.synchronize()
+                    outs.append((hdrs[b].download().copy(), ldrs[b].download().copy()))
+                fr.submit(v, hdrs[b], views[i + 1:i + 3], ldr=ldrs[b])
+            ctx.synchronize(); tctx.synchronize()
+            for b in (0, 1):
+                outs.append((hdrs[b].download().copy(), ldrs[b].download().copy()))
+            exposure = tm.download()[1]
+        finally:
+            ctx.synchronize(); tctx.synchronize()
+            ctx.set_frame_fusion(1)
+            tm.close()
+            for o in ldrs + hdrs + [rt]:
+                o.close()
+        return outs, exposure
+    try:
+        (want, e0), (got, e1) = run(0), run(1)
+        assert len(want) == len(got) == 6
+        for k, ((h0, l0), (h1, l1)) in enumerate(zip(want, got)):
+            assert np.array_equal(h0, h1), f"HdrColor of frame slot {k} differs"
+            assert np.array_equal(l0, l1), f"LdrColor of frame slot {k} differs"
+        assert np.float32(e0).view(np.uint32) == np.float32(e1).view(np.uint32), (e0, e1)
+    finally:
+        torch.cuda.synchronize()
+        tctx.close()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_partition_takes_the_two_passes(fx, world):
+    """A rank's share (packed tiles) is not fused: every rank's frame is queued as before, and is the same."""
+    w, h = 384, 256
+    views = [_fly(0, w, h), _fly(1, w, h)]
+    for rank in range(world):
+        _both(fx, f"rank {rank} of {world}", False, w, h, views, part=vr.Partition(rank, world))
+
+
+def test_prepare_two_frames_ahead(fx):
+    w, h = 256, 144
+    views = [_fly(i, w, h) for i in range(4)]
+    off, on = _both(fx, "two frames ahead", True, w, h, views, ahead=2)
+    _same(on, _frames(fx, 1, w, h, views), "prepared ahead vs not prepared")
+    _same(off, _frames(fx, 0, w, h, views), "prepared ahead vs not prepared (option off)")
+
+
+def test_one_8k_frame():
+    """The bench's frame (7680x4320, 2048^2 heightmap, flythrough view 0): HdrColor and depth on a seeded sample of 2^21 pixels."""
+    w, h, size = 7680, 4320, 2048
+    ctx = vr.Context(0)
+    hm = vr.synth_heightmap(ctx, size)
+    tp = vr.TerrainPass(ctx, params(size)).Init(hm, vr.synth_albedo(ctx, size, hm))
+    pick = np.sort(np.random.default_rng(20261016).choice(w * h, size=1 << 21, replace=False))
+    v = vr.make_view(*flythrough_camera(0), w, h)
+    res = []
+    try:
+        for fusion in (0, 1):
+            ctx.set_frame_fusion(fusion)
+            rt, hdr = vr.RenderTargets(ctx).Init(w, h), vr.HdrImage(ctx, w, h)
+            try:
+                fr = vr.Frame(tp, rt, vr.default_render_params(400.0, assume_cleared=1), [vr.reference_sun()], AMBIENT_TOP, AMBIENT_BOTTOM)
+                ctx.timing_enable(2)
+                fr.submit(v, hdr)
+                ctx.synchronize()
+                ran = ctx.timing_collect()
+                ctx.timing_enable(0)
+                assert (FUSED in ran) == bool(fusion) and (LIGHTING in ran) != bool(fusion), sorted(ran)
+                res.append((hdr.download().reshape(-1, 4)[pick].copy(), rt.download("depth").reshape(-1)[pick].view(np.uint32).copy(),
+                            rt.region_census()))
+            finally:
+                hdr.close()
+                rt.close()
+    finally:
+        tp.close()
+        ctx.close()
+    assert (res[0][1] != 0x3f800000).mean() > 0.3, "the frame shows little terrain"
+    assert np.array_equal(res[0][0], res[1][0]), "HdrColor"
+    assert np.array_equal(res[0][1], res[1][1]), "depth"
+    assert res[0][2] == res[1][2], "region census"

@@ -19,15 +19,27 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     int rc;
     // TerrainPass::Render, then the chains of the next frames under its tile pass (a frame already prepared is a no-op)
     // (a sticky code - VR_ERR_TOO_MANY_INSTANCES / VR_ERR_OVERFLOW of an EARLIER frame - does not stop this one: it is returned at the end)
-    int earlier = vr_terrain_render(t, f->view, f->view, gb, f->render, f->part);
+    // Under VR_OPT_FRAME_FUSION the tile pass shades as well where its G-buffer-keeping flavour applies (the plain streaming
+    // lighting pass of a whole frame; everything else is decided in vr_terrain_render_keep, in front of the launch): the frame is
+    // then one kernel, and what the G-buffer, its plane states and HdrColor hold afterwards is what the two passes leave.
+    bool fused = false;
+    hipEvent_t fused_stop = nullptr;
+    int earlier;
+    if (ctx->frame_fusion && !f->tiled && !f->shadow && !f->part)
+        earlier = vr_terrain_render_keep(t, f->view, gb, f->render, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, &fused, &fused_stop);
+    else earlier = vr_terrain_render(t, f->view, f->view, gb, f->render, f->part);
     if (earlier != VR_OK && earlier != VR_ERR_TOO_MANY_INSTANCES && earlier != VR_ERR_OVERFLOW) return earlier;
     for (int k = 0; k < 2; k++)
         if (f->prepare_views[k] && (rc = vr_terrain_prepare(t, f->prepare_views[k], gb, f->render, f->part))) return rc;
     // whoever still reads the image this lighting pass overwrites (the tone-map stage of two frames ago, on another stream)
+    // (a fused tile pass has waited for that reader in front of its own launch)
+    if (fused) rc = VR_OK;
+    else {
     if (hdr->read_pending) { VR_HIP(hipStreamWaitEvent(ctx->stream, hdr->ev_read_done, 0)); hdr->read_pending = false; }
     if (f->tiled) rc = vr_deferred_light_tiled(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part);
     else if (f->shadow) rc = vr_deferred_light_shadowed(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow);
     else rc = vr_deferred_light(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part);
+    }
     if (rc) return rc;
     if (!f->tonemap) return earlier;
 
@@ -38,7 +50,9 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     const bool cross = tc->stream != ctx->stream;
     if (cross) {
         // behind the lighting pass: its dispatch-stamped stop event when there is one, else an explicit record
-        hipEvent_t done = (ctx->dispatch_events && ctx->last_stop) ? ctx->last_stop : nullptr;
+        // (a fused frame: the tile pass's OWN stop event, handed out by the launch - vr_terrain_prepare has run since and the
+        // context's last stamped launch need not be that one any more)
+        hipEvent_t done = fused ? fused_stop : (ctx->dispatch_events && ctx->last_stop) ? ctx->last_stop : nullptr;
         if (!done) {
             if (!hdr->ev_written) VR_HIP(hipEventCreateWithFlags(&hdr->ev_written, hipEventDisableTiming));
             VR_HIP(hipEventRecord(hdr->ev_written, ctx->stream));

@@ -38,6 +38,7 @@ extern "C" VR_API int vr_context_create(int device, vr_context** out)
     struct Guard { vr_context*& c; ~Guard() { if (c) vr_context_destroy(c); } } guard{ c };   // frees what exists on an early return
     c->device = device;
     c->stream = nullptr;   // default stream until vr_context_set_stream
+    if (const char* e = getenv("VR_FRAME_FUSION")) c->frame_fusion = atoi(e) != 0;      // (A/B runs of an unchanged host program)
     for (int i = 0; i < 256; i++) c->h_srgb_lut[i] = (float)srgb_eotf((double)i / 255.0);
     c->h_srgb_thr[0] = 0.0f;
     for (int k = 1; k < 256; k++) c->h_srgb_thr[k] = (float)srgb_eotf(((double)k - 0.5) / 255.0);
@@ -100,10 +101,11 @@ extern "C" VR_API int vr_context_set_stream(vr_context* c, void* s)
 extern "C" VR_API int vr_context_set_option(vr_context* c, int option, int value)
 {
     VR_REQUIRE(c != nullptr, "ctx is NULL");
-    VR_REQUIRE(option == VR_OPT_ASYNC_GEOMETRY || option == VR_OPT_DISPATCH_EVENTS || option == VR_OPT_RASTER_TILE || option == VR_OPT_PLANE_TRACKING || option == VR_OPT_SCRATCH_WORST_CASE, "unknown option");
+    VR_REQUIRE(option == VR_OPT_ASYNC_GEOMETRY || option == VR_OPT_DISPATCH_EVENTS || option == VR_OPT_RASTER_TILE || option == VR_OPT_PLANE_TRACKING || option == VR_OPT_SCRATCH_WORST_CASE || option == VR_OPT_FRAME_FUSION, "unknown option");
     if (option == VR_OPT_ASYNC_GEOMETRY) c->async_geometry = value != 0;
     else if (option == VR_OPT_PLANE_TRACKING) c->plane_tracking = value != 0;
     else if (option == VR_OPT_SCRATCH_WORST_CASE) c->scratch_worst_case = value != 0;
+    else if (option == VR_OPT_FRAME_FUSION) c->frame_fusion = value != 0;
     else if (option == VR_OPT_RASTER_TILE) {
         VR_REQUIRE(value == 0 || value == 32 || value == 64, "VR_OPT_RASTER_TILE: 0 (by size), 32 or 64");
         c->raster_tile_force = value == 32 ? 5 : value == 64 ? 6 : 0;

@@ -164,6 +164,7 @@ struct vr_context {
     bool async_geometry = true;    // VR_OPT_ASYNC_GEOMETRY
     bool scratch_worst_case = false;   // VR_OPT_SCRATCH_WORST_CASE: terrains created from now on size their scratch for max_instances up front
     bool plane_tracking = true;    // VR_OPT_PLANE_TRACKING: the tile pass does not rewrite a G-buffer plane the library knows to be all zero (vr_gbuffer)
+    bool frame_fusion = true;      // VR_OPT_FRAME_FUSION: vr_frame_submit shades in the tile pass where its G-buffer-keeping flavour applies
     int raster_tile_force = 0;     // VR_OPT_RASTER_TILE: 0 = by size (vr_raster_tile_shift), 5 / 6 = 32- / 64-pixel raster tiles
     // VR_OPT_DISPATCH_EVENTS: the tile pass and the lighting pass are launched with hipExtLaunchKernelGGL, whose start/stop
     // events are stamped by the dispatch itself; the stop events double as the cross-stream dependencies (tile pass done ->
@@ -390,6 +391,12 @@ int vr_terrain_pick_set(vr_terrain* t);
 // reads the counters of completed chains (no wait), grows the scratch by the high-water mark; returns a completed frame's sticky
 // device-side error once (VR_OK otherwise).  Called at the head of vr_terrain_render / vr_terrain_prepare / vr_terrain_select.
 int vr_terrain_poll(vr_terrain* t, bool report);
+// vr_frame_submit's tile pass under VR_OPT_FRAME_FUSION (vr_raster.hip): vr_terrain_render of the whole frame that also shades
+// into hdr_out where the G-buffer-keeping fused flavour applies (*fused; *fused_stop = that launch's dispatch-stamped stop event
+// or NULL) and is exactly vr_terrain_render where it does not
+int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
+                           int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
+                           bool* fused, hipEvent_t* fused_stop);
 int vr_terrain_reserve_bins(vr_terrain* t, size_t tiles);     // room for a target of that many raster tiles (vr_select.hip)
 // tables of (w, h, part); part == NULL is the whole frame as rank 0 of 1
 int vr_partition_tables(vr_context* ctx, int w, int h, const vr_partition* part, const PartTables** out);

@@ -1217,14 +1217,22 @@ struct LitArgs {
     int slot_base, owner_tiles_x;
 };
 struct LitNone { int unused; };
-template <bool WIRE, int TILE, int MODE, bool RANGES = false, bool NOEMI = false, bool LIT = false>
+// KEEP (a flavour of LIT; 32-pixel tiles, NOEMI, whole frame: vr_frame_submit under VR_OPT_FRAME_FUSION): the fused resolve
+// ALSO leaves the G-buffer behind - the registers shade_pixel was given go to the planes through the unfused branch's stores,
+// region states kept as the unfused kernel keeps them.  Planes, states and HdrColor are what the pair of passes leaves; what
+// the frame saves is the lighting pass's read-back of 20 bytes per pixel, its cold start and one kernel boundary.
+// Waves per SIMD asked of the compiler for it: 83 VGPRs and no spill at 4 and at 5 alike (five waves either way); at 6 it spills.
+#ifndef VR_RASTER_WAVES_KEEP
+#define VR_RASTER_WAVES_KEEP 5
+#endif
+template <bool WIRE, int TILE, int MODE, bool RANGES = false, bool NOEMI = false, bool LIT = false, bool KEEP = false>
 // A 32-pixel tile's workgroup needs 11 KB of LDS: registers, not LDS, decide how many fit a CU.  Asked for six waves per SIMD
 // the compiler fits every 32-pixel variant into 80 VGPRs without a spill (84-90 otherwise: five waves): 5120x2880 frame
 // 0.288 -> 0.279 ms, 4K 0.203 -> 0.2015, the rank of an 8-way split 0.128 -> 0.126 (profiles/r03_tile32_waves.txt).
 #ifndef VR_RASTER_WAVES_32
 #define VR_RASTER_WAVES_32 6
 #endif
-__global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : VR_RASTER_WAVES_PER_EU)) void k_raster(RasterArgs a, DevTex hm, DevTex al, const DevVert* __restrict__ verts,
+__global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : VR_RASTER_WAVES_PER_EU)) void k_raster(RasterArgs a, DevTex hm, DevTex al, const DevVert* __restrict__ verts,
                                                  const HardTriRec* __restrict__ hard_tris, const uint32_t* __restrict__ hard_first,
                                                  const uint4* __restrict__ recs, uint32_t rec_hard_base,
                                                  const uint32_t* __restrict__ tile_cursor, const uint32_t* __restrict__ tile_offset,
@@ -1242,7 +1250,8 @@ __global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : V
     // spec_const in the specular plane (main_ps writes one constant there, terrain_ps.hlsl:76).  A region that is all sky and
     // known clear is not written at all, a region that is all terrain and known constant keeps its specular plane: the bytes in
     // memory are the same either way.
-    constexpr bool TRACK = MODE == RM_FAST && TILE == 32 && !LIT && !WIRE;
+    constexpr bool TRACK = MODE == RM_FAST && TILE == 32 && (!LIT || KEEP) && !WIRE;
+    static_assert(!KEEP || (LIT && NOEMI && TILE == 32), "the G-buffer-keeping flavour: fused, 32-pixel tiles, emissive plane known zero");
     static_assert(!LIT || (MODE == RM_FAST && !RANGES), "the fused variant is the fast variant");
     static_assert((!RANGES && !NOEMI) || MODE == RM_FAST, "depth ranges and the emissive skip come with the fast variant");
     __shared__ unsigned long long vis[TILE * TILE];
@@ -1277,7 +1286,7 @@ __global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : V
     const uint32_t off = tile_offset[tile], n_all = tile_cursor[tile] - off;     // bin = entries[off .. off + n_all)
     const uint32_t n = min(n_all, off < a.bin_capacity ? a.bin_capacity - off : 0u);   // (an overflowing frame drops the entries beyond the capacity: VR_ERR_OVERFLOW)
     const TileEntry* __restrict__ bin = entries + off;
-    if constexpr (TRACK) {
+    if constexpr (TRACK && !KEEP) {       // (KEEP: the tile's HdrColor is still to be written - its waves do that below)
         // nothing to draw and the whole tile known to hold the clear values already: done (workgroup-uniform)
         if (region != nullptr && a.assume_cleared && n_all == 0u
             && reinterpret_cast<const uint32_t*>(region)[tile] == kRegionClear * 0x01010101u) return;
@@ -1582,6 +1591,23 @@ __global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : V
             if (nst != st && lane == 0) region[ri] = (uint8_t)nst;
         }
     }
+    if constexpr (KEEP) {
+        // a region that is all sky and known clear: nothing for the G-buffer, +0 for HdrColor (what the lighting pass stores for
+        // a clear region, k_deferred) (wave-uniform)
+        if (skip_all) {
+            for (int g = tid; g < kStrips; g += kRT) {
+                const int gx = ox + g % TILE, gy0 = oy + (g / TILE) * 4;
+                if (!whole && gx >= a.w) continue;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    if (!whole && gy0 + k >= a.h) break;
+                    const u2 zv = { 0u, 0u };
+                    __builtin_nontemporal_store(zv, reinterpret_cast<u2*>(lit.hdr) + ((uint32_t)__umul24(gy0 + k, a.w) + (uint32_t)gx));
+                }
+            }
+            return;
+        }
+    }
     for (int g = skip_all ? kStrips : tid; g < kStrips; g += kRT) {
         const int lx = g % TILE, ly0 = (g / TILE) * 4;
         const int gx = ox + lx, gy0 = oy + ly0;
@@ -1652,8 +1678,8 @@ __global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : V
                 float lrgb[3] = { 0.0f, 0.0f, 0.0f };
                 if (__any(cov)) shade_pixel<false>(lit.da, s_lut, gx, gy0 + k, __uint_as_float(dep), dif, cov ? spec_const : 0u, nn0, nn1, 0u, 0u, lrgb);
                 const uint32_t o0 = vr_float_to_half(lrgb[0]) | (vr_float_to_half(lrgb[1]) << 16), o1 = vr_float_to_half(lrgb[2]);
-                __builtin_amdgcn_raw_buffer_store_b32(dep, rgb, pix4, 0, aux);
-                if (lit.tile_slot == nullptr) {
+                if constexpr (!KEEP) __builtin_amdgcn_raw_buffer_store_b32(dep, rgb, pix4, 0, aux);
+                if (KEEP || lit.tile_slot == nullptr) {
                     const u2 ov = { o0, o1 };
                     __builtin_nontemporal_store(ov, reinterpret_cast<u2*>(lit.hdr) + pix);
                 } else {
@@ -1664,7 +1690,7 @@ __global__ __launch_bounds__(kRT, (LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : V
                     uint16_t* dst = reinterpret_cast<uint16_t*>(lit.hdr) + oi * 3;
                     dst[0] = (uint16_t)o0; dst[1] = (uint16_t)(o0 >> 16); dst[2] = (uint16_t)o1;
                 }
-                continue;
+                if constexpr (!KEEP) continue;        // (KEEP: the same registers go on to the G-buffer's planes)
             }
             if (kExpNoStore) {        // (a dependent dummy keeps the shading alive)
                 if (a.w < 0) __builtin_amdgcn_raw_buffer_store_b32(dep ^ dif ^ nn0 ^ nn1, rgb, pix4, 0, aux);
@@ -1904,7 +1930,11 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
 }
 
 // what vr_terrain_render_lit adds to a render: the lighting pass's inputs and its output image
-struct LitRequest { const vr_light* lights; int32_t num_lights; const float* amb_top; const float* amb_bottom; vr_image* hdr; };
+// keep (vr_frame_submit under VR_OPT_FRAME_FUSION): fuse only where the G-buffer-keeping flavour applies (KEEP, k_raster) and
+// leave everything the unfused pair leaves; where it does not apply the call queues exactly the unfused tile pass and reports
+// "not fused".  stop_out: the fused launch's own dispatch-stamped stop event (NULL: the launch was not stamped).
+struct LitRequest { const vr_light* lights; int32_t num_lights; const float* amb_top; const float* amb_bottom; vr_image* hdr;
+                    bool keep; hipEvent_t* stop_out; };
 static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_partition* part,
                                const LitRequest* lit_req, bool* lit_done, int* earlier_out);
 
@@ -1931,13 +1961,26 @@ extern "C" VR_API int vr_terrain_render_lit(vr_terrain* t, const vr_view* view, 
     VR_REQUIRE(rp->assume_cleared && !rp->depth_only && !rp->wireframe && !rp->depth_ranges,
                "vr_terrain_render_lit draws into a cleared target (assume_cleared = 1), shaded fill mode, no depth ranges");
     VR_REQUIRE(num_lights >= 0 && num_lights <= kMaxLights && (num_lights == 0 || lights), "at most 16 lights (terrain_cb.h:15)");
-    const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out };
+    const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, false, nullptr };
     bool fused = false;
     int earlier = VR_OK;
     int rc = terrain_render_impl(t, view, gb, rp, part, &req, &fused, &earlier);
     if (rc) return rc;
     if (!fused && (rc = vr_deferred_light(t->ctx, view, gb, lights, num_lights, ambient_top, ambient_bottom, hdr_out, part))) return rc;     // the unfused pair
     return earlier;
+}
+
+// vr_frame_submit's tile pass: vr_terrain_render, shading in the same pass where the KEEP flavour applies (*fused; the caller
+// queues the lighting pass itself otherwise)
+int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
+                           int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
+                           bool* fused, hipEvent_t* fused_stop)
+{
+    const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, true, fused_stop };
+    int earlier = VR_OK;
+    *fused = false; *fused_stop = nullptr;
+    const int rc = terrain_render_impl(t, view, gb, rp, nullptr, &req, fused, &earlier);
+    return rc ? rc : earlier;
 }
 
 static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_partition* part,
@@ -1961,8 +2004,37 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     // RenderTargets::Clear is lazy under the plane-state tracking (vr_gbuffer::clear_pending): a shaded pass over the whole frame
     // writes every pixel of every plane anyway and runs as "over a cleared target" - Clear + Render is one pass over the
     // memory; any other pass (a rank's share, depth only, the fused variant) needs the clear values in memory first
+    // the fast variant: heightmap and albedo of one size (the albedo footprint shares the height taps' coordinates), a
+    // power-of-two world size, the five planes of the G-buffer within 4 GB (one buffer resource), filled and shaded
+    const bool same = t->height.w0 == t->albedo.w0 && t->height.h0 == t->albedo.h0 && t->height.levels == t->albedo.levels;
+    const uint64_t span = (uint64_t)((const char*)(gb->emissive + (size_t)gb->w * gb->h) - (const char*)gb->depth);
+    const bool one_rsrc = (const char*)gb->depth < (const char*)gb->diffuse && (const char*)gb->depth < (const char*)gb->specular
+                       && (const char*)gb->depth < (const char*)gb->normals && (const char*)gb->depth < (const char*)gb->emissive && span < (1ull << 32);
+    const bool fast = same && a.ws_pow2 && one_rsrc && !a.wireframe && !a.depth_only;
+    // A keep request is decided HERE, in front of everything the pass queues: where the KEEP flavour does not apply - or the
+    // lighting pass would refuse its inputs - the call goes on as the plain tile pass, the caller queues the lighting pass
+    // behind it as it always did and any error is that pass's to report.  The flavour exists for the whole frame on 32-pixel
+    // tiles over a target known cleared, with the emissive plane known zero and the streaming lighting pass's plain light list.
+    LitArgs la;
+    bool keep = false;
+    if (lit_req && lit_req->keep) {
+        const bool cleared = rp->assume_cleared || gb->clear_pending;          // (a pending clear is consumed by a whole-frame pass, below)
+        keep = part == nullptr && fast && a.tile_shift == 5 && cleared && !rp->depth_ranges
+            && ctx->plane_tracking && gb->emissive_zero && !gb->escaped
+            && view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0 && gb->w % 4 == 0
+            && lit_req->amb_top && lit_req->amb_bottom && lit_req->hdr && lit_req->hdr->data
+            && lit_req->num_lights >= 0 && lit_req->num_lights <= kMaxLights && (lit_req->num_lights == 0 || lit_req->lights)
+            && (size_t)gb->w * gb->h * 8 <= lit_req->hdr->capacity_bytes && lit_req->hdr->ctx->device == ctx->device;
+        if (keep) {
+            bool extra = false;
+            memset(&la, 0, sizeof(la));
+            keep = vr_deferred_make_args(view, gb->w, gb->h, lit_req->lights, lit_req->num_lights, lit_req->amb_top, lit_req->amb_bottom, &la.da, &extra) == VR_OK
+                && !extra;
+        }
+        if (!keep) lit_req = nullptr;           // from here on: a plain vr_terrain_render
+    }
     if (gb->clear_pending) {
-        if (a.world <= 1 && !a.depth_only && lit_req == nullptr) { a.assume_cleared = 1; gb->clear_pending = false; }
+        if (a.world <= 1 && !a.depth_only && (lit_req == nullptr || keep)) { a.assume_cleared = 1; gb->clear_pending = false; }
         else if ((rc = vr_gbuffer_materialise(gb, s))) return rc;
     }
 
@@ -1996,13 +2068,6 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         // G-buffer pass and must not be averaged with it
         VrKernelScope ks(ctx, rp->depth_only ? VR_K_RASTER_DEPTH : VR_K_RASTER, s, true);
         const int32_t* tiles = g.d_tile_order;            // this frame's tiles, longest bins first (k_scan)
-        // the fast variant: heightmap and albedo of one size (the albedo footprint shares the height taps' coordinates), a
-        // power-of-two world size, the five planes of the G-buffer within 4 GB (one buffer resource), filled and shaded
-        const bool same = t->height.w0 == t->albedo.w0 && t->height.h0 == t->albedo.h0 && t->height.levels == t->albedo.levels;
-        const uint64_t span = (uint64_t)((const char*)(gb->emissive + (size_t)gb->w * gb->h) - (const char*)gb->depth);
-        const bool one_rsrc = (const char*)gb->depth < (const char*)gb->diffuse && (const char*)gb->depth < (const char*)gb->specular
-                           && (const char*)gb->depth < (const char*)gb->normals && (const char*)gb->depth < (const char*)gb->emissive && span < (1ull << 32);
-        const bool fast = same && a.ws_pow2 && one_rsrc && !a.wireframe && !a.depth_only;
         const bool depth = a.depth_only && !a.wireframe;
         // the light tiles' depth ranges, if asked for: only from the fast variant over a target it fills completely
         const bool ranges = rp->depth_ranges && fast && a.assume_cleared && !gb->escaped;
@@ -2014,9 +2079,12 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         const bool noemi = fast && ctx->plane_tracking && gb->emissive_zero && !gb->escaped;
         auto kern = a.tile_shift == 5 ? pick_raster<32>(a.wireframe != 0, fast, depth, ranges, noemi) : pick_raster<64>(a.wireframe != 0, fast, depth, ranges, noemi);
         // the fused variant: only where the fast variant applies and the light list is the streaming pass's plain case
-        LitArgs la;
-        bool fuse = false;
-        if (lit_req && fast && !ranges) {
+        bool fuse = keep;
+        if (keep) {
+            la.lut_g = ctx->d_srgb_lut; la.hdr = (uint2*)lit_req->hdr->data;
+            // whoever still reads the image this pass overwrites (vr_frame_submit: the tone-map stage of two frames ago, on another stream)
+            if (lit_req->hdr->read_pending) { VR_HIP(hipStreamWaitEvent(s, lit_req->hdr->ev_read_done, 0)); lit_req->hdr->read_pending = false; }
+        } else if (lit_req && fast && !ranges) {
             bool extra = false;
             memset(&la, 0, sizeof(la));
             if ((rc = vr_deferred_make_args(view, gb->w, gb->h, lit_req->lights, lit_req->num_lights, lit_req->amb_top, lit_req->amb_bottom, &la.da, &extra))) return rc;
@@ -2035,19 +2103,21 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         if (lit_done) *lit_done = fuse;
         // region states: kept by the fast variant on 32-pixel tiles; any other variant writes the planes without keeping them
         uint8_t* region = nullptr;
-        if (fast && !fuse && a.tile_shift == 5 && ctx->plane_tracking && !gb->escaped) { if ((rc = vr_gbuffer_region_prepare(gb, s, &region))) return rc; }
+        if (fast && (!fuse || keep) && a.tile_shift == 5 && ctx->plane_tracking && !gb->escaped) { if ((rc = vr_gbuffer_region_prepare(gb, s, &region))) return rc; }
         else gb->region_fill = 0;
 #define VR_RASTER_ARGS a, t->height, t->albedo, g.d_verts, g.d_hard_tris, g.d_hard_first, \
                            (const uint4*)g.d_recs, (uint32_t)t->cap_instances * (uint32_t)kTrisPerInst, g.d_tile_cursor, g.d_tile_offset, g.d_bin_entries, tiles, g.d_counters + C_CLASS0, \
                            gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, ctx->d_srgb_thr, ctx->d_enc_tab, spec_const, ranges ? gb->d_ranges : (uint2*)nullptr, region
         if (fuse) {
             ks.id = VR_K_RASTER_LIT;
-            if (a.tile_shift == 5) VR_LAUNCH_TIMED(ks, (k_raster<false, 32, RM_FAST, false, true, true>), dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
+            if (keep) VR_LAUNCH_TIMED(ks, (k_raster<false, 32, RM_FAST, false, true, true, true>), dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
+            else if (a.tile_shift == 5) VR_LAUNCH_TIMED(ks, (k_raster<false, 32, RM_FAST, false, true, true>), dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
             else VR_LAUNCH_TIMED(ks, (k_raster<false, 64, RM_FAST, false, true, true>), dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
         } else
         VR_LAUNCH_TIMED(ks, kern, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, LitNone());
 #undef VR_RASTER_ARGS
         if (ctx->dispatch_events && ks.e0 && ks.e1) pass_stop = ks.e1;        // stamped by the dispatch: complete when the tile pass is
+        if (keep && lit_req->stop_out) *lit_req->stop_out = pass_stop;
         // a shaded pass over a cleared target writes the emissive texel (0) of EVERY pixel of the frame, covered or not: from here
         // on the plane is known zero again, whatever it held (a partitioned or keep-what-is-there pass writes zeros to some pixels:
         // the state stays what it was)

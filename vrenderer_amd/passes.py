@@ -66,6 +66,10 @@ class Context:
         """Terrains created from now on size their per-frame scratch for max_instances up front instead of by high-water mark."""
         check(self.lib.vr_context_set_option(self.handle, capi.VR_OPT_SCRATCH_WORST_CASE, int(enable)), "vr_context_set_option")
 
+    def set_frame_fusion(self, enable):
+        """Frame.submit shades in the tile pass where its G-buffer-keeping flavour applies (same results; default on)."""
+        check(self.lib.vr_context_set_option(self.handle, capi.VR_OPT_FRAME_FUSION, int(enable)), "vr_context_set_option")
+
     def set_dispatch_events(self, enable):
         """Tile pass / lighting pass launched with dispatch-stamped events that double as cross-stream dependencies (default on)."""
         check(self.lib.vr_context_set_option(self.handle, capi.VR_OPT_DISPATCH_EVENTS, int(enable)), "vr_context_set_option")
