@@ -3,8 +3,10 @@
 Test infrastructure: tests/test_oracle_cpu.py bounds the C oracle's raster / sampler model (revision 3: plane equations,
 fused sampler arithmetic, a pinned cubic for log2) against this file.  What is taken as given, because the text of the
 reference or of D3D pins it:
-  - the vertex stage's fp32 outputs (terrain_vs.hlsl:35-62 in its written order; the oracle's vertex_shader, which the
-    GPU suite compares with the HIP kernel bit for bit);
+  - the vertex stage's fp32 outputs, the node list (ot.select) and the mip chains: they are not this model's subject but
+    no longer rest on the oracle alone - tests/f64_frontend.py states main_vs (terrain_vs.hlsl:10-62), NodeSelect, SetHeight
+    and the box-filtered chains from the text and bounds the oracle (tests/test_frontend_cpu.py) and the HIP kernels
+    (tests/test_frontend_f64.py) by it;
   - what the rasteriser is handed per vertex: the fp32 viewport transform and perspective divide and the snap to 8
     sub-pixel bits (D3D11 3.4.1 / 3.4.3): X, Y as 24.8 integers, z = z_clip * (1 / w), 1 / w;
   - D3D's coverage rules: pixel centres at +0.5, top-left rule, in-order LessOrEqual depth test.
