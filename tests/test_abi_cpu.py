@@ -182,6 +182,19 @@ def test_cpp_host_example_compiles_links_and_fails_soft_without_gpu(product_lib,
         assert r.returncode == 0 and "no device" in r.stdout and "no HIP device" in r.stderr, r.stdout + r.stderr
 
 
+def test_raster_plan_matches_the_transcribed_decisions_and_invariants(tmp_path):
+    """vr_raster_plan.h compiles without HIP and raster_plan() agrees, for every input, with the tile pass's decisions as
+    they were written inside terrain_render_impl, and with the invariants of tests/host/raster_plan_check.cpp."""
+    import subprocess
+    exe = os.path.join(str(tmp_path), "raster_plan_check")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "raster_plan_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    assert "786432 cases" in r.stdout, r.stdout[-400:]          # 2^16 bools x 2 worlds x 2 tile edges x 3 requests
+
+
 def _build_allgather_example(tmpdir):
     import subprocess
     exe = os.path.join(str(tmpdir), "frame_allgather_example")

@@ -1732,6 +1732,81 @@ def test_fused_render_lit_at_8k_and_split_eight_ways(scene2048, gpu_ctx):
         assert np.array_equal(wp, gp), f"rank {r} of 8"
 
 
+def test_render_lit_refuses_a_bad_light_list_up_front_and_leaves_no_trace(scene256, gpu_ctx):
+    """vr_terrain_render_lit hands its light list to vr_deferred_make_args before it queues anything: a list the lighting pass
+    refuses (an unknown type, a spot light whose cone is inside out) is refused with that pass's code and words - where the
+    tile pass's fast variant applies and where it does not (albedo of another size) - and the objects behave afterwards like
+    fresh ones: Clear + Render + lighting on them is bit-identical in every plane and in HdrColor.  With a partial viewport
+    as well, the first complaint is the one the passes always made: the light list's where the fast variant applies, the
+    lighting pass's "viewport must cover" where it does not.  A valid spot light is no error: the call runs the two passes
+    and matches them bit for bit.  (What the host sees is checked; that nothing was queued before the refusal is not
+    observable through the API and is not claimed here.)"""
+    w, h = 256, 144
+    tp = scene256["tp"]
+    tp_other = vr.TerrainPass(gpu_ctx, params(256)).Init(scene256["h"], np.ascontiguousarray(scene256["a"][:128, :128]))
+    v = vr.make_view(*scaled_camera(CAMERAS[0], 256), w, h)
+    v_part = vr.make_view(*scaled_camera(CAMERAS[0], 256), 200, 100)
+    v_part.viewport_x, v_part.viewport_y = 16, 8
+    sun = [vr.reference_sun()]
+    rp, rp_lit = vr.default_render_params(400.0), vr.default_render_params(400.0, assume_cleared=1)
+    planes = ("depth", "diffuse", "specular", "normals", "emissive")
+
+    def pair(t, rt, hdr, lights):
+        rt.Clear()
+        t.Render(v, v, rt, rp)
+        vr.DeferredLightingPass(gpu_ctx).Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        return [rt.download(k).copy() for k in planes] + [hdr.download().copy()]
+
+    def same(want, got, what):
+        for name, a, b in zip(planes + ("HdrColor",), want, got):
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{name}: {what}"
+
+    unknown = vr.reference_sun()
+    unknown.type = 7
+    inside_out = vr.spot_light((-20.0, 60.0, 10.0), (0.3, -1.0, -0.2), 6000.0, 200.0, 25.0, 12.0)
+    bad_lists = ((unknown, "unknown light type"), (inside_out, "spot light needs outer_angle > inner_angle"))
+    cover = "view viewport must cover the G-buffer"
+    spots = sun + [vr.spot_light((-20.0, 60.0, 10.0), (0.3, -1.0, -0.2), 6000.0, 200.0, 12.0, 25.0, (0.2, 1.0, 0.4))]
+    objs = [vr.RenderTargets(gpu_ctx).Init(w, h), vr.HdrImage(gpu_ctx, w, h), vr.RenderTargets(gpu_ctx).Init(w, h), vr.HdrImage(gpu_ctx, w, h)]
+    fresh_rt, fresh_hdr, rt, hdr = objs
+
+    def refused(t, view, lights, words):
+        with pytest.raises(vr.capi.VrError) as e:
+            t.RenderLit(view, rt, rp_lit, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        assert e.value.code == vr.capi.VR_ERR_INVALID_ARGUMENT and words in str(e.value), str(e.value)
+
+    gpu_ctx.set_raster_tile(32)
+    try:
+        for t, fast in ((tp, True), (tp_other, False)):
+            want = pair(t, fresh_rt, fresh_hdr, sun)
+            assert 0.05 < (want[0] < 1.0).mean() < 0.95         # (terrain and sky in view)
+            for bad, words in bad_lists:
+                refused(t, v, sun + [bad], words)
+                refused(t, v_part, sun + [bad], words if fast else cover)
+            same(want, pair(t, rt, hdr, sun), f"after the refused calls (fast variant: {fast})")
+        want_spots = pair(tp, fresh_rt, fresh_hdr, spots)
+        rt.Clear()
+        tp.RenderLit(v, rt, rp_lit, spots, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        same(want_spots, [rt.download(k) for k in planes] + [hdr.download()], "render_lit with a spot light")
+        # A refused call leaves the library's knowledge of the planes alone: the emissive plane holds foreign data (not known
+        # zero), a whole-frame render_lit that cannot fuse (spot light) is refused for its partial viewport behind the geometry
+        # chain - and the next pass over a cleared target still rewrites the plane.
+        rt.Clear()
+        emi = rt.download("emissive").copy()
+        emi[...] = 0x3c00
+        rt.upload("emissive", emi)
+        refused(tp, v_part, spots, cover)
+        tp.Render(v, v, rt, rp_lit)
+        fresh_rt.Clear()
+        tp.Render(v, v, fresh_rt, rp_lit)
+        assert not rt.download("emissive").any(), "the emissive plane kept foreign data: it was taken for known zero"
+        same([fresh_rt.download(k) for k in planes], [rt.download(k) for k in planes], "after a refusal behind the geometry chain")
+    finally:
+        gpu_ctx.set_raster_tile(0)
+        for o in objs + [tp_other]:
+            o.close()
+
+
 def _render_view_both(sc, oracle, gpu_ctx, v, w, h, **rpkw):
     ot, tp = sc["ot"], sc["tp"]
     rp = vr.default_render_params(400.0, **rpkw)

@@ -819,9 +819,7 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
     // The light tiles' depth ranges, if the tile pass that filled this G-buffer left them (for the same split) and nothing has
     // written to it since.  The culling stage consumes them (every entry it reads is reset), hence CLEAN afterwards - for a
     // split, only if this rank's share is non-empty (else nothing was written either).
-    const bool use_ranges = gb->ranges_state == vr_gbuffer::RANGES_VALID && gb->d_ranges && gb->ranges_world == (part ? part->world_size : 1)
-                         && gb->ranges_rank == (part ? part->rank : 0);
-    if (use_ranges) gb->ranges_state = vr_gbuffer::RANGES_CLEAN;
+    const bool use_ranges = vr_gbuffer_consume_ranges(gb, part ? part->rank : 0, part ? part->world_size : 1);
     // two launches, each timed under its own id; the shading kernel's events are stamped by its dispatch like the streaming
     // pass's, so its stop event serves as the next frame's geometry start hint (vr_terrain_prepare)
     if (packed) {

@@ -1,5 +1,6 @@
 // Host side of libvrterrain.so: context, render targets, view helper, partition tables.
 #include "vr_internal.h"
+#include "vr_raster_plan.h"
 #include "vr_experiments.h"
 
 #include <math.h>
@@ -457,9 +458,12 @@ static int fill_u32(hipStream_t s, void* ptr, size_t count, uint32_t v)
     return VR_OK;
 }
 
+// (anything that writes the G-buffer without leaving depth ranges: they are stale)
+static void gbuffer_touch(vr_gbuffer* g) { if (g->ranges_state == vr_gbuffer::RANGES_VALID) g->ranges_state = vr_gbuffer::RANGES_DIRTY; }
+
 static int gbuffer_clear_now(vr_gbuffer* g, hipStream_t s)
 {
-    vr_gbuffer_touch(g);
+    gbuffer_touch(g);
     size_t n = (size_t)g->w * g->h;
     int rc;
     VrKernelScope scope(g->ctx, VR_K_CLEAR, s);
@@ -480,7 +484,7 @@ extern "C" VR_API int vr_gbuffer_clear(vr_gbuffer* g)
     VR_HIP(hipSetDevice(g->ctx->device));
     if (g->ctx->plane_tracking && !g->escaped && g->cleared_once) {
         // lazy (vr_internal.h): the planes are cleared by the next whole-frame tile pass, or by whoever looks at them first
-        vr_gbuffer_touch(g);
+        gbuffer_touch(g);
         g->clear_pending = true;
         return VR_OK;
     }
@@ -494,7 +498,8 @@ int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s)
     return gbuffer_clear_now(g, s);
 }
 
-int vr_gbuffer_region_prepare(vr_gbuffer* g, hipStream_t s, uint8_t** out)
+// the region array: allocated and current
+static int gbuffer_region_prepare(vr_gbuffer* g, hipStream_t s, uint8_t** out)
 {
     const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
     if (!g->d_region) {
@@ -526,7 +531,7 @@ int vr_gbuffer_plane_hints(vr_gbuffer* g, hipStream_t s, PlaneHints* out)
     { const int rc = vr_gbuffer_materialise(g, s); if (rc) return rc; }       // (a reader: a pending clear happens now)
     if (!g->ctx->plane_tracking || g->escaped) return VR_OK;
     uint8_t* r = nullptr;
-    const int rc = vr_gbuffer_region_prepare(g, s, &r);
+    const int rc = gbuffer_region_prepare(g, s, &r);
     if (rc) return rc;
     out->region = r; out->emissive_zero = g->emissive_zero ? 1 : 0;
     return VR_OK;
@@ -559,7 +564,8 @@ __global__ void k_fill_u32x2(uint2* p, size_t n, uint32_t x, uint32_t y)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint2(x, y);
 }
-int vr_gbuffer_ranges_prepare(vr_gbuffer* g, hipStream_t s)
+// the depth ranges: allocated and every entry "none"
+static int gbuffer_ranges_prepare(vr_gbuffer* g, hipStream_t s)
 {
     const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
     if (!g->d_ranges || g->ranges_tiles != tiles) {
@@ -576,14 +582,53 @@ int vr_gbuffer_ranges_prepare(vr_gbuffer* g, hipStream_t s)
     return VR_OK;
 }
 
+int vr_gbuffer_settle_clear(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s)
+{
+    if (plan.consume_pending_clear) g->clear_pending = false;
+    return plan.materialise_first ? vr_gbuffer_materialise(g, s) : VR_OK;
+}
+
+int vr_gbuffer_apply_plan(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s, int rank, int world, uint8_t** region)
+{
+    int rc;
+    *region = nullptr;
+    if (plan.ranges) {
+        if ((rc = gbuffer_ranges_prepare(g, s))) return rc;
+        g->ranges_state = vr_gbuffer::RANGES_VALID; g->ranges_rank = rank; g->ranges_world = world;
+    } else gbuffer_touch(g);
+    if (plan.track_regions) { if ((rc = gbuffer_region_prepare(g, s, region))) return rc; }
+    else g->region_fill = 0;
+    if (plan.emissive_zero_after) g->emissive_zero = true;
+    return VR_OK;
+}
+
+void vr_gbuffer_foreign_write(vr_gbuffer* g, int plane)
+{
+    gbuffer_touch(g);
+    if (plane == 4) g->emissive_zero = false;
+    g->region_fill = 0;                    // (no region is known clear - that includes the emissive plane - or constant any more)
+}
+
+void vr_gbuffer_escape(vr_gbuffer* g)
+{
+    gbuffer_touch(g);              // whatever the caller writes through the pointers is unknown here, now and for as long as
+    g->escaped = true;             // the G-buffer lives (no depth ranges, no plane-state tracking any more)
+    g->emissive_zero = false;
+    g->region_fill = 0;
+}
+
+bool vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world)
+{
+    const bool use = g->ranges_state == vr_gbuffer::RANGES_VALID && g->d_ranges && g->ranges_world == world && g->ranges_rank == rank;
+    if (use) g->ranges_state = vr_gbuffer::RANGES_CLEAN;
+    return use;
+}
+
 extern "C" VR_API int vr_gbuffer_describe(vr_gbuffer* g, vr_gbuffer_desc* d)
 {
     VR_REQUIRE(g && d, "NULL argument");
     { VR_HIP(hipSetDevice(g->ctx->device)); const int rc = vr_gbuffer_materialise(g, g->ctx->stream); if (rc) return rc; }
-    vr_gbuffer_touch(g);           // the caller gets the device pointers: whatever it writes through them is unknown here,
-    g->escaped = true;             // now and for as long as the G-buffer lives (no depth ranges, no plane-state tracking any more)
-    g->emissive_zero = false;
-    g->region_fill = 0;
+    vr_gbuffer_escape(g);          // the caller gets the device pointers
     d->width = g->w; d->height = g->h; d->depth = g->depth; d->diffuse = g->diffuse; d->specular = g->specular;
     d->normals = g->normals; d->emissive = g->emissive;
     return VR_OK;
@@ -620,9 +665,7 @@ extern "C" VR_API int vr_gbuffer_upload(vr_gbuffer* g, int plane, const void* ho
     VR_REQUIRE(bytes == nb, "byte count does not match the plane size");
     VR_HIP(hipSetDevice(g->ctx->device));
     if ((rc = vr_gbuffer_materialise(g, g->ctx->stream))) return rc;
-    vr_gbuffer_touch(g);
-    if (plane == 4) g->emissive_zero = false;
-    g->region_fill = 0;                    // (no region is known clear - that includes the emissive plane - or constant any more)
+    vr_gbuffer_foreign_write(g, plane);
     VR_HIP(hipMemcpyAsync(p, host, nb, hipMemcpyHostToDevice, g->ctx->stream));
     VR_HIP(hipStreamSynchronize(g->ctx->stream));
     return VR_OK;

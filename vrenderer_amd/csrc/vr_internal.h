@@ -247,9 +247,20 @@ struct vr_gbuffer {
     bool clear_pending = false;
     bool cleared_once = false;       // (the clear at creation is a real one: the allocation holds anything)
 };
-int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s);      // a pending clear is written now, on `s` (vr_host.hip)
 constexpr uint32_t kRegionSpec = 1u, kRegionClear = 2u;
-int vr_gbuffer_region_prepare(vr_gbuffer* g, hipStream_t s, uint8_t** out);     // allocated and current (vr_host.hip)
+// The state above changes only through these (vr_host.hip; vr_gbuffer_clear is the remaining one):
+int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s);      // a pending clear is written now, on `s`
+// A tile pass as raster_plan() decided it (vr_raster_plan.h).  settle_clear, in front of everything the pass queues: the
+// pending clear is written or consumed.  apply_plan, once nothing can refuse the launch any more: depth ranges ready and VALID
+// for (rank, world) - or stale -, the region array current (*region; NULL: not kept, nothing is known per region any more),
+// the emissive plane known zero if the pass leaves it so.
+struct RasterPlan;
+int vr_gbuffer_settle_clear(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s);
+int vr_gbuffer_apply_plan(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s, int rank, int world, uint8_t** region);
+void vr_gbuffer_foreign_write(vr_gbuffer* g, int plane);       // something outside the library's passes wrote the plane
+void vr_gbuffer_escape(vr_gbuffer* g);                         // the device pointers have left the library, for good
+// the tiled lighting pass takes the depth ranges if they are VALID for this split (they are "none" again once it has run)
+bool vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world);
 // What a pass that READS the G-buffer may take from the tracking instead of from memory (the lighting passes).
 struct PlaneHints {
     const uint8_t* region;       // region states (NULL: nothing known per region)
@@ -259,9 +270,6 @@ struct PlaneHints {
 };
 int vr_gbuffer_plane_hints(vr_gbuffer* g, hipStream_t s, PlaneHints* out);
 uint32_t vr_specular_constant(const vr_context* c);     // main_ps's specular output as the G-buffer holds it (terrain_ps.hlsl:76 -> SRGBA8)
-// (anything else that writes the G-buffer: its depth ranges are stale)
-inline void vr_gbuffer_touch(vr_gbuffer* g) { if (g->ranges_state == vr_gbuffer::RANGES_VALID) g->ranges_state = vr_gbuffer::RANGES_DIRTY; }
-int vr_gbuffer_ranges_prepare(vr_gbuffer* g, hipStream_t s);      // allocated and every entry "none" (vr_host.hip)
 
 struct vr_image {
     vr_context* ctx;

@@ -25,6 +25,7 @@
 // rule; all float math is in fixed order with contraction off, so the G-buffer is
 // bit-identical to the CPU oracle.
 #include "vr_internal.h"
+#include "vr_raster_plan.h"
 #include "vr_tex_dev.h"
 #include "vr_deferred_dev.h"
 #include "vr_experiments.h"
@@ -1858,14 +1859,30 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
     return VR_OK;
 }
 
-typedef decltype(&k_raster<false, 32, RM_GENERIC>) raster_kernel_t;
+// Every k_raster instantiation there is, by the plan's variant (vr_raster_plan.h says when each runs).  The fused ones take
+// LitArgs where the others take LitNone: `lit` or `plain` is set, never both.
+struct RasterKernel { decltype(&k_raster<false, 32, RM_GENERIC>) plain; decltype(&k_raster<false, 32, RM_FAST, false, true, true>) lit; };
 template <int TILE>
-static raster_kernel_t pick_raster(bool wire, bool fast, bool depth, bool ranges, bool noemi)
+static RasterKernel raster_kernel_edge(int v)       // v: the variant less its tile edge's first
 {
-    if (wire) return k_raster<true, TILE, RM_GENERIC>;
-    if (fast) return ranges ? (noemi ? k_raster<false, TILE, RM_FAST, true, true> : k_raster<false, TILE, RM_FAST, true, false>)
-                            : (noemi ? k_raster<false, TILE, RM_FAST, false, true> : k_raster<false, TILE, RM_FAST, false, false>);
-    return depth ? k_raster<false, TILE, RM_DEPTH> : k_raster<false, TILE, RM_GENERIC>;
+    switch (v) {
+    case RV_WIRE_32:              return { k_raster<true, TILE, RM_GENERIC>, nullptr };
+    case RV_FAST_RANGES_NOEMI_32: return { k_raster<false, TILE, RM_FAST, true, true>, nullptr };
+    case RV_FAST_RANGES_32:       return { k_raster<false, TILE, RM_FAST, true, false>, nullptr };
+    case RV_FAST_NOEMI_32:        return { k_raster<false, TILE, RM_FAST, false, true>, nullptr };
+    case RV_FAST_32:              return { k_raster<false, TILE, RM_FAST, false, false>, nullptr };
+    case RV_DEPTH_32:             return { k_raster<false, TILE, RM_DEPTH>, nullptr };
+    case RV_GENERIC_32:           return { k_raster<false, TILE, RM_GENERIC>, nullptr };
+    }
+    return { nullptr, nullptr };
+}
+static RasterKernel raster_kernel(RasterVariant v)
+{
+    if (v < RV_WIRE_64) return raster_kernel_edge<32>(v);
+    if (v < RV_LIT_32) return raster_kernel_edge<64>(v - RV_WIRE_64);
+    if (v == RV_KEEP_32) return { nullptr, k_raster<false, 32, RM_FAST, false, true, true, true> };
+    if (v == RV_LIT_32) return { nullptr, k_raster<false, 32, RM_FAST, false, true, true> };
+    return { nullptr, k_raster<false, 64, RM_FAST, false, true, true> };
 }
 
 static bool prepared_matches(const GeoSet& g, const vr_view* view, const vr_render_params* rp, int w, int h, const RasterArgs& a)
@@ -1935,8 +1952,143 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
 // "not fused".  stop_out: the fused launch's own dispatch-stamped stop event (NULL: the launch was not stamped).
 struct LitRequest { const vr_light* lights; int32_t num_lights; const float* amb_top; const float* amb_bottom; vr_image* hdr;
                     bool keep; hipEvent_t* stop_out; };
+// The facts raster_plan() decides on.  Whether a lit request's light list is the lighting pass's plain case is one of them:
+// the list goes through vr_deferred_make_args here (*la, *lights_rc).
+static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view, const vr_gbuffer* gb, const vr_render_params* rp,
+                                       const RasterArgs& a, const LitRequest* lit_req, LitArgs* la, int* lights_rc)
+{
+    const vr_context* ctx = t->ctx;
+    RasterPlanIn in{};
+    in.wireframe = a.wireframe != 0; in.depth_only = a.depth_only != 0; in.assume_cleared = a.assume_cleared != 0; in.depth_ranges = rp->depth_ranges != 0;
+    in.world = a.world; in.tile_shift = a.tile_shift;
+    in.tex_same = t->height.w0 == t->albedo.w0 && t->height.h0 == t->albedo.h0 && t->height.levels == t->albedo.levels;
+    in.ws_pow2 = a.ws_pow2 != 0;
+    const uint64_t span = (uint64_t)((const char*)(gb->emissive + (size_t)gb->w * gb->h) - (const char*)gb->depth);
+    in.one_rsrc = (const char*)gb->depth < (const char*)gb->diffuse && (const char*)gb->depth < (const char*)gb->specular
+               && (const char*)gb->depth < (const char*)gb->normals && (const char*)gb->depth < (const char*)gb->emissive && span < (1ull << 32);
+    in.plane_tracking = ctx->plane_tracking; in.clear_pending = gb->clear_pending; in.emissive_zero = gb->emissive_zero; in.escaped = gb->escaped;
+    in.viewport_full = view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0;
+    in.width_mult4 = gb->w % 4 == 0;
+    *lights_rc = VR_OK;
+    if (lit_req) {
+        const vr_image* hdr = lit_req->hdr;
+        in.request = lit_req->keep ? RASTER_REQ_KEEP : RASTER_REQ_LIT;
+        in.lit_inputs_ok = !lit_req->keep            // (vr_terrain_render_lit has checked its own)
+            || (lit_req->amb_top && lit_req->amb_bottom && hdr && hdr->data && lit_req->num_lights >= 0 && lit_req->num_lights <= kMaxLights
+                && (lit_req->num_lights == 0 || lit_req->lights) && hdr->ctx->device == ctx->device);
+        in.hdr_fits = in.lit_inputs_ok && (size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes;
+        // the light list: a keep request's only where everything else lets the pass fuse (else the lighting pass builds its own)
+        in.lit_plain = true;
+        if (lit_req->keep && !raster_plan(in).keep) in.lit_plain = false;
+        else {
+            bool extra = false;
+            memset(la, 0, sizeof(*la));
+            *lights_rc = vr_deferred_make_args(view, gb->w, gb->h, lit_req->lights, lit_req->num_lights, lit_req->amb_top, lit_req->amb_bottom, &la->da, &extra);
+            in.lit_plain = *lights_rc == VR_OK && !extra;
+        }
+    }
+    return in;
+}
+
+// The tile pass behind the three entry points below.  WHAT runs and what it does to the library's knowledge of the G-buffer is
+// raster_plan()'s decision (vr_raster_plan.h says when each variant applies); this function gathers the facts for it and
+// keeps the streams and events in order.
 static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_partition* part,
-                               const LitRequest* lit_req, bool* lit_done, int* earlier_out);
+                               const LitRequest* lit_req, bool* lit_done, int* earlier_out)
+{
+    int rc = check_render_inputs(t, view, gb, rp);
+    if (rc) return rc;
+    vr_context* ctx = t->ctx;
+    VR_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // what earlier frames' chains left in the host mirror: grows the scratch if due, and a device-side condition of a completed
+    // frame (too many nodes, a full work list) is returned - once - behind this frame's launches
+    const int earlier = vr_terrain_poll(t, true);
+    if (earlier && earlier != VR_ERR_OVERFLOW && earlier != VR_ERR_TOO_MANY_INSTANCES) return earlier;     // (the scratch could not grow)
+    RasterArgs a;
+    if ((rc = make_raster_args(t, view, rp, gb->w, gb->h, part, a))) return rc;
+    if ((rc = vr_terrain_reserve_bins(t, (size_t)a.rtx * a.rty / (size_t)(a.world > 1 ? a.world : 1)))) return rc;
+    a.bin_capacity = (uint32_t)t->bin_capacity;
+    const PartTables* pt = nullptr;       // this rank's raster tiles; unused (NULL) for the whole frame
+    if (a.world > 1 && (rc = vr_partition_tables(ctx, gb->w, gb->h, part, &pt))) return rc;
+    const int grid = pt ? pt->num_raster_tiles : a.rtx * a.rty;
+
+    LitArgs la;
+    int lights_rc;
+    const RasterPlanIn in = raster_plan_inputs(t, view, gb, rp, a, lit_req, &la, &lights_rc);
+    const RasterPlan plan = raster_plan(in);
+    const bool lit = lit_req && !lit_req->keep;
+    // a light list the lighting pass refuses is refused here, before anything is queued (a keep request goes on as the plain
+    // pass: the error is the lighting pass's to report - as is a partial viewport's, where that pass would look at it first)
+    if (lights_rc && lit && (in.viewport_full || (plan.fast && !plan.ranges))) return lights_rc;
+    if (lit_req && lit_req->keep && !plan.keep) lit_req = nullptr;           // from here on: a plain vr_terrain_render
+    if (plan.consume_pending_clear) a.assume_cleared = 1;
+    if ((rc = vr_gbuffer_settle_clear(gb, plan, s))) return rc;
+
+    // a set prepared for exactly this frame, else a free one (the oldest prepared set is given up if all are taken)
+    int gi = -1;
+    if (!rp->lock_view)
+        for (int i = 0; i < kGeoSets; i++)
+            if (i != t->cur && t->sets[i].prepared && prepared_matches(t->sets[i], view, rp, gb->w, gb->h, a)) { gi = i; break; }
+    const bool use_prepared = gi >= 0;
+    if (!use_prepared) gi = vr_terrain_pick_set(t);
+    GeoSet& g = t->sets[gi];
+    GeoSet& last = t->sets[t->cur];
+    g.prepared = false;
+    if (!use_prepared) {
+        GeoSet* sel = (rp->lock_view && last.have_selection) ? &last : nullptr;
+        if ((rc = launch_geometry(t, g, sel, view, rp, a, pt))) return rc;
+    }
+    t->cur = gi;
+    // the tile pass consumes verts + bins (a wait queued at prepare time counts only if it sits on the stream this pass runs on)
+    if (!(use_prepared && g.main_waited && g.main_wait_stream == s)) VR_HIP(hipStreamWaitEvent(s, g.ev_geo_done, 0));
+    g.main_waited = false;
+    const uint32_t spec_const = vr_specular_constant(ctx);               // terrain_ps.hlsl:76 -> SRGBA8
+    // vr_terrain_prepare's start hint: "the context's stream has reached this tile pass".  With dispatch-stamped events that
+    // is the stop event of whatever ran last on the stream (the previous frame's lighting pass); else an explicit record.
+    if (ctx->dispatch_events && ctx->last_stop) { t->start_hint = ctx->last_stop; t->start_hint_epoch = ctx->ev_epoch; t->raster_begin_recorded = true; }
+    else { VR_HIP(hipEventRecord(t->ev_raster_begin, s)); t->start_hint = t->ev_raster_begin; t->start_hint_epoch = 0; t->raster_begin_recorded = true; }
+    hipEvent_t pass_stop = nullptr;
+    if (grid > 0) {
+        // a depth-only tile pass (the shadow map's) is timed under its own id: it is an order of magnitude shorter than the
+        // G-buffer pass and must not be averaged with it
+        VrKernelScope ks(ctx, plan.fuse ? VR_K_RASTER_LIT : rp->depth_only ? VR_K_RASTER_DEPTH : VR_K_RASTER, s, true);
+        const int32_t* tiles = g.d_tile_order;            // this frame's tiles, longest bins first (k_scan)
+        if (lit && plan.fast && !plan.ranges) VR_REQUIRE(in.viewport_full, "view viewport must cover the G-buffer");
+        if (plan.fuse) {
+            la.lut_g = ctx->d_srgb_lut; la.hdr = (uint2*)lit_req->hdr->data;
+            // whoever still reads the image this pass overwrites (vr_frame_submit: the tone-map stage of two frames ago, on another stream)
+            if (plan.keep) { if (lit_req->hdr->read_pending) { VR_HIP(hipStreamWaitEvent(s, lit_req->hdr->ev_read_done, 0)); lit_req->hdr->read_pending = false; } }
+            else if (pt) {
+                VR_REQUIRE((size_t)pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= lit_req->hdr->capacity_bytes, "hdr_out is smaller than vr_partition_packed_bytes()");
+                la.tile_slot = pt->d_tile_slot; la.slot_base = pt->rank * pt->max_owned; la.owner_tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
+                la.da.tiles_x = la.owner_tiles_x;
+            } else VR_REQUIRE((size_t)gb->w * gb->h * 8 <= lit_req->hdr->capacity_bytes, "hdr_out is smaller than the frame");
+        }
+        if (lit_done) *lit_done = plan.fuse;
+        // nothing refuses the pass from here on: what the library knows of the G-buffer becomes what the pass leaves
+        uint8_t* region = nullptr;
+        if ((rc = vr_gbuffer_apply_plan(gb, plan, s, a.rank, a.world, &region))) return rc;
+#define VR_RASTER_ARGS a, t->height, t->albedo, g.d_verts, g.d_hard_tris, g.d_hard_first, \
+                           (const uint4*)g.d_recs, (uint32_t)t->cap_instances * (uint32_t)kTrisPerInst, g.d_tile_cursor, g.d_tile_offset, g.d_bin_entries, tiles, g.d_counters + C_CLASS0, \
+                           gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, ctx->d_srgb_thr, ctx->d_enc_tab, spec_const, plan.ranges ? gb->d_ranges : (uint2*)nullptr, region
+        const RasterKernel k = raster_kernel(plan.variant);
+        if (k.lit) VR_LAUNCH_TIMED(ks, k.lit, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
+        else VR_LAUNCH_TIMED(ks, k.plain, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, LitNone());
+#undef VR_RASTER_ARGS
+        if (ctx->dispatch_events && ks.e0 && ks.e1) pass_stop = ks.e1;        // stamped by the dispatch: complete when the tile pass is
+        if (plan.keep && lit_req->stop_out) *lit_req->stop_out = pass_stop;
+    }
+    if (pass_stop) { g.raster_done = pass_stop; g.raster_done_epoch = ctx->ev_epoch; }
+    else { VR_HIP(hipEventRecord(g.ev_raster_done, s)); g.raster_done = g.ev_raster_done; g.raster_done_epoch = 0; }
+    g.raster_recorded = true;
+    // chains prepared further ahead whose wait vr_terrain_prepare left for later: behind this tile pass
+    for (GeoSet& p : t->sets)
+        if (&p != &g && p.prepared && !(p.main_waited && p.main_wait_stream == s) && p.geo_recorded) { VR_HIP(hipStreamWaitEvent(s, p.ev_geo_done, 0)); p.main_waited = true; p.main_wait_stream = s; }
+    VR_HIP(hipGetLastError());
+    if (earlier_out) *earlier_out = earlier;
+    return VR_OK;
+}
 
 extern "C" VR_API int vr_terrain_render(vr_terrain* t, const vr_view* view, const vr_view* view_prev, vr_gbuffer* gb,
                                          const vr_render_params* rp, const vr_partition* part)
@@ -1981,157 +2133,6 @@ int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, c
     *fused = false; *fused_stop = nullptr;
     const int rc = terrain_render_impl(t, view, gb, rp, nullptr, &req, fused, &earlier);
     return rc ? rc : earlier;
-}
-
-static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_partition* part,
-                               const LitRequest* lit_req, bool* lit_done, int* earlier_out)
-{
-    int rc = check_render_inputs(t, view, gb, rp);
-    if (rc) return rc;
-    vr_context* ctx = t->ctx;
-    VR_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // what earlier frames' chains left in the host mirror: grows the scratch if due, and a device-side condition of a completed
-    // frame (too many nodes, a full work list) is returned - once - behind this frame's launches
-    const int earlier = vr_terrain_poll(t, true);
-    if (earlier && earlier != VR_ERR_OVERFLOW && earlier != VR_ERR_TOO_MANY_INSTANCES) return earlier;     // (the scratch could not grow)
-    RasterArgs a;
-    if ((rc = make_raster_args(t, view, rp, gb->w, gb->h, part, a))) return rc;
-    if ((rc = vr_terrain_reserve_bins(t, (size_t)a.rtx * a.rty / (size_t)(a.world > 1 ? a.world : 1)))) return rc;
-    a.bin_capacity = (uint32_t)t->bin_capacity;
-    const PartTables* pt = nullptr;       // this rank's raster tiles; unused (NULL) for the whole frame
-    if (a.world > 1 && (rc = vr_partition_tables(ctx, gb->w, gb->h, part, &pt))) return rc;
-    // RenderTargets::Clear is lazy under the plane-state tracking (vr_gbuffer::clear_pending): a shaded pass over the whole frame
-    // writes every pixel of every plane anyway and runs as "over a cleared target" - Clear + Render is one pass over the
-    // memory; any other pass (a rank's share, depth only, the fused variant) needs the clear values in memory first
-    // the fast variant: heightmap and albedo of one size (the albedo footprint shares the height taps' coordinates), a
-    // power-of-two world size, the five planes of the G-buffer within 4 GB (one buffer resource), filled and shaded
-    const bool same = t->height.w0 == t->albedo.w0 && t->height.h0 == t->albedo.h0 && t->height.levels == t->albedo.levels;
-    const uint64_t span = (uint64_t)((const char*)(gb->emissive + (size_t)gb->w * gb->h) - (const char*)gb->depth);
-    const bool one_rsrc = (const char*)gb->depth < (const char*)gb->diffuse && (const char*)gb->depth < (const char*)gb->specular
-                       && (const char*)gb->depth < (const char*)gb->normals && (const char*)gb->depth < (const char*)gb->emissive && span < (1ull << 32);
-    const bool fast = same && a.ws_pow2 && one_rsrc && !a.wireframe && !a.depth_only;
-    // A keep request is decided HERE, in front of everything the pass queues: where the KEEP flavour does not apply - or the
-    // lighting pass would refuse its inputs - the call goes on as the plain tile pass, the caller queues the lighting pass
-    // behind it as it always did and any error is that pass's to report.  The flavour exists for the whole frame on 32-pixel
-    // tiles over a target known cleared, with the emissive plane known zero and the streaming lighting pass's plain light list.
-    LitArgs la;
-    bool keep = false;
-    if (lit_req && lit_req->keep) {
-        const bool cleared = rp->assume_cleared || gb->clear_pending;          // (a pending clear is consumed by a whole-frame pass, below)
-        keep = part == nullptr && fast && a.tile_shift == 5 && cleared && !rp->depth_ranges
-            && ctx->plane_tracking && gb->emissive_zero && !gb->escaped
-            && view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0 && gb->w % 4 == 0
-            && lit_req->amb_top && lit_req->amb_bottom && lit_req->hdr && lit_req->hdr->data
-            && lit_req->num_lights >= 0 && lit_req->num_lights <= kMaxLights && (lit_req->num_lights == 0 || lit_req->lights)
-            && (size_t)gb->w * gb->h * 8 <= lit_req->hdr->capacity_bytes && lit_req->hdr->ctx->device == ctx->device;
-        if (keep) {
-            bool extra = false;
-            memset(&la, 0, sizeof(la));
-            keep = vr_deferred_make_args(view, gb->w, gb->h, lit_req->lights, lit_req->num_lights, lit_req->amb_top, lit_req->amb_bottom, &la.da, &extra) == VR_OK
-                && !extra;
-        }
-        if (!keep) lit_req = nullptr;           // from here on: a plain vr_terrain_render
-    }
-    if (gb->clear_pending) {
-        if (a.world <= 1 && !a.depth_only && (lit_req == nullptr || keep)) { a.assume_cleared = 1; gb->clear_pending = false; }
-        else if ((rc = vr_gbuffer_materialise(gb, s))) return rc;
-    }
-
-    // a set prepared for exactly this frame, else a free one (the oldest prepared set is given up if all are taken)
-    int gi = -1;
-    if (!rp->lock_view)
-        for (int i = 0; i < kGeoSets; i++)
-            if (i != t->cur && t->sets[i].prepared && prepared_matches(t->sets[i], view, rp, gb->w, gb->h, a)) { gi = i; break; }
-    const bool use_prepared = gi >= 0;
-    if (!use_prepared) gi = vr_terrain_pick_set(t);
-    GeoSet& g = t->sets[gi];
-    GeoSet& last = t->sets[t->cur];
-    g.prepared = false;
-    if (!use_prepared) {
-        GeoSet* sel = (rp->lock_view && last.have_selection) ? &last : nullptr;
-        if ((rc = launch_geometry(t, g, sel, view, rp, a, pt))) return rc;
-    }
-    t->cur = gi;
-    // the tile pass consumes verts + bins (a wait queued at prepare time counts only if it sits on the stream this pass runs on)
-    if (!(use_prepared && g.main_waited && g.main_wait_stream == s)) VR_HIP(hipStreamWaitEvent(s, g.ev_geo_done, 0));
-    g.main_waited = false;
-    const uint32_t spec_const = vr_specular_constant(ctx);               // terrain_ps.hlsl:76 -> SRGBA8
-    const int grid = pt ? pt->num_raster_tiles : a.rtx * a.rty;
-    // vr_terrain_prepare's start hint: "the context's stream has reached this tile pass".  With dispatch-stamped events that
-    // is the stop event of whatever ran last on the stream (the previous frame's lighting pass); else an explicit record.
-    if (ctx->dispatch_events && ctx->last_stop) { t->start_hint = ctx->last_stop; t->start_hint_epoch = ctx->ev_epoch; t->raster_begin_recorded = true; }
-    else { VR_HIP(hipEventRecord(t->ev_raster_begin, s)); t->start_hint = t->ev_raster_begin; t->start_hint_epoch = 0; t->raster_begin_recorded = true; }
-    hipEvent_t pass_stop = nullptr;
-    if (grid > 0) {
-        // a depth-only tile pass (the shadow map's) is timed under its own id: it is an order of magnitude shorter than the
-        // G-buffer pass and must not be averaged with it
-        VrKernelScope ks(ctx, rp->depth_only ? VR_K_RASTER_DEPTH : VR_K_RASTER, s, true);
-        const int32_t* tiles = g.d_tile_order;            // this frame's tiles, longest bins first (k_scan)
-        const bool depth = a.depth_only && !a.wireframe;
-        // the light tiles' depth ranges, if asked for: only from the fast variant over a target it fills completely
-        const bool ranges = rp->depth_ranges && fast && a.assume_cleared && !gb->escaped;
-        if (ranges) {
-            if ((rc = vr_gbuffer_ranges_prepare(gb, s))) return rc;
-            gb->ranges_state = vr_gbuffer::RANGES_VALID; gb->ranges_rank = a.rank; gb->ranges_world = a.world;
-        } else vr_gbuffer_touch(gb);
-        // plane-state tracking: the emissive plane holds zeros already and the fast variant would only write zeros again
-        const bool noemi = fast && ctx->plane_tracking && gb->emissive_zero && !gb->escaped;
-        auto kern = a.tile_shift == 5 ? pick_raster<32>(a.wireframe != 0, fast, depth, ranges, noemi) : pick_raster<64>(a.wireframe != 0, fast, depth, ranges, noemi);
-        // the fused variant: only where the fast variant applies and the light list is the streaming pass's plain case
-        bool fuse = keep;
-        if (keep) {
-            la.lut_g = ctx->d_srgb_lut; la.hdr = (uint2*)lit_req->hdr->data;
-            // whoever still reads the image this pass overwrites (vr_frame_submit: the tone-map stage of two frames ago, on another stream)
-            if (lit_req->hdr->read_pending) { VR_HIP(hipStreamWaitEvent(s, lit_req->hdr->ev_read_done, 0)); lit_req->hdr->read_pending = false; }
-        } else if (lit_req && fast && !ranges) {
-            bool extra = false;
-            memset(&la, 0, sizeof(la));
-            if ((rc = vr_deferred_make_args(view, gb->w, gb->h, lit_req->lights, lit_req->num_lights, lit_req->amb_top, lit_req->amb_bottom, &la.da, &extra))) return rc;
-            VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0,
-                       "view viewport must cover the G-buffer");
-            fuse = !extra && gb->w % 4 == 0;
-            if (fuse) {
-                la.lut_g = ctx->d_srgb_lut; la.hdr = (uint2*)lit_req->hdr->data;
-                if (pt) {
-                    VR_REQUIRE((size_t)pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= lit_req->hdr->capacity_bytes, "hdr_out is smaller than vr_partition_packed_bytes()");
-                    la.tile_slot = pt->d_tile_slot; la.slot_base = pt->rank * pt->max_owned; la.owner_tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
-                    la.da.tiles_x = la.owner_tiles_x;
-                } else VR_REQUIRE((size_t)gb->w * gb->h * 8 <= lit_req->hdr->capacity_bytes, "hdr_out is smaller than the frame");
-            }
-        }
-        if (lit_done) *lit_done = fuse;
-        // region states: kept by the fast variant on 32-pixel tiles; any other variant writes the planes without keeping them
-        uint8_t* region = nullptr;
-        if (fast && (!fuse || keep) && a.tile_shift == 5 && ctx->plane_tracking && !gb->escaped) { if ((rc = vr_gbuffer_region_prepare(gb, s, &region))) return rc; }
-        else gb->region_fill = 0;
-#define VR_RASTER_ARGS a, t->height, t->albedo, g.d_verts, g.d_hard_tris, g.d_hard_first, \
-                           (const uint4*)g.d_recs, (uint32_t)t->cap_instances * (uint32_t)kTrisPerInst, g.d_tile_cursor, g.d_tile_offset, g.d_bin_entries, tiles, g.d_counters + C_CLASS0, \
-                           gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, ctx->d_srgb_thr, ctx->d_enc_tab, spec_const, ranges ? gb->d_ranges : (uint2*)nullptr, region
-        if (fuse) {
-            ks.id = VR_K_RASTER_LIT;
-            if (keep) VR_LAUNCH_TIMED(ks, (k_raster<false, 32, RM_FAST, false, true, true, true>), dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
-            else if (a.tile_shift == 5) VR_LAUNCH_TIMED(ks, (k_raster<false, 32, RM_FAST, false, true, true>), dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
-            else VR_LAUNCH_TIMED(ks, (k_raster<false, 64, RM_FAST, false, true, true>), dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
-        } else
-        VR_LAUNCH_TIMED(ks, kern, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, LitNone());
-#undef VR_RASTER_ARGS
-        if (ctx->dispatch_events && ks.e0 && ks.e1) pass_stop = ks.e1;        // stamped by the dispatch: complete when the tile pass is
-        if (keep && lit_req->stop_out) *lit_req->stop_out = pass_stop;
-        // a shaded pass over a cleared target writes the emissive texel (0) of EVERY pixel of the frame, covered or not: from here
-        // on the plane is known zero again, whatever it held (a partitioned or keep-what-is-there pass writes zeros to some pixels:
-        // the state stays what it was)
-        if (!fuse && !noemi && !a.depth_only && a.assume_cleared && a.world <= 1) gb->emissive_zero = true;     // (the fused variant writes depth only)
-    }
-    if (pass_stop) { g.raster_done = pass_stop; g.raster_done_epoch = ctx->ev_epoch; }
-    else { VR_HIP(hipEventRecord(g.ev_raster_done, s)); g.raster_done = g.ev_raster_done; g.raster_done_epoch = 0; }
-    g.raster_recorded = true;
-    // chains prepared further ahead whose wait vr_terrain_prepare left for later: behind this tile pass
-    for (GeoSet& p : t->sets)
-        if (&p != &g && p.prepared && !(p.main_waited && p.main_wait_stream == s) && p.geo_recorded) { VR_HIP(hipStreamWaitEvent(s, p.ev_geo_done, 0)); p.main_waited = true; p.main_wait_stream = s; }
-    VR_HIP(hipGetLastError());
-    if (earlier_out) *earlier_out = earlier;
-    return VR_OK;
 }
 
 extern "C" VR_API int vr_debug_tile_order(vr_terrain* t, int32_t* out_tiles, uint32_t* out_bin_lengths, int32_t capacity, int32_t* out_count)
