@@ -195,6 +195,20 @@ def test_raster_plan_matches_the_transcribed_decisions_and_invariants(tmp_path):
     assert "786432 cases" in r.stdout, r.stdout[-400:]          # 2^16 bools x 2 worlds x 2 tile edges x 3 requests
 
 
+def test_devbuf_grow_is_all_or_nothing_at_every_failure_position(tmp_path):
+    """vr_devbuf.h compiles without HIP; a single grow and group grows of 1..15 buffers keep every pointer, capacity and live
+    block on a failure at any allocation (or a refusing quiesce) and free each old block once, behind quiesce, on success
+    (tests/host/devbuf_check.cpp)."""
+    import subprocess
+    exe = os.path.join(str(tmp_path), "devbuf_check")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "devbuf_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    assert "1152 cases" in r.stdout, r.stdout[-400:]            # single: 3 x 6 x 2 x 2; groups: 4 patterns x 2 x (N + 1), N = 1..15
+
+
 def _build_allgather_example(tmpdir):
     import subprocess
     exe = os.path.join(str(tmpdir), "frame_allgather_example")

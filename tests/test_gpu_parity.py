@@ -916,6 +916,88 @@ def test_frame_submit_passes_a_sticky_condition_on_and_still_queues_its_frame(sc
         hdr.close(); hdr_ref.close(); rt.close(); tp.close()
 
 
+@pytest.mark.parametrize("var,value", [("VR_SCRATCH_INITIAL_BINS", "20000"), ("VR_SCRATCH_INITIAL_NODES", "64")])
+def test_scratch_growth_refused_keeps_the_old_scratch_and_recovers(scene2048, oracle, gpu_ctx, monkeypatch, var, value):
+    """A growth of the scratch (bins; nodes) whose allocation fails (VR_ALLOC_FAIL_ABOVE): VR_ERR_OUT_OF_MEMORY once, naming
+    hipMalloc, and the terrain keeps the scratch it had - memory_bytes() unchanged, nothing queued.  Once memory can be had again
+    the usual sequence follows (truncated frame reported, scratch grown, complete frame).  Every return code and memory_bytes()
+    is looked at before the next frame is queued."""
+    import ctypes as C
+    h, a, ot = scene2048["h"], scene2048["a"], scene2048["ot"]
+    w, hh = 640, 360
+    v = vr.make_view(*CAMERAS[0], w, hh)
+    rp = vr.default_render_params(400.0, assume_cleared=1)
+    want = oracle.GBufferHost(w, hh)
+    assert ot.render(v, want, vr.default_render_params(400.0)) > 100
+    monkeypatch.setenv(var, value)
+    tp = vr.TerrainPass(gpu_ctx, params(2048)).Init(h, a)
+    monkeypatch.delenv(var)
+    rt = vr.RenderTargets(gpu_ctx).Init(w, hh)
+
+    def render():
+        rc = gpu_ctx.lib.vr_terrain_render(tp.handle, C.byref(v), C.byref(v), rt.handle, C.byref(rp), None)
+        err = gpu_ctx.lib.vr_last_error()
+        gpu_ctx.synchronize()
+        return rc, err
+    try:
+        assert render()[0] == vr.capi.VR_OK                      # truncated, not reported yet
+        assert not np.array_equal(rt.download("depth").view(np.uint32), want.depth.view(np.uint32))
+        before = tp.memory_bytes()
+        monkeypatch.setenv("VR_ALLOC_FAIL_ABOVE", "1")
+        rc, err = render()
+        monkeypatch.delenv("VR_ALLOC_FAIL_ABOVE")
+        assert rc == vr.capi.VR_ERR_OUT_OF_MEMORY and b"hipMalloc" in err, (rc, err)
+        assert tp.memory_bytes() == before
+        rcs = []
+        while len(rcs) < 4 and (not rcs or rcs[-1] != vr.capi.VR_OK):
+            rcs.append(render()[0])
+            assert rcs[-1] in (vr.capi.VR_OK, vr.capi.VR_ERR_OVERFLOW), rcs
+        assert rcs[-1] == vr.capi.VR_OK, rcs
+        _assert_gbuffer_equal(want, {k: rt.download(k) for k in ("depth", "diffuse", "specular", "normals", "emissive")}, f"{var}: after the growth")
+        assert tp.memory_bytes()["scratch"] > before["scratch"]
+    finally:
+        rt.close(); tp.close()
+
+
+def test_light_buffer_growth_refused_keeps_the_old_buffers(scene256, oracle, product_lib, monkeypatch):
+    """vr_deferred_light_tiled whose light buffers cannot grow (VR_ALLOC_FAIL_ABOVE) returns VR_ERR_OUT_OF_MEMORY and keeps
+    what it had: the 8-light frame from before comes out bit-identical (the list the device holds is still known), and the
+    1500-light frame, once memory can be had, meets the 1024-light test's bound against the oracle."""
+    w, h = 256, 144
+    v = vr.make_view(*scaled_camera(CAMERAS[0], 256), w, h)
+    gb = oracle.GBufferHost(w, h)
+    scene256["ot"].render(v, gb, vr.default_render_params(400.0))
+    few = _scene_lights(scene256, 8)
+    many = _scene_lights(scene256, 1501)[1:]                     # 1500 point lights
+    ref32 = oracle.deferred(v, gb, many, AMBIENT_TOP, AMBIENT_BOTTOM, f32=True)
+    ctx = vr.Context(0)                                          # its own: the shared context's light buffers have grown in other tests
+    rt = vr.RenderTargets(ctx).Init(w, h)
+    hdr = vr.HdrImage(ctx, w, h)
+    try:
+        for k, arr in (("depth", gb.depth), ("diffuse", gb.diffuse), ("specular", gb.specular), ("normals", gb.normals), ("emissive", gb.emissive)):
+            rt.upload(k, arr)
+        tiled = vr.TiledDeferredLightingPass(ctx)
+        tiled.Render(v, rt, few, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        kept = hdr.download().copy()
+        monkeypatch.setenv("VR_ALLOC_FAIL_ABOVE", "1")
+        with pytest.raises(vr.VrError) as e:
+            tiled.Render(v, rt, many, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        monkeypatch.delenv("VR_ALLOC_FAIL_ABOVE")
+        assert e.value.code == vr.capi.VR_ERR_OUT_OF_MEMORY and "hipMalloc" in str(e.value), e.value
+        tiled.Render(v, rt, few, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        assert np.array_equal(hdr.download(), kept)
+        tiled.Render(v, rt, many, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        tiled.Status()
+        got = oracle.half_to_float(hdr.download()).astype(np.float64)
+        for c in range(3):
+            rms = float(np.sqrt(np.mean((got[..., c] - ref32[..., c]) ** 2)))
+            print(f"1500 lights, channel {c}: RMS {rms:.3e}")
+            assert rms <= 1e-4, (c, rms)
+        assert np.abs(got[..., :3] - ref32[..., :3]).max() <= 2e-3 * max(1.0, float(ref32.max()))
+    finally:
+        hdr.close(); rt.close(); ctx.close()
+
+
 def test_too_many_instances_and_empty_selection(scene256, oracle, gpu_ctx):
     """MAX_INSTANCES overflow is an assert in the reference (TerrainPass.cpp:238): here an error code,
     with the first max_instances nodes still in order.  A camera that sees nothing selects nothing."""

@@ -769,12 +769,13 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
     VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0,
                "view viewport must cover the G-buffer");
     VR_HIP(hipSetDevice(ctx->device));
-    if ((size_t)num_lights > ctx->light_capacity) {
-        VR_HIP(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_lights); ctx->d_lights = nullptr; ctx->light_capacity = 0; ctx->h_lights_on_device.clear();
+    // (the buffers below grow through vr_grow: a growth that fails leaves the old buffer, its capacity and - d_lights - its contents)
+    const auto idle = [ctx]() -> int { VR_HIP(hipStreamSynchronize(ctx->stream)); return VR_OK; };
+    if ((size_t)num_lights * sizeof(DevLight) > ctx->light_bytes) {
         const size_t cap = (size_t)num_lights < 1024 ? 1024 : (size_t)num_lights;
-        VR_HIP(hipMalloc(&ctx->d_lights, cap * sizeof(DevLight)));
-        ctx->light_capacity = cap;
+        const int rc = vr_grow(&ctx->d_lights, &ctx->light_bytes, cap * sizeof(DevLight), idle);
+        if (rc) return rc;
+        ctx->h_lights_on_device.clear();
     }
     if (!ctx->d_flags) { VR_HIP(hipMalloc(&ctx->d_flags, 64)); VR_HIP(hipMemsetAsync(ctx->d_flags, 0, 64, ctx->stream)); }
     PlaneHints hints;                                         // (a reader: a pending clear happens now)
@@ -802,20 +803,10 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
     const int tx = (gb->w + kLightTile - 1) / kLightTile, ty = (gb->h + kLightTile - 1) / kLightTile;
     const int stride = (num_lights < kTileLightCap ? num_lights : kTileLightCap) + 1;
     const size_t words = (size_t)tx * ty * stride;
-    if (words > ctx->light_list_words) {
-        VR_HIP(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_light_lists); ctx->d_light_lists = nullptr; ctx->light_list_words = 0;
-        VR_HIP(hipMalloc(&ctx->d_light_lists, words * sizeof(uint32_t)));
-        ctx->light_list_words = words;
-    }
+    { const int rc = vr_grow(&ctx->d_light_lists, &ctx->light_list_bytes, words * sizeof(uint32_t), idle); if (rc) return rc; }
     // per macro tile: the lights that touch its box, in four regions (one per wave of k_light_cull)
     const size_t scratch_words = (size_t)macro_x * macro_y * (size_t)(((num_lights + 3) / 4) * 4) + 4;
-    if (scratch_words > ctx->macro_scratch_words) {
-        VR_HIP(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_macro_scratch); ctx->d_macro_scratch = nullptr; ctx->macro_scratch_words = 0;
-        VR_HIP(hipMalloc(&ctx->d_macro_scratch, scratch_words * sizeof(uint32_t)));
-        ctx->macro_scratch_words = scratch_words;
-    }
+    { const int rc = vr_grow(&ctx->d_macro_scratch, &ctx->macro_scratch_bytes, scratch_words * sizeof(uint32_t), idle); if (rc) return rc; }
     // The light tiles' depth ranges, if the tile pass that filled this G-buffer left them (for the same split) and nothing has
     // written to it since.  The culling stage consumes them (every entry it reads is reset), hence CLEAN afterwards - for a
     // split, only if this rank's share is non-empty (else nothing was written either).

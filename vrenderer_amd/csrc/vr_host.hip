@@ -18,6 +18,17 @@ void vr_set_error(const char* fmt, ...)
     va_end(ap);
 }
 extern "C" VR_API const char* vr_last_error(void) { return g_last_error; }
+// The growth paths' allocate function (vr_internal.h): hipMalloc; a failure leaves HIP's error state clear and its text in
+// vr_last_error.  VR_ALLOC_FAIL_ABOVE (environment, read at every call; tests): a request of more bytes fails without asking HIP.
+bool vr_dev_alloc(void** out, size_t bytes)
+{
+    const char* refuse = getenv("VR_ALLOC_FAIL_ABOVE");
+    const hipError_t e = refuse && bytes > strtoull(refuse, nullptr, 10) ? hipErrorOutOfMemory : hipMalloc(out, bytes);
+    if (e == hipSuccess) return true;
+    (void)hipGetLastError();
+    vr_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    return false;
+}
 extern "C" VR_API const char* vr_version(void) { return "vrterrain 0.1 (gfx950)"; }
 extern "C" VR_API uint32_t vr_build_experiments(void) { return kExpMask; }
 
@@ -503,8 +514,7 @@ static int gbuffer_region_prepare(vr_gbuffer* g, hipStream_t s, uint8_t** out)
 {
     const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
     if (!g->d_region) {
-        VR_HIP(hipMalloc(&g->d_region, (size_t)tiles * 4));
-        g->region_tiles = tiles;
+        if (!vr_dev_alloc((void**)&g->d_region, (size_t)tiles * 4)) return VR_ERR_OUT_OF_MEMORY;
         if (g->region_fill < 0) g->region_fill = 0;
     }
     if (g->region_fill >= 0) {
@@ -568,11 +578,10 @@ __global__ void k_fill_u32x2(uint2* p, size_t n, uint32_t x, uint32_t y)
 static int gbuffer_ranges_prepare(vr_gbuffer* g, hipStream_t s)
 {
     const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
-    if (!g->d_ranges || g->ranges_tiles != tiles) {
-        VR_HIP(hipStreamSynchronize(s));
-        (void)hipFree(g->d_ranges); g->d_ranges = nullptr; g->ranges_state = vr_gbuffer::RANGES_NONE;
-        VR_HIP(hipMalloc(&g->d_ranges, (size_t)tiles * sizeof(uint2)));
-        g->ranges_tiles = tiles;
+    if ((size_t)tiles * sizeof(uint2) > g->ranges_bytes) {
+        const int rc = vr_grow(&g->d_ranges, &g->ranges_bytes, (size_t)tiles * sizeof(uint2), [s]() -> int { VR_HIP(hipStreamSynchronize(s)); return VR_OK; });
+        if (rc) return rc;
+        g->ranges_state = vr_gbuffer::RANGES_NONE;
     }
     if (g->ranges_state != vr_gbuffer::RANGES_CLEAN) {
         hipLaunchKernelGGL(k_fill_u32x2, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, s, g->d_ranges, (size_t)tiles, 0x7f800000u, 0u);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vrterrain.h"
+#include "vr_devbuf.h"
 
 // ---- error plumbing -------------------------------------------------------------
 void vr_set_error(const char* fmt, ...);
@@ -23,6 +24,18 @@ void vr_set_error(const char* fmt, ...);
     } while (0)
 #define VR_REQUIRE(cond, msg)                                                         \
     do { if (!(cond)) { vr_set_error("%s:%d: %s", __FILE__, __LINE__, msg); return VR_ERR_INVALID_ARGUMENT; } } while (0)
+
+// ---- device buffers that grow (vr_devbuf.h) ----------------------------------------
+// Every buffer that a larger one replaces while the library runs goes through these: the new block is allocated first, `quiesce`
+// (the call site's stream synchronisations) runs in front of the free, and a failure - VR_ERR_OUT_OF_MEMORY, or quiesce's own
+// code - leaves pointer and capacity as they were.  vr_dev_alloc (vr_host.hip) is their one allocate function.
+bool vr_dev_alloc(void** out, size_t bytes);
+inline void vr_dev_free(void* p) { (void)hipFree(p); }
+inline int vr_grow_code(int rc) { return rc == kDevBufNoMemory ? VR_ERR_OUT_OF_MEMORY : rc; }
+template <class T, class Quiesce> int vr_grow(T** ptr, size_t* capacity_bytes, size_t bytes, Quiesce&& quiesce)
+{ return vr_grow_code(vr_devbuf_grow((void**)ptr, capacity_bytes, bytes, vr_dev_alloc, vr_dev_free, quiesce)); }
+template <size_t N, class Quiesce> int vr_grow_group(void** const (&slot)[N], const size_t (&bytes)[N], Quiesce&& quiesce)
+{ return vr_grow_code(vr_devbuf_grow_group(slot, bytes, vr_dev_alloc, vr_dev_free, quiesce)); }
 
 // ---- geometry constants -----------------------------------------------------------
 constexpr int kGrid = 32;                    // GRID_SIZE (TerrainPass.h:28)
@@ -178,9 +191,9 @@ struct vr_context {
     // complete' instead of waiting on an event that may since have been re-recorded for an unrelated kernel.
     uint64_t ev_epoch = 1;
     // light list of vr_deferred_light_tiled
-    DevLight* d_lights = nullptr; size_t light_capacity = 0; std::vector<DevLight> h_lights, h_lights_on_device;   // (the list d_lights holds)
-    uint32_t* d_macro_scratch = nullptr; size_t macro_scratch_words = 0;   // per macro tile: lights touching its box (k_light_cull's first stage)
-    uint32_t* d_light_lists = nullptr; size_t light_list_words = 0;    // per 32x32 light tile: count + light indices (k_light_cull)
+    DevLight* d_lights = nullptr; size_t light_bytes = 0; std::vector<DevLight> h_lights, h_lights_on_device;   // (the list d_lights holds)
+    uint32_t* d_macro_scratch = nullptr; size_t macro_scratch_bytes = 0;   // per macro tile: lights touching its box (k_light_cull's first stage)
+    uint32_t* d_light_lists = nullptr; size_t light_list_bytes = 0;    // per 32x32 light tile: count + light indices (k_light_cull)
     uint32_t* d_flags = nullptr;
     // per-kernel timing (vr_timing_*): event pairs recorded on `stream`
     int timing = 0;                      // 0 off, 1 every kernel (two event records each), 2 only the launches whose events the dispatch stamps
@@ -218,7 +231,7 @@ struct vr_gbuffer {
     // was asked for it (vr_render_params::depth_ranges) and consumed - and reset to "none" = (0x7f800000, 0) - by the tiled
     // lighting pass's culling stage, which then need not read the depth plane a second time.
     uint2* d_ranges = nullptr;
-    int ranges_tiles = 0;
+    size_t ranges_bytes = 0;
     enum { RANGES_NONE = 0, RANGES_CLEAN, RANGES_VALID, RANGES_DIRTY };
     int ranges_state = RANGES_NONE;          // CLEAN: every entry "none"; VALID: the last writer of the G-buffer left them; DIRTY: stale
     int ranges_rank = 0, ranges_world = 1;   // the screen-tile split they were rendered for
@@ -238,7 +251,6 @@ struct vr_gbuffer {
     // specular plane - the planes' contents are what they would be anyway.  region_fill: -1 = the device array is current,
     // else the byte it has to be filled with before its next use (0 after anything foreign wrote a plane, kRegionClear after a clear).
     uint8_t* d_region = nullptr;
-    int region_tiles = 0;
     int region_fill = 0;
     // RenderTargets::Clear (vr_gbuffer_clear) under the tracking is LAZY: the next tile pass that writes every pixel of every plane
     // anyway (whole frame, shaded) runs as "over a cleared target" and the 929 MB of clear values are never written twice;

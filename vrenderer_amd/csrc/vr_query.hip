@@ -379,18 +379,10 @@ static int reserve_stage(vr_terrain* t, size_t bytes)
     if (bytes <= t->query_stage_bytes) return VR_OK;
     size_t want = t->query_stage_bytes ? t->query_stage_bytes * 2 : (size_t)1 << 16;
     while (want < bytes) want *= 2;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess && want > bytes) { (void)hipGetLastError(); want = bytes; e = hipMalloc(&p, want); }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        vr_set_error("terrain query: %zu bytes of staging memory: %s", want, hipGetErrorString(e));
-        return VR_ERR_OUT_OF_MEMORY;                                     // the terrain keeps what it had
-    }
-    VR_HIP(hipStreamSynchronize(t->ctx->stream));
-    (void)hipFree(t->d_query_stage);
-    t->d_query_stage = p; t->query_stage_bytes = want;
-    return VR_OK;
+    const auto idle = [t]() -> int { VR_HIP(hipStreamSynchronize(t->ctx->stream)); return VR_OK; };
+    int rc = vr_grow(&t->d_query_stage, &t->query_stage_bytes, want, idle);
+    if (rc == VR_ERR_OUT_OF_MEMORY && want > bytes) rc = vr_grow(&t->d_query_stage, &t->query_stage_bytes, bytes, idle);
+    return rc;                                                           // (on failure the terrain keeps what it had)
 }
 
 void vr_query_release(vr_terrain* t)

@@ -1815,14 +1815,10 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
     }
     const int n_tiles = a.rtx * a.rty;
     if (n_tiles > g.scratch_tiles) {
-        VR_HIP(hipStreamSynchronize(gs));
-        VR_HIP(hipStreamSynchronize(s));
-        (void)hipFree(g.d_tile_count); (void)hipFree(g.d_tile_offset); (void)hipFree(g.d_tile_cursor); (void)hipFree(g.d_tile_order);
-        g.d_tile_count = g.d_tile_offset = g.d_tile_cursor = nullptr; g.d_tile_order = nullptr; g.scratch_tiles = 0;
-        VR_HIP(hipMalloc(&g.d_tile_count, sizeof(uint32_t) * n_tiles));
-        VR_HIP(hipMalloc(&g.d_tile_offset, sizeof(uint32_t) * n_tiles));
-        VR_HIP(hipMalloc(&g.d_tile_cursor, sizeof(uint32_t) * n_tiles));
-        VR_HIP(hipMalloc(&g.d_tile_order, sizeof(int32_t) * n_tiles * kScanClasses));      // a region per bin-length class
+        void** const slot[4] = { (void**)&g.d_tile_count, (void**)&g.d_tile_offset, (void**)&g.d_tile_cursor, (void**)&g.d_tile_order };
+        const size_t bytes[4] = { sizeof(uint32_t) * n_tiles, sizeof(uint32_t) * n_tiles, sizeof(uint32_t) * n_tiles,
+                                  sizeof(int32_t) * n_tiles * kScanClasses };               // (the order: a region per bin-length class)
+        if ((rc = vr_grow_group(slot, bytes, [gs, s]() -> int { VR_HIP(hipStreamSynchronize(gs)); VR_HIP(hipStreamSynchronize(s)); return VR_OK; }))) return rc;
         VR_HIP(hipMemsetAsync(g.d_tile_count, 0, sizeof(uint32_t) * n_tiles, gs));   // k_scan re-zeroes it every frame
         VR_HIP(hipMemsetAsync(g.d_tile_cursor, 0, sizeof(uint32_t) * n_tiles, gs));
         VR_HIP(hipMemsetAsync(g.d_tile_offset, 0, sizeof(uint32_t) * n_tiles, gs));

@@ -479,30 +479,34 @@ static void free_scratch(vr_terrain* t)
         g.d_verts = nullptr; g.d_rect = nullptr; g.d_recs = nullptr; g.d_hard_first = nullptr; g.d_bin_entries = nullptr;
     }
 }
-static int alloc_scratch(vr_terrain* t, int cap)
+// A scratch of `cap` nodes and at least `bin_want` bin entries replaces the one there is - all fifteen buffers or none (vr_grow_group:
+// the old ones are given up, behind the streams that use them, only once the new ones exist; a failure changes nothing).
+static int alloc_scratch(vr_terrain* t, int cap, size_t bin_want)
 {
-    free_scratch(t);
     const size_t mi = (size_t)cap, fixed = (size_t)t->p.max_instances * (sizeof(uint32_t) + sizeof(vr_instance)) + 64 * sizeof(uint32_t)
                     + kSelScratchWords * sizeof(uint32_t) + (size_t)t->hard_cap * (sizeof(uint32_t) + 4 * sizeof(HardTriRec));
-    t->bytes_scratch = (uint64_t)fixed * kGeoSets;
     // (triangle, tile) pairs: an 8K frame of ~300 nodes has ~0.3 M, a 1080p frame ~0.6 M; 1 M per 1024 nodes and never fewer
     // - or what the frames seen so far asked for (a large target on 32-pixel tiles: every triangle lands in more bins)
-    t->bin_capacity = ((size_t)1 << 20) * ((mi + 1023) / 1024);
-    if (const char* e = getenv("VR_SCRATCH_INITIAL_BINS")) { const long v = atol(e); if (v >= 1024) t->bin_capacity = (size_t)v; }   // (tests: force the growth path)
-    if (t->bin_want > t->bin_capacity) t->bin_capacity = t->bin_want;
-#define VR_ALLOC(ptr, bytes) do { hipError_t e_ = hipMalloc(&(ptr), (bytes)); if (e_ != hipSuccess) { \
-        vr_set_error("hipMalloc(%zu) failed: %s", (size_t)(bytes), hipGetErrorString(e_)); return VR_ERR_OUT_OF_MEMORY; } \
-        t->bytes_scratch += (uint64_t)(bytes); } while (0)
-    for (GeoSet& g : t->sets) {
-        VR_ALLOC(g.d_verts, (mi * kVertsPerInst + t->extra_vert_cap) * sizeof(DevVert));
-        VR_ALLOC(g.d_rect, mi * kTrisPerInst * sizeof(uint64_t));
-        VR_ALLOC(g.d_recs, (mi * kTrisPerInst + (size_t)t->hard_cap * 4) * kRecGroups * sizeof(uint4));
-        VR_ALLOC(g.d_hard_first, mi * kTrisPerInst * sizeof(uint32_t));
-        VR_ALLOC(g.d_bin_entries, t->bin_capacity * sizeof(TileEntry));
-        g.prepared = false;                   // geometry built for the old buffers is gone (a selection lives in the fixed part: kept)
+    size_t bins = ((size_t)1 << 20) * ((mi + 1023) / 1024);
+    if (const char* e = getenv("VR_SCRATCH_INITIAL_BINS")) { const long v = atol(e); if (v >= 1024) bins = (size_t)v; }   // (tests: force the growth path)
+    if (bin_want > bins) bins = bin_want;
+    const size_t per_set[5] = { (mi * kVertsPerInst + t->extra_vert_cap) * sizeof(DevVert), mi * kTrisPerInst * sizeof(uint64_t),
+                                (mi * kTrisPerInst + (size_t)t->hard_cap * 4) * kRecGroups * sizeof(uint4), mi * kTrisPerInst * sizeof(uint32_t),
+                                bins * sizeof(TileEntry) };
+    void** slot[5 * kGeoSets]; size_t bytes[5 * kGeoSets]; uint64_t total = (uint64_t)fixed * kGeoSets;
+    for (int i = 0; i < kGeoSets; i++) {
+        GeoSet& g = t->sets[i];
+        void** const of_set[5] = { (void**)&g.d_verts, (void**)&g.d_rect, (void**)&g.d_recs, (void**)&g.d_hard_first, (void**)&g.d_bin_entries };
+        for (int j = 0; j < 5; j++) { slot[5 * i + j] = of_set[j]; bytes[5 * i + j] = per_set[j]; total += per_set[j]; }
     }
-#undef VR_ALLOC
-    t->cap_instances = cap;
+    const int rc = vr_grow_group(slot, bytes, [t]() -> int {
+        for (hipStream_t gs : t->geo_streams) VR_HIP(hipStreamSynchronize(gs));
+        VR_HIP(hipStreamSynchronize(t->ctx->stream));
+        return VR_OK;
+    });
+    if (rc) return rc;
+    t->cap_instances = cap; t->bin_capacity = bins; t->bin_want = bin_want; t->bytes_scratch = total;
+    for (GeoSet& g : t->sets) g.prepared = false;    // geometry built for the old buffers is gone (a selection lives in the fixed part: kept)
     return VR_OK;
 }
 
@@ -515,11 +519,8 @@ int vr_terrain_reserve_bins(vr_terrain* t, size_t tiles)
     if (est <= t->bin_capacity) return VR_OK;
     size_t b = t->bin_capacity ? t->bin_capacity : ((size_t)1 << 20);
     while (b < est) b *= 2;
-    t->bin_want = b;
     VR_HIP(hipSetDevice(t->ctx->device));
-    for (hipStream_t gs : t->geo_streams) VR_HIP(hipStreamSynchronize(gs));
-    VR_HIP(hipStreamSynchronize(t->ctx->stream));
-    return alloc_scratch(t, t->cap_instances);
+    return alloc_scratch(t, t->cap_instances, b);       // (VR_ERR_OUT_OF_MEMORY: the bins stay as they are, and say so)
 }
 
 int vr_terrain_poll(vr_terrain* t, bool report)
@@ -545,18 +546,14 @@ int vr_terrain_poll(vr_terrain* t, bool report)
         int want = t->cap_instances;
         while (want < max_i && (size_t)t->high_water * 2 > (size_t)want) want *= 2;
         if (want > max_i) want = max_i;
-        if (grow_bins) { size_t b = t->bin_capacity; while (b < t->bin_high_water * 2) b *= 2; t->bin_want = b; }
+        size_t bin_want = t->bin_want;
+        if (grow_bins) { bin_want = t->bin_capacity; while (bin_want < t->bin_high_water * 2) bin_want *= 2; }
         VR_HIP(hipSetDevice(t->ctx->device));
-        for (hipStream_t gs : t->geo_streams) VR_HIP(hipStreamSynchronize(gs));
-        VR_HIP(hipStreamSynchronize(t->ctx->stream));
-        const int had = t->cap_instances;
-        int rc = alloc_scratch(t, want);
+        const int rc = alloc_scratch(t, want, bin_want);
         if (rc) {
-            // the larger scratch does not fit: back to the old size (frames that need more stay truncated and reported)
-            t->bin_want = 0;
-            const int rc2 = alloc_scratch(t, had);
-            t->high_water = 0; t->bin_high_water = 0;
-            return rc2 ? rc2 : rc;
+            // the larger scratch does not fit: the old one is still there (frames that need more stay truncated and reported)
+            t->bin_want = 0; t->high_water = 0; t->bin_high_water = 0;
+            return rc;
         }
     }
     if (report && t->sticky_error) {
@@ -617,11 +614,11 @@ extern "C" VR_API int vr_terrain_create(vr_context* ctx, const vr_terrain_params
     memset(t->h_status, 0, kGeoSets * 8 * sizeof(uint32_t));
     VR_HIP(hipHostGetDevicePointer((void**)&t->d_status, t->h_status, 0));
     {   // what the scratch holds to begin with: 1024 nodes (a 2048^2 world selects 300-600), or everything (VR_OPT_SCRATCH_WORST_CASE);
-        // VR_SCRATCH_INITIAL_NODES (environment) lets a test start smaller and watch it grow
+        // VR_SCRATCH_INITIAL_NODES (environment) lets a test start smaller and watch it grow, VR_ALLOC_FAIL_ABOVE (vr_dev_alloc) refuse a growth
         int initial = 1024;
         if (const char* e = getenv("VR_SCRATCH_INITIAL_NODES")) { const int v = atoi(e); if (v >= 1) initial = v; }
         if (ctx->scratch_worst_case || initial > (int)mi) initial = (int)mi;
-        if ((rc = alloc_scratch(t, initial))) return rc;
+        if ((rc = alloc_scratch(t, initial, 0))) return rc;
     }
     for (GeoSet& g : t->sets) {
         VR_HIP(hipMemsetAsync(g.d_counters, 0, 64 * sizeof(uint32_t), ctx->stream));
