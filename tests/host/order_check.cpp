@@ -1,0 +1,556 @@
+// Check of the cross-stream ordering protocol (vrenderer_amd/csrc/vr_order.h) over generated sequences of API calls:
+//  (a) SPECIFICATION: a flat transcription of the ordering code as the .hip files held it before the header existed (commit
+//      a8c67ef; the numbers in comments are that commit's lines of vr_raster.hip, vr_select.hip and vr_frame.hip), written as
+//      that code wrote it.  It and the protocol drive the same recording `ops`; for every sequence the two traces of
+//      (record | wait, stream, event) must be equal, operation for operation.  The intended differences are switches of the
+//      transcription (struct Intended), each beside the parent's line it changes; the comparison is against the transcription
+//      with all of them on, and exact.
+//  (b) HAPPENS-BEFORE MODEL of HIP's stream semantics: one vector clock per stream; a record snapshots the stream's clock into the
+//      event, a wait joins it, a dispatch-stamped event is a snapshot right behind its launch; a host-side synchronise joins the
+//      stream's (event's) clock into everything queued later.  Every kernel that touches a set's selection, a set's vertices and
+//      bins, the node heights or an HDR image registers a read or a write; a conflicting pair (write/write, read/write) that the
+//      clocks do not order is a failure.  The protocol must pass; where the plain transcription does not, that is a finding
+//      about the parent, and one of the intended differences must be what repairs it.
+//  (c) every sequence up to kExhaustive calls, then a fixed-seed random sample of longer ones.
+// What the model is not: the HIP runtime (it assumes the documented semantics of the two calls), or the 64-entry ring the
+// stamped events of ordinary runs come from (every stamped launch gets a fresh event here).
+//   order_check                 the check; prints sequences and failures
+//   order_check --drop-each     is the model alive?  The transcription (intended differences on) loses one wait site at a time;
+//                               prints for each site in how many sequences (b) reports it
+// Plain C++17, no GPU: g++ -std=c++17 -Wall -Werror -I vrenderer_amd/csrc tests/host/order_check.cpp
+#include "vr_order.h"
+
+#include <array>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+// ---- the world: trace, clocks, accesses -----------------------------------------------------------
+enum Stream { S_NONE = 0, G0, G1, M0, M1, TM, N_STREAMS };       // two geometry streams, the context's (a host may switch), the tone mapper's
+static const char* const kStreamName[N_STREAMS] = { "-", "geo0", "geo1", "main0", "main1", "tonemap" };
+enum Res { SEL0, SEL1, SEL2, GEO0, GEO1, GEO2, HEIGHTS, IMG0, IMG1, N_RES };
+static const char* const kResName[N_RES] = { "selection 0", "selection 1", "selection 2", "verts+bins 0", "verts+bins 1", "verts+bins 2",
+                                             "node heights", "image 0", "image 1" };
+// own events (0 = none); stamped events follow
+enum { EV_GEO_DONE = 1, EV_RASTER_DONE = 4, EV_SEL_READ = 7, EV_MAIN_DEP = 10, EV_SEL_COPY, EV_RASTER_BEGIN, EV_WRITTEN, EV_READ_DONE = 15, EV_FIRST_STAMPED = 17,
+       N_EVENTS = 96 };
+typedef std::array<uint32_t, N_STREAMS> Clock;
+static void join(Clock& a, const Clock& b) { for (int i = 0; i < N_STREAMS; i++) if (b[i] > a[i]) a[i] = b[i]; }
+
+struct Op { uint8_t wait, stream; uint16_t event; };
+struct World {
+    std::vector<Op> trace;
+    Clock clk[N_STREAMS], host, ev[N_EVENTS];
+    bool ev_recorded[N_EVENTS];
+    int next_event;
+    struct Acc { Clock c; int stream; };
+    Acc last_write[N_RES]; bool has_write[N_RES];
+    Acc reads[N_RES][64]; int n_reads[N_RES];
+    int unordered;                   // conflicting pairs the clocks do not order (+ waits on an event never recorded)
+    std::string first;
+    int drop_site;                   // the transcription's wait site that is left out (0: none)
+
+    void reset(int drop)
+    {
+        trace.clear();
+        memset(clk, 0, sizeof(clk)); memset(&host, 0, sizeof(host)); memset(ev, 0, sizeof(ev)); memset(ev_recorded, 0, sizeof(ev_recorded));
+        memset(has_write, 0, sizeof(has_write)); memset(n_reads, 0, sizeof(n_reads));
+        next_event = EV_FIRST_STAMPED; unordered = 0; first.clear(); drop_site = drop;
+    }
+    void op_on(int s) { join(clk[s], host); }                    // whatever the host waited for is before anything it queues later
+    int record(int e, int s) { op_on(s); ev[e] = clk[s]; ev_recorded[e] = true; trace.push_back({ 0, (uint8_t)s, (uint16_t)e }); return 0; }
+    int wait(int s, int e)
+    {
+        op_on(s);
+        if (!ev_recorded[e]) fail("a wait on an event that was never recorded");
+        join(clk[s], ev[e]);
+        trace.push_back({ 1, (uint8_t)s, (uint16_t)e });
+        return 0;
+    }
+    void kernel(int s) { op_on(s); clk[s][s]++; }
+    int stamp(int s) { const int e = next_event++; ev[e] = clk[s]; ev_recorded[e] = true; return e; }     // right behind the kernel just queued
+    void sync_stream(int s) { join(host, clk[s]); }
+    void sync_event(int e) { join(host, ev[e]); }
+    void host_orders(int later, int earlier) { join(clk[later], clk[earlier]); }      // what a host owes when it moves work to another stream
+    void fail(const std::string& what) { if (!unordered++) first = what; }
+    void access(int r, bool write, int s)                        // by the kernel just queued on s
+    {
+        const Clock& now = clk[s];
+        auto check = [&](const Acc& a, const char* kind) {
+            if (a.c[a.stream] > now[a.stream])
+                fail(std::string(kResName[r]) + ": " + kind + " on " + kStreamName[a.stream] + " not ordered before " + (write ? "write" : "read") + " on " + kStreamName[s]);
+        };
+        if (has_write[r]) check(last_write[r], "write");
+        if (write) {
+            for (int i = 0; i < n_reads[r]; i++) check(reads[r][i], "read");
+            n_reads[r] = 0; has_write[r] = true; last_write[r] = { now, s };
+        } else if (n_reads[r] < 64) reads[r][n_reads[r]++] = { now, s };
+        else fail("too many reads between two writes for the model");
+    }
+};
+struct Ops { World* w; int record(int e, int s) const { return w->record(e, s); } int wait(int s, int e) const { return w->wait(s, e); } };
+
+// ---- what the .hip files decide (the same for both protocols): the context and the terrain's set bookkeeping ---------------
+struct Host {
+    int main = M0;
+    bool async_geometry = true, dispatch_events = true, frame_fusion = true;
+    int timing = 0;                   // 0 or 2 (level 2: only the stamped launches are timed; level 1 synchronises more)
+    uint64_t ev_epoch = 1;
+    int last_stop = 0;
+    std::vector<int> pooled_end;      // stop events taken from the timing pool since it was last recycled
+    unsigned not_stamped = 0;         // bit k: the k-th stamped launch from now gets no events (the ring or pool gave none)
+    bool launched = false;
+    bool prepared[3] = { false, false, false }, have_selection[3] = { false, false, false };
+    int prep_view[3] = { 0, 0, 0 }; uint64_t prep_serial[3] = { 0, 0, 0 }, prep_counter = 0;
+    int cur = 0, frame_no = 0;
+    unsigned geo_turn = 0;
+    int pick_set() const              // vr_terrain_pick_set
+    {
+        int best = -1;
+        for (int i = 0; i < 3; i++) {
+            if (i == cur) continue;
+            if (!prepared[i]) return i;
+            if (best < 0 || prep_serial[i] < prep_serial[best]) best = i;
+        }
+        return best;
+    }
+    // VrKernelScope(attach) + VR_LAUNCH_TIMED on the context's stream: the kernel, and its stop event if the dispatch stamped one
+    int stamped_launch(World& w)
+    {
+        const bool events = (timing != 0 || dispatch_events) && !(not_stamped & 1u);
+        not_stamped >>= 1; launched = true;
+        w.kernel(main);
+        if (!events) return 0;
+        const int e1 = w.stamp(main);
+        if (timing) pooled_end.push_back(e1);
+        last_stop = e1;
+        return e1;
+    }
+    int stop_of(int e1) const { return dispatch_events ? e1 : 0; }      // VrKernelScope::stop
+};
+static const int kGeo[2] = { G0, G1 };
+
+// ---- (a) the parent's ordering code ----------------------------------------------------------------
+struct Intended {
+    bool own_stop;          // vr_frame_submit waits for the lighting pass's OWN stop event, or records; never ctx->last_stop
+    bool heights_behind;    // the node-height update runs behind every chain queued so far (found by (b): see main)
+    bool common_order;      // vr_terrain_select queues its waits in launch_geometry's order (the permitted reorder)
+};
+enum Site { W_LG_CHAIN = 1, W_LG_SEL_READ, W_LG_RASTER, W_LG_MAIN_DEP, W_LG_SEL_COPY, W_PREP_HINT, W_PREP_NOW, W_TILE_CHAIN, W_KEEP_READER, W_AHEAD,
+            W_SEL_MAIN_DEP, W_SEL_CHAIN, W_SEL_SEL_READ, W_SEL_RASTER, W_FRAME_READER, W_FRAME_WRITTEN, W_HEIGHTS_CHAIN, N_SITES };
+static const char* const kSiteName[N_SITES] = { "", "launch_geometry: previous chain", "launch_geometry: lock_view copy out of the set", "launch_geometry: tile pass",
+    "launch_geometry: main dependency", "launch_geometry: lock_view source complete", "prepare: start hint", "prepare: context's stream waits now",
+    "tile pass: chain", "fused tile pass: image's reader", "tile pass: deferred waits of sets prepared ahead", "select: main dependency", "select: previous chain",
+    "select: lock_view copy out of the set", "select: tile pass", "frame: image's reader", "frame: tone-map stage behind the writer",
+    "heights: chains queued so far (intended difference)" };
+
+struct Parent {
+    World& w; Host& h; Intended in;
+    struct Set { int ev_geo_done, ev_raster_done, raster_done = 0; uint64_t raster_done_epoch = 0; bool raster_recorded = false, geo_recorded = false;
+                 int ev_sel_read; bool sel_read_pending = false, main_waited = false; int main_wait_stream = 0, stream = G0; bool main_dep_pending = false; } sets[3];
+    int ev_sel_copy = EV_SEL_COPY, ev_main_dep = EV_MAIN_DEP, ev_raster_begin = EV_RASTER_BEGIN;
+    bool raster_begin_recorded = false; int start_hint = 0; uint64_t start_hint_epoch = 0;
+    struct Image { int ev_written, ev_read_done; bool read_pending = false; } img[2];
+    Parent(World& w_, Host& h_, Intended in_) : w(w_), h(h_), in(in_)
+    {
+        for (int i = 0; i < 3; i++) { sets[i].ev_geo_done = EV_GEO_DONE + i; sets[i].ev_raster_done = EV_RASTER_DONE + i; sets[i].ev_sel_read = EV_SEL_READ + i; }
+        for (int i = 0; i < 2; i++) { img[i].ev_written = EV_WRITTEN + i; img[i].ev_read_done = EV_READ_DONE + i; }
+    }
+    void R(int e, int s) { w.record(e, s); }
+    void W(int site, int s, int e) { if (site != w.drop_site) w.wait(s, e); }
+    int stream(int gi) const { return sets[gi].stream; }
+
+    void begin_chain(int gi)                                  // launch_geometry, vr_raster.hip
+    {
+        Set& g = sets[gi];
+        /* 1787 */ g.stream = kGeo[h.geo_turn++ & 1u];
+        /* 1788 */ g.main_waited = false;
+        /* 1789 */ const int s = h.main, gs = g.stream;
+        /* 1790 */ if (!h.async_geometry) {
+        /* 1791 */     R(ev_main_dep, s);
+        /* 1792 */     g.main_dep_pending = true;
+                   }
+        /* 1795 */ if (g.geo_recorded) W(W_LG_CHAIN, gs, g.ev_geo_done);
+        /* 1796 */ if (g.sel_read_pending) { W(W_LG_SEL_READ, gs, g.ev_sel_read); g.sel_read_pending = false; }
+        /* 1798 */ if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == h.ev_epoch)) W(W_LG_RASTER, gs, g.raster_done);
+        /* 1799 */ if (g.main_dep_pending) { W(W_LG_MAIN_DEP, gs, ev_main_dep); g.main_dep_pending = false; }
+    }
+    template <class Copy> void copy_selection(int gi, int from, Copy&& copy)
+    {
+        Set& g = sets[gi]; Set* selection_from = &sets[from]; const int gs = g.stream;
+        /* 1806 */ R(ev_sel_copy, selection_from->stream);
+        /* 1807 */ W(W_LG_SEL_COPY, gs, ev_sel_copy);
+        /* 1808-1810 */ copy();
+        /* 1812 */ R(selection_from->ev_sel_read, gs);
+        /* 1813 */ selection_from->sel_read_pending = true;
+    }
+    void end_chain(int gi)
+    {
+        Set& g = sets[gi];
+        /* 1852 */ R(g.ev_geo_done, g.stream);
+        /* 1853 */ g.geo_recorded = true;
+    }
+    void prepare_start()                                      // vr_terrain_prepare
+    {
+        /* 1925 */ if (raster_begin_recorded && (start_hint_epoch == 0 || start_hint_epoch == h.ev_epoch))
+        /* 1926 */     W(W_PREP_HINT, kGeo[h.geo_turn & 1u], start_hint);
+    }
+    void prepare_wait(int gi)
+    {
+        Set& g = sets[gi];
+        /* 1936 */ bool other_prepared = false;
+        /* 1937 */ for (int p = 0; p < 3; p++) other_prepared |= (p != gi) && h.prepared[p];
+        /* 1938 */ if (other_prepared) g.main_waited = false;
+        /* 1939 */ else { W(W_PREP_NOW, h.main, g.ev_geo_done); g.main_waited = true; g.main_wait_stream = h.main; }
+    }
+    void tile_pass_begin(int gi, bool use_prepared)           // terrain_render_impl
+    {
+        Set& g = sets[gi]; const int s = h.main;
+        /* 2040 */ if (!(use_prepared && g.main_waited && g.main_wait_stream == s)) W(W_TILE_CHAIN, s, g.ev_geo_done);
+        /* 2041 */ g.main_waited = false;
+        /* 2045 */ if (h.dispatch_events && h.last_stop) { start_hint = h.last_stop; start_hint_epoch = h.ev_epoch; raster_begin_recorded = true; }
+        /* 2046 */ else { R(ev_raster_begin, s); start_hint = ev_raster_begin; start_hint_epoch = 0; raster_begin_recorded = true; }
+    }
+    void keep_writer_begins(int im)
+    {
+        /* 2057 */ if (img[im].read_pending) { W(W_KEEP_READER, h.main, img[im].ev_read_done); img[im].read_pending = false; }
+    }
+    void tile_pass_launched(int gi, int pass_stop)            // pass_stop: 2075
+    {
+        Set& g = sets[gi]; const int s = h.main;
+        /* 2078 */ if (pass_stop) { g.raster_done = pass_stop; g.raster_done_epoch = h.ev_epoch; }
+        /* 2079 */ else { R(g.ev_raster_done, s); g.raster_done = g.ev_raster_done; g.raster_done_epoch = 0; }
+        /* 2080 */ g.raster_recorded = true;
+        /* 2082 */ for (int pi = 0; pi < 3; pi++) { Set& p = sets[pi];
+        /* 2083 */     if (pi != gi && h.prepared[pi] && !(p.main_waited && p.main_wait_stream == s) && p.geo_recorded) { W(W_AHEAD, s, p.ev_geo_done); p.main_waited = true; p.main_wait_stream = s; } }
+    }
+    void select_begin(int gi)                                 // vr_terrain_select, vr_select.hip
+    {
+        Set& g = sets[gi];
+        /* 750 */ g.stream = kGeo[h.geo_turn++ & 1u];
+        if (!in.common_order)
+        /* 751 */ if (g.main_dep_pending) { W(W_SEL_MAIN_DEP, g.stream, ev_main_dep); g.main_dep_pending = false; }
+        /* 753 */ if (g.geo_recorded) W(W_SEL_CHAIN, g.stream, g.ev_geo_done);
+        /* 754 */ if (g.sel_read_pending) { W(W_SEL_SEL_READ, g.stream, g.ev_sel_read); g.sel_read_pending = false; }
+        /* 755 */ if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == h.ev_epoch)) W(W_SEL_RASTER, g.stream, g.raster_done);
+        if (in.common_order)                                  // the same waits; the main dependency last, as launch_geometry has it
+        /* 751 */ if (g.main_dep_pending) { W(W_SEL_MAIN_DEP, g.stream, ev_main_dep); g.main_dep_pending = false; }
+    }
+    void select_end(int gi)
+    {
+        Set& g = sets[gi];
+        /* 759 */ R(g.ev_geo_done, g.stream);
+        /* 760 */ g.geo_recorded = true;
+    }
+    void heights_begin()                                      // vr_terrain_update_heights: the parent queued nothing in front of the kernels
+    {
+        if (in.heights_behind)
+            for (Set& g : sets) if (g.geo_recorded) W(W_HEIGHTS_CHAIN, h.main, g.ev_geo_done);
+    }
+    void heights_end()
+    {
+        /* 456 */ R(ev_main_dep, h.main);
+        /* 457 */ for (Set& g : sets) g.main_dep_pending = true;
+    }
+    void light_writer_begins(int im)                          // vr_frame_submit, vr_frame.hip
+    {
+        /* 38 */ if (img[im].read_pending) { W(W_FRAME_READER, h.main, img[im].ev_read_done); img[im].read_pending = false; }
+    }
+    void image_written(int im, bool fused, int fused_stop, int light_stop, int reader)
+    {
+        Image* hdr = &img[im];
+        /* 55 */ int done = fused ? fused_stop : (h.dispatch_events && h.last_stop) ? h.last_stop : 0;
+        if (in.own_stop && !fused) done = light_stop;
+        /* 56 */ if (!done) {
+        /* 58 */     R(hdr->ev_written, h.main);
+        /* 59 */     done = hdr->ev_written;
+                 }
+        /* 61 */ W(W_FRAME_WRITTEN, reader, done);
+    }
+    void reader_done(int im, int reader)
+    {
+        /* 71 */ R(img[im].ev_read_done, reader);
+        /* 72 */ img[im].read_pending = true;
+    }
+};
+
+// ---- the protocol as the .hip files call it now ------------------------------------------------------
+struct Protocol {
+    World& w; Host& h; Ops ops;
+    OrderTerrain<int> t; OrderSet<int, int> sets[3]; OrderImage<int> img[2];
+    Protocol(World& w_, Host& h_) : w(w_), h(h_), ops{ &w_ }
+    {
+        t.ev_changed = EV_MAIN_DEP; t.ev_sel_ready = EV_SEL_COPY; t.hint.own = EV_RASTER_BEGIN;
+        for (int i = 0; i < 3; i++) { sets[i].stream = G0; sets[i].chain.own = EV_GEO_DONE + i; sets[i].tile_pass.own = EV_RASTER_DONE + i;
+                                      sets[i].sel_read.ev = EV_SEL_READ + i; sets[i].main_dep.ev = t.ev_changed; }
+        for (int i = 0; i < 2; i++) { img[i].written.own = EV_WRITTEN + i; img[i].read_done.ev = EV_READ_DONE + i; }
+    }
+    int stream(int gi) const { return sets[gi].stream; }
+    void begin_chain(int gi) { order_begin_chain(t, sets[gi], ops, kGeo, h.geo_turn, h.main, !h.async_geometry, h.ev_epoch); }
+    template <class Copy> void copy_selection(int gi, int from, Copy&& copy) { order_copy_selection(t, sets[gi], sets[from], ops, [&]() -> int { copy(); return 0; }); }
+    void end_chain(int gi) { order_end_chain(sets[gi], ops); }
+    void prepare_start() { order_prepare_start(t, ops, kGeo, h.geo_turn, h.ev_epoch); }
+    void prepare_wait(int gi)
+    {
+        bool other_prepared = false;
+        for (int p = 0; p < 3; p++) other_prepared |= (p != gi) && h.prepared[p];
+        order_prepare_wait(sets[gi], ops, h.main, other_prepared);
+    }
+    void tile_pass_begin(int gi, bool use_prepared) { order_tile_pass_begin(t, sets[gi], ops, h.main, use_prepared, h.dispatch_events ? h.last_stop : 0, h.ev_epoch); }
+    void keep_writer_begins(int im) { order_image_writer_begins(img[im], ops, h.main); }
+    void tile_pass_launched(int gi, int pass_stop)
+    {
+        order_tile_pass_launched(sets[gi], ops, h.main, pass_stop, h.ev_epoch);
+        for (int p = 0; p < 3; p++) if (p != gi && h.prepared[p]) order_wait_ahead(sets[p], ops, h.main);
+    }
+    void select_begin(int gi) { order_begin_chain(t, sets[gi], ops, kGeo, h.geo_turn, h.main, false, h.ev_epoch); }
+    void select_end(int gi) { order_end_chain(sets[gi], ops); }
+    void heights_begin() { OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] }; order_terrain_changing(all, ops, h.main); }
+    void heights_end() { OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] }; order_terrain_changed(t, all, ops, h.main); }
+    void light_writer_begins(int im) { order_image_writer_begins(img[im], ops, h.main); }
+    void image_written(int im, bool fused, int fused_stop, int light_stop, int reader)
+    { order_image_written(img[im], ops, h.main, reader, fused ? fused_stop : light_stop, h.ev_epoch); }
+    void reader_done(int im, int reader) { order_image_reader_done(img[im], ops, reader); }
+};
+
+// ---- the API calls: what the .hip files do around the ordering steps, with the kernels' accesses ------------------------------
+enum Call { RENDER0, RENDER1, RENDER2, PREPARE0, PREPARE1, PREPARE2, RENDER_LOCKED, SELECT, HEIGHTS_UPDATE, SET_STREAM, ASYNC_TOGGLE, DISPATCH_TOGGLE,
+            FUSION_TOGGLE, NOT_STAMPED_1ST, NOT_STAMPED_2ND, TIMING_ON, TIMING_OFF, SUBMIT_A_CROSS, SUBMIT_A_SAME, SUBMIT_B_CROSS, SUBMIT_B_SAME, N_CALLS };
+static const char* const kCallName[N_CALLS] = { "render(0)", "render(1)", "render(2)", "prepare(0)", "prepare(1)", "prepare(2)", "render(lock_view)", "select",
+    "update_heights", "set_stream", "async_geometry^", "dispatch_events^", "frame_fusion^", "next launch not stamped", "launch after next not stamped",
+    "timing_enable(2)", "timing_enable(0)/collect", "submit(image A, tone mapper on another stream)", "submit(image A, same stream)",
+    "submit(image B, another stream)", "submit(image B, same stream)" };
+
+template <class P> struct Driver {
+    World& w; Host& h; P& p;
+    void geometry(int gi, int sel)                            // launch_geometry
+    {
+        p.begin_chain(gi);
+        const int gs = p.stream(gi);
+        if (sel < 0) { w.kernel(gs); w.access(HEIGHTS, false, gs); w.access(SEL0 + gi, true, gs); h.have_selection[gi] = true; }
+        else if (sel != gi) {
+            p.copy_selection(gi, sel, [&]() { w.kernel(gs); w.access(SEL0 + sel, false, gs); w.access(SEL0 + gi, true, gs); });
+            h.have_selection[gi] = true;
+        }
+        w.kernel(gs); w.access(SEL0 + gi, false, gs); w.access(GEO0 + gi, true, gs);
+        p.end_chain(gi);
+    }
+    void prepare(int view)                                    // vr_terrain_prepare
+    {
+        for (int i = 0; i < 3; i++) if (h.prepared[i] && h.prep_view[i] == view) return;
+        const int gi = h.pick_set();
+        h.prepared[gi] = false;
+        p.prepare_start();
+        geometry(gi, -1);
+        p.prepare_wait(gi);
+        h.prepared[gi] = true; h.prep_view[gi] = view; h.prep_serial[gi] = ++h.prep_counter;
+    }
+    int render(int view, bool lock, int keep_image)           // terrain_render_impl; returns the pass's stop event (keep: the fused launch's)
+    {
+        int gi = -1;
+        if (!lock) for (int i = 0; i < 3; i++) if (i != h.cur && h.prepared[i] && h.prep_view[i] == view) { gi = i; break; }
+        const bool use_prepared = gi >= 0;
+        if (!use_prepared) gi = h.pick_set();
+        const int last = h.cur;
+        h.prepared[gi] = false;
+        if (!use_prepared) geometry(gi, (lock && h.have_selection[last]) ? last : -1);
+        h.cur = gi;
+        p.tile_pass_begin(gi, use_prepared);
+        if (keep_image >= 0) p.keep_writer_begins(keep_image);
+        const int pass_stop = h.stop_of(h.stamped_launch(w));
+        w.access(SEL0 + gi, false, h.main); w.access(GEO0 + gi, false, h.main);
+        if (keep_image >= 0) w.access(IMG0 + keep_image, true, h.main);
+        p.tile_pass_launched(gi, pass_stop);
+        return pass_stop;
+    }
+    void select()                                             // vr_terrain_select (asynchronous form)
+    {
+        const int gi = h.pick_set();
+        p.select_begin(gi);
+        h.prepared[gi] = false;
+        const int gs = p.stream(gi);
+        w.kernel(gs); w.access(HEIGHTS, false, gs); w.access(SEL0 + gi, true, gs); h.have_selection[gi] = true;
+        p.select_end(gi);
+        h.cur = gi;
+    }
+    void update_heights()                                     // vr_terrain_update_heights
+    {
+        for (bool& b : h.prepared) b = false;
+        p.heights_begin();
+        w.kernel(h.main); w.access(HEIGHTS, true, h.main);
+        p.heights_end();
+    }
+    void timing(int level)                                    // vr_timing_enable / vr_timing_collect (vr_host.hip:216-218, timing_reset)
+    {
+        w.sync_stream(h.main);
+        for (int e : h.pooled_end) w.sync_event(e);
+        h.ev_epoch++; h.last_stop = 0; h.pooled_end.clear();
+        h.timing = level;
+    }
+    void submit(int im, bool tm_cross)                        // vr_frame_submit: view n, the next two prepared ahead
+    {
+        const int view = h.frame_no % 3;
+        const bool fused = h.frame_fusion;                    // (where the tile pass's G-buffer-keeping flavour applies)
+        const int fused_stop = render(view, false, fused ? im : -1);
+        prepare((view + 1) % 3); prepare((view + 2) % 3);
+        int light_stop = 0;
+        if (!fused) {
+            p.light_writer_begins(im);
+            light_stop = h.stop_of(h.stamped_launch(w));
+            w.access(IMG0 + im, true, h.main);
+        }
+        const int reader = tm_cross ? TM : h.main;
+        const bool cross = reader != h.main;
+        if (cross) p.image_written(im, fused, fused_stop, light_stop, reader);
+        w.kernel(reader); w.access(IMG0 + im, false, reader);
+        if (cross) p.reader_done(im, reader);
+        h.frame_no++;
+    }
+    void call(int c)
+    {
+        h.launched = false;
+        switch (c) {
+        case RENDER0: case RENDER1: case RENDER2: render(c - RENDER0, false, -1); break;
+        case PREPARE0: case PREPARE1: case PREPARE2: prepare(c - PREPARE0); break;
+        case RENDER_LOCKED: render(0, true, -1); break;
+        case SELECT: select(); break;
+        case HEIGHTS_UPDATE: update_heights(); break;
+        case SET_STREAM: { const int to = h.main == M0 ? M1 : M0; w.host_orders(to, h.main); h.main = to; } break;     // (test_context_stream_changed_...: "what the host owes")
+        case ASYNC_TOGGLE: h.async_geometry = !h.async_geometry; break;
+        case DISPATCH_TOGGLE: w.sync_stream(h.main); h.dispatch_events = !h.dispatch_events; h.last_stop = 0; break;   // vr_context_set_option
+        case FUSION_TOGGLE: h.frame_fusion = !h.frame_fusion; break;
+        case NOT_STAMPED_1ST: h.not_stamped = 1u; break;
+        case NOT_STAMPED_2ND: h.not_stamped = 2u; break;
+        case TIMING_ON: timing(2); break;
+        case TIMING_OFF: timing(0); break;
+        case SUBMIT_A_CROSS: submit(0, true); break;
+        case SUBMIT_A_SAME: submit(0, false); break;
+        case SUBMIT_B_CROSS: submit(1, true); break;
+        case SUBMIT_B_SAME: submit(1, false); break;
+        }
+        if (h.launched) h.not_stamped = 0;                    // the marker covers the next call that launches, no more
+    }
+};
+
+struct Outcome { std::vector<Op> trace; int unordered; std::string first; };
+static World g_world;
+static Outcome run_parent(const int* seq, int n, Intended in, int drop)
+{
+    g_world.reset(drop);
+    Host h; Parent p(g_world, h, in); Driver<Parent> d{ g_world, h, p };
+    for (int i = 0; i < n; i++) d.call(seq[i]);
+    return { g_world.trace, g_world.unordered, g_world.first };
+}
+static Outcome run_protocol(const int* seq, int n)
+{
+    g_world.reset(0);
+    Host h; Protocol p(g_world, h); Driver<Protocol> d{ g_world, h, p };
+    for (int i = 0; i < n; i++) d.call(seq[i]);
+    return { g_world.trace, g_world.unordered, g_world.first };
+}
+static bool same(const std::vector<Op>& a, const std::vector<Op>& b) { return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(Op)) == 0); }
+static std::string show(const int* seq, int n) { std::string s; for (int i = 0; i < n; i++) { if (i) s += "; "; s += kCallName[seq[i]]; } return s; }
+static std::string show(const std::vector<Op>& t)
+{
+    std::string s;
+    for (const Op& o : t) { char b[64]; snprintf(b, sizeof(b), " %s(%s,e%d)", o.wait ? "wait" : "record", kStreamName[o.stream], o.event); s += b; }
+    return s;
+}
+
+// ---- (c) the sequences ------------------------------------------------------------------------------------
+constexpr int kExhaustive = 4, kRandom = 200000, kRandomMax = 14;
+static const Intended kPlain = { false, false, false }, kAll = { true, true, true };
+static long sequences = 0, failures = 0;
+// the parent's own unordered pairs, by the one intended difference that repairs them
+struct Finding { const char* name; Intended only; long count; int shortest[kRandomMax], shortest_n; std::string pair; };
+static Finding findings[2] = {
+    { "vr_frame_submit took ctx->last_stop for a lighting pass that was not stamped", { true, false, false }, 0, {}, 0, "" },
+    { "the node-height update did not wait for chains that still read the heights", { false, true, false }, 0, {}, 0, "" },
+};
+static long drop_reported[N_SITES];
+
+static void check(const int* seq, int n)
+{
+    sequences++;
+    const Outcome now = run_protocol(seq, n);
+    if (now.unordered) { if (failures++ < 10) printf("FAIL (b) protocol: %s\n    %s\n", show(seq, n).c_str(), now.first.c_str()); }
+    const Outcome spec = run_parent(seq, n, kAll, 0);
+    if (!same(now.trace, spec.trace)) {
+        if (failures++ < 10) printf("FAIL (a) traces differ: %s\n    parent  :%s\n    protocol:%s\n", show(seq, n).c_str(), show(spec.trace).c_str(), show(now.trace).c_str());
+    }
+    const Outcome plain = run_parent(seq, n, kPlain, 0);
+    if (plain.unordered) {
+        // a finding about the parent: one of the two differences alone must repair it, or both together (two findings in one sequence)
+        bool explained = false;
+        for (Finding& f : findings) {
+            if (run_parent(seq, n, f.only, 0).unordered) continue;
+            explained = true; f.count++;
+            if (!f.shortest_n || n < f.shortest_n) { f.shortest_n = n; memcpy(f.shortest, seq, n * sizeof(int)); f.pair = plain.first; }
+        }
+        if (!explained && run_parent(seq, n, { true, true, false }, 0).unordered) {
+            if (failures++ < 10) printf("FAIL (b) parent, not repaired by the intended differences: %s\n    %s\n", show(seq, n).c_str(), plain.first.c_str());
+        }
+    }
+}
+static void check_drops(const int* seq, int n)
+{
+    sequences++;
+    for (int site = 1; site < N_SITES; site++) if (run_parent(seq, n, kAll, site).unordered) drop_reported[site]++;
+}
+
+template <class F> static void all_sequences(int longest, long random, F&& f)
+{
+    int seq[kRandomMax];
+    for (int n = 1; n <= longest; n++) {
+        long total = 1;
+        for (int i = 0; i < n; i++) total *= N_CALLS;
+        for (long k = 0; k < total; k++) { long v = k; for (int i = 0; i < n; i++) { seq[i] = (int)(v % N_CALLS); v /= N_CALLS; } f(seq, n); }
+    }
+    uint64_t x = 0x9E3779B97F4A7C15ull;                           // xorshift64, fixed seed
+    auto next = [&x]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
+    for (long k = 0; k < random; k++) {
+        const int n = longest + 1 + (int)(next() % (uint64_t)(kRandomMax - longest));
+        for (int i = 0; i < n; i++) seq[i] = (int)(next() % N_CALLS);
+        f(seq, n);
+    }
+}
+
+// a sequence on which the plain transcription must fail (b) and the protocol must pass
+static void known(const char* what, std::vector<int> seq)
+{
+    const Outcome plain = run_parent(seq.data(), (int)seq.size(), kPlain, 0), now = run_protocol(seq.data(), (int)seq.size());
+    printf("known: %s\n    %s\n    parent: %s\n    protocol: %s\n", what, show(seq.data(), (int)seq.size()).c_str(),
+           plain.unordered ? plain.first.c_str() : "ordered", now.unordered ? now.first.c_str() : "ordered");
+    if (!plain.unordered || now.unordered) { failures++; printf("FAIL: expected the parent unordered and the protocol ordered\n"); }
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1 && !strcmp(argv[1], "--drop-each")) {
+        all_sequences(3, 20000, check_drops);
+        printf("%ld sequences, the transcription (intended differences on) less one wait site at a time:\n", sequences);
+        int reported = 0, bad = 0;
+        for (int site = 1; site < N_SITES; site++) {
+            printf("  %-60s %s (%ld sequences)\n", kSiteName[site], drop_reported[site] ? "reported" : "NOT reported", drop_reported[site]);
+            reported += drop_reported[site] != 0;
+            // the start hint orders nothing: it only says when a prepared chain becomes runnable.  Every other wait is needed somewhere.
+            bad += (drop_reported[site] != 0) == (site == W_PREP_HINT);
+        }
+        printf("%d of %d wait sites reported, %d unexpected\n", reported, N_SITES - 1, bad);
+        return bad ? 1 : 0;
+    }
+    // intended difference 1 (known before): the tile pass is stamped, the lighting launch is not - ctx->last_stop is the tile pass's
+    // stop event and the tone-map stage reads the image while the lighting pass writes it
+    known(findings[0].name, { FUSION_TOGGLE, NOT_STAMPED_2ND, SUBMIT_A_CROSS });
+    // intended difference 2 (found by (b)): a select's chain is consumed by nothing on the context's stream, which then rewrites the heights
+    known(findings[1].name, { SELECT, HEIGHTS_UPDATE });
+    all_sequences(kExhaustive, kRandom, check);
+    for (const Finding& f : findings) {
+        printf("finding: %s: %ld sequences; shortest: %s\n    %s\n", f.name, f.count, show(f.shortest, f.shortest_n).c_str(), f.pair.c_str());
+        if (!f.count) { failures++; printf("FAIL: the finding was not seen\n"); }
+    }
+    printf("permitted reorder: vr_terrain_select queues the main-dependency wait last, as launch_geometry does (Intended::common_order)\n");
+    printf("%ld sequences (all up to %d calls of %d, %d random up to %d), %ld failures\n", sequences, kExhaustive, (int)N_CALLS, kRandom, kRandomMax, failures);
+    return failures ? 1 : 0;
+}

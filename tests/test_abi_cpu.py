@@ -209,6 +209,23 @@ def test_devbuf_grow_is_all_or_nothing_at_every_failure_position(tmp_path):
     assert "1152 cases" in r.stdout, r.stdout[-400:]            # single: 3 x 6 x 2 x 2; groups: 4 patterns x 2 x (N + 1), N = 1..15
 
 
+def test_stream_order_matches_the_transcribed_protocol_and_the_happens_before_model(tmp_path):
+    """vr_order.h compiles without HIP.  Over every sequence of up to four API calls and a fixed sample of longer ones
+    (tests/host/order_check.cpp) the protocol queues the records and waits the ordering code it replaced queued, apart from the
+    intended differences the program names, and no two conflicting accesses to a geometry set, the node heights or an HDR image
+    are left unordered by the streams' vector clocks; a transcription that loses any one wait but the start hint's is reported."""
+    import subprocess
+    exe = os.path.join(str(tmp_path), "order_check")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "order_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    assert "404204 sequences" in r.stdout, r.stdout[-400:]      # 21 + 21^2 + 21^3 + 21^4 of 21 calls, 200000 random
+    r = subprocess.run([exe, "--drop-each"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "16 of 17 wait sites reported" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+
+
 def _build_allgather_example(tmpdir):
     import subprocess
     exe = os.path.join(str(tmpdir), "frame_allgather_example")

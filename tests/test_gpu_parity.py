@@ -1320,6 +1320,46 @@ def test_context_stream_changed_between_prepare_and_render(scene2048, oracle, gp
         rt.close()
 
 
+def test_marks_of_a_recycled_timing_epoch_are_not_waited_for(scene256, oracle, gpu_ctx):
+    """The timing pool is recycled (vr_timing_enable / vr_timing_collect) between the two ends of a dependency: the start hint
+    a prepared chain was given and the tile-pass marks of the sets then hold stamped events of an older epoch, which count as
+    complete (vr_order.h, OrderMark) - nothing waits on an event that may have been re-recorded, nothing hangs, and with
+    VR_OPT_DISPATCH_EVENTS off and on again every frame's five planes still equal the oracle's.
+    This cannot detect a race: every frame is downloaded, which synchronises the streams.  A missing wait is what
+    tests/host/order_check.cpp (test_abi_cpu.py) finds."""
+    ot, tp = scene256["ot"], scene256["tp"]
+    w, h = 320, 180
+    rp = vr.default_render_params(400.0, assume_cleared=1)
+    rt = vr.RenderTargets(gpu_ctx).Init(w, h)
+    views, want = [], []
+    for cam in (CAMERAS[0], CAMERAS[3], CAMERAS[5], CAMERAS[1]):
+        v = vr.make_view(*scaled_camera(cam, 256), w, h)
+        gb = oracle.GBufferHost(w, h)
+        gb.clear(); ot.render(v, gb, rp)
+        views.append(v); want.append(gb)
+
+    def frame(k, what):
+        tp.Render(views[k], views[k], rt, rp)
+        planes = {p: rt.download(p) for p in ("depth", "diffuse", "specular", "normals", "emissive")}
+        _assert_gbuffer_equal(want[k], planes, what)
+
+    try:
+        frame(0, "first frame")
+        tp.Prepare(views[1], rt, rp)
+        gpu_ctx.timing_enable(1)                          # the prepared set's start hint and the current set's tile-pass mark are stale now
+        frame(1, "prepared before the pool was recycled")
+        frame(2, "into a set whose tile-pass mark is stale")
+        gpu_ctx.timing_collect()
+        gpu_ctx.set_dispatch_events(False)
+        frame(3, "after collect, explicit records")
+        gpu_ctx.set_dispatch_events(True)
+        frame(0, "stamped events again")
+    finally:
+        gpu_ctx.timing_enable(0)
+        gpu_ctx.set_dispatch_events(True)
+        rt.close()
+
+
 def test_region_tracking_never_changes_the_gbuffer(scene256, oracle, gpu_ctx):
     """VR_OPT_PLANE_TRACKING per region (8 rows x 32 pixels): a sky region known to hold the clear values is not written by a
     pass over a 'cleared' target, a terrain region known to hold the specular constant keeps that plane.  Through a history of

@@ -265,10 +265,12 @@ int vr_deferred_make_args(const vr_view* view, int w, int h, const vr_light* lig
     return VR_OK;
 }
 
+// *stop: the stop event this call's own launch was stamped with (NULL: not stamped, or nothing was launched)
 static int deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
                           int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
-                          vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
+                          vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, hipEvent_t* stop)
 {
+    *stop = nullptr;
     VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
     ShadowArgs sh;
     memset(&sh, 0, sizeof(sh));
@@ -340,15 +342,24 @@ static int deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, 
                                gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, sh, shadow ? 1 : 0);
         }
     }
+    *stop = ks.stop();
     VR_HIP(hipGetLastError());
     return VR_OK;
+}
+
+int vr_deferred_light_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                           const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
+                           const vr_shadow_binding* shadow, hipEvent_t* stop)
+{
+    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, stop);
 }
 
 extern "C" VR_API int vr_deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
                                          int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
                                          vr_image* hdr, const vr_partition* part)
 {
-    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr);
+    hipEvent_t stop;
+    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, &stop);
 }
 
 // DeferredLightingPass::Render with DirectionalLight::shadowMap set (Renderer.cpp:336, 427)
@@ -357,7 +368,8 @@ extern "C" VR_API int vr_deferred_light_shadowed(vr_context* ctx, const vr_view*
                                                   vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
 {
     VR_REQUIRE(shadow, "shadow binding is NULL (use vr_deferred_light)");
-    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow);
+    hipEvent_t stop;
+    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &stop);
 }
 
 // ---- tiled deferred lighting for many point lights (BASELINE config 5) ---------------------------
@@ -764,6 +776,14 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
                                                int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
                                                vr_image* hdr, const vr_partition* part)
 {
+    hipEvent_t stop;
+    return vr_deferred_light_tiled_stop(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, &stop);
+}
+
+int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                 const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop)
+{
+    *stop = nullptr;
     VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
     VR_REQUIRE(num_lights >= 0 && num_lights <= 65536 && (num_lights == 0 || lights), "bad light list");
     VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0,
@@ -828,6 +848,7 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
             VR_LAUNCH_TIMED(ks, (k_deferred_tiled<true, VR_TILED_PXB>), dim3((unsigned)pt->num_owned * kSubTiles), dim3(256), ctx->stream, a,
                             ctx->d_lights, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data,
                             ctx->d_srgb_lut, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, hints);
+            *stop = ks.stop();
         }
     } else {
         VR_REQUIRE((size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
@@ -843,6 +864,7 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
         else VR_LAUNCH_TIMED(ks, (k_deferred_tiled<false, VR_TILED_PXB, false>), dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
                              gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut,
                              (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints);
+        *stop = ks.stop();
     }
     VR_HIP(hipGetLastError());
     return VR_OK;

@@ -33,14 +33,16 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
         if (f->prepare_views[k] && (rc = vr_terrain_prepare(t, f->prepare_views[k], gb, f->render, f->part))) return rc;
     // whoever still reads the image this lighting pass overwrites (the tone-map stage of two frames ago, on another stream)
     // (a fused tile pass has waited for that reader in front of its own launch)
-    if (fused) rc = VR_OK;
-    else {
-    if (hdr->read_pending) { VR_HIP(hipStreamWaitEvent(ctx->stream, hdr->ev_read_done, 0)); hdr->read_pending = false; }
-    if (f->tiled) rc = vr_deferred_light_tiled(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part);
-    else if (f->shadow) rc = vr_deferred_light_shadowed(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow);
-    else rc = vr_deferred_light(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part);
+    // written_stop: the stop event of the pass that writes the image - the fused tile pass's or the lighting pass's OWN, handed out
+    // by the launch (vr_terrain_prepare has run since: the context's last stamped launch need not be that one)
+    const VrOrderOps ops;
+    hipEvent_t written_stop = fused_stop;
+    if (!fused) {
+        if ((rc = order_image_writer_begins(hdr->ord, ops, ctx->stream))) return rc;
+        if (f->tiled) rc = vr_deferred_light_tiled_stop(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, &written_stop);
+        else rc = vr_deferred_light_stop(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow, &written_stop);
+        if (rc) return rc;
     }
-    if (rc) return rc;
     if (!f->tonemap) return earlier;
 
     // ToneMappingPass::SimpleRender on the tone mapper's own context (another stream: it runs under the next frame's rendering)
@@ -49,16 +51,9 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     VR_REQUIRE(tc->device == ctx->device, "tone mapper lives on another device");
     const bool cross = tc->stream != ctx->stream;
     if (cross) {
-        // behind the lighting pass: its dispatch-stamped stop event when there is one, else an explicit record
-        // (a fused frame: the tile pass's OWN stop event, handed out by the launch - vr_terrain_prepare has run since and the
-        // context's last stamped launch need not be that one any more)
-        hipEvent_t done = fused ? fused_stop : (ctx->dispatch_events && ctx->last_stop) ? ctx->last_stop : nullptr;
-        if (!done) {
-            if (!hdr->ev_written) VR_HIP(hipEventCreateWithFlags(&hdr->ev_written, hipEventDisableTiming));
-            VR_HIP(hipEventRecord(hdr->ev_written, ctx->stream));
-            done = hdr->ev_written;
-        }
-        VR_HIP(hipStreamWaitEvent(tc->stream, done, 0));
+        // behind the pass that wrote the image: its dispatch-stamped stop event when there is one, else an explicit record
+        if (!written_stop && !hdr->ord.written.own) VR_HIP(hipEventCreateWithFlags(&hdr->ord.written.own, hipEventDisableTiming));
+        if ((rc = order_image_written(hdr->ord, ops, ctx->stream, tc->stream, written_stop, ctx->ev_epoch))) return rc;
     }
     const int w = gb->w, h = gb->h;
     if ((rc = vr_tonemap_reset_histogram(f->tonemap))) return rc;
@@ -67,9 +62,8 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     if ((rc = vr_tonemap_compute_exposure(f->tonemap, f->tonemap_params, f->frame_time_seconds))) return rc;
     if ((rc = vr_tonemap_render(f->tonemap, f->tonemap_params, hdr, w, h, f->ldr_out, f->ldr_capacity, f->part))) return rc;
     if (cross) {
-        if (!hdr->ev_read_done) VR_HIP(hipEventCreateWithFlags(&hdr->ev_read_done, hipEventDisableTiming));
-        VR_HIP(hipEventRecord(hdr->ev_read_done, tc->stream));
-        hdr->read_pending = true;
+        if (!hdr->ord.read_done.ev) VR_HIP(hipEventCreateWithFlags(&hdr->ord.read_done.ev, hipEventDisableTiming));
+        if ((rc = order_image_reader_done(hdr->ord, ops, tc->stream))) return rc;
     }
     if (f->nccl_comm) {
         VR_REQUIRE(f->part && f->gathered && f->ldr_frame, "exchange: partition / gathered / ldr_frame missing");

@@ -192,6 +192,7 @@ void VrKernelScope::commit()
 void VrKernelScope::launched()
 {
     commit();
+    stamped = true;
     if (st == c->stream) c->last_stop = e1;
 }
 VrKernelScope::~VrKernelScope()
@@ -701,9 +702,9 @@ extern "C" VR_API void vr_image_destroy(vr_image* im)
 {
     if (!im) return;
     (void)hipSetDevice(im->ctx->device);
-    if (im->read_pending) (void)hipEventSynchronize(im->ev_read_done);       // a stage on another stream may still be reading it
-    if (im->ev_written) (void)hipEventDestroy(im->ev_written);
-    if (im->ev_read_done) (void)hipEventDestroy(im->ev_read_done);
+    if (im->ord.read_done.pending) (void)hipEventSynchronize(im->ord.read_done.ev);       // a stage on another stream may still be reading it
+    if (im->ord.written.own) (void)hipEventDestroy(im->ord.written.own);
+    if (im->ord.read_done.ev) (void)hipEventDestroy(im->ord.read_done.ev);
     if (im->owned) (void)hipFree(im->data);
     delete im;
 }

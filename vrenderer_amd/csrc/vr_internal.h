@@ -11,6 +11,7 @@
 
 #include "../../include/vrterrain.h"
 #include "vr_devbuf.h"
+#include "vr_order.h"
 
 // ---- error plumbing -------------------------------------------------------------
 void vr_set_error(const char* fmt, ...);
@@ -36,6 +37,14 @@ template <class T, class Quiesce> int vr_grow(T** ptr, size_t* capacity_bytes, s
 { return vr_grow_code(vr_devbuf_grow((void**)ptr, capacity_bytes, bytes, vr_dev_alloc, vr_dev_free, quiesce)); }
 template <size_t N, class Quiesce> int vr_grow_group(void** const (&slot)[N], const size_t (&bytes)[N], Quiesce&& quiesce)
 { return vr_grow_code(vr_devbuf_grow_group(slot, bytes, vr_dev_alloc, vr_dev_free, quiesce)); }
+
+// ---- cross-stream order (vr_order.h) -----------------------------------------------------
+// The protocol's two operations on HIP's streams and events; its steps return what these return.
+struct VrOrderOps {
+    int record(hipEvent_t e, hipStream_t s) const { VR_HIP(hipEventRecord(e, s)); return VR_OK; }
+    int wait(hipStream_t s, hipEvent_t e) const { VR_HIP(hipStreamWaitEvent(s, e, 0)); return VR_OK; }
+};
+using VrOrderSet = OrderSet<hipStream_t, hipEvent_t>;
 
 // ---- geometry constants -----------------------------------------------------------
 constexpr int kGrid = 32;                    // GRID_SIZE (TerrainPass.h:28)
@@ -185,10 +194,12 @@ struct vr_context {
     // sit between the two big kernels of a frame.  Outside timing runs the events come from this ring.
     bool dispatch_events = true;
     std::vector<hipEvent_t> ev_ring; size_t ev_ring_pos = 0;
-    hipEvent_t last_stop = nullptr;     // stop event of the most recent dispatch-stamped launch on `stream`
-    // Handles to pooled timing events are only good until the pool is recycled (vr_timing_enable / vr_timing_collect, both
-    // of which synchronise the stream first): holders remember the epoch and treat a handle of an older epoch as 'already
-    // complete' instead of waiting on an event that may since have been re-recorded for an unrelated kernel.
+    // Stop event of the most recent dispatch-stamped launch on `stream`.  Read for ONE thing: the start hint of the next
+    // prepared chain (order_tile_pass_begin), where a wrong event costs time and not correctness.  It says nothing about which
+    // launch it belongs to: a pass that others must wait for hands out its own stop event (VrKernelScope::stop).
+    hipEvent_t last_stop = nullptr;
+    // Advanced whenever the timing pool is recycled (vr_timing_enable / vr_timing_collect, both of which synchronise the stream
+    // first): a mark that holds a stamped event of an older epoch counts as complete (OrderMark, vr_order.h).
     uint64_t ev_epoch = 1;
     // light list of vr_deferred_light_tiled
     DevLight* d_lights = nullptr; size_t light_bytes = 0; std::vector<DevLight> h_lights, h_lights_on_device;   // (the list d_lights holds)
@@ -216,6 +227,9 @@ struct VrKernelScope {
     // a scope that returns early without launching hands its events back instead of leaving a never-recorded pair)
     void commit();
     void launched();                // the dispatch that stamps the pair has been issued
+    bool stamped = false;
+    // this launch's own stop event where such events serve as dependencies (VR_OPT_DISPATCH_EVENTS); NULL: not stamped, or no launch
+    hipEvent_t stop() const { return stamped && c->dispatch_events ? e1 : nullptr; }
     ~VrKernelScope();
 };
 // launch under a scope created with attach = true
@@ -289,10 +303,7 @@ struct vr_image {
     void* data;
     bool owned;
     size_t capacity_bytes;
-    // vr_frame_submit's cross-stream bookkeeping: the lighting pass that wrote the image (when no dispatch-stamped event exists)
-    // and the stage on another stream that still reads it
-    hipEvent_t ev_written = nullptr, ev_read_done = nullptr;
-    bool read_pending = false;
+    OrderImage<hipEvent_t> ord;          // vr_frame_submit's cross-stream order (vr_order.h): who wrote it, who still reads it
 };
 
 struct vr_ldr_image {
@@ -324,23 +335,8 @@ struct GeoSet {
     TileEntry* d_bin_entries = nullptr;   // bin_capacity entries of 64 B (k_fill)
     int scratch_tiles = 0;
     int last_tiles = 0;                  // raster tiles of the target the last chain was built for (the stride of d_tile_order's class regions)
-    hipEvent_t ev_geo_done = nullptr, ev_raster_done = nullptr;
-    hipEvent_t raster_done = nullptr;    // what the geometry stream waits on before reusing this set: ev_raster_done, or the tile pass's own stop event
-    uint64_t raster_done_epoch = 0;      // 0: raster_done is this set's own ev_raster_done (always valid); else the context's ev_epoch when the handle was taken
-    bool raster_recorded = false, have_selection = false;
-    // Successive chains on one set may run on different geometry streams (they take turns) and a chain is not always
-    // consumed by a tile pass (an evicted prepared set, vr_terrain_select alone): every writer of the set first waits for
-    // the set's previous chain (ev_geo_done) and for a lock_view copy that may still be reading its selection.
-    bool geo_recorded = false;           // ev_geo_done has been recorded at least once
-    hipEvent_t ev_sel_read = nullptr;    // recorded behind a lock_view copy OUT of this set (on the copying set's stream)
-    bool sel_read_pending = false;
-    bool main_waited = false;            // the context's stream already waits for this set's chain (queued by vr_terrain_prepare)
-    hipStream_t main_wait_stream = nullptr;   // ... the stream that wait was queued on: a host may change the context's stream (vr_context_set_stream)
-                                         // between vr_terrain_prepare and vr_terrain_render; the wait only counts for the stream that holds it
-    // The geometry stream this set's last chain ran on (the terrain's two streams take turns, so that two prepared
-    // frames have their latency-bound chains in flight at once).
-    hipStream_t stream = nullptr;
-    bool main_dep_pending = false;       // the context's stream changed the terrain (node heights): wait for ev_main_dep first
+    bool have_selection = false;
+    VrOrderSet ord;                      // the set's stream, marks and pending readers (vr_order.h)
     bool status_pending = false;         // the last chain's counters have not been read from the host mirror yet
     // vr_terrain_prepare: geometry already built for exactly these inputs
     bool prepared = false;
@@ -388,11 +384,7 @@ struct vr_terrain {
     // Geometry stream: select / vertex / setup / bins depend only on the view, so they run on their own
     // stream and overlap whatever the context's stream is doing (the lighting pass of the previous frame,
     // or - after vr_terrain_prepare - its tile pass); the tile pass on the context's stream waits for them.
-    hipEvent_t ev_sel_copy = nullptr;      // lock_view: the source set's selection is complete
-    hipEvent_t ev_main_dep = nullptr, ev_raster_begin = nullptr;   // ev_raster_begin: the context's stream reached the last tile pass
-    bool raster_begin_recorded = false;
-    hipEvent_t start_hint = nullptr;        // vr_terrain_prepare starts its geometry behind this: ev_raster_begin, or the previous lighting pass's stop event
-    uint64_t start_hint_epoch = 0;          // as GeoSet::raster_done_epoch
+    OrderTerrain<hipEvent_t> ord;          // vr_order.h
     // Terrain queries (vr_query.hip): the min / max pyramid over the surface, built by the first ray cast on the context's stream and
     // kept until vr_terrain_destroy, and the staging memory of the host-pointer mode (grown by doubling).
     uchar2* d_pyramid = nullptr; uint64_t pyramid_bytes = 0;
@@ -417,6 +409,13 @@ int vr_terrain_poll(vr_terrain* t, bool report);
 int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
                            int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
                            bool* fused, hipEvent_t* fused_stop);
+// the lighting passes as vr_frame_submit queues them (vr_deferred.hip): the exported entry points (shadow may be NULL), and
+// *stop = the stop event their own launch was stamped with (NULL: not stamped, or nothing was launched)
+int vr_deferred_light_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                           const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
+                           const vr_shadow_binding* shadow, hipEvent_t* stop);
+int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                 const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop);
 int vr_terrain_reserve_bins(vr_terrain* t, size_t tiles);     // room for a target of that many raster tiles (vr_select.hip)
 // tables of (w, h, part); part == NULL is the whole frame as rank 0 of 1
 int vr_partition_tables(vr_context* ctx, int w, int h, const vr_partition* part, const PartTables** out);

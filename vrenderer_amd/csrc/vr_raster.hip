@@ -1781,36 +1781,23 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
                            const RasterArgs& a, const PartTables* pt)
 {
     vr_context* ctx = t->ctx;
-    // this chain's stream: the terrain's two geometry streams take turns.  Whatever the set did before on the other one
-    // is ordered by the events below: its previous chain (consumed by a tile pass or not), the tile pass that read it, and
-    // a lock_view copy of its selection into another set.
-    g.stream = t->geo_streams[t->geo_turn++ & 1u];
-    g.main_waited = false;
-    hipStream_t s = ctx->stream, gs = g.stream;
-    if (!ctx->async_geometry) {          // single-stream mode: order the geometry behind everything queued so far
-        VR_HIP(hipEventRecord(t->ev_main_dep, s));
-        g.main_dep_pending = true;
-    }
-    // after the tile pass that last read this set, and after anything the context's stream did to the terrain
-    if (g.geo_recorded) VR_HIP(hipStreamWaitEvent(gs, g.ev_geo_done, 0));
-    if (g.sel_read_pending) { VR_HIP(hipStreamWaitEvent(gs, g.ev_sel_read, 0)); g.sel_read_pending = false; }
-    // (a stop event of an older timing epoch: the stream was synchronised when the pool was recycled - that tile pass is done)
-    if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == ctx->ev_epoch)) VR_HIP(hipStreamWaitEvent(gs, g.raster_done, 0));
-    if (g.main_dep_pending) { VR_HIP(hipStreamWaitEvent(gs, t->ev_main_dep, 0)); g.main_dep_pending = false; }
+    const VrOrderOps ops;
     int rc;
+    // this chain's stream, behind whatever still uses the set (single-stream mode: behind everything queued so far)
+    if ((rc = order_begin_chain(t->ord, g.ord, ops, t->geo_streams, t->geo_turn, ctx->stream, !ctx->async_geometry, ctx->ev_epoch))) return rc;
+    hipStream_t s = ctx->stream, gs = g.ord.stream;
     if (selection_from == nullptr) {                                   // TerrainPass.cpp:173-190
         if ((rc = vr_select_launch(t, g, view, rp->max_height, gs))) return rc;
     } else if (selection_from != &g) {
-        // lockView: keep the selection of the last unlocked frame (TerrainPass.cpp:191-197); it lives in another set, whose
-        // select ran on that set's stream
-        VR_HIP(hipEventRecord(t->ev_sel_copy, selection_from->stream));
-        VR_HIP(hipStreamWaitEvent(gs, t->ev_sel_copy, 0));
-        VR_HIP(hipMemcpyAsync(g.d_node_ids, selection_from->d_node_ids, (size_t)t->p.max_instances * sizeof(uint32_t), hipMemcpyDeviceToDevice, gs));
-        VR_HIP(hipMemcpyAsync(g.d_instances, selection_from->d_instances, (size_t)t->p.max_instances * sizeof(vr_instance), hipMemcpyDeviceToDevice, gs));
-        VR_HIP(hipMemcpyAsync(g.d_counters, selection_from->d_counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, gs));
-        // the source set's next writer (a select into it, on either stream) must not overtake these copies
-        VR_HIP(hipEventRecord(selection_from->ev_sel_read, gs));
-        selection_from->sel_read_pending = true;
+        // lockView: keep the selection of the last unlocked frame (TerrainPass.cpp:191-197); it lives in another set
+        const GeoSet& from = *selection_from;
+        rc = order_copy_selection(t->ord, g.ord, selection_from->ord, ops, [&]() -> int {
+            VR_HIP(hipMemcpyAsync(g.d_node_ids, from.d_node_ids, (size_t)t->p.max_instances * sizeof(uint32_t), hipMemcpyDeviceToDevice, gs));
+            VR_HIP(hipMemcpyAsync(g.d_instances, from.d_instances, (size_t)t->p.max_instances * sizeof(vr_instance), hipMemcpyDeviceToDevice, gs));
+            VR_HIP(hipMemcpyAsync(g.d_counters, from.d_counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, gs));
+            return VR_OK;
+        });
+        if (rc) return rc;
         g.have_selection = true;
     }
     const int n_tiles = a.rtx * a.rty;
@@ -1849,8 +1836,7 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
     hipLaunchKernelGGL(k_fill, dim3(kGridFill), dim3(256), 0, gs, a, g.d_counters, g.d_rect, g.d_hard_tris, (const uint4*)g.d_recs,
                        (uint32_t)t->cap_instances * (uint32_t)kTrisPerInst, g.d_tile_cursor, g.d_bin_entries, t->d_status + (size_t)(&g - t->sets) * 8); }
     g.status_pending = true;
-    VR_HIP(hipEventRecord(g.ev_geo_done, gs));
-    g.geo_recorded = true;
+    if ((rc = order_end_chain(g.ord, ops))) return rc;
     VR_HIP(hipGetLastError());
     return VR_OK;
 }
@@ -1922,8 +1908,7 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
     // with the previous frame's lighting pass (bandwidth-bound) instead of with a tile pass (which leaves
     // half of every CU's wave slots free).  (Measured again in round 2, 8K: geometry under the tile pass 483 + 211 us,
     // frame 0.715 ms; geometry under the lighting pass 462 + 239 us, frame 0.723 ms.)
-    if (t->raster_begin_recorded && (t->start_hint_epoch == 0 || t->start_hint_epoch == t->ctx->ev_epoch))
-        VR_HIP(hipStreamWaitEvent(t->geo_streams[t->geo_turn & 1u], t->start_hint, 0));   // (the stream launch_geometry takes next)
+    if ((rc = order_prepare_start(t->ord, VrOrderOps(), t->geo_streams, t->geo_turn, t->ctx->ev_epoch))) return rc;
     if ((rc = launch_geometry(t, g, nullptr, view, rp, a, pt))) return rc;
     // Where the context's stream waits for this chain.  Never in front of the tile pass that consumes it (the lighting pass ->
     // tile pass boundary then holds no cross-stream wait) and never earlier than it has to:
@@ -1935,8 +1920,7 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
     //     difference (4K: 0.28 -> 0.22 ms per frame without it).
     bool other_prepared = false;
     for (const GeoSet& p : t->sets) other_prepared |= (&p != &g) && p.prepared;
-    if (other_prepared) g.main_waited = false;
-    else { VR_HIP(hipStreamWaitEvent(t->ctx->stream, g.ev_geo_done, 0)); g.main_waited = true; g.main_wait_stream = t->ctx->stream; }
+    if ((rc = order_prepare_wait(g.ord, VrOrderOps(), t->ctx->stream, other_prepared))) return rc;
     g.prepared = true; g.prep_view = *view; g.prep_rp = *rp; g.prep_w = gb->w; g.prep_h = gb->h; g.prep_rank = a.rank; g.prep_world = a.world; g.prep_tile_shift = a.tile_shift;
     g.prep_serial = ++t->prep_counter;
     return VR_OK;
@@ -2036,14 +2020,11 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         if ((rc = launch_geometry(t, g, sel, view, rp, a, pt))) return rc;
     }
     t->cur = gi;
-    // the tile pass consumes verts + bins (a wait queued at prepare time counts only if it sits on the stream this pass runs on)
-    if (!(use_prepared && g.main_waited && g.main_wait_stream == s)) VR_HIP(hipStreamWaitEvent(s, g.ev_geo_done, 0));
-    g.main_waited = false;
+    // the tile pass consumes verts + bins; vr_terrain_prepare's start hint: with dispatch-stamped events the stop event of whatever
+    // ran last on the stream (the previous frame's lighting pass)
+    const VrOrderOps ops;
+    if ((rc = order_tile_pass_begin(t->ord, g.ord, ops, s, use_prepared, ctx->dispatch_events ? ctx->last_stop : nullptr, ctx->ev_epoch))) return rc;
     const uint32_t spec_const = vr_specular_constant(ctx);               // terrain_ps.hlsl:76 -> SRGBA8
-    // vr_terrain_prepare's start hint: "the context's stream has reached this tile pass".  With dispatch-stamped events that
-    // is the stop event of whatever ran last on the stream (the previous frame's lighting pass); else an explicit record.
-    if (ctx->dispatch_events && ctx->last_stop) { t->start_hint = ctx->last_stop; t->start_hint_epoch = ctx->ev_epoch; t->raster_begin_recorded = true; }
-    else { VR_HIP(hipEventRecord(t->ev_raster_begin, s)); t->start_hint = t->ev_raster_begin; t->start_hint_epoch = 0; t->raster_begin_recorded = true; }
     hipEvent_t pass_stop = nullptr;
     if (grid > 0) {
         // a depth-only tile pass (the shadow map's) is timed under its own id: it is an order of magnitude shorter than the
@@ -2054,7 +2035,7 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         if (plan.fuse) {
             la.lut_g = ctx->d_srgb_lut; la.hdr = (uint2*)lit_req->hdr->data;
             // whoever still reads the image this pass overwrites (vr_frame_submit: the tone-map stage of two frames ago, on another stream)
-            if (plan.keep) { if (lit_req->hdr->read_pending) { VR_HIP(hipStreamWaitEvent(s, lit_req->hdr->ev_read_done, 0)); lit_req->hdr->read_pending = false; } }
+            if (plan.keep) { if ((rc = order_image_writer_begins(lit_req->hdr->ord, ops, s))) return rc; }
             else if (pt) {
                 VR_REQUIRE((size_t)pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= lit_req->hdr->capacity_bytes, "hdr_out is smaller than vr_partition_packed_bytes()");
                 la.tile_slot = pt->d_tile_slot; la.slot_base = pt->rank * pt->max_owned; la.owner_tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
@@ -2072,15 +2053,13 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         if (k.lit) VR_LAUNCH_TIMED(ks, k.lit, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
         else VR_LAUNCH_TIMED(ks, k.plain, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, LitNone());
 #undef VR_RASTER_ARGS
-        if (ctx->dispatch_events && ks.e0 && ks.e1) pass_stop = ks.e1;        // stamped by the dispatch: complete when the tile pass is
+        pass_stop = ks.stop();                                                // stamped by the dispatch: complete when the tile pass is
         if (plan.keep && lit_req->stop_out) *lit_req->stop_out = pass_stop;
     }
-    if (pass_stop) { g.raster_done = pass_stop; g.raster_done_epoch = ctx->ev_epoch; }
-    else { VR_HIP(hipEventRecord(g.ev_raster_done, s)); g.raster_done = g.ev_raster_done; g.raster_done_epoch = 0; }
-    g.raster_recorded = true;
+    if ((rc = order_tile_pass_launched(g.ord, ops, s, pass_stop, ctx->ev_epoch))) return rc;
     // chains prepared further ahead whose wait vr_terrain_prepare left for later: behind this tile pass
     for (GeoSet& p : t->sets)
-        if (&p != &g && p.prepared && !(p.main_waited && p.main_wait_stream == s) && p.geo_recorded) { VR_HIP(hipStreamWaitEvent(s, p.ev_geo_done, 0)); p.main_waited = true; p.main_wait_stream = s; }
+        if (&p != &g && p.prepared && (rc = order_wait_ahead(p.ord, ops, s))) return rc;
     VR_HIP(hipGetLastError());
     if (earlier_out) *earlier_out = earlier;
     return VR_OK;
@@ -2136,7 +2115,7 @@ extern "C" VR_API int vr_debug_tile_order(vr_terrain* t, int32_t* out_tiles, uin
     VR_REQUIRE(t && out_tiles && out_bin_lengths && out_count && capacity >= 0, "bad arguments");
     VR_HIP(hipSetDevice(t->ctx->device));
     const GeoSet& g = t->sets[t->cur];
-    VR_HIP(hipStreamSynchronize(g.stream));
+    VR_HIP(hipStreamSynchronize(g.ord.stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     *out_count = 0;
     const int n_tiles = g.last_tiles;

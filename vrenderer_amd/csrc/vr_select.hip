@@ -413,6 +413,10 @@ extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
     HeightArgs a;
     a.half_w = t->p.surface_size / 2.0f; a.half_h = t->p.surface_size / 2.0f; a.world_size = t->p.world_size;
     a.texel_x = t->texel_size[0]; a.texel_y = t->texel_size[1]; a.tex_w = t->height.w0; a.tex_h = t->height.h0;
+    // a select queued earlier may still be reading the heights; every set's next chain runs behind the new ones
+    static_assert(kGeoSets == 3, "the list below");
+    VrOrderSet* const ord_sets[kGeoSets] = { &t->sets[0].ord, &t->sets[1].ord, &t->sets[2].ord };
+    { const int rc = order_terrain_changing(ord_sets, VrOrderOps(), t->ctx->stream); if (rc) return rc; }
     VrKernelScope ks(t->ctx, VR_K_NODE_HEIGHTS);
     for (int surf = 0; surf < num_surfaces; surf++) {
     {   // TerrainPass.cpp:102-108
@@ -452,9 +456,7 @@ extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
     }
     }
     VR_HIP(hipGetLastError());
-    // NodeSelect runs on the geometry stream: make it see these results
-    VR_HIP(hipEventRecord(t->ev_main_dep, t->ctx->stream));
-    for (GeoSet& g : t->sets) g.main_dep_pending = true;
+    { const int rc = order_terrain_changed(t->ord, ord_sets, VrOrderOps(), t->ctx->stream); if (rc) return rc; }
     t->height_loaded = true;
     return VR_OK;
 }
@@ -528,7 +530,7 @@ int vr_terrain_poll(vr_terrain* t, bool report)
     uint32_t seen = 0;
     for (int i = 0; i < kGeoSets; i++) {
         GeoSet& g = t->sets[i];
-        if (!g.status_pending || !g.geo_recorded || hipEventQuery(g.ev_geo_done) != hipSuccess) continue;
+        if (!g.status_pending || !g.ord.chain.set || hipEventQuery(g.ord.chain.own) != hipSuccess) continue;
         g.status_pending = false;
         const volatile uint32_t* st = t->h_status + i * 8;
         const uint32_t flags = st[1], wanted = st[6];
@@ -622,9 +624,9 @@ extern "C" VR_API int vr_terrain_create(vr_context* ctx, const vr_terrain_params
     }
     for (GeoSet& g : t->sets) {
         VR_HIP(hipMemsetAsync(g.d_counters, 0, 64 * sizeof(uint32_t), ctx->stream));
-        VR_HIP(hipEventCreateWithFlags(&g.ev_geo_done, hipEventDisableTiming));
-        VR_HIP(hipEventCreateWithFlags(&g.ev_raster_done, hipEventDisableTiming));
-        VR_HIP(hipEventCreateWithFlags(&g.ev_sel_read, hipEventDisableTiming));
+        VR_HIP(hipEventCreateWithFlags(&g.ord.chain.own, hipEventDisableTiming));
+        VR_HIP(hipEventCreateWithFlags(&g.ord.tile_pass.own, hipEventDisableTiming));
+        VR_HIP(hipEventCreateWithFlags(&g.ord.sel_read.ev, hipEventDisableTiming));
     }
     VR_HIP(hipStreamSynchronize(ctx->stream));
     {   // lowest priority: geometry fills in around the tile / lighting passes (highest priority measured the same:
@@ -632,11 +634,12 @@ extern "C" VR_API int vr_terrain_create(vr_context* ctx, const vr_terrain_params
         int least = 0, greatest = 0;
         VR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         for (hipStream_t& gs : t->geo_streams) VR_HIP(hipStreamCreateWithPriority(&gs, hipStreamNonBlocking, least));
-        for (GeoSet& g : t->sets) g.stream = t->geo_streams[0];
+        for (GeoSet& g : t->sets) g.ord.stream = t->geo_streams[0];
     }
-    VR_HIP(hipEventCreateWithFlags(&t->ev_main_dep, hipEventDisableTiming));
-    VR_HIP(hipEventCreateWithFlags(&t->ev_sel_copy, hipEventDisableTiming));
-    VR_HIP(hipEventCreateWithFlags(&t->ev_raster_begin, hipEventDisableTiming));
+    VR_HIP(hipEventCreateWithFlags(&t->ord.ev_changed, hipEventDisableTiming));
+    VR_HIP(hipEventCreateWithFlags(&t->ord.ev_sel_ready, hipEventDisableTiming));
+    VR_HIP(hipEventCreateWithFlags(&t->ord.hint.own, hipEventDisableTiming));
+    for (GeoSet& g : t->sets) g.ord.main_dep.ev = t->ord.ev_changed;      // (the sets share the terrain's one)
     *out = t;
     t = nullptr;                 // released to the caller
     return VR_OK;
@@ -648,13 +651,9 @@ extern "C" VR_API void vr_terrain_destroy(vr_terrain* t)
     (void)hipSetDevice(t->ctx->device);
     (void)hipStreamSynchronize(t->ctx->stream);
     for (hipStream_t gs : t->geo_streams) if (gs) { (void)hipStreamSynchronize(gs); (void)hipStreamDestroy(gs); }
-    if (t->ev_main_dep) (void)hipEventDestroy(t->ev_main_dep);
-    if (t->ev_sel_copy) (void)hipEventDestroy(t->ev_sel_copy);
-    if (t->ev_raster_begin) (void)hipEventDestroy(t->ev_raster_begin);
+    for (hipEvent_t e : { t->ord.ev_changed, t->ord.ev_sel_ready, t->ord.hint.own }) if (e) (void)hipEventDestroy(e);
     for (GeoSet& g : t->sets) {
-        if (g.ev_geo_done) (void)hipEventDestroy(g.ev_geo_done);
-        if (g.ev_raster_done) (void)hipEventDestroy(g.ev_raster_done);
-        if (g.ev_sel_read) (void)hipEventDestroy(g.ev_sel_read);
+        for (hipEvent_t e : { g.ord.chain.own, g.ord.tile_pass.own, g.ord.sel_read.ev }) if (e) (void)hipEventDestroy(e);
         (void)hipFree(g.d_node_ids); (void)hipFree(g.d_instances); (void)hipFree(g.d_counters); (void)hipFree(g.d_sel_scratch);
         (void)hipFree(g.d_hard_list); (void)hipFree(g.d_hard_tris);
         (void)hipFree(g.d_tile_count); (void)hipFree(g.d_tile_offset); (void)hipFree(g.d_tile_cursor); (void)hipFree(g.d_tile_order);
@@ -697,7 +696,7 @@ extern "C" VR_API int vr_terrain_download_mip(vr_terrain* t, int which, int leve
 static int read_counters(vr_terrain* t, uint32_t* count, bool selection_only = false)
 {
     uint32_t c[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    VR_HIP(hipStreamSynchronize(t->sets[t->cur].stream)); // selection and bins are produced on the set's geometry stream
+    VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream)); // selection and bins are produced on the set's geometry stream
     VR_HIP(hipMemcpyAsync(c, t->sets[t->cur].d_counters, sizeof(c), hipMemcpyDeviceToHost, t->ctx->stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     if (count) *count = selection_only ? c[7] : c[0];           // NodeSelect's list is complete up to max_instances whatever the scratch holds
@@ -747,17 +746,12 @@ extern "C" VR_API int vr_terrain_select(vr_terrain* t, const vr_view* view, floa
     // behind whatever the context's stream did to the terrain (heights)
     const int gi = vr_terrain_pick_set(t);                         // a set no tile pass in flight is reading
     GeoSet& g = t->sets[gi];
-    g.stream = t->geo_streams[t->geo_turn++ & 1u];
-    if (g.main_dep_pending) { VR_HIP(hipStreamWaitEvent(g.stream, t->ev_main_dep, 0)); g.main_dep_pending = false; }
-    // the set's previous chain may have run on the other geometry stream and may never have been rastered
-    if (g.geo_recorded) VR_HIP(hipStreamWaitEvent(g.stream, g.ev_geo_done, 0));
-    if (g.sel_read_pending) { VR_HIP(hipStreamWaitEvent(g.stream, g.ev_sel_read, 0)); g.sel_read_pending = false; }
-    if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == t->ctx->ev_epoch)) VR_HIP(hipStreamWaitEvent(g.stream, g.raster_done, 0));
-    g.prepared = false;
-    int rc = vr_select_launch(t, g, view, max_height, g.stream);
+    // (not part of a frame: never behind the context's stream as a whole, whatever VR_OPT_ASYNC_GEOMETRY says)
+    int rc = order_begin_chain(t->ord, g.ord, VrOrderOps(), t->geo_streams, t->geo_turn, t->ctx->stream, false, t->ctx->ev_epoch);
     if (rc) return rc;
-    VR_HIP(hipEventRecord(g.ev_geo_done, g.stream));           // this select is the set's latest writer
-    g.geo_recorded = true;
+    g.prepared = false;
+    if ((rc = vr_select_launch(t, g, view, max_height, g.ord.stream))) return rc;
+    if ((rc = order_end_chain(g.ord, VrOrderOps()))) return rc;           // this select is the set's latest writer
     t->cur = gi;
     if (!node_ids && !instances && !count) return VR_OK;       // stays asynchronous
     uint32_t n = 0;
@@ -780,7 +774,7 @@ extern "C" VR_API int vr_debug_render_stats(vr_terrain* t, uint32_t out[8])
 {
     VR_REQUIRE(t && out, "NULL argument");
     VR_HIP(hipSetDevice(t->ctx->device));
-    VR_HIP(hipStreamSynchronize(t->sets[t->cur].stream));
+    VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     const GeoSet& g = t->sets[t->cur];
     VR_HIP(hipMemcpy(out, g.d_counters, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -802,7 +796,7 @@ extern "C" VR_API int vr_debug_download_vertices(vr_terrain* t, uint32_t first, 
 {
     VR_REQUIRE(t && out, "NULL argument");
     VR_HIP(hipSetDevice(t->ctx->device));
-    VR_HIP(hipStreamSynchronize(t->sets[t->cur].stream));
+    VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     const GeoSet& g = t->sets[t->cur];
     uint32_t n = 0;
