@@ -226,6 +226,22 @@ def test_stream_order_matches_the_transcribed_protocol_and_the_happens_before_mo
     assert r.returncode == 0 and "16 of 17 wait sites reported" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
 
 
+def test_scratch_policy_matches_the_transcribed_code_and_its_invariants(tmp_path):
+    """vr_scratch.h compiles without HIP.  Over every sequence of one and two events and a fixed sample of longer ones
+    (tests/host/scratch_check.cpp: chains completing with boundary status words, polls, synchronous reads, reserves, a granting
+    or refusing allocator) its functions leave the state, return the codes, request the allocations and pick the messages of
+    the code they replaced, and keep the capacity, reporting and refusal invariants the program names."""
+    import subprocess
+    exe = os.path.join(str(tmp_path), "scratch_check")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "scratch_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    # 12 configurations x (730 + 730^2 of 730 events, 20000 random); 730 = 3 sets x 6 x 8 x 5 words + 2 + 2 + 4 + 2
+    assert "6643560 sequences" in r.stdout, r.stdout[-400:]
+
+
 def _build_allgather_example(tmpdir):
     import subprocess
     exe = os.path.join(str(tmpdir), "frame_allgather_example")

@@ -6,12 +6,14 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/vrterrain.h"
 #include "vr_devbuf.h"
 #include "vr_order.h"
+#include "vr_scratch.h"
 
 // ---- error plumbing -------------------------------------------------------------
 void vr_set_error(const char* fmt, ...);
@@ -317,10 +319,11 @@ struct vr_ldr_image {
 // Everything one frame's geometry stages produce and its tile pass consumes.  Three sets rotate: the tile pass of
 // frame N reads one while the geometry of frames N+1 and N+2 is built in the other two (vr_terrain_prepare).
 constexpr int kGeoSets = 3;
+static_assert(kGeoSets == kScratchSets, "ScratchState::pending has one flag per geometry set");
 struct GeoSet {
     uint32_t* d_node_ids = nullptr;      // select outputs
     vr_instance* d_instances = nullptr;
-    uint32_t* d_counters = nullptr;      // [0] selected count, [1] status flags, [2..7] frame work counters
+    uint32_t* d_counters = nullptr;      // 64 words: the status words and k_scan's classes (vr_scratch.h: C_*)
     uint32_t* d_sel_scratch = nullptr;   // k_select: the frontiers' overflow beyond their LDS part and the selected keys (one workgroup's scratch)
     DevVert* d_verts = nullptr;          // max_instances*1089 regular + extra (clipper) region
     uint64_t* d_rect = nullptr;          // per triangle: tile rect or ~0 when culled
@@ -332,12 +335,11 @@ struct GeoSet {
     uint32_t* d_tile_offset = nullptr;
     uint32_t* d_tile_cursor = nullptr;
     int32_t* d_tile_order = nullptr;     // launch order of the tile pass: this frame's tiles by falling bin length
-    TileEntry* d_bin_entries = nullptr;   // bin_capacity entries of 64 B (k_fill)
+    TileEntry* d_bin_entries = nullptr;   // ScratchState::bin_capacity entries of 64 B (k_fill)
     int scratch_tiles = 0;
     int last_tiles = 0;                  // raster tiles of the target the last chain was built for (the stride of d_tile_order's class regions)
     bool have_selection = false;
     VrOrderSet ord;                      // the set's stream, marks and pending readers (vr_order.h)
-    bool status_pending = false;         // the last chain's counters have not been read from the host mirror yet
     // vr_terrain_prepare: geometry already built for exactly these inputs
     bool prepared = false;
     uint64_t prep_serial = 0;            // order of the vr_terrain_prepare calls (the oldest prepared set is evicted first)
@@ -353,20 +355,14 @@ struct vr_terrain {
     uint8_t* d_height = nullptr; uint8_t* d_albedo = nullptr;
     uint64_t bytes_textures = 0, bytes_scratch = 0;     // vr_terrain_memory_bytes
     uint32_t extra_vert_cap = 0, hard_cap = 0;
-    size_t bin_capacity = 0;
-    // Per-frame scratch by HIGH-WATER MARK (round 4): vertices, triangle records and bins are sized for cap_instances nodes - not
-    // for params.max_instances (4096: 1.7 GB per geometry set, of which an 8K frame's ~300 nodes use a few percent).  Every
-    // chain leaves its counters in a pinned host mirror (k_fill's first act); the next API call reads the mirrors of the chains that
-    // have completed (hipEventQuery, no wait), keeps the largest node count seen and doubles the scratch BEFORE a frame can
-    // exceed it (count > half the capacity).  A frame that does exceed it - the count more than doubled within three frames -
-    // is drawn without the excess nodes and reported like the other device-side conditions: sticky, by the next vr_terrain_render.
-    int cap_instances = 0;
-    uint32_t* h_status = nullptr;          // kGeoSets x 8 words, hipHostMalloc (mapped)
+    // Per-frame scratch by high-water mark (vr_scratch.h): its capacities, what completed frames wanted, what is still to be reported.
+    ScratchState scratch;
+    // where the regions behind the per-node ones begin
+    uint32_t scratch_tris() const { return (uint32_t)scratch.cap_instances * (uint32_t)kTrisPerInst; }     // regular triangles; the clipper's follow
+    size_t clip_rec_base() const { return (size_t)scratch.cap_instances * kTrisPerInst * kRecGroups; }      // 16-byte groups into d_recs
+    uint32_t extra_vert_base() const { return (uint32_t)scratch.cap_instances * kVertsPerInst; }            // the clipper's vertices in d_verts
+    uint32_t* h_status = nullptr;          // kGeoSets x kStatusWords, hipHostMalloc (mapped)
     uint32_t* d_status = nullptr;          // the device's view of it
-    uint32_t high_water = 0;               // most nodes a completed frame selected
-    size_t bin_high_water = 0, bin_want = 0;   // most bin entries a completed frame wanted; the capacity asked for because of it
-    int sticky_error = 0;                  // VR_ERR_* of a completed frame, not yet reported
-    uint32_t sticky_count = 0;
     GeoSet sets[kGeoSets];
     int cur = 0;                            // set of the most recent select / render
     uint64_t prep_counter = 0;
@@ -400,9 +396,11 @@ int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, in
                           DevTex* out, uint8_t** out_mem, uint64_t* out_bytes = nullptr);
 int vr_select_launch(vr_terrain* t, GeoSet& g, const vr_view* view, float max_height, hipStream_t stream);
 int vr_terrain_pick_set(vr_terrain* t);
-// reads the counters of completed chains (no wait), grows the scratch by the high-water mark; returns a completed frame's sticky
-// device-side error once (VR_OK otherwise).  Called at the head of vr_terrain_render / vr_terrain_prepare / vr_terrain_select.
-int vr_terrain_poll(vr_terrain* t, bool report);
+// In front of a frame's geometry (vr_terrain_prepare, the tile pass; vr_select.hip).  Completed chains' status words are read (no
+// wait) and the scratch grows if due; with `report` a completed frame's device-side condition comes back once, in *earlier - it
+// does not stop the frame.  Then target(&tiles) - the call site's RasterArgs, which read the capacities - says how many raster tiles
+// this rank draws, the bins get room for them and *bin_capacity is what they hold.  Any other code ends the call at once.
+int vr_terrain_frame_scratch(vr_terrain* t, bool report, const std::function<int(size_t* tiles)>& target, int* earlier, uint32_t* bin_capacity);
 // vr_frame_submit's tile pass under VR_OPT_FRAME_FUSION (vr_raster.hip): vr_terrain_render of the whole frame that also shades
 // into hdr_out where the G-buffer-keeping fused flavour applies (*fused; *fused_stop = that launch's dispatch-stamped stop event
 // or NULL) and is exactly vr_terrain_render where it does not
@@ -416,7 +414,6 @@ int vr_deferred_light_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb,
                            const vr_shadow_binding* shadow, hipEvent_t* stop);
 int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
                                  const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop);
-int vr_terrain_reserve_bins(vr_terrain* t, size_t tiles);     // room for a target of that many raster tiles (vr_select.hip)
 // tables of (w, h, part); part == NULL is the whole frame as rank 0 of 1
 int vr_partition_tables(vr_context* ctx, int w, int h, const vr_partition* part, const PartTables** out);
 // any cached table set of (w, h, world): the slot table does not depend on the rank

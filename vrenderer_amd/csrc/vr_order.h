@@ -113,7 +113,7 @@ template <class Event> struct OrderImage {
 };
 
 // `single_stream`: the chain is part of a frame and VR_OPT_ASYNC_GEOMETRY is off.  (A set whose status slot the host has not read
-// yet - GeoSet::status_pending - would be waited for here, too.)
+// yet - ScratchState::pending - would be waited for here, too.)
 template <class Stream, class Event, class Ops>
 int order_begin_chain(OrderTerrain<Event>& t, OrderSet<Stream, Event>& g, const Ops& ops, const Stream (&geo_streams)[2], unsigned& turn,
                       Stream main, bool single_stream, uint64_t epoch_now)

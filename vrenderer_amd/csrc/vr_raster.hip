@@ -64,10 +64,7 @@ struct RasterArgs {
     float vp_x, vp_y, vp_w, vp_h;
 };
 
-// counters[]: 0 selected nodes, 1 status flags, 2 hard sub-triangles, 3 extra verts,
-//             4 hard-list length, 5 total bin entries, 8..15 raster tiles per bin-length class (k_scan)
-// (2..15 are reset by k_vertex, the first kernel of a chain that uses them)
-enum { C_COUNT = 0, C_FLAGS = 1, C_HARDTRIS = 2, C_XVERTS = 3, C_HARDLIST = 4, C_BINTOTAL = 5, C_CLASS0 = 8 };
+// counters[]: the status words and k_scan's classes, C_* (vr_scratch.h)
 
 
 // ---------------------------------------------------------------------------------------
@@ -91,9 +88,10 @@ __global__ __launch_bounds__(256) void k_vertex(VertexArgs a, DevTex hm, const v
                                                  uint32_t* __restrict__ counters, DevVert* __restrict__ verts)
 {
     VR_GEOMETRY_PRIORITY();
-    // first kernel of every frame: reset the frame's work counters (k_setup is the first to use them); words 6 and 7 are
-    // k_select's (the selection's size before truncation, NodeSelect's count) and stay
-    if (blockIdx.x == 0 && threadIdx.x < 14 && (threadIdx.x < 4 || threadIdx.x >= 6)) counters[2 + threadIdx.x] = 0u;
+    // first kernel of every frame: reset the frame's work counters, C_HARDTRIS .. C_BINTOTAL and the classes (k_setup is the first
+    // to use them); C_WANTED and C_SELECTED between them are k_select's and stay
+    constexpr uint32_t kEnd = C_END - C_HARDTRIS, kKeep0 = C_WANTED - C_HARDTRIS, kKeep1 = C_CLASS0 - C_HARDTRIS;
+    if (blockIdx.x == 0 && threadIdx.x < kEnd && (threadIdx.x < kKeep0 || threadIdx.x >= kKeep1)) counters[C_HARDTRIS + threadIdx.x] = 0u;
     __shared__ float r8[256];
     __shared__ uint32_t s_qoff[kMaxLevels];
     r8[threadIdx.x] = (float)threadIdx.x / 255.0f;     // UNORM8 -> float, correctly rounded
@@ -502,7 +500,7 @@ __device__ __forceinline__ void clip_hard_list(const RasterArgs& a, DevVert* __r
         const uint32_t vbase = atomicAdd(&counters[C_XVERTS], (uint32_t)n);
         const uint32_t tbase = atomicAdd(&counters[C_HARDTRIS], nsub);
         if (vbase + (uint32_t)n > a.extra_vert_cap || tbase + nsub > a.hard_cap * 4u) {
-            atomicOr(&counters[C_FLAGS], 2u); hard_first[tri] = 0xffffffffu; continue;
+            atomicOr(&counters[C_FLAGS], kStListFull); hard_first[tri] = 0xffffffffu; continue;
         }
         for (int i = 0; i < n; i++) {
             DevVert o;
@@ -544,6 +542,7 @@ __device__ __forceinline__ void clip_hard_list(const RasterArgs& a, DevVert* __r
 // Every class has its own region of `order` (class c from c * stride); a workgroup claims its tiles' places in each
 // with one atomic per class, and the tile pass finds workgroup i's tile from the eight class totals (tile_of_block).
 constexpr int kScanClasses = 8;
+static_assert(C_CLASS0 + kScanClasses == C_END, "the classes' counters");
 constexpr int kScanPerThread = 4, kScanPerGroup = 256 * kScanPerThread;
 __device__ __forceinline__ int scan_class(uint32_t cnt)
 {
@@ -602,7 +601,7 @@ __global__ __launch_bounds__(256) void k_scan(int n_tiles, uint32_t* __restrict_
         uint32_t* __restrict__ w = tid < kScanClasses ? &s_cls[tid * NW] : s_wsum;
         const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], total = (w0 + w1) + (w2 + w3);
         uint32_t base = total ? atomicAdd(&counters[tid < kScanClasses ? C_CLASS0 + tid : C_BINTOTAL], total) : 0u;
-        if (tid == kScanClasses) { if (base + total > capacity) atomicOr(&counters[C_FLAGS], 2u); }
+        if (tid == kScanClasses) { if (base + total > capacity) atomicOr(&counters[C_FLAGS], kStListFull); }
         else base += (uint32_t)tid * (uint32_t)n_tiles;   // the class's own region of `order`
         w[0] = base; w[1] = base + w0; w[2] = base + (w0 + w1); w[3] = base + (w0 + w1) + w2;
     }
@@ -665,7 +664,7 @@ __global__ __launch_bounds__(256) void k_setup(RasterArgs a, const DevVert* __re
                                  || (c2.x < -g2) || (c2.x > g2) || (c2.y < -g2) || (c2.y > g2);
             if (need_near || need_guard) {
                 const uint32_t slot = atomicAdd(&counters[C_HARDLIST], 1u);
-                if (slot < a.hard_cap) hard_list[slot] = tri; else atomicOr(&counters[C_FLAGS], 2u);
+                if (slot < a.hard_cap) hard_list[slot] = tri; else atomicOr(&counters[C_FLAGS], kStListFull);
             } else {
                 r = triangle_rect(a, load_sv(verts, i0), load_sv(verts, i1), load_sv(verts, i2), recs + (size_t)tri * kRecGroups);
             }
@@ -699,8 +698,8 @@ __global__ __launch_bounds__(256) void k_fill(RasterArgs a, const uint32_t* __re
 {
     VR_GEOMETRY_PRIORITY();
     // the chain's counters (node count, status flags, work-list lengths: all final before this launch) into the terrain's pinned
-    // host mirror: the host reads them without a wait once the chain's event has completed (vr_terrain_poll)
-    if (blockIdx.x == 0 && threadIdx.x < 8) { __hip_atomic_store(&status[threadIdx.x], counters[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+    // host mirror: the host reads them without a wait once the chain's event has completed (vr_select.hip: terrain_poll)
+    if (blockIdx.x == 0 && threadIdx.x < kStatusWords) { __hip_atomic_store(&status[threadIdx.x], counters[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
     const uint32_t n_reg = counters[C_COUNT] * (uint32_t)kTrisPerInst;
     const uint32_t n_hard = min(counters[C_HARDTRIS], a.hard_cap * 4u);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_reg + n_hard; i += gridDim.x * blockDim.x) {
@@ -1743,8 +1742,9 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE 
 // ---------------------------------------------------------------------------------------
 // host: TerrainPass::Render (TerrainPass.cpp:143-232)
 // ---------------------------------------------------------------------------------------
+// (*rank_tiles: the raster tiles this rank draws of the target - what vr_terrain_frame_scratch makes room for)
 static int make_raster_args(vr_terrain* t, const vr_view* view, const vr_render_params* rp, int w, int h, const vr_partition* part,
-                            RasterArgs& a)
+                            RasterArgs& a, size_t* rank_tiles)
 {
     const int world = part ? part->world_size : 1, rank = part ? part->rank : 0;
     VR_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad partition");
@@ -1758,6 +1758,7 @@ static int make_raster_args(vr_terrain* t, const vr_view* view, const vr_render_
     if (a.vy1 > h - 1) a.vy1 = h - 1;
     a.tile_shift = vr_raster_tile_shift(w, h, world, t->ctx->raster_tile_force);
     { const int rt = 1 << a.tile_shift; a.rtx = (w + rt - 1) / rt; a.rty = (h + rt - 1) / rt; }
+    *rank_tiles = (size_t)a.rtx * a.rty / (size_t)world;
     a.mirrored = view->mirrored; a.world = world; a.rank = rank;
     VR_REQUIRE(world <= 64, "at most 64 ranks");                 // (the owner-tile test's reciprocal multiplication is exact up to there)
     a.world_magic = (65536u + (uint32_t)world - 1u) / (uint32_t)world;
@@ -1765,8 +1766,7 @@ static int make_raster_args(vr_terrain* t, const vr_view* view, const vr_render_
     a.world_size = t->p.world_size; a.inv_world_size = 1.0f / t->p.world_size;
     { uint32_t wb; memcpy(&wb, &t->p.world_size, 4); a.ws_pow2 = (wb & 0x7fffffu) == 0u && t->p.world_size >= 1.0f && t->p.world_size <= 65536.0f; }
     a.lod_w = (float)t->height.w0 * a.inv_world_size; a.lod_h = (float)t->height.h0 * a.inv_world_size; a.max_level_f = (float)(t->height.levels - 1);
-    a.bin_capacity = (uint32_t)t->bin_capacity;
-    a.extra_vert_base = (uint32_t)t->cap_instances * kVertsPerInst; a.extra_vert_cap = t->extra_vert_cap; a.hard_cap = t->hard_cap;
+    a.extra_vert_base = t->extra_vert_base(); a.extra_vert_cap = t->extra_vert_cap; a.hard_cap = t->hard_cap;
     a.vp_x = (float)view->viewport_x; a.vp_y = (float)view->viewport_y; a.vp_w = (float)view->viewport_w; a.vp_h = (float)view->viewport_h;
     return VR_OK;
 }
@@ -1794,7 +1794,7 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
         rc = order_copy_selection(t->ord, g.ord, selection_from->ord, ops, [&]() -> int {
             VR_HIP(hipMemcpyAsync(g.d_node_ids, from.d_node_ids, (size_t)t->p.max_instances * sizeof(uint32_t), hipMemcpyDeviceToDevice, gs));
             VR_HIP(hipMemcpyAsync(g.d_instances, from.d_instances, (size_t)t->p.max_instances * sizeof(vr_instance), hipMemcpyDeviceToDevice, gs));
-            VR_HIP(hipMemcpyAsync(g.d_counters, from.d_counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, gs));
+            VR_HIP(hipMemcpyAsync(g.d_counters, from.d_counters, (C_FLAGS + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, gs));     // C_COUNT, C_FLAGS
             return VR_OK;
         });
         if (rc) return rc;
@@ -1824,7 +1824,7 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
     hipLaunchKernelGGL(k_setup, dim3(kGridSetup), dim3(256), 0, gs, a, g.d_verts, g.d_counters, g.d_rect, g.d_hard_list, g.d_tile_count, g.d_recs); }
     { VrKernelScope ks(ctx, VR_K_CLIP, gs);
     hipLaunchKernelGGL(k_clip, dim3(64), dim3(64), 0, gs, a, g.d_verts, g.d_counters, g.d_hard_list, g.d_hard_tris, g.d_hard_first, g.d_tile_count,
-                       g.d_recs + (size_t)t->cap_instances * kTrisPerInst * kRecGroups); }
+                       g.d_recs + t->clip_rec_base()); }
     { VrKernelScope ks(ctx, VR_K_SCAN, gs);
     const bool whole = pt == nullptr;
     const int n_scan = whole ? n_tiles : pt->num_raster_tiles;
@@ -1834,8 +1834,8 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
                            g.d_tile_order); }
     { VrKernelScope ks(ctx, VR_K_FILL, gs);
     hipLaunchKernelGGL(k_fill, dim3(kGridFill), dim3(256), 0, gs, a, g.d_counters, g.d_rect, g.d_hard_tris, (const uint4*)g.d_recs,
-                       (uint32_t)t->cap_instances * (uint32_t)kTrisPerInst, g.d_tile_cursor, g.d_bin_entries, t->d_status + (size_t)(&g - t->sets) * 8); }
-    g.status_pending = true;
+                       t->scratch_tris(), g.d_tile_cursor, g.d_bin_entries, t->d_status + (size_t)(&g - t->sets) * kStatusWords); }
+    scratch_chain_queued(t->scratch, (int)(&g - t->sets));
     if ((rc = order_end_chain(g.ord, ops))) return rc;
     VR_HIP(hipGetLastError());
     return VR_OK;
@@ -1891,11 +1891,9 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
     VR_REQUIRE(!rp->lock_view, "vr_terrain_prepare builds a new selection; it cannot be combined with lock_view");
     VR_HIP(hipSetDevice(t->ctx->device));
     // completed chains' counters: the scratch grows here if due (a sticky condition is vr_terrain_render's to report)
-    if ((rc = vr_terrain_poll(t, false))) return rc;
     RasterArgs a;
-    if ((rc = make_raster_args(t, view, rp, gb->w, gb->h, part, a))) return rc;
-    if ((rc = vr_terrain_reserve_bins(t, (size_t)a.rtx * a.rty / (size_t)(a.world > 1 ? a.world : 1)))) return rc;
-    a.bin_capacity = (uint32_t)t->bin_capacity;
+    int earlier;
+    if ((rc = vr_terrain_frame_scratch(t, false, [&](size_t* tiles) { return make_raster_args(t, view, rp, gb->w, gb->h, part, a, tiles); }, &earlier, &a.bin_capacity))) return rc;
     const PartTables* pt = nullptr;       // this rank's raster tiles; unused (NULL) for the whole frame
     if (a.world > 1 && (rc = vr_partition_tables(t->ctx, gb->w, gb->h, part, &pt))) return rc;
     // already prepared for exactly these inputs (a caller may name the same future frame twice): nothing to do
@@ -1983,12 +1981,9 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     hipStream_t s = ctx->stream;
     // what earlier frames' chains left in the host mirror: grows the scratch if due, and a device-side condition of a completed
     // frame (too many nodes, a full work list) is returned - once - behind this frame's launches
-    const int earlier = vr_terrain_poll(t, true);
-    if (earlier && earlier != VR_ERR_OVERFLOW && earlier != VR_ERR_TOO_MANY_INSTANCES) return earlier;     // (the scratch could not grow)
     RasterArgs a;
-    if ((rc = make_raster_args(t, view, rp, gb->w, gb->h, part, a))) return rc;
-    if ((rc = vr_terrain_reserve_bins(t, (size_t)a.rtx * a.rty / (size_t)(a.world > 1 ? a.world : 1)))) return rc;
-    a.bin_capacity = (uint32_t)t->bin_capacity;
+    int earlier;
+    if ((rc = vr_terrain_frame_scratch(t, true, [&](size_t* tiles) { return make_raster_args(t, view, rp, gb->w, gb->h, part, a, tiles); }, &earlier, &a.bin_capacity))) return rc;
     const PartTables* pt = nullptr;       // this rank's raster tiles; unused (NULL) for the whole frame
     if (a.world > 1 && (rc = vr_partition_tables(ctx, gb->w, gb->h, part, &pt))) return rc;
     const int grid = pt ? pt->num_raster_tiles : a.rtx * a.rty;
@@ -2047,7 +2042,7 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         uint8_t* region = nullptr;
         if ((rc = vr_gbuffer_apply_plan(gb, plan, s, a.rank, a.world, &region))) return rc;
 #define VR_RASTER_ARGS a, t->height, t->albedo, g.d_verts, g.d_hard_tris, g.d_hard_first, \
-                           (const uint4*)g.d_recs, (uint32_t)t->cap_instances * (uint32_t)kTrisPerInst, g.d_tile_cursor, g.d_tile_offset, g.d_bin_entries, tiles, g.d_counters + C_CLASS0, \
+                           (const uint4*)g.d_recs, t->scratch_tris(), g.d_tile_cursor, g.d_tile_offset, g.d_bin_entries, tiles, g.d_counters + C_CLASS0, \
                            gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, ctx->d_srgb_thr, ctx->d_enc_tab, spec_const, plan.ranges ? gb->d_ranges : (uint2*)nullptr, region
         const RasterKernel k = raster_kernel(plan.variant);
         if (k.lit) VR_LAUNCH_TIMED(ks, k.lit, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);

@@ -242,14 +242,14 @@ __global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a, uint32_t* 
     if (tid == 0) for (int q = 0; q < 4; q++) { selected[kSelectedCap - 8 + 2 * q] = (uint32_t)prof_t[q]; selected[kSelectedCap - 7 + 2 * q] = (uint32_t)(prof_t[q] >> 32); }
 #endif
     if (tid == 0) {
-        counters[0] = min(limit, (uint32_t)a.cap_instances);                   // what the rest of the chain draws: as many as its scratch holds
-        counters[7] = limit;                                                   // what NodeSelect returns
+        counters[C_COUNT] = min(limit, (uint32_t)a.cap_instances);             // what the rest of the chain draws: as many as its scratch holds
+        counters[C_SELECTED] = limit;                                          // what NodeSelect returns
         uint32_t flags = 0;
-        if (n_sel > (uint32_t)a.max_instances) flags |= 1u;      // VR_ERR_TOO_MANY_INSTANCES
-        else if (n_sel > (uint32_t)a.cap_instances) flags |= 4u; // more than the scratch holds (it grows: vr_terrain_poll)
-        counters[6] = n_sel;                                     // the count before any truncation (the scratch's high-water mark)
-        if (overflow) flags |= 2u;                               // VR_ERR_OVERFLOW
-        counters[1] = flags;
+        if (n_sel > (uint32_t)a.max_instances) flags |= kStTooMany;           // VR_ERR_TOO_MANY_INSTANCES
+        else if (n_sel > (uint32_t)a.cap_instances) flags |= kStScratchShort; // more than the scratch holds (it grows: terrain_poll)
+        counters[C_WANTED] = n_sel;                              // the count before any truncation (the scratch's high-water mark)
+        if (overflow) flags |= kStListFull;                      // VR_ERR_OVERFLOW
+        counters[C_FLAGS] = flags;
     }
 }
 
@@ -260,7 +260,7 @@ int vr_select_launch(vr_terrain* t, GeoSet& g, const vr_view* view, float max_he
     for (int i = 0; i < 6; i++) for (int j = 0; j < 4; j++) a.planes[i][j] = view->planes[i][j];
     for (int i = 0; i < VR_MAX_LODS; i++) a.range2[i] = t->lod_ranges[i] * t->lod_ranges[i];
     a.half_w = t->p.surface_size / 2.0f; a.half_h = t->p.surface_size / 2.0f;
-    a.num_lods = t->num_lods; a.max_instances = t->p.max_instances; a.cap_instances = t->cap_instances; a.max_height = max_height;
+    a.num_lods = t->num_lods; a.max_instances = t->p.max_instances; a.cap_instances = t->scratch.cap_instances; a.max_height = max_height;
     a.height_loaded = (t->height_loaded && t->d_node_heights) ? 1 : 0;
     a.surfaces_per_side = t->surfaces_per_side; a.num_surfaces = t->surfaces_per_side * t->surfaces_per_side;
     a.surface_size = t->p.surface_size;
@@ -473,7 +473,7 @@ extern "C" VR_API int vr_terrain_download_node_heights(vr_terrain* t, uint32_t f
 }
 
 // ---- terrain object -------------------------------------------------------------------
-// The part of a terrain's per-frame scratch that scales with the number of nodes a frame selects (vr_terrain::cap_instances).
+// The part of a terrain's per-frame scratch that scales with the number of nodes a frame selects (ScratchState::cap_instances, vr_scratch.h).
 static void free_scratch(vr_terrain* t)
 {
     for (GeoSet& g : t->sets) {
@@ -487,11 +487,8 @@ static int alloc_scratch(vr_terrain* t, int cap, size_t bin_want)
 {
     const size_t mi = (size_t)cap, fixed = (size_t)t->p.max_instances * (sizeof(uint32_t) + sizeof(vr_instance)) + 64 * sizeof(uint32_t)
                     + kSelScratchWords * sizeof(uint32_t) + (size_t)t->hard_cap * (sizeof(uint32_t) + 4 * sizeof(HardTriRec));
-    // (triangle, tile) pairs: an 8K frame of ~300 nodes has ~0.3 M, a 1080p frame ~0.6 M; 1 M per 1024 nodes and never fewer
-    // - or what the frames seen so far asked for (a large target on 32-pixel tiles: every triangle lands in more bins)
-    size_t bins = ((size_t)1 << 20) * ((mi + 1023) / 1024);
-    if (const char* e = getenv("VR_SCRATCH_INITIAL_BINS")) { const long v = atol(e); if (v >= 1024) bins = (size_t)v; }   // (tests: force the growth path)
-    if (bin_want > bins) bins = bin_want;
+    const char* e = getenv("VR_SCRATCH_INITIAL_BINS");
+    const size_t bins = scratch_bins(cap, e ? atol(e) : 0, bin_want);
     const size_t per_set[5] = { (mi * kVertsPerInst + t->extra_vert_cap) * sizeof(DevVert), mi * kTrisPerInst * sizeof(uint64_t),
                                 (mi * kTrisPerInst + (size_t)t->hard_cap * 4) * kRecGroups * sizeof(uint4), mi * kTrisPerInst * sizeof(uint32_t),
                                 bins * sizeof(TileEntry) };
@@ -507,64 +504,45 @@ static int alloc_scratch(vr_terrain* t, int cap, size_t bin_want)
         return VR_OK;
     });
     if (rc) return rc;
-    t->cap_instances = cap; t->bin_capacity = bins; t->bin_want = bin_want; t->bytes_scratch = total;
+    scratch_allocated(t->scratch, cap, bins, bin_want); t->bytes_scratch = total;
     for (GeoSet& g : t->sets) g.prepared = false;    // geometry built for the old buffers is gone (a selection lives in the fixed part: kept)
     return VR_OK;
 }
 
-// A target of `tiles` raster tiles is about to be drawn: make room for ~8 bin entries per tile up front (measured: 9.3 per tile at
-// 8K, 5.9 at 15360x8640, 4.7 at 16384^2 - the terrain's triangles grow with the frame, the tiles do not), so that the first frame
-// on a very large target does not have to overflow before the bins grow.
-int vr_terrain_reserve_bins(vr_terrain* t, size_t tiles)
+// Reads the status words of completed chains (no wait) and grows the scratch if they say so; with `report`, returns a completed
+// frame's device-side condition once (VR_OK otherwise).  The rules are vr_scratch.h's.
+static int terrain_poll(vr_terrain* t, bool report)
 {
-    const size_t est = tiles * 8;
-    if (est <= t->bin_capacity) return VR_OK;
-    size_t b = t->bin_capacity ? t->bin_capacity : ((size_t)1 << 20);
-    while (b < est) b *= 2;
-    VR_HIP(hipSetDevice(t->ctx->device));
-    return alloc_scratch(t, t->cap_instances, b);       // (VR_ERR_OUT_OF_MEMORY: the bins stay as they are, and say so)
+    ScratchState& s = t->scratch;
+    for (int i = 0; i < kGeoSets; i++) {
+        const GeoSet& g = t->sets[i];
+        if (s.pending[i] && g.ord.chain.set && hipEventQuery(g.ord.chain.own) == hipSuccess) scratch_observe(s, i, t->h_status + i * kStatusWords);
+    }
+    const ScratchGrowth grow = scratch_growth(s, t->p.max_instances);
+    if (grow.due) {
+        VR_HIP(hipSetDevice(t->ctx->device));
+        const int rc = alloc_scratch(t, grow.cap, grow.bin_want);
+        if (rc) { scratch_refused(s); return rc; }
+    }
+    if (!report) return VR_OK;
+    const ScratchReport r = scratch_take_report(s);
+    if (r.code == VR_ERR_TOO_MANY_INSTANCES) vr_set_error("an earlier frame selected %u nodes, more than max_instances (TerrainPass.cpp:238 assert); it was drawn without the excess", r.count);
+    else if (r.code) vr_set_error("an earlier frame (%u nodes) overflowed a work list or the scratch: triangles or nodes were dropped (the scratch now holds %d nodes)", r.count, s.cap_instances);
+    return r.code;
 }
 
-int vr_terrain_poll(vr_terrain* t, bool report)
+int vr_terrain_frame_scratch(vr_terrain* t, bool report, const std::function<int(size_t* tiles)>& target, int* earlier, uint32_t* bin_capacity)
 {
-    uint32_t seen = 0;
-    for (int i = 0; i < kGeoSets; i++) {
-        GeoSet& g = t->sets[i];
-        if (!g.status_pending || !g.ord.chain.set || hipEventQuery(g.ord.chain.own) != hipSuccess) continue;
-        g.status_pending = false;
-        const volatile uint32_t* st = t->h_status + i * 8;
-        const uint32_t flags = st[1], wanted = st[6];
-        if (wanted > seen) seen = wanted;
-        if ((size_t)st[5] > t->bin_high_water) t->bin_high_water = (size_t)st[5];     // (triangle, tile) pairs the frame wanted
-        if (flags & 1u) { t->sticky_error = VR_ERR_TOO_MANY_INSTANCES; t->sticky_count = wanted; }
-        else if (flags & 6u) { if (!t->sticky_error) t->sticky_error = VR_ERR_OVERFLOW; t->sticky_count = wanted; }
-    }
-    if (seen > t->high_water) t->high_water = seen;
-    // grow before a frame can outgrow the scratch: twice the largest count seen, once that passes half the capacity
-    const int max_i = t->p.max_instances;
-    const bool grow_nodes = t->cap_instances < max_i && (size_t)t->high_water * 2 > (size_t)t->cap_instances;
-    const bool grow_bins = t->bin_high_water * 2 > t->bin_capacity;            // (the same rule for the bins: twice what was seen)
-    if (grow_nodes || grow_bins) {
-        int want = t->cap_instances;
-        while (want < max_i && (size_t)t->high_water * 2 > (size_t)want) want *= 2;
-        if (want > max_i) want = max_i;
-        size_t bin_want = t->bin_want;
-        if (grow_bins) { bin_want = t->bin_capacity; while (bin_want < t->bin_high_water * 2) bin_want *= 2; }
+    *earlier = terrain_poll(t, report);
+    if (*earlier && *earlier != VR_ERR_OVERFLOW && *earlier != VR_ERR_TOO_MANY_INSTANCES) return *earlier;     // (the scratch could not grow)
+    size_t tiles = 0;
+    int rc = target(&tiles);
+    if (rc) return rc;
+    if (const size_t bins = scratch_reserve(t->scratch, tiles)) {
         VR_HIP(hipSetDevice(t->ctx->device));
-        const int rc = alloc_scratch(t, want, bin_want);
-        if (rc) {
-            // the larger scratch does not fit: the old one is still there (frames that need more stay truncated and reported)
-            t->bin_want = 0; t->high_water = 0; t->bin_high_water = 0;
-            return rc;
-        }
+        if ((rc = alloc_scratch(t, t->scratch.cap_instances, bins))) return rc;       // (VR_ERR_OUT_OF_MEMORY: the bins stay as they are, and say so)
     }
-    if (report && t->sticky_error) {
-        const int e = t->sticky_error;
-        t->sticky_error = VR_OK;
-        if (e == VR_ERR_TOO_MANY_INSTANCES) vr_set_error("an earlier frame selected %u nodes, more than max_instances (TerrainPass.cpp:238 assert); it was drawn without the excess", t->sticky_count);
-        else vr_set_error("an earlier frame (%u nodes) overflowed a work list or the scratch: triangles or nodes were dropped (the scratch now holds %d nodes)", t->sticky_count, t->cap_instances);
-        return e;
-    }
+    *bin_capacity = (uint32_t)t->scratch.bin_capacity;
     return VR_OK;
 }
 
@@ -612,8 +590,8 @@ extern "C" VR_API int vr_terrain_create(vr_context* ctx, const vr_terrain_params
         if (e_ == hipSuccess) e_ = hipMalloc(&g.d_hard_tris, (size_t)t->hard_cap * 4 * sizeof(HardTriRec));
         if (e_ != hipSuccess) { vr_set_error("hipMalloc failed: %s", hipGetErrorString(e_)); return VR_ERR_OUT_OF_MEMORY; }
     }
-    VR_HIP(hipHostMalloc((void**)&t->h_status, kGeoSets * 8 * sizeof(uint32_t), hipHostMallocMapped));
-    memset(t->h_status, 0, kGeoSets * 8 * sizeof(uint32_t));
+    VR_HIP(hipHostMalloc((void**)&t->h_status, kGeoSets * kStatusWords * sizeof(uint32_t), hipHostMallocMapped));
+    memset(t->h_status, 0, kGeoSets * kStatusWords * sizeof(uint32_t));
     VR_HIP(hipHostGetDevicePointer((void**)&t->d_status, t->h_status, 0));
     {   // what the scratch holds to begin with: 1024 nodes (a 2048^2 world selects 300-600), or everything (VR_OPT_SCRATCH_WORST_CASE);
         // VR_SCRATCH_INITIAL_NODES (environment) lets a test start smaller and watch it grow, VR_ALLOC_FAIL_ABOVE (vr_dev_alloc) refuse a growth
@@ -695,31 +673,20 @@ extern "C" VR_API int vr_terrain_download_mip(vr_terrain* t, int which, int leve
 
 static int read_counters(vr_terrain* t, uint32_t* count, bool selection_only = false)
 {
-    uint32_t c[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    uint32_t c[kStatusWords] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream)); // selection and bins are produced on the set's geometry stream
     VR_HIP(hipMemcpyAsync(c, t->sets[t->cur].d_counters, sizeof(c), hipMemcpyDeviceToHost, t->ctx->stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
-    if (count) *count = selection_only ? c[7] : c[0];           // NodeSelect's list is complete up to max_instances whatever the scratch holds
-    t->sets[t->cur].status_pending = false;                     // read here; not reported a second time
-    if (c[1] & 1u) { vr_set_error("more than max_instances nodes selected (TerrainPass.cpp:238 assert)"); return VR_ERR_TOO_MANY_INSTANCES; }
-    if ((size_t)c[5] > t->bin_high_water) t->bin_high_water = (size_t)c[5];
-    if (c[1] & 2u) {
-        // a full work list: if it was the bins, they grow now (twice what this frame wanted) and rendering the frame again is complete
-        (void)vr_terrain_poll(t, false);
-        vr_set_error("internal work list overflowed (the frame wanted %u bin entries; the bins now hold %zu)", c[5], t->bin_capacity);
-        return VR_ERR_OVERFLOW;
-    }
-    if (c[1] & 4u) {
-        // the frame wanted more nodes than the scratch held: grow now, so that rendering the frame again is complete
-        if (c[6] > t->high_water) t->high_water = c[6];
-        (void)vr_terrain_poll(t, false);
-        if (selection_only) return VR_OK;                       // (a selection alone needs no scratch)
-        t->sticky_error = VR_OK;
-        vr_set_error("the frame selected more nodes than the scratch held (drawn without the excess); the scratch has been grown to %d nodes - render again",
-                     t->cap_instances);
-        return VR_ERR_OVERFLOW;
-    }
-    return VR_OK;
+    if (count) *count = selection_only ? c[C_SELECTED] : c[C_COUNT];   // NodeSelect's list is complete up to max_instances whatever the scratch holds
+    ScratchState& s = t->scratch;
+    const ScratchRead r = scratch_read(s, t->cur, c, selection_only);
+    if (r.poll) (void)terrain_poll(t, false);
+    if (r.drop_report) (void)scratch_take_report(s);
+    if (r.kind == SCRATCH_READ_TOO_MANY) vr_set_error("more than max_instances nodes selected (TerrainPass.cpp:238 assert)");
+    else if (r.kind == SCRATCH_READ_LIST_FULL) vr_set_error("internal work list overflowed (the frame wanted %u bin entries; the bins now hold %zu)", c[C_BINTOTAL], s.bin_capacity);
+    else if (r.kind == SCRATCH_READ_SHORT) vr_set_error("the frame selected more nodes than the scratch held (drawn without the excess); the scratch has been grown to %d nodes - render again",
+                                                        s.cap_instances);
+    return r.code;
 }
 
 // The set the next select / geometry build goes to: never the current one (a tile pass may be reading it and lock_view
@@ -741,7 +708,7 @@ extern "C" VR_API int vr_terrain_select(vr_terrain* t, const vr_view* view, floa
     VR_REQUIRE(t && view, "NULL argument");
     VR_HIP(hipSetDevice(t->ctx->device));
     // (grows the scratch if due; a sticky condition of an earlier frame is vr_terrain_render's to report)
-    { const int prc = vr_terrain_poll(t, false); if (prc) return prc; }
+    { const int prc = terrain_poll(t, false); if (prc) return prc; }
     // the selection buffers are consumed by geometry-stream kernels: order this launch behind them and
     // behind whatever the context's stream did to the terrain (heights)
     const int gi = vr_terrain_pick_set(t);                         // a set no tile pass in flight is reading
@@ -777,12 +744,12 @@ extern "C" VR_API int vr_debug_render_stats(vr_terrain* t, uint32_t out[8])
     VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     const GeoSet& g = t->sets[t->cur];
-    VR_HIP(hipMemcpy(out, g.d_counters, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VR_HIP(hipMemcpy(out, g.d_counters, (C_BINTOTAL + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
 #ifdef VR_SELECT_PROFILE
     { unsigned long long ts[4]; VR_HIP(hipMemcpy(ts, g.d_sel_scratch + 2 * (kFrontierCap - kFrontLds) + kSelectedCap - 8, sizeof(ts), hipMemcpyDeviceToHost));
       fprintf(stderr, "k_select cycles: levels %llu  rank %llu  write-out %llu\n", ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2]); }
 #endif
-    out[6] = 0; out[7] = 0;
+    out[6] = 0; out[7] = 0;              // (of the statistics, not status words: the longest bin, bins in use)
     if (g.scratch_tiles > 0 && g.d_tile_cursor) {
         std::vector<uint32_t> c((size_t)g.scratch_tiles), o((size_t)g.scratch_tiles);
         VR_HIP(hipMemcpy(c.data(), g.d_tile_cursor, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -800,7 +767,7 @@ extern "C" VR_API int vr_debug_download_vertices(vr_terrain* t, uint32_t first, 
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     const GeoSet& g = t->sets[t->cur];
     uint32_t n = 0;
-    VR_HIP(hipMemcpy(&n, g.d_counters, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VR_HIP(hipMemcpy(&n, g.d_counters + C_COUNT, sizeof(uint32_t), hipMemcpyDeviceToHost));
     VR_REQUIRE((uint64_t)first + count <= (uint64_t)n * kVertsPerInst, "vertex range exceeds the last draw's instances");
     std::vector<DevVert> v(count);
     if (count) VR_HIP(hipMemcpy(v.data(), g.d_verts + first, (size_t)count * sizeof(DevVert), hipMemcpyDeviceToHost));
