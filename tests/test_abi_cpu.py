@@ -242,6 +242,26 @@ def test_scratch_policy_matches_the_transcribed_code_and_its_invariants(tmp_path
     assert "6643560 sequences" in r.stdout, r.stdout[-400:]
 
 
+def test_gbuffer_state_matches_the_transcribed_code_and_the_memory_model(tmp_path):
+    """vr_gbuffer_state.h compiles without HIP.  Over every sequence of one and two events, every sequence of up to four of a
+    smaller set and a fixed sample of longer ones (tests/host/gbuffer_state_check.cpp: clears, renders of every variant over
+    every coverage - run or refused at each point -, lighting passes, uploads, download, describe, the tracking switched) its
+    transitions leave the state, the answers and the fills of the code they replaced, apart from the two intended differences
+    the program names, and the memory they describe is what it would be with every clear eager and nothing skipped; each
+    transition weakened in turn is reported."""
+    import subprocess
+    exe = os.path.join(str(tmp_path), "gbuffer_state_check")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "gbuffer_state_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    # 2089 + 2089^2 of all events, 57 + .. + 57^4 of the smaller set, 200000 random
+    assert "15310510 sequences" in r.stdout, r.stdout[-400:]
+    r = subprocess.run([exe, "--break-each"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "15 of 15 weakenings reported" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+
+
 def _build_allgather_example(tmpdir):
     import subprocess
     exe = os.path.join(str(tmpdir), "frame_allgather_example")

@@ -2779,3 +2779,76 @@ def test_both_tile_sizes_bit_exact_against_the_oracle(scene2048, oracle, gpu_ctx
     finally:
         gpu_ctx.set_raster_tile(0)
         rt.close()
+
+
+@pytest.mark.gpu
+def test_a_pending_clear_survives_a_refused_render(scene256, oracle, gpu_ctx, monkeypatch):
+    """A Clear the host asked for is never lost: a whole-frame render that would have consumed the pending clear and is then
+    refused (the G-buffer's region array cannot be allocated, VR_ALLOC_FAIL_ABOVE) leaves the clear pending - the planes read
+    as cleared, every region counts as clear, and the next render is the oracle's frame.  The terrain has rendered at this size
+    and renders again, into a G-buffer that has its arrays, while allocations are refused: the refusal below is the fresh
+    G-buffer's own allocation, not the tile arrays'."""
+    ot, tp = scene256["ot"], scene256["tp"]
+    w, h = 256, 144
+    v = vr.make_view(*scaled_camera(CAMERAS[0], 256), w, h)
+    rp = vr.default_render_params(400.0)
+    want = oracle.GBufferHost(w, h)
+    ot.render(v, want, rp)
+    names = ("depth", "diffuse", "specular", "normals", "emissive")
+    rt0, rt = vr.RenderTargets(gpu_ctx).Init(w, h), vr.RenderTargets(gpu_ctx).Init(w, h)
+    try:
+        for _ in range(3):                                   # (every one of the terrain's geometry sets has its tile arrays)
+            tp.Render(v, v, rt0, rp)
+        rt.upload("diffuse", np.full((h, w), 0x01020304, np.uint32))
+        rt.Clear()                                           # lazy: nothing is written yet
+        monkeypatch.setenv("VR_ALLOC_FAIL_ABOVE", "1")
+        tp.Render(v, v, rt0, rp)                             # nothing of the terrain's needs memory
+        with pytest.raises(vr.VrError) as e:
+            tp.Render(v, v, rt, rp)
+        monkeypatch.delenv("VR_ALLOC_FAIL_ABOVE")
+        assert e.value.code == vr.capi.VR_ERR_OUT_OF_MEMORY, e.value
+        assert not rt.download("diffuse").any()
+        census = rt.region_census()
+        assert census["clear"] == census["total"] > 0, census
+        tp.Render(v, v, rt, rp)
+        _assert_gbuffer_equal(want, {k: rt.download(k) for k in names}, "the render after the refused one")
+    finally:
+        monkeypatch.delenv("VR_ALLOC_FAIL_ABOVE", raising=False)
+        rt0.close(); rt.close()
+
+
+@pytest.mark.gpu
+def test_depth_ranges_survive_a_refused_render(scene256, gpu_ctx, monkeypatch):
+    """A tile pass with depth_ranges = 1 that is refused while it prepares (the region array cannot be allocated; the ranges
+    array exists, left VALID by an earlier pass that ran without the tracking) leaves the ranges what they were: the tiled
+    lighting pass behind it gives, bit for bit, what it gives with the depth plane re-read (its second call: the ranges are
+    consumed by then) - not a frame whose point lights were all culled against ranges that no pass ever filled."""
+    tp = scene256["tp"]
+    w, h = 256, 144
+    v, v2 = (vr.make_view(*scaled_camera(CAMERAS[i], 256), w, h) for i in (0, 5))
+    rp = vr.default_render_params(400.0, assume_cleared=1, depth_ranges=1)
+    lights = _scene_lights(scene256, 64)
+    rt, rt0 = vr.RenderTargets(gpu_ctx).Init(w, h), vr.RenderTargets(gpu_ctx).Init(w, h)
+    hdr = vr.HdrImage(gpu_ctx, w, h)
+    tiled = vr.TiledDeferredLightingPass(gpu_ctx)
+    try:
+        for _ in range(3):                                   # (every one of the terrain's geometry sets has its tile arrays)
+            tp.Render(v2, v2, rt0, rp)
+        gpu_ctx.set_plane_tracking(False)
+        tp.Render(v, v, rt, rp)                              # ranges allocated and VALID, no region array yet
+        gpu_ctx.set_plane_tracking(True)
+        monkeypatch.setenv("VR_ALLOC_FAIL_ABOVE", "1")
+        with pytest.raises(vr.VrError) as e:
+            tp.Render(v2, v2, rt, rp)
+        monkeypatch.delenv("VR_ALLOC_FAIL_ABOVE")
+        assert e.value.code == vr.capi.VR_ERR_OUT_OF_MEMORY, e.value
+        tiled.Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+        first = hdr.download().copy()
+        tiled.Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)          # the depth plane re-read
+        tiled.Status()
+        assert np.array_equal(first, hdr.download())
+        assert first.any()
+    finally:
+        monkeypatch.delenv("VR_ALLOC_FAIL_ABOVE", raising=False)
+        gpu_ctx.set_plane_tracking(True)
+        hdr.close(); rt0.close(); rt.close()

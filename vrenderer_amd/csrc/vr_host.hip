@@ -470,12 +470,12 @@ static int fill_u32(hipStream_t s, void* ptr, size_t count, uint32_t v)
     return VR_OK;
 }
 
-// (anything that writes the G-buffer without leaving depth ranges: they are stale)
-static void gbuffer_touch(vr_gbuffer* g) { if (g->ranges_state == vr_gbuffer::RANGES_VALID) g->ranges_state = vr_gbuffer::RANGES_DIRTY; }
-
-static int gbuffer_clear_now(vr_gbuffer* g, hipStream_t s)
+// ---- what the library knows of a G-buffer: vr_gbuffer_state.h decides, the functions below do the HIP work it names ----------
+// gbs_clear_requested / gbs_materialise: the state in front of the fills, gbs_clear_written behind them
+static int gbuffer_clear_step(vr_gbuffer* g, const GbufferStep& step, hipStream_t s)
 {
-    gbuffer_touch(g);
+    g->st = step.after;
+    if (!step.work.clear_now) return VR_OK;
     size_t n = (size_t)g->w * g->h;
     int rc;
     VrKernelScope scope(g->ctx, VR_K_CLEAR, s);
@@ -484,9 +484,7 @@ static int gbuffer_clear_now(vr_gbuffer* g, hipStream_t s)
     if ((rc = fill_u32(s, g->specular, n, 0u))) return rc;
     if ((rc = fill_u32(s, g->normals, n * 2, 0u))) return rc;
     if ((rc = fill_u32(s, g->emissive, n * 2, 0u))) return rc;
-    g->emissive_zero = true;               // (stream-ordered: every later pass on the context's stream sees the zeros)
-    g->region_fill = (int)kRegionClear;    // every region holds the clear values (the array is filled when a tile pass next asks for it)
-    g->clear_pending = false;
+    g->st = gbs_clear_written(g->st);
     return VR_OK;
 }
 
@@ -494,35 +492,37 @@ extern "C" VR_API int vr_gbuffer_clear(vr_gbuffer* g)
 {
     VR_REQUIRE(g != nullptr, "gbuffer is NULL");
     VR_HIP(hipSetDevice(g->ctx->device));
-    if (g->ctx->plane_tracking && !g->escaped && g->cleared_once) {
-        // lazy (vr_internal.h): the planes are cleared by the next whole-frame tile pass, or by whoever looks at them first
-        gbuffer_touch(g);
-        g->clear_pending = true;
-        return VR_OK;
-    }
-    g->cleared_once = true;
-    return gbuffer_clear_now(g, g->ctx->stream);
+    return gbuffer_clear_step(g, gbs_clear_requested(g->st, g->ctx->plane_tracking), g->ctx->stream);
 }
 
-int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s)
+int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s) { return gbuffer_clear_step(g, gbs_materialise(g->st), s); }
+
+__global__ void k_fill_u32x2(uint2* p, size_t n, uint32_t x, uint32_t y)
 {
-    if (!g->clear_pending) return VR_OK;
-    return gbuffer_clear_now(g, s);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint2(x, y);
 }
-
-// the region array: allocated and current
-static int gbuffer_region_prepare(vr_gbuffer* g, hipStream_t s, uint8_t** out)
+// A reader's or a tile pass's step: the arrays it needs, their fills, then - nothing can fail any more - its state.  A refusal
+// leaves the knowledge as it was; an array allocated and a reset of the ranges queued by then are facts, recorded as they happen.
+static int gbuffer_run_step(vr_gbuffer* g, const GbufferStep& step, hipStream_t s)
 {
     const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
-    if (!g->d_region) {
+    const GbufferWork& w = step.work;
+    if (w.alloc_ranges) {
+        const int rc = vr_grow(&g->d_ranges, &g->ranges_bytes, (size_t)tiles * sizeof(uint2), [s]() -> int { VR_HIP(hipStreamSynchronize(s)); return VR_OK; });
+        if (rc) return rc;
+        g->st = gbs_ranges_allocated(g->st);
+    }
+    if (w.alloc_region) {
         if (!vr_dev_alloc((void**)&g->d_region, (size_t)tiles * 4)) return VR_ERR_OUT_OF_MEMORY;
-        if (g->region_fill < 0) g->region_fill = 0;
+        g->st = gbs_region_allocated(g->st);
     }
-    if (g->region_fill >= 0) {
-        VR_HIP(hipMemsetAsync(g->d_region, g->region_fill, (size_t)tiles * 4, s));
-        g->region_fill = -1;
+    if (w.reset_ranges) {
+        hipLaunchKernelGGL(k_fill_u32x2, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, s, g->d_ranges, (size_t)tiles, 0x7f800000u, 0u);
+        VR_HIP(hipGetLastError());
+        g->st = gbs_ranges_reset(g->st);
     }
-    *out = g->d_region;
+    if (w.region_byte >= 0) VR_HIP(hipMemsetAsync(g->d_region, w.region_byte, (size_t)tiles * 4, s));
+    g->st = step.after;
     return VR_OK;
 }
 
@@ -540,11 +540,10 @@ int vr_gbuffer_plane_hints(vr_gbuffer* g, hipStream_t s, PlaneHints* out)
 {
     out->region = nullptr; out->spec_const = vr_specular_constant(g->ctx); out->emissive_zero = 0; out->tiles32_x = (g->w + 31) / 32;
     { const int rc = vr_gbuffer_materialise(g, s); if (rc) return rc; }       // (a reader: a pending clear happens now)
-    if (!g->ctx->plane_tracking || g->escaped) return VR_OK;
-    uint8_t* r = nullptr;
-    const int rc = gbuffer_region_prepare(g, s, &r);
+    const GbufferStep step = gbs_reader(g->st, g->ctx->plane_tracking);
+    const int rc = gbuffer_run_step(g, step, s);
     if (rc) return rc;
-    out->region = r; out->emissive_zero = g->emissive_zero ? 1 : 0;
+    out->region = step.region_usable ? g->d_region : nullptr; out->emissive_zero = step.emissive_zero ? 1 : 0;
     return VR_OK;
 }
 
@@ -554,9 +553,8 @@ extern "C" VR_API int vr_gbuffer_region_census(vr_gbuffer* g, uint32_t counts[4]
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
     const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
     counts[3] = (uint32_t)tiles * 4u;
-    if (!g->ctx->plane_tracking || g->escaped) { counts[0] = counts[3]; return VR_OK; }      // no region is known to hold anything
-    if (g->clear_pending) { counts[2] = counts[3]; return VR_OK; }            // (cleared, as far as anyone can tell)
-    if (!g->d_region || g->region_fill >= 0) { counts[g->region_fill == (int)kRegionClear ? 2 : 0] = counts[3]; return VR_OK; }
+    const int all = gbs_census(g->st, g->ctx->plane_tracking);
+    if (all >= 0) { counts[all] = counts[3]; return VR_OK; }          // the host knows without looking
     VR_HIP(hipSetDevice(g->ctx->device));
     std::vector<uint8_t> h((size_t)tiles * 4);
     VR_HIP(hipMemcpyAsync(h.data(), g->d_region, h.size(), hipMemcpyDeviceToHost, g->ctx->stream));
@@ -567,70 +565,23 @@ extern "C" VR_API int vr_gbuffer_region_census(vr_gbuffer* g, uint32_t counts[4]
 
 extern "C" VR_API int vr_gbuffer_plane_known_zero(vr_gbuffer* g, int plane)
 {
-    if (!g || plane != 4) return 0;
-    return (g->ctx->plane_tracking && (g->emissive_zero || g->clear_pending) && !g->escaped) ? 1 : 0;
-}
-
-__global__ void k_fill_u32x2(uint2* p, size_t n, uint32_t x, uint32_t y)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint2(x, y);
-}
-// the depth ranges: allocated and every entry "none"
-static int gbuffer_ranges_prepare(vr_gbuffer* g, hipStream_t s)
-{
-    const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
-    if ((size_t)tiles * sizeof(uint2) > g->ranges_bytes) {
-        const int rc = vr_grow(&g->d_ranges, &g->ranges_bytes, (size_t)tiles * sizeof(uint2), [s]() -> int { VR_HIP(hipStreamSynchronize(s)); return VR_OK; });
-        if (rc) return rc;
-        g->ranges_state = vr_gbuffer::RANGES_NONE;
-    }
-    if (g->ranges_state != vr_gbuffer::RANGES_CLEAN) {
-        hipLaunchKernelGGL(k_fill_u32x2, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, s, g->d_ranges, (size_t)tiles, 0x7f800000u, 0u);
-        VR_HIP(hipGetLastError());
-        g->ranges_state = vr_gbuffer::RANGES_CLEAN;
-    }
-    return VR_OK;
-}
-
-int vr_gbuffer_settle_clear(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s)
-{
-    if (plan.consume_pending_clear) g->clear_pending = false;
-    return plan.materialise_first ? vr_gbuffer_materialise(g, s) : VR_OK;
+    return g && gbs_plane_known_zero(g->st, g->ctx->plane_tracking, plane) ? 1 : 0;
 }
 
 int vr_gbuffer_apply_plan(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s, int rank, int world, uint8_t** region)
 {
-    int rc;
+    const GbufferStep step = gbs_pass_prepare(g->st, plan, rank, world);
     *region = nullptr;
-    if (plan.ranges) {
-        if ((rc = gbuffer_ranges_prepare(g, s))) return rc;
-        g->ranges_state = vr_gbuffer::RANGES_VALID; g->ranges_rank = rank; g->ranges_world = world;
-    } else gbuffer_touch(g);
-    if (plan.track_regions) { if ((rc = gbuffer_region_prepare(g, s, region))) return rc; }
-    else g->region_fill = 0;
-    if (plan.emissive_zero_after) g->emissive_zero = true;
+    const int rc = gbuffer_run_step(g, step, s);
+    if (rc) return rc;
+    *region = step.region_usable ? g->d_region : nullptr;
     return VR_OK;
-}
-
-void vr_gbuffer_foreign_write(vr_gbuffer* g, int plane)
-{
-    gbuffer_touch(g);
-    if (plane == 4) g->emissive_zero = false;
-    g->region_fill = 0;                    // (no region is known clear - that includes the emissive plane - or constant any more)
-}
-
-void vr_gbuffer_escape(vr_gbuffer* g)
-{
-    gbuffer_touch(g);              // whatever the caller writes through the pointers is unknown here, now and for as long as
-    g->escaped = true;             // the G-buffer lives (no depth ranges, no plane-state tracking any more)
-    g->emissive_zero = false;
-    g->region_fill = 0;
 }
 
 bool vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world)
 {
-    const bool use = g->ranges_state == vr_gbuffer::RANGES_VALID && g->d_ranges && g->ranges_world == world && g->ranges_rank == rank;
-    if (use) g->ranges_state = vr_gbuffer::RANGES_CLEAN;
+    bool use;
+    g->st = gbs_consume_ranges(g->st, rank, world, &use);
     return use;
 }
 
@@ -638,7 +589,7 @@ extern "C" VR_API int vr_gbuffer_describe(vr_gbuffer* g, vr_gbuffer_desc* d)
 {
     VR_REQUIRE(g && d, "NULL argument");
     { VR_HIP(hipSetDevice(g->ctx->device)); const int rc = vr_gbuffer_materialise(g, g->ctx->stream); if (rc) return rc; }
-    vr_gbuffer_escape(g);          // the caller gets the device pointers
+    g->st = gbs_escape(g->st);     // the caller gets the device pointers
     d->width = g->w; d->height = g->h; d->depth = g->depth; d->diffuse = g->diffuse; d->specular = g->specular;
     d->normals = g->normals; d->emissive = g->emissive;
     return VR_OK;
@@ -675,7 +626,7 @@ extern "C" VR_API int vr_gbuffer_upload(vr_gbuffer* g, int plane, const void* ho
     VR_REQUIRE(bytes == nb, "byte count does not match the plane size");
     VR_HIP(hipSetDevice(g->ctx->device));
     if ((rc = vr_gbuffer_materialise(g, g->ctx->stream))) return rc;
-    vr_gbuffer_foreign_write(g, plane);
+    g->st = gbs_foreign_write(g->st, plane);
     VR_HIP(hipMemcpyAsync(p, host, nb, hipMemcpyHostToDevice, g->ctx->stream));
     VR_HIP(hipStreamSynchronize(g->ctx->stream));
     return VR_OK;

@@ -12,6 +12,7 @@
 
 #include "../../include/vrterrain.h"
 #include "vr_devbuf.h"
+#include "vr_gbuffer_state.h"
 #include "vr_order.h"
 #include "vr_scratch.h"
 
@@ -248,45 +249,16 @@ struct vr_gbuffer {
     // lighting pass's culling stage, which then need not read the depth plane a second time.
     uint2* d_ranges = nullptr;
     size_t ranges_bytes = 0;
-    enum { RANGES_NONE = 0, RANGES_CLEAN, RANGES_VALID, RANGES_DIRTY };
-    int ranges_state = RANGES_NONE;          // CLEAN: every entry "none"; VALID: the last writer of the G-buffer left them; DIRTY: stale
-    int ranges_rank = 0, ranges_world = 1;   // the screen-tile split they were rendered for
-    // Plane-state tracking (VR_OPT_PLANE_TRACKING): main_ps writes 0 to the emissive target for every pixel it shades
-    // (terrain_ps.hlsl:80) and RenderTargets::Clear writes 0 everywhere, so on this path the plane only ever holds zeros -
-    // 8 of the G-buffer's 28 bytes per pixel.  While the library KNOWS the plane is all zero (it cleared it, or a tile pass
-    // that writes every pixel of the target has run since the last foreign write) the tile pass does not rewrite it.
-    // Foreign writes: vr_gbuffer_upload of the plane -> not known zero; vr_gbuffer_describe -> the pointers have left the
-    // library for good (`escaped`): nothing about the planes' contents is assumed ever again (the same goes for the light
-    // tiles' depth ranges above).
-    bool emissive_zero = false;
-    bool escaped = false;
-    // The same idea per REGION (the 8 rows x 32 pixels one wave of a 32-pixel raster tile resolves), one byte each, kept on the
-    // device by the fast variant of the tile pass: kRegionClear = every pixel holds the clear values in all planes (RenderTargets::
-    // Clear, or a pass over a cleared target that drew nothing there); kRegionSpec = every pixel holds the pass's one specular
-    // constant (terrain_ps.hlsl:76).  A sky region that is known clear is not written again and a terrain region keeps its
-    // specular plane - the planes' contents are what they would be anyway.  region_fill: -1 = the device array is current,
-    // else the byte it has to be filled with before its next use (0 after anything foreign wrote a plane, kRegionClear after a clear).
-    uint8_t* d_region = nullptr;
-    int region_fill = 0;
-    // RenderTargets::Clear (vr_gbuffer_clear) under the tracking is LAZY: the next tile pass that writes every pixel of every plane
-    // anyway (whole frame, shaded) runs as "over a cleared target" and the 929 MB of clear values are never written twice;
-    // anything else that looks at the planes first (a lighting pass, a partitioned / depth-only / fused pass, download, upload,
-    // describe) materialises the clear (vr_gbuffer_materialise).  Clear + Render then costs what Render(assume_cleared) costs.
-    bool clear_pending = false;
-    bool cleared_once = false;       // (the clear at creation is a real one: the allocation holds anything)
+    uint8_t* d_region = nullptr;     // one state byte per region (kRegionClear / kRegionSpec), kept by the fast tile pass
+    // What the library knows of the planes and of the two arrays (vr_gbuffer_state.h).  Only vr_host.hip assigns it, through
+    // that header's transitions; it owns the arrays, the fills and the error codes.
+    GbufferState st;
 };
-constexpr uint32_t kRegionSpec = 1u, kRegionClear = 2u;
-// The state above changes only through these (vr_host.hip; vr_gbuffer_clear is the remaining one):
 int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s);      // a pending clear is written now, on `s`
-// A tile pass as raster_plan() decided it (vr_raster_plan.h).  settle_clear, in front of everything the pass queues: the
-// pending clear is written or consumed.  apply_plan, once nothing can refuse the launch any more: depth ranges ready and VALID
-// for (rank, world) - or stale -, the region array current (*region; NULL: not kept, nothing is known per region any more),
-// the emissive plane known zero if the pass leaves it so.
+// A tile pass as raster_plan() decided it (vr_raster_plan.h), once nothing but this call can refuse the launch any more: the
+// arrays it needs, their fills, then the state behind the pass (*region; NULL: not kept).  A refusal leaves the state as it was.
 struct RasterPlan;
-int vr_gbuffer_settle_clear(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s);
 int vr_gbuffer_apply_plan(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s, int rank, int world, uint8_t** region);
-void vr_gbuffer_foreign_write(vr_gbuffer* g, int plane);       // something outside the library's passes wrote the plane
-void vr_gbuffer_escape(vr_gbuffer* g);                         // the device pointers have left the library, for good
 // the tiled lighting pass takes the depth ranges if they are VALID for this split (they are "none" again once it has run)
 bool vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world);
 // What a pass that READS the G-buffer may take from the tracking instead of from memory (the lighting passes).

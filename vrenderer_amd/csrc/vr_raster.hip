@@ -1203,7 +1203,7 @@ constexpr int kRT = VR_RASTER_THREADS, kRW = kRT / 64;
 //   RM_GENERIC everything else, decided at run time.
 enum { RM_GENERIC = 0, RM_FAST = 1, RM_DEPTH = 2 };
 // RANGES (fast variant only): the depth range of every 32x32 light tile is left at `ranges` for the tiled lighting pass.
-// NOEMI (fast variant only): the emissive plane is known to hold zeros already (vr_gbuffer::emissive_zero) and is not rewritten -
+// NOEMI (fast variant only): the emissive plane is known to hold zeros already (GbufferState::emissive_zero) and is not rewritten -
 // main_ps's o_channel3 = 0 (terrain_ps.hlsl:80) changes nothing there; 8 of the 28 bytes a pixel sends through the CU's store path.
 // LIT (fast variant only; vr_terrain_render_lit): the fused pass of SURVEY 7 step 6 - the resolve encodes the pixel to the
 // G-buffer's formats in registers, decodes and shades it with the lighting pass's own arithmetic (shade_pixel, vr_deferred_dev.h)
@@ -1944,7 +1944,7 @@ static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view,
     const uint64_t span = (uint64_t)((const char*)(gb->emissive + (size_t)gb->w * gb->h) - (const char*)gb->depth);
     in.one_rsrc = (const char*)gb->depth < (const char*)gb->diffuse && (const char*)gb->depth < (const char*)gb->specular
                && (const char*)gb->depth < (const char*)gb->normals && (const char*)gb->depth < (const char*)gb->emissive && span < (1ull << 32);
-    in.plane_tracking = ctx->plane_tracking; in.clear_pending = gb->clear_pending; in.emissive_zero = gb->emissive_zero; in.escaped = gb->escaped;
+    in.plane_tracking = ctx->plane_tracking; in.clear_pending = gb->st.clear_pending; in.emissive_zero = gb->st.emissive_zero; in.escaped = gb->st.escaped;
     in.viewport_full = view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0;
     in.width_mult4 = gb->w % 4 == 0;
     *lights_rc = VR_OK;
@@ -1997,8 +1997,10 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     // pass: the error is the lighting pass's to report - as is a partial viewport's, where that pass would look at it first)
     if (lights_rc && lit && (in.viewport_full || (plan.fast && !plan.ranges))) return lights_rc;
     if (lit_req && lit_req->keep && !plan.keep) lit_req = nullptr;           // from here on: a plain vr_terrain_render
+    // a pending clear is written now, or the pass is that clear: the kernel is told so, the state learns it with the rest
+    // (vr_gbuffer_apply_plan) - a refusal in between leaves the clear pending
     if (plan.consume_pending_clear) a.assume_cleared = 1;
-    if ((rc = vr_gbuffer_settle_clear(gb, plan, s))) return rc;
+    if (plan.materialise_first && (rc = vr_gbuffer_materialise(gb, s))) return rc;
 
     // a set prepared for exactly this frame, else a free one (the oldest prepared set is given up if all are taken)
     int gi = -1;

@@ -1,9 +1,9 @@
 // The tile pass's host decisions as one pure function: which k_raster instantiation runs and what the pass does to the
-// library's knowledge of the G-buffer (vr_gbuffer, vr_internal.h).  Plain C++17: no HIP, no library types - a CPU program
+// library's knowledge of the G-buffer (GbufferState, vr_gbuffer_state.h).  Plain C++17: no HIP, no library types - a CPU program
 // enumerates every input (tests/host/raster_plan_check.cpp).  terrain_render_impl (vr_raster.hip) gathers the facts, asks
-// raster_plan() and hands the answer to vr_gbuffer_settle_clear / _apply_plan (vr_host.hip).
+// raster_plan() and hands the answer to vr_gbuffer_apply_plan (vr_host.hip: gbs_pass_prepare, the HIP work, commit).
 //
-// Clear handling.  RenderTargets::Clear is lazy under the plane-state tracking (vr_gbuffer::clear_pending): a shaded pass over
+// Clear handling.  RenderTargets::Clear is lazy under the plane-state tracking (GbufferState::clear_pending): a shaded pass over
 // the whole frame writes every pixel of every plane anyway and runs as "over a cleared target" - Clear + Render is one pass
 // over the memory (consume_pending_clear); any other pass (a rank's share, depth only, the fused LIT variant) needs the clear
 // values in memory first (materialise_first).
@@ -21,6 +21,7 @@
 // its plain case.  Where it does not apply the call goes on as the plain tile pass - the caller queues the lighting pass behind
 // it as it always did and any error is that pass's to report.
 #pragma once
+#include "vr_gbuffer_state.h"
 
 enum RasterRequest { RASTER_REQ_NONE = 0, RASTER_REQ_LIT, RASTER_REQ_KEEP };     // vr_terrain_render / _render_lit / vr_frame_submit
 
@@ -65,7 +66,7 @@ inline RasterPlan raster_plan(const RasterPlanIn& in)
 {
     RasterPlan p{};
     const bool whole = in.world <= 1, tile32 = in.tile_shift == 5;
-    const bool tracking_live = in.plane_tracking && !in.escaped;
+    const bool tracking_live = ::tracking_live(in.plane_tracking, in.escaped);
     const bool emissive_skip = tracking_live && in.emissive_zero;
     p.fast = in.tex_same && in.ws_pow2 && in.one_rsrc && !in.wireframe && !in.depth_only;
     p.keep = in.request == RASTER_REQ_KEEP && whole && p.fast && tile32 && (in.assume_cleared || in.clear_pending) && !in.depth_ranges
