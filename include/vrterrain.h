@@ -381,7 +381,9 @@ VR_API int  vr_deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* 
  * light order) and raises a device-side flag; the launch stays asynchronous, so the condition is
  * reported by vr_deferred_tiled_status.  The light array is uploaded only when it differs from the
  * one the previous call left on the device.  Device memory: (w/32) x (h/32) lists of
- * min(num_lights, VR_TILE_LIGHT_CAP) + 1 words, kept by the context. */
+ * min(num_lights, VR_TILE_LIGHT_CAP) + 1 words, kept by the context.
+ * This entry point takes directional and punctual point lights only (a spot light or a radius > 0 is
+ * VR_ERR_INVALID_ARGUMENT) and has no shadow term: vr_deferred_light_tiled_ex, below, lifts both. */
 #define VR_TILE_LIGHT_CAP 1024
 VR_API int  vr_deferred_light_tiled(vr_context* ctx, const vr_view* view, vr_gbuffer* gb,
                                     const vr_light* lights, int32_t num_lights,
@@ -425,6 +427,19 @@ VR_API int  vr_deferred_light_shadowed(vr_context* ctx, const vr_view* view, vr_
                                        const float ambient_top[3], const float ambient_bottom[3],
                                        vr_image* hdr_out, const vr_partition* part,
                                        const vr_shadow_binding* shadow);
+/* vr_deferred_light_tiled for every light type, with the sun's shadow term: the inputs, outputs, limits, overflow report
+ * (vr_deferred_tiled_status) and packed output of vr_deferred_light_tiled, and in addition
+ *  - VR_LIGHT_SPOT and spherical sources (radius > 0), shaded with the arithmetic of vr_deferred_light; a spot light still needs
+ *    outer_angle > inner_angle.  A spot light is culled by its range as a point light is and, when its outer_angle is below
+ *    pi/2 and its direction is of unit length, also dropped from the tiles that lie outside its cone;
+ *  - shadow (may be NULL): the conditions and the shadow term of vr_deferred_light_shadowed on lights[shadow->light_index] - a
+ *    directional light, a square map that matches the light view, on this device; out_of_bounds_shadow outside the map.
+ * A list without spot or spherical lights and without a binding runs vr_deferred_light_tiled's kernels. */
+VR_API int  vr_deferred_light_tiled_ex(vr_context* ctx, const vr_view* view, vr_gbuffer* gb,
+                                       const vr_light* lights, int32_t num_lights,
+                                       const float ambient_top[3], const float ambient_bottom[3],
+                                       vr_image* hdr_out, const vr_partition* part,
+                                       const vr_shadow_binding* shadow /* may be NULL */);
 
 /* LdrColor: SRGBA8_UNORM render target (Renderer.h:81-92), width*height*4 bytes of device memory, or - as a
  * multi-GPU send buffer - the packed RGB8 tiles of one rank (capacity_bytes >= vr_partition_packed_bytes_ldr).
@@ -538,7 +553,7 @@ VR_API int  vr_tonemap_allreduce_histogram(vr_tonemap* tm, void* nccl_comm);
 /* ---- a whole frame in one call ---------------------------------------------------- */
 /* The terrain part of Renderer::RecordCommand (Renderer.cpp:321-446: ONE command list per frame) as one entry point:
  * vr_terrain_render(view) [RenderTargets::Clear fused when render->assume_cleared] -> vr_terrain_prepare for up to two upcoming
- * frames -> vr_deferred_light / _tiled / _shadowed -> optionally ToneMappingPass::SimpleRender on the tone mapper's own context
+ * frames -> vr_deferred_light / _tiled / _tiled_ex / _shadowed -> optionally ToneMappingPass::SimpleRender on the tone mapper's own context
  * (reset + add_frame_to_histogram [+ vr_tonemap_allreduce_histogram] + compute_exposure + render) [+ vr_frame_allgather_ldr].
  * It queues what those calls queue, in that order, on the same streams; it exists because a frame is otherwise about nine calls
  * and a rank of an 8-way split of the 8K frame has a period near 0.1 ms.  When the tone mapper's context uses another stream than
@@ -551,9 +566,10 @@ typedef struct vr_frame_desc {
     const vr_partition*     part;               /* NULL = whole frame */
     const vr_light*         lights;
     int32_t                 num_lights;
-    int32_t                 tiled;              /* 1 = vr_deferred_light_tiled (many lights) */
+    int32_t                 tiled;              /* 0 = vr_deferred_light[_shadowed]; 1 = vr_deferred_light_tiled (many lights; it has no
+                                                   shadow term: `shadow` is ignored); 2 = vr_deferred_light_tiled_ex with `shadow` */
     float                   ambient_top[3], ambient_bottom[3];
-    const vr_shadow_binding* shadow;            /* optional: vr_deferred_light_shadowed */
+    const vr_shadow_binding* shadow;            /* optional: vr_deferred_light_shadowed (tiled = 0), vr_deferred_light_tiled_ex (tiled = 2) */
     vr_image*               hdr_out;            /* HdrColor, or this rank's packed RGB16F tiles */
     /* optional tone-map stage: tonemap NULL = none */
     struct vr_tonemap*      tonemap;
@@ -584,6 +600,10 @@ VR_API int vr_debug_render_stats(vr_terrain* t, uint32_t out[8]);
  * longest bins first in eight classes (k_scan) - and each of those tiles' bin lengths, in that order.  `capacity` entries per
  * array; *out_count = number of tiles (0 if nothing was rendered).  Synchronises. */
 VR_API int vr_debug_tile_order(vr_terrain* t, int32_t* out_tiles, uint32_t* out_bin_lengths, int32_t capacity, int32_t* out_count);
+/* Test helper: the light indices (into the pass's `lights`, in rising order) that the culling stage of this context's last tiled
+ * lighting pass - either entry point - left for the 32x32 light tile (tile_x, tile_y).  *out_count = the length of the list; the
+ * first min(*out_count, capacity) indices go to `out`.  A pass over a partition writes its own tiles' lists only.  Synchronises. */
+VR_API int vr_debug_tile_light_list(vr_context* ctx, int32_t tile_x, int32_t tile_y, uint32_t* out, int32_t capacity, int32_t* out_count);
 /* Device memory a terrain holds, in bytes: out[0] textures (chains + decoded tables, and the query pyramid once a ray was cast), out[1] per-frame geometry scratch
  * (three rotating sets: instances, vertices, triangle records, bins - sized for params->max_instances) plus the staging
  * memory of host-pointer queries, out[2] node heights (after vr_terrain_update_heights), out[3] the sum. */

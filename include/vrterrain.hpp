@@ -262,6 +262,18 @@ namespace vRenderer
         {
             static const std::vector<vr_light> none;
             const std::vector<vr_light>& l = inputs.lights ? *inputs.lights : none;
+            // More lights than DEFERRED_MAX_LIGHTS (16) - which used to be vr_deferred_light's "at most 16 lights" error - go to the
+            // tiled pass for every light type, with the shadow map if there is one.  That pass needs a frame width that is a
+            // multiple of 4, and reports a light tile that kept more than VR_TILE_LIGHT_CAP lights through vr_deferred_tiled_status
+            // (asynchronously: call it once per frame or less), not through this return value.
+            if (l.size() > 16) {
+                vr_shadow_binding sb{};
+                if (inputs.shadowMap) sb = inputs.shadowMap->Binding(inputs.shadowLightIndex);
+                return Check(vr_deferred_light_tiled_ex(m_Device.Get(), &view, inputs.gbuffer->GBufferFramebuffer(), l.data(), (int32_t)l.size(),
+                                                        inputs.ambientColorTop, inputs.ambientColorBottom, inputs.output, partition,
+                                                        inputs.shadowMap ? &sb : nullptr),
+                             "vr_deferred_light_tiled_ex");
+            }
             if (inputs.shadowMap) {
                 const vr_shadow_binding sb = inputs.shadowMap->Binding(inputs.shadowLightIndex);
                 return Check(vr_deferred_light_shadowed(m_Device.Get(), &view, inputs.gbuffer->GBufferFramebuffer(), l.data(), (int32_t)l.size(),

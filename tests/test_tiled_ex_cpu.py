@@ -1,0 +1,63 @@
+"""CPU tests of vr_deferred_light_tiled_ex: the ABI of the two new entry points and the host check of the culling stage's
+cone test (tests/host/light_cull_check.cpp)."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+from vrenderer_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("vr_deferred_light_tiled_ex", "vr_debug_tile_light_list")
+
+
+def test_new_entry_points_are_declared_listed_and_exported(product_lib):
+    header = open(os.path.join(ROOT, "include", "vrterrain.h")).read()
+    declared = re.findall(r"VR_API\s+[\w\s\*]+?\b(vr_\w+)\s*\(", header)
+    for name in NEW:
+        assert name in declared, f"{name} is not declared in include/vrterrain.h"
+        assert name in capi.EXPORTS, f"{name} is missing from capi.EXPORTS"
+        fn = getattr(product_lib, name)
+        assert fn.argtypes is not None and fn.restype is C.c_int
+    assert len(product_lib.vr_deferred_light_tiled_ex.argtypes) == len(product_lib.vr_deferred_light_tiled.argtypes) + 1
+    assert capi.VR_K_COUNT == product_lib.vr_timing_kernel_count() == 22        # the new kernels are timed under existing ids
+    assert capi.VR_TILE_LIGHT_CAP == int(re.search(r"#define VR_TILE_LIGHT_CAP (\d+)", header).group(1))
+
+
+def test_null_context_is_an_invalid_argument_without_a_device(product_lib):
+    amb = (C.c_float * 3)(0.0, 0.0, 0.0)
+    view, light = capi.View(), capi.Light()
+    rc = product_lib.vr_deferred_light_tiled_ex(None, C.byref(view), None, C.byref(light), 1, amb, amb, None, None, None)
+    assert rc == capi.VR_ERR_INVALID_ARGUMENT
+    assert b"NULL argument" in product_lib.vr_last_error()
+    out, n = (C.c_uint32 * 4)(), C.c_int32(-1)
+    rc = product_lib.vr_debug_tile_light_list(None, 0, 0, out, 4, C.byref(n))
+    assert rc == capi.VR_ERR_INVALID_ARGUMENT and n.value == -1
+
+
+def _build_check(tmp_path, name, extra):
+    exe = os.path.join(str(tmp_path), name)
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "light_cull_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    return exe
+
+
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_cone_test_never_drops_a_cone_that_reaches_the_box_and_is_not_vacuous(tmp_path, sanitize):
+    """vr_light_cull.h compiles without HIP.  Over 120000 fixed-seed (cone, box) pairs - boxes around, on and behind the axis,
+    with the apex inside, touching the cone's surface, at coordinates up to 2048, outer_angle 0.5 .. 89 degrees - sampled at
+    corners, edge and face midpoints and a 9^3 lattice in double precision, the fp32 test never drops a cone that some sample
+    lies in, and drops at least half of the pairs whose every sample is more than 5 degrees outside
+    (tests/host/light_cull_check.cpp).  Once more with the address and undefined-behaviour sanitizers."""
+    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if sanitize else []
+    exe = _build_check(tmp_path, "light_cull_check_san" if sanitize else "light_cull_check", extra)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    m = re.search(r"(\d+) pairs .* (\d+) clear of the cone by 5 degrees, (\d+) of them dropped", r.stdout)
+    assert m, r.stdout[-400:]
+    pairs, clear, dropped = (int(x) for x in m.groups())
+    assert pairs >= 100000 and clear >= pairs // 10 and 2 * dropped >= clear, r.stdout[-400:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-2000:]

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "vr_deferred_dev.h"
+#include "vr_light_cull.h"
 
 // Output of 4 pixels (o[2k] = r|g<<16, o[2k+1] = b, alpha 0).  Row-major frames are RGBA16F (8 B/px);
 // the packed tile buffer that goes through the all-gather drops the always-zero alpha: RGB16F, 6 B/px,
@@ -242,7 +243,7 @@ static int fill_light(const vr_light& l, DevLight& d, bool allow_extra)
     const double half = l.type == VR_LIGHT_DIRECTIONAL ? 0.5 * (double)l.angular_size_or_inv_range : 0.0;
     d.cosH = (float)cos(half); d.sinH = (float)sin(half); d.tanH = (float)tan(half);
     d.radius = l.type != VR_LIGHT_DIRECTIONAL ? l.radius : 0.0f;
-    d.inner_angle = l.inner_angle; d.outer_angle = l.outer_angle; d.pad0 = d.pad1 = 0.0f;
+    d.inner_angle = l.inner_angle; d.outer_angle = l.outer_angle; d.cone_cos = d.cone_sin = 0.0f;
     return VR_OK;
 }
 
@@ -265,14 +266,11 @@ int vr_deferred_make_args(const vr_view* view, int w, int h, const vr_light* lig
     return VR_OK;
 }
 
-// *stop: the stop event this call's own launch was stamped with (NULL: not stamped, or nothing was launched)
-static int deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
-                          int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
-                          vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, hipEvent_t* stop)
+// The shadow binding of a lighting pass (vr_deferred_light_shadowed, vr_deferred_light_tiled_ex): its conditions, the map made
+// real, the kernels' constants.  shadow == NULL: *sh is all zero.
+static int fill_shadow(vr_context* ctx, const vr_light* lights, int32_t num_lights, const vr_shadow_binding* shadow, ShadowArgs* out)
 {
-    *stop = nullptr;
-    VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
-    ShadowArgs sh;
+    ShadowArgs& sh = *out;
     memset(&sh, 0, sizeof(sh));
     if (shadow) {
         VR_REQUIRE(shadow->light_view && shadow->shadow_map, "shadow binding has NULL members");
@@ -286,6 +284,18 @@ static int deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, 
         sh.depth = shadow->shadow_map->depth; sh.res = shadow->shadow_map->w; sh.light_index = shadow->light_index;
         sh.bias = shadow->depth_bias; sh.out_of_bounds = lights[shadow->light_index].out_of_bounds_shadow;
     }
+    return VR_OK;
+}
+
+// *stop: the stop event this call's own launch was stamped with (NULL: not stamped, or nothing was launched)
+static int deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
+                          int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
+                          vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, hipEvent_t* stop)
+{
+    *stop = nullptr;
+    VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
+    ShadowArgs sh;
+    { const int rc = fill_shadow(ctx, lights, num_lights, shadow, &sh); if (rc) return rc; }
     VR_REQUIRE(num_lights >= 0 && num_lights <= kMaxLights, "at most 16 lights (terrain_cb.h:15)");
     VR_REQUIRE(num_lights == 0 || lights, "lights is NULL");
     VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0,
@@ -396,22 +406,16 @@ constexpr int kSubSide = kMacroTile / kLightTile;       // 4 light tiles per mac
 constexpr int kSubTiles = kSubSide * kSubSide;
 static_assert(kSubTiles == 16 && kMacroTile == 128, "k_light_cull's lane mapping assumes 128-px macro tiles of 4x4 light tiles");
 
-// squared distance from a point to a box, compared with the light's range (attenuation is exactly 0 from the range outwards).
-// The caller passes r2 = range^2 * 1.0001: the test's own fp32 rounding (three squares and two sums, the reciprocal and
-// the square of the range: < 8 u relative) cannot turn a touching sphere into a miss.
-__device__ __forceinline__ bool sphere_touches(const float* __restrict__ box, const float pos[3], float r2)
-{
-    float d2 = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 3; c++) { const float d = fmax1(fmax1(box[c] - pos[c], pos[c] - box[3 + c]), 0.0f); d2 += d * d; }
-    return d2 <= r2;
-}
+// (the two geometric tests - sphere_touches, cone_misses_box - are in vr_light_cull.h, which the host compiles and checks too)
 
 // RANGES: the light tiles' depth ranges come from the tile pass that rendered the G-buffer (vr_gbuffer::d_ranges: the same
 // minima / maxima of the depths below 1.0, merged with atomics while the pixels were resolved) instead of from a second
 // pass over the depth plane - the kernel's first phase, and most of its time: sixteen 16-byte loads per lane from 512-byte
 // rows 30 KB apart.  The entries are consumed: reset to "none" for the next frame.
-template <bool RANGES>
+// CONE (vr_deferred_light_tiled_ex with spot lights in the list): a spot light passes the range test as a point light does and is
+// then dropped from a cell whose padded box lies outside its cone (cone_misses_box), at both levels.  Everything it adds is
+// compiled out of k_light_cull<RANGES, false>, vr_deferred_light_tiled's kernel.
+template <bool RANGES, bool CONE = false>
 __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLight* __restrict__ lights, int num_lights,
                                                      const float* __restrict__ g_depth, const uint2* __restrict__ g_nrm, int macro_x,
                                                      const int32_t* __restrict__ owned_tiles, uint32_t* __restrict__ lists, int stride,
@@ -565,9 +569,11 @@ __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLig
     // ---- A. every wave takes a quarter of the light list and keeps, in order, the lights that touch the macro tile's box
     // (its region of the scratch list: no synchronisation until all four are done; the next 64 lights are in flight
     // while the current ones are tested)
-    struct Lite { float pos[3]; float inv_range; int type; };
+    struct Lite { float pos[3]; float inv_range; int type; float axis[3]; float cone_cos, cone_sin; };      // (the cone: CONE only)
     auto fetch = [&](int li, int hi) { Lite l; l.pos[0] = l.pos[1] = l.pos[2] = 0.0f; l.inv_range = 0.0f; l.type = -1;
-        if (li < hi) { const DevLight& L = lights[li]; l.pos[0] = L.pos[0]; l.pos[1] = L.pos[1]; l.pos[2] = L.pos[2]; l.inv_range = L.inv_range; l.type = L.type; }
+        l.axis[0] = l.axis[1] = l.axis[2] = 0.0f; l.cone_cos = l.cone_sin = 0.0f;
+        if (li < hi) { const DevLight& L = lights[li]; l.pos[0] = L.pos[0]; l.pos[1] = L.pos[1]; l.pos[2] = L.pos[2]; l.inv_range = L.inv_range; l.type = L.type;
+                       if (CONE && L.type == VR_LIGHT_SPOT) { l.axis[0] = L.dir[0]; l.axis[1] = L.dir[1]; l.axis[2] = L.dir[2]; l.cone_cos = L.cone_cos; l.cone_sin = L.cone_sin; } }
         return l; };
     const int quarter = (num_lights + 3) / 4;
     const int lo_w = min(wave * quarter, num_lights), hi_w = min(lo_w + quarter, num_lights);
@@ -581,6 +587,7 @@ __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLig
             if (cur.type >= 0) {
                 if (cur.type == VR_LIGHT_DIRECTIONAL || !(cur.inv_range > 0.0f)) keep = true;
                 else { const float r = 1.0f / cur.inv_range; keep = sphere_touches(s_box[kSubTiles], cur.pos, (r * r) * 1.0001f); }
+                if (CONE && keep && cur.type == VR_LIGHT_SPOT) keep = !cone_misses_box(s_box[kSubTiles], cur.pos, cur.axis, cur.cone_cos, cur.cone_sin);
             }
             const unsigned long long m = __ballot(keep);
             if (keep) kept_list[(uint32_t)lo_w + kept + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)(base + lane);
@@ -612,6 +619,12 @@ __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLig
 #pragma unroll
                     for (int b = 0; b < kSubTiles; b++) mask |= sphere_touches(s_box[b], pos, r2) ? 1u << b : 0u;
                 }
+                if (CONE && L.type == VR_LIGHT_SPOT && L.cone_cos > 0.0f) {
+                    const float pos[3] = { L.pos[0], L.pos[1], L.pos[2] }, axis[3] = { L.dir[0], L.dir[1], L.dir[2] };
+                    const float cone_cos = L.cone_cos, cone_sin = L.cone_sin;
+#pragma unroll 1                                                     // (sixteen inlined copies cost 90 VGPRs and a wave per SIMD)
+                    for (int b = 0; b < kSubTiles; b++) if (cone_misses_box(s_box[b], pos, axis, cone_cos, cone_sin)) mask &= ~(1u << b);
+                }
             }
 #pragma unroll
             for (int b = 0; b < kSubTiles; b++) {
@@ -636,17 +649,32 @@ __global__ __launch_bounds__(256) void k_light_cull(DeferredArgs a, const DevLig
 #ifndef VR_TILED_PXB
 #define VR_TILED_PXB 1
 #endif
-template <bool PACKED, int PXB, bool NT = false>
+// What vr_deferred_light_tiled_ex stages beside a TiledLight: a flag word per light (EXTRA or SHADOW: what the light loop - uniformly
+// per staged light - does with it) and, in the EXTRA instantiations only, 32 B with the cone and the source radius of a spot or
+// spherical light.
+struct TiledExtra { float axis[3]; float radius; float inner_angle, outer_angle; uint32_t pad0, pad1; };
+constexpr uint32_t kTlExtra = 1u, kTlSpot = 2u, kTlShadowed = 4u;   // needs a LightExtra; is a spot light; carries the shadow term
+
+// EXTRA = false, SHADOW = false is vr_deferred_light_tiled's kernel: everything the two add is compiled out of it (sh is not
+// read).  EXTRA: spot and spherical lights go through add_light with a LightExtra (the streaming pass's arithmetic),
+// punctual point lights keep the fast form.  SHADOW: shadow_factor() once per pixel in front of the light loop; the staged light
+// whose index in the list is sh.light_index (a directional one: it is in every covered tile's list) has irradiance intensity * sf
+// and is skipped where sf == 0, as in shade_pixel<_, true>.
+template <bool PACKED, int PXB, bool NT = false, bool EXTRA = false, bool SHADOW = false>
 __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const DevLight* __restrict__ lights,
                                                          const float* __restrict__ g_depth, const uint32_t* __restrict__ g_diff,
                                                          const uint32_t* __restrict__ g_spec, const uint2* __restrict__ g_nrm,
                                                          const uint2* __restrict__ g_emi, uint2* __restrict__ out,
                                                          const float* __restrict__ lut_g, const int32_t* __restrict__ owned_tiles,
-                                                         const uint32_t* __restrict__ lists, int stride, int tiles32_x, PlaneHints hints)
+                                                         const uint32_t* __restrict__ lists, int stride, int tiles32_x, PlaneHints hints,
+                                                         ShadowArgs sh)
 {
 #pragma clang fp contract(fast)
+    constexpr bool MORE = EXTRA || SHADOW;
     __shared__ float lut[256];
     __shared__ TiledLight s_light[kStageLights];
+    __shared__ uint32_t s_flags[MORE ? kStageLights : 1];
+    __shared__ TiledExtra s_extra[EXTRA ? kStageLights : 1];
     const int tid = threadIdx.x;
     lut[tid] = lut_g[tid];
 
@@ -719,7 +747,8 @@ __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const De
     const bool multi = n > (uint32_t)kStageLights;
     auto stage = [&](uint32_t chunk) {
         if (chunk + (uint32_t)tid < n) {
-            const DevLight L = lights[list[1u + chunk + tid]];
+            const uint32_t li = list[1u + chunk + tid];
+            const DevLight L = lights[li];
             const bool dir = L.type == VR_LIGHT_DIRECTIONAL;
             TiledLight t;
             const float* v = dir ? L.dir : L.pos;
@@ -727,8 +756,25 @@ __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const De
             t.color[0] = L.color[0] * L.intensity; t.color[1] = L.color[1] * L.intensity; t.color[2] = L.color[2] * L.intensity;
             t.w = dir ? L.cosH : 0.0f;
             s_light[tid] = t;
+            if (MORE) {
+                const bool spot = L.type == VR_LIGHT_SPOT;
+                s_flags[tid] = (EXTRA && !dir && (spot || L.radius > 0.0f) ? kTlExtra : 0u) | (EXTRA && spot ? kTlSpot : 0u)
+                             | (SHADOW && (int)li == sh.light_index ? kTlShadowed : 0u);
+            }
+            if (EXTRA) {
+                TiledExtra e;
+                e.axis[0] = L.dir[0]; e.axis[1] = L.dir[1]; e.axis[2] = L.dir[2]; e.radius = L.radius;
+                e.inner_angle = L.inner_angle; e.outer_angle = L.outer_angle; e.pad0 = e.pad1 = 0u;
+                s_extra[tid] = e;
+            }
         }
     };
+    // the sun's shadow term, once per pixel (a background pixel needs none: it receives no light)
+    float sf[4] = { 1.0f, 1.0f, 1.0f, 1.0f };
+    if (SHADOW) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (!bg[k]) sf[k] = shadow_factor(a, sh, px0 + k, py, depth[k]);
+    }
     if (!multi) stage(0u);
     __syncthreads();                                                 // (also publishes the decode table)
 #pragma unroll
@@ -748,11 +794,27 @@ __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const De
             if (multi) { __syncthreads(); stage(chunk); __syncthreads(); }
             for (uint32_t i = 0; i < m; i++) {
                 const TiledLight& t = s_light[i];
+                const uint32_t fl = MORE ? s_flags[i] : 0u;      // (block-uniform, like every branch on a staged light)
                 if (t.w > 0.0f) {                                  // directional (block-uniform branch)
                     const float tanH = t.inv_range * fast_rcp(t.w);
+                    if (SHADOW && (fl & kTlShadowed)) {
+#pragma unroll
+                        for (int j = 0; j < PXB; j++)
+                            if (!bg[kb + j] && sf[kb + j] != 0.0f)
+                                add_light(sv[j], VR_LIGHT_DIRECTIONAL, t.vec, 0.0f, t.color, sf[kb + j], t.w, t.inv_range, tanH, dT[j], sT[j]);
+                        continue;
+                    }
 #pragma unroll
                     for (int j = 0; j < PXB; j++)
                         if (!bg[kb + j]) add_light(sv[j], VR_LIGHT_DIRECTIONAL, t.vec, 0.0f, t.color, 1.0f, t.w, t.inv_range, tanH, dT[j], sT[j]);
+                } else if (EXTRA && (fl & kTlExtra)) {             // spot or spherical: the streaming pass's form (vr_deferred_dev.h)
+                    const TiledExtra& e = s_extra[i];
+                    LightExtra ex; ex.axis[0] = e.axis[0]; ex.axis[1] = e.axis[1]; ex.axis[2] = e.axis[2];
+                    ex.radius = e.radius; ex.inner_angle = e.inner_angle; ex.outer_angle = e.outer_angle;
+                    const int type = (fl & kTlSpot) ? VR_LIGHT_SPOT : VR_LIGHT_POINT;
+#pragma unroll
+                    for (int j = 0; j < PXB; j++)
+                        if (!bg[kb + j]) add_light(sv[j], type, t.vec, t.inv_range, t.color, 1.0f, 1.0f, 0.0f, 0.0f, dT[j], sT[j], &ex);
                 } else {
 #pragma unroll
                     for (int j = 0; j < PXB; j++)
@@ -780,12 +842,18 @@ extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* vi
     return vr_deferred_light_tiled_stop(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, &stop);
 }
 
-int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                                 const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop)
+// Both tiled entry points.  ex = false: vr_deferred_light_tiled - directional and punctual point lights, no shadow, the kernels
+// k_light_cull<RANGES> and k_deferred_tiled<PACKED, PXB, NT> and nothing else.  ex = true: vr_deferred_light_tiled_ex - every light
+// type and the optional shadow binding; a list (and binding) the plain kernels can take goes to the plain kernels.
+static int deferred_light_tiled(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
+                                const vr_shadow_binding* shadow, bool ex, hipEvent_t* stop)
 {
     *stop = nullptr;
     VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
     VR_REQUIRE(num_lights >= 0 && num_lights <= 65536 && (num_lights == 0 || lights), "bad light list");
+    ShadowArgs sh;
+    { const int rc = fill_shadow(ctx, lights, num_lights, shadow, &sh); if (rc) return rc; }
     VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0,
                "view viewport must cover the G-buffer");
     VR_HIP(hipSetDevice(ctx->device));
@@ -801,7 +869,14 @@ int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffe
     PlaneHints hints;                                         // (a reader: a pending clear happens now)
     { const int rc = vr_gbuffer_plane_hints(gb, ctx->stream, &hints); if (rc) return rc; }
     ctx->h_lights.resize((size_t)num_lights);
-    for (int i = 0; i < num_lights; i++) { int rc = fill_light(lights[i], ctx->h_lights[i], false); if (rc) return rc; }
+    bool extra = false, cone = false;       // (ex only) spot or spherical lights in the list; spot lights whose cone is culled
+    for (int i = 0; i < num_lights; i++) {
+        DevLight& d = ctx->h_lights[i];
+        int rc = fill_light(lights[i], d, ex); if (rc) return rc;
+        if (d.type == VR_LIGHT_SPOT) { cone_cull_terms(d.dir, d.outer_angle, &d.cone_cos, &d.cone_sin); cone = cone || d.cone_cos > 0.0f; }
+        extra = extra || d.type == VR_LIGHT_SPOT || d.radius > 0.0f;
+    }
+    const bool more = extra || shadow != nullptr;
     // a scene's light list rarely changes between frames: upload only when it differs from what the device holds
     const size_t light_bytes = (size_t)num_lights * sizeof(DevLight);
     if (num_lights && (ctx->h_lights_on_device.size() != (size_t)num_lights
@@ -831,6 +906,8 @@ int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffe
     // written to it since.  The culling stage consumes them (every entry it reads is reset), hence CLEAN afterwards - for a
     // split, only if this rank's share is non-empty (else nothing was written either).
     const bool use_ranges = vr_gbuffer_consume_ranges(gb, part ? part->rank : 0, part ? part->world_size : 1);
+    ctx->list_stride = stride; ctx->list_tiles_x = tx; ctx->list_tiles_y = ty;
+    const auto cull = cone ? (use_ranges ? k_light_cull<true, true> : k_light_cull<false, true>) : (use_ranges ? k_light_cull<true> : k_light_cull<false>);
     // two launches, each timed under its own id; the shading kernel's events are stamped by its dispatch like the streaming
     // pass's, so its stop event serves as the next frame's geometry start hint (vr_terrain_prepare)
     if (packed) {
@@ -841,32 +918,85 @@ int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffe
         a.tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
         if (pt->num_owned > 0) {
             { VrKernelScope kc(ctx, VR_K_LIGHT_CULL);
-              hipLaunchKernelGGL(use_ranges ? k_light_cull<true> : k_light_cull<false>, dim3((unsigned)pt->num_owned), dim3(256), 0, ctx->stream, a, ctx->d_lights,
+              hipLaunchKernelGGL(cull, dim3((unsigned)pt->num_owned), dim3(256), 0, ctx->stream, a, ctx->d_lights,
                                  num_lights, gb->depth, (const uint2*)gb->normals, macro_x, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
                                  gb->d_ranges); }
             VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
+            if (more) {
+                const auto kern = shadow ? (extra ? k_deferred_tiled<true, VR_TILED_PXB, false, true, true> : k_deferred_tiled<true, VR_TILED_PXB, false, false, true>)
+                                         : k_deferred_tiled<true, VR_TILED_PXB, false, true, false>;
+                VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)pt->num_owned * kSubTiles), dim3(256), ctx->stream, a,
+                                ctx->d_lights, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data,
+                                ctx->d_srgb_lut, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, hints, sh);
+            } else
             VR_LAUNCH_TIMED(ks, (k_deferred_tiled<true, VR_TILED_PXB>), dim3((unsigned)pt->num_owned * kSubTiles), dim3(256), ctx->stream, a,
                             ctx->d_lights, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data,
-                            ctx->d_srgb_lut, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, hints);
+                            ctx->d_srgb_lut, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, hints, sh);
             *stop = ks.stop();
         }
     } else {
         VR_REQUIRE((size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
         { VrKernelScope kc(ctx, VR_K_LIGHT_CULL);
-          hipLaunchKernelGGL(use_ranges ? k_light_cull<true> : k_light_cull<false>, dim3((unsigned)(macro_x * macro_y)), dim3(256), 0, ctx->stream, a, ctx->d_lights,
+          hipLaunchKernelGGL(cull, dim3((unsigned)(macro_x * macro_y)), dim3(256), 0, ctx->stream, a, ctx->d_lights,
                              num_lights, gb->depth, (const uint2*)gb->normals, macro_x, (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
                              gb->d_ranges); }
         VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
         const bool nt = true;                                         // as in the streaming pass
-        if (nt) VR_LAUNCH_TIMED(ks, (k_deferred_tiled<false, VR_TILED_PXB, true>), dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
+        if (more) {
+            const auto kern = shadow ? (extra ? k_deferred_tiled<false, VR_TILED_PXB, true, true, true> : k_deferred_tiled<false, VR_TILED_PXB, true, false, true>)
+                                     : k_deferred_tiled<false, VR_TILED_PXB, true, true, false>;
+            VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
+                            gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut,
+                            (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints, sh);
+        } else if (nt) VR_LAUNCH_TIMED(ks, (k_deferred_tiled<false, VR_TILED_PXB, true>), dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
                                 gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut,
-                                (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints);
+                                (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints, sh);
         else VR_LAUNCH_TIMED(ks, (k_deferred_tiled<false, VR_TILED_PXB, false>), dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
                              gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut,
-                             (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints);
+                             (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints, sh);
         *stop = ks.stop();
     }
     VR_HIP(hipGetLastError());
+    return VR_OK;
+}
+
+int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                 const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop)
+{
+    return deferred_light_tiled(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, false, stop);
+}
+
+int vr_deferred_light_tiled_ex_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                    const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
+                                    const vr_shadow_binding* shadow, hipEvent_t* stop)
+{
+    return deferred_light_tiled(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, true, stop);
+}
+
+// vr_deferred_light_tiled for every light type, with the sun's shadow term (shadow may be NULL)
+extern "C" VR_API int vr_deferred_light_tiled_ex(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
+                                                  int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
+                                                  vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
+{
+    hipEvent_t stop;
+    return deferred_light_tiled(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, true, &stop);
+}
+
+// Test helper: the list the last tiled pass of this context left for light tile (tile_x, tile_y); synchronises.
+extern "C" VR_API int vr_debug_tile_light_list(vr_context* ctx, int32_t tile_x, int32_t tile_y, uint32_t* out, int32_t capacity, int32_t* out_count)
+{
+    VR_REQUIRE(ctx && out_count && capacity >= 0 && (capacity == 0 || out), "NULL argument");
+    VR_REQUIRE(ctx->d_light_lists && ctx->list_stride > 0, "no tiled lighting pass has run on this context");
+    VR_REQUIRE(tile_x >= 0 && tile_x < ctx->list_tiles_x && tile_y >= 0 && tile_y < ctx->list_tiles_y, "light tile outside the last pass's frame");
+    VR_HIP(hipSetDevice(ctx->device));
+    VR_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t* list = ctx->d_light_lists + (size_t)(tile_y * ctx->list_tiles_x + tile_x) * ctx->list_stride;
+    uint32_t n = 0;
+    VR_HIP(hipMemcpy(&n, list, sizeof(n), hipMemcpyDeviceToHost));
+    VR_REQUIRE(n <= (uint32_t)(ctx->list_stride - 1), "the tile's list was not written by the last pass");
+    *out_count = (int32_t)n;
+    const uint32_t m = n < (uint32_t)capacity ? n : (uint32_t)capacity;
+    if (m) VR_HIP(hipMemcpy(out, list + 1, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VR_OK;
 }
 

@@ -123,7 +123,8 @@ struct DevLight {
     float pos[3];  float inv_range;
     float color[3]; float intensity;
     float cosH, sinH, tanH, radius;   // radius > 0: spherical source (half angle per pixel)
-    float inner_angle, outer_angle, pad0, pad1;   // spot cone (radians)
+    float inner_angle, outer_angle;   // spot cone (radians)
+    float cone_cos, cone_sin;         // vr_deferred_light_tiled_ex only: cone_cull_terms() of a spot light (vr_light_cull.h); 0 elsewhere
 };
 
 // Transformed vertex: clip position, world xz and the snapped screen vertex.
@@ -209,6 +210,7 @@ struct vr_context {
     uint32_t* d_macro_scratch = nullptr; size_t macro_scratch_bytes = 0;   // per macro tile: lights touching its box (k_light_cull's first stage)
     uint32_t* d_light_lists = nullptr; size_t light_list_bytes = 0;    // per 32x32 light tile: count + light indices (k_light_cull)
     uint32_t* d_flags = nullptr;
+    int list_stride = 0, list_tiles_x = 0, list_tiles_y = 0;   // layout of d_light_lists as the last tiled pass left it (vr_debug_tile_light_list)
     // per-kernel timing (vr_timing_*): event pairs recorded on `stream`
     int timing = 0;                      // 0 off, 1 every kernel (two event records each), 2 only the launches whose events the dispatch stamps
     std::vector<hipEvent_t> ev_pool;     // reusable events
@@ -386,6 +388,9 @@ int vr_deferred_light_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb,
                            const vr_shadow_binding* shadow, hipEvent_t* stop);
 int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
                                  const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop);
+int vr_deferred_light_tiled_ex_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                    const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
+                                    const vr_shadow_binding* shadow, hipEvent_t* stop);
 // tables of (w, h, part); part == NULL is the whole frame as rank 0 of 1
 int vr_partition_tables(vr_context* ctx, int w, int h, const vr_partition* part, const PartTables** out);
 // any cached table set of (w, h, world): the slot table does not depend on the rank

@@ -584,15 +584,23 @@ class Frame:
     set once; submit() fills in the views and the output image and makes the one call."""
 
     def __init__(self, terrain_pass, render_targets, render_params, lights, ambient_top, ambient_bottom, partition=None, tiled=False,
-                 tonemap=None, tonemap_params=None, ldr=None, comm=None, gathered_ptr=None, ldr_frame=None):
+                 tonemap=None, tonemap_params=None, ldr=None, comm=None, gathered_ptr=None, ldr_frame=None, shadow_map=None,
+                 shadow_light_index=0):
+        """tiled: False / 0 = the streaming lighting pass, True / 1 = vr_deferred_light_tiled (no shadow term: shadow_map is
+        ignored), 2 = vr_deferred_light_tiled_ex (every light type, shadow_map applies).  shadow_map: a CascadedShadowMap."""
         self.tp, self.rt = terrain_pass, render_targets
-        self._keep = (render_params, light_array(lights), partition, tonemap, tonemap_params, ldr, comm, ldr_frame)
+        sb = None
+        if shadow_map is not None:
+            sb = capi.ShadowBinding(C.cast(C.pointer(shadow_map.view), C.c_void_p), shadow_map.targets.handle, shadow_light_index,
+                                    shadow_map.params.depth_bias)
+        self._keep = (render_params, light_array(lights), partition, tonemap, tonemap_params, ldr, comm, ldr_frame, sb, shadow_map)
         d = capi.FrameDesc()
         d.render = C.addressof(render_params)
         d.part = C.addressof(partition) if partition is not None else None
         d.lights = C.addressof(self._keep[1])
         d.num_lights = len(lights)
-        d.tiled = 1 if tiled else 0
+        d.tiled = 1 if tiled is True else int(tiled)
+        d.shadow = C.addressof(sb) if sb is not None else None
         d.ambient_top[:] = [float(x) for x in ambient_top]
         d.ambient_bottom[:] = [float(x) for x in ambient_bottom]
         if tonemap is not None:
@@ -630,9 +638,23 @@ def light_array(lights):
 class TiledDeferredLightingPass(DeferredLightingPass):
     """DeferredLightingPass for many lights (BASELINE config 5): light lists per 32x32 screen tile."""
 
-    def Render(self, view, render_targets, lights, ambient_top, ambient_bottom, output, partition=None, num_lights=None):
+    def Render(self, view, render_targets, lights, ambient_top, ambient_bottom, output, partition=None, num_lights=None, *,
+               all_light_types=False, shadow_map=None, shadow_light_index=0):
+        """Default: vr_deferred_light_tiled (directional and punctual point lights, no shadow term).  all_light_types=True or a
+        shadow_map (a CascadedShadowMap, as DeferredLightingPass.Render takes it): vr_deferred_light_tiled_ex."""
         n = len(lights) if num_lights is None else num_lights
         arr = light_array(lights)
+        if all_light_types or shadow_map is not None:
+            sb = None
+            if shadow_map is not None:
+                sb = capi.ShadowBinding(C.cast(C.pointer(shadow_map.view), C.c_void_p), shadow_map.targets.handle, shadow_light_index,
+                                        shadow_map.params.depth_bias)
+            check(self.ctx.lib.vr_deferred_light_tiled_ex(self.ctx.handle, C.byref(view), render_targets.handle, arr, n,
+                                                          _f3(ambient_top), _f3(ambient_bottom), output.handle,
+                                                          C.byref(partition) if partition is not None else None,
+                                                          C.byref(sb) if sb is not None else None),
+                  "vr_deferred_light_tiled_ex")
+            return
         check(self.ctx.lib.vr_deferred_light_tiled(self.ctx.handle, C.byref(view), render_targets.handle, arr, n,
                                                    _f3(ambient_top), _f3(ambient_bottom), output.handle,
                                                    C.byref(partition) if partition is not None else None),
@@ -642,6 +664,15 @@ class TiledDeferredLightingPass(DeferredLightingPass):
         """Waits for the passes queued so far; raises VrError(VR_ERR_OVERFLOW) if a tile kept more than
         VR_TILE_LIGHT_CAP lights since the last call (the launch itself stays asynchronous)."""
         check(self.ctx.lib.vr_deferred_tiled_status(self.ctx.handle), "vr_deferred_tiled_status")
+
+    def tile_light_list(self, tile_x, tile_y):
+        """Light indices the culling stage of this context's last tiled pass left for 32x32 light tile (tile_x, tile_y), as a
+        uint32 array (test helper; synchronises)."""
+        out = np.zeros(capi.VR_TILE_LIGHT_CAP, np.uint32)
+        n = C.c_int32()
+        check(self.ctx.lib.vr_debug_tile_light_list(self.ctx.handle, tile_x, tile_y, _vp(out), out.size, C.byref(n)),
+              "vr_debug_tile_light_list")
+        return out[:n.value].copy()
 
 
 def synthetic_point_lights(n, world_size, heightmap, max_height=400.0, seed=9001, intensity=50.0):
