@@ -230,6 +230,27 @@ VR_API int  vr_terrain_lod_ranges(const vr_terrain* t, float out[VR_MAX_LODS]); 
  * 1 albedo SRGBA8); *w,*h receive the level size; host may be NULL to query sizes. */
 VR_API int  vr_terrain_download_mip(vr_terrain* t, int which, int level, void* host, size_t bytes,
                                     int32_t* w, int32_t* h, int32_t* levels);
+/* In-place edit of level 0 of a terrain's heightmap (which = 0, R8: 1 byte per texel) or albedo (which = 1, SRGBA8: 4 bytes per
+ * texel): the w x h texels at (x, y) are replaced by `texels` (rows row_pitch_bytes apart; 0 = tightly packed).  Afterwards
+ * every call on the terrain behaves exactly as on a terrain created from the edited arrays: the mip chain and the decoded
+ * tables, the node heights (where vr_terrain_update_heights(t, 1) is in force) and the query pyramid (where a ray cast has built
+ * it) are rebuilt inside the dirty rectangle of each, with the arithmetic vr_terrain_create uses.  Geometry prepared ahead
+ * (vr_terrain_prepare, vr_frame_desc::prepare_views) is stale after an edit of either map and is built again by the frame that
+ * would have used it; a lock_view frame keeps reusing the selection of the last unlocked frame.
+ * Order: the edit is stream-ordered on the context's stream, behind every geometry chain and tile pass queued so far.
+ *   device_pointer = 1: `texels` is device memory; the call synchronises nothing, and the caller keeps `texels` alive and
+ *     unchanged until the stream has passed the edit.
+ *   device_pointer = 0: `texels` is the caller's host memory; the call returns once it has been consumed (it synchronises the
+ *     stream, as vr_terrain_create does; staging memory is kept with the terrain, shared with the queries).
+ * w == 0 or h == 0 is VR_OK and queues nothing.  VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the
+ * terrain untouched and nothing launched: a NULL pointer with a non-empty rectangle; `which` not 0 or 1; a negative coordinate
+ * or extent; a rectangle not wholly inside level 0; a non-zero pitch smaller than w texels; a device pointer (or its pitch) not
+ * aligned to the texel size.  An edit allocates nothing once it has begun to write: the staging memory of the host-pointer mode
+ * is reserved before anything is launched, and a refusal (VR_ERR_OUT_OF_MEMORY) leaves the terrain as it was.
+ * Timing: the node-height work counts under VR_K_NODE_HEIGHTS, the pyramid work under VR_K_QUERY_PYRAMID; the mip and table
+ * kernels are untimed, as at create time. */
+VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32_t y, int32_t w, int32_t h,
+                           const void* texels, size_t row_pitch_bytes, int device_pointer);
 
 /* QuadTree::SetHeight for every node (QuadTree.cpp:164-208) as a device reduction over the heightmap,
  * and m_HeightLoaded (QuadTree.h:70).  The reference wrote this and left its launch commented out

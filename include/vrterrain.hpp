@@ -202,6 +202,13 @@ namespace vRenderer
         {
             return Check(vr_terrain_cast_rays(m_Terrain, rays, n, m_MaxHeight, hits, 0), "vr_terrain_cast_rays");
         }
+        // vr_terrain_edit: the w x h texels at (x, y) of the heightmap's (which = 0, 1 byte each) or the albedo's (which = 1, 4 bytes
+        // each) level 0 are replaced in place; afterwards the pass behaves as one initialised from the edited arrays.  Host memory
+        // by default (the call returns once it has been consumed); devicePointer: stream-ordered, nothing is synchronised.
+        bool Edit(int which, int32_t x, int32_t y, int32_t w, int32_t h, const void* texels, size_t rowPitchBytes = 0, bool devicePointer = false)
+        {
+            return Check(vr_terrain_edit(m_Terrain, which, x, y, w, h, texels, rowPitchBytes, devicePointer ? 1 : 0), "vr_terrain_edit");
+        }
         void SetMaxHeight(float maxHeight) { m_MaxHeight = maxHeight; }      // for queries before the first Render
         const std::vector<std::shared_ptr<QuadTree>>& GetQuadTrees() const { return m_QuadTrees; }
         vr_terrain* Get() const { return m_Terrain; }

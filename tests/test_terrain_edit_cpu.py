@@ -1,0 +1,46 @@
+"""CPU tests of vr_terrain_edit: the entry point is declared, mirrored and exported, the kernel ids stay as they were, and
+the dirty-rectangle rules of vrenderer_amd/csrc/vr_dirty.h hold against a full rebuild (tests/host/dirty_check.cpp)."""
+import os
+import re
+import subprocess
+
+from vrenderer_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_edit_is_declared_mirrored_and_exported(product_lib):
+    header = open(os.path.join(ROOT, "include", "vrterrain.h")).read()
+    assert re.search(r"VR_API\s+int\s+vr_terrain_edit\s*\(\s*vr_terrain\*\s*t,\s*int which,\s*int32_t x,\s*int32_t y,\s*int32_t w,\s*int32_t h,"
+                     r"\s*const void\*\s*texels,\s*size_t row_pitch_bytes,\s*int device_pointer\)", header)
+    assert "vr_terrain_edit" in capi.EXPORTS
+    assert hasattr(product_lib, "vr_terrain_edit")
+    assert len(product_lib.vr_terrain_edit.argtypes) == 9
+    # an edit adds no kernel id: its node-height and pyramid work is timed under the ids there are
+    assert capi.VR_K_COUNT == 22 and product_lib.vr_timing_kernel_count() == 22
+    hpp = open(os.path.join(ROOT, "include", "vrterrain.hpp")).read()
+    assert "Edit(" in hpp and "vr_terrain_edit" in hpp
+    # argument checks come before any use of the device: they answer on a machine without one
+    assert product_lib.vr_terrain_edit(None, 0, 0, 0, 1, 1, None, 0, 0) == capi.VR_ERR_INVALID_ARGUMENT
+
+
+def _build_check(tmp_path, name, extra):
+    exe = os.path.join(str(tmp_path), name)
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host", "dirty_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    return exe
+
+
+def test_dirty_rectangles_hold_what_a_full_rebuild_changes(tmp_path):
+    """vr_dirty.h compiles without HIP.  For every rectangle of every map of 1..9 x 1..9 texels and 2000 seeded rectangles each
+    of 16 x 16, 17 x 5 and 32 x 32 (tests/host/dirty_check.cpp) whatever a full rebuild changes - chain, the three table shapes,
+    the dyadic min / max tree, the query pyramid, at every level - lies inside the predicted rectangle, and the prediction is
+    within the program's stated K elements per axis of what changed.  Run once more under the address and undefined-behaviour
+    sanitizers, as a stand-alone program."""
+    r = subprocess.run([_build_check(tmp_path, "dirty_check", [])], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    assert "33225 rectangles" in r.stdout, r.stdout[-400:]      # sum over w, h in 1..9 of w (w + 1) / 2 * h (h + 1) / 2 = 165^2, + 3 x 2000
+    san = _build_check(tmp_path, "dirty_check_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    r = subprocess.run([san], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]

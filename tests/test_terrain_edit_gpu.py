@@ -1,0 +1,368 @@
+"""GPU tests of vr_terrain_edit: after an edit a terrain is indistinguishable from one freshly created from the edited
+arrays.  Terrain A is created from the original maps, put into the state under test (SetHeight(True), one ray cast so the query
+pyramid exists, one frame rendered) and edited; terrain B is created afresh from the edited arrays.  Everything the library
+exposes is compared bit for bit - no tolerance anywhere: both sides run the same kernels' arithmetic.
+
+Scenes, the smallest at which each mechanism can go wrong: 64^2 + 64^2 (the tile pass's fast variant, the dyadic SetHeight
+path), 67x45 height + 33x50 albedo (odd chains, the clamped last column, the non-dyadic SetHeight path, the general raster
+variant) and a 2x2-surface world of 128 on 128^2 maps (per-surface node bases)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import vrenderer_amd as vr
+from vrenderer_amd import capi
+from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
+from tests import queries_common as qc
+from tests.f64_queries import Surface64
+
+pytestmark = pytest.mark.gpu
+
+PLANES = ("depth", "diffuse", "specular", "normals", "emissive")
+W, H = 256, 144
+SCENES = ("fast64", "odd", "multi")
+RENDER_CAMERAS = (0, 5, 7)
+
+
+def _bits(a):
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+class Scene:
+    """The original maps of one scene, its terrain parameters and the world size its cameras are scaled to."""
+
+    def __init__(self, ctx, name):
+        self.ctx, self.name = ctx, name
+        if name == "fast64":
+            self.hm = vr.synth_heightmap(ctx, 64)
+            self.al = vr.synth_albedo(ctx, 64, self.hm)
+            self.p, self.world = params(64), 64
+        elif name == "odd":
+            self.hm = np.ascontiguousarray(vr.synth_heightmap(ctx, 67)[:45, :67])
+            h50 = vr.synth_heightmap(ctx, 50)
+            self.al = np.ascontiguousarray(vr.synth_albedo(ctx, 50, h50)[:50, :33])
+            self.p, self.world = params(64), 64
+        else:
+            self.hm = vr.synth_heightmap(ctx, 128)
+            self.al = vr.synth_albedo(ctx, 128, self.hm)
+            self.p, self.world = params(64), 128
+            self.p.world_size = 128.0
+        self.mh = qc.scaled_max_height(self.world)
+
+    def terrain(self, hm, al, cast=True, render=True):
+        """A terrain of (hm, al) in the state under test: node heights on, the pyramid built by one cast, one frame rendered."""
+        tp = vr.TerrainPass(self.ctx, self.p).Init(hm, al)
+        tp.SetHeight(True)
+        if cast:
+            tp.CastRays(np.float32([[0.0, 4.0 * self.mh, 0.0]]), np.float32([[0.1, -1.0, 0.2]]), np.inf, self.mh)
+        if render:
+            rt = vr.RenderTargets(self.ctx).Init(W, H)
+            v = self.view(0)
+            tp.Render(v, v, rt, vr.default_render_params(self.mh))
+            rt.close()
+        return tp
+
+    def view(self, cam, w=W, h=H):
+        eye, tgt = scaled_camera(CAMERAS[cam], self.world)
+        return vr.make_view(eye, tgt, w, h)
+
+
+class Maps:
+    """Host copies of the two maps that follow every edit made to terrain A."""
+
+    def __init__(self, sc):
+        self.hm, self.al = sc.hm.copy(), sc.al.copy()
+
+    def edit(self, tp, which, x, y, texels):
+        tp.Edit(which, x, y, texels)
+        dst = self.hm if which == "height" else self.al
+        dst[y:y + texels.shape[0], x:x + texels.shape[1]] = texels
+
+    def random(self, tp, rng, which, x, y, w, h):
+        shape = (h, w) if which == "height" else (h, w, 4)
+        self.edit(tp, which, x, y, rng.integers(0, 256, shape, dtype=np.uint8))
+
+
+@pytest.fixture(scope="module")
+def scenes(gpu_ctx):
+    return {n: Scene(gpu_ctx, n) for n in SCENES}
+
+
+def _edit_some(sc, tp, maps, seed=7):
+    """A handful of edits of both maps that touch a corner, the interior and the right / bottom edges."""
+    rng = np.random.default_rng(seed)
+    for which, full in (("height", maps.hm), ("albedo", maps.al)):
+        fh, fw = full.shape[:2]
+        maps.random(tp, rng, which, 0, 0, 1, 1)
+        maps.random(tp, rng, which, 3, 5, 7, 9)
+        maps.random(tp, rng, which, fw - 6, fh - 4, 6, 4)
+        maps.random(tp, rng, which, fw // 2 - 1, 0, 1, fh)
+
+
+def _assert_chains_equal(a, b, what):
+    for which in ("height", "albedo"):
+        n = a.mip_levels(which)
+        assert n == b.mip_levels(which)
+        for l in range(n):
+            x, y = a.download_mip(which, l), b.download_mip(which, l)
+            assert np.array_equal(x, y), f"{what}: {which} level {l} differs in {(x != y).sum()} bytes, first {np.argwhere(x != y)[:4].tolist()}"
+
+
+def _render(sc, tp, cam, part=None, **rpkw):
+    rt = vr.RenderTargets(sc.ctx).Init(W, H)
+    if not rpkw.get("assume_cleared"):
+        rt.Clear()
+    v = sc.view(cam)
+    tp.Render(v, v, rt, vr.default_render_params(sc.mh, **rpkw), part)
+    out = {p: rt.download(p).copy() for p in PLANES}
+    rt.close()
+    return out
+
+
+def _assert_frames_equal(a, b, what):
+    for p in PLANES:
+        x, y = _bits(a[p]), _bits(b[p])
+        assert np.array_equal(x, y), f"{what}: {p} differs in {(x != y).sum()} elements, first {np.argwhere(x != y)[:4].tolist()}"
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_every_mip_level_after_every_kind_of_rectangle(scenes, name):
+    """1x1 at the four corners and at an odd interior coordinate, (3, 5) 7x9, a full-width row, a full-height column, the
+    rectangle that touches the right and bottom edges, the whole map, then 20 seeded random rectangles on height and albedo
+    alternately: after each sequence every level of both chains of A is B's, byte for byte."""
+    sc = scenes[name]
+    a, maps, rng = sc.terrain(sc.hm, sc.al), Maps(sc), np.random.default_rng(2024)
+
+    def both(fn):
+        for which, full in (("height", maps.hm), ("albedo", maps.al)):
+            fn(which, full.shape[1], full.shape[0])
+
+    sequences = [
+        ("corners", lambda wh, fw, fh: [maps.random(a, rng, wh, x, y, 1, 1) for x, y in ((0, 0), (fw - 1, 0), (0, fh - 1), (fw - 1, fh - 1))]),
+        ("odd interior texel", lambda wh, fw, fh: maps.random(a, rng, wh, 11, 7, 1, 1)),
+        ("(3, 5) 7x9", lambda wh, fw, fh: maps.random(a, rng, wh, 3, 5, 7, 9)),
+        ("full-width row", lambda wh, fw, fh: maps.random(a, rng, wh, 0, 13, fw, 1)),
+        ("full-height column", lambda wh, fw, fh: maps.random(a, rng, wh, 9, 0, 1, fh)),
+        ("right and bottom edges", lambda wh, fw, fh: maps.random(a, rng, wh, fw - 5, fh - 3, 5, 3)),
+        ("whole map", lambda wh, fw, fh: maps.random(a, rng, wh, 0, 0, fw, fh)),
+    ]
+    for what, fn in sequences:
+        both(fn)
+        b = sc.terrain(maps.hm, maps.al, cast=False, render=False)
+        _assert_chains_equal(a, b, f"{name}, {what}")
+        b.close()
+    for k in range(20):
+        which = "height" if k % 2 == 0 else "albedo"
+        fh, fw = (maps.hm if which == "height" else maps.al).shape[:2]
+        x, y = int(rng.integers(0, fw)), int(rng.integers(0, fh))
+        maps.random(a, rng, which, x, y, int(rng.integers(1, fw - x + 1)), int(rng.integers(1, fh - y + 1)))
+    b = sc.terrain(maps.hm, maps.al, cast=False, render=False)
+    _assert_chains_equal(a, b, f"{name}, 20 random rectangles")
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_every_gbuffer_plane(scenes, oracle, name):
+    """All five planes of A and B at 256x144, depth as bits: three cameras x fill over a cleared target (the fast variant on
+    the 64^2 scene), wireframe, depth_only and rank 1 of 3.  On the 64^2 scene A also equals the oracle on the edited arrays."""
+    sc = scenes[name]
+    a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
+    _edit_some(sc, a, maps)
+    b = sc.terrain(maps.hm, maps.al)
+    covered = 0
+    for cam in RENDER_CAMERAS:
+        for what, kw, part in (("fill", dict(assume_cleared=1), None), ("wireframe", dict(wireframe=1), None),
+                               ("depth_only", dict(depth_only=1), None), ("rank 1 of 3", {}, vr.Partition(1, 3))):
+            fa, fb = _render(sc, a, cam, part, **kw), _render(sc, b, cam, part, **kw)
+            _assert_frames_equal(fa, fb, f"{name}, camera {cam}, {what}")
+            covered += int((fa["depth"] < 1.0).sum())
+    assert covered > 0
+    if name == "fast64":
+        ot = oracle.OracleTerrain(sc.p, maps.hm, maps.al)
+        ot.set_height(True)
+        gb = oracle.GBufferHost(W, H)
+        ot.render(sc.view(0), gb, vr.default_render_params(sc.mh, assume_cleared=1))
+        fa = _render(sc, a, 0, None, assume_cleared=1)
+        _assert_frames_equal(fa, {p: getattr(gb, p) for p in PLANES}, "64^2 against the oracle on the edited arrays")
+        assert (fa["depth"] < 1.0).mean() > 0.05
+        ot.close()
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_node_heights_and_selection(scenes, name):
+    """node_heights(0, all) as uint32 and NodeSelect's ids and instances for two cameras: the dyadic path (64^2), the full
+    re-run (67x45) and the per-surface bases (2x2 surfaces)."""
+    sc = scenes[name]
+    a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
+    _edit_some(sc, a, maps)
+    # a tall spike and a pit, so that min and max of their nodes' ancestors move
+    spike = np.full((2, 2), 255, np.uint8)
+    maps.edit(a, "height", maps.hm.shape[1] // 2 + 1, maps.hm.shape[0] // 2 - 3, spike)
+    maps.edit(a, "height", 5, maps.hm.shape[0] - 7, np.zeros((3, 3), np.uint8))
+    b = sc.terrain(maps.hm, maps.al)
+    surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
+    nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
+    ha, hb = a.node_heights(0, nodes), b.node_heights(0, nodes)
+    assert np.array_equal(ha.view(np.uint32), hb.view(np.uint32)), f"{name}: {(ha.view(np.uint32) != hb.view(np.uint32)).any(1).sum()} of {nodes} nodes differ"
+    for cam in (0, 5):
+        v = sc.view(cam)
+        na, ia, insta = a.NodeSelect(v, sc.mh)
+        nb, ib, instb = b.NodeSelect(v, sc.mh)
+        assert na == nb and na > 0 and np.array_equal(ia, ib) and np.array_equal(insta, instb), (name, cam, na, nb)
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("cast_first", (True, False))
+@pytest.mark.parametrize("name", SCENES)
+def test_queries(scenes, name, cast_first):
+    """SampleHeights with normals at 4,096 seeded points and CastRays over queries_common.make_rays: the same bits, with the
+    pyramid built before the edit and with no cast before the edit."""
+    sc = scenes[name]
+    a, maps = sc.terrain(sc.hm, sc.al, cast=cast_first), Maps(sc)
+    _edit_some(sc, a, maps)
+    maps.edit(a, "height", 20, 20, np.full((5, 4), 250, np.uint8))
+    b = sc.terrain(maps.hm, maps.al, cast=False)
+    pts = qc.uniform_points(sc.world)
+    (h1, n1), (h2, n2) = a.SampleHeights(pts, sc.mh, normals=True), b.SampleHeights(pts, sc.mh, normals=True)
+    assert np.array_equal(h1.view(np.uint32), h2.view(np.uint32)) and np.array_equal(n1.view(np.uint32), n2.view(np.uint32))
+    surf = Surface64(b.download_mip("height", 0), b.download_mip("height", 1), sc.world, sc.mh)
+    o, d, tm = qc.make_rays(surf, sc.world)
+    ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
+    assert ra.tobytes() == rb.tobytes(), f"{name}: {(ra != rb).sum()} of {len(ra)} hits differ"
+    assert (ra["status"] == capi.VR_RAY_HIT).mean() > 0.2
+    a.close(); b.close()
+
+
+def _submit_frames(sc, tp, views, fusion, edit=None, lock_after=False):
+    """Two vr_frame_submit frames with the next view prepared ahead; `edit` runs between them.  Returns per frame the planes,
+    HdrColor and the selected node ids."""
+    ctx = sc.ctx
+    ctx.set_frame_fusion(fusion)
+    rt, hdr = vr.RenderTargets(ctx).Init(W, H), vr.HdrImage(ctx, W, H)
+    out = []
+    try:
+        for i in range(2):
+            rp = vr.default_render_params(sc.mh, assume_cleared=1, lock_view=1 if (lock_after and i == 1) else 0)
+            fr = vr.Frame(tp, rt, rp, [vr.reference_sun()], AMBIENT_TOP, AMBIENT_BOTTOM)
+            rt.Clear()
+            hdr.upload(np.zeros(W * H * 4, np.uint16))
+            fr.submit(views[i], hdr, views[i + 1:i + 2])
+            ctx.synchronize()
+            f = {p: rt.download(p).copy() for p in PLANES}
+            f["hdr"] = hdr.download().copy()
+            f["chunks"] = tp.num_chunks()
+            out.append(f)
+            if i == 0 and edit is not None:
+                edit()
+    finally:
+        ctx.set_frame_fusion(1)
+        hdr.close(); rt.close()
+    return out
+
+
+def test_prepared_geometry_is_stale_after_an_edit(scenes):
+    """Prepare(view), Edit, Render(view): A's frame is B's - for a height edit and for an albedo edit.  Under vr_frame_submit
+    with prepare_views set, an edit between two submits gives B's second frame, fused and two-pass alike.  With lock_view the
+    frame after the edit draws the nodes of the frame before it."""
+    sc = scenes["fast64"]
+    rng = np.random.default_rng(99)
+    for which in ("height", "albedo"):
+        a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
+        rt = vr.RenderTargets(sc.ctx).Init(W, H)
+        v, rp = sc.view(5), vr.default_render_params(sc.mh, assume_cleared=1)
+        a.Prepare(v, rt, rp)
+        maps.random(a, rng, which, 10, 12, 30, 25)
+        rt.Clear(); a.Render(v, v, rt, rp)
+        fa = {p: rt.download(p).copy() for p in PLANES}
+        rt.close()
+        b = sc.terrain(maps.hm, maps.al)
+        _assert_frames_equal(fa, _render(sc, b, 5, None, assume_cleared=1), f"prepare, {which} edit, render")
+        a.close(); b.close()
+    views = [sc.view(5), sc.view(0), sc.view(0)]
+    results = {}
+    for fusion in (1, 0):
+        a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
+        erng = np.random.default_rng(5)
+        fa = _submit_frames(sc, a, views, fusion, edit=lambda: (maps.random(a, erng, "height", 8, 8, 40, 33), maps.random(a, erng, "albedo", 0, 30, 64, 9)))
+        b = sc.terrain(maps.hm, maps.al)
+        fb = _submit_frames(sc, b, views, fusion)
+        for p in PLANES + ("hdr",):
+            assert np.array_equal(_bits(fa[1][p]), _bits(fb[1][p])), f"frame submit, fusion {fusion}: {p} of the frame after the edit differs"
+        results[fusion] = fa
+        a.close(); b.close()
+    for p in PLANES + ("hdr",):
+        assert np.array_equal(_bits(results[1][1][p]), _bits(results[0][1][p])), f"fused and two-pass frames after the edit differ in {p}"
+    # lock_view: the frame after the edit draws the nodes of the frame before it (a node is named by two opposite corners of its
+    # patch: vertices 0 and 1088, which no morph moves)
+    a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
+    rt = vr.RenderTargets(sc.ctx).Init(W, H)
+    v0, v1 = sc.view(5), sc.view(0)
+
+    def corners(lock, v):
+        rt.Clear(); a.Render(v, v, rt, vr.default_render_params(sc.mh, lock_view=lock))
+        n = a.num_chunks()
+        return n, a.download_vertices(0, n)[:, [0, 1088], 4:6].copy()
+
+    n0, c0 = corners(0, v0)
+    maps.random(a, rng, "height", 0, 0, 64, 64)
+    n1, c1 = corners(1, v1)
+    assert n1 == n0 and np.array_equal(c0, c1)
+    n2, c2 = corners(0, v1)
+    assert n2 != n0 or not np.array_equal(c0, c2)                # (the unlocked frame of that view selects other nodes)
+    rt.close(); a.close()
+
+
+def test_device_pointer_mode_with_a_wide_pitch(scenes):
+    """A rectangle out of a torch tensor on the device whose rows are wider than the rectangle == the same edit in host mode."""
+    import torch
+    sc = scenes["odd"]
+    rng = np.random.default_rng(31)
+    a, b = sc.terrain(sc.hm, sc.al), sc.terrain(sc.hm, sc.al)
+    dev = f"cuda:{sc.ctx.device}"
+    for which, tb, (x, y, w, h) in (("height", 1, (5, 3, 21, 17)), ("albedo", 4, (2, 29, 31, 21)), ("height", 1, (66, 44, 1, 1))):
+        pitch = (w + 13) * tb
+        host = rng.integers(0, 256, (h, pitch), dtype=np.uint8)
+        t = torch.from_numpy(host).to(dev)
+        torch.cuda.synchronize()
+        a.Edit(which, x, y, device_ptr=t.data_ptr(), w=w, h=h, pitch=pitch)
+        sc.ctx.synchronize()
+        rect = host[:, :w * tb]
+        b.Edit(which, x, y, rect.copy() if tb == 1 else rect.reshape(h, w, 4).copy())
+    _assert_chains_equal(a, b, "device-pointer mode")
+    _assert_frames_equal(_render(sc, a, 0), _render(sc, b, 0), "device-pointer mode")
+    pts = qc.uniform_points(sc.world, 512)
+    assert np.array_equal(a.SampleHeights(pts, sc.mh), b.SampleHeights(pts, sc.mh))
+    a.close(); b.close()
+
+
+def test_refusals_leave_the_terrain_alone(scenes):
+    """Every invalid argument returns VR_ERR_INVALID_ARGUMENT, an empty rectangle VR_OK; the chains and a rendered frame of A
+    are what they were."""
+    import torch
+    sc = scenes["odd"]
+    a = sc.terrain(sc.hm, sc.al)
+    lib, hnd = sc.ctx.lib, a.handle
+    chains = {(wh, l): a.download_mip(wh, l) for wh in ("height", "albedo") for l in range(a.mip_levels(wh))}
+    frame = _render(sc, a, 0)
+    buf = np.full((64, 64, 4), 77, np.uint8)
+    p = buf.ctypes.data_as(C.c_void_p)
+    dev = torch.full((4096,), 77, dtype=torch.uint8, device=f"cuda:{sc.ctx.device}")
+    torch.cuda.synchronize()
+    bad = [(0, 0, 0, 4, 4, None, 0, 0),                     # NULL with a non-empty rectangle
+           (2, 0, 0, 4, 4, p, 0, 0), (-1, 0, 0, 4, 4, p, 0, 0),          # which
+           (0, -1, 0, 4, 4, p, 0, 0), (0, 0, -1, 4, 4, p, 0, 0), (0, 0, 0, -4, 4, p, 0, 0), (0, 0, 0, 4, -4, p, 0, 0),
+           (0, 64, 0, 4, 4, p, 0, 0), (0, 0, 42, 4, 4, p, 0, 0), (0, 0, 0, 68, 4, p, 0, 0), (0, 67, 45, 1, 1, p, 0, 0),     # outside 67 x 45
+           (1, 30, 0, 4, 4, p, 0, 0), (1, 0, 0, 33, 51, p, 0, 0), (0, 2**31 - 1, 0, 2**31 - 1, 1, p, 0, 0),                 # outside 33 x 50
+           (0, 0, 0, 8, 4, p, 7, 0), (1, 0, 0, 8, 4, p, 31, 0),          # pitch smaller than a row
+           (1, 0, 0, 4, 4, C.c_void_p(dev.data_ptr() + 2), 0, 1)]        # device pointer not aligned to the texel
+    for args in bad:
+        assert lib.vr_terrain_edit(hnd, *args) == capi.VR_ERR_INVALID_ARGUMENT, args
+    assert lib.vr_terrain_edit(None, 0, 0, 0, 1, 1, p, 0, 0) == capi.VR_ERR_INVALID_ARGUMENT
+    for args in ((0, 3, 3, 0, 5, p, 0, 0), (1, 3, 3, 5, 0, p, 0, 0), (0, 0, 0, 0, 0, None, 0, 0), (0, 67, 45, 0, 0, None, 0, 1)):
+        assert lib.vr_terrain_edit(hnd, *args) == capi.VR_OK, args
+    for (wh, l), want in chains.items():
+        assert np.array_equal(a.download_mip(wh, l), want), (wh, l)
+    _assert_frames_equal(_render(sc, a, 0), frame, "after the refusals")
+    a.close()

@@ -171,7 +171,7 @@ EXPORTS = [
     "vr_tonemap_default_params", "vr_tonemap_create", "vr_tonemap_destroy", "vr_tonemap_reset_exposure", "vr_tonemap_reset_histogram",
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
-    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray",
+    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray", "vr_terrain_edit",
 ]
 
 _lib = None
@@ -293,6 +293,7 @@ def load_library():
         "vr_terrain_query_heights": (C.c_int, [vp, vp, C.c_uint32, C.c_float, vp, vp, C.c_int]),
         "vr_terrain_cast_rays": (C.c_int, [vp, vp, C.c_uint32, C.c_float, vp, C.c_int]),
         "vr_view_pixel_ray": (C.c_int, [P(View), C.c_float, C.c_float, P(Ray)]),
+        "vr_terrain_edit": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int]),
     }
     for name in EXPORTS:
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

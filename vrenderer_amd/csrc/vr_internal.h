@@ -117,6 +117,13 @@ struct DevTex {
     uint32_t fast_bytes, pad2;
 };
 
+// Where the levels of a DevTex begin, on the host (the device reads the same figures from DevTex::off / qoff / fast_lv).
+struct TexLayout {
+    uint32_t off[kMaxLevels];          // bytes into the chain
+    uint32_t qoff[kMaxLevels];         // entries into quad / quadf (R8 only)
+    uint32_t fast_entry[kMaxLevels];   // entries into fast
+};
+
 // Per-light constants the deferred kernel reads (host precomputes the half-angle terms).
 struct DevLight {
     float dir[3];  int type;
@@ -326,6 +333,7 @@ struct vr_terrain {
     int num_lods;
     float lod_ranges[VR_MAX_LODS];
     DevTex height, albedo;
+    TexLayout height_layout, albedo_layout;
     uint8_t* d_height = nullptr; uint8_t* d_albedo = nullptr;
     uint64_t bytes_textures = 0, bytes_scratch = 0;     // vr_terrain_memory_bytes
     uint32_t extra_vert_cap = 0, hard_cap = 0;
@@ -347,7 +355,7 @@ struct vr_terrain {
     unsigned geo_turn = 0;
     // QuadTree::SetHeight results: (position.y, extents.y) per node id; m_HeightLoaded
     float2* d_node_heights = nullptr;
-    uchar2* d_minmax = nullptr;          // raw (min, max) bytes per node of one surface: scratch of the mip-style SetHeight
+    uchar2* d_minmax = nullptr;          // raw (min, max) bytes per node, surface by surface: the mip-style SetHeight's levels (an edit recomputes a node from its children's)
     bool height_loaded = false;
     float texel_size[2] = { 0.0f, 0.0f };   // m_TexelSize (QuadTree.cpp:29)
     int surfaces_per_side = 1;              // WORLD_SIZE / SURFACE_SIZE (TerrainPass.cpp:97)
@@ -362,12 +370,27 @@ struct vr_terrain {
     void* d_query_stage = nullptr; size_t query_stage_bytes = 0;
 };
 void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
+// the staging memory holds at least `bytes` (grown by doubling; on failure the terrain keeps what it had); whoever uses it
+// synchronises the context's stream before it returns
+int vr_query_reserve_stage(vr_terrain* t, size_t bytes);
+constexpr int kPyrMaxLevels = 16;           // (16384 + 1) cells on a side halve to 1 in 16 levels
+struct PyrDesc {
+    uint32_t off[kPyrMaxLevels];            // first cell of each level, in cells
+    int levels;
+    int cw, ch;                             // cells of level 0: w0 + 1, h0 + 1
+};
+PyrDesc vr_pyramid_desc(const vr_terrain* t, size_t* cells);     // (cells: all levels together; may be NULL)
+// QuadTree::SetHeight's per-surface inputs (vr_select.hip): the surface's location and, where the mip-style path applies to it,
+// the texel origin of its root and the texels per leaf node
+struct NodeSurface { float loc[3]; bool dyadic; int rx0, ry0, leaf; };
+NodeSurface vr_node_surface(const vr_terrain* t, int surf);
+int vr_node_heights_surface(vr_terrain* t, int surf, const NodeSurface& ns);     // the whole reduction of one surface, queued on the context's stream
 
 struct vr_tonemap;
 vr_context* vr_tonemap_context(vr_tonemap* tm);
 // ---- cross-TU entry points ----------------------------------------------------------
 int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, int texel_bytes,
-                          DevTex* out, uint8_t** out_mem, uint64_t* out_bytes = nullptr);
+                          DevTex* out, uint8_t** out_mem, uint64_t* out_bytes = nullptr, TexLayout* layout = nullptr);
 int vr_select_launch(vr_terrain* t, GeoSet& g, const vr_view* view, float max_height, hipStream_t stream);
 int vr_terrain_pick_set(vr_terrain* t);
 // In front of a frame's geometry (vr_terrain_prepare, the tile pass; vr_select.hip).  Completed chains' status words are read (no

@@ -35,6 +35,9 @@
 //   order_terrain_changing, order_terrain_changed
 //                           around a write of the node heights on the context's stream: behind every chain queued so far (a
 //                           select may still be reading them), and every set's next chain behind the write.
+//   order_terrain_tables_changing
+//                           in front of a write of the maps themselves (vr_terrain_edit), with order_terrain_changing: behind
+//                           every set's tile pass, which reads the maps' tables.
 //   order_image_writer_begins / _written / _reader_done
 //                           the pass that writes an image waits for the stage that still reads it; the stage on another stream
 //                           waits for the pass's own stop event (or an explicit record); the image remembers the stage.
@@ -197,6 +200,15 @@ int order_terrain_changed(OrderTerrain<Event>& t, OrderSet<Stream, Event>* const
 {
     VR_ORDER_TRY(ops.record(t.ev_changed, main));
     for (OrderSet<Stream, Event>* g : sets) g->main_dep.pending = true;
+    return 0;
+}
+
+// A write of the maps' tables on the context's stream (vr_terrain_edit), next to order_terrain_changing: behind every set's tile
+// pass, which reads them - on whatever stream the context had when that pass was queued.
+template <class Stream, class Event, class Ops, size_t N>
+int order_terrain_tables_changing(OrderSet<Stream, Event>* const (&sets)[N], const Ops& ops, Stream main, uint64_t epoch_now)
+{
+    for (OrderSet<Stream, Event>* g : sets) VR_ORDER_TRY(order_mark_wait(g->tile_pass, ops, main, epoch_now));
     return 0;
 }
 

@@ -18,22 +18,16 @@
 //                     root is refined against the sampler itself, and the reported point's height is the sampler's value.
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
+#include "vr_terrain_dev.h"
 #include "vr_experiments.h"
 
 #include <math.h>
 #include <string.h>
 
-constexpr int kPyrMaxLevels = 16;           // (16384 + 1) cells on a side halve to 1 in 16 levels
 constexpr float kInf = __builtin_huge_valf();
 // The walk starts at the pyramid's top; the experiment build of tools/exp_queries.py pins it to level 0 (a plain DDA over
 // the finest cells) to show what the pyramid buys.
 constexpr bool kWalkPinnedToLevel0 = kExpQueryLevel0;
-
-struct PyrDesc {
-    uint32_t off[kPyrMaxLevels];            // first cell of each level, in cells
-    int levels;
-    int cw, ch;                             // cells of level 0: w0 + 1, h0 + 1
-};
 
 struct QueryArgs {
     float world_size, max_height;
@@ -120,45 +114,20 @@ __global__ __launch_bounds__(256) void k_query_heights(DevTex hm, QueryArgs a, c
 // ---------------------------------------------------------------------------------------
 // bound pyramid
 // ---------------------------------------------------------------------------------------
-// Level 0.  Cell (ix, iz) is the quad table's entry (ix, iz): texel-centre coordinates X0 in [ix - 1, ix].  Its level-0 part is
-// bounded by the entry's four texels (a bilinear interpolant lies between its corners); its level-1 part by every level-1 texel
-// a bilinear tap at a point of the cell can touch: X1 = (X0 + 0.5) w1 / w0 - 0.5 over the cell, floor(X1) .. floor(X1) + 1,
-// widened by 1/64 texel for the sampler's fp32 rounding of uv.  The two combine at 0.9 : 0.1 in integers (units of 1/2550) and
-// round outwards to the 1/255 grid.
+// One lane per cell; a cell's expressions are vr_terrain_dev.h's (vr_pyramid_leaf_cell, vr_pyramid_up_cell), shared with the
+// in-place edit (vr_edit.hip).
 __global__ __launch_bounds__(256) void k_query_pyramid_leaf(DevTex hm, int cw, int ch, uchar2* __restrict__ out)
 {
     const int ix = blockIdx.x * 64 + (threadIdx.x & 63), iz = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (ix >= cw || iz >= ch) return;
-    const int w0 = hm.w0, h0 = hm.h0;
-    const int l1 = min(1, hm.levels - 1);
-    const int w1 = max(1, w0 >> l1), h1 = max(1, h0 >> l1);
-    const uint32_t e = hm.quad[hm.qoff[0] + (uint32_t)iz * (uint32_t)(w0 + 2) + (uint32_t)ix];
-    const uint32_t b0 = e & 255u, b1 = (e >> 8) & 255u, b2 = (e >> 16) & 255u, b3 = e >> 24;
-    const uint32_t mn0 = min(min(b0, b1), min(b2, b3)), mx0 = max(max(b0, b1), max(b2, b3));
-    const float m = 1.0f / 64.0f;
-    const float rx = (float)w1 / (float)w0, rz = (float)h1 / (float)h0;
-    int jx0 = (int)floorf(((float)ix - 0.5f) * rx - 0.5f - m), jx1 = (int)floorf(((float)ix + 0.5f) * rx - 0.5f + m) + 1;
-    int jz0 = (int)floorf(((float)iz - 0.5f) * rz - 0.5f - m), jz1 = (int)floorf(((float)iz + 0.5f) * rz - 0.5f + m) + 1;
-    jx0 = vr_clampi(jx0, 0, w1 - 1); jx1 = vr_clampi(jx1, 0, w1 - 1);
-    jz0 = vr_clampi(jz0, 0, h1 - 1); jz1 = vr_clampi(jz1, 0, h1 - 1);
-    const uint8_t* __restrict__ lv1 = hm.base + hm.off[l1];
-    uint32_t mn1 = 255u, mx1 = 0u;
-    for (int z = jz0; z <= jz1; z++)
-        for (int x = jx0; x <= jx1; x++) {
-            const uint32_t v = lv1[(size_t)z * w1 + x];
-            mn1 = min(mn1, v); mx1 = max(mx1, v);
-        }
-    const uint32_t lo = (9u * mn0 + mn1) / 10u, hi = (9u * mx0 + mx1 + 9u) / 10u;
-    out[(size_t)iz * cw + ix] = make_uchar2((unsigned char)lo, (unsigned char)min(hi, 255u));
+    vr_pyramid_leaf_cell(hm, cw, out, ix, iz);
 }
 
 __global__ __launch_bounds__(256) void k_query_pyramid_up(const uchar2* __restrict__ child, int cw, int ch, uchar2* __restrict__ parent, int pw, int ph)
 {
     const int px = blockIdx.x * 64 + (threadIdx.x & 63), pz = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (px >= pw || pz >= ph) return;
-    const int x0 = 2 * px, x1 = min(2 * px + 1, cw - 1), z0 = 2 * pz, z1 = min(2 * pz + 1, ch - 1);
-    const uchar2 a = child[(size_t)z0 * cw + x0], b = child[(size_t)z0 * cw + x1], c = child[(size_t)z1 * cw + x0], d = child[(size_t)z1 * cw + x1];
-    parent[(size_t)pz * pw + px] = make_uchar2(min(min(a.x, b.x), min(c.x, d.x)), max(max(a.y, b.y), max(c.y, d.y)));
+    vr_pyramid_up_cell(child, cw, ch, parent, pw, px, pz);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -374,7 +343,7 @@ static int grid_for(uint32_t n)
 }
 
 // staging of the host-pointer mode: kept with the terrain, grown by doubling
-static int reserve_stage(vr_terrain* t, size_t bytes)
+int vr_query_reserve_stage(vr_terrain* t, size_t bytes)
 {
     if (bytes <= t->query_stage_bytes) return VR_OK;
     size_t want = t->query_stage_bytes ? t->query_stage_bytes * 2 : (size_t)1 << 16;
@@ -392,7 +361,7 @@ void vr_query_release(vr_terrain* t)
     if (t->ev_pyramid) { (void)hipEventDestroy(t->ev_pyramid); t->ev_pyramid = nullptr; }
 }
 
-static PyrDesc pyramid_desc(const vr_terrain* t, size_t* cells)
+PyrDesc vr_pyramid_desc(const vr_terrain* t, size_t* cells)
 {
     PyrDesc pd; memset(&pd, 0, sizeof(pd));
     pd.cw = t->height.w0 + 1; pd.ch = t->height.h0 + 1;
@@ -413,7 +382,7 @@ static PyrDesc pyramid_desc(const vr_terrain* t, size_t* cells)
 static int ensure_pyramid(vr_terrain* t, PyrDesc* out)
 {
     size_t cells = 0;
-    *out = pyramid_desc(t, &cells);
+    *out = vr_pyramid_desc(t, &cells);
     hipStream_t s = t->ctx->stream;
     if (t->d_pyramid) {
         if (s != t->pyramid_stream) VR_HIP(hipStreamWaitEvent(s, t->ev_pyramid, 0));     // the host changed the context's stream since
@@ -464,7 +433,7 @@ extern "C" VR_API int vr_terrain_query_heights(vr_terrain* t, const float* xz, u
     const float2* d_xz = (const float2*)xz; float* d_h = out_height; float* d_n = out_normal;
     const size_t b_xz = (size_t)n * 8, b_h = ((size_t)n * 4 + 15) / 16 * 16, b_n = (size_t)n * 12;
     if (!device_pointers) {
-        const int rc = reserve_stage(t, b_xz + b_h + (out_normal ? b_n : 0));
+        const int rc = vr_query_reserve_stage(t, b_xz + b_h + (out_normal ? b_n : 0));
         if (rc) return rc;
         char* base = (char*)t->d_query_stage;
         d_xz = (const float2*)base; d_h = (float*)(base + b_xz); d_n = out_normal ? (float*)(base + b_xz + b_h) : nullptr;
@@ -498,7 +467,7 @@ extern "C" VR_API int vr_terrain_cast_rays(vr_terrain* t, const vr_ray* rays, ui
     const float4* d_rays = (const float4*)rays; float4* d_hits = (float4*)hits;
     const size_t b = (size_t)n * 32;
     if (!device_pointers) {
-        const int rc = reserve_stage(t, 2 * b);
+        const int rc = vr_query_reserve_stage(t, 2 * b);
         if (rc) return rc;
         d_rays = (const float4*)t->d_query_stage; d_hits = (float4*)((char*)t->d_query_stage + b);
     }

@@ -12,6 +12,7 @@
 // Nothing is allocated per frame and nothing crosses PCIe: UpdateTransforms
 // (TerrainPass.cpp:234-256) is fused into the write-out.
 #include "vr_internal.h"
+#include "vr_terrain_dev.h"
 #include "vr_experiments.h"
 
 #include <math.h>
@@ -297,13 +298,6 @@ __device__ __forceinline__ int height_byte(const HeightArgs& a, const uint8_t* _
     index = index < 0 ? 0 : (index >= n ? n - 1 : index);
     return tex[index];
 }
-__device__ __forceinline__ float2 finish_minmax(int mnb, int mxb)
-{
-    float mn = mnb <= 255 ? (float)mnb / 255.0f : INFINITY, mx = mxb >= 0 ? (float)mxb / 255.0f : -INFINITY;
-    mn = (mx - mn) == 0.0f ? 0.0f : mn;
-    const float extent = (mx - mn) / 2.0f;
-    return make_float2(mn + extent, extent);          // m_Position.y, m_Extents.y (QuadTree.cpp:197-198)
-}
 __device__ __forceinline__ NodeGeom node_from_index(const HeightArgs& a, uint32_t ix, uint32_t iz, int depth)
 {
     SelectArgs s;   // only the fields node_from_path reads; a.loc is already the surface's location
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(256) void k_node_heights_block(HeightArgs a, const 
     if (threadIdx.x == 0) {
         mn = min(min(s_mn[0], s_mn[1]), min(s_mn[2], s_mn[3])); mx = max(max(s_mx[0], s_mx[1]), max(s_mx[2], s_mx[3]));
         const uint32_t base = (uint32_t)((((uint64_t)1 << (2 * a.depth)) - 1) / 3);
-        out[base + node] = finish_minmax(mn, mx);
+        out[base + node] = vr_finish_minmax(mn, mx);
     }
 }
 // one lane per node (small rectangles)
@@ -351,7 +345,7 @@ __global__ __launch_bounds__(256) void k_node_heights_thread(HeightArgs a, const
         int mn = 256, mx = -1;
         for (int i = x0; i < x1; i++) for (int j = y0; j < y1; j++) { const int b = height_byte(a, tex, i, j); mn = min(mn, b); mx = max(mx, b); }
         const uint32_t base = (uint32_t)((((uint64_t)1 << (2 * a.depth)) - 1) / 3);
-        out[base + node] = finish_minmax(mn, mx);
+        out[base + node] = vr_finish_minmax(mn, mx);
     }
 }
 
@@ -363,26 +357,14 @@ __global__ __launch_bounds__(256) void k_minmax_leaf(const uint8_t* __restrict__
                                                       uchar2* __restrict__ mm, float2* __restrict__ out)
 {
     const uint64_t total = (uint64_t)n * n;
-    for (uint64_t node = (uint64_t)blockIdx.x * 256 + threadIdx.x; node < total; node += (uint64_t)gridDim.x * 256) {
-        const uint32_t ix = (uint32_t)(node % n), iz = (uint32_t)(node / n);
-        const uint8_t* p = tex + (size_t)(ry0 + (int)iz * s) * tex_w + (rx0 + (int)ix * s);
-        int mn = 256, mx = -1;
-        for (int j = 0; j < s; j++) for (int i = 0; i < s; i++) { const int b = p[(size_t)j * tex_w + i]; mn = min(mn, b); mx = max(mx, b); }
-        mm[node] = make_uchar2((unsigned char)mn, (unsigned char)mx);
-        out[node] = finish_minmax(mn, mx);
-    }
+    for (uint64_t node = (uint64_t)blockIdx.x * 256 + threadIdx.x; node < total; node += (uint64_t)gridDim.x * 256)
+        vr_minmax_leaf_node(tex, tex_w, rx0, ry0, n, s, mm, out, (uint32_t)(node % n), (uint32_t)(node / n));
 }
 __global__ __launch_bounds__(256) void k_minmax_up(const uchar2* __restrict__ child, uint32_t n, uchar2* __restrict__ mm, float2* __restrict__ out)
 {
     const uint64_t total = (uint64_t)n * n;
-    for (uint64_t node = (uint64_t)blockIdx.x * 256 + threadIdx.x; node < total; node += (uint64_t)gridDim.x * 256) {
-        const uint32_t ix = (uint32_t)(node % n), iz = (uint32_t)(node / n);
-        const uchar2* c = child + (size_t)(2u * iz) * (2u * n) + 2u * ix;
-        const uchar2 a0 = c[0], a1 = c[1], a2 = c[2u * n], a3 = c[2u * n + 1];
-        const int mn = min(min((int)a0.x, (int)a1.x), min((int)a2.x, (int)a3.x)), mx = max(max((int)a0.y, (int)a1.y), max((int)a2.y, (int)a3.y));
-        mm[node] = make_uchar2((unsigned char)mn, (unsigned char)mx);
-        out[node] = finish_minmax(mn, mx);
-    }
+    for (uint64_t node = (uint64_t)blockIdx.x * 256 + threadIdx.x; node < total; node += (uint64_t)gridDim.x * 256)
+        vr_minmax_up_node(child, n, mm, out, (uint32_t)(node % n), (uint32_t)(node / n));
 }
 
 // texel origin of a surface's root if the mip-style path applies to it, else false
@@ -401,46 +383,45 @@ static bool dyadic_root(const vr_terrain* t, const float loc[3], int* rx0, int* 
     return true;
 }
 
-extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
+static uint64_t nodes_per_surface(const vr_terrain* t) { return ((((uint64_t)1 << (2 * (t->num_lods + 1))) - 1) / 3); }
+
+NodeSurface vr_node_surface(const vr_terrain* t, int surf)
 {
-    VR_REQUIRE(t != nullptr, "terrain is NULL");
-    VR_HIP(hipSetDevice(t->ctx->device));
-    for (GeoSet& g : t->sets) g.prepared = false;          // geometry prepared with the old bounds is stale
-    if (!enable) { t->height_loaded = false; return VR_OK; }
-    const uint64_t nodes = ((((uint64_t)1 << (2 * (t->num_lods + 1))) - 1) / 3);
-    const int num_surfaces = t->surfaces_per_side * t->surfaces_per_side;
-    if (!t->d_node_heights) VR_HIP(hipMalloc(&t->d_node_heights, nodes * num_surfaces * sizeof(float2)));
-    HeightArgs a;
-    a.half_w = t->p.surface_size / 2.0f; a.half_h = t->p.surface_size / 2.0f; a.world_size = t->p.world_size;
-    a.texel_x = t->texel_size[0]; a.texel_y = t->texel_size[1]; a.tex_w = t->height.w0; a.tex_h = t->height.h0;
-    // a select queued earlier may still be reading the heights; every set's next chain runs behind the new ones
-    static_assert(kGeoSets == 3, "the list below");
-    VrOrderSet* const ord_sets[kGeoSets] = { &t->sets[0].ord, &t->sets[1].ord, &t->sets[2].ord };
-    { const int rc = order_terrain_changing(ord_sets, VrOrderOps(), t->ctx->stream); if (rc) return rc; }
-    VrKernelScope ks(t->ctx, VR_K_NODE_HEIGHTS);
-    for (int surf = 0; surf < num_surfaces; surf++) {
+    NodeSurface ns;
     {   // TerrainPass.cpp:102-108
         const int column = surf % t->surfaces_per_side, row = surf / t->surfaces_per_side;
         const float x = -0.5f * (float)(t->surfaces_per_side - 1) + (float)column, y = -0.5f * (float)(t->surfaces_per_side - 1) + (float)row;
-        a.loc[0] = t->p.location[0] + x * t->p.surface_size; a.loc[1] = t->p.location[1] + 0.0f; a.loc[2] = t->p.location[2] + y * t->p.surface_size;
+        ns.loc[0] = t->p.location[0] + x * t->p.surface_size; ns.loc[1] = t->p.location[1] + 0.0f; ns.loc[2] = t->p.location[2] + y * t->p.surface_size;
     }
+    ns.rx0 = 0; ns.ry0 = 0; ns.leaf = 0;
+    ns.dyadic = dyadic_root(t, ns.loc, &ns.rx0, &ns.ry0, &ns.leaf);
+    return ns;
+}
+
+// d_node_heights exists, and d_minmax if ns.dyadic (one array of raw bytes per surface: an edit recomputes a node from its children's)
+int vr_node_heights_surface(vr_terrain* t, int surf, const NodeSurface& ns)
+{
+    const uint64_t nodes = nodes_per_surface(t);
     float2* out = t->d_node_heights + (size_t)surf * nodes;
-    int rx0 = 0, ry0 = 0, leaf = 0;
-    if (dyadic_root(t, a.loc, &rx0, &ry0, &leaf)) {
-        if (!t->d_minmax) VR_HIP(hipMalloc(&t->d_minmax, nodes * sizeof(uchar2)));
+    if (ns.dyadic) {
+        uchar2* mm = t->d_minmax + (size_t)surf * nodes;
         for (int d = t->num_lods; d >= 0; d--) {
             const uint32_t n = 1u << d;
             const uint64_t base = ((((uint64_t)1 << (2 * d)) - 1) / 3), cells = (uint64_t)n * n, blocks = (cells + 255) / 256;
             const unsigned grid = (unsigned)(blocks > 16384 ? 16384 : blocks);
             if (d == t->num_lods)
-                hipLaunchKernelGGL(k_minmax_leaf, dim3(grid), dim3(256), 0, t->ctx->stream, (const uint8_t*)t->d_height, t->height.w0, rx0, ry0, n, leaf,
-                                   t->d_minmax + base, out + base);
+                hipLaunchKernelGGL(k_minmax_leaf, dim3(grid), dim3(256), 0, t->ctx->stream, (const uint8_t*)t->d_height, t->height.w0, ns.rx0, ns.ry0, n, ns.leaf,
+                                   mm + base, out + base);
             else
                 hipLaunchKernelGGL(k_minmax_up, dim3(grid), dim3(256), 0, t->ctx->stream,
-                                   (const uchar2*)(t->d_minmax + ((((uint64_t)1 << (2 * (d + 1))) - 1) / 3)), n, t->d_minmax + base, out + base);
+                                   (const uchar2*)(mm + ((((uint64_t)1 << (2 * (d + 1))) - 1) / 3)), n, mm + base, out + base);
         }
-        continue;
+        return VR_OK;
     }
+    HeightArgs a;
+    a.half_w = t->p.surface_size / 2.0f; a.half_h = t->p.surface_size / 2.0f; a.world_size = t->p.world_size;
+    a.texel_x = t->texel_size[0]; a.texel_y = t->texel_size[1]; a.tex_w = t->height.w0; a.tex_h = t->height.h0;
+    a.loc[0] = ns.loc[0]; a.loc[1] = ns.loc[1]; a.loc[2] = ns.loc[2];
     for (int d = 0; d <= t->num_lods; d++) {
         a.depth = d;
         const uint64_t n = (uint64_t)1 << (2 * d);
@@ -454,7 +435,27 @@ extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
                                t->d_height, out);
         }
     }
-    }
+    return VR_OK;
+}
+
+extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
+{
+    VR_REQUIRE(t != nullptr, "terrain is NULL");
+    VR_HIP(hipSetDevice(t->ctx->device));
+    for (GeoSet& g : t->sets) g.prepared = false;          // geometry prepared with the old bounds is stale
+    if (!enable) { t->height_loaded = false; return VR_OK; }
+    const uint64_t nodes = nodes_per_surface(t);
+    const int num_surfaces = t->surfaces_per_side * t->surfaces_per_side;
+    if (!t->d_node_heights) VR_HIP(hipMalloc(&t->d_node_heights, nodes * num_surfaces * sizeof(float2)));
+    bool any_dyadic = false;
+    for (int surf = 0; surf < num_surfaces; surf++) any_dyadic |= vr_node_surface(t, surf).dyadic;
+    if (any_dyadic && !t->d_minmax) VR_HIP(hipMalloc(&t->d_minmax, nodes * num_surfaces * sizeof(uchar2)));
+    // a select queued earlier may still be reading the heights; every set's next chain runs behind the new ones
+    static_assert(kGeoSets == 3, "the list below");
+    VrOrderSet* const ord_sets[kGeoSets] = { &t->sets[0].ord, &t->sets[1].ord, &t->sets[2].ord };
+    { const int rc = order_terrain_changing(ord_sets, VrOrderOps(), t->ctx->stream); if (rc) return rc; }
+    VrKernelScope ks(t->ctx, VR_K_NODE_HEIGHTS);
+    for (int surf = 0; surf < num_surfaces; surf++) { const int rc = vr_node_heights_surface(t, surf, vr_node_surface(t, surf)); if (rc) return rc; }
     VR_HIP(hipGetLastError());
     { const int rc = order_terrain_changed(t->ord, ord_sets, VrOrderOps(), t->ctx->stream); if (rc) return rc; }
     t->height_loaded = true;
@@ -577,8 +578,8 @@ extern "C" VR_API int vr_terrain_create(vr_context* ctx, const vr_terrain_params
     t->num_lods = (VR_MAX_LODS - 1) < l2 ? (VR_MAX_LODS - 1) : l2;
     t->texel_size[0] = (float)hm_w / params->world_size; t->texel_size[1] = (float)hm_h / params->world_size;   // QuadTree.cpp:29
     int rc;
-    if ((rc = vr_tex_upload_and_mip(ctx, height_r8, hm_w, hm_h, 1, &t->height, &t->d_height, &t->bytes_textures))) return rc;
-    if ((rc = vr_tex_upload_and_mip(ctx, albedo, al_w, al_h, 4, &t->albedo, &t->d_albedo, &t->bytes_textures))) return rc;
+    if ((rc = vr_tex_upload_and_mip(ctx, height_r8, hm_w, hm_h, 1, &t->height, &t->d_height, &t->bytes_textures, &t->height_layout))) return rc;
+    if ((rc = vr_tex_upload_and_mip(ctx, albedo, al_w, al_h, 4, &t->albedo, &t->d_albedo, &t->bytes_textures, &t->albedo_layout))) return rc;
     const size_t mi = (size_t)params->max_instances;
     t->extra_vert_cap = 1u << 16; t->hard_cap = 1u << 15;
     for (GeoSet& g : t->sets) {         // what does not depend on the scratch's capacity
@@ -786,7 +787,8 @@ extern "C" VR_API int vr_terrain_memory_bytes(const vr_terrain* t, uint64_t out[
     uint64_t heights = 0;
     if (t->d_node_heights) {
         const uint64_t nodes = ((((uint64_t)1 << (2 * (t->num_lods + 1))) - 1) / 3);
-        heights = nodes * (uint64_t)(t->surfaces_per_side * t->surfaces_per_side) * sizeof(float2) + (t->d_minmax ? nodes * sizeof(uchar2) : 0);
+        const uint64_t surfaces = (uint64_t)(t->surfaces_per_side * t->surfaces_per_side);
+        heights = nodes * surfaces * sizeof(float2) + (t->d_minmax ? nodes * surfaces * sizeof(uchar2) : 0);
     }
     out[0] = t->bytes_textures + t->pyramid_bytes; out[1] = t->bytes_scratch + tiles + t->query_stage_bytes; out[2] = heights; out[3] = out[0] + out[1] + out[2];
     return VR_OK;

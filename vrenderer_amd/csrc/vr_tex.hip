@@ -2,21 +2,18 @@
 // generators (the reference's media/ directory is git-ignored: .gitignore:36,52).
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
+#include "vr_terrain_dev.h"
 
 #include <string.h>
 
-// 2x2 box downsample of an R8_UNORM level: round(avg * 255) == (sum + 2) >> 2.
+// One lane per element of a level; the expressions are vr_terrain_dev.h's (shared with the in-place edit, vr_edit.hip).
 __global__ void k_mip_r8(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh)
 {
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= dw || y >= dh) return;
-    int x0 = 2 * x, x1 = min(2 * x + 1, sw - 1), y0 = 2 * y, y1 = min(2 * y + 1, sh - 1);
-    int sum = src[y0 * sw + x0] + src[y0 * sw + x1] + src[y1 * sw + x0] + src[y1 * sw + x1];
-    dst[y * dw + x] = (uint8_t)((sum + 2) >> 2);
+    vr_mip_r8_texel(src, sw, sh, dst, dw, x, y);
 }
 
-// SRGBA8 level: decode to linear, average, re-encode (what a blit into an SRGBA8
-// render target does); alpha is linear.
 __global__ void k_mip_srgba8(const uint32_t* __restrict__ src, int sw, int sh, uint32_t* __restrict__ dst, int dw, int dh,
                              const float* __restrict__ lut_g, const float* __restrict__ thr_g)
 {
@@ -27,40 +24,21 @@ __global__ void k_mip_srgba8(const uint32_t* __restrict__ src, int sw, int sh, u
     __syncthreads();
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= dw || y >= dh) return;
-    int x0 = 2 * x, x1 = min(2 * x + 1, sw - 1), y0 = 2 * y, y1 = min(2 * y + 1, sh - 1);
-    uint32_t p00 = src[(size_t)y0 * sw + x0], p10 = src[(size_t)y0 * sw + x1];
-    uint32_t p01 = src[(size_t)y1 * sw + x0], p11 = src[(size_t)y1 * sw + x1];
-    uint32_t o = 0;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        int sh8 = 8 * c;
-        float a = (lut[(p00 >> sh8) & 255u] + lut[(p10 >> sh8) & 255u]) + (lut[(p01 >> sh8) & 255u] + lut[(p11 >> sh8) & 255u]);
-        o |= vr_srgb_encode(a * 0.25f, thr) << sh8;
-    }
-    uint32_t al = ((p00 >> 24) + (p10 >> 24) + (p01 >> 24) + (p11 >> 24) + 2u) >> 2;
-    dst[(size_t)y * dw + x] = o | (al << 24);
+    vr_mip_srgba8_texel(src, sw, sh, dst, dw, x, y, lut, thr);
 }
 
 __global__ void k_build_quads(const uint8_t* __restrict__ src, int w, int h, uint32_t* __restrict__ dst)
 {
     const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
     if (ix >= w + 2 || iy >= h + 2) return;
-    const int x0 = min(max(ix - 1, 0), w - 1), x1 = min(max(ix, 0), w - 1);
-    const int y0 = min(max(iy - 1, 0), h - 1), y1 = min(max(iy, 0), h - 1);
-    dst[(size_t)iy * (w + 2) + ix] = (uint32_t)src[y0 * w + x0] | ((uint32_t)src[y0 * w + x1] << 8)
-                                   | ((uint32_t)src[y1 * w + x0] << 16) | ((uint32_t)src[y1 * w + x1] << 24);
+    vr_quad_entry(src, w, h, dst, ix, iy);
 }
 
 __global__ void k_build_quads_f32(const uint8_t* __restrict__ src, int w, int h, float4* __restrict__ dst)
 {
     const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
     if (ix >= w + 2 || iy >= h + 2) return;
-    const int x0 = min(max(ix - 1, 0), w - 1), x1 = min(max(ix, 0), w - 1);
-    const int y0 = min(max(iy - 1, 0), h - 1), y1 = min(max(iy, 0), h - 1);
-    // UNORM8 -> float, correctly rounded, and the differences the bilinear filter forms first
-    const float t00 = (float)src[y0 * w + x0] / 255.0f, t10 = (float)src[y0 * w + x1] / 255.0f;
-    const float t01 = (float)src[y1 * w + x0] / 255.0f, t11 = (float)src[y1 * w + x1] / 255.0f;
-    dst[(size_t)iy * (w + 2) + ix] = make_float4(t00, t10 - t00, t01, t11 - t01);
+    vr_footprint_entry(src, w, h, dst, w + 2, ix, iy);
 }
 
 // Tables of the tile pass's fast variant (DevTex::fast): (w+3) x (h+3) clamp-addressed entries per level.
@@ -68,29 +46,21 @@ __global__ void k_build_fast_r8(const uint8_t* __restrict__ src, int w, int h, f
 {
     const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
     if (ix >= w + 3 || iy >= h + 3) return;
-    const int x0 = min(max(ix - 1, 0), w - 1), x1 = min(max(ix, 0), w - 1);
-    const int y0 = min(max(iy - 1, 0), h - 1), y1 = min(max(iy, 0), h - 1);
-    const float t00 = (float)src[y0 * w + x0] / 255.0f, t10 = (float)src[y0 * w + x1] / 255.0f;
-    const float t01 = (float)src[y1 * w + x0] / 255.0f, t11 = (float)src[y1 * w + x1] / 255.0f;
-    dst[(size_t)iy * (w + 3) + ix] = make_float4(t00, t10 - t00, t01, t11 - t01);
+    vr_footprint_entry(src, w, h, dst, w + 3, ix, iy);
 }
 __global__ void k_build_fast_srgba8(const uint32_t* __restrict__ src, int w, int h, const float* __restrict__ lut, float4* __restrict__ dst)
 {
     const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
     if (ix >= w + 3 || iy >= h + 3) return;
-    const uint32_t p = src[(size_t)min(max(iy - 1, 0), h - 1) * w + min(max(ix - 1, 0), w - 1)];
-    dst[(size_t)iy * (w + 3) + ix] = make_float4(lut[p & 255u], lut[(p >> 8) & 255u], lut[(p >> 16) & 255u], 0.0f);
+    vr_fast_srgba8_entry(src, w, h, lut, dst, ix, iy);
 }
 
 __global__ void k_decode_rgbf(const uint32_t* __restrict__ src, size_t n, const float* __restrict__ lut, float* __restrict__ dst)
 {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t p = src[i];
-        reinterpret_cast<float4*>(dst)[i] = make_float4(lut[p & 255u], lut[(p >> 8) & 255u], lut[(p >> 16) & 255u], 0.0f);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) vr_rgbf_texel(src, i, lut, dst);
 }
 
-int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, int tb, DevTex* out, uint8_t** out_mem, uint64_t* out_bytes)
+int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, int tb, DevTex* out, uint8_t** out_mem, uint64_t* out_bytes, TexLayout* layout)
 {
     VR_REQUIRE(host && w > 0 && h > 0 && w <= 16384 && h <= 16384, "bad texture");
     // The tile pass reads DECODED copies (16 B per heightmap footprint and per albedo texel) through 32-bit byte offsets:
@@ -197,6 +167,7 @@ int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, in
     out->base = mem; out->off = (const uint32_t*)(mem + table_off); out->levels = levels; out->w0 = w; out->h0 = h;
     out->chain_bytes = (uint32_t)table_off; out->quad_bytes = (uint32_t)(quad_dwords * sizeof(uint32_t)); out->pad = 0;
     *out_mem = mem;
+    if (layout) for (int l = 0; l < kMaxLevels; l++) { layout->off[l] = off[l]; layout->qoff[l] = qoff[l]; layout->fast_entry[l] = l < levels ? (uint32_t)fast_entry[l] : 0u; }
     return VR_OK;
 }
 

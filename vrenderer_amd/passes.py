@@ -487,6 +487,20 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_cast_rays(self.handle, _vp(rays), rays.shape[0], max_height, _vp(hits), 0), "vr_terrain_cast_rays")
         return hits
 
+    def Edit(self, which, x, y, texels=None, device_ptr=None, w=None, h=None, pitch=0):
+        """vr_terrain_edit: replaces a sub-rectangle of level 0 of the heightmap (which = 'height' / 0) or the albedo ('albedo' / 1)
+        at (x, y) in place; afterwards the terrain is the one Init would build from the edited arrays.  With device_ptr=None,
+        `texels` is a numpy array, uint8 (h, w) for the height and uint8 (h, w, 4) for the albedo, and the call returns once it
+        has been consumed.  Otherwise device_ptr is a raw device pointer to w x h texels whose rows are `pitch` bytes apart
+        (0 = tightly packed); the edit is then stream-ordered and the memory must stay as it is until the stream has passed it."""
+        idx = {"height": 0, "albedo": 1}.get(which, which)
+        if device_ptr is None:
+            a = np.ascontiguousarray(texels, np.uint8)
+            assert (a.ndim == 2) if idx == 0 else (a.ndim == 3 and a.shape[2] == 4)
+            check(self.ctx.lib.vr_terrain_edit(self.handle, idx, x, y, a.shape[1], a.shape[0], _vp(a), 0, 0), "vr_terrain_edit")
+        else:
+            check(self.ctx.lib.vr_terrain_edit(self.handle, idx, x, y, w, h, C.c_void_p(device_ptr), pitch, 1), "vr_terrain_edit")
+
     def Prepare(self, view, render_targets, render_params, partition=None):
         """Build the next frame's geometry ahead of time (overlaps the current frame's tile pass)."""
         check(self.ctx.lib.vr_terrain_prepare(self.handle, C.byref(view), render_targets.handle, C.byref(render_params),
