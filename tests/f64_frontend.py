@@ -3,7 +3,7 @@ written from the reference's text (QuadTree.cpp, QuadTree.h, TerrainPass.cpp, sh
 D3D / Donut rules DESIGN.md section 2 cites, NOT from oracle/vr_oracle.c or the kernels.
 
 Test infrastructure.  tests/test_frontend_cpu.py holds the C oracle to this file, tests/test_frontend_f64.py the HIP
-kernels (k_mip_*, k_node_heights_*, k_minmax_*, k_select, k_vertex).  What is taken as given:
+kernels (k_derive_mip_*, k_node_heights_*, k_derive_minmax_*, k_select, k_vertex).  What is taken as given:
   - the level-0 textures, the terrain parameters and the view as the caller hands them over in fp32: the two matrices, the
     six planes (outward normal, distance) and the camera position;
   - the numbering of nodes (include/vrterrain.h: id = (4^d - 1) / 3 + iz 2^d + ix, surfaces one tree after the other) and

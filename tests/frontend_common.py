@@ -20,6 +20,30 @@ def random_texture(w, h, seed):
 # (name, width, height, seed) of the random textures of the mip tests; the synthetic 256^2 pair is added by the tests
 MIP_TEXTURES = [("129x129", 129, 129, 11), ("67x41", 67, 41, 12), ("64x1", 64, 1, 13), ("1x37", 1, 37, 14), ("256x64", 256, 64, 15)]
 MIP_FLAG_CAP = 0.005
+# (width, height) of the maps of tests/test_terrain_create_gpu.py: the smallest pair vr_terrain_create accepts, then odd sizes
+# whose every level is ragged, sizes of which one side reaches one texel levels before the other, and 33 x 17.  Map k is the
+# heightmap of case k and the albedo of case k - 1.  With CREATE_SEED no colour component of any level of any of them is
+# flagged (tests/test_frontend_cpu.py), so their chains are the model's byte for byte.
+CREATE_SHAPES = [(1, 1), (5, 5), (7, 2), (2, 7), (33, 17)]
+CREATE_SEED = 100
+CREATE_WORLD = 64
+
+
+def check_chain(tp, name, rows, flag_cap=MIP_FLAG_CAP):
+    """Every level of both chains of a device terrain against the model applied to the device's own previous level."""
+    for which, srgb in (("height", False), ("albedo", True)):
+        levels = tp.mip_levels(which)
+        prev = tp.download_mip(which, 0)
+        assert levels == fe.num_mip_levels(prev.shape[1], prev.shape[0]), (name, which, levels)
+        flagged = 0.0
+        for l in range(1, levels):
+            got = tp.download_mip(which, l)
+            r = fe.check_mip(prev, got, srgb)
+            assert r["bad"] == 0, f"{name}: {which} level {l} ({got.shape[1]}x{got.shape[0]}): {r['bad']} components differ from the model"
+            assert r["flagged"] <= flag_cap, (name, which, l, r["flagged"])
+            flagged = max(flagged, r["flagged"])
+            prev = got
+        rows.append((f"{name} {which}", f"{levels} levels equal; largest flagged share {flagged:.5f}"))
 
 
 def ragged_heightmap():

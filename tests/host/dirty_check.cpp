@@ -1,8 +1,9 @@
-// CPU check of vr_dirty.h, the dirty-rectangle rules of vr_terrain_edit.  No HIP: g++ -std=c++17 -I vrenderer_amd/csrc.
+// CPU check of vr_dirty.h, the rectangle rules of vr_derive.hip (vr_terrain_edit, and vr_terrain_create as the edit of the whole
+// map).  No HIP: g++ -std=c++17 -I vrenderer_amd/csrc.
 //
 // The program restates, on the CPU, what the library derives from a map - the mip chain, the three table shapes (quad / quadf,
 // fast R8, fast SRGBA8; rgbf is indexed like the chain), the dyadic min / max tree of the node heights (one surface and 2 x 2
-// surfaces, leaf nodes of one and of two texels) and the query pyramid with k_query_pyramid_leaf's level-1 reach - and for every
+// surfaces, leaf nodes of one and of two texels) and the query pyramid with vr_pyramid_leaf_cell's level-1 reach - and for every
 // rectangle of every map size w, h in 1..9 (a seeded sample of 2000 rectangles for 16 x 16, 17 x 5 and 32 x 32) changes the
 // texels inside, rebuilds everything IN FULL and compares with the state before:
 //
@@ -28,6 +29,9 @@
 //     span at most ceil(s / 2) wide of it, and one stray child can still name one stray parent.
 // Hence area(predicted) <= (a + K)(b + K) = area(changed) + K (a + b) + K^2 for a changed a x b block: factor 1 on the area
 // plus a border term, nowhere near "dirty = everything".
+//
+// Creating a terrain rests on the opposite end: the rectangle {0, 0, w, h} dirties ALL of every structure, at every level
+// (check_whole_map: every w, h in 1..20 and 31, 32, 33, 64, 67, the same surfaces and leaf sizes), as equalities.
 #include "vr_dirty.h"
 
 #include <math.h>
@@ -60,7 +64,7 @@ static Built build(const Grid& map, int w0, int h0, bool real, const std::vector
     int levels = 1; { int m = w0 > h0 ? w0 : h0; while (m > 1) { m >>= 1; levels++; } }
     B.levels = levels;
     B.chain.push_back(map); B.w.push_back(w0); B.h.push_back(h0);
-    for (int l = 1; l < levels; l++) {                    // k_mip_r8 / k_mip_srgba8: 2x, min(2x + 1, sw - 1)
+    for (int l = 1; l < levels; l++) {                    // vr_mip_*_texel: 2x, min(2x + 1, sw - 1)
         const int sw = B.w[l - 1], sh = B.h[l - 1], dw = sw > 1 ? sw >> 1 : 1, dh = sh > 1 ? sh >> 1 : 1;
         const Grid& src = B.chain[l - 1];
         Grid dst((size_t)dw * dh);
@@ -75,16 +79,16 @@ static Built build(const Grid& map, int w0, int h0, bool real, const std::vector
         const int w = B.w[l], h = B.h[l];
         const Grid& src = B.chain[l];
         Grid q((size_t)(w + 2) * (h + 2)), f((size_t)(w + 3) * (h + 3)), p((size_t)(w + 3) * (h + 3));
-        for (int tw = 2; tw <= 3; tw++)                    // k_build_quads / _f32 (tw = 2), k_build_fast_r8 (tw = 3)
+        for (int tw = 2; tw <= 3; tw++)                    // vr_quad_entry / vr_footprint_entry: quad, quadf (tw = 2), fast R8 (tw = 3)
             for (int iy = 0; iy < h + tw; iy++) for (int ix = 0; ix < w + tw; ix++) {
                 const int x0 = clampi(ix - 1, 0, w - 1), x1 = clampi(ix, 0, w - 1), y0 = clampi(iy - 1, 0, h - 1), y1 = clampi(iy, 0, h - 1);
                 (tw == 2 ? q : f)[(size_t)iy * (w + tw) + ix] = fold(real, src[y0 * w + x0], src[y0 * w + x1], src[y1 * w + x0], src[y1 * w + x1]);
             }
-        for (int iy = 0; iy < h + 3; iy++) for (int ix = 0; ix < w + 3; ix++)          // k_build_fast_srgba8
+        for (int iy = 0; iy < h + 3; iy++) for (int ix = 0; ix < w + 3; ix++)          // vr_fast_srgba8_entry
             p[(size_t)iy * (w + 3) + ix] = src[clampi(iy - 1, 0, h - 1) * w + clampi(ix - 1, 0, w - 1)];
         B.quad.push_back(q); B.fast_r8.push_back(f); B.fast_px.push_back(p);
     }
-    for (const NodeCfg& c : cfgs) {                        // k_minmax_leaf / k_minmax_up
+    for (const NodeCfg& c : cfgs) {                        // vr_minmax_leaf_node / vr_minmax_up_node
         std::vector<std::vector<Grid>> per_surface;
         for (int surf = 0; surf < c.per_side * c.per_side; surf++) {
             const int rx0 = (surf % c.per_side) * c.S, ry0 = (surf / c.per_side) * c.S;
@@ -112,7 +116,7 @@ static Built build(const Grid& map, int w0, int h0, bool real, const std::vector
         }
         B.nodes.push_back(per_surface);
     }
-    {   // k_query_pyramid_leaf / _up
+    {   // vr_pyramid_leaf_cell / vr_pyramid_up_cell
         const int l1 = std::min(1, levels - 1), w1 = B.w[l1], h1 = B.h[l1], cw = w0 + 1, ch = h0 + 1;
         const Grid& lv1 = B.chain[l1];
         Grid leaf((size_t)cw * ch);
@@ -182,7 +186,7 @@ static void run_rect(const Grid& base_real, int w0, int h0, const DirtyRect& e, 
         const Built after = build(map, w0, h0, real, cfgs);
         const Built& b4 = before[mode];
         const int K0 = real ? -1 : 0;
-        // the chain and the tables, exactly as vr_edit.hip walks them
+        // the chain and the tables, exactly as vr_derive_chain walks them
         std::vector<DirtyRect> chain(after.levels);
         chain[0] = e;
         for (int l = 1; l < after.levels; l++)
@@ -201,7 +205,7 @@ static void run_rect(const Grid& base_real, int w0, int h0, const DirtyRect& e, 
                 const int rx0 = (surf % cfgs[c].per_side) * cfgs[c].S, ry0 = (surf / cfgs[c].per_side) * cfgs[c].S;
                 DirtySpan x = dirty_leaf_nodes(dirty_x(e), rx0, cfgs[c].s, 1 << cfgs[c].L), y = dirty_leaf_nodes(dirty_y(e), ry0, cfgs[c].s, 1 << cfgs[c].L);
                 for (int d = cfgs[c].L; d >= 0; d--) {
-                    // (vr_edit.hip stops at the first empty level: the levels above must then be unchanged - an empty prediction says so)
+                    // (vr_derive_node_heights stops at the first empty level: the levels above must then be unchanged - an empty prediction says so)
                     compare(b4.nodes[c][surf][d], after.nodes[c][surf][d], 1 << d, dirty_rect(x, y), K0, "nodes", d, w0, h0, e);
                     x = dirty_node_parents(x); y = dirty_node_parents(y);
                     if (dirty_empty(x) || dirty_empty(y)) { x = DirtySpan(); y = DirtySpan(); }
@@ -223,10 +227,11 @@ static void run_rect(const Grid& base_real, int w0, int h0, const DirtyRect& e, 
 static uint32_t g_rng = 0x2545F491u;
 static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 17; g_rng ^= g_rng << 5; return g_rng; }
 
-static void run_size(int w0, int h0, int sample)
+// the surfaces the mip-style path of the node heights applies to: power-of-two surfaces inside the map, leaf nodes of one and of two texels
+static std::vector<NodeCfg> node_configs(int w0, int h0)
 {
     std::vector<NodeCfg> cfgs;
-    if (w0 == h0 && (w0 & (w0 - 1)) == 0) {                // the mip-style path needs power-of-two surfaces inside the map
+    if (w0 == h0 && (w0 & (w0 - 1)) == 0) {
         for (int per_side = 1; per_side <= 2; per_side++) {
             const int S = w0 / per_side;
             if (S < 1) continue;
@@ -234,6 +239,12 @@ static void run_size(int w0, int h0, int sample)
             for (int s = 1; s <= 2 && s <= S; s++) { NodeCfg c; c.per_side = per_side; c.S = S; c.s = s; c.L = lg - (s - 1); cfgs.push_back(c); }
         }
     }
+    return cfgs;
+}
+
+static void run_size(int w0, int h0, int sample)
+{
+    const std::vector<NodeCfg> cfgs = node_configs(w0, h0);
     Grid base((size_t)w0 * h0);
     for (uint32_t& v : base) v = rnd() & 255u;
     const Built before[2] = { build(base, w0, h0, true, cfgs), build(Grid((size_t)w0 * h0, 0u), w0, h0, false, cfgs) };
@@ -253,13 +264,66 @@ static void run_size(int w0, int h0, int sample)
     }
 }
 
+static long g_whole = 0;
+static void expect_whole(const DirtyRect& r, int w, int h, const char* what, int level, int w0, int h0)
+{
+    g_checks++;
+    if (r.x0 == 0 && r.y0 == 0 && r.x1 == w && r.y1 == h) return;
+    if (g_failures++ < 20) printf("FAIL whole map %d x %d: %s level %d is [%d,%d)x[%d,%d), not all %d x %d\n", w0, h0, what, level, r.x0, r.x1, r.y0, r.y1, w, h);
+}
+// vr_terrain_create: the rectangle {0, 0, w0, h0} is all of every structure, walked as vr_derive.hip walks them
+static void check_whole_map(int w0, int h0)
+{
+    g_whole++;
+    int levels = 1; { int m = w0 > h0 ? w0 : h0; while (m > 1) { m >>= 1; levels++; } }
+    const DirtyRect whole = dirty_whole(w0, h0);
+    DirtyRect chain = whole, chain1 = whole;
+    for (int l = 0; l < levels; l++) {
+        const int w = dirty_level_size(w0, l), h = dirty_level_size(h0, l);
+        if (l) chain = dirty_rect(dirty_mip_next(dirty_x(chain), w), dirty_mip_next(dirty_y(chain), h));
+        if (l == 1) chain1 = chain;
+        const DirtySpan cx = dirty_x(chain), cy = dirty_y(chain);
+        expect_whole(chain, w, h, "chain (rgbf, SRGBA8 inner)", l, w0, h0);
+        expect_whole(dirty_rect(dirty_quad_entries(cx, w), dirty_quad_entries(cy, h)), w + 2, h + 2, "quad (R8 inner)", l, w0, h0);
+        expect_whole(dirty_rect(dirty_fast_r8_entries(cx, w), dirty_fast_r8_entries(cy, h)), w + 3, h + 3, "fast R8 entries", l, w0, h0);
+        expect_whole(dirty_rect(dirty_fast_srgba8_entries(cx, w), dirty_fast_srgba8_entries(cy, h)), w + 3, h + 3, "fast SRGBA8 entries", l, w0, h0);
+    }
+    for (const NodeCfg& c : node_configs(w0, h0))
+        for (int surf = 0; surf < c.per_side * c.per_side; surf++) {
+            const int rx0 = (surf % c.per_side) * c.S, ry0 = (surf / c.per_side) * c.S;
+            DirtySpan x = dirty_leaf_nodes(dirty_x(whole), rx0, c.s, 1 << c.L), y = dirty_leaf_nodes(dirty_y(whole), ry0, c.s, 1 << c.L);
+            for (int d = c.L; d >= 0; d--) {
+                expect_whole(dirty_rect(x, y), 1 << d, 1 << d, "nodes", d, w0, h0);
+                x = dirty_node_parents(x); y = dirty_node_parents(y);
+            }
+        }
+    {
+        const int l1 = levels > 1 ? 1 : 0;
+        const DirtyRect leaf = dirty_pyramid_leaf_cells(whole, chain1, w0, h0, dirty_level_size(w0, l1), dirty_level_size(h0, l1));
+        DirtySpan x = dirty_x(leaf), y = dirty_y(leaf);
+        int cw = w0 + 1, ch = h0 + 1;
+        for (int l = 0;; l++) {
+            expect_whole(dirty_rect(x, y), cw, ch, "pyramid", l, w0, h0);
+            if (cw == 1 && ch == 1) break;
+            cw = (cw + 1) / 2; ch = (ch + 1) / 2;
+            x = dirty_pyramid_parents(x, cw); y = dirty_pyramid_parents(y, ch);
+        }
+    }
+}
+
 int main()
 {
     for (int h = 1; h <= 9; h++) for (int w = 1; w <= 9; w++) run_size(w, h, 0);
     run_size(16, 16, 2000); run_size(17, 5, 2000); run_size(32, 32, 2000);
+    {
+        std::vector<int> sizes;
+        for (int n = 1; n <= 20; n++) sizes.push_back(n);
+        for (int n : { 31, 32, 33, 64, 67 }) sizes.push_back(n);
+        for (int h : sizes) for (int w : sizes) check_whole_map(w, h);
+    }
     // the span helpers on their own
     { DirtySpan s; s.lo = 4; s.hi = 5; if (!dirty_empty(dirty_mip_next(s, 2))) { g_failures++; printf("FAIL the last column of an odd level feeds nothing\n"); } }
     if (dirty_floor_div(-1, 2) != -1 || dirty_ceil_div(-1, 2) != 0 || dirty_floor_div(5, 2) != 2 || dirty_ceil_div(5, 2) != 3) { g_failures++; printf("FAIL floor / ceil division\n"); }
-    printf("%ld rectangles, %ld comparisons, %ld failures\n", g_cases, g_checks, g_failures);
+    printf("%ld rectangles, %ld whole maps, %ld comparisons, %ld failures\n", g_cases, g_whole, g_checks, g_failures);
     return g_failures ? 1 : 0;
 }

@@ -56,6 +56,25 @@ def test_mip_chains_of_the_oracle_follow_the_box_filter(oracle, worlds):
     fc.report("mip chains, oracle vs model", rows)
 
 
+def test_create_shapes_leave_nothing_open_to_the_model(oracle):
+    """What tests/test_terrain_create_gpu.py relies on: no colour component of any level of its maps is flagged, so "equal to
+    the model" is byte for byte there (and the oracle's chains are); on the 64 world their texel sizes w / 64 are dyadic, every
+    footprint bound is an exact fp32 product and no node is flagged either."""
+    maps = [fc.random_texture(w, h, fc.CREATE_SEED) for w, h in fc.CREATE_SHAPES]
+    for k, (hm, _) in enumerate(maps):
+        al = maps[(k + 1) % len(maps)][1]
+        ot = oracle.OracleTerrain(params(fc.CREATE_WORLD), hm, al)
+        try:
+            for l in range(1, ot.height_levels()):
+                assert fe.check_mip(ot.height_mip(l - 1), ot.height_mip(l), srgb=False)["bad"] == 0, (hm.shape, l)
+            for l in range(1, ot.albedo_levels()):
+                r = fe.check_mip(ot.albedo_mip(l - 1), ot.albedo_mip(l), srgb=True)
+                assert r["bad"] == 0 and r["flagged"] == 0.0, (al.shape, l, r)
+        finally:
+            ot.close()
+        assert not fe.set_height(fe.Tree(fc.CREATE_WORLD, fc.CREATE_WORLD), hm).flagged.any(), hm.shape
+
+
 def test_mip_model_known_answers():
     """The model itself: round-half-up, the clamp at odd sizes, a strip, and sRGB averaging in linear light."""
     assert fe.mip_r8(np.array([[1, 2, 9], [2, 1, 9], [7, 7, 3]], np.uint8)).tolist() == [[2]]                 # 6 / 4 = 1.5 -> 2; 3 x 3 -> 1 x 1

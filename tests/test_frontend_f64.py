@@ -1,4 +1,4 @@
-"""The HIP front end - k_mip_r8 / k_mip_srgba8, k_node_heights_* / k_minmax_*, k_select, k_vertex - against the model of
+"""The HIP front end - k_derive_mip_*, k_node_heights_* / k_derive_minmax_*, k_select, k_vertex - against the model of
 tests/f64_frontend.py directly, not through the oracle.  tests/test_frontend_cpu.py checks the conditions this file relies
 on (flagged shares, unambiguous views, real ties, vertex classes).  Every test prints its worst |error| / bound (-rA)."""
 import numpy as np
@@ -38,23 +38,6 @@ def _heights(sc):
     return sc["heights"]
 
 
-def _check_chain(tp, name, rows):
-    """Every level against the model applied to the device's own previous level."""
-    for which, srgb in (("height", False), ("albedo", True)):
-        levels = tp.mip_levels(which)
-        prev = tp.download_mip(which, 0)
-        assert levels == fe.num_mip_levels(prev.shape[1], prev.shape[0]), (name, which, levels)
-        flagged = 0.0
-        for l in range(1, levels):
-            got = tp.download_mip(which, l)
-            r = fe.check_mip(prev, got, srgb)
-            assert r["bad"] == 0, f"{name}: {which} level {l} ({got.shape[1]}x{got.shape[0]}): {r['bad']} components differ from the model"
-            assert r["flagged"] <= fc.MIP_FLAG_CAP, (name, which, l, r["flagged"])
-            flagged = max(flagged, r["flagged"])
-            prev = got
-        rows.append((f"{name} {which}", f"{levels} levels equal; largest flagged share {flagged:.5f}"))
-
-
 def test_mip_chains_follow_the_box_filter(gpu_ctx, worlds):
     """The synthetic 256^2 pair, random bytes with random alpha at 129 x 129 and 67 x 41 (odd sizes: clamped last row and
     column, sides that reach one texel before the other), the strips 64 x 1 and 1 x 37, and 256 x 64 - all sizes
@@ -62,13 +45,13 @@ def test_mip_chains_follow_the_box_filter(gpu_ctx, worlds):
     rows = []
     sc = worlds(256)
     assert np.array_equal(sc["tp"].download_mip("height", 0), sc["h"]) and np.array_equal(sc["tp"].download_mip("albedo", 0), sc["a"])
-    _check_chain(sc["tp"], "synthetic 256", rows)
+    fc.check_chain(sc["tp"], "synthetic 256", rows)
     for name, w, h, seed in fc.MIP_TEXTURES:
         hm, al = fc.random_texture(w, h, seed)
         tp = vr.TerrainPass(gpu_ctx, params(256)).Init(hm, al)
         try:
             assert np.array_equal(tp.download_mip("albedo", 0), al)
-            _check_chain(tp, name, rows)
+            fc.check_chain(tp, name, rows)
         finally:
             tp.close()
     fc.report("mip chains, device vs model", rows)
@@ -77,7 +60,7 @@ def test_mip_chains_follow_the_box_filter(gpu_ctx, worlds):
 @pytest.mark.parametrize("name", ["256", "two surfaces", "ragged 200x200 on 256", "420x300 on 200", "2048"])
 def test_set_height_is_the_exact_min_max(name, gpu_ctx, worlds):
     """All nodes through node_heights(0, num_nodes).  The 256, two-surface and 2048 worlds sample one texel per world unit and take
-    the k_minmax_leaf / k_minmax_up pyramid (2048: twelve levels of it); the ragged maps take the per-node scan:
+    the k_derive_minmax_leaf / k_derive_minmax_up pyramid (2048: twelve levels of it); the ragged maps take the per-node scan:
     k_node_heights_block while a node covers 512 texels or more (depths 0-3 of the 200 x 200 map), k_node_heights_thread
     below.  No node of the dyadic worlds is flagged, at most 1 % of the ragged one; the 420 x 300 map on the 200 world
     exercises the flagged branch (tests/test_frontend_cpu.py says why up to 10 %)."""

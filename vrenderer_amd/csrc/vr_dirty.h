@@ -1,7 +1,9 @@
-// What an in-place edit of a w x h sub-rectangle of level 0 has to rebuild (vr_terrain_edit, vr_edit.hip).  Plain C++17: no HIP,
-// no library types - a CPU program changes every rectangle of small maps, rebuilds everything in full and checks that
-// whatever changed lies inside what this header predicts, and that the prediction stays close to it (tests/host/dirty_check.cpp).
-// vr_edit.hip takes every rectangle from here and computes none itself.
+// What has to be (re)built of everything derived from a map once a rectangle of its level 0 holds new texels (vr_derive.hip).
+// vr_terrain_edit passes the w x h sub-rectangle it replaced; creating a terrain passes the whole map, which dirties the whole of
+// every structure (the edge rules below; asserted by tests/host/dirty_check.cpp), so there is one path and no rule of its own for
+// "everything".  Plain C++17: no HIP, no library types - a CPU program changes every rectangle of small maps, rebuilds everything
+// in full and checks that whatever changed lies inside what this header predicts, and that the prediction stays close to it
+// (tests/host/dirty_check.cpp).  vr_derive.hip takes every rectangle from here and computes none itself.
 //
 // A DirtyRect is half open, [x0, x1) x [y0, y1), in the index space of the array it names; empty once a side is.  The two axes
 // never mix, so every rule is a rule on one axis (DirtySpan), applied twice.  Every structure is a pure function of the chain, and
@@ -20,7 +22,7 @@
 //   leaf nodes     node ix of a surface's finest level covers the texels [rx0 + ix s, rx0 + (ix + 1) s); n = 2^num_lods of them
 //                  per side.  Parents: node ix of a level has the children 2 ix and 2 ix + 1.
 //   pyramid cells  leaf cell ix (w0 + 1 of them) reads the level-0 quad entry ix and the level-1 texels jx0(ix) .. jx1(ix) of
-//                  k_query_pyramid_leaf: floor((ix - 0.5) r - 0.5 - m) .. floor((ix + 0.5) r - 0.5 + m) + 1, clamped, r = w1 / w0,
+//                  vr_pyramid_leaf_cell: floor((ix - 0.5) r - 0.5 - m) .. floor((ix + 0.5) r - 0.5 + m) + 1, clamped, r = w1 / w0,
 //                  m = 1 / 64.  Texel j is therefore read by cells with (j - 0.5 - m) / r - 0.5 <= ix < (j + 1.5 + m) / r + 0.5;
 //                  in integers, with m < 1 / 2 and room for the kernel's fp32 rounding of r (relative 2^-23, ix <= 2^14):
 //                  floor((j - 1) w0 / w1) - 1 <= ix <= ceil((j + 2) w0 / w1) + 1.  The clamps again extend a span that touches
@@ -38,6 +40,7 @@ inline bool dirty_empty(const DirtyRect& r) { return r.x1 <= r.x0 || r.y1 <= r.y
 inline DirtyRect dirty_rect(DirtySpan x, DirtySpan y) { DirtyRect r; r.x0 = x.lo; r.x1 = x.hi; r.y0 = y.lo; r.y1 = y.hi; return r; }
 inline DirtySpan dirty_x(const DirtyRect& r) { DirtySpan s; s.lo = r.x0; s.hi = r.x1; return s; }
 inline DirtySpan dirty_y(const DirtyRect& r) { DirtySpan s; s.lo = r.y0; s.hi = r.y1; return s; }
+inline DirtyRect dirty_whole(int w, int h) { DirtyRect r; r.x1 = w; r.y1 = h; return r; }      // all of a w x h level
 inline DirtySpan dirty_clip(DirtySpan s, int n)
 {
     if (s.lo < 0) s.lo = 0;

@@ -117,11 +117,13 @@ struct DevTex {
     uint32_t fast_bytes, pad2;
 };
 
-// Where the levels of a DevTex begin, on the host (the device reads the same figures from DevTex::off / qoff / fast_lv).
+// Where the levels and the tables of a DevTex begin, on the host (the device reads the same figures from DevTex::off / qoff /
+// fast_lv): enough to derive everything from the texture's one allocation before there is a DevTex (vr_derive_chain).
 struct TexLayout {
     uint32_t off[kMaxLevels];          // bytes into the chain
     uint32_t qoff[kMaxLevels];         // entries into quad / quadf (R8 only)
     uint32_t fast_entry[kMaxLevels];   // entries into fast
+    size_t quad_at, quadf_at, rgbf_at, fast_at;     // bytes from the chain's first to each table (0: the texture has none)
 };
 
 // Per-light constants the deferred kernel reads (host precomputes the half-angle terms).
@@ -385,6 +387,16 @@ PyrDesc vr_pyramid_desc(const vr_terrain* t, size_t* cells);     // (cells: all 
 struct NodeSurface { float loc[3]; bool dyadic; int rx0, ry0, leaf; };
 NodeSurface vr_node_surface(const vr_terrain* t, int surf);
 int vr_node_heights_surface(vr_terrain* t, int surf, const NodeSurface& ns);     // the whole reduction of one surface, queued on the context's stream
+// Everything derived from a map, (re)built inside a rectangle of its level 0 (vr_derive.hip; rectangles: vr_dirty.h).  Creating a
+// terrain passes the whole map, vr_terrain_edit what it replaced.  The three queue launches and report nothing: hipGetLastError
+// afterwards.
+struct DirtyRect;
+// levels 1 .. of the chain at `mem` and the texture's tables (quad, quadf, fast of an R8 map; fast, rgbf of an SRGBA8 one), on the context's stream
+void vr_derive_chain(vr_context* ctx, uint8_t* mem, const TexLayout& lay, int w0, int h0, int levels, int texel_bytes, const DirtyRect& dirty);
+// the node heights of one surface on the mip-style path (ns.dyadic; d_node_heights and d_minmax exist), on the context's stream
+void vr_derive_node_heights(vr_terrain* t, int surf, const NodeSurface& ns, const DirtyRect& dirty);
+// the query pyramid at `pyramid`; l0, l1: the rectangle in levels 0 and 1 of the heightmap (a one-level chain: l1 = l0)
+void vr_derive_pyramid(const DevTex& hm, const PyrDesc& pd, uchar2* pyramid, const DirtyRect& l0, const DirtyRect& l1, hipStream_t s);
 
 struct vr_tonemap;
 vr_context* vr_tonemap_context(vr_tonemap* tm);

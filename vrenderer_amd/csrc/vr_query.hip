@@ -5,10 +5,10 @@
 //
 // k_query_heights   : one point per lane; H with exactly k_vertex's statements (vr_raster.hip, sampleHeight) through the
 //                     shared quad_tap / quad_filter of vr_tex_dev.h, so a height is bit for bit the drawn vertex's.
-// k_query_pyramid_* : a min / max pyramid over H / max_height.  Level 0 has one cell per level-0 bilinear footprint (texel-centre
-//                     interval, plus the clamp border: (w + 1) x (h + 1) cells, indexed like the quad table); a cell keeps a
-//                     uint8 pair (lo, hi) with lo / 255 <= H / max_height <= hi / 255 on the cell; each higher level is the
-//                     min / max of 2 x 2 children, ragged edges included.
+// the bound pyramid : a min / max pyramid over H / max_height, built by vr_derive.hip (vr_derive_pyramid).  Level 0 has one cell
+//                     per level-0 bilinear footprint (texel-centre interval, plus the clamp border: (w + 1) x (h + 1) cells,
+//                     indexed like the quad table); a cell keeps a uint8 pair (lo, hi) with lo / 255 <= H / max_height <= hi / 255
+//                     on the cell; each higher level is the min / max of 2 x 2 children, ragged edges included.
 // k_query_rays      : one ray per lane.  Slab clip to the box, then a hierarchical DDA over the pyramid from the coarsest
 //                     level: a cell whose bound lies below the ray's segment is stepped over, any other is entered one level
 //                     down; crossing a cell boundary that is also the parent's goes one level up again, so no stack is
@@ -18,7 +18,7 @@
 //                     root is refined against the sampler itself, and the reported point's height is the sampler's value.
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
-#include "vr_terrain_dev.h"
+#include "vr_dirty.h"
 #include "vr_experiments.h"
 
 #include <math.h>
@@ -109,25 +109,6 @@ __global__ __launch_bounds__(256) void k_query_heights(DevTex hm, QueryArgs a, c
             out_height[i] = s.hv * a.max_height;
         }
     }
-}
-
-// ---------------------------------------------------------------------------------------
-// bound pyramid
-// ---------------------------------------------------------------------------------------
-// One lane per cell; a cell's expressions are vr_terrain_dev.h's (vr_pyramid_leaf_cell, vr_pyramid_up_cell), shared with the
-// in-place edit (vr_edit.hip).
-__global__ __launch_bounds__(256) void k_query_pyramid_leaf(DevTex hm, int cw, int ch, uchar2* __restrict__ out)
-{
-    const int ix = blockIdx.x * 64 + (threadIdx.x & 63), iz = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (ix >= cw || iz >= ch) return;
-    vr_pyramid_leaf_cell(hm, cw, out, ix, iz);
-}
-
-__global__ __launch_bounds__(256) void k_query_pyramid_up(const uchar2* __restrict__ child, int cw, int ch, uchar2* __restrict__ parent, int pw, int ph)
-{
-    const int px = blockIdx.x * 64 + (threadIdx.x & 63), pz = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (px >= pw || pz >= ph) return;
-    vr_pyramid_up_cell(child, cw, ch, parent, pw, px, pz);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -398,13 +379,8 @@ static int ensure_pyramid(vr_terrain* t, PyrDesc* out)
     }
     {
         VrKernelScope ks(t->ctx, VR_K_QUERY_PYRAMID);
-        int w = out->cw, h = out->ch;
-        hipLaunchKernelGGL(k_query_pyramid_leaf, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, s, t->height, w, h, p);
-        for (int l = 1; l < out->levels; l++) {
-            const int pw = (w + 1) / 2, ph = (h + 1) / 2;
-            hipLaunchKernelGGL(k_query_pyramid_up, dim3((pw + 63) / 64, (ph + 3) / 4), dim3(256), 0, s, (const uchar2*)(p + out->off[l - 1]), w, h, p + out->off[l], pw, ph);
-            w = pw; h = ph;
-        }
+        const int w0 = t->height.w0, h0 = t->height.h0, lv1 = t->height.levels > 1 ? 1 : 0;
+        vr_derive_pyramid(t->height, *out, p, dirty_whole(w0, h0), dirty_whole(dirty_level_size(w0, lv1), dirty_level_size(h0, lv1)), s);
     }
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess || hipEventRecord(ev, s) != hipSuccess) {

@@ -13,6 +13,7 @@
 // (TerrainPass.cpp:234-256) is fused into the write-out.
 #include "vr_internal.h"
 #include "vr_terrain_dev.h"
+#include "vr_dirty.h"
 #include "vr_experiments.h"
 
 #include <math.h>
@@ -352,20 +353,8 @@ __global__ __launch_bounds__(256) void k_node_heights_thread(HeightArgs a, const
 // Mip-style path (the usual case: a power-of-two surface sampled one texel per world unit): every node's texel
 // rectangle is then an exact dyadic square and the four children tile their parent, so the raw (min, max) bytes of a
 // level follow from the level below; the reference's "max == min => min = 0" quirk and the float conversion are
-// applied per node on the way out (finish_minmax), which keeps the result identical to the per-node scan.
-__global__ __launch_bounds__(256) void k_minmax_leaf(const uint8_t* __restrict__ tex, int tex_w, int rx0, int ry0, uint32_t n, int s,
-                                                      uchar2* __restrict__ mm, float2* __restrict__ out)
-{
-    const uint64_t total = (uint64_t)n * n;
-    for (uint64_t node = (uint64_t)blockIdx.x * 256 + threadIdx.x; node < total; node += (uint64_t)gridDim.x * 256)
-        vr_minmax_leaf_node(tex, tex_w, rx0, ry0, n, s, mm, out, (uint32_t)(node % n), (uint32_t)(node / n));
-}
-__global__ __launch_bounds__(256) void k_minmax_up(const uchar2* __restrict__ child, uint32_t n, uchar2* __restrict__ mm, float2* __restrict__ out)
-{
-    const uint64_t total = (uint64_t)n * n;
-    for (uint64_t node = (uint64_t)blockIdx.x * 256 + threadIdx.x; node < total; node += (uint64_t)gridDim.x * 256)
-        vr_minmax_up_node(child, n, mm, out, (uint32_t)(node % n), (uint32_t)(node / n));
-}
+// applied per node on the way out (vr_finish_minmax), which keeps the result identical to the per-node scan.  Its
+// kernels are vr_derive.hip's (vr_derive_node_heights).
 
 // texel origin of a surface's root if the mip-style path applies to it, else false
 static bool dyadic_root(const vr_terrain* t, const float loc[3], int* rx0, int* ry0, int* leaf_texels)
@@ -403,21 +392,7 @@ int vr_node_heights_surface(vr_terrain* t, int surf, const NodeSurface& ns)
 {
     const uint64_t nodes = nodes_per_surface(t);
     float2* out = t->d_node_heights + (size_t)surf * nodes;
-    if (ns.dyadic) {
-        uchar2* mm = t->d_minmax + (size_t)surf * nodes;
-        for (int d = t->num_lods; d >= 0; d--) {
-            const uint32_t n = 1u << d;
-            const uint64_t base = ((((uint64_t)1 << (2 * d)) - 1) / 3), cells = (uint64_t)n * n, blocks = (cells + 255) / 256;
-            const unsigned grid = (unsigned)(blocks > 16384 ? 16384 : blocks);
-            if (d == t->num_lods)
-                hipLaunchKernelGGL(k_minmax_leaf, dim3(grid), dim3(256), 0, t->ctx->stream, (const uint8_t*)t->d_height, t->height.w0, ns.rx0, ns.ry0, n, ns.leaf,
-                                   mm + base, out + base);
-            else
-                hipLaunchKernelGGL(k_minmax_up, dim3(grid), dim3(256), 0, t->ctx->stream,
-                                   (const uchar2*)(mm + ((((uint64_t)1 << (2 * (d + 1))) - 1) / 3)), n, mm + base, out + base);
-        }
-        return VR_OK;
-    }
+    if (ns.dyadic) { vr_derive_node_heights(t, surf, ns, dirty_whole(t->height.w0, t->height.h0)); return VR_OK; }
     HeightArgs a;
     a.half_w = t->p.surface_size / 2.0f; a.half_h = t->p.surface_size / 2.0f; a.world_size = t->p.world_size;
     a.texel_x = t->texel_size[0]; a.texel_y = t->texel_size[1]; a.tex_w = t->height.w0; a.tex_h = t->height.h0;

@@ -1,7 +1,7 @@
 // Everything the library derives from a terrain's two maps, one element at a time: a texel of the next mip level, an entry
-// of each decoded table, a node's (min, max), a cell of the query pyramid.  The kernels that build a terrain (vr_tex.hip,
-// vr_select.hip, vr_query.hip) call these for every element of a level; the kernels of an in-place edit (vr_edit.hip) call
-// them for the elements of a dirty rectangle.  There is no second copy of any of these expressions.
+// of each decoded table, a node's (min, max), a cell of the query pyramid.  The kernels of vr_derive.hip call these for the
+// elements of a rectangle - the whole map when a terrain is created, the dirty rectangle of an in-place edit - and no other
+// kernel does.  There is no second copy of any of these expressions, nor of the kernels around them.
 #pragma once
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
@@ -66,7 +66,7 @@ __device__ __forceinline__ void vr_rgbf_texel(const uint32_t* __restrict__ src, 
     reinterpret_cast<float4*>(dst)[i] = make_float4(lut[p & 255u], lut[(p >> 8) & 255u], lut[(p >> 16) & 255u], 0.0f);
 }
 
-// ---- node heights, mip-style path (vr_select.hip) -----------------------------------------------------
+// ---- node heights, mip-style path -----------------------------------------------------------------------
 __device__ __forceinline__ float2 vr_finish_minmax(int mnb, int mxb)
 {
     float mn = mnb <= 255 ? (float)mnb / 255.0f : INFINITY, mx = mxb >= 0 ? (float)mxb / 255.0f : -INFINITY;
@@ -97,7 +97,7 @@ __device__ __forceinline__ void vr_minmax_up_node(const uchar2* __restrict__ chi
     out[node] = vr_finish_minmax(mn, mx);
 }
 
-// ---- query pyramid (vr_query.hip) -----------------------------------------------------------------------
+// ---- query pyramid ---------------------------------------------------------------------------------------
 // Level 0.  Cell (ix, iz) is the quad table's entry (ix, iz): texel-centre coordinates X0 in [ix - 1, ix].  Its level-0 part is
 // bounded by the entry's four texels (a bilinear interpolant lies between its corners); its level-1 part by every level-1 texel
 // a bilinear tap at a point of the cell can touch: X1 = (X0 + 0.5) w1 / w0 - 0.5 over the cell, floor(X1) .. floor(X1) + 1,

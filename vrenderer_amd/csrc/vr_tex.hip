@@ -1,64 +1,13 @@
-// Texture upload + mip-chain generation on the device, and the synthetic input
-// generators (the reference's media/ directory is git-ignored: .gitignore:36,52).
+// Texture upload - the layout of a texture's one allocation, level 0 and the offset tables; the mip chain and the decoded
+// tables are vr_derive.hip's - and the synthetic input generators (the reference's media/ directory is git-ignored:
+// .gitignore:36,52).
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
-#include "vr_terrain_dev.h"
+#include "vr_dirty.h"
 
 #include <string.h>
 
-// One lane per element of a level; the expressions are vr_terrain_dev.h's (shared with the in-place edit, vr_edit.hip).
-__global__ void k_mip_r8(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh)
-{
-    int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= dw || y >= dh) return;
-    vr_mip_r8_texel(src, sw, sh, dst, dw, x, y);
-}
-
-__global__ void k_mip_srgba8(const uint32_t* __restrict__ src, int sw, int sh, uint32_t* __restrict__ dst, int dw, int dh,
-                             const float* __restrict__ lut_g, const float* __restrict__ thr_g)
-{
-    __shared__ float lut[256];
-    __shared__ float thr[256];
-    int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    for (int i = tid; i < 256; i += blockDim.x * blockDim.y) { lut[i] = lut_g[i]; thr[i] = thr_g[i]; }
-    __syncthreads();
-    int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= dw || y >= dh) return;
-    vr_mip_srgba8_texel(src, sw, sh, dst, dw, x, y, lut, thr);
-}
-
-__global__ void k_build_quads(const uint8_t* __restrict__ src, int w, int h, uint32_t* __restrict__ dst)
-{
-    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
-    if (ix >= w + 2 || iy >= h + 2) return;
-    vr_quad_entry(src, w, h, dst, ix, iy);
-}
-
-__global__ void k_build_quads_f32(const uint8_t* __restrict__ src, int w, int h, float4* __restrict__ dst)
-{
-    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
-    if (ix >= w + 2 || iy >= h + 2) return;
-    vr_footprint_entry(src, w, h, dst, w + 2, ix, iy);
-}
-
-// Tables of the tile pass's fast variant (DevTex::fast): (w+3) x (h+3) clamp-addressed entries per level.
-__global__ void k_build_fast_r8(const uint8_t* __restrict__ src, int w, int h, float4* __restrict__ dst)
-{
-    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
-    if (ix >= w + 3 || iy >= h + 3) return;
-    vr_footprint_entry(src, w, h, dst, w + 3, ix, iy);
-}
-__global__ void k_build_fast_srgba8(const uint32_t* __restrict__ src, int w, int h, const float* __restrict__ lut, float4* __restrict__ dst)
-{
-    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y;
-    if (ix >= w + 3 || iy >= h + 3) return;
-    vr_fast_srgba8_entry(src, w, h, lut, dst, ix, iy);
-}
-
-__global__ void k_decode_rgbf(const uint32_t* __restrict__ src, size_t n, const float* __restrict__ lut, float* __restrict__ dst)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) vr_rgbf_texel(src, i, lut, dst);
-}
+static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 
 int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, int tb, DevTex* out, uint8_t** out_mem, uint64_t* out_bytes, TexLayout* layout)
 {
@@ -68,53 +17,41 @@ int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, in
     VR_REQUIRE((size_t)w * (size_t)h <= ((size_t)1 << 26), "textures above 2^26 texels (8192 x 8192) are not supported (decoded tables are addressed with 32-bit offsets)");
     int levels = 1; { int m = w > h ? w : h; while (m > 1) { m >>= 1; levels++; } }
     VR_REQUIRE(levels <= kMaxLevels, "too many mip levels");
-    uint32_t off[kMaxLevels] = { 0 };
-    size_t total = 0;
+    TexLayout lay; memset(&lay, 0, sizeof(lay));
+    // the chain, the quad tables (bilinear footprints, R8 only) and the tables of the tile pass's fast variant ((w+3) x (h+3) entries
+    // of 16 B per level, levels 256-B aligned), level by level
+    uint32_t fast_lv[kMaxLevels][4];
+    memset(fast_lv, 0, sizeof(fast_lv));
+    size_t chain_bytes = 0, quad_dwords = 0, fast_bytes = 0;
     for (int l = 0; l < levels; l++) {
-        int lw = (w >> l) > 1 ? (w >> l) : 1, lh = (h >> l) > 1 ? (h >> l) : 1;
-        off[l] = (uint32_t)total;
-        total += ((size_t)lw * lh * tb + 255) / 256 * 256;
-    }
-    size_t table_off = total;
-    total += sizeof(uint32_t) * kMaxLevels;
-    // quad (bilinear footprint) tables for R8 textures
-    uint32_t qoff[kMaxLevels] = { 0 };
-    size_t qtable_off = 0, quad_off = 0, quad_dwords = 0, quadf_off = 0;
-    if (tb == 1) {
-        for (int l = 0; l < levels; l++) {
-            int lw = (w >> l) > 1 ? (w >> l) : 1, lh = (h >> l) > 1 ? (h >> l) : 1;
-            qoff[l] = (uint32_t)quad_dwords;
+        const int lw = dirty_level_size(w, l), lh = dirty_level_size(h, l);
+        lay.off[l] = (uint32_t)chain_bytes;
+        chain_bytes += align256((size_t)lw * lh * tb);
+        if (tb == 1) {
+            lay.qoff[l] = (uint32_t)quad_dwords;
             quad_dwords += ((size_t)(lw + 2) * (lh + 2) + 63) / 64 * 64;
         }
-        qtable_off = total; total += sizeof(uint32_t) * kMaxLevels;
-        total = (total + 255) / 256 * 256;
-        quad_off = total; total += quad_dwords * sizeof(uint32_t);
-        total = (total + 255) / 256 * 256;
-        quadf_off = total; total += quad_dwords * sizeof(float4);
-    }
-    size_t rgbf_off = 0;
-    if (tb == 4) { total = (total + 255) / 256 * 256; rgbf_off = total; total += table_off / 4 * 16; }   // decoded copy of the whole chain
-    // tables of the tile pass's fast variant: (w+3) x (h+3) entries of 16 B per level, levels 256-B aligned
-    uint32_t fast_lv[kMaxLevels][4];
-    size_t fast_entry[kMaxLevels];
-    memset(fast_lv, 0, sizeof(fast_lv));
-    total = (total + 255) / 256 * 256;
-    const size_t fastlv_off = total; total += sizeof(fast_lv);
-    total = (total + 255) / 256 * 256;
-    const size_t fast_off = total;
-    size_t fast_bytes = 0;
-    for (int l = 0; l < levels; l++) {
-        const int lw = (w >> l) > 1 ? (w >> l) : 1, lh = (h >> l) > 1 ? (h >> l) : 1;
-        fast_entry[l] = fast_bytes / 16;
+        lay.fast_entry[l] = (uint32_t)(fast_bytes / 16);
         const uint32_t row = (uint32_t)(lw + 3) * 16u;
         const float wf = (float)lw, hf = (float)lh;
         fast_lv[l][0] = (uint32_t)fast_bytes + row + 16u; fast_lv[l][1] = row;
         memcpy(&fast_lv[l][2], &wf, 4); memcpy(&fast_lv[l][3], &hf, 4);
-        fast_bytes += ((size_t)(lw + 3) * (lh + 3) * 16 + 255) / 256 * 256;
+        fast_bytes += align256((size_t)(lw + 3) * (lh + 3) * 16);
     }
-    total += fast_bytes;
+    // the allocation: chain, its offset table, then the tables
+    size_t total = chain_bytes;
+    const size_t table_off = total; total += sizeof(lay.off);
+    size_t qtable_off = 0;
+    if (tb == 1) {
+        qtable_off = total; total += sizeof(lay.qoff);
+        lay.quad_at = total = align256(total); total += quad_dwords * sizeof(uint32_t);
+        lay.quadf_at = total = align256(total); total += quad_dwords * sizeof(float4);
+    }
+    if (tb == 4) { lay.rgbf_at = total = align256(total); total += chain_bytes / 4 * 16; }   // a float4 per dword of the chain
+    const size_t fastlv_off = total = align256(total); total += sizeof(fast_lv);
+    lay.fast_at = total = align256(total); total += fast_bytes;
     // every table is read through its own buffer resource with 32-bit byte offsets: each must stay below 2 GB
-    VR_REQUIRE(quad_dwords * sizeof(float4) < ((size_t)1 << 31) && table_off * 4 < ((size_t)1 << 31) && fast_bytes < ((size_t)1 << 31),
+    VR_REQUIRE(quad_dwords * sizeof(float4) < ((size_t)1 << 31) && chain_bytes * 4 < ((size_t)1 << 31) && fast_bytes < ((size_t)1 << 31),
                "texture too large");
 
     uint8_t* mem = nullptr;
@@ -126,48 +63,21 @@ int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, in
         vr_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
         return e_ == hipErrorOutOfMemory ? VR_ERR_OUT_OF_MEMORY : VR_ERR_HIP; } } while (0)
     VR_TEX_TRY(hipMemcpyAsync(mem, host, (size_t)w * h * tb, hipMemcpyHostToDevice, s));
-    VR_TEX_TRY(hipMemcpyAsync(mem + table_off, off, sizeof(off), hipMemcpyHostToDevice, s));
-    int sw = w, sh = h;
-    for (int l = 1; l < levels; l++) {
-        int dw = sw > 1 ? sw >> 1 : 1, dh = sh > 1 ? sh >> 1 : 1;
-        dim3 blk(32, 8), grd((dw + 31) / 32, (dh + 7) / 8);
-        if (tb == 1) hipLaunchKernelGGL(k_mip_r8, grd, blk, 0, s, mem + off[l - 1], sw, sh, mem + off[l], dw, dh);
-        else hipLaunchKernelGGL(k_mip_srgba8, grd, blk, 0, s, (const uint32_t*)(mem + off[l - 1]), sw, sh,
-                                (uint32_t*)(mem + off[l]), dw, dh, ctx->d_srgb_lut, ctx->d_srgb_thr);
-        sw = dw; sh = dh;
-    }
-    out->quad = nullptr; out->qoff = nullptr; out->quadf = nullptr; out->rgbf = nullptr;
+    VR_TEX_TRY(hipMemcpyAsync(mem + table_off, lay.off, sizeof(lay.off), hipMemcpyHostToDevice, s));
     VR_TEX_TRY(hipMemcpyAsync(mem + fastlv_off, fast_lv, sizeof(fast_lv), hipMemcpyHostToDevice, s));
-    for (int l = 0; l < levels; l++) {
-        const int lw = (w >> l) > 1 ? (w >> l) : 1, lh = (h >> l) > 1 ? (h >> l) : 1;
-        dim3 blk(32, 8), grd((lw + 3 + 31) / 32, (lh + 3 + 7) / 8);
-        float4* dst = (float4*)(mem + fast_off) + fast_entry[l];
-        if (tb == 1) hipLaunchKernelGGL(k_build_fast_r8, grd, blk, 0, s, mem + off[l], lw, lh, dst);
-        else hipLaunchKernelGGL(k_build_fast_srgba8, grd, blk, 0, s, (const uint32_t*)(mem + off[l]), lw, lh, ctx->d_srgb_lut, dst);
-    }
-    out->fast = (const float4*)(mem + fast_off); out->fast_lv = (const uint4*)(mem + fastlv_off); out->fast_bytes = (uint32_t)fast_bytes; out->pad2 = 0;
-    if (tb == 4) {       // (padding texels between levels are decoded too; nothing reads them)
-        hipLaunchKernelGGL(k_decode_rgbf, dim3(4096), dim3(256), 0, s, (const uint32_t*)mem, table_off / 4, ctx->d_srgb_lut, (float*)(mem + rgbf_off));
-        out->rgbf = (const float*)(mem + rgbf_off);
-    }
-    if (tb == 1) {
-        VR_TEX_TRY(hipMemcpyAsync(mem + qtable_off, qoff, sizeof(qoff), hipMemcpyHostToDevice, s));
-        for (int l = 0; l < levels; l++) {
-            int lw = (w >> l) > 1 ? (w >> l) : 1, lh = (h >> l) > 1 ? (h >> l) : 1;
-            dim3 blk(32, 8), grd((lw + 2 + 31) / 32, (lh + 2 + 7) / 8);
-            hipLaunchKernelGGL(k_build_quads, grd, blk, 0, s, mem + off[l], lw, lh, (uint32_t*)(mem + quad_off) + qoff[l]);
-            hipLaunchKernelGGL(k_build_quads_f32, grd, blk, 0, s, mem + off[l], lw, lh, (float4*)(mem + quadf_off) + qoff[l]);
-        }
-        out->quadf = (const float4*)(mem + quadf_off);
-        out->quad = (const uint32_t*)(mem + quad_off); out->qoff = (const uint32_t*)(mem + qtable_off);
-    }
+    if (tb == 1) VR_TEX_TRY(hipMemcpyAsync(mem + qtable_off, lay.qoff, sizeof(lay.qoff), hipMemcpyHostToDevice, s));
+    vr_derive_chain(ctx, mem, lay, w, h, levels, tb, dirty_whole(w, h));       // everything else, from level 0
     VR_TEX_TRY(hipGetLastError());
     VR_TEX_TRY(hipStreamSynchronize(s));   // host source buffer is caller-owned: finish the copy before returning
 #undef VR_TEX_TRY
     out->base = mem; out->off = (const uint32_t*)(mem + table_off); out->levels = levels; out->w0 = w; out->h0 = h;
-    out->chain_bytes = (uint32_t)table_off; out->quad_bytes = (uint32_t)(quad_dwords * sizeof(uint32_t)); out->pad = 0;
+    out->chain_bytes = (uint32_t)chain_bytes; out->quad_bytes = (uint32_t)(quad_dwords * sizeof(uint32_t)); out->pad = 0;
+    out->quad = tb == 1 ? (const uint32_t*)(mem + lay.quad_at) : nullptr; out->qoff = tb == 1 ? (const uint32_t*)(mem + qtable_off) : nullptr;
+    out->quadf = tb == 1 ? (const float4*)(mem + lay.quadf_at) : nullptr;
+    out->rgbf = tb == 4 ? (const float*)(mem + lay.rgbf_at) : nullptr;
+    out->fast = (const float4*)(mem + lay.fast_at); out->fast_lv = (const uint4*)(mem + fastlv_off); out->fast_bytes = (uint32_t)fast_bytes; out->pad2 = 0;
     *out_mem = mem;
-    if (layout) for (int l = 0; l < kMaxLevels; l++) { layout->off[l] = off[l]; layout->qoff[l] = qoff[l]; layout->fast_entry[l] = l < levels ? (uint32_t)fast_entry[l] : 0u; }
+    if (layout) *layout = lay;
     return VR_OK;
 }
 
