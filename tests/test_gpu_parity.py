@@ -2852,3 +2852,55 @@ def test_depth_ranges_survive_a_refused_render(scene256, gpu_ctx, monkeypatch):
         monkeypatch.delenv("VR_ALLOC_FAIL_ABOVE", raising=False)
         gpu_ctx.set_plane_tracking(True)
         hdr.close(); rt0.close(); rt.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("part", [None, (0, 2)], ids=["whole-frame", "packed-rank0of2"])
+def test_depth_ranges_survive_a_refused_lighting_call(scene256, gpu_ctx, part):
+    """A tiled lighting call that is refused (its hdr_out is too small for the frame: VR_ERR_INVALID_ARGUMENT) leaves the depth
+    ranges of the tile pass in front of it VALID.  Sequence A: render v (assume_cleared, depth_ranges), the refused call, the same
+    call into a full-size image, render v2 (depth_ranges), tiled lighting.  Sequence B: the same without the refused call, on
+    fresh targets.  The 8x5 light tiles' lists are equal tile for tile and the two HdrColor images are bit-identical.
+    Before the lighting pass took its refusals first, the refused call had already marked the ranges consumed: the next call
+    re-read the depth plane and reset nothing, v2's tile pass merged its minima and maxima into v's, and the lists of A came out
+    longer than those of B (conservatively: a culled light contributes exactly zero - but the state no longer described memory)."""
+    from vrenderer_amd.passes import partition_info
+    tp = scene256["tp"]
+    w, h = 256, 144
+    v, v2 = (vr.make_view(*scaled_camera(CAMERAS[i], 256), w, h) for i in (0, 5))
+    rp = vr.default_render_params(400.0, assume_cleared=1, depth_ranges=1)
+    lights = _scene_lights(scene256, 64)
+    p = vr.Partition(*part) if part else None
+    info = partition_info(w, h, *(part or (0, 1)))
+    size = (128, info["max_owned"] * 128) if part else (w, h)
+    nbytes = info["packed_bytes"] if part else w * h * 8
+    tiled = vr.TiledDeferredLightingPass(gpu_ctx)
+
+    def sequence(with_refused_call):
+        rt = vr.RenderTargets(gpu_ctx).Init(w, h)
+        hdr, small = vr.HdrImage(gpu_ctx, *size), vr.HdrImage(gpu_ctx, 128, 64)
+        try:
+            hdr.upload(np.zeros(size[0] * size[1] * 4, np.uint16))     # (a packed tile's rows below the frame's edge are never written)
+            tp.Render(v, v, rt, rp, p)
+            if with_refused_call:
+                with pytest.raises(vr.VrError) as e:
+                    tiled.Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, small, p)
+                assert e.value.code == vr.capi.VR_ERR_INVALID_ARGUMENT and "hdr_out is smaller" in str(e.value), e.value
+            tiled.Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr, p)
+            tp.Render(v2, v2, rt, rp, p)
+            tiled.Render(v2, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr, p)
+            tiled.Status()
+            lists = {(x, y): tiled.tile_light_list(x, y).tolist() for y in range(5) for x in range(8)
+                     if part is None or (x // 4 + y // 4) % part[1] == part[0]}
+            return lists, hdr.download(nbytes).copy()
+        finally:
+            small.close(); hdr.close(); rt.close()
+
+    lists_a, hdr_a = sequence(True)
+    lists_b, hdr_b = sequence(False)
+    assert len(lists_a) == (20 if part else 40) and any(lists_b.values())
+    assert any(len(m) < len(lights) for m in lists_b.values()), "nothing was culled: the lists say nothing"
+    for t in lists_b:
+        assert lists_a[t] == lists_b[t], (t, lists_a[t], lists_b[t])
+    assert np.array_equal(hdr_a, hdr_b)
+    assert hdr_a.any()

@@ -12,6 +12,9 @@
 // output leaves as two 16-byte stores.  All seven loads are issued before any
 // arithmetic so a wave keeps 112 B/lane in flight.  The sRGB decode table lives in
 // LDS.  fp32 math; checked against the CPU oracle to per-channel RMS <= 1e-4.
+//
+// The host side (behind the kernels) decides nothing about kernels itself: vr_light_plan.h holds the variant rules as one pure function, checked
+// on the CPU, and each kernel family is launched from one place.  All five entry points go through vr_light_pass, which refuses first and acts afterwards.
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
 
@@ -24,11 +27,7 @@
 // Output of 4 pixels (o[2k] = r|g<<16, o[2k+1] = b, alpha 0).  Row-major frames are RGBA16F (8 B/px);
 // the packed tile buffer that goes through the all-gather drops the always-zero alpha: RGB16F, 6 B/px,
 // 25 % less xGMI traffic, restored by k_detile.
-// NT (row-major frames only): streaming stores, with streaming loads in the kernel.  An 8K frame's lighting pass moves 1.2 GB
-// through the caches and leaves 265 MB of dirty lines; the NEXT frame's tile pass then finds its texel tables evicted.
-// Measured (tools/exp_serial.py, profiles/r03_serial_cache_experiment.txt): tile pass 373-379 us behind a lighting pass with
-// plain loads and stores, 325-332 us behind one that streams both (= its time with no lighting pass in between); streaming
-// only the loads or only the stores changes nothing; the lighting pass itself goes from 199-205 to 207 us.
+// NT (row-major frames only): streaming stores, with streaming loads in the kernel (why, and what it measured: vr_light_plan.h).
 template <bool PACKED, bool NT = false>
 __device__ __forceinline__ void store_quad(uint2* __restrict__ out, size_t out_index, const uint32_t o[8])
 {
@@ -247,15 +246,21 @@ static int fill_light(const vr_light& l, DevLight& d, bool allow_extra)
     return VR_OK;
 }
 
-// The lighting kernels' constant block for a view and a light list (also the fused tile pass's: vr_terrain_render_lit).
-int vr_deferred_make_args(const vr_view* view, int w, int h, const vr_light* lights, int32_t num_lights, const float amb_top[3],
-                          const float amb_bottom[3], DeferredArgs* out, bool* extra_lights)
+// The lighting kernels' constant block: the view and the ambient terms (every pass; no light in it yet) ...
+static void deferred_view_args(const vr_view* view, int w, int h, const float amb_top[3], const float amb_bottom[3], DeferredArgs* out)
 {
     DeferredArgs& a = *out;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < 16; i++) a.c2w[i] = view->clip_to_world[i];
     for (int i = 0; i < 3; i++) { a.cam[i] = view->camera_pos[i]; a.amb_top[i] = amb_top[i]; a.amb_bot[i] = amb_bottom[i]; }
     a.w = w; a.h = h; a.sx = 2.0f / (float)w; a.sy = -2.0f / (float)h;
+}
+// ... and with a light list of up to kMaxLights in it: the streaming pass's and the fused tile pass's (vr_terrain_render_lit)
+int vr_deferred_make_args(const vr_view* view, int w, int h, const vr_light* lights, int32_t num_lights, const float amb_top[3],
+                          const float amb_bottom[3], DeferredArgs* out, bool* extra_lights)
+{
+    DeferredArgs& a = *out;
+    deferred_view_args(view, w, h, amb_top, amb_bottom, out);
     a.num_lights = num_lights;
     *extra_lights = false;
     for (int i = 0; i < num_lights; i++) {
@@ -264,122 +269,6 @@ int vr_deferred_make_args(const vr_view* view, int w, int h, const vr_light* lig
         if (a.lights[i].type != VR_LIGHT_DIRECTIONAL) a.exact_pos = 1;
     }
     return VR_OK;
-}
-
-// The shadow binding of a lighting pass (vr_deferred_light_shadowed, vr_deferred_light_tiled_ex): its conditions, the map made
-// real, the kernels' constants.  shadow == NULL: *sh is all zero.
-static int fill_shadow(vr_context* ctx, const vr_light* lights, int32_t num_lights, const vr_shadow_binding* shadow, ShadowArgs* out)
-{
-    ShadowArgs& sh = *out;
-    memset(&sh, 0, sizeof(sh));
-    if (shadow) {
-        VR_REQUIRE(shadow->light_view && shadow->shadow_map, "shadow binding has NULL members");
-        VR_REQUIRE(shadow->light_index >= 0 && shadow->light_index < num_lights, "shadow light_index out of range");
-        VR_REQUIRE(lights[shadow->light_index].type == VR_LIGHT_DIRECTIONAL, "only a directional light carries the cascaded shadow map");
-        VR_REQUIRE(shadow->shadow_map->w == shadow->shadow_map->h && shadow->shadow_map->w == shadow->light_view->viewport_w
-                   && shadow->light_view->viewport_h == shadow->light_view->viewport_w, "shadow map must be square and match the light view's viewport");
-        VR_REQUIRE(shadow->shadow_map->ctx->device == ctx->device, "shadow map lives on another device");
-        for (int i = 0; i < 16; i++) sh.w2c[i] = shadow->light_view->world_to_clip[i];
-        { VR_HIP(hipSetDevice(ctx->device)); const int rc = vr_gbuffer_materialise(shadow->shadow_map, ctx->stream); if (rc) return rc; }
-        sh.depth = shadow->shadow_map->depth; sh.res = shadow->shadow_map->w; sh.light_index = shadow->light_index;
-        sh.bias = shadow->depth_bias; sh.out_of_bounds = lights[shadow->light_index].out_of_bounds_shadow;
-    }
-    return VR_OK;
-}
-
-// *stop: the stop event this call's own launch was stamped with (NULL: not stamped, or nothing was launched)
-static int deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
-                          int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
-                          vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, hipEvent_t* stop)
-{
-    *stop = nullptr;
-    VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
-    ShadowArgs sh;
-    { const int rc = fill_shadow(ctx, lights, num_lights, shadow, &sh); if (rc) return rc; }
-    VR_REQUIRE(num_lights >= 0 && num_lights <= kMaxLights, "at most 16 lights (terrain_cb.h:15)");
-    VR_REQUIRE(num_lights == 0 || lights, "lights is NULL");
-    VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0,
-               "view viewport must cover the G-buffer");
-    VR_HIP(hipSetDevice(ctx->device));
-    DeferredArgs a;
-    bool extra = false;
-    { int rc = vr_deferred_make_args(view, gb->w, gb->h, lights, num_lights, amb_top, amb_bottom, &a, &extra); if (rc) return rc; }
-    const size_t npx = (size_t)gb->w * gb->h;
-    const bool packed = part != nullptr;     // a partition (even of one rank) selects the packed tile-major output
-    PlaneHints hints;
-    { int rc = vr_gbuffer_plane_hints(gb, ctx->stream, &hints); if (rc) return rc; }
-    const bool hinted = hints.region != nullptr || hints.emissive_zero != 0;       // else: the pure-stream kernel
-    VrKernelScope ks(ctx, VR_K_DEFERRED, ctx->stream, true);
-    if (packed) {
-        const PartTables* pt = nullptr;
-        int rc = vr_partition_tables(ctx, gb->w, gb->h, part, &pt);
-        if (rc) return rc;
-        VR_REQUIRE((size_t)pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= hdr->capacity_bytes,
-                   "hdr_out is smaller than vr_partition_packed_bytes()");
-        VR_REQUIRE(gb->w % 4 == 0, "partitioned frames need a width that is a multiple of 4");
-        a.tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
-        if (pt->num_owned > 0) {
-            if (!hinted) {
-                auto kern = shadow ? k_deferred_stream<true, true, true> : (extra ? k_deferred_stream<true, true> : k_deferred_stream<true, false>);
-                VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)pt->num_owned * 16), dim3(256), ctx->stream, a, gb->depth, gb->diffuse,
-                                   gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, pt->d_owned_tiles, sh);
-            } else {
-            auto kern = shadow ? k_deferred<true, true, true> : (extra ? k_deferred<true, true> : k_deferred<true, false>);
-            VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)pt->num_owned * 16), dim3(256), ctx->stream, a, gb->depth, gb->diffuse,
-                               gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, pt->d_owned_tiles, sh, hints);
-            }
-        }
-    } else {
-        VR_REQUIRE(npx * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
-        if (gb->w % 4 == 0) {
-            const size_t quads = npx / 4;
-            // streaming loads and stores at every frame size, like the tile pass's stores (vr_raster.hip: measured per size)
-            const bool nt = true;
-            if (!hinted) {
-                auto kern = shadow ? k_deferred_stream<false, true, true, true> : extra ? k_deferred_stream<false, true, false, true>
-                                                                                        : k_deferred_stream<false, false, false, true>;
-                VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)((quads + 255) / 256)), dim3(256), ctx->stream, a, gb->depth, gb->diffuse,
-                                   gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, (const int32_t*)nullptr, sh);
-            } else {
-            auto kern = shadow ? (nt ? k_deferred<false, true, true, true> : k_deferred<false, true, true, false>)
-                               : extra ? (nt ? k_deferred<false, true, false, true> : k_deferred<false, true, false, false>)
-                                       : (nt ? k_deferred<false, false, false, true> : k_deferred<false, false, false, false>);
-            VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)((quads + 255) / 256)), dim3(256), ctx->stream, a, gb->depth, gb->diffuse,
-                               gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, (const int32_t*)nullptr, sh, hints);
-            }
-        } else {
-            VR_LAUNCH_TIMED(ks, k_deferred_scalar, dim3((unsigned)((npx + 255) / 256)), dim3(256), ctx->stream, a, gb->depth, gb->diffuse,
-                               gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, sh, shadow ? 1 : 0);
-        }
-    }
-    *stop = ks.stop();
-    VR_HIP(hipGetLastError());
-    return VR_OK;
-}
-
-int vr_deferred_light_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                           const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
-                           const vr_shadow_binding* shadow, hipEvent_t* stop)
-{
-    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, stop);
-}
-
-extern "C" VR_API int vr_deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
-                                         int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
-                                         vr_image* hdr, const vr_partition* part)
-{
-    hipEvent_t stop;
-    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, &stop);
-}
-
-// DeferredLightingPass::Render with DirectionalLight::shadowMap set (Renderer.cpp:336, 427)
-extern "C" VR_API int vr_deferred_light_shadowed(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
-                                                  int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
-                                                  vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
-{
-    VR_REQUIRE(shadow, "shadow binding is NULL (use vr_deferred_light)");
-    hipEvent_t stop;
-    return deferred_light(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &stop);
 }
 
 // ---- tiled deferred lighting for many point lights (BASELINE config 5) ---------------------------
@@ -834,33 +723,59 @@ __global__ __launch_bounds__(256) void k_deferred_tiled(DeferredArgs a, const De
     if (inside) store_quad<PACKED, NT>(out, out_index, o);
 }
 
-extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
-                                               int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
-                                               vr_image* hdr, const vr_partition* part)
+// ---- the host side of both passes -------------------------------------------------------------------------------------------------
+// Which instantiation runs, over which grid, is light_plan()'s decision (vr_light_plan.h says when each applies); the tables give
+// its enum values their kernels, in the enums' order.  (LV_SCALAR is k_deferred_scalar, alone in its argument list.)
+static_assert(kPlanOwnerTile == VR_OWNER_TILE && kPlanLightTile == kLightTile && kPlanTileLightCap == VR_TILE_LIGHT_CAP, "vr_light_plan.h");
+static decltype(&k_deferred_stream<false, false>) const kStreamKernels[] = {          // <PACKED, EXTRA, SHADOW, NT>, from LV_STREAM_ROW
+    k_deferred_stream<false, false, false, true>, k_deferred_stream<false, true, false, true>, k_deferred_stream<false, true, true, true>,
+    k_deferred_stream<true, false>, k_deferred_stream<true, true>, k_deferred_stream<true, true, true> };
+static decltype(&k_deferred<false, false>) const kHintedKernels[] = {                 // the same, from LV_HINTED_ROW
+    k_deferred<false, false, false, true>, k_deferred<false, true, false, true>, k_deferred<false, true, true, true>,
+    k_deferred<true, false>, k_deferred<true, true>, k_deferred<true, true, true> };
+static decltype(&k_deferred_tiled<false, VR_TILED_PXB>) const kTiledKernels[] = {     // <PACKED, PXB, NT, EXTRA, SHADOW>, from LV_TILED_ROW
+    k_deferred_tiled<false, VR_TILED_PXB, true>, k_deferred_tiled<false, VR_TILED_PXB, true, true, false>, k_deferred_tiled<false, VR_TILED_PXB, true, false, true>,
+    k_deferred_tiled<false, VR_TILED_PXB, true, true, true>, k_deferred_tiled<true, VR_TILED_PXB>, k_deferred_tiled<true, VR_TILED_PXB, false, true, false>,
+    k_deferred_tiled<true, VR_TILED_PXB, false, false, true>, k_deferred_tiled<true, VR_TILED_PXB, false, true, true> };
+static decltype(&k_light_cull<false>) const kCullKernels[LC_COUNT] = {                // <RANGES, CONE>
+    k_light_cull<false>, k_light_cull<true>, k_light_cull<false, true>, k_light_cull<true, true> };
+static_assert(sizeof(kStreamKernels) / sizeof(kStreamKernels[0]) == LV_HINTED_ROW - LV_STREAM_ROW && sizeof(kHintedKernels) / sizeof(kHintedKernels[0]) == LV_SCALAR - LV_HINTED_ROW
+              && sizeof(kTiledKernels) / sizeof(kTiledKernels[0]) == LV_COUNT - LV_TILED_ROW, "one kernel per LightVariant");
+
+// What a pass gets from vr_light_pass, behind every refusal: the call's facts for the plan, the kernels' constants, the rank's tables.
+struct LightCall { LightPlanIn in; DeferredArgs a; ShadowArgs sh; const PartTables* pt; };
+
+// The streaming pass: vr_deferred_light, vr_deferred_light_shadowed.
+// *stop: the stop event this call's own launch was stamped with (NULL: not stamped, or nothing was launched)
+static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightCall& c, hipEvent_t* stop)
 {
-    hipEvent_t stop;
-    return vr_deferred_light_tiled_stop(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, &stop);
+    PlaneHints hints;                                         // (a reader: a pending clear happens now)
+    { const int rc = vr_gbuffer_plane_hints(gb, ctx->stream, &hints); if (rc) return rc; }
+    c.in.hinted = hints.region != nullptr || hints.emissive_zero != 0;       // else: the pure-stream kernel
+    const LightPlan plan = light_plan(c.in);
+    if (plan.launch) {
+        const int32_t* owned = c.pt ? c.pt->d_owned_tiles : nullptr;
+        VrKernelScope ks(ctx, VR_K_DEFERRED, ctx->stream, true);
+#define VR_LIGHT_ARGS c.a, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut
+        if (plan.shade == LV_SCALAR) VR_LAUNCH_TIMED(ks, k_deferred_scalar, dim3(plan.shade_grid), dim3(256), ctx->stream, VR_LIGHT_ARGS, c.sh, c.in.shadow ? 1 : 0);
+        else if (plan.shade < LV_HINTED_ROW) VR_LAUNCH_TIMED(ks, kStreamKernels[plan.shade - LV_STREAM_ROW], dim3(plan.shade_grid), dim3(256), ctx->stream, VR_LIGHT_ARGS, owned, c.sh);
+        else VR_LAUNCH_TIMED(ks, kHintedKernels[plan.shade - LV_HINTED_ROW], dim3(plan.shade_grid), dim3(256), ctx->stream, VR_LIGHT_ARGS, owned, c.sh, hints);
+#undef VR_LIGHT_ARGS
+        *stop = ks.stop();
+    }
+    VR_HIP(hipGetLastError());
+    return VR_OK;
 }
 
-// Both tiled entry points.  ex = false: vr_deferred_light_tiled - directional and punctual point lights, no shadow, the kernels
-// k_light_cull<RANGES> and k_deferred_tiled<PACKED, PXB, NT> and nothing else.  ex = true: vr_deferred_light_tiled_ex - every light
-// type and the optional shadow binding; a list (and binding) the plain kernels can take goes to the plain kernels.
-static int deferred_light_tiled(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                                const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
-                                const vr_shadow_binding* shadow, bool ex, hipEvent_t* stop)
+// Both tiled entry points: vr_deferred_light_tiled, vr_deferred_light_tiled_ex (what either can get: vr_light_plan.h).
+// The list is in ctx->h_lights (vr_light_pass); c.a has no light in it: the kernels read d_lights.
+static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, LightCall& c, hipEvent_t* stop)
 {
-    *stop = nullptr;
-    VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
-    VR_REQUIRE(num_lights >= 0 && num_lights <= 65536 && (num_lights == 0 || lights), "bad light list");
-    ShadowArgs sh;
-    { const int rc = fill_shadow(ctx, lights, num_lights, shadow, &sh); if (rc) return rc; }
-    VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0,
-               "view viewport must cover the G-buffer");
-    VR_HIP(hipSetDevice(ctx->device));
     // (the buffers below grow through vr_grow: a growth that fails leaves the old buffer, its capacity and - d_lights - its contents)
     const auto idle = [ctx]() -> int { VR_HIP(hipStreamSynchronize(ctx->stream)); return VR_OK; };
-    if ((size_t)num_lights * sizeof(DevLight) > ctx->light_bytes) {
-        const size_t cap = (size_t)num_lights < 1024 ? 1024 : (size_t)num_lights;
+    const size_t light_bytes = (size_t)c.in.num_lights * sizeof(DevLight);
+    if (light_bytes > ctx->light_bytes) {
+        const size_t cap = (size_t)c.in.num_lights < 1024 ? 1024 : (size_t)c.in.num_lights;
         const int rc = vr_grow(&ctx->d_lights, &ctx->light_bytes, cap * sizeof(DevLight), idle);
         if (rc) return rc;
         ctx->h_lights_on_device.clear();
@@ -868,119 +783,112 @@ static int deferred_light_tiled(vr_context* ctx, const vr_view* view, vr_gbuffer
     if (!ctx->d_flags) { VR_HIP(hipMalloc(&ctx->d_flags, 64)); VR_HIP(hipMemsetAsync(ctx->d_flags, 0, 64, ctx->stream)); }
     PlaneHints hints;                                         // (a reader: a pending clear happens now)
     { const int rc = vr_gbuffer_plane_hints(gb, ctx->stream, &hints); if (rc) return rc; }
-    ctx->h_lights.resize((size_t)num_lights);
-    bool extra = false, cone = false;       // (ex only) spot or spherical lights in the list; spot lights whose cone is culled
-    for (int i = 0; i < num_lights; i++) {
-        DevLight& d = ctx->h_lights[i];
-        int rc = fill_light(lights[i], d, ex); if (rc) return rc;
-        if (d.type == VR_LIGHT_SPOT) { cone_cull_terms(d.dir, d.outer_angle, &d.cone_cos, &d.cone_sin); cone = cone || d.cone_cos > 0.0f; }
-        extra = extra || d.type == VR_LIGHT_SPOT || d.radius > 0.0f;
-    }
-    const bool more = extra || shadow != nullptr;
     // a scene's light list rarely changes between frames: upload only when it differs from what the device holds
-    const size_t light_bytes = (size_t)num_lights * sizeof(DevLight);
-    if (num_lights && (ctx->h_lights_on_device.size() != (size_t)num_lights
-                       || memcmp(ctx->h_lights_on_device.data(), ctx->h_lights.data(), light_bytes) != 0)) {
+    if (light_bytes && (ctx->h_lights_on_device.size() != (size_t)c.in.num_lights || memcmp(ctx->h_lights_on_device.data(), ctx->h_lights.data(), light_bytes) != 0)) {
         ctx->h_lights_on_device.clear();
         VR_HIP(hipMemcpyAsync(ctx->d_lights, ctx->h_lights.data(), light_bytes, hipMemcpyHostToDevice, ctx->stream));
         ctx->h_lights_on_device = ctx->h_lights;
     }
-    DeferredArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int i = 0; i < 16; i++) a.c2w[i] = view->clip_to_world[i];
-    for (int i = 0; i < 3; i++) { a.cam[i] = view->camera_pos[i]; a.amb_top[i] = amb_top[i]; a.amb_bot[i] = amb_bottom[i]; }
-    a.w = gb->w; a.h = gb->h; a.sx = 2.0f / (float)gb->w; a.sy = -2.0f / (float)gb->h; a.num_lights = 0;
-    for (int i = 0; i < num_lights; i++) if (ctx->h_lights[i].type != VR_LIGHT_DIRECTIONAL) a.exact_pos = 1;
-    const bool packed = part != nullptr;
-    VR_REQUIRE(gb->w % 4 == 0, "the tiled pass needs a frame width that is a multiple of 4");
-    // light lists: one per 32x32 light tile, count + up to min(num_lights, VR_TILE_LIGHT_CAP) indices
-    const int macro_x = (gb->w + kMacroTile - 1) / kMacroTile, macro_y = (gb->h + kMacroTile - 1) / kMacroTile;
-    const int tx = (gb->w + kLightTile - 1) / kLightTile, ty = (gb->h + kLightTile - 1) / kLightTile;
-    const int stride = (num_lights < kTileLightCap ? num_lights : kTileLightCap) + 1;
-    const size_t words = (size_t)tx * ty * stride;
-    { const int rc = vr_grow(&ctx->d_light_lists, &ctx->light_list_bytes, words * sizeof(uint32_t), idle); if (rc) return rc; }
-    // per macro tile: the lights that touch its box, in four regions (one per wave of k_light_cull)
-    const size_t scratch_words = (size_t)macro_x * macro_y * (size_t)(((num_lights + 3) / 4) * 4) + 4;
-    { const int rc = vr_grow(&ctx->d_macro_scratch, &ctx->macro_scratch_bytes, scratch_words * sizeof(uint32_t), idle); if (rc) return rc; }
-    // The light tiles' depth ranges, if the tile pass that filled this G-buffer left them (for the same split) and nothing has
-    // written to it since.  The culling stage consumes them (every entry it reads is reset), hence CLEAN afterwards - for a
-    // split, only if this rank's share is non-empty (else nothing was written either).
-    const bool use_ranges = vr_gbuffer_consume_ranges(gb, part ? part->rank : 0, part ? part->world_size : 1);
-    ctx->list_stride = stride; ctx->list_tiles_x = tx; ctx->list_tiles_y = ty;
-    const auto cull = cone ? (use_ranges ? k_light_cull<true, true> : k_light_cull<false, true>) : (use_ranges ? k_light_cull<true> : k_light_cull<false>);
+    // the light tiles' depth ranges, if the tile pass that filled this G-buffer left them (for the same split) and nothing has written to it since
+    const int rank = part ? part->rank : 0, world = part ? part->world_size : 1;
+    c.in.ranges_usable = vr_gbuffer_ranges_usable(gb, rank, world);
+    const LightPlan plan = light_plan(c.in);
+    { const int rc = vr_grow(&ctx->d_light_lists, &ctx->light_list_bytes, plan.list_words * sizeof(uint32_t), idle); if (rc) return rc; }
+    { const int rc = vr_grow(&ctx->d_macro_scratch, &ctx->macro_scratch_bytes, plan.scratch_words * sizeof(uint32_t), idle); if (rc) return rc; }
+    // Only the launches are left: now the state may say what the culling stage does.  It consumes the ranges (every entry it
+    // reads is reset), hence CLEAN afterwards - for a split, also where this rank's share is empty (nothing was written either).
+    if (plan.consume_ranges) vr_gbuffer_consume_ranges(gb, rank, world);
+    ctx->list_stride = plan.list_stride; ctx->list_tiles_x = plan.tiles32_x; ctx->list_tiles_y = plan.tiles32_y;
     // two launches, each timed under its own id; the shading kernel's events are stamped by its dispatch like the streaming
     // pass's, so its stop event serves as the next frame's geometry start hint (vr_terrain_prepare)
-    if (packed) {
-        const PartTables* pt = nullptr;
-        int rc = vr_partition_tables(ctx, gb->w, gb->h, part, &pt);
-        if (rc) return rc;
-        VR_REQUIRE((size_t)pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= hdr->capacity_bytes, "hdr_out is smaller than vr_partition_packed_bytes()");
-        a.tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
-        if (pt->num_owned > 0) {
-            { VrKernelScope kc(ctx, VR_K_LIGHT_CULL);
-              hipLaunchKernelGGL(cull, dim3((unsigned)pt->num_owned), dim3(256), 0, ctx->stream, a, ctx->d_lights,
-                                 num_lights, gb->depth, (const uint2*)gb->normals, macro_x, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
-                                 gb->d_ranges); }
-            VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
-            if (more) {
-                const auto kern = shadow ? (extra ? k_deferred_tiled<true, VR_TILED_PXB, false, true, true> : k_deferred_tiled<true, VR_TILED_PXB, false, false, true>)
-                                         : k_deferred_tiled<true, VR_TILED_PXB, false, true, false>;
-                VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)pt->num_owned * kSubTiles), dim3(256), ctx->stream, a,
-                                ctx->d_lights, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data,
-                                ctx->d_srgb_lut, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, hints, sh);
-            } else
-            VR_LAUNCH_TIMED(ks, (k_deferred_tiled<true, VR_TILED_PXB>), dim3((unsigned)pt->num_owned * kSubTiles), dim3(256), ctx->stream, a,
-                            ctx->d_lights, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data,
-                            ctx->d_srgb_lut, pt->d_owned_tiles, ctx->d_light_lists, stride, tx, hints, sh);
-            *stop = ks.stop();
-        }
-    } else {
-        VR_REQUIRE((size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
+    if (plan.launch) {
+        const int32_t* owned = c.pt ? c.pt->d_owned_tiles : nullptr;
         { VrKernelScope kc(ctx, VR_K_LIGHT_CULL);
-          hipLaunchKernelGGL(cull, dim3((unsigned)(macro_x * macro_y)), dim3(256), 0, ctx->stream, a, ctx->d_lights,
-                             num_lights, gb->depth, (const uint2*)gb->normals, macro_x, (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, ty, ctx->d_flags, ctx->d_macro_scratch,
-                             gb->d_ranges); }
+          hipLaunchKernelGGL(kCullKernels[plan.cull], dim3(plan.cull_grid), dim3(256), 0, ctx->stream, c.a, ctx->d_lights, c.in.num_lights, gb->depth, (const uint2*)gb->normals,
+                             plan.macro_x, owned, ctx->d_light_lists, plan.list_stride, plan.tiles32_x, plan.tiles32_y, ctx->d_flags, ctx->d_macro_scratch, gb->d_ranges); }
         VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
-        const bool nt = true;                                         // as in the streaming pass
-        if (more) {
-            const auto kern = shadow ? (extra ? k_deferred_tiled<false, VR_TILED_PXB, true, true, true> : k_deferred_tiled<false, VR_TILED_PXB, true, false, true>)
-                                     : k_deferred_tiled<false, VR_TILED_PXB, true, true, false>;
-            VR_LAUNCH_TIMED(ks, kern, dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
-                            gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut,
-                            (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints, sh);
-        } else if (nt) VR_LAUNCH_TIMED(ks, (k_deferred_tiled<false, VR_TILED_PXB, true>), dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
-                                gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut,
-                                (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints, sh);
-        else VR_LAUNCH_TIMED(ks, (k_deferred_tiled<false, VR_TILED_PXB, false>), dim3((unsigned)(tx * ty)), dim3(256), ctx->stream, a, ctx->d_lights,
-                             gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut,
-                             (const int32_t*)nullptr, ctx->d_light_lists, stride, tx, hints, sh);
+        VR_LAUNCH_TIMED(ks, kTiledKernels[plan.shade - LV_TILED_ROW], dim3(plan.shade_grid), dim3(256), ctx->stream, c.a, ctx->d_lights, gb->depth, gb->diffuse, gb->specular,
+                        gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, owned, ctx->d_light_lists, plan.list_stride, plan.tiles32_x, hints, c.sh);
         *stop = ks.stop();
     }
     VR_HIP(hipGetLastError());
     return VR_OK;
 }
 
-int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                                 const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop)
+// Every lighting pass: the five exported entry points below, and vr_frame_submit.  One order for all of them: every refusal of an
+// argument, the rank's tables (a lookup that at most fills the context's cache; needed to size-check hdr_out), the remaining
+// refusals - and only then the effects, which the two functions above continue: the device, the shadow map and the G-buffer made
+// real, the tiled pass's buffers and its light upload, the depth ranges consumed, the launches.  A refused call leaves no trace.
+int vr_light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                  const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, hipEvent_t* stop)
 {
-    return deferred_light_tiled(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, false, stop);
+    *stop = nullptr;
+    const bool tiled = entry != LIGHT_STREAM;
+    if (entry == LIGHT_TILED) shadow = nullptr;               // (vr_deferred_light_tiled has no shadow term: a binding that comes with it is ignored)
+    VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
+    VR_REQUIRE(!tiled || (num_lights >= 0 && num_lights <= 65536 && (num_lights == 0 || lights)), "bad light list");
+    VR_REQUIRE(tiled || (num_lights >= 0 && num_lights <= kMaxLights), "at most 16 lights (terrain_cb.h:15)");
+    VR_REQUIRE(tiled || num_lights == 0 || lights, "lights is NULL");
+    if (shadow) {                                             // (vr_deferred_light_shadowed, vr_deferred_light_tiled_ex)
+        VR_REQUIRE(shadow->light_view && shadow->shadow_map, "shadow binding has NULL members");
+        VR_REQUIRE(shadow->light_index >= 0 && shadow->light_index < num_lights, "shadow light_index out of range");
+        VR_REQUIRE(lights[shadow->light_index].type == VR_LIGHT_DIRECTIONAL, "only a directional light carries the cascaded shadow map");
+        VR_REQUIRE(shadow->shadow_map->w == shadow->shadow_map->h && shadow->shadow_map->w == shadow->light_view->viewport_w
+                   && shadow->light_view->viewport_h == shadow->light_view->viewport_w, "shadow map must be square and match the light view's viewport");
+        VR_REQUIRE(shadow->shadow_map->ctx->device == ctx->device, "shadow map lives on another device");
+    }
+    VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0, "view viewport must cover the G-buffer");
+    LightCall c{};
+    LightPlanIn& in = c.in;       // extra: spot or spherical lights in the list; cone (LIGHT_TILED_EX): spot lights whose cone is culled
+    if (!tiled) { const int rc = vr_deferred_make_args(view, gb->w, gb->h, lights, num_lights, amb_top, amb_bottom, &c.a, &in.extra); if (rc) return rc; }
+    else {
+        deferred_view_args(view, gb->w, gb->h, amb_top, amb_bottom, &c.a);
+        ctx->h_lights.resize((size_t)num_lights);             // (staging: nothing reads it between calls)
+        for (int i = 0; i < num_lights; i++) {
+            DevLight& d = ctx->h_lights[i];
+            int rc = fill_light(lights[i], d, entry == LIGHT_TILED_EX); if (rc) return rc;
+            if (d.type == VR_LIGHT_SPOT) { cone_cull_terms(d.dir, d.outer_angle, &d.cone_cos, &d.cone_sin); in.cone = in.cone || d.cone_cos > 0.0f; }
+            in.extra = in.extra || d.type == VR_LIGHT_SPOT || d.radius > 0.0f;
+            if (d.type != VR_LIGHT_DIRECTIONAL) c.a.exact_pos = 1;
+        }
+    }
+    if (part) { const int rc = vr_partition_tables(ctx, gb->w, gb->h, part, &c.pt); if (rc) return rc; }
+    VR_REQUIRE(!c.pt || (size_t)c.pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= hdr->capacity_bytes, "hdr_out is smaller than vr_partition_packed_bytes()");
+    VR_REQUIRE(c.pt || (size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
+    in.entry = entry; in.packed = c.pt != nullptr; in.num_owned = c.pt ? c.pt->num_owned : 0;      // a partition (even of one rank) selects the packed tile-major output
+    in.width_mult4 = gb->w % 4 == 0; in.shadow = shadow != nullptr; in.num_lights = num_lights; in.w = gb->w; in.h = gb->h;
+    VR_REQUIRE(light_width_ok(in), tiled ? "the tiled pass needs a frame width that is a multiple of 4" : "partitioned frames need a width that is a multiple of 4");
+    // ---- nothing refuses an argument from here on
+    VR_HIP(hipSetDevice(ctx->device));
+    if (in.packed) c.a.tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
+    if (shadow) {                                             // the map made real (a pending clear is written), the kernels' constants
+        ShadowArgs& sh = c.sh;
+        for (int i = 0; i < 16; i++) sh.w2c[i] = shadow->light_view->world_to_clip[i];
+        { const int rc = vr_gbuffer_materialise(shadow->shadow_map, ctx->stream); if (rc) return rc; }
+        sh.depth = shadow->shadow_map->depth; sh.res = shadow->shadow_map->w; sh.light_index = shadow->light_index;
+        sh.bias = shadow->depth_bias; sh.out_of_bounds = lights[shadow->light_index].out_of_bounds_shadow;
+    }
+    return tiled ? deferred_light_tiled(ctx, gb, hdr, part, c, stop) : deferred_light(ctx, gb, hdr, c, stop);
 }
 
-int vr_deferred_light_tiled_ex_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                                    const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
-                                    const vr_shadow_binding* shadow, hipEvent_t* stop)
+extern "C" VR_API int vr_deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                         const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part)
+{ hipEvent_t stop; return vr_light_pass(ctx, LIGHT_STREAM, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, &stop); }
+// DeferredLightingPass::Render with DirectionalLight::shadowMap set (Renderer.cpp:336, 427)
+extern "C" VR_API int vr_deferred_light_shadowed(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights, const float amb_top[3],
+                                                  const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
 {
-    return deferred_light_tiled(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, true, stop);
-}
-
-// vr_deferred_light_tiled for every light type, with the sun's shadow term (shadow may be NULL)
-extern "C" VR_API int vr_deferred_light_tiled_ex(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights,
-                                                  int32_t num_lights, const float amb_top[3], const float amb_bottom[3],
-                                                  vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
-{
+    VR_REQUIRE(shadow, "shadow binding is NULL (use vr_deferred_light)");
     hipEvent_t stop;
-    return deferred_light_tiled(ctx, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, true, &stop);
+    return vr_light_pass(ctx, LIGHT_STREAM, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &stop);
 }
+extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                                               const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part)
+{ hipEvent_t stop; return vr_light_pass(ctx, LIGHT_TILED, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, &stop); }
+// vr_deferred_light_tiled for every light type, with the sun's shadow term (shadow may be NULL)
+extern "C" VR_API int vr_deferred_light_tiled_ex(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights, const float amb_top[3],
+                                                  const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
+{ hipEvent_t stop; return vr_light_pass(ctx, LIGHT_TILED_EX, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &stop); }
 
 // Test helper: the list the last tiled pass of this context left for light tile (tile_x, tile_y); synchronises.
 extern "C" VR_API int vr_debug_tile_light_list(vr_context* ctx, int32_t tile_x, int32_t tile_y, uint32_t* out, int32_t capacity, int32_t* out_count)

@@ -41,10 +41,8 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
         if ((rc = order_image_writer_begins(hdr->ord, ops, ctx->stream))) return rc;
         // tiled: 2 = every light type and the shadow binding (vr_deferred_light_tiled_ex); any other non-zero value = 1 =
         // vr_deferred_light_tiled, which has no shadow term: the binding is ignored
-        if (f->tiled == 2) rc = vr_deferred_light_tiled_ex_stop(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow, &written_stop);
-        else if (f->tiled) rc = vr_deferred_light_tiled_stop(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, &written_stop);
-        else rc = vr_deferred_light_stop(ctx, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow, &written_stop);
-        if (rc) return rc;
+        const LightEntry entry = f->tiled == 2 ? LIGHT_TILED_EX : f->tiled ? LIGHT_TILED : LIGHT_STREAM;
+        if ((rc = vr_light_pass(ctx, entry, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow, &written_stop))) return rc;
     }
     if (!f->tonemap) return earlier;
 

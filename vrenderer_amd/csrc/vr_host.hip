@@ -578,11 +578,16 @@ int vr_gbuffer_apply_plan(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s, 
     return VR_OK;
 }
 
-bool vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world)
+bool vr_gbuffer_ranges_usable(const vr_gbuffer* g, int rank, int world)
+{
+    bool use;
+    (void)gbs_consume_ranges(g->st, rank, world, &use);
+    return use;
+}
+void vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world)
 {
     bool use;
     g->st = gbs_consume_ranges(g->st, rank, world, &use);
-    return use;
 }
 
 extern "C" VR_API int vr_gbuffer_describe(vr_gbuffer* g, vr_gbuffer_desc* d)

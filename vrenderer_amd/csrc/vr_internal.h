@@ -13,6 +13,7 @@
 #include "../../include/vrterrain.h"
 #include "vr_devbuf.h"
 #include "vr_gbuffer_state.h"
+#include "vr_light_plan.h"
 #include "vr_order.h"
 #include "vr_scratch.h"
 
@@ -270,8 +271,10 @@ int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s);      // a pending clea
 // arrays it needs, their fills, then the state behind the pass (*region; NULL: not kept).  A refusal leaves the state as it was.
 struct RasterPlan;
 int vr_gbuffer_apply_plan(vr_gbuffer* g, const RasterPlan& plan, hipStream_t s, int rank, int world, uint8_t** region);
-// the tiled lighting pass takes the depth ranges if they are VALID for this split (they are "none" again once it has run)
-bool vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world);
+// the tiled lighting pass takes the depth ranges if they are VALID for this split: asked first, and committed - they are "none"
+// again once its culling stage has run - only when nothing can refuse the call any more
+bool vr_gbuffer_ranges_usable(const vr_gbuffer* g, int rank, int world);
+void vr_gbuffer_consume_ranges(vr_gbuffer* g, int rank, int world);
 // What a pass that READS the G-buffer may take from the tracking instead of from memory (the lighting passes).
 struct PlaneHints {
     const uint8_t* region;       // region states (NULL: nothing known per region)
@@ -416,16 +419,11 @@ int vr_terrain_frame_scratch(vr_terrain* t, bool report, const std::function<int
 int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
                            int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
                            bool* fused, hipEvent_t* fused_stop);
-// the lighting passes as vr_frame_submit queues them (vr_deferred.hip): the exported entry points (shadow may be NULL), and
-// *stop = the stop event their own launch was stamped with (NULL: not stamped, or nothing was launched)
-int vr_deferred_light_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                           const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
-                           const vr_shadow_binding* shadow, hipEvent_t* stop);
-int vr_deferred_light_tiled_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                                 const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, hipEvent_t* stop);
-int vr_deferred_light_tiled_ex_stop(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                                    const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
-                                    const vr_shadow_binding* shadow, hipEvent_t* stop);
+// the lighting passes as vr_frame_submit queues them (vr_deferred.hip): the exported entry point that `entry` names (shadow may be
+// NULL; LIGHT_TILED ignores it), and *stop = the stop event its own launch was stamped with (NULL: not stamped, or nothing was launched)
+int vr_light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                  const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
+                  const vr_shadow_binding* shadow, hipEvent_t* stop);
 // tables of (w, h, part); part == NULL is the whole frame as rank 0 of 1
 int vr_partition_tables(vr_context* ctx, int w, int h, const vr_partition* part, const PartTables** out);
 // any cached table set of (w, h, world): the slot table does not depend on the rank
