@@ -290,3 +290,96 @@ def test_one_8k_frame():
     assert np.array_equal(res[0][0], res[1][0]), "HdrColor"
     assert np.array_equal(res[0][1], res[1][1]), "depth"
     assert res[0][2] == res[1][2], "region census"
+
+
+@pytest.mark.parametrize("split", [False, True], ids=["whole", "rank0of2"])
+def test_a_refused_frame_leaves_no_trace(fx, split):
+    """vr_frame_submit refuses before it queues anything.  With a Clear pending, sentinels in HdrColor and the LDR buffer (a
+    rank's packed buffers with `split`), known bins and an adapted luminance of 0.25, a frame whose tone-map stage is refused -
+    no parameters, an LDR capacity one byte short, an empty log-luminance range - or whose hdr_out is too small (by one pixel:
+    an image's capacity is a whole number of them) returns VR_ERR_INVALID_ARGUMENT with the message it always had, queues no
+    kernel at all, leaves both buffers, the bins and the adapted luminance as they were, and leaves the Clear pending: every
+    region still counts as clear and the planes' first download is what writes it.  The corrected descriptor then gives the
+    planes, HdrColor, LdrColor and tone-mapper state of the per-call sequence, bit for bit."""
+    import ctypes as C
+    from vrenderer_amd.passes import partition_info
+    ctx, tp = fx["ctx"], fx["tp"]
+    w, h = 256, 144
+    v = _fly(0, w, h)
+    rp = vr.default_render_params(400.0, assume_cleared=1)
+    lights = [vr.reference_sun()]
+    tmp, bad = vr.default_tonemap_params(), vr.default_tonemap_params(max_log_luminance=-10.0)
+    assert bad.max_log_luminance == bad.min_log_luminance
+    part = vr.Partition(0, 2) if split else None
+    hdr_bytes = partition_info(w, h, 0, 2)["packed_bytes"] if split else w * h * 8
+    ldr_bytes = hdr_bytes // 2
+    mk_hdr = lambda px: vr.HdrImage(ctx, vr.VR_OWNER_TILE, px // vr.VR_OWNER_TILE) if px % vr.VR_OWNER_TILE == 0 else vr.HdrImage(ctx, px, 1)
+    hdrs, small = [mk_hdr(hdr_bytes // 8) for _ in range(2)], mk_hdr(hdr_bytes // 8 - 1)
+    ldrs = [vr.LdrImage(ctx, w, h, capacity_bytes=ldr_bytes) for _ in range(2)]
+    rts = [vr.RenderTargets(ctx).Init(w, h) for _ in range(2)]
+    tms = [vr.ToneMappingPass(ctx) for _ in range(2)]
+    sent_hdr, sent_ldr = np.full(hdr_bytes // 2, 0x3c00, np.uint16), np.full(ldr_bytes, 0x5a, np.uint8)
+    rt, hdr, ldr, tm = rts[0], hdrs[0], ldrs[0], tms[0]
+    try:
+        for t in tms:
+            t.AdvanceFrame(1.0 / 60.0)
+        hdr.upload(sent_hdr)
+        tm.AddFrameToHistogram(tmp, hdr, w, h, part)
+        tm.ResetExposure(0.25)
+        bins, lum = tm.download()
+        assert bins.any() and lum == 0.25
+        fr = vr.Frame(tp, rt, rp, lights, AMBIENT_TOP, AMBIENT_BOTTOM, part, tonemap=tm, tonemap_params=tmp, ldr=ldr)
+        d = fr.desc
+        for case, text in (("params", "tone-map stage: params / ldr_out missing"),
+                           ("ldr_capacity", "ldr buffer is smaller than vr_partition_packed_bytes_ldr()" if split else "ldr buffer is smaller than the frame"),
+                           ("log_range", "max_log_luminance must exceed min_log_luminance"),
+                           ("hdr_out", "hdr_out is smaller than vr_partition_packed_bytes()" if split else "hdr_out is smaller than the frame")):
+            rt.upload("diffuse", np.full((h, w), 0x01020304, np.uint32))
+            rt.Clear()                                           # lazy: nothing is written yet
+            hdr.upload(sent_hdr); small.upload(sent_hdr[:-4]); ldr.upload(sent_ldr)
+            d.tonemap_params = None if case == "params" else C.addressof(bad if case == "log_range" else tmp)
+            d.ldr_capacity = ldr.capacity - (1 if case == "ldr_capacity" else 0)
+            ctx.synchronize()
+            ctx.timing_enable(1)
+            with pytest.raises(vr.VrError) as e:
+                fr.submit(v, small if case == "hdr_out" else hdr, [_fly(1, w, h)])
+            ctx.synchronize()
+            ran = ctx.timing_collect()
+            assert e.value.code == vr.capi.VR_ERR_INVALID_ARGUMENT and text in str(e.value), (case, e.value)
+            assert not ran, f"{case}: the refused frame queued {sorted(ran)}"
+            census = rt.region_census()
+            assert census["clear"] == census["total"] > 0, (case, census)
+            assert np.array_equal(hdr.download(hdr_bytes), sent_hdr) and np.array_equal(small.download(hdr_bytes - 8), sent_hdr[:-4]), f"{case}: HdrColor"
+            assert np.array_equal(ldr.download(ldr_bytes), sent_ldr), f"{case}: the LDR buffer"
+            bins1, lum1 = tm.download()
+            assert np.array_equal(bins, bins1) and np.float32(lum1).view(np.uint32) == np.float32(lum).view(np.uint32), f"{case}: bins / adapted luminance"
+            planes = {p: rt.download(p) for p in PLANES}         # (the first of them writes the pending clear)
+            written = ctx.timing_collect()
+            ctx.timing_enable(0)
+            assert len(written) == 1 and [n for _, n in written.values()] == [1], f"{case}: the Clear was no longer pending: {written}"
+            assert (planes["depth"] == 1.0).all() and not any(planes[p].any() for p in PLANES[1:]), f"{case}: the planes do not read as cleared"
+        # the corrected descriptor against the per-call sequence
+        d.tonemap_params, d.ldr_capacity = C.addressof(tmp), ldr.capacity
+        rt.Clear()
+        fr.submit(v, hdr, [_fly(1, w, h)])
+        rts[1].Clear(); hdrs[1].upload(sent_hdr); ldrs[1].upload(sent_ldr)
+        tms[1].ResetExposure(0.25)
+        tp.Render(v, v, rts[1], rp, part)
+        vr.DeferredLightingPass(ctx).Render(v, rts[1], lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdrs[1], partition=part)
+        tms[1].ResetHistogram()
+        tms[1].AddFrameToHistogram(tmp, hdrs[1], w, h, part)
+        tms[1].ComputeExposure(tmp)
+        tms[1].Render(tmp, hdrs[1], ldrs[1], w, h, part)
+        ctx.synchronize()
+        for p in PLANES:
+            assert np.array_equal(rts[0].download(p).view(np.uint8), rts[1].download(p).view(np.uint8)), p
+        assert np.array_equal(hdrs[0].download(hdr_bytes), hdrs[1].download(hdr_bytes)), "HdrColor"
+        assert np.array_equal(ldrs[0].download(ldr_bytes), ldrs[1].download(ldr_bytes)), "LdrColor"
+        assert not np.array_equal(ldrs[0].download(ldr_bytes), sent_ldr)
+        (b0, l0), (b1, l1) = tms[0].download(), tms[1].download()
+        assert np.array_equal(b0, b1) and np.float32(l0).view(np.uint32) == np.float32(l1).view(np.uint32), (l0, l1)
+    finally:
+        ctx.synchronize()
+        ctx.timing_enable(0)
+        for o in tms + ldrs + hdrs + [small] + rts:
+            o.close()

@@ -301,3 +301,28 @@ def test_extreme_exposure_saturates(gpu_ctx, how, w):
     assert got[4].tolist() == [255, 0, 0] and got[5].tolist() == [0, 255, 0]
     for o in (hdr, ldr, tm):
         o.close()
+
+
+@pytest.mark.parametrize("w", [8, 6], ids=["vector", "scalar"])
+def test_a_refused_simple_render_leaves_bins_and_adapted_luminance(gpu_ctx, w):
+    """vr_tonemap_simple_render with an LDR buffer one byte short is refused before its first step: the bins keep their
+    (non-zero) content instead of being reset, and the adapted luminance is not advanced."""
+    tmp = vr.default_tonemap_params()
+    hdr, ldr = vr.HdrImage(gpu_ctx, w, 1), vr.LdrImage(gpu_ctx, w, 1, capacity_bytes=w * 4 - 1)
+    tm = vr.ToneMappingPass(gpu_ctx)
+    try:
+        hdr.upload(np.tile(np.array([0x3800, 0x3c00, 0x4000, 0], np.uint16), w))
+        tm.AdvanceFrame(1.0 / 60.0)
+        tm.AddFrameToHistogram(tmp, hdr)
+        tm.ResetExposure(0.25)
+        bins, lum = tm.download()
+        assert bins.any() and lum == 0.25
+        with pytest.raises(vr.VrError) as e:
+            tm.SimpleRender(tmp, hdr, ldr)
+        assert e.value.code == vr.capi.VR_ERR_INVALID_ARGUMENT and "ldr buffer is smaller than the frame" in str(e.value), e.value
+        bins1, lum1 = tm.download()
+        assert np.array_equal(bins, bins1), "the refused call touched the histogram"
+        assert np.float32(lum1).view(np.uint32) == np.float32(lum).view(np.uint32), (lum, lum1)
+    finally:
+        for o in (tm, ldr, hdr):
+            o.close()

@@ -1,7 +1,8 @@
 // Multi-GPU frame assembly through the C ABI: the RCCL all-gather of a rank's packed tiles on the
 // context's stream followed by the de-tile kernel, and the one real exchange step of the tone mapper (all-reduce of
 // the 256 histogram bins).  One process per GPU; the communicator is the host's (ncclCommInitRank, or the one its
-// framework created).
+// framework created).  A wrapper takes every refusal - its own arguments', the loader's, the de-tile's - in front of the stream's
+// release and the collective: a rank that entered a collective and then refused would leave its peers waiting in the next one.
 //
 // RCCL is not a link-time dependency of libvrterrain.so: the three entry points are resolved at first use from the
 // RCCL that is already in the process - the one the caller's ncclComm_t came from - and only then from librccl.so on
@@ -21,7 +22,7 @@ typedef int (*AllReduceFn)(const void*, void*, size_t, int, int, void*, hipStrea
 typedef const char* (*ErrStrFn)(int);
 
 // Resolved exactly once (std::call_once): a host may drive its ranks as threads of one process (tests/host/
-// frame_allgather_example.cpp), and every one of them comes through rccl_load() on its first frame.  The pointers are
+// frame_allgather_example.cpp), and every one of them comes through vr_rccl_load() on its first frame.  The pointers are
 // written inside the once-block only and read after it has returned, so no thread can see a half-filled table.
 struct Rccl {
     std::once_flag once;
@@ -46,7 +47,9 @@ void* find_symbol(const char* name)
     return nullptr;
 }
 
-int rccl_load()
+} // namespace
+
+int vr_rccl_load()
 {
     std::call_once(g_rccl.once, [] {
         g_rccl.all_gather = (AllGatherFn)find_symbol("ncclAllGather");
@@ -60,6 +63,7 @@ int rccl_load()
     return VR_OK;
 }
 
+namespace {
 // The library's own events carry hipEventDisableSystemFence (device-to-device ordering on one GPU).  A collective hands this
 // GPU's buffers to kernels that move them to peer GPUs: in front of it the stream gets ONE event record with the default flags,
 // i.e. a system-scope release of everything the stream has written (a few microseconds on the exchange stream, per collective).
@@ -82,7 +86,8 @@ extern "C" VR_API int vr_frame_allgather(vr_context* ctx, void* nccl_comm, const
                                           vr_image* frame_out)
 {
     VR_REQUIRE(ctx && nccl_comm && packed && gathered && frame_out && world >= 1, "bad arguments");
-    int rc = rccl_load(); if (rc) return rc;
+    int rc = vr_rccl_load(); if (rc) return rc;
+    if ((rc = vr_frame_detile_check(ctx, gathered, world, frame_out))) return rc;
     VR_HIP(hipSetDevice(ctx->device));
     const size_t bytes = vr_partition_packed_bytes(frame_out->w, frame_out->h, world);
     if ((rc = system_release(ctx))) return rc;
@@ -93,7 +98,7 @@ extern "C" VR_API int vr_frame_allgather(vr_context* ctx, void* nccl_comm, const
 extern "C" VR_API int vr_frame_allgather_tiles(vr_context* ctx, void* nccl_comm, const void* packed, void* gathered, int32_t world, size_t bytes_per_rank)
 {
     VR_REQUIRE(ctx && nccl_comm && packed && gathered && world >= 1 && bytes_per_rank > 0, "bad arguments");
-    int rc = rccl_load(); if (rc) return rc;
+    int rc = vr_rccl_load(); if (rc) return rc;
     VR_HIP(hipSetDevice(ctx->device));
     if ((rc = system_release(ctx))) return rc;
     return rccl_check(g_rccl.all_gather(packed, gathered, bytes_per_rank, kNcclUint8, nccl_comm, ctx->stream), "ncclAllGather");
@@ -103,7 +108,8 @@ extern "C" VR_API int vr_frame_allgather_ldr(vr_context* ctx, void* nccl_comm, c
                                               int32_t w, int32_t h, void* ldr_frame)
 {
     VR_REQUIRE(ctx && nccl_comm && packed_ldr && gathered && ldr_frame && world >= 1 && w > 0 && h > 0, "bad arguments");
-    int rc = rccl_load(); if (rc) return rc;
+    int rc = vr_rccl_load(); if (rc) return rc;
+    if ((rc = vr_frame_detile_ldr_check(ctx, gathered, world, w, h, ldr_frame))) return rc;
     VR_HIP(hipSetDevice(ctx->device));
     const size_t bytes = vr_partition_packed_bytes_ldr(w, h, world);
     if ((rc = system_release(ctx))) return rc;
@@ -114,7 +120,7 @@ extern "C" VR_API int vr_frame_allgather_ldr(vr_context* ctx, void* nccl_comm, c
 extern "C" VR_API int vr_tonemap_allreduce_histogram(vr_tonemap* tm, void* nccl_comm)
 {
     VR_REQUIRE(tm && nccl_comm, "bad arguments");
-    int rc = rccl_load(); if (rc) return rc;
+    int rc = vr_rccl_load(); if (rc) return rc;
     vr_context* ctx = vr_tonemap_context(tm);
     VR_HIP(hipSetDevice(ctx->device));
     void* hist = vr_tonemap_histogram_device_ptr(tm);

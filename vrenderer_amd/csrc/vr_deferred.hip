@@ -14,7 +14,7 @@
 // LDS.  fp32 math; checked against the CPU oracle to per-channel RMS <= 1e-4.
 //
 // The host side (behind the kernels) decides nothing about kernels itself: vr_light_plan.h holds the variant rules as one pure function, checked
-// on the CPU, and each kernel family is launched from one place.  All five entry points go through vr_light_pass, which refuses first and acts afterwards.
+// on the CPU, and each kernel family is launched from one place.  All five entry points go through vr_light_check and vr_light_queue: every refusal first, the effects afterwards.
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
 
@@ -742,9 +742,6 @@ static decltype(&k_light_cull<false>) const kCullKernels[LC_COUNT] = {          
 static_assert(sizeof(kStreamKernels) / sizeof(kStreamKernels[0]) == LV_HINTED_ROW - LV_STREAM_ROW && sizeof(kHintedKernels) / sizeof(kHintedKernels[0]) == LV_SCALAR - LV_HINTED_ROW
               && sizeof(kTiledKernels) / sizeof(kTiledKernels[0]) == LV_COUNT - LV_TILED_ROW, "one kernel per LightVariant");
 
-// What a pass gets from vr_light_pass, behind every refusal: the call's facts for the plan, the kernels' constants, the rank's tables.
-struct LightCall { LightPlanIn in; DeferredArgs a; ShadowArgs sh; const PartTables* pt; };
-
 // The streaming pass: vr_deferred_light, vr_deferred_light_shadowed.
 // *stop: the stop event this call's own launch was stamped with (NULL: not stamped, or nothing was launched)
 static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightCall& c, hipEvent_t* stop)
@@ -768,7 +765,7 @@ static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightC
 }
 
 // Both tiled entry points: vr_deferred_light_tiled, vr_deferred_light_tiled_ex (what either can get: vr_light_plan.h).
-// The list is in ctx->h_lights (vr_light_pass); c.a has no light in it: the kernels read d_lights.
+// The list is in ctx->h_lights (vr_light_check); c.a has no light in it: the kernels read d_lights.
 static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, LightCall& c, hipEvent_t* stop)
 {
     // (the buffers below grow through vr_grow: a growth that fails leaves the old buffer, its capacity and - d_lights - its contents)
@@ -815,14 +812,16 @@ static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, 
     return VR_OK;
 }
 
-// Every lighting pass: the five exported entry points below, and vr_frame_submit.  One order for all of them: every refusal of an
-// argument, the rank's tables (a lookup that at most fills the context's cache; needed to size-check hdr_out), the remaining
-// refusals - and only then the effects, which the two functions above continue: the device, the shadow map and the G-buffer made
-// real, the tiled pass's buffers and its light upload, the depth ranges consumed, the launches.  A refused call leaves no trace.
-int vr_light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                  const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, hipEvent_t* stop)
+// Every lighting pass: the five exported entry points below, and vr_frame_submit.  One order for all of them, in two halves.
+// vr_light_check: every refusal of an argument, the rank's tables (a lookup that at most fills the context's cache; needed to
+// size-check hdr_out; the pointer is not kept), the remaining refusals - it fills *c and, for a tiled pass, stages the list in
+// ctx->h_lights, which nothing but this unit reads.  vr_light_queue: only then the effects, which the two functions above
+// continue: the device, the shadow map and the G-buffer made real, the tiled pass's buffers and its light upload, the depth
+// ranges consumed, the launches.  A refused call leaves no trace.  The entry points call the halves back to back;
+// vr_frame_submit checks in front of its tile pass and queues behind it.
+int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                   const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall* call)
 {
-    *stop = nullptr;
     const bool tiled = entry != LIGHT_STREAM;
     if (entry == LIGHT_TILED) shadow = nullptr;               // (vr_deferred_light_tiled has no shadow term: a binding that comes with it is ignored)
     VR_REQUIRE(ctx && view && gb && hdr && amb_top && amb_bottom, "NULL argument");
@@ -838,7 +837,8 @@ int vr_light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbu
         VR_REQUIRE(shadow->shadow_map->ctx->device == ctx->device, "shadow map lives on another device");
     }
     VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0, "view viewport must cover the G-buffer");
-    LightCall c{};
+    LightCall& c = *call;
+    c = LightCall{};
     LightPlanIn& in = c.in;       // extra: spot or spherical lights in the list; cone (LIGHT_TILED_EX): spot lights whose cone is culled
     if (!tiled) { const int rc = vr_deferred_make_args(view, gb->w, gb->h, lights, num_lights, amb_top, amb_bottom, &c.a, &in.extra); if (rc) return rc; }
     else {
@@ -852,43 +852,63 @@ int vr_light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbu
             if (d.type != VR_LIGHT_DIRECTIONAL) c.a.exact_pos = 1;
         }
     }
-    if (part) { const int rc = vr_partition_tables(ctx, gb->w, gb->h, part, &c.pt); if (rc) return rc; }
-    VR_REQUIRE(!c.pt || (size_t)c.pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= hdr->capacity_bytes, "hdr_out is smaller than vr_partition_packed_bytes()");
-    VR_REQUIRE(c.pt || (size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
-    in.entry = entry; in.packed = c.pt != nullptr; in.num_owned = c.pt ? c.pt->num_owned : 0;      // a partition (even of one rank) selects the packed tile-major output
+    const PartTables* pt = nullptr;
+    if (part) { const int rc = vr_partition_tables(ctx, gb->w, gb->h, part, &pt); if (rc) return rc; }
+    VR_REQUIRE(!pt || (size_t)pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= hdr->capacity_bytes, "hdr_out is smaller than vr_partition_packed_bytes()");
+    VR_REQUIRE(pt || (size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes, "hdr_out is smaller than the frame");
+    in.entry = entry; in.packed = pt != nullptr; in.num_owned = pt ? pt->num_owned : 0;      // a partition (even of one rank) selects the packed tile-major output
     in.width_mult4 = gb->w % 4 == 0; in.shadow = shadow != nullptr; in.num_lights = num_lights; in.w = gb->w; in.h = gb->h;
     VR_REQUIRE(light_width_ok(in), tiled ? "the tiled pass needs a frame width that is a multiple of 4" : "partitioned frames need a width that is a multiple of 4");
-    // ---- nothing refuses an argument from here on
-    VR_HIP(hipSetDevice(ctx->device));
     if (in.packed) c.a.tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
-    if (shadow) {                                             // the map made real (a pending clear is written), the kernels' constants
+    if (shadow) {                                             // the kernels' constants (the map itself: vr_light_queue)
         ShadowArgs& sh = c.sh;
         for (int i = 0; i < 16; i++) sh.w2c[i] = shadow->light_view->world_to_clip[i];
-        { const int rc = vr_gbuffer_materialise(shadow->shadow_map, ctx->stream); if (rc) return rc; }
-        sh.depth = shadow->shadow_map->depth; sh.res = shadow->shadow_map->w; sh.light_index = shadow->light_index;
+        sh.res = shadow->shadow_map->w; sh.light_index = shadow->light_index;
         sh.bias = shadow->depth_bias; sh.out_of_bounds = lights[shadow->light_index].out_of_bounds_shadow;
     }
-    return tiled ? deferred_light_tiled(ctx, gb, hdr, part, c, stop) : deferred_light(ctx, gb, hdr, c, stop);
+    return VR_OK;
+}
+
+// ---- nothing refuses an argument from here on.  The arguments are those vr_light_check took; *stop = the stop event the
+// pass's own launch was stamped with (NULL: not stamped, or nothing was launched).
+int vr_light_queue(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall& c, hipEvent_t* stop)
+{
+    *stop = nullptr;
+    VR_HIP(hipSetDevice(ctx->device));
+    if (part) { const int rc = vr_partition_tables(ctx, gb->w, gb->h, part, &c.pt); if (rc) return rc; }      // (a cache hit)
+    if (c.in.shadow) {                                        // the map made real (a pending clear is written)
+        { const int rc = vr_gbuffer_materialise(shadow->shadow_map, ctx->stream); if (rc) return rc; }
+        c.sh.depth = shadow->shadow_map->depth;
+    }
+    return c.in.entry != LIGHT_STREAM ? deferred_light_tiled(ctx, gb, hdr, part, c, stop) : deferred_light(ctx, gb, hdr, c, stop);
+}
+
+static int light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                      const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
+{
+    LightCall c;
+    hipEvent_t stop;
+    const int rc = vr_light_check(ctx, entry, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &c);
+    return rc ? rc : vr_light_queue(ctx, gb, hdr, part, shadow, c, &stop);
 }
 
 extern "C" VR_API int vr_deferred_light(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
                                          const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part)
-{ hipEvent_t stop; return vr_light_pass(ctx, LIGHT_STREAM, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, &stop); }
+{ return light_pass(ctx, LIGHT_STREAM, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr); }
 // DeferredLightingPass::Render with DirectionalLight::shadowMap set (Renderer.cpp:336, 427)
 extern "C" VR_API int vr_deferred_light_shadowed(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights, const float amb_top[3],
                                                   const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
 {
     VR_REQUIRE(shadow, "shadow binding is NULL (use vr_deferred_light)");
-    hipEvent_t stop;
-    return vr_light_pass(ctx, LIGHT_STREAM, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &stop);
+    return light_pass(ctx, LIGHT_STREAM, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow);
 }
 extern "C" VR_API int vr_deferred_light_tiled(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
                                                const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part)
-{ hipEvent_t stop; return vr_light_pass(ctx, LIGHT_TILED, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr, &stop); }
+{ return light_pass(ctx, LIGHT_TILED, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, nullptr); }
 // vr_deferred_light_tiled for every light type, with the sun's shadow term (shadow may be NULL)
 extern "C" VR_API int vr_deferred_light_tiled_ex(vr_context* ctx, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights, const float amb_top[3],
                                                   const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
-{ hipEvent_t stop; return vr_light_pass(ctx, LIGHT_TILED_EX, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &stop); }
+{ return light_pass(ctx, LIGHT_TILED_EX, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow); }
 
 // Test helper: the list the last tiled pass of this context left for light tile (tile_x, tile_y); synchronises.
 extern "C" VR_API int vr_debug_tile_light_list(vr_context* ctx, int32_t tile_x, int32_t tile_y, uint32_t* out, int32_t capacity, int32_t* out_count)
@@ -941,10 +961,17 @@ __global__ __launch_bounds__(256) void k_detile(const uint32_t* __restrict__ gat
     frame[i] = make_uint4(d0, d1 & 0xffffu, (d1 >> 16) | (d2 << 16), d2 >> 16);
 }
 
-extern "C" VR_API int vr_frame_detile(vr_context* ctx, const void* gathered, int32_t world, vr_image* frame)
+// the de-tile's refusals, apart from its launch: vr_frame_allgather asks in front of its collective
+int vr_frame_detile_check(vr_context* ctx, const void* gathered, int32_t world, vr_image* frame)
 {
     VR_REQUIRE(ctx && gathered && frame, "NULL argument");
     VR_REQUIRE(frame->w % 2 == 0 && world >= 1, "frame width must be even");
+    return VR_OK;
+}
+
+extern "C" VR_API int vr_frame_detile(vr_context* ctx, const void* gathered, int32_t world, vr_image* frame)
+{
+    { const int rc = vr_frame_detile_check(ctx, gathered, world, frame); if (rc) return rc; }
     VR_HIP(hipSetDevice(ctx->device));
     const PartTables* pt = nullptr;
     { int rc = vr_partition_slot_tables(ctx, frame->w, frame->h, world, &pt); if (rc) return rc; }

@@ -215,6 +215,14 @@ struct ShadowArgs {
     float bias, out_of_bounds;
 };
 
+// A lighting pass between its two halves (vr_deferred.hip): vr_light_check fills it behind every refusal - the call's facts for
+// the plan, the kernels' constants - and vr_light_queue adds what only exists then: the rank's tables, the shadow map's plane.
+struct LightCall { LightPlanIn in; DeferredArgs a; ShadowArgs sh; const PartTables* pt; };
+int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
+                   const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
+                   const vr_shadow_binding* shadow, LightCall* call);
+int vr_light_queue(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall& c, hipEvent_t* stop);
+
 __device__ __forceinline__ float shadow_factor(const DeferredArgs& a, const ShadowArgs& s, int px, int py, float depth)
 {
     const float cx = ((float)px + 0.5f) * a.sx + -1.0f, cy = ((float)py + 0.5f) * a.sy + 1.0f;

@@ -7,7 +7,12 @@
 // The cross-stream order between the lighting pass (terrain's context) and a tone-map stage on another context's stream is
 // the library's here: the stage waits for the lighting pass's stop event, and an image remembers who still reads it, so a
 // later lighting pass into the same vr_image waits for that reader (a host that rotates two images keeps both streams busy).
-#include "vr_internal.h"
+// The frame refuses before it queues anything: the lighting pass's arguments (vr_light_check), the tone-map stage's - sizes
+// and capacities included -, the exchange's, the LDR de-tile's width and the RCCL entry points (vr_tonemap_stage, queue = false)
+// are all looked at in front of the tile pass.  A refused frame leaves the G-buffer, its pending clear, HdrColor, the bins and
+// the adapted luminance as they were, and a rank of an N-GPU run never enters one collective and skips the next.  What is left
+// behind the tile pass is what that pass itself refuses (its own arguments) and what a HIP call reports.
+#include "vr_deferred_dev.h"
 
 extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_frame_desc* f)
 {
@@ -17,6 +22,19 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     VR_REQUIRE(gb->ctx == ctx && f->hdr_out->ctx->device == ctx->device, "G-buffer / image belong to another context");
     vr_image* hdr = f->hdr_out;
     int rc;
+    // tiled: 2 = every light type and the shadow binding (vr_deferred_light_tiled_ex); any other non-zero value = 1 =
+    // vr_deferred_light_tiled, which has no shadow term: the binding is ignored
+    const LightEntry entry = f->tiled == 2 ? LIGHT_TILED_EX : f->tiled ? LIGHT_TILED : LIGHT_STREAM;
+    LightCall lc;
+    if ((rc = vr_light_check(ctx, entry, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow, &lc))) return rc;
+    // ToneMappingPass::SimpleRender [+ the bins' all-reduce] on the tone mapper's own context
+    TmStageCall tmc{};
+    if (f->tonemap) {
+        tmc.steps = TM_RESET | TM_HISTOGRAM | (f->nccl_comm ? TM_ALLREDUCE : 0u) | TM_EXPOSURE | TM_RENDER;
+        tmc.p = f->tonemap_params; tmc.frame_time = f->frame_time_seconds; tmc.hdr = hdr; tmc.w = gb->w; tmc.h = gb->h;
+        tmc.ldr = f->ldr_out; tmc.ldr_capacity = f->ldr_capacity; tmc.part = f->part; tmc.comm = f->nccl_comm; tmc.frame = f; tmc.frame_device = ctx->device;
+        if ((rc = vr_tonemap_stage(f->tonemap, tmc, false))) return rc;
+    }
     // TerrainPass::Render, then the chains of the next frames under its tile pass (a frame already prepared is a no-op)
     // (a sticky code - VR_ERR_TOO_MANY_INSTANCES / VR_ERR_OVERFLOW of an EARLIER frame - does not stop this one: it is returned at the end)
     // Under VR_OPT_FRAME_FUSION the tile pass shades as well where its G-buffer-keeping flavour applies (the plain streaming
@@ -39,36 +57,23 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     hipEvent_t written_stop = fused_stop;
     if (!fused) {
         if ((rc = order_image_writer_begins(hdr->ord, ops, ctx->stream))) return rc;
-        // tiled: 2 = every light type and the shadow binding (vr_deferred_light_tiled_ex); any other non-zero value = 1 =
-        // vr_deferred_light_tiled, which has no shadow term: the binding is ignored
-        const LightEntry entry = f->tiled == 2 ? LIGHT_TILED_EX : f->tiled ? LIGHT_TILED : LIGHT_STREAM;
-        if ((rc = vr_light_pass(ctx, entry, f->view, gb, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, f->part, f->shadow, &written_stop))) return rc;
+        if ((rc = vr_light_queue(ctx, gb, hdr, f->part, f->shadow, lc, &written_stop))) return rc;
     }
     if (!f->tonemap) return earlier;
 
-    // ToneMappingPass::SimpleRender on the tone mapper's own context (another stream: it runs under the next frame's rendering)
-    VR_REQUIRE(f->tonemap_params && f->ldr_out, "tone-map stage: params / ldr_out missing");
+    // the tone-map stage (another stream: it runs under the next frame's rendering)
     vr_context* tc = vr_tonemap_context(f->tonemap);
-    VR_REQUIRE(tc->device == ctx->device, "tone mapper lives on another device");
     const bool cross = tc->stream != ctx->stream;
     if (cross) {
         // behind the pass that wrote the image: its dispatch-stamped stop event when there is one, else an explicit record
         if (!written_stop && !hdr->ord.written.own) VR_HIP(hipEventCreateWithFlags(&hdr->ord.written.own, hipEventDisableTiming));
         if ((rc = order_image_written(hdr->ord, ops, ctx->stream, tc->stream, written_stop, ctx->ev_epoch))) return rc;
     }
-    const int w = gb->w, h = gb->h;
-    if ((rc = vr_tonemap_reset_histogram(f->tonemap))) return rc;
-    if ((rc = vr_tonemap_add_frame_to_histogram(f->tonemap, f->tonemap_params, hdr, w, h, f->part))) return rc;
-    if (f->nccl_comm && (rc = vr_tonemap_allreduce_histogram(f->tonemap, f->nccl_comm))) return rc;
-    if ((rc = vr_tonemap_compute_exposure(f->tonemap, f->tonemap_params, f->frame_time_seconds))) return rc;
-    if ((rc = vr_tonemap_render(f->tonemap, f->tonemap_params, hdr, w, h, f->ldr_out, f->ldr_capacity, f->part))) return rc;
+    if ((rc = vr_tonemap_stage(f->tonemap, tmc, true))) return rc;
     if (cross) {
         if (!hdr->ord.read_done.ev) VR_HIP(hipEventCreateWithFlags(&hdr->ord.read_done.ev, hipEventDisableTiming));
         if ((rc = order_image_reader_done(hdr->ord, ops, tc->stream))) return rc;
     }
-    if (f->nccl_comm) {
-        VR_REQUIRE(f->part && f->gathered && f->ldr_frame, "exchange: partition / gathered / ldr_frame missing");
-        if ((rc = vr_frame_allgather_ldr(tc, f->nccl_comm, f->ldr_out, f->gathered, f->part->world_size, w, h, f->ldr_frame))) return rc;
-    }
+    if (f->nccl_comm && (rc = vr_frame_allgather_ldr(tc, f->nccl_comm, f->ldr_out, f->gathered, f->part->world_size, gb->w, gb->h, f->ldr_frame))) return rc;
     return earlier;
 }

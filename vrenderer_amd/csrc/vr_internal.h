@@ -16,6 +16,7 @@
 #include "vr_light_plan.h"
 #include "vr_order.h"
 #include "vr_scratch.h"
+#include "vr_tonemap_plan.h"
 
 // ---- error plumbing -------------------------------------------------------------
 void vr_set_error(const char* fmt, ...);
@@ -419,11 +420,22 @@ int vr_terrain_frame_scratch(vr_terrain* t, bool report, const std::function<int
 int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
                            int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
                            bool* fused, hipEvent_t* fused_stop);
-// the lighting passes as vr_frame_submit queues them (vr_deferred.hip): the exported entry point that `entry` names (shadow may be
-// NULL; LIGHT_TILED ignores it), and *stop = the stop event its own launch was stamped with (NULL: not stamped, or nothing was launched)
-int vr_light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
-                  const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
-                  const vr_shadow_binding* shadow, hipEvent_t* stop);
+// the lighting passes as vr_frame_submit queues them: vr_light_check, vr_light_queue (vr_deferred_dev.h)
+// The tone-map stage (vr_tonemap.hip): the steps of `steps` (TmStep, vr_tonemap_plan.h) in their order - reset, histogram, all-reduce
+// over `comm`, exposure, render - behind every refusal of every one of them; queue = false: the refusals alone.  `frame`:
+// vr_frame_submit's descriptor, whose stage also answers for the exchange that follows it (frame_device: the terrain's).
+struct TmStageCall {
+    unsigned steps;
+    const vr_tonemap_params* p; float frame_time;
+    vr_image* hdr; int w, h; void* ldr; size_t ldr_capacity; const vr_partition* part;
+    void* comm;
+    const vr_frame_desc* frame; int frame_device;
+};
+int vr_tonemap_stage(vr_tonemap* tm, const TmStageCall& c, bool queue);
+int vr_rccl_load();       // the RCCL entry points, resolved at first use (vr_comm.hip); VR_OK, or the refusal that names what is missing
+// the de-tile kernels' refusals, for the wrappers that put a collective in front of them (vr_comm.hip)
+int vr_frame_detile_check(vr_context* ctx, const void* gathered, int32_t world, vr_image* frame);
+int vr_frame_detile_ldr_check(vr_context* ctx, const void* gathered, int32_t world, int32_t w, int32_t h, void* frame);
 // tables of (w, h, part); part == NULL is the whole frame as rank 0 of 1
 int vr_partition_tables(vr_context* ctx, int w, int h, const vr_partition* part, const PartTables** out);
 // any cached table set of (w, h, world): the slot table does not depend on the rank

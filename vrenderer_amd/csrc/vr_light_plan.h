@@ -1,6 +1,6 @@
 // The lighting pass's host decisions as one pure function: which instantiation of the shading kernel and of k_light_cull runs,
 // over which grids, how the light lists are laid out and whether the G-buffer's depth ranges are taken.  Plain C++17: no HIP, no
-// library types - a CPU program enumerates every input (tests/host/light_plan_check.cpp).  vr_light_pass (vr_deferred.hip) gathers
+// library types - a CPU program enumerates every input (tests/host/light_plan_check.cpp).  vr_light_check (vr_deferred.hip) gathers
 // the facts behind its refusals; deferred_light and deferred_light_tiled ask light_plan() and launch what it names.
 //
 // The streaming pass: k_deferred, which asks first what it need not read, where the plane-state tracking knows something (hinted),

@@ -13,6 +13,7 @@
 // polynomials, so histogram bins and LDR bytes are bit-exact against the oracle.
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
+#include "vr_tonemap_plan.h"
 
 #include <float.h>
 #include <math.h>
@@ -32,17 +33,6 @@ struct TmArgs {
     float exposure_scale, wp_inv2, min_adapted;
     uint32_t q;                              // bin weight quantum of one pixel (tm_bin_quantum)
 };
-
-// Q = 64 >> s, s the smallest shift with Q * pixels <= 2^32 - 1 (pixels of the whole frame, also for a rank's share): no
-// bin, LDS copy or per-workgroup sum can exceed Q * pixels, so the 32-bit bins never wrap, summed over the ranks included.
-// 0 = more than 2^32 - 1 pixels.
-static uint32_t tm_bin_quantum(int w, int h)
-{
-    const uint64_t n = (uint64_t)w * (uint64_t)h;
-    uint32_t q = 64u;
-    while (q > 0u && (uint64_t)q * n > 0xffffffffull) q >>= 1;
-    return q;
-}
 
 __device__ __forceinline__ float tm_luminance(float r, float g, float b) { return (r * 0.2126f + g * 0.7152f) + b * 0.0722f; }
 
@@ -378,43 +368,90 @@ extern "C" VR_API int vr_tonemap_reset_histogram(vr_tonemap* tm)
     return VR_OK;
 }
 
-static int check_params(const vr_tonemap_params* p)
+// ---- the stage ------------------------------------------------------------------------------
+// What runs, over which grids, and whether the call goes ahead at all are tm_plan()'s and tm_refusal()'s decisions
+// (vr_tonemap_plan.h); the tables give the two quad families their kernels (TM_SCALAR's have an argument list of their own).
+static_assert(kTmOwnerTile == VR_OWNER_TILE && kTmHistBlocks == kHistBlocks, "vr_tonemap_plan.h");
+static decltype(&k_tm_histogram<false>) const kHistKernels[] = { k_tm_histogram<true>, k_tm_histogram<false> };      // TM_PACKED, TM_ROW
+static decltype(&k_tonemap<false>) const kMapKernels[] = { k_tonemap<true>, k_tonemap<false> };
+
+// log-luminance -> [0, 1]
+static void exposure_constants(const vr_tonemap_params* p, float* scale, float* bias)
 {
-    VR_REQUIRE(p, "NULL argument");
-    VR_REQUIRE(p->max_log_luminance > p->min_log_luminance, "max_log_luminance must exceed min_log_luminance");
-    VR_REQUIRE(p->white_point > 0.0f, "white_point must be positive");
-    VR_REQUIRE(p->min_adapted_luminance > 0.0f && p->max_adapted_luminance >= p->min_adapted_luminance, "bad adapted-luminance range");
-    VR_REQUIRE(p->histogram_low_percentile >= 0.0f && p->histogram_high_percentile <= 1.0f
-               && p->histogram_high_percentile >= p->histogram_low_percentile, "bad histogram percentiles");
-    return VR_OK;
+    *scale = 1.0f / (p->max_log_luminance - p->min_log_luminance);
+    *bias = (0.0f - p->min_log_luminance) * *scale;
 }
 
-static TmArgs make_args(const vr_tonemap_params* p, int w, int h)
+// Every tone-map call: the four exported entry points below, and vr_frame_submit - which asks twice, with queue = false in
+// front of its tile pass and for the work behind its lighting pass.  One order: the facts (the rank's tables and the RCCL entry
+// points are lookups that at most fill a cache), every refusal of every step asked for, and only then the device, the memset,
+// the launches and the collective.  A refused call leaves the bins and the adapted luminance as they were.
+int vr_tonemap_stage(vr_tonemap* tm, const TmStageCall& c, bool queue)
 {
-    TmArgs a;
-    a.w = w; a.h = h; a.tiles_x = (w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
-    a.scale = 1.0f / (p->max_log_luminance - p->min_log_luminance);
-    a.bias = (0.0f - p->min_log_luminance) * a.scale;
+    const vr_tonemap_params* p = c.p;
+    vr_image* hdr = c.hdr;
+    const bool source = (c.steps & (TM_HISTOGRAM | TM_RENDER)) != 0;
+    TmPlanIn in{};
+    in.steps = c.steps; in.have_tm = tm != nullptr; in.have_params = p != nullptr; in.have_hdr = hdr != nullptr; in.have_ldr = c.ldr != nullptr;
+    if (p) {
+        in.min_log = p->min_log_luminance; in.max_log = p->max_log_luminance; in.white_point = p->white_point;
+        in.min_adapted = p->min_adapted_luminance; in.max_adapted = p->max_adapted_luminance;
+        in.low_percentile = p->histogram_low_percentile; in.high_percentile = p->histogram_high_percentile;
+    }
+    in.device_same = tm && hdr && hdr->ctx->device == tm->ctx->device;
+    in.w = c.w; in.h = c.h; in.packed = c.part != nullptr;
+    in.hdr_capacity = hdr ? hdr->capacity_bytes : 0; in.ldr_capacity = c.ldr_capacity;
+    if (c.frame) {
+        in.frame = true; in.frame_device_same = tm && tm->ctx->device == c.frame_device;
+        in.have_comm = c.comm != nullptr; in.have_part = c.part != nullptr; in.have_gathered = c.frame->gathered != nullptr; in.have_ldr_frame = c.frame->ldr_frame != nullptr;
+    }
+    // (the tables last: of two failed lookups tm_refusal() names this one, and its message is the one that stands)
+    const int rccl_rc = (c.steps & TM_ALLREDUCE) ? vr_rccl_load() : VR_OK;
+    const PartTables* pt = nullptr;
+    int tables_rc = VR_OK;
+    if (tm && source && c.part && c.w > 0 && c.h > 0 && (tables_rc = vr_partition_tables(tm->ctx, c.w, c.h, c.part, &pt)) == VR_OK) { in.num_owned = pt->num_owned; in.max_owned = pt->max_owned; }
+    in.rccl_missing = rccl_rc != VR_OK; in.tables_failed = tables_rc != VR_OK;
+    const TmRefusal refusal = tm_refusal(in);
+    if (refusal == TM_NO_TABLES) return tables_rc;
+    if (refusal == TM_NO_RCCL) return rccl_rc;
+    VR_REQUIRE(refusal == TM_ACCEPTED, tm_refusal_text(refusal));
+    // ---- nothing refuses an argument from here on
+    if (!queue) return VR_OK;
+    vr_context* ctx = tm->ctx;
+    VR_HIP(hipSetDevice(ctx->device));
+    const TmPlan plan = tm_plan(in);
+    TmArgs a{};
+    a.w = c.w; a.h = c.h; a.tiles_x = (c.w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
+    exposure_constants(p, &a.scale, &a.bias);
     a.exposure_scale = exp2f(p->exposure_bias);
     a.wp_inv2 = 1.0f / (p->white_point * p->white_point);
     a.min_adapted = p->min_adapted_luminance;
-    a.q = tm_bin_quantum(w, h);
-    return a;
-}
-
-// size checks of a (possibly packed) HDR source; returns the number of 256-lane blocks of the vector path
-static int source_blocks(vr_context* ctx, vr_image* hdr, int w, int h, const vr_partition* part, size_t* blocks, const PartTables** tables)
-{
-    VR_REQUIRE(w > 0 && h > 0, "bad frame size");
-    *tables = nullptr;
-    if (part) {
-        int rc = vr_partition_tables(ctx, w, h, part, tables);
-        if (rc) return rc;
-        VR_REQUIRE((size_t)(*tables)->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 6 <= hdr->capacity_bytes, "hdr is smaller than vr_partition_packed_bytes()");
-        *blocks = (size_t)(*tables)->num_owned * 16;
-    } else {
-        VR_REQUIRE((size_t)w * h * 8 <= hdr->capacity_bytes, "hdr is smaller than the frame");
-        *blocks = ((size_t)w * h / 4 + 255) / 256;
+    a.q = plan.q;
+    const int32_t* owned = pt ? pt->d_owned_tiles : nullptr;
+    if (c.steps & TM_RESET) VR_HIP(hipMemsetAsync(tm->d_hist, 0, sizeof(uint32_t) * VR_TONEMAP_BINS, ctx->stream));
+    if (c.steps & TM_HISTOGRAM) {
+        VrKernelScope ks(ctx, VR_K_TM_HISTOGRAM);
+        if (plan.launch && plan.family == TM_SCALAR) hipLaunchKernelGGL(k_tm_histogram_scalar, dim3(plan.hist_grid), dim3(256), 0, ctx->stream, a, (const uint2*)hdr->data, tm->d_hist);
+        else if (plan.launch) hipLaunchKernelGGL(kHistKernels[plan.family], dim3(plan.hist_grid), dim3(256), 0, ctx->stream, a, (const void*)hdr->data, owned, plan.blocks, tm->d_hist);
+        VR_HIP(hipGetLastError());
+    }
+    if (c.steps & TM_ALLREDUCE) { const int rc = vr_tonemap_allreduce_histogram(tm, c.comm); if (rc) return rc; }
+    if (c.steps & TM_EXPOSURE) {
+        const float k_up = (float)(1.0 - exp(-(double)c.frame_time * (double)p->eye_adaptation_speed_up));
+        const float k_down = (float)(1.0 - exp(-(double)c.frame_time * (double)p->eye_adaptation_speed_down));
+        VrKernelScope ks(ctx, VR_K_TM_EXPOSURE);
+        hipLaunchKernelGGL(k_tm_exposure, dim3(1), dim3(256), 0, ctx->stream, (const uint32_t*)tm->d_hist, tm->d_exposure, a.scale, a.bias,
+                           p->histogram_low_percentile, p->histogram_high_percentile, p->min_log_luminance, p->min_adapted_luminance,
+                           p->max_adapted_luminance, k_up, k_down, p->eye_adaptation_speed_up > 0.0f ? 1 : 0, p->eye_adaptation_speed_down > 0.0f ? 1 : 0);
+        VR_HIP(hipGetLastError());
+    }
+    if (c.steps & TM_RENDER) {
+        VrKernelScope ks(ctx, VR_K_TONEMAP);
+        if (plan.launch && plan.family == TM_SCALAR) hipLaunchKernelGGL(k_tonemap_scalar, dim3(plan.map_grid), dim3(256), 0, ctx->stream, a, (const uint2*)hdr->data,
+                                                                        (const float*)tm->d_exposure, (uint32_t*)c.ldr, ctx->d_srgb_thr, ctx->d_enc_tab);
+        else if (plan.launch) hipLaunchKernelGGL(kMapKernels[plan.family], dim3(plan.map_grid), dim3(256), 0, ctx->stream, a, (const void*)hdr->data, owned,
+                                (const float*)tm->d_exposure, c.ldr, ctx->d_srgb_thr, ctx->d_enc_tab);
+        VR_HIP(hipGetLastError());
     }
     return VR_OK;
 }
@@ -422,49 +459,16 @@ static int source_blocks(vr_context* ctx, vr_image* hdr, int w, int h, const vr_
 extern "C" VR_API int vr_tonemap_add_frame_to_histogram(vr_tonemap* tm, const vr_tonemap_params* p, vr_image* hdr, int32_t w, int32_t h,
                                                          const vr_partition* part)
 {
-    VR_REQUIRE(tm && hdr, "NULL argument");
-    int rc = check_params(p); if (rc) return rc;
-    vr_context* ctx = tm->ctx;
-    VR_REQUIRE(hdr->ctx->device == ctx->device, "image and tone-mapping pass live on different devices");
-    VR_HIP(hipSetDevice(ctx->device));
-    size_t blocks = 0;
-    const PartTables* pt = nullptr;
-    if ((rc = source_blocks(ctx, hdr, w, h, part, &blocks, &pt))) return rc;
-    const TmArgs a = make_args(p, w, h);
-    VR_REQUIRE(a.q != 0u, "frame has more than 2^32 - 1 pixels: the 32-bit histogram cannot count it");
-    VrKernelScope ks(ctx, VR_K_TM_HISTOGRAM);
-    if (part) {
-        if (blocks > 0)
-            hipLaunchKernelGGL(k_tm_histogram<true>, dim3((unsigned)(blocks < (size_t)kHistBlocks ? blocks : (size_t)kHistBlocks)), dim3(256), 0, ctx->stream, a, (const void*)hdr->data,
-                               pt->d_owned_tiles, blocks, tm->d_hist);
-    } else if (w % 4 == 0) {
-        hipLaunchKernelGGL(k_tm_histogram<false>, dim3((unsigned)(blocks < (size_t)kHistBlocks ? blocks : (size_t)kHistBlocks)), dim3(256), 0, ctx->stream, a, (const void*)hdr->data,
-                           (const int32_t*)nullptr, blocks, tm->d_hist);
-    } else {
-        const size_t b = ((size_t)w * h + 255) / 256;
-        hipLaunchKernelGGL(k_tm_histogram_scalar, dim3((unsigned)(b < (size_t)kHistBlocks ? b : (size_t)kHistBlocks)), dim3(256), 0, ctx->stream, a, (const uint2*)hdr->data, tm->d_hist);
-    }
-    VR_HIP(hipGetLastError());
-    return VR_OK;
+    TmStageCall c{}; c.steps = TM_HISTOGRAM; c.p = p; c.hdr = hdr; c.w = w; c.h = h; c.part = part;
+    return vr_tonemap_stage(tm, c, true);
 }
 
 extern "C" VR_API void* vr_tonemap_histogram_device_ptr(vr_tonemap* tm) { return tm ? tm->d_hist : nullptr; }
 
 extern "C" VR_API int vr_tonemap_compute_exposure(vr_tonemap* tm, const vr_tonemap_params* p, float frame_time)
 {
-    VR_REQUIRE(tm, "NULL argument");
-    int rc = check_params(p); if (rc) return rc;
-    vr_context* ctx = tm->ctx;
-    VR_HIP(hipSetDevice(ctx->device));
-    const TmArgs a = make_args(p, 4, 4);
-    const float k_up = (float)(1.0 - exp(-(double)frame_time * (double)p->eye_adaptation_speed_up));
-    const float k_down = (float)(1.0 - exp(-(double)frame_time * (double)p->eye_adaptation_speed_down));
-    VrKernelScope ks(ctx, VR_K_TM_EXPOSURE);
-    hipLaunchKernelGGL(k_tm_exposure, dim3(1), dim3(256), 0, ctx->stream, (const uint32_t*)tm->d_hist, tm->d_exposure, a.scale, a.bias,
-                       p->histogram_low_percentile, p->histogram_high_percentile, p->min_log_luminance, p->min_adapted_luminance,
-                       p->max_adapted_luminance, k_up, k_down, p->eye_adaptation_speed_up > 0.0f ? 1 : 0, p->eye_adaptation_speed_down > 0.0f ? 1 : 0);
-    VR_HIP(hipGetLastError());
-    return VR_OK;
+    TmStageCall c{}; c.steps = TM_EXPOSURE; c.p = p; c.frame_time = frame_time;
+    return vr_tonemap_stage(tm, c, true);
 }
 
 extern "C" VR_API size_t vr_partition_packed_bytes_ldr(int32_t w, int32_t h, int32_t world)
@@ -475,45 +479,17 @@ extern "C" VR_API size_t vr_partition_packed_bytes_ldr(int32_t w, int32_t h, int
 extern "C" VR_API int vr_tonemap_render(vr_tonemap* tm, const vr_tonemap_params* p, vr_image* hdr, int32_t w, int32_t h, void* ldr,
                                          size_t ldr_capacity, const vr_partition* part)
 {
-    VR_REQUIRE(tm && hdr && ldr, "NULL argument");
-    int rc = check_params(p); if (rc) return rc;
-    vr_context* ctx = tm->ctx;
-    VR_REQUIRE(hdr->ctx->device == ctx->device, "image and tone-mapping pass live on different devices");
-    VR_HIP(hipSetDevice(ctx->device));
-    size_t blocks = 0;
-    const PartTables* pt = nullptr;
-    if ((rc = source_blocks(ctx, hdr, w, h, part, &blocks, &pt))) return rc;
-    const TmArgs a = make_args(p, w, h);
-    VrKernelScope ks(ctx, VR_K_TONEMAP);
-    if (part) {
-        VR_REQUIRE((size_t)pt->max_owned * VR_OWNER_TILE * VR_OWNER_TILE * 3 <= ldr_capacity, "ldr buffer is smaller than vr_partition_packed_bytes_ldr()");
-        if (blocks > 0)
-            hipLaunchKernelGGL(k_tonemap<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a, (const void*)hdr->data, pt->d_owned_tiles,
-                               (const float*)tm->d_exposure, ldr, ctx->d_srgb_thr, ctx->d_enc_tab);
-    } else {
-        VR_REQUIRE((size_t)w * h * 4 <= ldr_capacity, "ldr buffer is smaller than the frame");
-        if (w % 4 == 0) {
-            hipLaunchKernelGGL(k_tonemap<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a, (const void*)hdr->data, (const int32_t*)nullptr,
-                               (const float*)tm->d_exposure, ldr, ctx->d_srgb_thr, ctx->d_enc_tab);
-        } else {
-            const size_t b = ((size_t)w * h + 255) / 256;
-            hipLaunchKernelGGL(k_tonemap_scalar, dim3((unsigned)b), dim3(256), 0, ctx->stream, a, (const uint2*)hdr->data, (const float*)tm->d_exposure,
-                               (uint32_t*)ldr, ctx->d_srgb_thr, ctx->d_enc_tab);
-        }
-    }
-    VR_HIP(hipGetLastError());
-    return VR_OK;
+    TmStageCall c{}; c.steps = TM_RENDER; c.p = p; c.hdr = hdr; c.w = w; c.h = h; c.ldr = ldr; c.ldr_capacity = ldr_capacity; c.part = part;
+    return vr_tonemap_stage(tm, c, true);
 }
 
 extern "C" VR_API int vr_tonemap_simple_render(vr_tonemap* tm, const vr_tonemap_params* p, float frame_time, vr_image* hdr, void* ldr,
                                                 size_t ldr_capacity)
 {
     VR_REQUIRE(tm && hdr, "NULL argument");
-    int rc;
-    if ((rc = vr_tonemap_reset_histogram(tm))) return rc;
-    if ((rc = vr_tonemap_add_frame_to_histogram(tm, p, hdr, hdr->w, hdr->h, nullptr))) return rc;
-    if ((rc = vr_tonemap_compute_exposure(tm, p, frame_time))) return rc;
-    return vr_tonemap_render(tm, p, hdr, hdr->w, hdr->h, ldr, ldr_capacity, nullptr);
+    TmStageCall c{}; c.steps = TM_RESET | TM_HISTOGRAM | TM_EXPOSURE | TM_RENDER; c.p = p; c.frame_time = frame_time;
+    c.hdr = hdr; c.w = hdr->w; c.h = hdr->h; c.ldr = ldr; c.ldr_capacity = ldr_capacity;
+    return vr_tonemap_stage(tm, c, true);
 }
 
 extern "C" VR_API int vr_tonemap_download(vr_tonemap* tm, uint32_t histogram[VR_TONEMAP_BINS], float* adapted)
@@ -526,10 +502,17 @@ extern "C" VR_API int vr_tonemap_download(vr_tonemap* tm, uint32_t histogram[VR_
     return VR_OK;
 }
 
-extern "C" VR_API int vr_frame_detile_ldr(vr_context* ctx, const void* gathered, int32_t world, int32_t w, int32_t h, void* frame)
+// the de-tile's refusals, apart from its launch: vr_frame_allgather_ldr asks in front of its collective
+int vr_frame_detile_ldr_check(vr_context* ctx, const void* gathered, int32_t world, int32_t w, int32_t h, void* frame)
 {
     VR_REQUIRE(ctx && gathered && frame, "NULL argument");
     VR_REQUIRE(w % 4 == 0 && w > 0 && h > 0 && world >= 1, "frame width must be a multiple of 4");
+    return VR_OK;
+}
+
+extern "C" VR_API int vr_frame_detile_ldr(vr_context* ctx, const void* gathered, int32_t world, int32_t w, int32_t h, void* frame)
+{
+    { const int rc = vr_frame_detile_ldr_check(ctx, gathered, world, w, h, frame); if (rc) return rc; }
     VR_HIP(hipSetDevice(ctx->device));
     const PartTables* pt = nullptr;
     { int rc = vr_partition_slot_tables(ctx, w, h, world, &pt); if (rc) return rc; }
