@@ -251,6 +251,35 @@ VR_API int  vr_terrain_download_mip(vr_terrain* t, int which, int level, void* h
  * kernels are untimed, as at create time. */
 VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32_t y, int32_t w, int32_t h,
                            const void* texels, size_t row_pitch_bytes, int device_pointer);
+/* A brush stroke - one op and up to VR_MAX_BRUSH_DABS dabs, applied in list order - on level 0 of the heightmap (RAISE, FLATTEN,
+ * SMOOTH) or the albedo (PAINT), computed on the device from the map as it is there, followed by the refresh vr_terrain_edit does:
+ * afterwards the terrain is the one vr_terrain_create builds from the stroked maps.  A dab is a disc of `radius` world units
+ * about (x, z) - the world spans [-world_size/2, world_size/2]^2, as for the queries - with weight 1 out to hardness * radius and
+ * a smoothstep fall-off to 0 at the rim.  Each texel's value (0 .. 255, the stored byte; four for the albedo) is carried in fp32
+ * through the dabs that cover it, with a = weight * strength:
+ *   VR_BRUSH_RAISE    value += weight * strength      strength signed, in heightmap steps (1/255 of max_height), |strength| <= 255
+ *   VR_BRUSH_FLATTEN  value += a * (target - value)   strength = opacity in [0, 1], target in [0, 255]
+ *   VR_BRUSH_SMOOTH   value += a * (mean - value)     mean of the 3 x 3 clamped neighbourhood in the map BEFORE the stroke
+ *   VR_BRUSH_PAINT    per channel c of channel_mask (bit c = byte c of the SRGBA8 texel, alpha included):
+ *                     value_c += a * (color[c] - value_c), color in [0, 255] in the stored encoding
+ * clamped to [0, 255] after every dab and rounded to the nearest byte once, after the last: sub-step strengths accumulate inside
+ * a stroke, and a stroke split over two calls is two roundings.  A texel no dab covers keeps its byte.  The arithmetic is defined
+ * bit for bit in vrenderer_amd/csrc/vr_brush.h.
+ * out_rect (may be NULL) receives {x, y, w, h} of the level-0 rectangle the call treated as dirty - the hull of the dabs'
+ * conservative spans, clipped to the map; no texel outside it changes - or {0, 0, 0, 0} when that is empty.
+ * `dabs` is host memory and may be reused as soon as the call returns.  The call is stream-ordered on the context's stream, like
+ * a device-pointer edit, and synchronises nothing: the host waits only where the previous stroke of this terrain has not been
+ * consumed yet.  n == 0, or a stroke whose dabs all miss the map, is VR_OK and launches nothing.
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the terrain untouched: NULL t or stroke, NULL dabs
+ * with n > 0; n > VR_MAX_BRUSH_DABS; an unknown op; a NaN or an infinity in target, color or a dab; radius <= 0; hardness outside
+ * [0, 1); a strength outside its op's range; FLATTEN with target outside [0, 255]; PAINT with a color outside [0, 255] or a
+ * channel_mask of 0 or above 15.  The memory a stroke needs is reserved before anything is launched (VR_ERR_OUT_OF_MEMORY leaves
+ * the terrain as it was).  Timing: as for vr_terrain_edit; the brush kernel itself is untimed. */
+#define VR_MAX_BRUSH_DABS 4096
+enum { VR_BRUSH_RAISE = 0, VR_BRUSH_FLATTEN = 1, VR_BRUSH_SMOOTH = 2, VR_BRUSH_PAINT = 3 };
+typedef struct vr_brush_dab    { float x, z, radius, hardness, strength; float reserved[3]; } vr_brush_dab;      /* 32 B */
+typedef struct vr_brush_stroke { int32_t op; uint32_t channel_mask; float target; float color[4]; int32_t reserved; } vr_brush_stroke; /* 32 B */
+VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* stroke, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
 
 /* QuadTree::SetHeight for every node (QuadTree.cpp:164-208) as a device reduction over the heightmap,
  * and m_HeightLoaded (QuadTree.h:70).  The reference wrote this and left its launch commented out

@@ -209,6 +209,13 @@ namespace vRenderer
         {
             return Check(vr_terrain_edit(m_Terrain, which, x, y, w, h, texels, rowPitchBytes, devicePointer ? 1 : 0), "vr_terrain_edit");
         }
+        // vr_terrain_brush: one stroke - stroke.op and n dabs in order - on level 0 of the heightmap or (VR_BRUSH_PAINT) the albedo,
+        // computed on the device; stream-ordered, nothing is synchronised, and `dabs` is free again when the call returns.
+        // outRect (optional): {x, y, w, h} of the level-0 rectangle treated as dirty.
+        bool Brush(const vr_brush_stroke& stroke, const vr_brush_dab* dabs, uint32_t n, int32_t outRect[4] = nullptr)
+        {
+            return Check(vr_terrain_brush(m_Terrain, &stroke, dabs, n, outRect), "vr_terrain_brush");
+        }
         void SetMaxHeight(float maxHeight) { m_MaxHeight = maxHeight; }      // for queries before the first Render
         const std::vector<std::shared_ptr<QuadTree>>& GetQuadTrees() const { return m_QuadTrees; }
         vr_terrain* Get() const { return m_Terrain; }

@@ -33,6 +33,11 @@ VR_RAY_MISS = 0
 VR_RAY_HIT = 1
 VR_RAY_INVALID = 2
 VR_RAY_STEP_LIMIT = 3
+VR_MAX_BRUSH_DABS = 4096
+VR_BRUSH_RAISE = 0
+VR_BRUSH_FLATTEN = 1
+VR_BRUSH_SMOOTH = 2
+VR_BRUSH_PAINT = 3
 
 
 class TerrainParams(C.Structure):
@@ -147,7 +152,19 @@ class RayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("position", C.c_float * 3), ("normal", C.c_float * 3), ("status", C.c_uint32)]
 
 
+class BrushDab(C.Structure):
+    """vr_brush_dab: a disc of `radius` world units about (x, z); hardness in [0, 1); strength per op (vr_terrain_brush)."""
+    _fields_ = [("x", C.c_float), ("z", C.c_float), ("radius", C.c_float), ("hardness", C.c_float), ("strength", C.c_float),
+                ("reserved", C.c_float * 3)]
+
+
+class BrushStroke(C.Structure):
+    _fields_ = [("op", C.c_int32), ("channel_mask", C.c_uint32), ("target", C.c_float), ("color", C.c_float * 4),
+                ("reserved", C.c_int32)]
+
+
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
+assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -171,7 +188,7 @@ EXPORTS = [
     "vr_tonemap_default_params", "vr_tonemap_create", "vr_tonemap_destroy", "vr_tonemap_reset_exposure", "vr_tonemap_reset_histogram",
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
-    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray", "vr_terrain_edit",
+    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush",
 ]
 
 _lib = None
@@ -294,6 +311,7 @@ def load_library():
         "vr_terrain_cast_rays": (C.c_int, [vp, vp, C.c_uint32, C.c_float, vp, C.c_int]),
         "vr_view_pixel_ray": (C.c_int, [P(View), C.c_float, C.c_float, P(Ray)]),
         "vr_terrain_edit": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int]),
+        "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),
     }
     for name in EXPORTS:
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

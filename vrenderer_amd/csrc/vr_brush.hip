@@ -1,0 +1,251 @@
+// vr_terrain_brush: a stroke - an ordered list of dabs - applied to level 0 of a map on the device by one kernel, followed by the
+// refresh vr_terrain_edit does (vr_derive_level0_write).  The definition of a stroke, texel by texel, is vr_brush.h; this file
+// holds nothing of it but the order in which the header's functions are called.
+//
+//   k_brush_snapshot   SMOOTH only: the stroke's rectangle grown by one texel (clamped) out of the map, so that the 3 x 3 means
+//                      are those of the map before the stroke whatever order the tiles run in
+//   k_brush<op>        one 256-thread workgroup per 32 x 8 tile of the stroke's rectangle, one texel per lane.  The dab list is
+//                      walked in chunks of 256: lane d tests dab d's span against the tile, the survivors are compacted IN LIST
+//                      ORDER into an LDS index list (ballot + popcount prefix inside a wave, the four waves' totals through LDS),
+//                      then every lane applies the listed dabs in order.  A texel no dab covers is not written.
+//
+// The kernel is untimed, like the mip and table kernels; the node-height and pyramid work counts where the edit's does.
+#include "vr_internal.h"
+#include "vr_dirty.h"
+#include "vr_brush.h"
+
+#include <string.h>
+
+struct BrushArgs {
+    float target;               // FLATTEN
+    float color[4];             // PAINT, stored encoding
+    uint32_t channel_mask;      // PAINT
+};
+
+__global__ __launch_bounds__(256) void k_brush_snapshot(const uint8_t* __restrict__ map, int w0, uint8_t* __restrict__ snap, DirtyRect sr)
+{
+    const int x = sr.x0 + blockIdx.x * 32 + (threadIdx.x & 31), y = sr.y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= sr.x1 || y >= sr.y1) return;
+    snap[(size_t)(y - sr.y0) * (size_t)(sr.x1 - sr.x0) + (size_t)(x - sr.x0)] = map[(size_t)y * w0 + x];
+}
+
+__device__ __forceinline__ int brush_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// `map`: level 0 (R8: bytes, SRGBA8: dwords), w0 x h0; `r`: the stroke's rectangle, inside the map; `dabs`: n of them, none empty;
+// `snap`: SMOOTH's snapshot of the rectangle `sr`
+template <int OP>
+__global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, int h0, DirtyRect r, const BrushDab* __restrict__ dabs, uint32_t n,
+                                               BrushArgs a, const uint8_t* __restrict__ snap, DirtyRect sr)
+{
+    constexpr int NC = OP == kBrushPaint ? 4 : 1;
+    __shared__ uint16_t list[256];          // the chunk's dabs that meet this tile, in list order
+    __shared__ uint32_t wave_total[4];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tx0 = r.x0 + (int)blockIdx.x * 32, ty0 = r.y0 + (int)blockIdx.y * 8;
+    const int tx1 = tx0 + 32 < r.x1 ? tx0 + 32 : r.x1, ty1 = ty0 + 8 < r.y1 ? ty0 + 8 : r.y1;
+    const int x = tx0 + (tid & 31), y = ty0 + (tid >> 5);
+    const bool inside = x < tx1 && y < ty1;
+    // every lane stays to the end (the ballots and barriers below want whole waves); one outside the rectangle works on the
+    // clamped texel and writes nothing
+    const size_t at = (size_t)brush_clampi(y, 0, h0 - 1) * (size_t)w0 + (size_t)brush_clampi(x, 0, w0 - 1);
+    float val[NC];
+    uint32_t stored;
+    if (OP == kBrushPaint) {
+        stored = ((const uint32_t*)map)[at];
+#pragma unroll
+        for (int c = 0; c < NC; c++) val[c] = (float)((stored >> (8 * c)) & 255u);
+    } else {
+        stored = ((const uint8_t*)map)[at];
+        val[0] = (float)stored;
+    }
+    float mean = 0.0f;
+    if (OP == kBrushSmooth) {
+        const int sw = sr.x1 - sr.x0;
+        int sum = 0;
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                const int nx = brush_clampi(brush_clampi(x + dx, 0, w0 - 1), sr.x0, sr.x1 - 1), ny = brush_clampi(brush_clampi(y + dy, 0, h0 - 1), sr.y0, sr.y1 - 1);
+                sum += (int)snap[(size_t)(ny - sr.y0) * (size_t)sw + (size_t)(nx - sr.x0)];
+            }
+        mean = brush_mean9(sum);
+    }
+    bool touched = false;
+    for (uint32_t base = 0; base < n; base += 256) {               // (n is a kernel argument: the trip count is uniform)
+        const uint32_t d = base + (uint32_t)tid;
+        bool hit = false;
+        if (d < n) {
+            const BrushDab& b = dabs[d];
+            hit = b.x0 < tx1 && b.x1 > tx0 && b.y0 < ty1 && b.y1 > ty0;
+        }
+        const unsigned long long m = __ballot(hit);
+        const uint32_t before = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t first = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const uint32_t c = wave_total[k]; first += k < wave ? c : 0u; total += c; }
+        if (hit) list[first + before] = (uint16_t)d;               // first + before < total <= 256
+        __syncthreads();
+        total = __builtin_amdgcn_readfirstlane(total);             // the same in every lane: a scalar loop bound
+        for (uint32_t e = 0; e < total; e++) {
+            uint32_t di = __builtin_amdgcn_readfirstlane((uint32_t)list[e]);
+            di = di < n ? di : n - 1;
+            const BrushDab b = dabs[di];
+            float f;
+            if (inside && brush_weight(b, x, y, &f)) {
+                touched = true;
+                if (OP == kBrushRaise) val[0] = brush_raise(val[0], f, b.strength);
+                else if (OP == kBrushFlatten) val[0] = brush_blend(val[0], f, b.strength, a.target);
+                else if (OP == kBrushSmooth) val[0] = brush_blend(val[0], f, b.strength, mean);
+                else {
+#pragma unroll
+                    for (int c = 0; c < NC; c++)
+                        if (a.channel_mask & (1u << c)) val[c] = brush_blend(val[c], f, b.strength, a.color[c]);
+                }
+            }
+        }
+        __syncthreads();                                           // the next chunk overwrites list and wave_total
+    }
+    if (!touched) return;                                          // (touched implies inside)
+    if (OP == kBrushPaint) {
+        uint32_t out = 0;
+#pragma unroll
+        for (int c = 0; c < NC; c++) out |= (uint32_t)brush_byte(val[c]) << (8 * c);
+        ((uint32_t*)map)[at] = out;
+    } else ((uint8_t*)map)[at] = brush_byte(val[0]);
+}
+
+// ---------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------
+static bool host_finite(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
+static dim3 tiles_32x8(const DirtyRect& r) { return dim3((unsigned)((r.x1 - r.x0 + 31) / 32), (unsigned)((r.y1 - r.y0 + 7) / 8)); }
+
+void vr_brush_release(vr_terrain* t)
+{
+    if (t->ev_brush) { (void)hipEventSynchronize(t->ev_brush); (void)hipEventDestroy(t->ev_brush); t->ev_brush = nullptr; }
+    if (t->h_brush_dabs) { (void)hipHostFree(t->h_brush_dabs); t->h_brush_dabs = nullptr; }
+    (void)hipFree(t->d_brush_dabs); t->d_brush_dabs = nullptr;
+    (void)hipFree(t->d_brush_snap); t->d_brush_snap = nullptr; t->brush_snap_bytes = 0;
+    t->brush_pending = false;
+}
+
+// the previous stroke's kernel has passed: the pinned dabs, their device copy and the snapshot are free again
+static int brush_consumed(vr_terrain* t)
+{
+    if (!t->brush_pending) return VR_OK;
+    VR_HIP(hipEventSynchronize(t->ev_brush));
+    t->brush_pending = false;
+    return VR_OK;
+}
+
+// Everything a stroke needs, before anything is launched: a refusal leaves the terrain as it was.
+static int brush_reserve(vr_terrain* t, size_t snap_bytes)
+{
+    constexpr size_t dab_bytes = (size_t)VR_MAX_BRUSH_DABS * sizeof(BrushDab);
+    if (!t->ev_brush) VR_HIP(hipEventCreateWithFlags(&t->ev_brush, hipEventDisableTiming));
+    if (!t->h_brush_dabs) {
+        const hipError_t e = hipHostMalloc((void**)&t->h_brush_dabs, dab_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipGetLastError(); t->h_brush_dabs = nullptr; vr_set_error("terrain brush: %zu bytes of pinned memory: %s", dab_bytes, hipGetErrorString(e)); return VR_ERR_OUT_OF_MEMORY; }
+    }
+    if (!t->d_brush_dabs) {
+        void* p = nullptr;
+        if (!vr_dev_alloc(&p, dab_bytes)) { vr_set_error("terrain brush: %zu bytes for the dab list", dab_bytes); return VR_ERR_OUT_OF_MEMORY; }
+        t->d_brush_dabs = (BrushDab*)p;
+    }
+    if (snap_bytes > t->brush_snap_bytes) {
+        size_t want = t->brush_snap_bytes ? t->brush_snap_bytes * 2 : (size_t)1 << 16;
+        while (want < snap_bytes) want *= 2;
+        const auto idle = [t]() -> int { return brush_consumed(t); };
+        int rc = vr_grow(&t->d_brush_snap, &t->brush_snap_bytes, want, idle);
+        if (rc == VR_ERR_OUT_OF_MEMORY && want > snap_bytes) rc = vr_grow(&t->d_brush_snap, &t->brush_snap_bytes, snap_bytes, idle);
+        if (rc) { if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain brush: %zu bytes for the snapshot", snap_bytes); return rc; }
+    }
+    return VR_OK;
+}
+
+extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* stroke, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4])
+{
+    static_assert(sizeof(vr_brush_dab) == 32 && sizeof(vr_brush_stroke) == 32, "vr_brush_dab / vr_brush_stroke layout");
+    static_assert(VR_BRUSH_RAISE == kBrushRaise && VR_BRUSH_FLATTEN == kBrushFlatten && VR_BRUSH_SMOOTH == kBrushSmooth && VR_BRUSH_PAINT == kBrushPaint, "vr_brush.h's ops");
+    static_assert(VR_MAX_BRUSH_DABS <= 65536, "k_brush's index list holds 16-bit indices");
+    // the argument checks come before any use of the device (and leave the terrain alone)
+    VR_REQUIRE(t != nullptr, "terrain is NULL");
+    VR_REQUIRE(stroke != nullptr, "stroke is NULL");
+    VR_REQUIRE(dabs != nullptr || n == 0, "dabs is NULL with n > 0");
+    VR_REQUIRE(n <= VR_MAX_BRUSH_DABS, "more than VR_MAX_BRUSH_DABS dabs");
+    const int op = stroke->op;
+    VR_REQUIRE(op == VR_BRUSH_RAISE || op == VR_BRUSH_FLATTEN || op == VR_BRUSH_SMOOTH || op == VR_BRUSH_PAINT, "unknown op");
+    VR_REQUIRE(host_finite(stroke->target), "target is NaN or infinite");
+    for (int c = 0; c < 4; c++) VR_REQUIRE(host_finite(stroke->color[c]), "color is NaN or infinite");
+    if (op == VR_BRUSH_FLATTEN) VR_REQUIRE(stroke->target >= 0.0f && stroke->target <= 255.0f, "target outside [0, 255]");
+    if (op == VR_BRUSH_PAINT) {
+        VR_REQUIRE(stroke->channel_mask >= 1u && stroke->channel_mask <= 15u, "channel_mask must be 1 .. 15");
+        for (int c = 0; c < 4; c++) VR_REQUIRE(stroke->color[c] >= 0.0f && stroke->color[c] <= 255.0f, "color outside [0, 255]");
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const vr_brush_dab& d = dabs[i];
+        VR_REQUIRE(host_finite(d.x) && host_finite(d.z) && host_finite(d.radius) && host_finite(d.hardness) && host_finite(d.strength), "a dab holds a NaN or an infinity");
+        VR_REQUIRE(d.radius > 0.0f, "radius must be positive");
+        VR_REQUIRE(d.hardness >= 0.0f && d.hardness < 1.0f, "hardness outside [0, 1)");
+        if (op == VR_BRUSH_RAISE) VR_REQUIRE(fabsf(d.strength) <= 255.0f, "RAISE: |strength| above 255");
+        else VR_REQUIRE(d.strength >= 0.0f && d.strength <= 1.0f, "opacity outside [0, 1]");
+    }
+    const int which = op == VR_BRUSH_PAINT ? 1 : 0;
+    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    // The dabs that meet the map, in order, prepared for the map the stroke addresses, and the hull of their spans - still on the
+    // host alone (the vector keeps its room from stroke to stroke).
+    std::vector<BrushDab>& prepared = t->brush_prepared;
+    prepared.clear();
+    prepared.reserve(VR_MAX_BRUSH_DABS);
+    DirtySpan hx, hy;
+    for (uint32_t i = 0; i < n; i++) {
+        const vr_brush_dab& d = dabs[i];
+        const BrushDab b = brush_prepare(d.x, d.z, d.radius, d.hardness, d.strength, t->p.world_size, tex.w0, tex.h0);
+        if (brush_dab_empty(b)) continue;
+        DirtySpan sx, sy; sx.lo = b.x0; sx.hi = b.x1; sy.lo = b.y0; sy.hi = b.y1;
+        hx = dirty_hull(hx, sx); hy = dirty_hull(hy, sy);
+        prepared.push_back(b);
+    }
+    const DirtyRect dirty = dirty_rect(hx, hy);
+    if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
+    if (prepared.empty()) return VR_OK;                            // n == 0, or every dab misses the map: nothing is launched
+
+    vr_context* ctx = t->ctx;
+    VR_HIP(hipSetDevice(ctx->device));
+    // SMOOTH reads the rectangle grown by one texel, clamped to the map
+    DirtyRect sr = dirty;
+    if (op == VR_BRUSH_SMOOTH) sr = dirty_rect(dirty_clip(DirtySpan{ dirty.x0 - 1, dirty.x1 + 1 }, tex.w0), dirty_clip(DirtySpan{ dirty.y0 - 1, dirty.y1 + 1 }, tex.h0));
+    { const int rc = brush_reserve(t, op == VR_BRUSH_SMOOTH ? (size_t)(sr.x1 - sr.x0) * (size_t)(sr.y1 - sr.y0) : 0); if (rc) return rc; }
+    // the one wait on the host: only where the previous stroke has not been consumed yet
+    { const int rc = brush_consumed(t); if (rc) return rc; }
+    const uint32_t nd = (uint32_t)prepared.size();
+    memcpy(t->h_brush_dabs, prepared.data(), (size_t)nd * sizeof(BrushDab));
+
+    BrushArgs a; memset(&a, 0, sizeof(a));
+    a.target = stroke->target; a.channel_mask = stroke->channel_mask;
+    for (int c = 0; c < 4; c++) a.color[c] = stroke->color[c];
+    void* mem = const_cast<uint8_t*>(tex.base);
+    const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t s) -> int {
+        VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)nd * sizeof(BrushDab), hipMemcpyHostToDevice, s));
+        const uint8_t* snap = (const uint8_t*)t->d_brush_snap;
+        const dim3 grid = tiles_32x8(dirty);
+        switch (op) {
+        case VR_BRUSH_RAISE: hipLaunchKernelGGL(k_brush<kBrushRaise>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+        case VR_BRUSH_FLATTEN: hipLaunchKernelGGL(k_brush<kBrushFlatten>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+        case VR_BRUSH_SMOOTH:
+            hipLaunchKernelGGL(k_brush_snapshot, tiles_32x8(sr), dim3(256), 0, s, (const uint8_t*)mem, tex.w0, (uint8_t*)t->d_brush_snap, sr);
+            hipLaunchKernelGGL(k_brush<kBrushSmooth>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+        default: hipLaunchKernelGGL(k_brush<kBrushPaint>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+        }
+        VR_HIP(hipGetLastError());
+        VR_HIP(hipEventRecord(t->ev_brush, s));
+        t->brush_pending = true;
+        return VR_OK;
+    });
+    if (rc) return rc;
+    if (out_rect) { out_rect[0] = dirty.x0; out_rect[1] = dirty.y0; out_rect[2] = dirty.x1 - dirty.x0; out_rect[3] = dirty.y1 - dirty.y0; }
+    return VR_OK;
+}

@@ -4,6 +4,9 @@
 //   create   vr_tex_upload_and_mip, vr_node_heights_surface, the first ray cast's pyramid: the rectangle is the whole map
 //   edit     vr_terrain_edit (below): a sub-rectangle of level 0 is replaced in place and everything is brought up to date inside
 //            the dirty rectangle of each structure, so that the terrain is the one vr_terrain_create builds from the edited arrays
+//   brush    vr_terrain_brush (vr_brush.hip): a kernel rewrites texels of level 0 inside a stroke's bounding rectangle; the same
+//            refresh follows.  Edit and brush share vr_derive_level0_write: the waits in front of the write, the write itself
+//            (the caller's), the chain and the tables, the node heights, the pyramid, the order mark behind.
 //
 // Every rectangle comes from vr_dirty.h (the whole map dirties the whole of every structure: tests/host/dirty_check.cpp); every
 // element is computed by the expressions of vr_terrain_dev.h.  Grids are sized from the rectangle, never from the map.
@@ -212,51 +215,23 @@ void vr_derive_pyramid(const DevTex& hm, const PyrDesc& pd, uchar2* pyramid, con
     }
 }
 
-extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32_t y, int32_t w, int32_t h,
-                                       const void* texels, size_t row_pitch_bytes, int device_pointer)
+int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, const std::function<int(hipStream_t)>& write_level0)
 {
-    // the argument checks come before any use of the device (and leave the terrain alone)
-    VR_REQUIRE(t != nullptr, "terrain is NULL");
-    VR_REQUIRE(which == 0 || which == 1, "which must be 0 (heightmap) or 1 (albedo)");
-    VR_REQUIRE(x >= 0 && y >= 0 && w >= 0 && h >= 0, "negative coordinate or extent");
+    vr_context* ctx = t->ctx;
+    hipStream_t s = ctx->stream;
     const DevTex& tex = which == 0 ? t->height : t->albedo;
     const TexLayout& lay = which == 0 ? t->height_layout : t->albedo_layout;
-    const size_t tb = which == 0 ? 1 : 4;
-    VR_REQUIRE((int64_t)x + w <= tex.w0 && (int64_t)y + h <= tex.h0, "the rectangle is not inside level 0");
-    if (w == 0 || h == 0) return VR_OK;
-    VR_REQUIRE(texels != nullptr, "texels is NULL");
-    VR_REQUIRE(row_pitch_bytes == 0 || row_pitch_bytes >= (size_t)w * tb, "row pitch smaller than a row");
-    VR_REQUIRE(!device_pointer || (((uintptr_t)texels | row_pitch_bytes) & (tb - 1)) == 0, "device pointer and pitch must be aligned to the texel size");
-    const size_t row = (size_t)w * tb, pitch = row_pitch_bytes ? row_pitch_bytes : row;
-    vr_context* ctx = t->ctx;
-    VR_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // staging of the host-pointer mode: reserved before anything is launched (a refusal leaves the terrain as it was)
-    const uint8_t* src = (const uint8_t*)texels; size_t src_pitch = pitch;
-    if (!device_pointer) {
-        const int rc = vr_query_reserve_stage(t, row * (size_t)h);
-        if (rc) return rc;
-        src = (const uint8_t*)t->d_query_stage; src_pitch = row;
-    }
-    DirtyRect dirty; dirty.x0 = x; dirty.y0 = y; dirty.x1 = x + w; dirty.y1 = y + h;
-
     // before the first write: behind every chain queued so far (its vertex stage reads the heightmap) and behind every tile pass
     // (it reads the tables, and the host may have changed the context's stream since it was queued)
     static_assert(kGeoSets == 3, "the list below");
     VrOrderSet* const ord_sets[kGeoSets] = { &t->sets[0].ord, &t->sets[1].ord, &t->sets[2].ord };
     { const int rc = order_terrain_changing(ord_sets, VrOrderOps(), s); if (rc) return rc; }
     { const int rc = order_terrain_tables_changing(ord_sets, VrOrderOps(), s, ctx->ev_epoch); if (rc) return rc; }
-    if (!device_pointer) {
-        if (pitch == row) VR_HIP(hipMemcpyAsync(t->d_query_stage, texels, row * (size_t)h, hipMemcpyHostToDevice, s));
-        else VR_HIP(hipMemcpy2DAsync(t->d_query_stage, row, texels, pitch, row, (size_t)h, hipMemcpyHostToDevice, s));
-    }
     // geometry built from the old map is stale, whichever map it was (one rule); selections and lock_view stay as they are
     for (GeoSet& g : t->sets) g.prepared = false;
 
-    uint8_t* mem = const_cast<uint8_t*>(tex.base);
-    if (which == 0) hipLaunchKernelGGL(k_derive_copy<uint8_t>, tiles_32x8(dirty), dim3(256), 0, s, src, src_pitch, mem, tex.w0, dirty);
-    else hipLaunchKernelGGL(k_derive_copy<uint32_t>, tiles_32x8(dirty), dim3(256), 0, s, src, src_pitch, (uint32_t*)mem, tex.w0, dirty);
-    vr_derive_chain(ctx, mem, lay, tex.w0, tex.h0, tex.levels, (int)tb, dirty);
+    { const int rc = write_level0(s); if (rc) return rc; }
+    vr_derive_chain(ctx, const_cast<uint8_t*>(tex.base), lay, tex.w0, tex.h0, tex.levels, which == 0 ? 1 : 4, dirty);
     VR_HIP(hipGetLastError());
     if (which == 0 && t->height_loaded && t->d_node_heights) {
         VrKernelScope ks(ctx, VR_K_NODE_HEIGHTS);
@@ -279,8 +254,49 @@ extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32
         VR_HIP(hipEventRecord(t->ev_pyramid, s));
         t->pyramid_stream = s;
     }
-    // every set's next chain runs behind the edit
+    // every set's next chain runs behind the write
     { const int rc = order_terrain_changed(t->ord, ord_sets, VrOrderOps(), s); if (rc) return rc; }
+    return VR_OK;
+}
+
+extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32_t y, int32_t w, int32_t h,
+                                       const void* texels, size_t row_pitch_bytes, int device_pointer)
+{
+    // the argument checks come before any use of the device (and leave the terrain alone)
+    VR_REQUIRE(t != nullptr, "terrain is NULL");
+    VR_REQUIRE(which == 0 || which == 1, "which must be 0 (heightmap) or 1 (albedo)");
+    VR_REQUIRE(x >= 0 && y >= 0 && w >= 0 && h >= 0, "negative coordinate or extent");
+    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const size_t tb = which == 0 ? 1 : 4;
+    VR_REQUIRE((int64_t)x + w <= tex.w0 && (int64_t)y + h <= tex.h0, "the rectangle is not inside level 0");
+    if (w == 0 || h == 0) return VR_OK;
+    VR_REQUIRE(texels != nullptr, "texels is NULL");
+    VR_REQUIRE(row_pitch_bytes == 0 || row_pitch_bytes >= (size_t)w * tb, "row pitch smaller than a row");
+    VR_REQUIRE(!device_pointer || (((uintptr_t)texels | row_pitch_bytes) & (tb - 1)) == 0, "device pointer and pitch must be aligned to the texel size");
+    const size_t row = (size_t)w * tb, pitch = row_pitch_bytes ? row_pitch_bytes : row;
+    vr_context* ctx = t->ctx;
+    VR_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // staging of the host-pointer mode: reserved before anything is launched (a refusal leaves the terrain as it was)
+    const uint8_t* src = (const uint8_t*)texels; size_t src_pitch = pitch;
+    if (!device_pointer) {
+        const int rc = vr_query_reserve_stage(t, row * (size_t)h);
+        if (rc) return rc;
+        src = (const uint8_t*)t->d_query_stage; src_pitch = row;
+    }
+    DirtyRect dirty; dirty.x0 = x; dirty.y0 = y; dirty.x1 = x + w; dirty.y1 = y + h;
+    uint8_t* mem = const_cast<uint8_t*>(tex.base);
+    // the host's texels into the staging memory, then one strided copy into level 0; everything else is the shared path
+    const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t st) -> int {
+        if (!device_pointer) {
+            if (pitch == row) VR_HIP(hipMemcpyAsync(t->d_query_stage, texels, row * (size_t)h, hipMemcpyHostToDevice, st));
+            else VR_HIP(hipMemcpy2DAsync(t->d_query_stage, row, texels, pitch, row, (size_t)h, hipMemcpyHostToDevice, st));
+        }
+        if (which == 0) hipLaunchKernelGGL(k_derive_copy<uint8_t>, tiles_32x8(dirty), dim3(256), 0, st, src, src_pitch, mem, tex.w0, dirty);
+        else hipLaunchKernelGGL(k_derive_copy<uint32_t>, tiles_32x8(dirty), dim3(256), 0, st, src, src_pitch, (uint32_t*)mem, tex.w0, dirty);
+        return VR_OK;
+    });
+    if (rc) return rc;
     if (!device_pointer) VR_HIP(hipStreamSynchronize(s));        // the caller's host memory has been consumed
     return VR_OK;
 }

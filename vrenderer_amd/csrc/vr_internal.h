@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/vrterrain.h"
+#include "vr_brush.h"
 #include "vr_devbuf.h"
 #include "vr_gbuffer_state.h"
 #include "vr_light_plan.h"
@@ -374,8 +375,18 @@ struct vr_terrain {
     uchar2* d_pyramid = nullptr; uint64_t pyramid_bytes = 0;
     hipEvent_t ev_pyramid = nullptr; hipStream_t pyramid_stream = nullptr;     // the build; a cast on another stream waits for it
     void* d_query_stage = nullptr; size_t query_stage_bytes = 0;
+    // Brush strokes (vr_brush.hip): the prepared dabs of the latest stroke in pinned host memory and their copy on the device
+    // (VR_MAX_BRUSH_DABS each, from the first stroke on), SMOOTH's snapshot of the map (grown to the largest rectangle so far),
+    // and the event behind the latest stroke's kernel - the one reader of all three.  vr_terrain_brush synchronises nothing, so
+    // this memory is its own and not d_query_stage, whose users leave it idle when they return: the next stroke waits on the
+    // host for the event where the previous stroke has not been consumed yet, whichever stream that one ran on.
+    std::vector<BrushDab> brush_prepared;       // a stroke's dabs as they are prepared, before anything touches the device
+    BrushDab* h_brush_dabs = nullptr; BrushDab* d_brush_dabs = nullptr;
+    void* d_brush_snap = nullptr; size_t brush_snap_bytes = 0;
+    hipEvent_t ev_brush = nullptr; bool brush_pending = false;
 };
 void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
+void vr_brush_release(vr_terrain* t);      // the brush's memory and event (vr_brush.hip)
 // the staging memory holds at least `bytes` (grown by doubling; on failure the terrain keeps what it had); whoever uses it
 // synchronises the context's stream before it returns
 int vr_query_reserve_stage(vr_terrain* t, size_t bytes);
@@ -401,6 +412,11 @@ void vr_derive_chain(vr_context* ctx, uint8_t* mem, const TexLayout& lay, int w0
 void vr_derive_node_heights(vr_terrain* t, int surf, const NodeSurface& ns, const DirtyRect& dirty);
 // the query pyramid at `pyramid`; l0, l1: the rectangle in levels 0 and 1 of the heightmap (a one-level chain: l1 = l0)
 void vr_derive_pyramid(const DevTex& hm, const PyrDesc& pd, uchar2* pyramid, const DirtyRect& l0, const DirtyRect& l1, hipStream_t s);
+// A write of the rectangle `dirty` of level 0 of a map (which: 0 heightmap, 1 albedo) and everything that follows from it, on the
+// context's stream - the one path of vr_terrain_edit and vr_terrain_brush: the write waits behind every chain and tile pass queued
+// so far, prepared geometry is dropped, write_level0(stream) queues the write itself, then the chain and the tables, the node
+// heights and the query pyramid are brought up to date inside their dirty rectangles and every set's next chain runs behind it.
+int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, const std::function<int(hipStream_t)>& write_level0);
 
 struct vr_tonemap;
 vr_context* vr_tonemap_context(vr_tonemap* tm);

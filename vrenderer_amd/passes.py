@@ -501,6 +501,30 @@ class TerrainPass:
         else:
             check(self.ctx.lib.vr_terrain_edit(self.handle, idx, x, y, w, h, C.c_void_p(device_ptr), pitch, 1), "vr_terrain_edit")
 
+    def Brush(self, op, dabs, target=0.0, color=None, channels=0xF):
+        """vr_terrain_brush: one stroke on level 0 of the heightmap (op 'raise', 'flatten', 'smooth' or capi.VR_BRUSH_*) or of the
+        albedo ('paint'), computed on the device; stream-ordered, nothing is synchronised.  `dabs`: (n, 5) float32 rows of
+        (x, z, radius, hardness, strength) in world units, applied in order - or (n, 8) rows laid out as the C struct
+        vr_brush_dab, which are passed as they are (the array may be reused as soon as the call returns).  `target`: FLATTEN's
+        level, 0 .. 255; `color`: PAINT's four stored bytes' worth, 0 .. 255 each; `channels`: PAINT's channel mask.
+        Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
+        idx = {"raise": capi.VR_BRUSH_RAISE, "flatten": capi.VR_BRUSH_FLATTEN, "smooth": capi.VR_BRUSH_SMOOTH,
+               "paint": capi.VR_BRUSH_PAINT}.get(op, op)
+        a = np.asarray(dabs, np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 5)
+        assert a.ndim == 2 and a.shape[1] in (5, 8)
+        if a.shape[1] == 5:
+            full = np.zeros((a.shape[0], 8), np.float32)
+            full[:, :5] = a
+            a = full
+        a = np.ascontiguousarray(a)
+        stroke = capi.BrushStroke(op=idx, channel_mask=channels, target=target)
+        stroke.color[:] = [float(c) for c in (color if color is not None else (0.0, 0.0, 0.0, 0.0))]
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_brush(self.handle, C.byref(stroke), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_brush")
+        return tuple(int(v) for v in rect)
+
     def Prepare(self, view, render_targets, render_params, partition=None):
         """Build the next frame's geometry ahead of time (overlaps the current frame's tile pass)."""
         check(self.ctx.lib.vr_terrain_prepare(self.handle, C.byref(view), render_targets.handle, C.byref(render_params),
