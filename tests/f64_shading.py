@@ -42,6 +42,12 @@ the 1024-light tiled frame, the 8K sample and the deferred fuzz test):
   frames, the 1024-light frame and the 8K sample).  It is dominated by the
   half rounding term (a value next to a rounding midpoint uses all of its 2^-11): the fp32 error proper is a small
   fraction of the budget, and a kernel change that moves a value by more than its half-rounding step fails.
+  The all-light-type tiled kernels (test_tiled_ex_f64.py), kernel / oracle on the same input - equal to four digits
+  everywhere, the worst value being one next to a rounding midpoint that both round alike: edge frame 512 `extra`
+  0.9985 / 0.9985, 13 lights 0.9966 / 0.9966; edge frame 508 `extra` 0.9956 / 0.9956, 13 lights (row-major, packed) and
+  suns + points 0.9947 / 0.9947; PCF frame, sun first (w = 1, 2, packed) and second 0.9986 / 0.9986, fourth of four and
+  with every light type 0.9862 / 0.9862; 300 lights in one tile 0.9665 / 0.9665; terrain from the tile pass's ranges
+  0.8142 / 0.8142.
 * TAU_AREA = 1e-4 (sinT): the R = -L pixels; 1e-3 flags the same pixels on these frames.
 * TAU_GRAZING = 1e-5: below it fp32 and float64 may disagree on whether a saturate clamps to 0 (exact zeros, as
   axis-aligned vectors give them, are not flagged).
@@ -670,3 +676,244 @@ def pcf_coverage(r_geo, res=PCF_RES, W=PCF_W):
                 v1=int((inside & (v == 1)).sum()), z0=int((inside & (zc == 0)).sum()), z1=int((inside & (zc == 1)).sum()),
                 edge=int(edge.sum()), clamp_path=int(clamp.sum()), row_path=int((inside & ~clamp).sum()),
                 outside=int((~inside).sum()))
+
+
+# ---- inputs of the all-light-type tiled pass (tests/test_tiled_ex_f64.py and its CPU companion) ----------------------
+def plan_facts(lights):
+    """What vr_light_check gathers from a light list for light_plan() (vr_light_plan.h).  extra: a spot or a spherical
+    (radius > 0) light is in the list.  cone: a spot light whose cone the culling stage tests - a positive outer_angle
+    below pi / 2 and a unit axis (cone_cull_terms, vr_light_cull.h).  kinds: (type, spherical, ranged) of every light."""
+    extra = cone = False
+    kinds = set()
+    for l in lights:
+        directional = l.type == VR_LIGHT_DIRECTIONAL
+        kinds.add((int(l.type), (not directional) and l.radius > 0, (not directional) and l.angular_size_or_inv_range > 0))
+        if directional:
+            continue
+        extra = extra or l.type == VR_LIGHT_SPOT or l.radius > 0
+        if l.type == VR_LIGHT_SPOT:
+            # cone_cull_terms' constants (vr_light_cull.h): kConeAxisTolerance = 1e-6 on | |axis|^2 - 1 |, kConeAngleMargin
+            # = 1e-5 added to outer_angle, and its bound 1.5707 on the sum - a change there must be followed here
+            a2 = sum(float(x) ** 2 for x in l.direction[:3])
+            cone = cone or (abs(a2 - 1.0) <= 1e-6 and l.outer_angle > 0 and float(l.outer_angle) + 1e-5 < 1.5707)
+    return dict(extra=bool(extra), cone=bool(cone), kinds=kinds)
+
+
+ALL_KINDS = {(VR_LIGHT_DIRECTIONAL, False, False), (VR_LIGHT_POINT, False, True), (VR_LIGHT_SPOT, False, True),
+             (VR_LIGHT_SPOT, False, False), (VR_LIGHT_POINT, True, True), (VR_LIGHT_SPOT, True, False)}
+
+
+def all_type_lights(vr, wp, covered, n, seed):
+    """The sun, a point light, a spot light and a spherical point and spot source, extended to n lights by a fixed seed:
+    point lights, spot lights with and without a range, spherical point and spot sources, each above a covered pixel of the
+    frame (wp: (h, w, 3) world positions) and at least 5 units from every visible surface point (a light that all but
+    touches the steep terrain would put single pixels at 10 and more, where one RGBA16F ulp is larger than the whole
+    error budget)."""
+    scale = 1.0
+    surface = wp[covered]
+    lights = [vr.reference_sun(), vr.point_light((10.0, 40.0, -5.0), 3000.0 * scale, 120.0, (1.0, 0.5, 0.25)),
+              vr.spot_light((-20.0, 60.0, 10.0), (0.3, -1.0, -0.2), 6000.0 * scale, 200.0, 12.0, 25.0, (0.2, 1.0, 0.4)),
+              vr.point_light((30.0, 35.0, -30.0), 2000.0 * scale, 150.0, (0.9, 0.9, 1.0), radius=6.0),
+              vr.spot_light((0.0, 80.0, -40.0), (0.0, -1.0, 0.3), 9000.0 * scale, 0.0, 5.0, 40.0, (1.0, 0.2, 0.2), radius=3.0)]
+    rng = np.random.default_rng(seed)
+    ys, xs = np.nonzero(covered)
+    while len(lights) < n:
+        k = rng.integers(len(ys))
+        pos = wp[ys[k], xs[k]] + np.array([rng.uniform(-3, 3), rng.uniform(6, 25), rng.uniform(-3, 3)])
+        if np.sqrt(((surface - pos) ** 2).sum(axis=1)).min() < 5.0:
+            continue
+        col, inten, rad = rng.uniform(0.1, 1.0, 3), rng.uniform(5.0, 40.0) * scale, rng.uniform(15.0, 60.0)
+        kind = len(lights) % 5
+        axis = np.array([rng.uniform(-0.5, 0.5), -1.0, rng.uniform(-0.5, 0.5)])
+        outer = rng.uniform(8.0, 70.0)
+        if kind == 0:
+            lights.append(vr.point_light(pos, inten, rad, col))
+        elif kind == 1:
+            lights.append(vr.spot_light(pos, axis, inten * 3, rad * 1.5, outer * 0.5, outer, col))
+        elif kind == 2:
+            lights.append(vr.spot_light(pos, axis, inten * 0.3, 0.0, outer * 0.6, outer, col))              # no range
+        elif kind == 3:
+            lights.append(vr.point_light(pos, inten, rad, col, radius=rng.uniform(0.5, 4.0)))
+        else:
+            lights.append(vr.spot_light(pos, axis, inten * 3, rad * 1.5, outer * 0.3, outer, col, radius=rng.uniform(0.5, 3.0)))
+    return lights
+
+
+def pcf_lights(vr):
+    """(the shadowed sun, the unshadowed directional light) of the PCF tests."""
+    return vr.reference_sun(), vr.directional_light((0.3, -1.0, 0.2), 0.5, 0.0)
+
+
+def pcf_all_type_lights(vr):
+    """The two directional lights of the PCF frame and one light of every other kind, 6 to 25 units above the receivers
+    (which lie at heights 0 .. 1: every light is at least 5 units from every surface point).  The ranged point and spot
+    lights stand in front of the sun in the list: in a tile that culls one of them the sun's staged slot differs from
+    its list index.  Returns (lights, the sun's index)."""
+    sun, fill = pcf_lights(vr)
+    lights = [vr.point_light((-30.0, 12.0, 20.0), 250.0, 60.0, (1.0, 0.5, 0.25)),
+              vr.spot_light((20.0, 15.0, -10.0), (0.2, -1.0, 0.1), 500.0, 80.0, 15.0, 35.0, (0.2, 1.0, 0.4)),
+              fill, sun,
+              vr.spot_light((-10.0, 20.0, -30.0), (0.0, -1.0, 0.2), 600.0, 0.0, 10.0, 30.0, (1.0, 0.2, 0.2)),         # no range
+              vr.point_light((40.0, 10.0, 30.0), 150.0, 50.0, (0.9, 0.9, 1.0), radius=2.0),
+              vr.spot_light((0.0, 25.0, 0.0), (-0.1, -1.0, 0.0), 900.0, 0.0, 20.0, 50.0, (0.6, 0.7, 1.0), radius=1.5)]
+    return lights, 3
+
+
+PCF_CROWD_W, PCF_CROWD_TILE, PCF_CROWD_N = 256, (3, 0), 300
+
+
+def pcf_crowd_lights(vr, seed=6):
+    """PCF_CROWD_N weak lights above the light tile PCF_CROWD_TILE of the PCF frame of width PCF_CROWD_W (spherical point
+    lights, punctual and spherical spot lights pointing down, 6 to 7.5 units above the receivers' plane, short ranges and
+    narrow cones: the tile's list holds them all, a pixel is reached by a few), the unshadowed directional light in front
+    of them and the sun behind them.  Returns (lights, the sun's index)."""
+    W, H = PCF_CROWD_W, PCF_H
+    tx, ty = PCF_CROWD_TILE
+    x0, x1 = 64.0 * (tx * 32 * 2.0 / W - 1.0), 64.0 * ((tx + 1) * 32 * 2.0 / W - 1.0)
+    z1, z0 = 64.0 * (1.0 - ty * 32 * 2.0 / H), 64.0 * (1.0 - (ty + 1) * 32 * 2.0 / H)
+    rng = np.random.default_rng(seed)
+    sun, fill = pcf_lights(vr)
+    lights = [fill]
+    for i in range(PCF_CROWD_N):
+        pos = (rng.uniform(x0 + 1.0, x1 - 1.0), rng.uniform(6.0, 7.5), rng.uniform(z0 + 1.0, z1 - 1.0))
+        col = rng.uniform(0.1, 1.0, 3)
+        axis = (rng.uniform(-0.2, 0.2), -1.0, rng.uniform(-0.2, 0.2))
+        outer = rng.uniform(10.0, 25.0)
+        if i % 3 == 0:
+            lights.append(vr.point_light(pos, 4.0, 8.0, col, radius=rng.uniform(0.5, 2.0)))
+        elif i % 3 == 1:
+            lights.append(vr.spot_light(pos, axis, 12.0, 20.0, outer * 0.5, outer, col))
+        else:
+            lights.append(vr.spot_light(pos, axis, 12.0, 0.0, outer * 0.4, outer, col, radius=rng.uniform(0.5, 1.5)))
+    return lights + [sun], len(lights)
+
+
+def pcf_crowd_mask(seed=6):
+    """4096 pixels of the PCF_CROWD_W frame: every pixel of PCF_CROWD_TILE and a seeded sample of its neighbours in the
+    frame (the frame has two rows of light tiles: five of the eight exist)."""
+    W, H = PCF_CROWD_W, PCF_H
+    tx, ty = PCF_CROWD_TILE
+    py, px = np.mgrid[0:H, 0:W]
+    gx, gy = px // 32, py // 32
+    hot = (gx == tx) & (gy == ty)
+    near = (np.abs(gx - tx) <= 1) & (np.abs(gy - ty) <= 1) & ~hot
+    idx = np.flatnonzero(near)
+    pick = np.random.default_rng(seed).choice(idx, 4096 - int(hot.sum()), replace=False)
+    mask = hot.copy()
+    mask.flat[pick] = True
+    assert mask.sum() == 4096
+    return mask
+
+
+def masked_pcf_coverage(r_geo, res=PCF_RES):
+    """pcf_coverage's counts of u / v / zc exactly 0 and 1, of footprints over the map's edge and of pixels outside the map,
+    for any list of pixels (a mask)."""
+    u, v, zc, tx, ty = r_geo.T
+    inside = (u >= 0) & (u <= 1) & (v >= 0) & (v <= 1) & (zc >= 0) & (zc <= 1)
+    ix, iy = np.floor(tx) - 1, np.floor(ty) - 1
+    edge = inside & ((ix < 0) | (ix + 3 > res - 1) | (iy < 0) | (iy + 3 > res - 1))
+    return dict(u0=int((inside & (u == 0)).sum()), u1=int((inside & (u == 1)).sum()), v0=int((inside & (v == 0)).sum()),
+                v1=int((inside & (v == 1)).sum()), z0=int((inside & (zc == 0)).sum()), z1=int((inside & (zc == 1)).sum()),
+                edge=int(edge.sum()), outside=int((~inside).sum()))
+
+
+class TiledCase:
+    """One (frame, light list, shadow) input of the tiled pass with the conditions its check runs under, for the kernels
+    and for the fp32 oracle alike: caps (None: check()'s default), mask (None: the whole frame), exact_geometry and the
+    least share of values that must be held to the tight bound.  shadow: (light view, map, light index, bias) or None.
+    The float64 reference is computed once per case and never changed."""
+
+    def __init__(self, name, view, planes, lights, ambient, shadow=None, caps=None, mask=None, exact_geometry=False,
+                 min_checked=0.9, rows=None):
+        self.name, self.view, self.planes, self.lights, self.ambient = name, view, planes, list(lights), ambient
+        self.shadow, self.caps, self.mask, self.exact_geometry, self.min_checked = shadow, caps, mask, exact_geometry, min_checked
+        self.rows = rows
+        self.h, self.w = planes["depth"].shape
+        if mask is None:
+            self.pix = Pixels.from_planes(planes)
+        else:
+            py, px = np.nonzero(mask)
+            self.pix = Pixels.from_planes(planes, px, py)
+        self._ref = None
+
+    def reference(self):
+        if self._ref is None:
+            sh = None
+            if self.shadow is not None:
+                lv, smap, li, bias = self.shadow
+                sh = (lv, smap, li, bias, self.lights[li].out_of_bounds_shadow)
+            self._ref = reference(self.pix, self.view, self.lights, self.ambient[0], self.ambient[1], shadow=sh,
+                                  exact_geometry=self.exact_geometry)
+        return self._ref
+
+    def check(self, frame, what, report=True):
+        """frame: (h, w, 3) values of an implementation.  Returns check()'s result, with the shadow lookup's coverage of the
+        checked pixels in it (a shadowed case)."""
+        got = np.asarray(frame, np.float64)[self.pix.py, self.pix.px]
+        r = self.reference()
+        res = check(got, r, self.pix, f"{self.name}: {what}", caps=self.caps)
+        assert res["checked"] > self.min_checked * got.size, res
+        if self.shadow is not None:
+            # a whole frame: pcf_coverage; a mask: the same keys from the geometry of the checked pixels (the two load-path
+            # counts need a row-major list and are not asserted here)
+            cov = pcf_coverage(r["shadow_geo"], W=self.w) if self.mask is None else masked_pcf_coverage(r["shadow_geo"])
+            res["coverage"] = cov
+            for k in ("v0", "v1", "z0", "z1", "edge", "outside"):
+                assert cov[k] > 0, cov
+            # u = 0 and u = 1 lie half a frame apart (W / 2 pixels: four light tiles at the narrowest width, 256): a whole
+            # frame has both, a mask of three tile columns can hold one of them
+            assert (cov["u0"] > 0 and cov["u1"] > 0) if self.mask is None else (cov["u0"] + cov["u1"] > 0), cov
+        if report:
+            print(f"{self.name}: {what}: worst ratio {res['worst']:.4f}, classes {res['counts']}"
+                  + (f", coverage {res['coverage']}" if "coverage" in res else ""))
+        return res
+
+    def oracle_frame(self, oracle):
+        """The fp32 oracle's half output for this input, (h, w, 3) float64."""
+        gb = oracle.GBufferHost(self.w, self.h)
+        for k, a in self.planes.items():
+            getattr(gb, k)[...] = np.asarray(a).reshape(getattr(gb, k).shape)
+        out = oracle.deferred(self.view, gb, self.lights, self.ambient[0], self.ambient[1], shadow=self.shadow)
+        return oracle.half_to_float(out)[..., :3].astype(np.float64)
+
+
+def tiled_edge_case(vr, ambient, width, lights_name):
+    """The edge-case frame at width x 128 with 'extra', 'all' (suns + points + extra: 13 lights) or 'tiled' (suns +
+    points) of edge_lights; EDGE_CAPS.  The caps are conditions on the input, and the frame's seed is part of it: at 508
+    the seed 1 of the other widths puts 119 pixels into the class 'area' (cap 100) for the oracle as for any other
+    implementation, and three R = -L texels with kk = 0 under a spot light (NaN or inf, as the undefined rotation falls);
+    seed 2 gives 32 'area' pixels and none of those (test_tiled_ex_f64_cpu.py holds the oracle to it)."""
+    view, planes, rows = edge_case_frame(vr, width, 128, seed={508: 2}.get(width, 1))
+    L = edge_lights(vr, view, planes, rows)
+    L["all"] = L["suns"] + L["points"] + L["extra"]
+    return TiledCase(f"edge frame {width}, {lights_name}", view, planes, L[lights_name], ambient, caps=EDGE_CAPS, rows=rows)
+
+
+def tiled_pcf_case(vr, ambient, lists, w_scale=1.0):
+    """The PCF frame with one of the light lists 'sun_first' [sun, fill], 'sun_second' [fill, sun], 'twice' [fill, sun,
+    fill, sun] (the second sun shadowed), 'all_types' (pcf_all_type_lights) or 'crowd' (pcf_crowd_lights at PCF_CROWD_W,
+    checked on pcf_crowd_mask).  The shadow light's index goes to the model and to the oracle through the shadow tuple."""
+    width = PCF_CROWD_W if lists == "crowd" else PCF_W
+    cam, lv, smap, planes = pcf_frame(vr, w_scale, width)
+    sun, fill = pcf_lights(vr)
+    mask = None
+    if lists == "all_types":
+        lights, li = pcf_all_type_lights(vr)
+    elif lists == "crowd":
+        lights, li = pcf_crowd_lights(vr)
+        mask = pcf_crowd_mask()
+    else:
+        lights, li = dict(sun_first=([sun, fill], 0), sun_second=([fill, sun], 1), twice=([fill, sun, fill, sun], 3))[lists]
+    case = TiledCase(f"PCF frame {width}, w = {w_scale}, {lists}", cam, planes, lights, ambient, shadow=(lv, smap, li, PCF_BIAS),
+                     mask=mask, exact_geometry=True, min_checked=0.99)
+    case.light_view, case.shadow_map = lv, smap
+    return case
+
+
+def tiled_terrain_case(vr, ambient, view, planes, n=40, seed=20261019):
+    """A terrain G-buffer (planes: as the tile pass left them) under all_type_lights; check()'s default caps."""
+    h, w = planes["depth"].shape
+    py, px = np.mgrid[0:h, 0:w]
+    wp = world_position(view, w, h, px, py, planes["depth"])
+    lights = all_type_lights(vr, wp, planes["depth"] < 1.0, n, seed)
+    return TiledCase(f"terrain {w}x{h}, {n} lights", view, planes, lights, ambient)

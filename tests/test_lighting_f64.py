@@ -1,12 +1,18 @@
 """Every lighting-pass kernel against the float64 model (tests/f64_shading.py): the streaming and the hinted kernel
 (with and without the spot / spherical variant), the scalar kernel for widths that are not a multiple of 4, the
-shadowed variants, the tiled pass, and the fused RenderLit on terrain frames.  No kernel is compared with another."""
+shadowed variants, the tiled pass, and the fused RenderLit on terrain frames.  No kernel is compared with another.
+
+Coverage of the instantiations vr_light_plan.h names, together with tests/test_tiled_ex_f64.py: 21 of 21 shading variants
+(LightVariant) and 4 of 4 culling variants (LightCull).  This module reaches the twelve streaming and hinted variants (the
+packed ones in test_packed_output), LV_SCALAR, LV_TILED_ROW, LV_TILED_PACKED, LC_DEPTH and LC_RANGES; test_tiled_ex_f64.py
+reaches the six EXTRA / SHADOW variants of k_deferred_tiled, LC_DEPTH_CONE and LC_RANGES_CONE."""
 import numpy as np
 import pytest
 
 import vrenderer_amd as vr
 from tests import f64_shading as fs
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
+from tests.common import hdr_rgb as _rgb, packed_frame as _packed, upload_planes as _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -23,18 +29,6 @@ def terrain(gpu_ctx):
     yield out
     for tp in out.values():
         tp.close()
-
-
-def _upload(gpu_ctx, planes):
-    h, w = planes["depth"].shape
-    rt = vr.RenderTargets(gpu_ctx).Init(w, h)
-    for k, a in planes.items():
-        rt.upload(k, a)
-    return rt
-
-
-def _rgb(hdr, w, h):
-    return hdr.download().view(np.float16).reshape(h, w, 4)[..., :3].astype(np.float64)
 
 
 def _edge(w):
@@ -130,47 +124,33 @@ def test_pcf_frame(gpu_ctx, width, w_scale, tracking):
         gpu_ctx.set_plane_tracking(True)
 
 
-def _packed(gpu_ctx, w, h, world, render):
-    """Each rank's packed tile-major output (vr_partition), de-tiled on the host into an (h, w, 3) image."""
-    from vrenderer_amd import partition as pt
-    from vrenderer_amd.passes import partition_info
-    info = partition_info(w, h, 0, world)
-    rows = (info["packed_bytes"] + 8 * 128 - 1) // (8 * 128)
-    got = np.full((h, w, 3), np.nan)
-    tx, _ = pt.owner_grid(w, h)
-    for r in range(world):
-        buf = vr.HdrImage(gpu_ctx, 128, rows)
-        render(buf, vr.Partition(r, world))
-        packed = buf.download(info["packed_bytes"]).view(np.float16).reshape(-1, 128, 128, 3)
-        for lt, tile in enumerate(pt.owned_tiles(w, h, r, world)):
-            y0, x0 = (tile // tx) * 128, (tile % tx) * 128
-            hh, ww = min(128, h - y0), min(128, w - x0)
-            got[y0:y0 + hh, x0:x0 + ww] = packed[lt, :hh, :ww]
-        buf.close()
-    return got
-
-
 @pytest.mark.parametrize("world", [1, 2, 3])
-@pytest.mark.parametrize("kind", ["stream", "hinted", "tiled", "shadow"])
+@pytest.mark.parametrize("kind", ["stream", "hinted", "tiled", "shadow", "stream_suns", "hinted_suns", "shadow_hinted"])
 def test_packed_output(gpu_ctx, world, kind):
     """The PACKED instantiations (a vr_partition of 1, 2 and 3 ranks): k_deferred_stream, k_deferred, k_deferred_tiled on
-    the edge-case frame and the shadowed stream kernel on the PCF frame, every rank's owner tiles de-tiled on the host."""
-    if kind == "shadow":
+    the edge-case frame and the shadowed stream kernel on the PCF frame, every rank's owner tiles de-tiled on the host.
+    "stream" and "hinted" run the 16-light `max` list (spot and spherical lights: LV_STREAM_PACKED_EXTRA with the tracking
+    off, LV_HINTED_PACKED_EXTRA with it on); "stream_suns" and "hinted_suns" the four suns (no spot, no spherical light, no
+    binding: LV_STREAM_PACKED with the tracking off, LV_HINTED_PACKED with it on); "shadow" runs with the tracking off
+    (LV_STREAM_PACKED_SHADOW), "shadow_hinted" with it on (a binding, the region array as a hint: LV_HINTED_PACKED_SHADOW)."""
+    if kind in ("shadow", "shadow_hinted"):
         cam, sm, planes, lights, sh = _pcf_setup(gpu_ctx, fs.PCF_W, 1.0)
+        assert all(l.type == fs.VR_LIGHT_DIRECTIONAL for l in lights)
         rt = _upload(gpu_ctx, planes)
-        gpu_ctx.set_plane_tracking(False)
+        gpu_ctx.set_plane_tracking(kind == "shadow_hinted")
         try:
             got = _packed(gpu_ctx, fs.PCF_W, fs.PCF_H, world, lambda buf, part: vr.DeferredLightingPass(gpu_ctx).Render(
                 cam, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, buf, part, shadow_map=sm))
         finally:
             gpu_ctx.set_plane_tracking(True)
         assert not np.isnan(got).any(), "every pixel belongs to one rank's tiles"
-        _pcf_check(got, planes, cam, lights, sh, fs.PCF_W, f"packed shadowed, world {world}")
+        _pcf_check(got, planes, cam, lights, sh, fs.PCF_W, f"packed shadowed ({kind}), world {world}")
         rt.close(); sm.close()
         return
     view, planes, rows, L = _edge(EDGE_W)
-    lights = L["tiled" if kind == "tiled" else "max"]
-    gpu_ctx.set_plane_tracking(kind != "stream")
+    lights = L["tiled" if kind == "tiled" else "suns" if kind.endswith("_suns") else "max"]
+    assert fs.plan_facts(lights)["extra"] == (kind in ("stream", "hinted"))
+    gpu_ctx.set_plane_tracking(not kind.startswith("stream"))
     try:
         rt = _upload(gpu_ctx, planes)
         if kind == "tiled":

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import vrenderer_amd as vr
+from tests import f64_shading as fs
 from tests import frontend_common as fc
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
 from vrenderer_amd.passes import frame_detile, partition_info
@@ -32,38 +33,9 @@ def _world_positions(view, depth):
 
 
 def _all_type_lights(wp, covered, n, seed):
-    """The list of test_deferred_spot_and_spherical_lights, extended to n lights by a fixed seed: point lights, spot lights
-    with and without a range, spherical point and spot sources, each above a covered pixel of the frame and at least 5 units
-    from every visible surface point (a light that all but touches the steep terrain would put single pixels at 10 and
-    more, where one RGBA16F ulp is larger than the whole error budget)."""
-    scale = 1.0
-    surface = wp[covered]
-    lights = [vr.reference_sun(), vr.point_light((10.0, 40.0, -5.0), 3000.0 * scale, 120.0, (1.0, 0.5, 0.25)),
-              vr.spot_light((-20.0, 60.0, 10.0), (0.3, -1.0, -0.2), 6000.0 * scale, 200.0, 12.0, 25.0, (0.2, 1.0, 0.4)),
-              vr.point_light((30.0, 35.0, -30.0), 2000.0 * scale, 150.0, (0.9, 0.9, 1.0), radius=6.0),
-              vr.spot_light((0.0, 80.0, -40.0), (0.0, -1.0, 0.3), 9000.0 * scale, 0.0, 5.0, 40.0, (1.0, 0.2, 0.2), radius=3.0)]
-    rng = np.random.default_rng(seed)
-    ys, xs = np.nonzero(covered)
-    while len(lights) < n:
-        k = rng.integers(len(ys))
-        pos = wp[ys[k], xs[k]] + np.array([rng.uniform(-3, 3), rng.uniform(6, 25), rng.uniform(-3, 3)])
-        if np.sqrt(((surface - pos) ** 2).sum(axis=1)).min() < 5.0:
-            continue
-        col, inten, rad = rng.uniform(0.1, 1.0, 3), rng.uniform(5.0, 40.0) * scale, rng.uniform(15.0, 60.0)
-        kind = len(lights) % 5
-        axis = np.array([rng.uniform(-0.5, 0.5), -1.0, rng.uniform(-0.5, 0.5)])
-        outer = rng.uniform(8.0, 70.0)
-        if kind == 0:
-            lights.append(vr.point_light(pos, inten, rad, col))
-        elif kind == 1:
-            lights.append(vr.spot_light(pos, axis, inten * 3, rad * 1.5, outer * 0.5, outer, col))
-        elif kind == 2:
-            lights.append(vr.spot_light(pos, axis, inten * 0.3, 0.0, outer * 0.6, outer, col))              # no range
-        elif kind == 3:
-            lights.append(vr.point_light(pos, inten, rad, col, radius=rng.uniform(0.5, 4.0)))
-        else:
-            lights.append(vr.spot_light(pos, axis, inten * 3, rad * 1.5, outer * 0.3, outer, col, radius=rng.uniform(0.5, 3.0)))
-    return lights
+    """The all-type list of the float64 tests (f64_shading.all_type_lights says how it is built and why every light stays 5
+    units from the surface)."""
+    return fs.all_type_lights(vr, wp, covered, n, seed)
 
 
 @pytest.fixture(scope="module")
