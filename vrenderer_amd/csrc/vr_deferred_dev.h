@@ -5,6 +5,7 @@
 #pragma once
 #include "vr_internal.h"
 #include "vr_tex_dev.h"
+#include "vr_terrain_surface.h"
 
 #include <math.h>
 
@@ -52,19 +53,48 @@ struct Surface {
     float occlusion, alpha, a2, kk, gv;
 };
 
+// What the specular plane's word decodes to.  The fused resolve of the tile pass (vr_raster.hip) knows that word before its
+// first pixel - main_ps writes one constant there - and decodes it once per lane, with decode_surface's expressions.
+struct SpecularKnown { float F0[3], occlusion; };
+__device__ __forceinline__ SpecularKnown decode_specular(const float* __restrict__ lut, uint32_t spec)
+{
+    SpecularKnown k;
+#pragma unroll
+    for (int c = 0; c < 3; c++) k.F0[c] = lut[(spec >> (8 * c)) & 255u];
+    k.occlusion = (float)(spec >> 24) * (1.0f / 255.0f);
+    return k;
+}
+
+// TERRAIN (the fused resolve only; every other caller keeps false and the code it had): the texel was encoded by
+// pixel_shader_fast a few instructions ago in this lane, so beyond albedo, normal and depth it holds the terrain's constants
+// (vr_terrain_surface.h): `known` is the specular word's decode, roughness is 1 (alpha, a2, kk are compile-time constants), the
+// emissive words are 0, and no component of the normal is the one snorm16 code (-32768) that the decode's clamp is there for.
+template <bool TERRAIN = false>
 __device__ __forceinline__ Surface decode_surface(const DeferredArgs& a, const float* __restrict__ lut, int px, int py, float depth,
-                                                  uint32_t diff, uint32_t spec, uint32_t n01, uint32_t n23, uint32_t e01, uint32_t e23)
+                                                  uint32_t diff, uint32_t spec, uint32_t n01, uint32_t n23, uint32_t e01, uint32_t e23,
+                                                  const SpecularKnown* known = nullptr)
 {
 #pragma clang fp contract(fast)
     Surface s;
+    const float sn16 = kSnorm16Scale;
+    float rough;
+    if constexpr (TERRAIN) {
 #pragma unroll
-    for (int c = 0; c < 3; c++) { s.albedo[c] = lut[(diff >> (8 * c)) & 255u]; s.F0[c] = lut[(spec >> (8 * c)) & 255u]; }
-    s.occlusion = (float)(spec >> 24) * (1.0f / 255.0f);
-    const float sn16 = 1.0f / 32767.0f;
-    s.N[0] = fmax1((float)(int16_t)(n01 & 0xffffu) * sn16, -1.0f); s.N[1] = fmax1((float)(int16_t)(n01 >> 16) * sn16, -1.0f);
-    s.N[2] = fmax1((float)(int16_t)(n23 & 0xffffu) * sn16, -1.0f);
-    const float rough = fmax1((float)(int16_t)(n23 >> 16) * sn16, -1.0f);
-    s.E[0] = vr_half_to_float(e01 & 0xffffu); s.E[1] = vr_half_to_float(e01 >> 16); s.E[2] = vr_half_to_float(e23 & 0xffffu);
+        for (int c = 0; c < 3; c++) { s.albedo[c] = lut[(diff >> (8 * c)) & 255u]; s.F0[c] = known->F0[c]; }
+        s.occlusion = known->occlusion;
+        s.N[0] = (float)(int16_t)(n01 & 0xffffu) * sn16; s.N[1] = (float)(int16_t)(n01 >> 16) * sn16;
+        s.N[2] = (float)(int16_t)(n23 & 0xffffu) * sn16;
+        rough = kTerrainRough;
+        s.E[0] = 0.0f; s.E[1] = 0.0f; s.E[2] = 0.0f;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; c++) { s.albedo[c] = lut[(diff >> (8 * c)) & 255u]; s.F0[c] = lut[(spec >> (8 * c)) & 255u]; }
+        s.occlusion = (float)(spec >> 24) * (1.0f / 255.0f);
+        s.N[0] = fmax1((float)(int16_t)(n01 & 0xffffu) * sn16, -1.0f); s.N[1] = fmax1((float)(int16_t)(n01 >> 16) * sn16, -1.0f);
+        s.N[2] = fmax1((float)(int16_t)(n23 & 0xffffu) * sn16, -1.0f);
+        rough = fmax1((float)(int16_t)(n23 >> 16) * sn16, -1.0f);
+        s.E[0] = vr_half_to_float(e01 & 0xffffu); s.E[1] = vr_half_to_float(e01 >> 16); s.E[2] = vr_half_to_float(e23 & 0xffffu);
+    }
     {
         // ReconstructWorldPosition: window -> clip -> world
         float cx, cy;
@@ -101,9 +131,12 @@ __device__ __forceinline__ Surface decode_surface(const DeferredArgs& a, const f
 #pragma unroll
     for (int c = 0; c < 3; c++) s.R[c] = s.vi[c] - s.N[c] * two;        // reflect(viewIncident, N)
     const float NdotV = fsat1(-NdotVi);
-    s.alpha = fmax1(0.01f, rough * rough);
-    s.a2 = s.alpha * s.alpha;
-    s.kk = ((rough + 1.0f) * (rough + 1.0f)) * 0.125f;
+    if constexpr (TERRAIN) { s.alpha = kTerrainAlpha; s.a2 = kTerrainA2; s.kk = kTerrainKk; }     // the expressions below, on rough = 1
+    else {
+        s.alpha = fmax1(0.01f, rough * rough);
+        s.a2 = s.alpha * s.alpha;
+        s.kk = ((rough + 1.0f) * (rough + 1.0f)) * 0.125f;
+    }
     s.gv = NdotV * (1.0f - s.kk) + s.kk;
     return s;
 }
@@ -113,6 +146,8 @@ __device__ __forceinline__ Surface decode_surface(const DeferredArgs& a, const f
 // Spot cone and spherical-source terms of ShadeSurface (only evaluated for such lights).
 struct LightExtra { float axis[3]; float radius, inner_angle, outer_angle; };
 
+// TERRAIN: s came from decode_surface<true> - s.alpha, s.a2, s.kk are vr_terrain_surface.h's constants
+template <bool TERRAIN = false>
 __device__ __forceinline__ void add_light(const Surface& s, int type, const float vec[3], float inv_range, const float color[3],
                                           float intensity, float cosH, float sinH, float tanH, float diffuseTerm[3], float specularTerm[3],
                                           const LightExtra* extra = nullptr, bool punctual = false)
@@ -168,15 +203,20 @@ __device__ __forceinline__ void add_light(const Surface& s, int type, const floa
     const float Hv[3] = { CL[0] - s.vi[0], CL[1] - s.vi[1], CL[2] - s.vi[2] };
     const float hl2 = dot3c(Hv[0], Hv[1], Hv[2], Hv[0], Hv[1], Hv[2]);
     const float hs = hl2 > 0.0f ? fast_rsq(hl2) : 0.0f;
-    const float NdotH = fsat1(dot3c(s.N[0], s.N[1], s.N[2], Hv[0], Hv[1], Hv[2]) * hs);
+    // TERRAIN: NdotH comes out of a saturate, so it is finite, and a2 - 1 is +0: dd = NdotH^2 * 0 + 1 is exactly 1, whatever
+    // NdotH is - neither is computed (the compiler may not fold fma(x, 0, 1) by itself: x could be infinite)
+    float NdotH = 0.0f;
+    if constexpr (!TERRAIN) NdotH = fsat1(dot3c(s.N[0], s.N[1], s.N[2], Hv[0], Hv[1], Hv[2]) * hs);
     const float NdotL = fsat1(dot3c(s.N[0], s.N[1], s.N[2], CL[0], CL[1], CL[2]));
     const float VdotH = fsat1(-dot3c(s.vi[0], s.vi[1], s.vi[2], Hv[0], Hv[1], Hv[2]) * hs);
     const float corrAlpha = fsat1(s.alpha + 0.5f * tanH);
-    const float dd = (NdotH * NdotH) * (s.a2 - 1.0f) + 1.0f;
+    float dd = 1.0f;
+    if constexpr (!TERRAIN) dd = (NdotH * NdotH) * (s.a2 - 1.0f) + 1.0f;
     const float gl = NdotL * (1.0f - s.kk) + s.kk;
     // D * G * NdotL / 4 * irradiance with D = a2/(pi dd^2) (alpha/corrAlpha)^2, G = 1/(gl gv)
-    const float num = (s.a2 * s.a2) * (NdotL * irr) * (0.25f * VR_INV_PI);
-    const float den = ((corrAlpha * dd) * (corrAlpha * dd)) * (gl * s.gv);
+    // (TERRAIN: a2 * a2 == 1 and dd == 1 leave both products as they are)
+    const float num = TERRAIN ? (NdotL * irr) * (0.25f * VR_INV_PI) : (s.a2 * s.a2) * (NdotL * irr) * (0.25f * VR_INV_PI);
+    const float den = TERRAIN ? (corrAlpha * corrAlpha) * (gl * s.gv) : ((corrAlpha * dd) * (corrAlpha * dd)) * (gl * s.gv);
     const float ks = num * fast_rcp(den);
     const float om = 1.0f - VdotH;
     const float om2 = om * om;
@@ -271,12 +311,14 @@ __device__ __forceinline__ float shadow_factor(const DeferredArgs& a, const Shad
 
 // EXTRA: the light list contains spot or spherical lights (compiled out of the common variant, which
 // keeps the streaming kernel at its leanest for directional / punctual lights).
-template <bool EXTRA, bool SHADOW = false>
+// TERRAIN: a texel the tile pass has just encoded (decode_surface); `known` = decode_specular of its specular word.
+template <bool EXTRA, bool SHADOW = false, bool TERRAIN = false>
 __device__ __forceinline__ void shade_pixel(const DeferredArgs& a, const float* __restrict__ lut, int px, int py, float depth,
                                             uint32_t diff, uint32_t spec, uint32_t n01, uint32_t n23, uint32_t e01, uint32_t e23,
-                                            float out[3], const ShadowArgs* sh = nullptr)
+                                            float out[3], const ShadowArgs* sh = nullptr, const SpecularKnown* known = nullptr)
 {
-    const Surface s = decode_surface(a, lut, px, py, depth, diff, spec, n01, n23, e01, e23);
+    static_assert(!TERRAIN || (!EXTRA && !SHADOW), "the fused resolve admits directional and punctual lights without a shadow term");
+    const Surface s = decode_surface<TERRAIN>(a, lut, px, py, depth, diff, spec, n01, n23, e01, e23, known);
     float diffuseTerm[3] = { 0.0f, 0.0f, 0.0f }, specularTerm[3] = { 0.0f, 0.0f, 0.0f };
     float sf = 1.0f;
     if (SHADOW) sf = shadow_factor(a, *sh, px, py, depth);
@@ -293,7 +335,7 @@ __device__ __forceinline__ void shade_pixel(const DeferredArgs& a, const float* 
             ex.radius = Lc.radius; ex.inner_angle = Lc.inner_angle; ex.outer_angle = Lc.outer_angle;
             add_light(s, Lc.type, vec, Lc.inv_range, Lc.color, Lc.intensity, Lc.cosH, Lc.sinH, Lc.tanH, diffuseTerm, specularTerm, &ex);
         } else {
-            add_light(s, Lc.type, vec, Lc.inv_range, Lc.color, Lc.intensity, Lc.cosH, Lc.sinH, Lc.tanH, diffuseTerm, specularTerm);
+            add_light<TERRAIN>(s, Lc.type, vec, Lc.inv_range, Lc.color, Lc.intensity, Lc.cosH, Lc.sinH, Lc.tanH, diffuseTerm, specularTerm);
         }
     }
     finish_pixel(a, s, diffuseTerm, specularTerm, out);

@@ -28,6 +28,7 @@
 #include "vr_raster_plan.h"
 #include "vr_tex_dev.h"
 #include "vr_deferred_dev.h"
+#include "vr_terrain_surface.h"
 #include "vr_experiments.h"
 #include <type_traits>
 
@@ -882,7 +883,7 @@ __device__ __forceinline__ void pixel_shader(const RasterArgs& a, const DevTex& 
     diffuse = vr_srgb_encode_fast(col[0], thr, enc) | (vr_srgb_encode_fast(col[1], thr, enc) << 8) | (vr_srgb_encode_fast(col[2], thr, enc) << 16)
             | 0xff000000u;                                                                  // :68, :73-75
     n01 = snorm16_finite(nx) | (snorm16_finite(ny) << 16);                                  // :78
-    n23 = snorm16_finite(nz) | (32767u << 16);                                              // :79 roughness = 1
+    n23 = snorm16_finite(nz) | (kTerrainRoughBits << 16);                                             // :79 roughness = 1
 }
 
 // Phase clocks for experiments (tools/build_variant.py prof -DVR_RASTER_PROFILE; needs -DVR_EXPERIMENT_BUILD, vr_experiments.h); not in the product build.
@@ -1036,7 +1037,7 @@ __device__ __forceinline__ void pixel_shader_fast(const RasterArgs& a, __amdgpu_
     diffuse = srgb_encode_nonneg(col[0], thr, enc) | (srgb_encode_nonneg(col[1], thr, enc) << 8) | (srgb_encode_nonneg(col[2], thr, enc) << 16)
             | 0xff000000u;                                                                  // :68, :73-75
     n01 = snorm16_unit<false>(nx) | (snorm16_unit<true>(ny) << 16);                         // :78
-    n23 = snorm16_unit<false>(nz) | (32767u << 16);                                         // :79 roughness = 1
+    n23 = snorm16_unit<false>(nz) | (kTerrainRoughBits << 16);                              // :79 roughness = 1
     VR_PROF_MARK(14);
 }
 
@@ -1209,6 +1210,11 @@ enum { RM_GENERIC = 0, RM_FAST = 1, RM_DEPTH = 2 };
 // G-buffer's formats in registers, decodes and shades it with the lighting pass's own arithmetic (shade_pixel, vr_deferred_dev.h)
 // and stores depth + HdrColor only: 12 bytes per pixel leave the pass instead of 28, and the lighting pass's 36 are not moved at
 // all.  Same bits as vr_terrain_render + vr_deferred_light.  Opt-in; the unfused pair stays the default and the graded path.
+// The pass assumes finite light and matrix inputs, as the lighting pass's clear-wave shortcut does (vr_deferred.hip): a cleared
+// texel then shades to +0 in every channel, and an uncovered pixel is given that +0 lane by lane instead of being shaded.  Every
+// pixel that IS shaded is therefore a terrain pixel the same lane has just encoded: the TERRAIN flavour of the shading
+// (vr_deferred_dev.h) takes roughness 1, the specular word's decode and the zero emissive from what is known of main_ps
+// (vr_terrain_surface.h) instead of decoding them per pixel and light - the same expressions on the same values, the same bits.
 struct LitArgs {
     DeferredArgs da;                   // the lighting pass's constants
     const float* lut_g;                // sRGB8 -> linear (256 floats)
@@ -1608,6 +1614,8 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE 
             return;
         }
     }
+    SpecularKnown known = {};                                    // the specular word's decode: the same for every terrain pixel of the launch
+    if constexpr (LIT) known = decode_specular(s_lut, spec_const);
     for (int g = skip_all ? kStrips : tid; g < kStrips; g += kRT) {
         const int lx = g % TILE, ly0 = (g / TILE) * 4;
         const int gx = ox + lx, gy0 = oy + ly0;
@@ -1674,10 +1682,14 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE 
             if constexpr (LIT) {
                 // the pixel as the lighting pass would read it back from the G-buffer: the encoded texel (a cleared one where nothing
                 // was drawn), the same decode, the same shading, the same half conversion
-                // (a wave of uncovered pixels - cleared texels - shades to +0 in every channel: vr_deferred.hip, k_deferred; wave-uniform)
+                // (a wave of uncovered pixels - cleared texels - shades to +0 in every channel: vr_deferred.hip, k_deferred; wave-uniform.
+                // The same assumption - finite light and matrix inputs - holds lane by lane: an uncovered pixel of a mixed wave is
+                // given the +0 the model arrives at on a cleared texel.  Every lane whose shading is kept is then a terrain pixel:
+                // the TERRAIN flavour of the model, the specular word's decode from `known`, vr_terrain_surface.h's roughness.)
                 float lrgb[3] = { 0.0f, 0.0f, 0.0f };
-                if (__any(cov)) shade_pixel<false>(lit.da, s_lut, gx, gy0 + k, __uint_as_float(dep), dif, cov ? spec_const : 0u, nn0, nn1, 0u, 0u, lrgb);
-                const uint32_t o0 = vr_float_to_half(lrgb[0]) | (vr_float_to_half(lrgb[1]) << 16), o1 = vr_float_to_half(lrgb[2]);
+                if (__any(cov)) shade_pixel<false, false, true>(lit.da, s_lut, gx, gy0 + k, __uint_as_float(dep), dif, spec_const, nn0, nn1, 0u, 0u, lrgb, nullptr, &known);
+                uint32_t o0 = vr_float_to_half(lrgb[0]) | (vr_float_to_half(lrgb[1]) << 16), o1 = vr_float_to_half(lrgb[2]);
+                if (!cov) { o0 = 0u; o1 = 0u; }
                 if constexpr (!KEEP) __builtin_amdgcn_raw_buffer_store_b32(dep, rgb, pix4, 0, aux);
                 if (KEEP || lit.tile_slot == nullptr) {
                     const u2 ov = { o0, o1 };
