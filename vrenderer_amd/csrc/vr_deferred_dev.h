@@ -309,20 +309,48 @@ __device__ __forceinline__ float shadow_factor(const DeferredArgs& a, const Shad
     return sum / 9.0f;
 }
 
+// The first light of the list as add_light takes it, read once per workgroup by the fused resolve of the tile pass (vr_raster.hip)
+// instead of once per pixel: the list is a kernel argument, the same for every pixel of the launch, and the reference's scene has
+// one sun in front.  vec is the vector add_light is given for the type (dir of a directional light, pos otherwise).
+struct LightFirst { float vec[3]; int type; float inv_range, color[3], intensity, cosH, sinH, tanH; int num_lights; };
+__device__ __forceinline__ LightFirst light_first(const DeferredArgs& a)
+{
+    const DevLight& Lc = a.lights[0];
+    LightFirst f;
+    const bool dir = Lc.type == VR_LIGHT_DIRECTIONAL;
+#pragma unroll
+    for (int c = 0; c < 3; c++) { f.vec[c] = dir ? Lc.dir[c] : Lc.pos[c]; f.color[c] = Lc.color[c]; }
+    f.type = Lc.type; f.inv_range = Lc.inv_range; f.intensity = Lc.intensity;
+    f.cosH = Lc.cosH; f.sinH = Lc.sinH; f.tanH = Lc.tanH;
+    f.num_lights = a.num_lights;
+    return f;
+}
+
 // EXTRA: the light list contains spot or spherical lights (compiled out of the common variant, which
 // keeps the streaming kernel at its leanest for directional / punctual lights).
-// TERRAIN: a texel the tile pass has just encoded (decode_surface); `known` = decode_specular of its specular word.
+// TERRAIN: a texel the tile pass has just encoded (decode_surface); `known` = decode_specular of its specular word, `first` =
+// light_first of the list (shaded first, as the loop would; a list without lights shades none).
 template <bool EXTRA, bool SHADOW = false, bool TERRAIN = false>
 __device__ __forceinline__ void shade_pixel(const DeferredArgs& a, const float* __restrict__ lut, int px, int py, float depth,
                                             uint32_t diff, uint32_t spec, uint32_t n01, uint32_t n23, uint32_t e01, uint32_t e23,
-                                            float out[3], const ShadowArgs* sh = nullptr, const SpecularKnown* known = nullptr)
+                                            float out[3], const ShadowArgs* sh = nullptr, const SpecularKnown* known = nullptr,
+                                            const LightFirst* first = nullptr)
 {
     static_assert(!TERRAIN || (!EXTRA && !SHADOW), "the fused resolve admits directional and punctual lights without a shadow term");
     const Surface s = decode_surface<TERRAIN>(a, lut, px, py, depth, diff, spec, n01, n23, e01, e23, known);
     float diffuseTerm[3] = { 0.0f, 0.0f, 0.0f }, specularTerm[3] = { 0.0f, 0.0f, 0.0f };
     float sf = 1.0f;
     if (SHADOW) sf = shadow_factor(a, *sh, px, py, depth);
-    for (int i = 0; i < a.num_lights; i++) {
+    int i0 = 0, n = a.num_lights;
+    if constexpr (TERRAIN) {
+        // light 0 from the workgroup's registers: a scalar branch on its type, no load; an early return inside add_light
+        // (att == 0) leaves this light only.  Lights 1 .. n - 1 follow in the list's order, from the kernel arguments.
+        n = first->num_lights;
+        if (n > 0) add_light<true>(s, first->type, first->vec, first->inv_range, first->color, first->intensity, first->cosH, first->sinH,
+                                   first->tanH, diffuseTerm, specularTerm);
+        i0 = 1;
+    }
+    for (int i = i0; i < n; i++) {
         const DevLight& Lc = a.lights[i];
         const float* vec = Lc.type == VR_LIGHT_DIRECTIONAL ? Lc.dir : Lc.pos;
         if (SHADOW && i == sh->light_index) {          // a directional light (checked on the host): irradiance = intensity * shadow

@@ -1492,8 +1492,12 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE 
     const bool depth_only = DEPTH || (!FAST && a.depth_only != 0);
     const __amdgpu_buffer_rsrc_t rq = FAST ? __builtin_amdgcn_make_buffer_rsrc((void*)hm.fast, (short)0, (int)hm.fast_bytes, 0x00020000)
                                            : __builtin_amdgcn_make_buffer_rsrc((void*)hm.quadf, (short)0, (int)(hm.quad_bytes * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rc = FAST ? __builtin_amdgcn_make_buffer_rsrc((void*)al.fast, (short)0, (int)al.fast_bytes, 0x00020000)
-                                           : __builtin_amdgcn_make_buffer_rsrc((void*)al.rgbf, (short)0, (int)(al.chain_bytes * 4u), 0x00020000);
+    __amdgpu_buffer_rsrc_t rc = FAST ? __builtin_amdgcn_make_buffer_rsrc((void*)al.fast, (short)0, (int)al.fast_bytes, 0x00020000)
+                                     : __builtin_amdgcn_make_buffer_rsrc((void*)al.rgbf, (short)0, (int)(al.chain_bytes * 4u), 0x00020000);
+    // fused flavours: the descriptor stays formed.  Its fourth dword is the same constant as rq's; seeing that, the compiler kept one
+    // copy, and under the resolve's scalar register pressure restored rc from spill lanes, replaced that dword and wrote rc back in
+    // every pixel body (4 v_readlane + 4 v_writelane per pixel).  Opaque, it is four registers for the whole resolve.
+    if constexpr (LIT) asm volatile("" : "+s"(rc));
     // targets through one buffer resource when the planes lie within 4 GB of the depth plane (a vr_gbuffer of up to 16K x 8K;
     // the host launches the fast variant only then)
     const uint64_t gb_span = (uint64_t)(reinterpret_cast<const char*>(g_emi + (size_t)a.w * a.h) - reinterpret_cast<const char*>(g_depth));
@@ -1615,7 +1619,8 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE 
         }
     }
     SpecularKnown known = {};                                    // the specular word's decode: the same for every terrain pixel of the launch
-    if constexpr (LIT) known = decode_specular(s_lut, spec_const);
+    LightFirst first = {};                                       // the list's first light: kernel arguments, read here and not per pixel
+    if constexpr (LIT) { known = decode_specular(s_lut, spec_const); first = light_first(lit.da); }
     for (int g = skip_all ? kStrips : tid; g < kStrips; g += kRT) {
         const int lx = g % TILE, ly0 = (g / TILE) * 4;
         const int gx = ox + lx, gy0 = oy + ly0;
@@ -1687,7 +1692,7 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE 
                 // given the +0 the model arrives at on a cleared texel.  Every lane whose shading is kept is then a terrain pixel:
                 // the TERRAIN flavour of the model, the specular word's decode from `known`, vr_terrain_surface.h's roughness.)
                 float lrgb[3] = { 0.0f, 0.0f, 0.0f };
-                if (__any(cov)) shade_pixel<false, false, true>(lit.da, s_lut, gx, gy0 + k, __uint_as_float(dep), dif, spec_const, nn0, nn1, 0u, 0u, lrgb, nullptr, &known);
+                if (__any(cov)) shade_pixel<false, false, true>(lit.da, s_lut, gx, gy0 + k, __uint_as_float(dep), dif, spec_const, nn0, nn1, 0u, 0u, lrgb, nullptr, &known, &first);
                 uint32_t o0 = vr_float_to_half(lrgb[0]) | (vr_float_to_half(lrgb[1]) << 16), o1 = vr_float_to_half(lrgb[2]);
                 if (!cov) { o0 = 0u; o1 = 0u; }
                 if constexpr (!KEEP) __builtin_amdgcn_raw_buffer_store_b32(dep, rgb, pix4, 0, aux);
