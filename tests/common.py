@@ -33,18 +33,27 @@ def hdr_rgb(hdr, w, h):
     return hdr.download().view(np.float16).reshape(h, w, 4)[..., :3].astype(np.float64)
 
 
+def packed_hdr(ctx, w, h, part):
+    """An HdrImage that holds a rank's packed RGB16F tiles of a w x h frame (VR_OWNER_TILE pixels wide, as many rows as
+    vr_partition_packed_bytes() needs), and the number of bytes of it that `part`'s own tiles occupy."""
+    from vrenderer_amd.passes import partition_info
+    info = partition_info(w, h, part.rank, part.world_size)
+    rows = (info["packed_bytes"] + vr.VR_OWNER_TILE * 8 - 1) // (vr.VR_OWNER_TILE * 8)
+    return vr.HdrImage(ctx, vr.VR_OWNER_TILE, rows), info["owned"] * 128 * 128 * 6
+
+
 def packed_frame(gpu_ctx, w, h, world, render):
     """Each rank's packed tile-major output (vr_partition; render(buffer, partition) queues one rank's pass), de-tiled on the
     host into an (h, w, 3) image."""
     from vrenderer_amd import partition as pt
     from vrenderer_amd.passes import partition_info
     info = partition_info(w, h, 0, world)
-    rows = (info["packed_bytes"] + 8 * 128 - 1) // (8 * 128)
     got = np.full((h, w, 3), np.nan)
     tx, _ = pt.owner_grid(w, h)
     for r in range(world):
-        buf = vr.HdrImage(gpu_ctx, 128, rows)
-        render(buf, vr.Partition(r, world))
+        part = vr.Partition(r, world)
+        buf, _ = packed_hdr(gpu_ctx, w, h, part)
+        render(buf, part)
         packed = buf.download(info["packed_bytes"]).view(np.float16).reshape(-1, 128, 128, 3)
         for lt, tile in enumerate(pt.owned_tiles(w, h, r, world)):
             y0, x0 = (tile // tx) * 128, (tile % tx) * 128

@@ -3,6 +3,7 @@ declares, its pure-host entry points behave, and it fails loudly without a GPU."
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -11,6 +12,7 @@ import vrenderer_amd as vr
 from vrenderer_amd import capi
 from vrenderer_amd import partition as pt
 from tests.common import DEFAULT_EYE, DEFAULT_TARGET
+from tests.host_check import build_host_check, run_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -161,7 +163,6 @@ def test_pack_detile_roundtrip_numpy():
 
 
 def _build_host_example(tmpdir):
-    import subprocess
     exe = os.path.join(str(tmpdir), "frame_example")
     lib_dir = os.path.join(ROOT, "vrenderer_amd", "lib")
     cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
@@ -173,7 +174,6 @@ def _build_host_example(tmpdir):
 
 def test_cpp_host_example_compiles_links_and_fails_soft_without_gpu(product_lib, tmp_path):
     """The header is usable from C++ and the library links; without a device the example reports it."""
-    import subprocess
     exe = _build_host_example(tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     if _has_gpu(product_lib):
@@ -185,13 +185,8 @@ def test_cpp_host_example_compiles_links_and_fails_soft_without_gpu(product_lib,
 def test_raster_plan_matches_the_transcribed_decisions_and_invariants(tmp_path):
     """vr_raster_plan.h compiles without HIP and raster_plan() agrees, for every input, with the tile pass's decisions as
     they were written inside terrain_render_impl, and with the invariants of tests/host/raster_plan_check.cpp."""
-    import subprocess
-    exe = os.path.join(str(tmp_path), "raster_plan_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "raster_plan_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    exe = build_host_check(tmp_path, "raster_plan_check")
+    r = run_host_check(exe)
     assert "786432 cases" in r.stdout, r.stdout[-400:]          # 2^16 bools x 2 worlds x 2 tile edges x 3 requests
 
 
@@ -199,13 +194,8 @@ def test_devbuf_grow_is_all_or_nothing_at_every_failure_position(tmp_path):
     """vr_devbuf.h compiles without HIP; a single grow and group grows of 1..15 buffers keep every pointer, capacity and live
     block on a failure at any allocation (or a refusing quiesce) and free each old block once, behind quiesce, on success
     (tests/host/devbuf_check.cpp)."""
-    import subprocess
-    exe = os.path.join(str(tmp_path), "devbuf_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "devbuf_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    exe = build_host_check(tmp_path, "devbuf_check")
+    r = run_host_check(exe)
     assert "1152 cases" in r.stdout, r.stdout[-400:]            # single: 3 x 6 x 2 x 2; groups: 4 patterns x 2 x (N + 1), N = 1..15
 
 
@@ -214,16 +204,10 @@ def test_stream_order_matches_the_transcribed_protocol_and_the_happens_before_mo
     (tests/host/order_check.cpp) the protocol queues the records and waits the ordering code it replaced queued, apart from the
     intended differences the program names, and no two conflicting accesses to a geometry set, the node heights or an HDR image
     are left unordered by the streams' vector clocks; a transcription that loses any one wait but the start hint's is reported."""
-    import subprocess
-    exe = os.path.join(str(tmp_path), "order_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "order_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    exe = build_host_check(tmp_path, "order_check")
+    r = run_host_check(exe)
     assert "404204 sequences" in r.stdout, r.stdout[-400:]      # 21 + 21^2 + 21^3 + 21^4 of 21 calls, 200000 random
-    r = subprocess.run([exe, "--drop-each"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "16 of 17 wait sites reported" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    run_host_check(exe, "--drop-each", expect="16 of 17 wait sites reported")
 
 
 def test_scratch_policy_matches_the_transcribed_code_and_its_invariants(tmp_path):
@@ -231,13 +215,8 @@ def test_scratch_policy_matches_the_transcribed_code_and_its_invariants(tmp_path
     (tests/host/scratch_check.cpp: chains completing with boundary status words, polls, synchronous reads, reserves, a granting
     or refusing allocator) its functions leave the state, return the codes, request the allocations and pick the messages of
     the code they replaced, and keep the capacity, reporting and refusal invariants the program names."""
-    import subprocess
-    exe = os.path.join(str(tmp_path), "scratch_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "scratch_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    exe = build_host_check(tmp_path, "scratch_check")
+    r = run_host_check(exe)
     # 12 configurations x (730 + 730^2 of 730 events, 20000 random); 730 = 3 sets x 6 x 8 x 5 words + 2 + 2 + 4 + 2
     assert "6643560 sequences" in r.stdout, r.stdout[-400:]
 
@@ -249,21 +228,14 @@ def test_gbuffer_state_matches_the_transcribed_code_and_the_memory_model(tmp_pat
     transitions leave the state, the answers and the fills of the code they replaced, apart from the two intended differences
     the program names, and the memory they describe is what it would be with every clear eager and nothing skipped; each
     transition weakened in turn is reported."""
-    import subprocess
-    exe = os.path.join(str(tmp_path), "gbuffer_state_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "gbuffer_state_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    exe = build_host_check(tmp_path, "gbuffer_state_check")
+    r = run_host_check(exe)
     # 2089 + 2089^2 of all events, 57 + .. + 57^4 of the smaller set, 200000 random
     assert "15310510 sequences" in r.stdout, r.stdout[-400:]
-    r = subprocess.run([exe, "--break-each"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "15 of 15 weakenings reported" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    run_host_check(exe, "--break-each", expect="15 of 15 weakenings reported")
 
 
 def _build_allgather_example(tmpdir):
-    import subprocess
     exe = os.path.join(str(tmpdir), "frame_allgather_example")
     lib_dir = os.path.join(ROOT, "vrenderer_amd", "lib")
     cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
@@ -276,7 +248,6 @@ def _build_allgather_example(tmpdir):
 def test_cpp_allgather_example_compiles_and_fails_soft_without_gpu(product_lib, tmp_path):
     """The N-rank C++ host (RCCL communicator + vr_frame_allgather_ldr + vr_tonemap_allreduce_histogram) builds against
     rccl.h and the C ABI; without a device it says so."""
-    import subprocess
     exe = _build_allgather_example(tmp_path)
     if _has_gpu(product_lib):
         pytest.skip("run by the GPU suite")
@@ -286,13 +257,11 @@ def test_cpp_allgather_example_compiles_and_fails_soft_without_gpu(product_lib, 
 
 def test_library_does_not_link_rccl(product_lib):
     """RCCL is resolved at first use from the copy in the process (vr_comm.hip): no DT_NEEDED entry for it."""
-    import subprocess
     out = subprocess.run(["readelf", "-d", os.path.join(ROOT, "vrenderer_amd", "lib", "libvrterrain.so")], capture_output=True, text=True).stdout
     assert "rccl" not in out.lower(), out
 
 
 def test_header_is_valid_c(tmp_path):
-    import subprocess
     src = tmp_path / "c_check.c"
     src.write_text('#include <vrterrain.h>\nint main(void) { vr_view v; vr_light l; (void)v; (void)l; return sizeof(vr_instance) == 112 ? 0 : 1; }\n')
     subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o",
@@ -302,7 +271,6 @@ def test_header_is_valid_c(tmp_path):
 
 def test_ctypes_mirrors_have_the_header_s_struct_sizes(tmp_path):
     """The ctypes structures of vrenderer_amd/capi.py against sizeof() of the C declarations they mirror."""
-    import subprocess
     from vrenderer_amd import capi
     pairs = [("vr_view", capi.View), ("vr_light", capi.Light), ("vr_instance", capi.Instance), ("vr_terrain_params", capi.TerrainParams),
              ("vr_render_params", capi.RenderParams), ("vr_partition", capi.Partition), ("vr_shadow_params", capi.ShadowParams),

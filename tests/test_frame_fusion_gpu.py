@@ -6,95 +6,31 @@ import pytest
 
 import vrenderer_amd as vr
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, flythrough_camera, params, scaled_camera
+from tests.fusion_common import (FUSED, LIGHTING, PLANES, assert_same_frames, download_frame, submit_frames,
+                                 terrain_fixture)
 
 pytestmark = pytest.mark.gpu
-
-FUSED, LIGHTING = "k_raster (fused with lighting)", "k_deferred"
-PLANES = ("depth", "diffuse", "specular", "normals", "emissive")
 
 
 @pytest.fixture(scope="module")
 def fx(product_lib):
-    """A context of this module's own (the option is per context) with a 256^2 terrain."""
-    ctx = vr.Context(0)
-    size = 256
-    h = vr.synth_heightmap(ctx, size)
-    a = vr.synth_albedo(ctx, size, h)
-    tp = vr.TerrainPass(ctx, params(size)).Init(h, a)
-    yield dict(ctx=ctx, tp=tp, h=h, size=size)
-    tp.close()
-    ctx.close()
+    with terrain_fixture(256) as f:
+        yield f
 
 
 def _fly(i, w, h, size=256):
     return vr.make_view(*scaled_camera(flythrough_camera(i), size), w, h)
 
 
-def _frames(fx, fusion, w, h, views, lights=None, clear=False, before=None, ahead=0, part=None, tiled=False, tile=0, **rpkw):
-    """Renders `views` one after the other into fresh targets through vr_frame_submit; per frame: everything the frame left
-    behind and which of the two kernels ran."""
-    ctx, tp = fx["ctx"], fx["tp"]
-    lights = [vr.reference_sun()] if lights is None else lights
-    rpkw.setdefault("assume_cleared", 1)
-    rp = vr.default_render_params(400.0, **rpkw)
-    ctx.set_frame_fusion(fusion)
-    ctx.set_raster_tile(tile)
-    rt = vr.RenderTargets(ctx).Init(w, h)
-    if part is None:
-        hdr, nbytes = vr.HdrImage(ctx, w, h), None
-    else:
-        from vrenderer_amd.passes import partition_info
-        info = partition_info(w, h, part.rank, part.world_size)
-        rows = (info["packed_bytes"] + vr.VR_OWNER_TILE * 8 - 1) // (vr.VR_OWNER_TILE * 8)
-        hdr, nbytes = vr.HdrImage(ctx, vr.VR_OWNER_TILE, rows), info["owned"] * 128 * 128 * 6
-    hdr.upload(np.zeros(hdr.width * hdr.height * 4, np.uint16))
-    fr = vr.Frame(tp, rt, rp, lights, AMBIENT_TOP, AMBIENT_BOTTOM, part, tiled)
-    out = []
-    try:
-        for i, v in enumerate(views):
-            if clear:
-                rt.Clear()
-            if before is not None:
-                before(i, rt)
-            ctx.timing_enable(2)
-            fr.submit(v, hdr, views[i + 1:i + 1 + ahead])
-            ctx.synchronize()
-            ran = ctx.timing_collect()
-            ctx.timing_enable(0)
-            f = {p: rt.download(p).copy() for p in PLANES}
-            f["hdr"] = hdr.download(nbytes).copy()
-            f["census"] = rt.region_census()
-            f["emissive_known_zero"] = rt.plane_known_zero("emissive")
-            f["fused"], f["lighting"] = FUSED in ran, LIGHTING in ran
-            assert not (f["fused"] and f["lighting"]), sorted(ran)
-            out.append(f)
-    finally:
-        ctx.set_frame_fusion(1)
-        ctx.set_raster_tile(0)
-        hdr.close()
-        rt.close()
-    return out
-
-
-def _same(want, got, what):
-    assert len(want) == len(got)
-    for i, (a, b) in enumerate(zip(want, got)):
-        for p in PLANES + ("hdr",):
-            x, y = a[p].view(np.uint32 if a[p].dtype == np.float32 else a[p].dtype), b[p].view(np.uint32 if b[p].dtype == np.float32 else b[p].dtype)
-            assert np.array_equal(x, y), f"{what}: frame {i}, {p} differs in {(x != y).sum()} elements"
-        assert a["census"] == b["census"], f"{what}: frame {i}, region census {a['census']} != {b['census']}"
-        assert a["emissive_known_zero"] == b["emissive_known_zero"], f"{what}: frame {i}, emissive plane knowledge"
-
-
 def _both(fx, what, expect_fused, *args, **kw):
     """The same frames with the option off (reference) and on; expect_fused: per frame, or one value for all."""
-    off, on = _frames(fx, 0, *args, **kw), _frames(fx, 1, *args, **kw)
+    off, on = submit_frames(fx, 0, *args, **kw), submit_frames(fx, 1, *args, **kw)
     assert not any(f["fused"] for f in off), what + ": the option is off and a frame was fused"
     exp = expect_fused if isinstance(expect_fused, (list, tuple)) else [expect_fused] * len(on)
     assert [f["fused"] for f in on] == list(exp), what + f": fused frames {[f['fused'] for f in on]}"
     if not kw.get("tiled"):         # a frame that is not fused launches the lighting pass
         assert all(f["fused"] != f["lighting"] for f in off + on), what
-    _same(off, on, what)
+    assert_same_frames(off, on, what)
     return off, on
 
 
@@ -147,7 +83,7 @@ def test_light_lists(fx):
     _both(fx, "17 lights (tiled)", False, w, h, views, lights=[sun] + pts, tiled=True)
     for fusion in (0, 1):
         with pytest.raises(Exception, match="16 lights"):
-            _frames(fx, fusion, w, h, views[:1], lights=[sun] + pts)
+            submit_frames(fx, fusion, w, h, views[:1], lights=[sun] + pts)
     spot = vr.spot_light((-2.5, 7.5, 1.25), (0.3, -1.0, -0.2), 6000.0, 25.0, 12.0, 25.0, (0.2, 1.0, 0.4))
     _both(fx, "spot light", False, w, h, views, lights=[sun, spot])
 
@@ -177,14 +113,14 @@ def test_ineligible_render_params_fall_back(fx):
             ran = ctx.timing_collect()
             ctx.timing_enable(0)
             assert LIGHTING in ran and FUSED not in ran, sorted(ran)
-            f = {p: rt.download(p).copy() for p in PLANES}
-            f.update(hdr=hdr.download().copy(), census=rt.region_census(), emissive_known_zero=rt.plane_known_zero("emissive"))
+            f = download_frame(rt, hdr)
+            f.update(census=rt.region_census(), emissive_known_zero=rt.plane_known_zero("emissive"))
             outs.append([f])
         finally:
             ctx.set_frame_fusion(1)
             hdr.close()
             rt.close()
-    _same(outs[0], outs[1], "assume_cleared = 0 over a drawn target")
+    assert_same_frames(outs[0], outs[1], "assume_cleared = 0 over a drawn target")
 
 
 @pytest.mark.parametrize("w,h", [(256, 144), (1024, 576)])
@@ -253,8 +189,8 @@ def test_prepare_two_frames_ahead(fx):
     w, h = 256, 144
     views = [_fly(i, w, h) for i in range(4)]
     off, on = _both(fx, "two frames ahead", True, w, h, views, ahead=2)
-    _same(on, _frames(fx, 1, w, h, views), "prepared ahead vs not prepared")
-    _same(off, _frames(fx, 0, w, h, views), "prepared ahead vs not prepared (option off)")
+    assert_same_frames(on, submit_frames(fx, 1, w, h, views), "prepared ahead vs not prepared")
+    assert_same_frames(off, submit_frames(fx, 0, w, h, views), "prepared ahead vs not prepared (option off)")
 
 
 def test_one_8k_frame():

@@ -12,12 +12,12 @@ import numpy as np
 import pytest
 
 import vrenderer_amd as vr
-from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, flythrough_camera, params, scaled_camera
+from tests.common import flythrough_camera, scaled_camera
+from tests.fusion_common import (PLANES, assert_same_bits, assert_same_frame, expect_kernels, region_kinds, render_lit,
+                                 submit_frames, terrain_fixture)
 
 pytestmark = pytest.mark.gpu
 
-FUSED, LIGHTING = "k_raster (fused with lighting)", "k_deferred"
-PLANES = ("depth", "diffuse", "specular", "normals", "emissive")
 SIZES = [(96, 64), (70, 50), (68, 50)]
 SIZE = 64
 MAX_HEIGHT = 400.0
@@ -25,13 +25,8 @@ MAX_HEIGHT = 400.0
 
 @pytest.fixture(scope="module")
 def fx(product_lib):
-    ctx = vr.Context(0)
-    h = vr.synth_heightmap(ctx, SIZE)
-    a = vr.synth_albedo(ctx, SIZE, h)
-    tp = vr.TerrainPass(ctx, params(SIZE)).Init(h, a)
-    yield dict(ctx=ctx, tp=tp, h=h, views={}, unfused={})
-    tp.close()
-    ctx.close()
+    with terrain_fixture(SIZE) as f:
+        yield dict(f, views={}, unfused={})
 
 
 def _sun():
@@ -77,39 +72,17 @@ LISTS = {
 CASES = [(w, h, name) for (w, h) in SIZES for name in LISTS]
 
 
-def _region_kinds(depth):
-    h, w = depth.shape
-    cov = depth < 1.0
-    k = dict(terrain=0, sky=0, mixed=0)
-    for y in range(0, h, 8):
-        for x in range(0, w, 32):
-            r = cov[y:y + 8, x:x + 32]
-            k["terrain" if r.all() else "mixed" if r.any() else "sky"] += 1
-    return k
-
-
 def _submit(fx, fusion, w, h, v, lights, expect_fused=None):
-    """One frame through vr_frame_submit into fresh targets: everything the frame left behind."""
-    ctx, tp = fx["ctx"], fx["tp"]
-    expect_fused = (bool(fusion) and w % 4 == 0) if expect_fused is None else expect_fused
-    ctx.set_frame_fusion(fusion)
-    rt, hdr = vr.RenderTargets(ctx).Init(w, h), vr.HdrImage(ctx, w, h)
-    fr = vr.Frame(tp, rt, vr.default_render_params(MAX_HEIGHT, assume_cleared=1), lights, AMBIENT_TOP, AMBIENT_BOTTOM)
-    try:
-        hdr.upload(np.full(w * h * 4, 0x3c00, np.uint16))
-        ctx.timing_enable(2)
-        fr.submit(v, hdr)
-        ctx.synchronize()
-        ran = ctx.timing_collect()
-        ctx.timing_enable(0)
-        assert (FUSED in ran) == expect_fused and (LIGHTING in ran) != expect_fused, sorted(ran)
-        f = {p: rt.download(p).copy() for p in PLANES}
-        f.update(hdr=hdr.download().copy(), census=rt.region_census())
-    finally:
-        ctx.set_frame_fusion(1)
-        hdr.close()
-        rt.close()
-    return f
+    """One frame through vr_frame_submit over an HdrColor of 0x3c00: everything the frame left behind.  Unless told otherwise,
+    the fused kernel ran exactly when the option is on and the width is a multiple of four."""
+    frames = submit_frames(fx, fusion, w, h, [v], lights, hdr_fill=0x3c00)
+    expect_kernels(frames, (bool(fusion) and w % 4 == 0) if expect_fused is None else expect_fused, f"{w}x{h}, fusion {fusion}")
+    return frames[0]
+
+
+def _render_lit(fx, w, h, v, lights):
+    """(HdrColor, depth) of vr_terrain_render_lit, whole frame, over an HdrColor of 0x3c00."""
+    return render_lit(fx["ctx"], fx["tp"], v, w, h, lights, hdr_fill=0x3c00)
 
 
 def _view(fx, w, h):
@@ -118,7 +91,7 @@ def _view(fx, w, h):
         found = None
         for i in range(8):
             v = vr.make_view(*scaled_camera(flythrough_camera(i), SIZE), w, h)
-            k = _region_kinds(_submit(fx, 0, w, h, v, [])["depth"])
+            k = region_kinds(_submit(fx, 0, w, h, v, [])["depth"])
             if k["terrain"] > 0 and k["sky"] > 0 and k["mixed"] > 0:
                 found = v
                 break
@@ -139,34 +112,14 @@ def _unfused(fx, w, h, name):
     return fx["unfused"][key]
 
 
-def _render_lit(fx, w, h, v, lights):
-    """(HdrColor, depth) of vr_terrain_render_lit, whole frame."""
-    ctx, tp = fx["ctx"], fx["tp"]
-    rt, hdr = vr.RenderTargets(ctx).Init(w, h), vr.HdrImage(ctx, w, h)
-    try:
-        hdr.upload(np.full(w * h * 4, 0x3c00, np.uint16))
-        tp.RenderLit(v, rt, vr.default_render_params(MAX_HEIGHT, assume_cleared=1), lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
-        return hdr.download().copy(), rt.download("depth").copy()
-    finally:
-        hdr.close()
-        rt.close()
-
-
-def _same(a, b, what):
-    x, y = np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)
-    assert x.shape == y.shape and np.array_equal(x, y), f"{what} differs in {(x != y).sum()} bytes"
-
-
 @pytest.mark.parametrize("w,h,name", CASES)
 def test_keep_flavour_equals_unfused_pair(fx, w, h, name):
     """vr_frame_submit with fusion on: HdrColor, the five planes and the region census are those of the unfused pair."""
     want = _unfused(fx, w, h, name)
-    k = _region_kinds(want["depth"])
+    k = region_kinds(want["depth"])
     assert k["terrain"] > 0 and k["sky"] > 0 and k["mixed"] > 0, k
     got = _submit(fx, 1, w, h, _view(fx, w, h), LISTS[name](fx["h"]))
-    for p in ("hdr",) + PLANES:
-        _same(want[p], got[p], f"{name}, {w}x{h}: {p}")
-    assert want["census"] == got["census"], f"{name}, {w}x{h}: region census {want['census']} != {got['census']}"
+    assert_same_frame(want, got, f"{name}, {w}x{h}", ("hdr",) + PLANES + ("census",))
     cov = want["depth"] < 1.0
     lit = want["hdr"].reshape(h, w, 4)[cov][:, :3].any()
     assert lit, f"{name}: no terrain pixel is lit (the ambient term alone lights them)"
@@ -177,8 +130,8 @@ def test_lit_flavour_equals_unfused_pair(fx, w, h, name):
     """vr_terrain_render_lit: HdrColor and depth are those of the unfused pair."""
     want = _unfused(fx, w, h, name)
     hdr, depth = _render_lit(fx, w, h, _view(fx, w, h), LISTS[name](fx["h"]))
-    _same(want["depth"], depth, f"{name}, {w}x{h}: depth")
-    _same(want["hdr"], hdr, f"{name}, {w}x{h}: HdrColor")
+    assert_same_bits(want["depth"], depth, f"{name}, {w}x{h}: depth")
+    assert_same_bits(want["hdr"], hdr, f"{name}, {w}x{h}: HdrColor")
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -192,8 +145,8 @@ def test_out_of_range_first_light_leaves_the_sun_alone(fx, w, h):
     n_keep = int((keep["hdr"].view(np.uint16) != sun["hdr"].view(np.uint16)).sum())
     n_lit = int((hdr.view(np.uint16) != sun["hdr"].view(np.uint16)).sum())
     print(f"{w}x{h}: halfs that differ from the sun alone: frame submit {n_keep}, render_lit {n_lit} of {sun['hdr'].size}")
-    _same(sun["hdr"], keep["hdr"], f"{w}x{h}: frame submit, out-of-range light + sun against the sun alone")
-    _same(sun["hdr"], hdr, f"{w}x{h}: render_lit, out-of-range light + sun against the sun alone")
+    assert_same_bits(sun["hdr"], keep["hdr"], f"{w}x{h}: frame submit, out-of-range light + sun against the sun alone")
+    assert_same_bits(sun["hdr"], hdr, f"{w}x{h}: render_lit, out-of-range light + sun against the sun alone")
     assert sun["hdr"].reshape(h, w, 4)[sun["depth"] < 1.0][:, :3].any()
 
 
@@ -207,5 +160,4 @@ def test_spot_or_spherical_first_light_is_queued_unfused(fx, kind):
     v = _view(fx, w, h)
     off = _submit(fx, 0, w, h, v, lights)
     on = _submit(fx, 1, w, h, v, lights, expect_fused=False)          # asserts: k_deferred ran, the fused kernel did not
-    for p in ("hdr",) + PLANES:
-        _same(off[p], on[p], f"{kind} first, {p}")
+    assert_same_frame(off, on, f"{kind} first", ("hdr",) + PLANES)

@@ -9,12 +9,11 @@ import numpy as np
 import pytest
 
 import vrenderer_amd as vr
-from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, flythrough_camera, params, scaled_camera, upload_planes
+from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, flythrough_camera, scaled_camera, upload_planes
+from tests.fusion_common import assert_same_frames, expect_kernels, lit_pair, region_kinds, submit_frames, terrain_fixture
 
 pytestmark = pytest.mark.gpu
 
-FUSED, LIGHTING = "k_raster (fused with lighting)", "k_deferred"
-PLANES = ("depth", "diffuse", "specular", "normals", "emissive")
 SIZES = [(256, 144), (252, 132)]
 VIEWS = (0, 7)
 SIZE = 256
@@ -22,13 +21,8 @@ SIZE = 256
 
 @pytest.fixture(scope="module")
 def fx(product_lib):
-    ctx = vr.Context(0)
-    h = vr.synth_heightmap(ctx, SIZE)
-    a = vr.synth_albedo(ctx, SIZE, h)
-    tp = vr.TerrainPass(ctx, params(SIZE)).Init(h, a)
-    yield dict(ctx=ctx, tp=tp, h=h)
-    tp.close()
-    ctx.close()
+    with terrain_fixture(SIZE) as f:
+        yield f
 
 
 def _view(i, w, h):
@@ -61,78 +55,11 @@ LIST_NAMES = ["reference sun", "sun of zero angular size", "sun and a point ligh
               "a light of intensity 0"]
 
 
-def _region_kinds(depth):
-    """Number of 8-row x 32-pixel regions (a wave's share of a 32-pixel tile) that are all terrain / all sky / mixed."""
-    h, w = depth.shape
-    cov = depth < 1.0
-    k = dict(terrain=0, sky=0, mixed=0)
-    for y in range(0, h, 8):
-        for x in range(0, w, 32):
-            r = cov[y:y + 8, x:x + 32]
-            k["terrain" if r.all() else "mixed" if r.any() else "sky"] += 1
-    return k
-
-
 def _submit(fx, fusion, w, h, views, lights):
-    """`views` one after the other through vr_frame_submit into fresh targets; per frame everything the frame left behind."""
-    ctx, tp = fx["ctx"], fx["tp"]
-    ctx.set_frame_fusion(fusion)
-    rt, hdr = vr.RenderTargets(ctx).Init(w, h), vr.HdrImage(ctx, w, h)
-    fr = vr.Frame(tp, rt, vr.default_render_params(400.0, assume_cleared=1), lights, AMBIENT_TOP, AMBIENT_BOTTOM)
-    out = []
-    try:
-        for v in views:
-            hdr.upload(np.full(w * h * 4, 0x3c00, np.uint16))
-            ctx.timing_enable(2)
-            fr.submit(v, hdr)
-            ctx.synchronize()
-            ran = ctx.timing_collect()
-            ctx.timing_enable(0)
-            assert (FUSED in ran) == bool(fusion) and (LIGHTING in ran) != bool(fusion), sorted(ran)
-            f = {p: rt.download(p).copy() for p in PLANES}
-            f.update(hdr=hdr.download().copy(), census=rt.region_census(), emissive_known_zero=rt.plane_known_zero("emissive"))
-            out.append(f)
-    finally:
-        ctx.set_frame_fusion(1)
-        hdr.close()
-        rt.close()
-    return out
-
-
-def _same_frames(want, got, what):
-    for i, (a, b) in enumerate(zip(want, got)):
-        for p in PLANES + ("hdr",):
-            x, y = a[p].view(np.uint8), b[p].view(np.uint8)
-            assert np.array_equal(x, y), f"{what}: frame {i}, {p} differs in {(x != y).sum()} bytes"
-        assert a["census"] == b["census"], f"{what}: frame {i}, region census {a['census']} != {b['census']}"
-        assert a["emissive_known_zero"] == b["emissive_known_zero"], f"{what}: frame {i}, emissive plane knowledge"
-
-
-def _lit_pair(fx, v, w, h, lights, part=None):
-    """(HdrColor, depth) of vr_terrain_render + vr_deferred_light and of vr_terrain_render_lit."""
-    from vrenderer_amd.passes import partition_info
-    ctx, tp = fx["ctx"], fx["tp"]
-    rp = vr.default_render_params(400.0, assume_cleared=1)
-    rt = vr.RenderTargets(ctx).Init(w, h)
-    if part is None:
-        imgs, nbytes = [vr.HdrImage(ctx, w, h) for _ in range(2)], None
-    else:
-        info = partition_info(w, h, part.rank, part.world_size)
-        rows = (info["packed_bytes"] + vr.VR_OWNER_TILE * 8 - 1) // (vr.VR_OWNER_TILE * 8)
-        imgs, nbytes = [vr.HdrImage(ctx, vr.VR_OWNER_TILE, rows) for _ in range(2)], info["owned"] * 128 * 128 * 6
-    try:
-        for img in imgs:                                    # (pixels of a partial edge tile outside the frame are never written)
-            img.upload(np.zeros(img.width * img.height * 4, np.uint16))
-        tp.Render(v, v, rt, rp, part)
-        vr.DeferredLightingPass(ctx).Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, imgs[0], part)
-        want = (imgs[0].download(nbytes).copy(), rt.download("depth").copy())
-        rt.Clear()
-        tp.RenderLit(v, rt, rp, lights, AMBIENT_TOP, AMBIENT_BOTTOM, imgs[1], part)
-        got = (imgs[1].download(nbytes).copy(), rt.download("depth").copy())
-    finally:
-        for o in imgs + [rt]:
-            o.close()
-    return want, got
+    """`views` through vr_frame_submit over an HdrColor of 0x3c00; the fused kernel ran exactly when the option is on."""
+    frames = submit_frames(fx, fusion, w, h, views, lights, hdr_fill=0x3c00)
+    expect_kernels(frames, bool(fusion), f"fusion {fusion}")
+    return frames
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -143,10 +70,10 @@ def test_frame_submit_fusion_on_equals_fusion_off(fx, w, h):
     lights = [vr.reference_sun()]
     off, on = _submit(fx, 0, w, h, views, lights), _submit(fx, 1, w, h, views, lights)
     for i, f in enumerate(off):
-        k = _region_kinds(f["depth"])
+        k = region_kinds(f["depth"])
         assert k["terrain"] > 0 and k["sky"] > 0 and k["mixed"] > 0, f"frame {i}: {k}"
         assert not (f["hdr"].reshape(h, w, 4)[f["depth"] == 1.0] != 0).any(), f"frame {i}: a sky pixel is not +0"
-    _same_frames(off, on, f"{w}x{h}")
+    assert_same_frames(off, on, f"{w}x{h}")
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -157,11 +84,11 @@ def test_render_lit_equals_render_plus_lighting(fx, w, h):
         v = _view(i, w, h)
         for part in (None, vr.Partition(0, 2), vr.Partition(1, 2)):
             what = f"{w}x{h} view {i} part {None if part is None else (part.rank, part.world_size)}"
-            (hdr_a, d_a), (hdr_b, d_b) = _lit_pair(fx, v, w, h, lights, part)
+            (hdr_a, d_a), (hdr_b, d_b) = lit_pair(fx["ctx"], fx["tp"], v, w, h, lights, part)
             assert np.array_equal(d_a.view(np.uint32), d_b.view(np.uint32)), "depth: " + what
             assert np.array_equal(hdr_a, hdr_b), f"HdrColor differs at {(hdr_a != hdr_b).sum()} halfs: " + what
             if part is None:
-                k = _region_kinds(d_a)
+                k = region_kinds(d_a)
                 assert k["terrain"] > 0 and k["sky"] > 0 and k["mixed"] > 0, what + f": {k}"
 
 
@@ -172,8 +99,8 @@ def test_light_lists_through_both_fused_flavours(fx, name):
     lights = _light_lists(fx["h"])[name]
     v = _view(0, w, h)
     off, on = _submit(fx, 0, w, h, [v], lights), _submit(fx, 1, w, h, [v], lights)
-    _same_frames(off, on, name)
-    (hdr_a, d_a), (hdr_b, d_b) = _lit_pair(fx, v, w, h, lights)
+    assert_same_frames(off, on, name)
+    (hdr_a, d_a), (hdr_b, d_b) = lit_pair(fx["ctx"], fx["tp"], v, w, h, lights)
     assert np.array_equal(d_a.view(np.uint32), d_b.view(np.uint32)), name + ": depth"
     assert np.array_equal(hdr_a, hdr_b), f"{name}: render_lit's HdrColor differs at {(hdr_a != hdr_b).sum()} halfs"
     assert np.array_equal(off[0]["hdr"], hdr_a), name + ": the two unfused references differ"

@@ -4,7 +4,8 @@ import pytest
 
 import vrenderer_amd as vr
 from tests import f64_shading
-from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
+from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, packed_hdr, params, scaled_camera
+from tests.fusion_common import lit_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -1778,34 +1779,6 @@ def test_frame_submit_equals_the_per_call_sequence(scene256, oracle, gpu_ctx, cr
             tctx.close()
 
 
-def _fused_vs_unfused(tp, gpu_ctx, v, w, h, lights, part=None):
-    from vrenderer_amd.passes import partition_info
-    rp = vr.default_render_params(400.0, assume_cleared=1)
-    rt = vr.RenderTargets(gpu_ctx).Init(w, h)
-    if part is None:
-        mk = lambda: vr.HdrImage(gpu_ctx, w, h)
-        nbytes = None
-    else:
-        info = partition_info(w, h, part.rank, part.world_size)
-        rows = (info["packed_bytes"] + vr.VR_OWNER_TILE * 8 - 1) // (vr.VR_OWNER_TILE * 8)
-        mk = lambda: vr.HdrImage(gpu_ctx, vr.VR_OWNER_TILE, rows)
-        nbytes = info["owned"] * 128 * 128 * 6            # the live tiles of the packed buffer
-    a, b = mk(), mk()
-    for img in (a, b):                                     # (pixels of a partial edge tile that lie outside the frame are never written)
-        img.upload(np.zeros(img.width * img.height * 4, np.uint16))
-    tp.Render(v, v, rt, rp, part)
-    vr.DeferredLightingPass(gpu_ctx).Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, a, part)
-    depth_a = rt.download("depth").copy()
-    want = a.download(nbytes).copy()
-    rt.Clear()                                             # (the fused pass must not depend on what the other planes hold)
-    tp.RenderLit(v, rt, rp, lights, AMBIENT_TOP, AMBIENT_BOTTOM, b, part)
-    got = b.download(nbytes)
-    depth_b = rt.download("depth")
-    for o in (a, b, rt):
-        o.close()
-    return want, got, depth_a, depth_b
-
-
 def test_fused_render_lit_equals_render_plus_lighting(scene256, scene2048, oracle, gpu_ctx):
     """vr_terrain_render_lit (opt-in): the tile pass's resolve shades what it has just encoded and writes depth +
     HdrColor only.  Bit-identical to vr_terrain_render + vr_deferred_light - sun only, sun + point lights (the exact-position
@@ -1822,7 +1795,7 @@ def test_fused_render_lit_equals_render_plus_lighting(scene256, scene2048, oracl
         try:
             for sc, size, w, h, cam, lights, part in cases:
                 v = vr.make_view(*scaled_camera(cam, size), w, h)
-                want, got, da, db = _fused_vs_unfused(sc["tp"], gpu_ctx, v, w, h, lights, part)
+                (want, da), (got, db) = lit_pair(gpu_ctx, sc["tp"], v, w, h, lights, part)
                 what = f"{w}x{h} scene {size} lights {len(lights)} part {None if part is None else (part.rank, part.world_size)} tile {tile}"
                 assert np.array_equal(da.view(np.uint32), db.view(np.uint32)), "depth: " + what
                 assert np.array_equal(want, got), f"HdrColor differs at {(want != got).sum()} halfs: " + what
@@ -1831,7 +1804,7 @@ def test_fused_render_lit_equals_render_plus_lighting(scene256, scene2048, oracl
     # ... and against the oracle (one case; the unfused pair has its own tests)
     w, h = 512, 288
     v = vr.make_view(*scaled_camera(CAMERAS[0], 256), w, h)
-    _, got, _, _ = _fused_vs_unfused(scene256["tp"], gpu_ctx, v, w, h, sun)
+    _, (got, _) = lit_pair(gpu_ctx, scene256["tp"], v, w, h, sun)
     gb = oracle.GBufferHost(w, h)
     scene256["ot"].render(v, gb, vr.default_render_params(400.0))
     ref = oracle.deferred(v, gb, sun, AMBIENT_TOP, AMBIENT_BOTTOM)
@@ -1846,11 +1819,11 @@ def test_fused_render_lit_at_8k_and_split_eight_ways(scene2048, gpu_ctx):
     w, h = 7680, 4320
     v = vr.make_view(*CAMERAS[1], w, h)
     sun = [vr.reference_sun()]
-    want, got, da, db = _fused_vs_unfused(scene2048["tp"], gpu_ctx, v, w, h, sun)
+    (want, da), (got, db) = lit_pair(gpu_ctx, scene2048["tp"], v, w, h, sun)
     assert np.array_equal(da.view(np.uint32), db.view(np.uint32)) and np.array_equal(want, got)
     assert (da < 1.0).mean() > 0.3
     for r in range(8):
-        wp, gp, _, _ = _fused_vs_unfused(scene2048["tp"], gpu_ctx, v, w, h, sun, vr.Partition(r, 8))
+        (wp, _), (gp, _) = lit_pair(gpu_ctx, scene2048["tp"], v, w, h, sun, vr.Partition(r, 8))
         assert np.array_equal(wp, gp), f"rank {r} of 8"
 
 
@@ -2018,13 +1991,12 @@ def test_tonemap_on_packed_tiles_and_ldr_detile(scene256, oracle, gpu_ctx, world
     tm_o = oracle.ToneMapper()
     want = tm_o.SimpleRender(p, full.download())
     info = partition_info(w, h, 0, world)
-    rows = (info["packed_bytes"] + 8 * 128 - 1) // (8 * 128)
     tm = vr.ToneMappingPass(gpu_ctx)
     tm.ResetHistogram()
     packed = []
     for r in range(world):
         part = vr.Partition(r, world)
-        buf = vr.HdrImage(gpu_ctx, 128, rows)
+        buf, _ = packed_hdr(gpu_ctx, w, h, part)
         _lit_frame(scene256, gpu_ctx, 5, w, h, part=part, hdr=buf)
         tm.AddFrameToHistogram(p, buf, w, h, part)             # accumulates: the sum over ranks
         packed.append(buf)
@@ -2116,10 +2088,9 @@ def test_shadowed_deferred_on_packed_tiles(scene256, oracle, gpu_ctx):
     from vrenderer_amd import partition as pt
     from vrenderer_amd.passes import partition_info
     info = partition_info(w, h, 0, world)
-    rows = (info["packed_bytes"] + 8 * 128 - 1) // (8 * 128)
     for r in range(world):
         part = vr.Partition(r, world)
-        buf = vr.HdrImage(gpu_ctx, 128, rows)
+        buf, _ = packed_hdr(gpu_ctx, w, h, part)
         dl.Render(cam, rt, [sun], AMBIENT_TOP, AMBIENT_BOTTOM, buf, part, shadow_map=sm)
         packed = buf.download(info["packed_bytes"]).reshape(-1, 128, 128, 3)
         tx, _ = pt.owner_grid(w, h)

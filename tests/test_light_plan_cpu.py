@@ -1,11 +1,9 @@
 """CPU test of the lighting pass's host plan (vrenderer_amd/csrc/vr_light_plan.h) through tests/host/light_plan_check.cpp."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_check import build_host_check, run_host_check
 
 
 @pytest.mark.parametrize("sanitize", [False, True])
@@ -17,12 +15,7 @@ def test_light_plan_matches_the_transcribed_launch_sites_and_invariants(tmp_path
     table of each variant's compiled-in flags, and every enum value is chosen by some input.  Once more as the same stand-alone
     program under the address and undefined-behaviour sanitizers."""
     extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    exe = os.path.join(str(tmp_path), "light_plan_check_san" if sanitize else "light_plan_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "light_plan_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    r = run_host_check(build_host_check(tmp_path, "light_plan_check", extra, "light_plan_check_san" if sanitize else None))
     # 3 entry points x 2^7 bools x 5 light counts x 2 owner-tile counts x 3 sizes per width class; of the half whose width is no
     # multiple of 4 the tiled passes refuse all and the streaming pass the packed half: 5/12 of the cases
     m = re.search(r"(\d+) cases \((\d+) refused widths", r.stdout)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import brush_model as bm
+from tests.host_check import build_host_check, run_host_check
 from vrenderer_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,17 +47,9 @@ def test_struct_sizes_in_c(tmp_path):
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split() == ["32", "32", "4096"]
 
 
-def _build_check(tmp_path, name, extra):
-    exe = os.path.join(str(tmp_path), name)
-    cmd = ["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "brush_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return exe
-
-
 @pytest.fixture(scope="module")
 def brush_check(tmp_path_factory):
-    return _build_check(tmp_path_factory.mktemp("brush"), "brush_check", [])
+    return build_host_check(tmp_path_factory.mktemp("brush"), "brush_check", ["-ffp-contract=off"])
 
 
 def test_prepared_spans_hold_every_texel_inside_a_dab(brush_check, tmp_path):
@@ -64,12 +57,11 @@ def test_prepared_spans_hold_every_texel_inside_a_dab(brush_check, tmp_path):
     included, radii 0.05 .. 40 texels) and five at the ends of fp32's range: every texel with q < 1, by the header's own weight
     function over the whole map, lies inside the prepared span.  Run once more under the address and undefined-behaviour
     sanitizers, as a stand-alone program."""
-    r = subprocess.run([brush_check], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " dabs, 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    r = run_host_check(brush_check, expect=" dabs, 0 failures")
     assert "72180 dabs" in r.stdout, r.stdout[-400:]            # 36 maps x (2000 + 5)
-    san = _build_check(tmp_path, "brush_check_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
-    r = subprocess.run([san], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and " dabs, 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
+    san = build_host_check(tmp_path, "brush_check", ["-ffp-contract=off", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                           "brush_check_san")
+    run_host_check(san, timeout=300, expect=" dabs, 0 failures", stderr_tail=4000)
 
 
 def _host_stroke(exe, tmp_path, texels, op, dabs, world, target=0.0, color=(0, 0, 0, 0), channels=0xF):

@@ -2,9 +2,9 @@
 the dirty-rectangle rules of vrenderer_amd/csrc/vr_dirty.h hold against a full rebuild (tests/host/dirty_check.cpp)."""
 import os
 import re
-import subprocess
 
 from vrenderer_amd import capi
+from tests.host_check import build_host_check, run_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,14 +24,6 @@ def test_edit_is_declared_mirrored_and_exported(product_lib):
     assert product_lib.vr_terrain_edit(None, 0, 0, 0, 1, 1, None, 0, 0) == capi.VR_ERR_INVALID_ARGUMENT
 
 
-def _build_check(tmp_path, name, extra):
-    exe = os.path.join(str(tmp_path), name)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "dirty_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return exe
-
-
 def test_dirty_rectangles_hold_what_a_full_rebuild_changes(tmp_path):
     """vr_dirty.h compiles without HIP.  For every rectangle of every map of 1..9 x 1..9 texels and 2000 seeded rectangles each
     of 16 x 16, 17 x 5 and 32 x 32 (tests/host/dirty_check.cpp) whatever a full rebuild changes - chain, the three table shapes,
@@ -39,10 +31,8 @@ def test_dirty_rectangles_hold_what_a_full_rebuild_changes(tmp_path):
     within the program's stated K elements per axis of what changed.  And what creating a terrain rests on: for every map of
     w, h in 1..20 and 31, 32, 33, 64, 67 the rectangle of the whole map is ALL of every structure at every level.  Run once more
     under the address and undefined-behaviour sanitizers, as a stand-alone program."""
-    r = subprocess.run([_build_check(tmp_path, "dirty_check", [])], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    r = run_host_check(build_host_check(tmp_path, "dirty_check"))
     assert "33225 rectangles" in r.stdout, r.stdout[-400:]      # sum over w, h in 1..9 of w (w + 1) / 2 * h (h + 1) / 2 = 165^2, + 3 x 2000
     assert "625 whole maps" in r.stdout, r.stdout[-400:]        # 25 sizes per axis
-    san = _build_check(tmp_path, "dirty_check_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
-    r = subprocess.run([san], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
+    san = build_host_check(tmp_path, "dirty_check", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "dirty_check_san")
+    run_host_check(san, timeout=300, stderr_tail=4000)

@@ -14,12 +14,12 @@ import pytest
 import vrenderer_amd as vr
 from vrenderer_amd import capi
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
+from tests.fusion_common import PLANES, download_frame
 from tests import queries_common as qc
 from tests.f64_queries import Surface64
 
 pytestmark = pytest.mark.gpu
 
-PLANES = ("depth", "diffuse", "specular", "normals", "emissive")
 W, H = 256, 144
 SCENES = ("fast64", "odd", "multi")
 RENDER_CAMERAS = (0, 5, 7)
@@ -250,8 +250,7 @@ def _submit_frames(sc, tp, views, fusion, edit=None, lock_after=False):
             hdr.upload(np.zeros(W * H * 4, np.uint16))
             fr.submit(views[i], hdr, views[i + 1:i + 2])
             ctx.synchronize()
-            f = {p: rt.download(p).copy() for p in PLANES}
-            f["hdr"] = hdr.download().copy()
+            f = download_frame(rt, hdr)
             f["chunks"] = tp.num_chunks()
             out.append(f)
             if i == 0 and edit is not None:

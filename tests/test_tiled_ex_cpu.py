@@ -3,11 +3,11 @@ cone test (tests/host/light_cull_check.cpp)."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
 from vrenderer_amd import capi
+from tests.host_check import build_host_check, run_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vr_deferred_light_tiled_ex", "vr_debug_tile_light_list")
@@ -37,14 +37,6 @@ def test_null_context_is_an_invalid_argument_without_a_device(product_lib):
     assert rc == capi.VR_ERR_INVALID_ARGUMENT and n.value == -1
 
 
-def _build_check(tmp_path, name, extra):
-    exe = os.path.join(str(tmp_path), name)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "light_cull_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return exe
-
-
 @pytest.mark.parametrize("sanitize", [False, True])
 def test_cone_test_never_drops_a_cone_that_reaches_the_box_and_is_not_vacuous(tmp_path, sanitize):
     """vr_light_cull.h compiles without HIP.  Over 120000 fixed-seed (cone, box) pairs - boxes around, on and behind the axis,
@@ -53,9 +45,8 @@ def test_cone_test_never_drops_a_cone_that_reaches_the_box_and_is_not_vacuous(tm
     lies in, and drops at least half of the pairs whose every sample is more than 5 degrees outside
     (tests/host/light_cull_check.cpp).  Once more with the address and undefined-behaviour sanitizers."""
     extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if sanitize else []
-    exe = _build_check(tmp_path, "light_cull_check_san" if sanitize else "light_cull_check", extra)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    exe = build_host_check(tmp_path, "light_cull_check", extra, "light_cull_check_san" if sanitize else None)
+    r = run_host_check(exe, timeout=300)
     m = re.search(r"(\d+) pairs .* (\d+) clear of the cone by 5 degrees, (\d+) of them dropped", r.stdout)
     assert m, r.stdout[-400:]
     pairs, clear, dropped = (int(x) for x in m.groups())

@@ -1,11 +1,9 @@
 """CPU test of the tone-map stage's host plan (vrenderer_amd/csrc/vr_tonemap_plan.h) through tests/host/tonemap_plan_check.cpp."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_check import build_host_check, run_host_check
 
 
 @pytest.mark.parametrize("sanitize", [False, True])
@@ -18,12 +16,7 @@ def test_tonemap_plan_matches_the_transcribed_checks_and_launch_sites(tmp_path, 
     sites; every refusal and every family is produced by some input, and a refused input never yields a plan that launches.
     Once more as the same stand-alone program under the address and undefined-behaviour sanitizers."""
     extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    exe = os.path.join(str(tmp_path), "tonemap_plan_check_san" if sanitize else "tonemap_plan_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "vrenderer_amd", "csrc"),
-           os.path.join(ROOT, "tests", "host", "tonemap_plan_check.cpp"), "-o", exe]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    r = run_host_check(build_host_check(tmp_path, "tonemap_plan_check", extra, "tonemap_plan_check_san" if sanitize else None))
     # 2 layouts x 34 sizes x 3 owner-tile counts x 4 capacity pairs x 6 parameter sets, times the boolean facts: ldr, device, tables
     # and - the four entry points - tone mapper, image (2^5 each), or - the frame - communicator, gathered, ldr_frame, RCCL (2^7)
     m = re.search(r"(\d+) cases \((\d+) accepted\)", r.stdout)
