@@ -280,6 +280,46 @@ enum { VR_BRUSH_RAISE = 0, VR_BRUSH_FLATTEN = 1, VR_BRUSH_SMOOTH = 2, VR_BRUSH_P
 typedef struct vr_brush_dab    { float x, z, radius, hardness, strength; float reserved[3]; } vr_brush_dab;      /* 32 B */
 typedef struct vr_brush_stroke { int32_t op; uint32_t channel_mask; float target; float color[4]; int32_t reserved; } vr_brush_stroke; /* 32 B */
 VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* stroke, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
+/* History: undo and redo of vr_terrain_edit and vr_terrain_brush, kept on the device.  Off by default: every call then queues
+ * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
+ *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
+ *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
+ *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
+ *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
+ *   records               with history on, every vr_terrain_edit and vr_terrain_brush that writes (not w == 0, n == 0 or a stroke
+ *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
+ *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
+ *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no
+ *                         open step commit does nothing).  undo and redo close an open step first.  A new record discards all redo
+ *                         steps and frees their room.
+ *   undo / redo           undo applies the newest closed step, its records newest first; redo re-applies the step undone last, its
+ *                         records oldest first.  Per record a kernel exchanges the rectangle between the record and level 0 in place
+ *                         and the refresh of vr_terrain_edit follows, so afterwards every call on the terrain behaves exactly as on a
+ *                         terrain created from the maps of that point in history; prepared geometry is stale, as after an edit.
+ *                         Both are stream-ordered on the context's stream and synchronise nothing.  *applied (may be NULL) is 1 if
+ *                         a step was applied, 0 if there was none - then nothing is queued.
+ *   budget                the arena is a ring of contiguous records: a record's rows lie at a pitch that is a multiple of 16 bytes,
+ *                         the first byte of a row (x * texel bytes) mod 16 bytes into it (the exact size: vr_history.h,
+ *                         DESIGN.md 4t).  Room is made by dropping the oldest undo steps whole, one count of dropped_steps each; a
+ *                         full table of records is treated like a full arena.  History never refuses or alters a write: if room
+ *                         could only be made by dropping the open step itself, or one record is larger than the arena, the write
+ *                         happens unrecorded, ALL steps are dropped (nothing older can be restored across an unrecorded change), and
+ *                         the open step is lost - it records nothing more until commit.  dropped_steps counts every step lost,
+ *                         that one included.
+ * VR_ERR_INVALID_ARGUMENT, before any use of the device: NULL t; NULL out for the status.  Timing: the refresh counts as for
+ * vr_terrain_edit; the capture and swap kernels are untimed. */
+#define VR_HISTORY_MAX_RECORDS 4096
+typedef struct vr_history_status {
+    uint32_t undo_steps, redo_steps;   /* closed steps that undo / redo can apply now */
+    uint32_t open_records;             /* records of the step still open (0 = none open) */
+    uint32_t dropped_steps;            /* steps lost to the budget since enable (monotonic) */
+    uint64_t bytes_used, bytes_budget; /* arena bytes held by live records / the arena's size */
+} vr_history_status;                   /* 32 B */
+VR_API int vr_terrain_history_enable(vr_terrain* t, size_t budget_bytes); /* 0 = off: drops all steps, frees the arena */
+VR_API int vr_terrain_history_commit(vr_terrain* t);                      /* closes the open step; no open step = VR_OK */
+VR_API int vr_terrain_undo(vr_terrain* t, int32_t* applied);              /* *applied (may be NULL) = 1 or 0 */
+VR_API int vr_terrain_redo(vr_terrain* t, int32_t* applied);
+VR_API int vr_terrain_history_status(const vr_terrain* t, vr_history_status* out);
 
 /* QuadTree::SetHeight for every node (QuadTree.cpp:164-208) as a device reduction over the heightmap,
  * and m_HeightLoaded (QuadTree.h:70).  The reference wrote this and left its launch commented out

@@ -216,6 +216,13 @@ namespace vRenderer
         {
             return Check(vr_terrain_brush(m_Terrain, &stroke, dabs, n, outRect), "vr_terrain_brush");
         }
+        // vr_terrain_history_*: undo and redo of Edit and Brush on the device.  EnableHistory(bytes) sets the arena (0: off);
+        // CommitHistory closes the open step (mouse-up); Undo / Redo return whether a step was applied (*applied).
+        bool EnableHistory(size_t budgetBytes) { return Check(vr_terrain_history_enable(m_Terrain, budgetBytes), "vr_terrain_history_enable"); }
+        bool CommitHistory() { return Check(vr_terrain_history_commit(m_Terrain), "vr_terrain_history_commit"); }
+        bool Undo() { int32_t applied = 0; return Check(vr_terrain_undo(m_Terrain, &applied), "vr_terrain_undo") && applied != 0; }
+        bool Redo() { int32_t applied = 0; return Check(vr_terrain_redo(m_Terrain, &applied), "vr_terrain_redo") && applied != 0; }
+        vr_history_status HistoryStatus() const { vr_history_status st = {}; (void)vr_terrain_history_status(m_Terrain, &st); return st; }
         void SetMaxHeight(float maxHeight) { m_MaxHeight = maxHeight; }      // for queries before the first Render
         const std::vector<std::shared_ptr<QuadTree>>& GetQuadTrees() const { return m_QuadTrees; }
         vr_terrain* Get() const { return m_Terrain; }

@@ -38,6 +38,7 @@ VR_BRUSH_RAISE = 0
 VR_BRUSH_FLATTEN = 1
 VR_BRUSH_SMOOTH = 2
 VR_BRUSH_PAINT = 3
+VR_HISTORY_MAX_RECORDS = 4096
 
 
 class TerrainParams(C.Structure):
@@ -163,6 +164,13 @@ class BrushStroke(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class HistoryStatus(C.Structure):
+    """vr_history_status: what undo / redo can apply now, the open step, the steps lost to the budget, the arena's bytes."""
+    _fields_ = [("undo_steps", C.c_uint32), ("redo_steps", C.c_uint32), ("open_records", C.c_uint32), ("dropped_steps", C.c_uint32),
+                ("bytes_used", C.c_uint64), ("bytes_budget", C.c_uint64)]
+
+
+assert C.sizeof(HistoryStatus) == 32
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32
 assert C.sizeof(Instance) == 112
@@ -189,6 +197,7 @@ EXPORTS = [
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
     "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush",
+    "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
 ]
 
 _lib = None
@@ -312,6 +321,11 @@ def load_library():
         "vr_view_pixel_ray": (C.c_int, [P(View), C.c_float, C.c_float, P(Ray)]),
         "vr_terrain_edit": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int]),
         "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),
+        "vr_terrain_history_enable": (C.c_int, [vp, C.c_size_t]),
+        "vr_terrain_history_commit": (C.c_int, [vp]),
+        "vr_terrain_undo": (C.c_int, [vp, P(C.c_int32)]),
+        "vr_terrain_redo": (C.c_int, [vp, P(C.c_int32)]),
+        "vr_terrain_history_status": (C.c_int, [vp, P(HistoryStatus)]),
     }
     for name in EXPORTS:
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

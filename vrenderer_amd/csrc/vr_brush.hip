@@ -229,6 +229,7 @@ extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* str
     for (int c = 0; c < 4; c++) a.color[c] = stroke->color[c];
     void* mem = const_cast<uint8_t*>(tex.base);
     const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t s) -> int {
+        { const int hrc = vr_history_capture(t, which, dirty, s); if (hrc) return hrc; }       // history on: the rectangle as it is, first
         VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)nd * sizeof(BrushDab), hipMemcpyHostToDevice, s));
         const uint8_t* snap = (const uint8_t*)t->d_brush_snap;
         const dim3 grid = tiles_32x8(dirty);

@@ -288,6 +288,7 @@ extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32
     uint8_t* mem = const_cast<uint8_t*>(tex.base);
     // the host's texels into the staging memory, then one strided copy into level 0; everything else is the shared path
     const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t st) -> int {
+        { const int hrc = vr_history_capture(t, which, dirty, st); if (hrc) return hrc; }      // history on: the rectangle as it is, first
         if (!device_pointer) {
             if (pitch == row) VR_HIP(hipMemcpyAsync(t->d_query_stage, texels, row * (size_t)h, hipMemcpyHostToDevice, st));
             else VR_HIP(hipMemcpy2DAsync(t->d_query_stage, row, texels, pitch, row, (size_t)h, hipMemcpyHostToDevice, st));

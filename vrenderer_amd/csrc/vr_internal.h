@@ -14,6 +14,7 @@
 #include "vr_brush.h"
 #include "vr_devbuf.h"
 #include "vr_gbuffer_state.h"
+#include "vr_history.h"
 #include "vr_light_plan.h"
 #include "vr_order.h"
 #include "vr_scratch.h"
@@ -384,9 +385,21 @@ struct vr_terrain {
     BrushDab* h_brush_dabs = nullptr; BrushDab* d_brush_dabs = nullptr;
     void* d_brush_snap = nullptr; size_t brush_snap_bytes = 0;
     hipEvent_t ev_brush = nullptr; bool brush_pending = false;
+    // History (vr_history.hip): the journal's bookkeeping (vr_history.h) over a table of kHistoryMaxRecords records and one device
+    // arena, both from vr_terrain_history_enable on, and the event behind the latest journal kernel with the stream it ran on - a
+    // journal kernel on another stream waits for it (the rule of ev_pyramid / pyramid_stream).
+    HistoryState history;
+    std::vector<HistoryRecord> history_table;
+    uint8_t* d_history = nullptr;
+    hipEvent_t ev_history = nullptr; hipStream_t history_stream = nullptr; bool history_queued = false;
 };
 void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
 void vr_brush_release(vr_terrain* t);      // the brush's memory and event (vr_brush.hip)
+void vr_history_release(vr_terrain* t);    // the journal's arena and event; history is off afterwards (vr_history.hip)
+// In front of a write of the rectangle `dirty` of level 0 (inside vr_derive_level0_write's write_level0, so behind its waits): with
+// history on, a record is appended and the kernel that captures the rectangle is queued on `s`.  Synchronises nothing; with
+// history off it does nothing at all.
+int vr_history_capture(vr_terrain* t, int which, const DirtyRect& dirty, hipStream_t s);
 // the staging memory holds at least `bytes` (grown by doubling; on failure the terrain keeps what it had); whoever uses it
 // synchronises the context's stream before it returns
 int vr_query_reserve_stage(vr_terrain* t, size_t bytes);

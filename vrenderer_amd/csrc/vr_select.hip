@@ -615,6 +615,7 @@ extern "C" VR_API void vr_terrain_destroy(vr_terrain* t)
     free_scratch(t);
     vr_query_release(t);
     vr_brush_release(t);
+    vr_history_release(t);
     if (t->h_status) (void)hipHostFree(t->h_status);
     (void)hipFree(t->d_height); (void)hipFree(t->d_albedo); (void)hipFree(t->d_node_heights); (void)hipFree(t->d_minmax);
     delete t;
@@ -766,6 +767,6 @@ extern "C" VR_API int vr_terrain_memory_bytes(const vr_terrain* t, uint64_t out[
         const uint64_t surfaces = (uint64_t)(t->surfaces_per_side * t->surfaces_per_side);
         heights = nodes * surfaces * sizeof(float2) + (t->d_minmax ? nodes * surfaces * sizeof(uchar2) : 0);
     }
-    out[0] = t->bytes_textures + t->pyramid_bytes; out[1] = t->bytes_scratch + tiles + t->query_stage_bytes + t->brush_snap_bytes + (t->d_brush_dabs ? (uint64_t)VR_MAX_BRUSH_DABS * sizeof(BrushDab) : 0); out[2] = heights; out[3] = out[0] + out[1] + out[2];
+    out[0] = t->bytes_textures + t->pyramid_bytes; out[1] = t->bytes_scratch + tiles + t->query_stage_bytes + t->brush_snap_bytes + (t->d_brush_dabs ? (uint64_t)VR_MAX_BRUSH_DABS * sizeof(BrushDab) : 0) + t->history.budget; out[2] = heights; out[3] = out[0] + out[1] + out[2];
     return VR_OK;
 }

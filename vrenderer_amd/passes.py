@@ -525,6 +525,34 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_brush(self.handle, C.byref(stroke), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_brush")
         return tuple(int(v) for v in rect)
 
+    def EnableHistory(self, budget_bytes):
+        """vr_terrain_history_enable: a device arena of budget_bytes in which every Edit and Brush from now on first records the
+        rectangle it is about to write; 0 switches history off and frees the arena; another budget drops all steps."""
+        check(self.ctx.lib.vr_terrain_history_enable(self.handle, int(budget_bytes)), "vr_terrain_history_enable")
+
+    def CommitHistory(self):
+        """vr_terrain_history_commit: closes the open step - everything recorded since the last commit, undo or redo is one step."""
+        check(self.ctx.lib.vr_terrain_history_commit(self.handle), "vr_terrain_history_commit")
+
+    def Undo(self):
+        """vr_terrain_undo: takes the newest step back (closing an open one first); stream-ordered, nothing is synchronised.
+        True if a step was applied, False if there was none (then nothing is queued)."""
+        applied = C.c_int32()
+        check(self.ctx.lib.vr_terrain_undo(self.handle, C.byref(applied)), "vr_terrain_undo")
+        return bool(applied.value)
+
+    def Redo(self):
+        """vr_terrain_redo: applies the step undone last again; True if a step was applied."""
+        applied = C.c_int32()
+        check(self.ctx.lib.vr_terrain_redo(self.handle, C.byref(applied)), "vr_terrain_redo")
+        return bool(applied.value)
+
+    def HistoryStatus(self):
+        """vr_terrain_history_status as a dict: undo_steps, redo_steps, open_records, dropped_steps, bytes_used, bytes_budget."""
+        st = capi.HistoryStatus()
+        check(self.ctx.lib.vr_terrain_history_status(self.handle, C.byref(st)), "vr_terrain_history_status")
+        return {name: int(getattr(st, name)) for name, _ in capi.HistoryStatus._fields_}
+
     def Prepare(self, view, render_targets, render_params, partition=None):
         """Build the next frame's geometry ahead of time (overlaps the current frame's tile pass)."""
         check(self.ctx.lib.vr_terrain_prepare(self.handle, C.byref(view), render_targets.handle, C.byref(render_params),
