@@ -214,6 +214,7 @@ def test_camera_inside_terrain_near_plane_clipping(scene256, oracle, gpu_ctx):
     tgt = (60.0, hgt - 5.0, 40.0)
     v, gb_o, planes, _, _ = _render_both(scene256, oracle, gpu_ctx, eye, tgt, 640, 360)
     _assert_gbuffer_equal(gb_o, planes, "near-plane")
+    assert scene256["tp"].render_stats()["clipped_tris"] > 0
 
 
 @pytest.mark.parametrize("cam_index", [0, 5])
