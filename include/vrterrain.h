@@ -176,8 +176,21 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * tiles, a target known cleared (assume_cleared = 1 or a pending vr_gbuffer_clear), shaded fill mode without depth ranges, a
  * viewport that covers the target, a width that is a multiple of 4, and VR_OPT_PLANE_TRACKING with the emissive plane known zero.
  * Any other frame - and every frame with 0 - queues the two passes as before. */
+/* VR_OPT_GBUFFER_LAZY (default 1; a context starts with 0 where the environment holds VR_GBUFFER_LAZY=0): a frame that
+ * VR_OPT_FRAME_FUSION shades in the tile pass leaves the G-buffer's diffuse, specular and normals planes (and the region states) to
+ * their first reader.  The frame's one kernel stores depth and HdrColor - the same bits - and the library records the frame (view,
+ * render parameters, terrain).  Every call that reads those planes or the region states, writes part of them, or changes what the
+ * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
+ * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
+ * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
+ * vr_terrain_edit / _brush / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
+ * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
+ * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
+ * vr_terrain pointer: destroy the target, or let a reader run, before a terrain with frames still recorded is handed to another
+ * thread.  Not taken with lock_view.  0 = every fused frame writes the whole G-buffer. */
 enum { VR_OPT_ASYNC_GEOMETRY = 1, VR_OPT_DISPATCH_EVENTS = 2, VR_OPT_RASTER_TILE = 3, VR_OPT_PLANE_TRACKING = 4, VR_OPT_SCRATCH_WORST_CASE = 5,
-       VR_OPT_FRAME_FUSION = 6 };
+       VR_OPT_FRAME_FUSION = 6, VR_OPT_GBUFFER_LAZY = 7 };
 VR_API int  vr_context_set_option(vr_context* ctx, int option, int value);
 VR_API const char* vr_last_error(void);
 VR_API const char* vr_version(void);

@@ -50,6 +50,7 @@ namespace vRenderer
         void SetStream(void* hipStream) { vr_context_set_stream(m_Ctx, hipStream); }
         void SetOption(int option, int value) { Check(vr_context_set_option(m_Ctx, option, value), "vr_context_set_option"); }   // VR_OPT_*
         void SetFrameFusion(bool enable) { SetOption(VR_OPT_FRAME_FUSION, enable ? 1 : 0); }
+        void SetGbufferLazy(bool enable) { SetOption(VR_OPT_GBUFFER_LAZY, enable ? 1 : 0); }
         void WaitForIdle() { vr_context_synchronize(m_Ctx); }            // nvrhi::IDevice::waitForIdle
     };
 

@@ -1,0 +1,313 @@
+"""VR_OPT_GBUFFER_LAZY: a fused frame leaves the G-buffer's colour planes to their first reader.  The same sequence of calls
+with the option off (every fused frame writes the whole G-buffer: the reference) and on must leave the same bytes in every plane,
+HdrColor and depth, the same region census and the same knowledge of the emissive plane, whichever call looks first and whatever
+happened to the terrain or the target in between.  Which kernels ran comes from the dispatch-stamped timing records: the fused
+frame is "k_raster (fused with lighting)" either way, a materialisation is the plain "k_raster"."""
+import numpy as np
+import pytest
+
+import vrenderer_amd as vr
+from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, flythrough_camera, scaled_camera
+from tests.fusion_common import FRAME_KEYS, FUSED, LIGHTING, PLANES, assert_same_bits, assert_same_frame, terrain_fixture
+
+pytestmark = pytest.mark.gpu
+PLAIN = "k_raster"
+SIZES = [(68, 50), (96, 64), (256, 144)]      # partial tiles at the smallest size the fused plan takes; whole tiles; several tile rows
+
+
+@pytest.fixture(scope="module")
+def fx(product_lib):
+    with terrain_fixture(256) as f:
+        yield f
+
+
+def _views(w, h):
+    """Two flythrough views (terrain under a band of sky) and the top-down camera (no sky at all)."""
+    return [vr.make_view(*scaled_camera(flythrough_camera(0), 256), w, h), vr.make_view(*scaled_camera(CAMERAS[4], 256), w, h),
+            vr.make_view(*scaled_camera(flythrough_camera(5), 256), w, h)]
+
+
+def _timed(ctx, fn):
+    ctx.timing_enable(2)
+    try:
+        out = fn()
+        ctx.synchronize()
+        return out, ctx.timing_collect()
+    finally:
+        ctx.timing_enable(0)
+
+
+def _capture(rt, hdr):
+    f = {p: rt.download(p).copy() for p in PLANES}
+    f.update(hdr=hdr.download().copy(), census=rt.region_census(), emissive_known_zero=rt.plane_known_zero("emissive"))
+    return f
+
+
+class Scene:
+    """Fresh targets and a Frame on the fixture's terrain, with the option set to `lazy`."""
+
+    def __init__(self, fx, lazy, w, h):
+        self.ctx, self.tp, self.w, self.h = fx["ctx"], fx["tp"], w, h
+        self.ctx.set_gbuffer_lazy(lazy)
+        self.rt = vr.RenderTargets(self.ctx).Init(w, h)
+        self.hdr, self.hdr2 = vr.HdrImage(self.ctx, w, h), vr.HdrImage(self.ctx, w, h)
+        self.rp = vr.default_render_params(400.0, assume_cleared=1)
+        self.lights = [vr.reference_sun()]
+        self.fr = vr.Frame(self.tp, self.rt, self.rp, self.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+
+    def submit(self, v, fused=True):
+        """One frame; returns the names of the stamped kernels it queued."""
+        _, ran = _timed(self.ctx, lambda: self.fr.submit(v, self.hdr))
+        assert (FUSED in ran) == fused and (LIGHTING in ran) != fused, sorted(ran)
+        return ran
+
+    def close(self):
+        self.ctx.set_gbuffer_lazy(1)
+        for o in (self.hdr, self.hdr2, self.rt):
+            o.close()
+
+
+def _both(fx, w, h, script):
+    """script(scene) -> dict of results, with the option off and on; the two must agree bit for bit."""
+    outs = []
+    for lazy in (0, 1):
+        sc = Scene(fx, lazy, w, h)
+        try:
+            outs.append(script(sc, lazy))
+        finally:
+            sc.close()
+    want, got = outs
+    assert want.keys() == got.keys()
+    for k in want:
+        if isinstance(want[k], dict) and "depth" in want[k]:
+            assert_same_frame(want[k], got[k], f"{w}x{h}, {k}", [q for q in FRAME_KEYS + ("hdr2",) if q in want[k]])
+        elif isinstance(want[k], np.ndarray):
+            assert_same_bits(want[k], got[k], f"{w}x{h}, {k}")
+        else:
+            assert want[k] == got[k], f"{w}x{h}, {k}: {want[k]} != {got[k]}"
+    return want, got
+
+
+def test_the_views_show_sky_and_no_sky(fx):
+    w, h = 96, 64
+    sc = Scene(fx, 0, w, h)
+    try:
+        cov = []
+        for v in _views(w, h):
+            sc.submit(v)
+            cov.append((sc.rt.download("depth") < 1.0).mean())
+        assert 0.2 < cov[0] < 1.0 and cov[1] == 1.0 and 0.2 < cov[2] < 1.0, cov
+    finally:
+        sc.close()
+
+
+READERS = ("download", "census", "light", "upload", "describe")
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("reader", READERS)
+def test_every_kind_of_reader_finds_the_eager_frame(fx, w, h, reader):
+    """Two frames with nobody looking (sky, then no sky), the reader, everything the target holds; then a third frame and all
+    of it again.  Lazy: the two frames queue no plain tile pass, the reader queues one, and from then on the target's frames
+    keep their G-buffer - the capture behind the third frame queues nothing."""
+    v = _views(w, h)
+    foreign = np.random.default_rng(7).integers(0, 1 << 32, (h, w), dtype=np.uint64).astype(np.uint32)
+
+    def script(sc, lazy):
+        out = {}
+        ran = [sc.submit(v[0]), sc.submit(v[1])]
+        assert all(PLAIN not in r and r[FUSED][1] == 1 for r in ran), ran      # no unfused tile pass, option on or off
+
+        def read():
+            if reader == "download":
+                out["first"] = sc.rt.download("normals").copy()
+            elif reader == "census":
+                out["first"] = sc.rt.region_census()
+            elif reader == "light":
+                vr.DeferredLightingPass(sc.ctx).Render(v[1], sc.rt, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM, sc.hdr2)
+                out["first"] = sc.hdr2.download().copy()
+            elif reader == "upload":
+                sc.rt.upload("specular", foreign)
+            else:
+                d = sc.rt.describe()
+                out["first"] = (d.width, d.height)
+        _, r = _timed(sc.ctx, read)
+        assert (PLAIN in r) == bool(lazy), (reader, sorted(r))                   # the one materialisation
+        out["behind the reader"] = _capture(sc.rt, sc.hdr)
+        if reader == "light":      # the lighting pass over the materialised planes is the fused frame's HdrColor
+            assert_same_bits(out["first"], out["behind the reader"]["hdr"], "vr_deferred_light against the fused frame")
+        sc.submit(v[2], fused=reader != "describe")      # (the pointers have left the library: the two passes from now on)
+        cap, r = _timed(sc.ctx, lambda: _capture(sc.rt, sc.hdr))
+        assert PLAIN not in r, f"{reader}: the frame after a materialisation did not keep its G-buffer: {sorted(r)}"
+        out["third frame"] = cap
+        return out
+    _both(fx, w, h, script)
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("download_first", [False, True], ids=["edit-submit-download", "edit-download-submit"])
+def test_an_edit_with_a_frame_pending(fx, w, h, download_first):
+    """submit, edit, submit, download: the planes are the second frame's on the edited terrain; with the download between the
+    edit and the second submit they are the first frame's on the terrain as it was."""
+    v = _views(w, h)
+    hm = fx["h"]
+    block = np.full((64, 64), 255, np.uint8)
+    x0 = y0 = 96
+
+    def script(sc, lazy):
+        out = {}
+        try:
+            sc.submit(v[1])
+            sc.tp.Edit("height", x0, y0, block)
+            if download_first:
+                out["before the edit"] = _capture(sc.rt, sc.hdr)
+            sc.submit(v[1])
+            out["after the edit"] = _capture(sc.rt, sc.hdr)
+        finally:
+            sc.tp.Edit("height", x0, y0, hm[y0:y0 + 64, x0:x0 + 64])
+        return out
+    want, _ = _both(fx, w, h, script)
+    if download_first:
+        assert not np.array_equal(want["before the edit"]["normals"], want["after the edit"]["normals"]), "the edit is not in view"
+
+
+def test_undo_and_redo_with_a_frame_pending(fx):
+    w, h = 96, 64
+    v = _views(w, h)
+    block = np.full((64, 64), 255, np.uint8)
+
+    def script(sc, lazy):
+        out = {}
+        sc.tp.EnableHistory(1 << 20)
+        try:
+            sc.tp.Edit("height", 96, 96, block)
+            sc.tp.CommitHistory()
+            sc.submit(v[1])
+            assert sc.tp.Undo() is True
+            out["edited"] = _capture(sc.rt, sc.hdr)          # the frame was submitted on the edited terrain
+            sc = Scene(fx, lazy, w, h)                        # (a fresh target: the first one has given laziness up)
+            try:
+                sc.submit(v[1])
+                assert sc.tp.Redo() is True
+                out["original"] = _capture(sc.rt, sc.hdr)
+            finally:
+                sc.tp.Undo()
+                for o in (sc.hdr, sc.hdr2, sc.rt):
+                    o.close()
+        finally:
+            sc.tp.EnableHistory(0)
+        return out
+    want, _ = _both(fx, w, h, script)
+    assert not np.array_equal(want["edited"]["normals"], want["original"]["normals"])
+
+
+def test_resize_and_clear_with_a_frame_pending(fx):
+    w, h = 96, 64
+    v = _views(w, h)
+
+    def script(sc, lazy):
+        out = {}
+        sc.submit(v[0])
+        sc.rt.Init(68, 50)                                    # the pending frame goes with the old target
+        sc.hdr.upload(np.zeros(w * h * 4, np.uint16))
+        sc.fr = vr.Frame(sc.tp, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+        sc.submit(vr.make_view(*scaled_camera(flythrough_camera(0), 256), 68, 50))
+        out["resized"] = {p: sc.rt.download(p).copy() for p in PLANES}
+        out["resized census"] = sc.rt.region_census()
+        sc.rt.Init(w, h)
+        sc.fr = vr.Frame(sc.tp, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+        sc.submit(v[0])
+        sc.rt.Clear()                                         # the clear replaces the frame nobody looked at
+        _, r = _timed(sc.ctx, lambda: out.update(cleared=_capture(sc.rt, sc.hdr)))
+        assert PLAIN not in r, sorted(r)
+        assert (out["cleared"]["depth"] == 1.0).all() and not out["cleared"]["diffuse"].any()
+        sc.submit(v[1])
+        sc.rp.assume_cleared = 0                              # keep-what-is-there over a pending frame: a partial writer
+        sc.tp.Render(v[0], v[0], sc.rt, sc.rp)
+        out["kept"] = _capture(sc.rt, sc.hdr)
+        return out
+    _both(fx, w, h, script)
+
+
+def test_a_second_target_on_the_same_terrain(fx):
+    """The terrain holds at most one pending target: a lazy frame into a second one produces the first one's planes."""
+    w, h = 96, 64
+    v = _views(w, h)
+
+    def script(sc, lazy):
+        other = Scene(fx, lazy, w, h)
+        try:
+            sc.submit(v[0])
+            other.submit(v[1])
+            return {"first": _capture(sc.rt, sc.hdr), "second": _capture(other.rt, other.hdr)}
+        finally:
+            for o in (other.hdr, other.hdr2, other.rt):
+                o.close()
+    _both(fx, w, h, script)
+
+
+def test_a_pending_clear_belongs_to_the_frame_that_consumed_it(fx):
+    """Clear, a frame without assume_cleared (the frame is that clear), then a keep-what-is-there pass: it keeps the FRAME's
+    pixels where it draws nothing, not the clear's - the clear is not pending a second time behind a lazy frame."""
+    w, h = 96, 64
+    v = _views(w, h)
+
+    def script(sc, lazy):
+        sc.rp.assume_cleared = 0
+        sc.rt.Clear()
+        sc.submit(v[1])
+        sc.tp.Render(v[0], v[0], sc.rt, sc.rp)
+        out = {"kept": _capture(sc.rt, sc.hdr)}
+        sc.rt.Clear()
+        sc.submit(v[0])
+        sc.rt.Clear()
+        sc.submit(v[1])
+        out["second clear"] = _capture(sc.rt, sc.hdr)
+        return out
+    want, _ = _both(fx, w, h, script)
+    assert (want["kept"]["depth"] < 1.0).all(), "the top-down frame's pixels were not kept under the sky of the second view"
+
+
+def test_a_second_terrain_takes_over_the_target(fx):
+    """A change of level, then a resize: terrain A's frame is pending on the target, terrain B's frame replaces it - A lets go
+    of the target - the target is destroyed and made again at another size, and A is edited.  The edit queues no tile pass (A
+    holds nothing), and what B and A then draw is the eager world's.  Without the resize, an edit of A leaves B's frame pending:
+    the target stays lazy until somebody looks."""
+    from tests.common import params
+    w, h = 96, 64
+    v = _views(w, h)
+    ctx, hm = fx["ctx"], fx["h"]
+    other = vr.TerrainPass(ctx, params(256)).Init(np.ascontiguousarray(hm[::-1]), vr.synth_albedo(ctx, 256, hm))
+    block = np.full((64, 64), 255, np.uint8)
+
+    def edit_a(sc):
+        _, r = _timed(sc.ctx, lambda: sc.tp.Edit("height", 96, 96, block))
+        sc.tp.Edit("height", 96, 96, hm[96:160, 96:160])
+        return r
+
+    def script(sc, lazy):
+        out = {}
+        fr_b = vr.Frame(other, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+        sc.submit(v[0])                                       # terrain A
+        _timed(sc.ctx, lambda: fr_b.submit(v[1], sc.hdr))     # terrain B into the same target
+        assert PLAIN not in edit_a(sc), "an edit of the first terrain drew the second terrain's frame"
+        _, r = _timed(sc.ctx, lambda: out.update(b=_capture(sc.rt, sc.hdr)))
+        assert (PLAIN in r) == bool(lazy), sorted(r)          # B's frame was still pending
+        # again on a fresh target, with the resize in between
+        sc.rt.Init(w, h)
+        sc.fr = vr.Frame(sc.tp, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+        fr_b = vr.Frame(other, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+        sc.submit(v[0])
+        _timed(sc.ctx, lambda: fr_b.submit(v[1], sc.hdr))
+        sc.rt.Init(68, 50)                                    # the target goes; neither terrain may still hold it
+        assert PLAIN not in edit_a(sc)
+        _, r = _timed(sc.ctx, lambda: other.Edit("height", 96, 96, np.ascontiguousarray(hm[::-1])[96:160, 96:160]))
+        assert PLAIN not in r
+        sc.fr = vr.Frame(sc.tp, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+        sc.submit(vr.make_view(*scaled_camera(flythrough_camera(0), 256), 68, 50))
+        out["a resized"] = {p: sc.rt.download(p).copy() for p in PLANES}
+        return out
+    try:
+        _both(fx, w, h, script)
+    finally:
+        other.close()

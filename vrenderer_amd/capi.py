@@ -29,6 +29,7 @@ VR_OPT_RASTER_TILE = 3
 VR_OPT_PLANE_TRACKING = 4
 VR_OPT_SCRATCH_WORST_CASE = 5
 VR_OPT_FRAME_FUSION = 6
+VR_OPT_GBUFFER_LAZY = 7
 VR_RAY_MISS = 0
 VR_RAY_HIT = 1
 VR_RAY_INVALID = 2

@@ -221,6 +221,8 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
     hipStream_t s = ctx->stream;
     const DevTex& tex = which == 0 ? t->height : t->albedo;
     const TexLayout& lay = which == 0 ? t->height_layout : t->albedo_layout;
+    // a frame recorded for a target's pending colour planes draws the map as it is now
+    { const int rc = vr_terrain_materialise_pending(t); if (rc) return rc; }
     // before the first write: behind every chain queued so far (its vertex stage reads the heightmap) and behind every tile pass
     // (it reads the tables, and the host may have changed the context's stream since it was queued)
     static_assert(kGeoSets == 3, "the list below");

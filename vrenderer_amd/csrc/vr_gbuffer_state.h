@@ -23,6 +23,18 @@
 //
 // Foreign writes: an upload of a plane -> nothing known of it; describe -> the pointers have left the library for good
 // (`escaped`): nothing is assumed ever again, no hint, no skip, no depth ranges (tracking_live).
+//
+// The colour planes of a fused frame are LAZY as well (VR_OPT_GBUFFER_LAZY): vr_frame_submit's one kernel shades in registers and
+// the tone-map stage reads HdrColor, so nothing in the frame reads diffuse, specular and normals.  Where the G-buffer-keeping fused
+// flavour would run, the flavour that stores depth + HdrColor alone runs instead and the state remembers `planes_pending`: the three
+// planes and the region bytes are those of the last materialised frame (consistent with each other; a clear that was pending is
+// consumed - the recorded pass runs "over a cleared target", as the frame did, and writes what the clear would have), depth is the new frame's, and the host keeps the record of the frame (vr_gbuffer: view, parameters, terrain).  Whoever
+// looks at the planes or the regions, writes part of them, or changes what the recorded frame would draw, first has the
+// unfused tile pass queued for the record (gbs_planes_materialised behind it).  That pass over a cleared target writes - or, by
+// the region bytes, knows to hold already - every pixel of every plane and leaves region bytes that depend on the frame alone, so
+// frames nobody looked at drop out without a trace: a whole-frame pass over a cleared target, a Clear, or the next lazy frame
+// replaces the record.  The first materialisation a target needs ends its laziness for good (`lazy_off`): a host that does read the
+// G-buffer pays one extra tile pass once.  Depth is never pending.
 #pragma once
 #include <stdint.h>
 
@@ -40,10 +52,24 @@ struct GbufferState {
     int ranges_state = RANGES_NONE;
     int ranges_rank = 0, ranges_world = 1;     // the screen-tile split a VALID array was rendered for
     bool ranges_allocated = false;
+    bool planes_pending = false;     // diffuse, specular, normals and the region bytes are the last materialised frame's; the current frame is recorded
+    bool lazy_off = false;           // a materialisation was needed once: this target's frames keep their planes from now on
 };
 
 inline bool tracking_live(bool plane_tracking, bool escaped) { return plane_tracking && !escaped; }
 inline bool tracking_live(const GbufferState& s, bool plane_tracking) { return tracking_live(plane_tracking, s.escaped); }
+
+// VR_OPT_GBUFFER_LAZY's policy: may a frame that qualifies for the G-buffer-keeping fused flavour leave its colour planes pending?
+inline bool gbs_lazy_allowed(const GbufferState& s, bool plane_tracking, bool lazy_option, bool lock_view)
+{ return lazy_option && tracking_live(s, plane_tracking) && !s.lazy_off && !lock_view; }
+// Behind the unfused tile pass of the recorded frame (that pass's own step has been committed: gbs_pass_prepare ends `planes_pending`).
+inline GbufferState gbs_planes_materialised(GbufferState s) { s.planes_pending = false; s.lazy_off = true; return s; }
+// The record is given up without its pass: the target is destroyed or its terrain is, and nothing may be assumed of the planes.
+inline GbufferState gbs_planes_abandoned(GbufferState s) { if (s.planes_pending) { s.planes_pending = false; s.lazy_off = true; s.region_fill = 0; } return s; }
+// May a tile pass run over pending planes as it is?  Only one that leaves no trace of them: a shaded pass of the whole frame over a
+// cleared target (it writes every plane; the next lazy frame among them).  Anything else has the record materialised first.
+template <class Plan> inline bool gbs_pass_replaces_pending(const Plan& plan, bool whole, bool shaded, bool viewport_full)
+{ return whole && shaded && viewport_full && plan.assume_cleared && (!plan.fuse || plan.keep); }
 
 // The HIP work of a step, in the order the host does it.
 struct GbufferWork {
@@ -68,6 +94,7 @@ inline GbufferState gbs_touched(GbufferState s) { if (s.ranges_state == RANGES_V
 inline GbufferStep gbs_clear_requested(const GbufferState& s, bool plane_tracking)
 {
     GbufferStep r; r.after = gbs_touched(s);
+    r.after.planes_pending = false;          // (the clear replaces whatever the recorded frame would have left; depth is not pending)
     if (tracking_live(s, plane_tracking) && s.cleared_once) r.after.clear_pending = true;      // lazy
     else { r.after.cleared_once = true; r.work.clear_now = true; }
     return r;
@@ -132,6 +159,12 @@ template <class Plan> inline GbufferStep gbs_pass_prepare(const GbufferState& s,
 {
     GbufferStep r; r.after = s;
     if (plan.consume_pending_clear) r.after.clear_pending = false;
+    if (plan.lazy) {             // depth + HdrColor only: the planes and the region bytes stay as they are, consistent with each other
+        r.after = gbs_touched(r.after);
+        r.after.planes_pending = true;
+        return r;
+    }
+    r.after.planes_pending = false;      // (materialised in front of the pass, or the pass leaves no trace of them)
     if (plan.ranges) {
         r.work.alloc_ranges = !s.ranges_allocated;
         r.work.reset_ranges = !s.ranges_allocated || s.ranges_state != RANGES_CLEAN;

@@ -147,6 +147,17 @@ static int history_apply(vr_terrain* t, bool undo, int32_t* applied)
 {
     if (applied) *applied = 0;
     uint64_t lo = 0, hi = 0;
+    // A frame recorded for a target's pending colour planes draws the map as it is now: where a step will be applied its pass is
+    // queued first, in front of the journal's own move - a refusal there leaves the journal where it was.  (Asked of a copy of the
+    // bookkeeping: a call that applies nothing queues nothing.)
+    if (t->pending_target) {
+        HistoryState probe = t->history;
+        if (undo ? history_undo(probe, &lo, &hi) : history_redo(probe, &lo, &hi)) {
+            VR_HIP(hipSetDevice(t->ctx->device));
+            const int rc = vr_terrain_materialise_pending(t);
+            if (rc) return rc;
+        }
+    }
     if (!(undo ? history_undo(t->history, &lo, &hi) : history_redo(t->history, &lo, &hi))) return VR_OK;      // queues nothing
     VR_HIP(hipSetDevice(t->ctx->device));
     for (uint64_t k = 0; k < hi - lo; k++) {

@@ -51,6 +51,7 @@ extern "C" VR_API int vr_context_create(int device, vr_context** out)
     c->device = device;
     c->stream = nullptr;   // default stream until vr_context_set_stream
     if (const char* e = getenv("VR_FRAME_FUSION")) c->frame_fusion = atoi(e) != 0;      // (A/B runs of an unchanged host program)
+    if (const char* e = getenv("VR_GBUFFER_LAZY")) c->gbuffer_lazy = atoi(e) != 0;
     for (int i = 0; i < 256; i++) c->h_srgb_lut[i] = (float)srgb_eotf((double)i / 255.0);
     c->h_srgb_thr[0] = 0.0f;
     for (int k = 1; k < 256; k++) c->h_srgb_thr[k] = (float)srgb_eotf(((double)k - 0.5) / 255.0);
@@ -113,11 +114,12 @@ extern "C" VR_API int vr_context_set_stream(vr_context* c, void* s)
 extern "C" VR_API int vr_context_set_option(vr_context* c, int option, int value)
 {
     VR_REQUIRE(c != nullptr, "ctx is NULL");
-    VR_REQUIRE(option == VR_OPT_ASYNC_GEOMETRY || option == VR_OPT_DISPATCH_EVENTS || option == VR_OPT_RASTER_TILE || option == VR_OPT_PLANE_TRACKING || option == VR_OPT_SCRATCH_WORST_CASE || option == VR_OPT_FRAME_FUSION, "unknown option");
+    VR_REQUIRE(option == VR_OPT_ASYNC_GEOMETRY || option == VR_OPT_DISPATCH_EVENTS || option == VR_OPT_RASTER_TILE || option == VR_OPT_PLANE_TRACKING || option == VR_OPT_SCRATCH_WORST_CASE || option == VR_OPT_FRAME_FUSION || option == VR_OPT_GBUFFER_LAZY, "unknown option");
     if (option == VR_OPT_ASYNC_GEOMETRY) c->async_geometry = value != 0;
     else if (option == VR_OPT_PLANE_TRACKING) c->plane_tracking = value != 0;
     else if (option == VR_OPT_SCRATCH_WORST_CASE) c->scratch_worst_case = value != 0;
     else if (option == VR_OPT_FRAME_FUSION) c->frame_fusion = value != 0;
+    else if (option == VR_OPT_GBUFFER_LAZY) c->gbuffer_lazy = value != 0;       // (frames to come; a frame already pending stays so)
     else if (option == VR_OPT_RASTER_TILE) {
         VR_REQUIRE(value == 0 || value == 32 || value == 64, "VR_OPT_RASTER_TILE: 0 (by size), 32 or 64");
         c->raster_tile_force = value == 32 ? 5 : value == 64 ? 6 : 0;
@@ -440,6 +442,8 @@ extern "C" VR_API void vr_gbuffer_destroy(vr_gbuffer* g)
 {
     if (!g) return;
     (void)hipSetDevice(g->ctx->device);
+    g->st = gbs_planes_abandoned(g->st);      // nobody will look at the planes again: the recorded frame is never drawn
+    vr_gbuffer_record_settle(g);
     (void)hipFree(g->depth);   // base of the single allocation
     (void)hipFree(g->d_ranges);
     (void)hipFree(g->d_region);
@@ -472,9 +476,17 @@ static int fill_u32(hipStream_t s, void* ptr, size_t count, uint32_t v)
 
 // ---- what the library knows of a G-buffer: vr_gbuffer_state.h decides, the functions below do the HIP work it names ----------
 // gbs_clear_requested / gbs_materialise: the state in front of the fills, gbs_clear_written behind them
+void vr_gbuffer_record_unlink(vr_gbuffer* g)
+{
+    if (!g->pending.terrain) return;
+    if (g->pending.terrain->pending_target == g) g->pending.terrain->pending_target = nullptr;
+    g->pending.terrain = nullptr;
+}
+void vr_gbuffer_record_settle(vr_gbuffer* g) { if (!g->st.planes_pending) vr_gbuffer_record_unlink(g); }
 static int gbuffer_clear_step(vr_gbuffer* g, const GbufferStep& step, hipStream_t s)
 {
     g->st = step.after;
+    vr_gbuffer_record_settle(g);
     if (!step.work.clear_now) return VR_OK;
     size_t n = (size_t)g->w * g->h;
     int rc;
@@ -495,7 +507,12 @@ extern "C" VR_API int vr_gbuffer_clear(vr_gbuffer* g)
     return gbuffer_clear_step(g, gbs_clear_requested(g->st, g->ctx->plane_tracking), g->ctx->stream);
 }
 
-int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s) { return gbuffer_clear_step(g, gbs_materialise(g->st), s); }
+int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s)
+{
+    // the planes first: their pass is the one that consumes a clear pending beside them (depth holds the frame, not the clear)
+    { const int rc = vr_gbuffer_materialise_planes(g); if (rc) return rc; }
+    return gbuffer_clear_step(g, gbs_materialise(g->st), s);
+}
 
 __global__ void k_fill_u32x2(uint2* p, size_t n, uint32_t x, uint32_t y)
 {
@@ -553,6 +570,7 @@ extern "C" VR_API int vr_gbuffer_region_census(vr_gbuffer* g, uint32_t counts[4]
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
     const int tiles = ((g->w + 31) / 32) * ((g->h + 31) / 32);
     counts[3] = (uint32_t)tiles * 4u;
+    if (g->st.planes_pending) { VR_HIP(hipSetDevice(g->ctx->device)); const int rc = vr_gbuffer_materialise_planes(g); if (rc) return rc; }
     const int all = gbs_census(g->st, g->ctx->plane_tracking);
     if (all >= 0) { counts[all] = counts[3]; return VR_OK; }          // the host knows without looking
     VR_HIP(hipSetDevice(g->ctx->device));

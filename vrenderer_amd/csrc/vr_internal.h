@@ -204,6 +204,7 @@ struct vr_context {
     bool scratch_worst_case = false;   // VR_OPT_SCRATCH_WORST_CASE: terrains created from now on size their scratch for max_instances up front
     bool plane_tracking = true;    // VR_OPT_PLANE_TRACKING: the tile pass does not rewrite a G-buffer plane the library knows to be all zero (vr_gbuffer)
     bool frame_fusion = true;      // VR_OPT_FRAME_FUSION: vr_frame_submit shades in the tile pass where its G-buffer-keeping flavour applies
+    bool gbuffer_lazy = true;      // VR_OPT_GBUFFER_LAZY: a fused frame leaves its colour planes to their first reader (vr_gbuffer_state.h)
     int raster_tile_force = 0;     // VR_OPT_RASTER_TILE: 0 = by size (vr_raster_tile_shift), 5 / 6 = 32- / 64-pixel raster tiles
     // VR_OPT_DISPATCH_EVENTS: the tile pass and the lighting pass are launched with hipExtLaunchKernelGGL, whose start/stop
     // events are stamped by the dispatch itself; the stop events double as the cross-stream dependencies (tile pass done ->
@@ -268,8 +269,19 @@ struct vr_gbuffer {
     // What the library knows of the planes and of the two arrays (vr_gbuffer_state.h).  Only vr_host.hip assigns it, through
     // that header's transitions; it owns the arrays, the fills and the error codes.
     GbufferState st;
+    // GbufferState::planes_pending: the frame whose unfused tile pass produces the colour planes and the region bytes.  The terrain
+    // holds the target in turn (vr_terrain::pending_target): whatever changes what the frame would draw materialises it first.
+    // (The target's size is the object's own - a resize is destroy + create; a lazy clear the frame consumed is consumed in `st`.)
+    struct PendingFrame { vr_terrain* terrain = nullptr; vr_view view; vr_render_params rp; } pending;
 };
-int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s);      // a pending clear is written now, on `s`
+// Whoever reads the planes or the region state, or writes part of them: pending colour planes (the recorded frame's unfused tile pass,
+// on the context's stream), then a pending clear (written now, on `s`).  An error is the caller's to report; what was pending stays so.
+int vr_gbuffer_materialise(vr_gbuffer* g, hipStream_t s);
+int vr_gbuffer_materialise_planes(vr_gbuffer* g);              // (vr_raster.hip) the first half alone
+int vr_terrain_materialise_pending(vr_terrain* t);             // in front of anything that changes what the terrain's recorded frame would draw
+// the state no longer says planes_pending (a clear, a pass that replaces the record, the materialisation itself): the record goes
+void vr_gbuffer_record_settle(vr_gbuffer* g);
+void vr_gbuffer_record_unlink(vr_gbuffer* g);                  // the terrain named by the record no longer holds this target (the record is about to name another)
 // A tile pass as raster_plan() decided it (vr_raster_plan.h), once nothing but this call can refuse the launch any more: the
 // arrays it needs, their fills, then the state behind the pass (*region; NULL: not kept).  A refusal leaves the state as it was.
 struct RasterPlan;
@@ -388,6 +400,7 @@ struct vr_terrain {
     // History (vr_history.hip): the journal's bookkeeping (vr_history.h) over a table of kHistoryMaxRecords records and one device
     // arena, both from vr_terrain_history_enable on, and the event behind the latest journal kernel with the stream it ran on - a
     // journal kernel on another stream waits for it (the rule of ev_pyramid / pyramid_stream).
+    vr_gbuffer* pending_target = nullptr;       // the (at most one) G-buffer whose colour planes wait for a frame of this terrain
     HistoryState history;
     std::vector<HistoryRecord> history_table;
     uint8_t* d_history = nullptr;

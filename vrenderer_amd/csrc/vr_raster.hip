@@ -1231,6 +1231,11 @@ struct LitNone { int unused; };
 #ifndef VR_RASTER_WAVES_KEEP
 #define VR_RASTER_WAVES_KEEP 5
 #endif
+// LIT on 32-pixel tiles is the frame's kernel under VR_OPT_GBUFFER_LAZY (the colour planes left to their first reader): asked for
+// the same five waves (profiles/r08_lazy_gbuffer.txt has the resource reports at four and at five); on 64-pixel tiles it keeps four.
+#ifndef VR_RASTER_WAVES_LIT32
+#define VR_RASTER_WAVES_LIT32 5
+#endif
 template <bool WIRE, int TILE, int MODE, bool RANGES = false, bool NOEMI = false, bool LIT = false, bool KEEP = false>
 // A 32-pixel tile's workgroup needs 11 KB of LDS: registers, not LDS, decide how many fit a CU.  Asked for six waves per SIMD
 // the compiler fits every 32-pixel variant into 80 VGPRs without a spill (84-90 otherwise: five waves): 5120x2880 frame
@@ -1238,7 +1243,7 @@ template <bool WIRE, int TILE, int MODE, bool RANGES = false, bool NOEMI = false
 #ifndef VR_RASTER_WAVES_32
 #define VR_RASTER_WAVES_32 6
 #endif
-__global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE == 32 ? VR_RASTER_WAVES_32 : VR_RASTER_WAVES_PER_EU)) void k_raster(RasterArgs a, DevTex hm, DevTex al, const DevVert* __restrict__ verts,
+__global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? (TILE == 32 ? VR_RASTER_WAVES_LIT32 : 4) : TILE == 32 ? VR_RASTER_WAVES_32 : VR_RASTER_WAVES_PER_EU)) void k_raster(RasterArgs a, DevTex hm, DevTex al, const DevVert* __restrict__ verts,
                                                  const HardTriRec* __restrict__ hard_tris, const uint32_t* __restrict__ hard_first,
                                                  const uint4* __restrict__ recs, uint32_t rec_hard_base,
                                                  const uint32_t* __restrict__ tile_cursor, const uint32_t* __restrict__ tile_offset,
@@ -1760,8 +1765,9 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? 4 : TILE 
 // host: TerrainPass::Render (TerrainPass.cpp:143-232)
 // ---------------------------------------------------------------------------------------
 // (*rank_tiles: the raster tiles this rank draws of the target - what vr_terrain_frame_scratch makes room for)
+// (tile_force: VR_OPT_RASTER_TILE as the pass takes it - the context's, or a recorded frame's)
 static int make_raster_args(vr_terrain* t, const vr_view* view, const vr_render_params* rp, int w, int h, const vr_partition* part,
-                            RasterArgs& a, size_t* rank_tiles)
+                            int tile_force, RasterArgs& a, size_t* rank_tiles)
 {
     const int world = part ? part->world_size : 1, rank = part ? part->rank : 0;
     VR_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad partition");
@@ -1773,7 +1779,7 @@ static int make_raster_args(vr_terrain* t, const vr_view* view, const vr_render_
     if (a.vy0 < 0) a.vy0 = 0;
     if (a.vx1 > w - 1) a.vx1 = w - 1;
     if (a.vy1 > h - 1) a.vy1 = h - 1;
-    a.tile_shift = vr_raster_tile_shift(w, h, world, t->ctx->raster_tile_force);
+    a.tile_shift = vr_raster_tile_shift(w, h, world, tile_force);
     { const int rt = 1 << a.tile_shift; a.rtx = (w + rt - 1) / rt; a.rty = (h + rt - 1) / rt; }
     *rank_tiles = (size_t)a.rtx * a.rty / (size_t)world;
     a.mirrored = view->mirrored; a.world = world; a.rank = rank;
@@ -1910,7 +1916,7 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
     // completed chains' counters: the scratch grows here if due (a sticky condition is vr_terrain_render's to report)
     RasterArgs a;
     int earlier;
-    if ((rc = vr_terrain_frame_scratch(t, false, [&](size_t* tiles) { return make_raster_args(t, view, rp, gb->w, gb->h, part, a, tiles); }, &earlier, &a.bin_capacity))) return rc;
+    if ((rc = vr_terrain_frame_scratch(t, false, [&](size_t* tiles) { return make_raster_args(t, view, rp, gb->w, gb->h, part, t->ctx->raster_tile_force, a, tiles); }, &earlier, &a.bin_capacity))) return rc;
     const PartTables* pt = nullptr;       // this rank's raster tiles; unused (NULL) for the whole frame
     if (a.world > 1 && (rc = vr_partition_tables(t->ctx, gb->w, gb->h, part, &pt))) return rc;
     // already prepared for exactly these inputs (a caller may name the same future frame twice): nothing to do
@@ -1950,7 +1956,7 @@ struct LitRequest { const vr_light* lights; int32_t num_lights; const float* amb
 // The facts raster_plan() decides on.  Whether a lit request's light list is the lighting pass's plain case is one of them:
 // the list goes through vr_deferred_make_args here (*la, *lights_rc).
 static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view, const vr_gbuffer* gb, const vr_render_params* rp,
-                                       const RasterArgs& a, const LitRequest* lit_req, LitArgs* la, int* lights_rc)
+                                       const RasterArgs& a, bool plane_tracking, const LitRequest* lit_req, LitArgs* la, int* lights_rc)
 {
     const vr_context* ctx = t->ctx;
     RasterPlanIn in{};
@@ -1961,7 +1967,7 @@ static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view,
     const uint64_t span = (uint64_t)((const char*)(gb->emissive + (size_t)gb->w * gb->h) - (const char*)gb->depth);
     in.one_rsrc = (const char*)gb->depth < (const char*)gb->diffuse && (const char*)gb->depth < (const char*)gb->specular
                && (const char*)gb->depth < (const char*)gb->normals && (const char*)gb->depth < (const char*)gb->emissive && span < (1ull << 32);
-    in.plane_tracking = ctx->plane_tracking; in.clear_pending = gb->st.clear_pending; in.emissive_zero = gb->st.emissive_zero; in.escaped = gb->st.escaped;
+    in.plane_tracking = plane_tracking; in.clear_pending = gb->st.clear_pending; in.emissive_zero = gb->st.emissive_zero; in.escaped = gb->st.escaped;
     in.viewport_full = view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0;
     in.width_mult4 = gb->w % 4 == 0;
     *lights_rc = VR_OK;
@@ -1972,9 +1978,10 @@ static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view,
             || (lit_req->amb_top && lit_req->amb_bottom && hdr && hdr->data && lit_req->num_lights >= 0 && lit_req->num_lights <= kMaxLights
                 && (lit_req->num_lights == 0 || lit_req->lights) && hdr->ctx->device == ctx->device);
         in.hdr_fits = in.lit_inputs_ok && (size_t)gb->w * gb->h * 8 <= hdr->capacity_bytes;
+        in.lazy_ok = lit_req->keep && gbs_lazy_allowed(gb->st, plane_tracking, ctx->gbuffer_lazy, rp->lock_view != 0);
         // the light list: a keep request's only where everything else lets the pass fuse (else the lighting pass builds its own)
         in.lit_plain = true;
-        if (lit_req->keep && !raster_plan(in).keep) in.lit_plain = false;
+        if (lit_req->keep && !raster_plan(in).keep) in.lit_plain = false;      // (lit_plain is still true here)
         else {
             bool extra = false;
             memset(la, 0, sizeof(*la));
@@ -1988,9 +1995,15 @@ static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view,
 // The tile pass behind the three entry points below.  WHAT runs and what it does to the library's knowledge of the G-buffer is
 // raster_plan()'s decision (vr_raster_plan.h says when each variant applies); this function gathers the facts for it and
 // keeps the streams and events in order.
+// RenderMode: the two options the plan depends on, as this pass takes them.  A frame's own pass reads the context's; the pass of a
+// recorded frame (vr_gbuffer_materialise_planes: `materialising`) runs as that frame did - 32-pixel tiles, the tracking on -
+// whatever the options say by now, reports no earlier frame's condition and looks at no pending planes (it produces them).
+struct RenderMode { int tile_force; bool plane_tracking; bool materialising; };
+static RenderMode render_mode_of(const vr_context* ctx) { return { ctx->raster_tile_force, ctx->plane_tracking, false }; }
 static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_partition* part,
-                               const LitRequest* lit_req, bool* lit_done, int* earlier_out)
+                               const LitRequest* lit_req, bool* lit_done, int* earlier_out, const RenderMode& mode)
 {
+    const bool materialising = mode.materialising;
     int rc = check_render_inputs(t, view, gb, rp);
     if (rc) return rc;
     vr_context* ctx = t->ctx;
@@ -2000,15 +2013,25 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     // frame (too many nodes, a full work list) is returned - once - behind this frame's launches
     RasterArgs a;
     int earlier;
-    if ((rc = vr_terrain_frame_scratch(t, true, [&](size_t* tiles) { return make_raster_args(t, view, rp, gb->w, gb->h, part, a, tiles); }, &earlier, &a.bin_capacity))) return rc;
+    if ((rc = vr_terrain_frame_scratch(t, !materialising, [&](size_t* tiles) { return make_raster_args(t, view, rp, gb->w, gb->h, part, mode.tile_force, a, tiles); }, &earlier, &a.bin_capacity))) return rc;
     const PartTables* pt = nullptr;       // this rank's raster tiles; unused (NULL) for the whole frame
     if (a.world > 1 && (rc = vr_partition_tables(ctx, gb->w, gb->h, part, &pt))) return rc;
     const int grid = pt ? pt->num_raster_tiles : a.rtx * a.rty;
 
     LitArgs la;
     int lights_rc;
-    const RasterPlanIn in = raster_plan_inputs(t, view, gb, rp, a, lit_req, &la, &lights_rc);
-    const RasterPlan plan = raster_plan(in);
+    RasterPlanIn in = raster_plan_inputs(t, view, gb, rp, a, mode.plane_tracking, lit_req, &la, &lights_rc);
+    RasterPlan plan = raster_plan(in);
+    // Colour planes still pending on the target: a pass that writes every pixel of every plane replaces the record (nobody looked
+    // at that frame), any other pass finds the planes as that frame would have left them - and is then planned on what that leaves.
+    if (gb->st.planes_pending && !materialising
+        && !gbs_pass_replaces_pending(plan, a.world <= 1, !in.depth_only && !in.wireframe, in.viewport_full)) {
+        if ((rc = vr_gbuffer_materialise_planes(gb))) return rc;
+        in = raster_plan_inputs(t, view, gb, rp, a, mode.plane_tracking, lit_req, &la, &lights_rc);
+        plan = raster_plan(in);
+    }
+    // this terrain's recorded frame belongs to another target: one record per terrain, so that one is drawn now
+    if (plan.lazy && t->pending_target && t->pending_target != gb && (rc = vr_gbuffer_materialise_planes(t->pending_target))) return rc;
     const bool lit = lit_req && !lit_req->keep;
     // a light list the lighting pass refuses is refused here, before anything is queued (a keep request goes on as the plain
     // pass: the error is the lighting pass's to report - as is a partial viewport's, where that pass would look at it first)
@@ -2016,7 +2039,7 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     if (lit_req && lit_req->keep && !plan.keep) lit_req = nullptr;           // from here on: a plain vr_terrain_render
     // a pending clear is written now, or the pass is that clear: the kernel is told so, the state learns it with the rest
     // (vr_gbuffer_apply_plan) - a refusal in between leaves the clear pending
-    if (plan.consume_pending_clear) a.assume_cleared = 1;
+    if (plan.consume_pending_clear || plan.lazy) a.assume_cleared = 1;
     if (plan.materialise_first && (rc = vr_gbuffer_materialise(gb, s))) return rc;
 
     // a set prepared for exactly this frame, else a free one (the oldest prepared set is given up if all are taken)
@@ -2060,6 +2083,15 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         // nothing refuses the pass from here on: what the library knows of the G-buffer becomes what the pass leaves
         uint8_t* region = nullptr;
         if ((rc = vr_gbuffer_apply_plan(gb, plan, s, a.rank, a.world, &region))) return rc;
+        vr_gbuffer_record_settle(gb);              // (a record this pass replaces)
+        if (plan.lazy) {
+            // a lazy frame that replaces a record: planes_pending never fell, so the settle above kept the old link - the terrain
+            // that held this target (another one, after a change of level) lets go of it before the record names the new one
+            vr_gbuffer_record_unlink(gb);
+            gb->pending.terrain = t; gb->pending.view = *view; gb->pending.rp = *rp;
+            gb->pending.rp.assume_cleared = 1;     // (a clear that was pending is consumed: the frame was that clear, and its pass runs over a "cleared" target)
+            t->pending_target = gb;
+        }
 #define VR_RASTER_ARGS a, t->height, t->albedo, g.d_verts, g.d_hard_tris, g.d_hard_first, \
                            (const uint4*)g.d_recs, t->scratch_tris(), g.d_tile_cursor, g.d_tile_offset, g.d_bin_entries, tiles, g.d_counters + C_CLASS0, \
                            gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, ctx->d_srgb_thr, ctx->d_enc_tab, spec_const, plan.ranges ? gb->d_ranges : (uint2*)nullptr, region
@@ -2084,7 +2116,7 @@ extern "C" VR_API int vr_terrain_render(vr_terrain* t, const vr_view* view, cons
 {
     (void)view_prev;   // MOTION_VECTORS = 0 (TerrainPass.cpp:361,368)
     int earlier = VR_OK;
-    const int rc = terrain_render_impl(t, view, gb, rp, part, nullptr, nullptr, &earlier);
+    const int rc = terrain_render_impl(t, view, gb, rp, part, nullptr, nullptr, &earlier, render_mode_of(t->ctx));
     return rc ? rc : earlier;          // this frame is queued either way; `earlier` = a completed frame's device-side condition (sticky, once)
 }
 
@@ -2105,11 +2137,33 @@ extern "C" VR_API int vr_terrain_render_lit(vr_terrain* t, const vr_view* view, 
     const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, false, nullptr };
     bool fused = false;
     int earlier = VR_OK;
-    int rc = terrain_render_impl(t, view, gb, rp, part, &req, &fused, &earlier);
+    int rc = terrain_render_impl(t, view, gb, rp, part, &req, &fused, &earlier, render_mode_of(t->ctx));
     if (rc) return rc;
     if (!fused && (rc = vr_deferred_light(t->ctx, view, gb, lights, num_lights, ambient_top, ambient_bottom, hdr_out, part))) return rc;     // the unfused pair
     return earlier;
 }
+
+// The colour planes a lazy frame left pending: the frame's unfused tile pass - geometry chain, then k_raster - on the context's
+// stream, behind the fused launch.  It is planned from the state the fused launch left alone (the region bytes are those of the
+// planes in memory), runs over a "cleared" target as the frame did, and rewrites depth with the same bits.  The pass runs as the frame would have:
+// 32-pixel tiles and the tracking on, whatever the options say by now (RenderMode); the terrain's current set stays the one it was.
+// One thing the pass cannot repeat: a frame that overflowed the scratch (VR_ERR_TOO_MANY_INSTANCES / VR_ERR_OVERFLOW, reported by the
+// next render) was drawn truncated, and if the scratch has grown since, this pass draws it whole - depth and planes are then the
+// complete frame's, consistent with each other, while HdrColor keeps the truncated one until the next frame.
+int vr_gbuffer_materialise_planes(vr_gbuffer* gb)
+{
+    if (!gb->st.planes_pending) return VR_OK;
+    vr_terrain* t = gb->pending.terrain;
+    const int cur = t->cur;
+    const RenderMode recorded = { 5, true, true };
+    const int rc = terrain_render_impl(t, &gb->pending.view, gb, &gb->pending.rp, nullptr, nullptr, nullptr, nullptr, recorded);
+    t->cur = cur;
+    if (rc) return rc;                     // (before the plan was applied: still pending)
+    gb->st = gbs_planes_materialised(gb->st);
+    vr_gbuffer_record_settle(gb);
+    return VR_OK;
+}
+int vr_terrain_materialise_pending(vr_terrain* t) { return t->pending_target ? vr_gbuffer_materialise_planes(t->pending_target) : VR_OK; }
 
 // vr_frame_submit's tile pass: vr_terrain_render, shading in the same pass where the KEEP flavour applies (*fused; the caller
 // queues the lighting pass itself otherwise)
@@ -2120,7 +2174,7 @@ int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, c
     const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, true, fused_stop };
     int earlier = VR_OK;
     *fused = false; *fused_stop = nullptr;
-    const int rc = terrain_render_impl(t, view, gb, rp, nullptr, &req, fused, &earlier);
+    const int rc = terrain_render_impl(t, view, gb, rp, nullptr, &req, fused, &earlier, render_mode_of(t->ctx));
     return rc ? rc : earlier;
 }
 

@@ -48,6 +48,7 @@ struct RasterPlanIn {
     bool lit_inputs_ok;            // KEEP: pointers, light count and device (LIT: its entry point has refused anything else)
     bool lit_plain;                // vr_deferred_make_args took the light list, without `extra` lights
     bool hdr_fits;                 // KEEP: the frame fits the image (LIT: the host refuses an image too small)
+    bool lazy_ok;                  // KEEP: the colour planes may stay pending (gbs_lazy_allowed)
 };
 
 struct RasterPlan {
@@ -60,6 +61,7 @@ struct RasterPlan {
     bool noemi, fuse, keep;
     bool track_regions;            // the pass gets the region array; otherwise region_fill = 0
     bool emissive_zero_after;      // the plane is known zero behind the pass (false: the state is left as it is)
+    bool lazy;                     // a KEEP frame that stores depth + HdrColor only (RV_LIT_32): planes_pending behind it
 };
 
 inline RasterPlan raster_plan(const RasterPlanIn& in)
@@ -71,6 +73,14 @@ inline RasterPlan raster_plan(const RasterPlanIn& in)
     p.fast = in.tex_same && in.ws_pow2 && in.one_rsrc && !in.wireframe && !in.depth_only;
     p.keep = in.request == RASTER_REQ_KEEP && whole && p.fast && tile32 && (in.assume_cleared || in.clear_pending) && !in.depth_ranges
           && emissive_skip && in.viewport_full && in.width_mult4 && in.lit_inputs_ok && in.hdr_fits && in.lit_plain;
+    // VR_OPT_GBUFFER_LAZY: the whole-frame LIT kernel in KEEP's place; the planes, the region bytes and a pending clear are left alone
+    p.lazy = p.keep && in.lazy_ok;
+    if (p.lazy) {
+        p.assume_cleared = true; p.noemi = true; p.fuse = true;
+        p.consume_pending_clear = in.clear_pending;      // (depth is written everywhere; the planes' share of the clear is the recorded pass's, over a "cleared" target)
+        p.variant = RV_LIT_32;
+        return p;
+    }
     const bool lit = in.request == RASTER_REQ_LIT;           // (a KEEP request that does not qualify: a plain render from here on)
     // a pending clear: a whole-frame shaded pass is that clear, unless it is the LIT variant (depth + HdrColor only)
     p.consume_pending_clear = in.clear_pending && whole && !in.depth_only && !lit;

@@ -417,6 +417,7 @@ extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
 {
     VR_REQUIRE(t != nullptr, "terrain is NULL");
     VR_HIP(hipSetDevice(t->ctx->device));
+    { const int rc = vr_terrain_materialise_pending(t); if (rc) return rc; }      // (a recorded frame selects with the bounds of now)
     for (GeoSet& g : t->sets) g.prepared = false;          // geometry prepared with the old bounds is stale
     if (!enable) { t->height_loaded = false; return VR_OK; }
     const uint64_t nodes = nodes_per_surface(t);
@@ -603,6 +604,12 @@ extern "C" VR_API void vr_terrain_destroy(vr_terrain* t)
 {
     if (!t) return;
     (void)hipSetDevice(t->ctx->device);
+    // a target whose colour planes wait for a frame of this terrain gets them now; if that fails nothing is known of them any more
+    if (t->pending_target && vr_terrain_materialise_pending(t) != VR_OK) {
+        vr_gbuffer* g = t->pending_target;
+        g->st = gbs_planes_abandoned(g->st);
+        vr_gbuffer_record_settle(g);
+    }
     (void)hipStreamSynchronize(t->ctx->stream);
     for (hipStream_t gs : t->geo_streams) if (gs) { (void)hipStreamSynchronize(gs); (void)hipStreamDestroy(gs); }
     for (hipEvent_t e : { t->ord.ev_changed, t->ord.ev_sel_ready, t->ord.hint.own }) if (e) (void)hipEventDestroy(e);

@@ -70,6 +70,10 @@ class Context:
         """Frame.submit shades in the tile pass where its G-buffer-keeping flavour applies (same results; default on)."""
         check(self.lib.vr_context_set_option(self.handle, capi.VR_OPT_FRAME_FUSION, int(enable)), "vr_context_set_option")
 
+    def set_gbuffer_lazy(self, enable):
+        """A fused frame leaves the G-buffer's colour planes to their first reader (same results; default on)."""
+        check(self.lib.vr_context_set_option(self.handle, capi.VR_OPT_GBUFFER_LAZY, int(enable)), "vr_context_set_option")
+
     def set_dispatch_events(self, enable):
         """Tile pass / lighting pass launched with dispatch-stamped events that double as cross-stream dependencies (default on)."""
         check(self.lib.vr_context_set_option(self.handle, capi.VR_OPT_DISPATCH_EVENTS, int(enable)), "vr_context_set_option")
