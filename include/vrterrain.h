@@ -183,7 +183,7 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
  * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
  * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
- * vr_terrain_edit / _brush / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * vr_terrain_edit / _brush / _erode / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
  * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
  * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
  * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
@@ -293,13 +293,40 @@ enum { VR_BRUSH_RAISE = 0, VR_BRUSH_FLATTEN = 1, VR_BRUSH_SMOOTH = 2, VR_BRUSH_P
 typedef struct vr_brush_dab    { float x, z, radius, hardness, strength; float reserved[3]; } vr_brush_dab;      /* 32 B */
 typedef struct vr_brush_stroke { int32_t op; uint32_t channel_mask; float target; float color[4]; int32_t reserved; } vr_brush_stroke; /* 32 B */
 VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* stroke, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
-/* History: undo and redo of vr_terrain_edit and vr_terrain_brush, kept on the device.  Off by default: every call then queues
+/* Thermal (talus) erosion of level 0 of the heightmap under a brush mask, computed on the device from the map as it is there and
+ * followed by the refresh vr_terrain_edit does: afterwards the terrain is the one vr_terrain_create builds from the eroded map.
+ * The dabs are those of a stroke on the heightmap, their strength an opacity in [0, 1]; they form a mask, per texel the largest
+ * weight * strength of the dabs that cover it (0 where none does), so their order does not matter.  A texel's height h (fp32, in
+ * heightmap steps, the stored byte to begin with) is then relaxed `iterations` times, every texel of a sweep from the heights of
+ * the sweep before.  For each of the eight neighbours n inside the map, in the order (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1)
+ * (0,1) (1,1) of (dx, dy): T = talus for an axis neighbour and talus * 1.41421354f for a diagonal one, w = min(mask, mask_n); where
+ * w > 0 and the difference |h - h_n| exceeds T by e > 0, the higher of the two gives up (rate * e) * w and the lower receives it -
+ * both ends of an edge compute the same amount, bit for bit.  Nothing is clamped between sweeps; with rate <= 1/8 the heights
+ * stay between the lowest and the highest of the neighbourhood.  After the last sweep a texel with a positive mask is stored as
+ * the nearest byte of min(max(h, 0), 255); a texel with mask 0 keeps its byte (it is not written).  The arithmetic is defined bit
+ * for bit in vrenderer_amd/csrc/vr_erode.h; the result does not depend on how the device divides the work.
+ * out_rect, `dabs`, the stream order and what the host waits for are vr_terrain_brush's: the call synchronises nothing, and strokes
+ * and erosions of one terrain are ordered against each other.  With history on, one call is one record.  n == 0, or dabs that all
+ * miss the map, is VR_OK and launches nothing.  The device advances several sweeps per launch: a call costs about
+ * iterations / 8 short kernels on top of the refresh.
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the terrain untouched: NULL t or p, NULL dabs with
+ * n > 0; n > VR_MAX_BRUSH_DABS; iterations < 1 or > VR_ERODE_MAX_ITERATIONS; talus or rate NaN or infinite; talus outside
+ * [0, 255]; rate <= 0 or > 0.125; a non-zero reserved word; the dab refusals of vr_terrain_brush with an opacity for a strength.
+ * The memory a call needs - three fp32 planes of the rectangle's size, kept with the terrain and counted under scratch by
+ * vr_terrain_memory_bytes - is reserved before anything is launched (VR_ERR_OUT_OF_MEMORY leaves the terrain as it was).  Timing: as
+ * for vr_terrain_edit; the erosion kernels themselves are untimed. */
+#define VR_ERODE_MAX_ITERATIONS 1024
+typedef struct vr_erode_params { int32_t iterations; float talus; float rate; int32_t reserved[5]; } vr_erode_params; /* 32 B */
+VR_API int vr_terrain_erode(vr_terrain* t, const vr_erode_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
+/* test helper: {tile width, tile height, sweeps per launch, 0} of this build's erosion kernel */
+VR_API int vr_debug_erode_config(int32_t out[4]);
+/* History: undo and redo of vr_terrain_edit, vr_terrain_brush and vr_terrain_erode, kept on the device.  Off by default: every call then queues
  * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
  *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
  *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
  *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
  *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
- *   records               with history on, every vr_terrain_edit and vr_terrain_brush that writes (not w == 0, n == 0 or a stroke
+ *   records               with history on, every vr_terrain_edit, _brush and _erode that writes (not w == 0, n == 0 or a stroke
  *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
  *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
  *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no

@@ -217,7 +217,16 @@ namespace vRenderer
         {
             return Check(vr_terrain_brush(m_Terrain, &stroke, dabs, n, outRect), "vr_terrain_brush");
         }
-        // vr_terrain_history_*: undo and redo of Edit and Brush on the device.  EnableHistory(bytes) sets the arena (0: off);
+        // vr_terrain_erode: `iterations` sweeps of thermal erosion of the heightmap's level 0 under the mask the n dabs form (strength =
+        // opacity; their order does not matter), computed on the device; stream-ordered like Brush, nothing is synchronised.
+        // talus: the height step per texel that stays, in heightmap steps; rate: 0 < rate <= 0.125.  outRect as for Brush.
+        bool Erode(const vr_brush_dab* dabs, uint32_t n, int32_t iterations, float talus, float rate, int32_t outRect[4] = nullptr)
+        {
+            vr_erode_params p = {};
+            p.iterations = iterations; p.talus = talus; p.rate = rate;
+            return Check(vr_terrain_erode(m_Terrain, &p, dabs, n, outRect), "vr_terrain_erode");
+        }
+        // vr_terrain_history_*: undo and redo of Edit, Brush and Erode on the device.  EnableHistory(bytes) sets the arena (0: off);
         // CommitHistory closes the open step (mouse-up); Undo / Redo return whether a step was applied (*applied).
         bool EnableHistory(size_t budgetBytes) { return Check(vr_terrain_history_enable(m_Terrain, budgetBytes), "vr_terrain_history_enable"); }
         bool CommitHistory() { return Check(vr_terrain_history_commit(m_Terrain), "vr_terrain_history_commit"); }

@@ -1,0 +1,238 @@
+"""GPU tests of vr_terrain_erode.  The eroded map must equal the numpy float32 model (tests/erode_model.py) in every byte - no
+tolerance anywhere: vr_erode.h's arithmetic is IEEE fp32 in a fixed order, and a cell is a pure function of the sweep before, so
+neither the tile of the device's kernel nor the number of sweeps it advances per launch may show - and the eroded terrain must be
+the one created from the model's map.  Scenes and the state under test are those of tests/test_terrain_edit_gpu.py."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from vrenderer_amd import capi
+from tests import brush_model as bm
+from tests import erode_model as em
+from tests import queries_common as qc
+from tests import test_terrain_edit_gpu as te
+from tests.f64_queries import Surface64
+from tests.test_terrain_brush_gpu import assert_bytes, dab, five_dabs, level0, world_of
+
+pytestmark = pytest.mark.gpu
+
+ITER, TALUS, RATE = 20, 1.5, 0.125
+
+
+@pytest.fixture(scope="module")
+def scenes(gpu_ctx):
+    return {n: te.Scene(gpu_ctx, n) for n in te.SCENES}
+
+
+def mask_dabs(shape, world):
+    """five_dabs with opacities for strengths: radii 0.4 .. 12 texels, hardness 0 and 0.7, a centre on the map's corner, one outside."""
+    return five_dabs(shape, world, bm.FLATTEN)
+
+
+def full_mask(world):
+    return np.float32([[0.0, 0.0, 4.0 * world, 0.5, 1.0]])          # mask 1 on every texel
+
+
+_MODEL = {}
+
+
+def model(sc, dabs, iterations, talus=TALUS, rate=RATE, hm=None):
+    """The model's (map, rect), computed once per distinct call."""
+    src = sc.hm if hm is None else hm
+    key = (sc.name, src.tobytes(), np.asarray(dabs, np.float32).tobytes(), iterations, talus, rate)
+    if key not in _MODEL:
+        _MODEL[key] = em.erode(src, dabs, world_of(sc), iterations, talus, rate)
+    return _MODEL[key]
+
+
+@pytest.mark.parametrize("name", te.SCENES)
+def test_bytes_equal_the_model(scenes, name):
+    """1. A five-dab mask on each scene: level 0 equals the model in every byte, the albedo is untouched, the rectangle is the model's."""
+    sc = scenes[name]
+    dabs = mask_dabs(sc.hm.shape, world_of(sc))
+    want, want_rect = model(sc, dabs, ITER)
+    changed = want != sc.hm
+    assert changed.sum() >= 30 and ((want[changed] > 0) & (want[changed] < 255)).sum() >= 10
+    a = sc.terrain(sc.hm, sc.al, cast=False, render=False)
+    rect = a.Erode(dabs, ITER, TALUS, RATE)
+    assert rect == tuple(want_rect), (rect, want_rect)
+    assert_bytes(level0(a, "height"), want, f"{name}, erode")
+    assert_bytes(level0(a, "albedo"), sc.al, f"{name}, erode: the albedo")
+    a.close()
+
+
+def _borders(size, tile):
+    return list(range(tile, size, tile))
+
+
+def _far_from_sources(src, k):
+    """True where no non-zero texel of `src` lies within k texels (Chebyshev)."""
+    near = src != 0
+    for _ in range(k):
+        p = np.pad(near, 1)
+        near = np.logical_or.reduce([p[dy:dy + src.shape[0], dx:dx + src.shape[1]] for dy in range(3) for dx in range(3)])
+    return ~near
+
+
+def test_tile_borders_and_launch_boundaries(scenes, gpu_ctx):
+    """2. A full mask over the 128^2 map, which the build's tile does not divide, for 1, K - 1, K, K + 1 and 2K + 1 iterations (one
+    launch with a remainder, a full one, a full one and a remainder, two and a remainder).  On a noise map every row and column on
+    both sides of every interior tile border changes at every count; on a map of bands that lie more than K texels from every
+    border, 2K + 1 iterations change border texels further than K from every band - what reaches them crossed a launch."""
+    cfg = (C.c_int32 * 4)()
+    assert gpu_ctx.lib.vr_debug_erode_config(cfg) == capi.VR_OK
+    tw, th, k = cfg[0], cfg[1], cfg[2]
+    sc = scenes["multi"]
+    size = sc.hm.shape[0]
+    assert sc.hm.shape == (size, size)
+    bx, by = _borders(size, tw), _borders(size, th)
+    assert (len(bx) >= 2 and len(by) >= 1 or len(bx) >= 1 and len(by) >= 2) and size % tw and size % th, (tw, th, size)
+    assert min(tw, th) > 2 * (k + 4)                                 # room for the bands between two borders
+    dabs = full_mask(world_of(sc))
+    noise = np.random.default_rng(5).integers(0, 256, sc.hm.shape, dtype=np.uint8)
+    bands = np.zeros_like(sc.hm)
+    for b in by:
+        bands[b + k + 1:b + k + 4, :] = 255
+        bands[b - k - 4:b - k - 1, :] = 255
+    for b in bx:
+        bands[:, b + k + 1:b + k + 4] = 255
+        bands[:, b - k - 4:b - k - 1] = 255
+    cases = [(noise, n) for n in (1, k - 1, k, k + 1, 2 * k + 1)] + [(bands, 2 * k + 1)]
+    for hm, n in cases:
+        want, want_rect = model(sc, dabs, n, talus=0.0, hm=hm)
+        assert tuple(want_rect) == (0, 0, size, size)
+        changed = want != hm
+        if hm is bands:
+            changed &= _far_from_sources(bands, k)
+        for b in by:
+            assert changed[b - 1, :].any() and changed[b, :].any(), (n, b)
+        for b in bx:
+            assert changed[:, b - 1].any() and changed[:, b].any(), (n, b)
+        a = sc.terrain(hm, sc.al, cast=False, render=False)
+        assert a.Erode(dabs, n, 0.0, RATE) == tuple(want_rect)
+        assert_bytes(level0(a, "height"), want, f"{'bands' if hm is bands else 'noise'}, {n} iterations, tile {tw} x {th}, K {k}")
+        a.close()
+
+
+@pytest.mark.parametrize("name", te.SCENES)
+def test_the_terrain_is_the_one_created_from_the_eroded_map(scenes, name):
+    """3. A (SetHeight on, pyramid built, one frame rendered; then eroded) against B created from the model's map: every mip level,
+    node heights and selections, every G-buffer plane for cameras 0 and 5, sampled heights with normals, 64 ray hits."""
+    sc = scenes[name]
+    dabs = mask_dabs(sc.hm.shape, world_of(sc))
+    hm, _ = model(sc, dabs, ITER)
+    a = sc.terrain(sc.hm, sc.al)
+    a.Erode(dabs, ITER, TALUS, RATE)
+    b = sc.terrain(hm, sc.al)
+    te._assert_chains_equal(a, b, name)
+    surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
+    nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
+    ha, hb = a.node_heights(0, nodes), b.node_heights(0, nodes)
+    assert np.array_equal(ha.view(np.uint32), hb.view(np.uint32)), f"{name}: {(ha.view(np.uint32) != hb.view(np.uint32)).any(1).sum()} of {nodes} nodes differ"
+    for cam in (0, 5):
+        v = sc.view(cam)
+        na, ia, insta = a.NodeSelect(v, sc.mh)
+        nb, ib, instb = b.NodeSelect(v, sc.mh)
+        assert na == nb and na > 0 and np.array_equal(ia, ib) and np.array_equal(insta, instb), (name, cam, na, nb)
+        te._assert_frames_equal(te._render(sc, a, cam), te._render(sc, b, cam), f"{name}, camera {cam}")
+    pts = qc.uniform_points(sc.world, 1024)
+    (h1, n1), (h2, n2) = a.SampleHeights(pts, sc.mh, normals=True), b.SampleHeights(pts, sc.mh, normals=True)
+    assert np.array_equal(h1.view(np.uint32), h2.view(np.uint32)) and np.array_equal(n1.view(np.uint32), n2.view(np.uint32))
+    surf = Surface64(b.download_mip("height", 0), b.download_mip("height", 1), sc.world, sc.mh)
+    o, d, tm = qc.make_rays(surf, sc.world, n=64)
+    ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
+    assert ra.tobytes() == rb.tobytes(), f"{name}: {(ra != rb).sum()} of {len(ra)} hits differ"
+    assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
+    a.close(); b.close()
+
+
+def test_history(scenes):
+    """4. Enable, erode, commit, undo: the original bytes; redo: the model's.  One erode is one record; an erode and a RAISE stroke
+    in one step undo together."""
+    sc = scenes["odd"]
+    S = world_of(sc)
+    dabs = mask_dabs(sc.hm.shape, S)
+    want, _ = model(sc, dabs, ITER)
+    a = sc.terrain(sc.hm, sc.al, cast=False, render=False)
+    a.EnableHistory(1 << 20)
+    a.Erode(dabs, ITER, TALUS, RATE)
+    assert a.HistoryStatus()["open_records"] == 1
+    a.CommitHistory()
+    assert_bytes(level0(a, "height"), want, "eroded")
+    assert a.Undo()
+    assert_bytes(level0(a, "height"), sc.hm, "undone")
+    assert a.Redo()
+    assert_bytes(level0(a, "height"), want, "redone")
+    raise_dabs = five_dabs(sc.hm.shape, S, bm.RAISE)
+    raised, _ = bm.stroke(want, bm.RAISE, raise_dabs, S)
+    both, _ = em.erode(raised, dabs, S, 3, 0.0, RATE)
+    assert (both != raised).sum() >= 30 and (raised != want).sum() >= 30
+    a.Brush("raise", raise_dabs)
+    a.Erode(dabs, 3, 0.0, RATE)
+    assert a.HistoryStatus()["open_records"] == 2
+    a.CommitHistory()
+    assert_bytes(level0(a, "height"), both, "a stroke and an erode")
+    assert a.Undo()
+    assert_bytes(level0(a, "height"), want, "the step of two undone")
+    assert a.Undo() and not a.Undo()
+    assert_bytes(level0(a, "height"), sc.hm, "everything undone")
+    a.close()
+
+
+@pytest.mark.parametrize("second_stream", (False, True))
+def test_a_stroke_then_an_erode_with_nothing_between(scenes, gpu_ctx, second_stream):
+    """5. A RAISE stroke immediately followed by an erode over an overlapping rectangle (both reuse the terrain's dab buffers), then
+    an erode followed by a stroke, with no synchronisation between: the model of the calls in sequence.  Again with the context on a
+    second stream."""
+    import torch
+    sc = scenes["fast64"]
+    S = world_of(sc)
+    raise_dabs = five_dabs(sc.hm.shape, S, bm.RAISE)
+    mask = np.float32([dab(sc.hm.shape, S, 24.0, 30.0, 20.0, 0.0, 1.0), dab(sc.hm.shape, S, 50.0, 12.0, 9.0, 0.7, 0.6)])
+    m1, r1 = bm.stroke(sc.hm, bm.RAISE, raise_dabs, S)
+    m2, r2 = em.erode(m1, mask, S, ITER, TALUS, RATE)
+    m3, _ = bm.stroke(m2, bm.RAISE, raise_dabs[::-1] * np.float32([1, 1, 1, 1, -0.5]), S)
+    assert (m2 != m1).sum() >= 30 and (m3 != m2).sum() >= 30
+    assert r1[0] < r2[0] + r2[2] and r2[0] < r1[0] + r1[2] and r1[1] < r2[1] + r2[3] and r2[1] < r1[1] + r1[3]         # the rectangles overlap
+    a = sc.terrain(sc.hm, sc.al)
+    gpu_ctx.synchronize()
+    side = torch.cuda.Stream() if second_stream else None
+    try:
+        if side is not None:
+            gpu_ctx.set_stream(side.cuda_stream)
+        a.Brush("raise", raise_dabs)
+        assert a.Erode(mask, ITER, TALUS, RATE) == tuple(r2)
+        a.Brush("raise", raise_dabs[::-1] * np.float32([1, 1, 1, 1, -0.5]))
+        gpu_ctx.synchronize()
+        assert_bytes(level0(a, "height"), m3, f"stroke, erode, stroke (second stream: {second_stream})")
+    finally:
+        torch.cuda.synchronize()
+        gpu_ctx.set_stream(0)
+        a.close()
+
+
+def test_a_refused_call_leaves_no_trace(scenes):
+    """6. A refused call (rate above 1/8) between two good ones: VR_ERR_INVALID_ARGUMENT, and the map is the model's of the two good
+    calls.  n == 0 and dabs that all miss the map are VR_OK with the rectangle {0, 0, 0, 0} and change nothing."""
+    sc = scenes["odd"]
+    S = world_of(sc)
+    dabs = mask_dabs(sc.hm.shape, S)
+    first, _ = model(sc, dabs, 5)
+    second, rect2 = em.erode(first, dabs, S, 9, 0.0, 0.03)
+    assert (second != first).sum() >= 30
+    a = sc.terrain(sc.hm, sc.al, cast=False, render=False)
+    a.Erode(dabs, 5, TALUS, RATE)
+    full = np.zeros((len(dabs), 8), np.float32)
+    full[:, :5] = dabs
+    params = capi.ErodeParams(iterations=9, talus=0.0, rate=0.2)
+    rect = (C.c_int32 * 4)(-1, -1, -1, -1)
+    assert sc.ctx.lib.vr_terrain_erode(a.handle, C.byref(params), full.ctypes.data_as(C.c_void_p), len(full), rect) == capi.VR_ERR_INVALID_ARGUMENT
+    assert_bytes(level0(a, "height"), first, "after the refused call")
+    miss = np.float32([dab(sc.hm.shape, S, -40.0, 5.0, 3.0, 0.0, 1.0), dab(sc.hm.shape, S, 10.5, 12.5, 0.2, 0.0, 1.0)])
+    assert a.Erode(miss, 9, 0.0, RATE) == (0, 0, 0, 0) and a.Erode(np.zeros((0, 5), np.float32), 9, 0.0, RATE) == (0, 0, 0, 0)
+    assert_bytes(level0(a, "height"), first, "after calls that miss")
+    assert a.Erode(dabs, 9, 0.0, 0.03) == tuple(rect2)
+    assert_bytes(level0(a, "height"), second, "after the second good call")
+    assert a.memory_bytes()["scratch"] >= 3 * 4 * rect2[2] * rect2[3]
+    a.close()

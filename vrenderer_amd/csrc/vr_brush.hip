@@ -7,12 +7,14 @@
 //   k_brush<op>        one 256-thread workgroup per 32 x 8 tile of the stroke's rectangle, one texel per lane.  The dab list is
 //                      walked in chunks of 256: lane d tests dab d's span against the tile, the survivors are compacted IN LIST
 //                      ORDER into an LDS index list (ballot + popcount prefix inside a wave, the four waves' totals through LDS),
-//                      then every lane applies the listed dabs in order.  A texel no dab covers is not written.
+//                      then every lane applies the listed dabs in order.  A texel no dab covers is not written.  (The chunk walk
+//                      is vr_brush_dev.h's, shared with vr_erode.hip's mask kernel.)
 //
 // The kernel is untimed, like the mip and table kernels; the node-height and pyramid work counts where the edit's does.
 #include "vr_internal.h"
 #include "vr_dirty.h"
 #include "vr_brush.h"
+#include "vr_brush_dev.h"
 
 #include <string.h>
 
@@ -29,8 +31,6 @@ __global__ __launch_bounds__(256) void k_brush_snapshot(const uint8_t* __restric
     snap[(size_t)(y - sr.y0) * (size_t)(sr.x1 - sr.x0) + (size_t)(x - sr.x0)] = map[(size_t)y * w0 + x];
 }
 
-__device__ __forceinline__ int brush_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // `map`: level 0 (R8: bytes, SRGBA8: dwords), w0 x h0; `r`: the stroke's rectangle, inside the map; `dabs`: n of them, none empty;
 // `snap`: SMOOTH's snapshot of the rectangle `sr`
 template <int OP>
@@ -38,9 +38,9 @@ __global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, i
                                                BrushArgs a, const uint8_t* __restrict__ snap, DirtyRect sr)
 {
     constexpr int NC = OP == kBrushPaint ? 4 : 1;
-    __shared__ uint16_t list[256];          // the chunk's dabs that meet this tile, in list order
+    __shared__ uint16_t list[kBrushChunk];  // the chunk's dabs that meet this tile, in list order
     __shared__ uint32_t wave_total[4];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int tx0 = r.x0 + (int)blockIdx.x * 32, ty0 = r.y0 + (int)blockIdx.y * 8;
     const int tx1 = tx0 + 32 < r.x1 ? tx0 + 32 : r.x1, ty1 = ty0 + 8 < r.y1 ? ty0 + 8 : r.y1;
     const int x = tx0 + (tid & 31), y = ty0 + (tid >> 5);
@@ -73,26 +73,9 @@ __global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, i
     }
     bool touched = false;
     for (uint32_t base = 0; base < n; base += 256) {               // (n is a kernel argument: the trip count is uniform)
-        const uint32_t d = base + (uint32_t)tid;
-        bool hit = false;
-        if (d < n) {
-            const BrushDab& b = dabs[d];
-            hit = b.x0 < tx1 && b.x1 > tx0 && b.y0 < ty1 && b.y1 > ty0;
-        }
-        const unsigned long long m = __ballot(hit);
-        const uint32_t before = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t first = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const uint32_t c = wave_total[k]; first += k < wave ? c : 0u; total += c; }
-        if (hit) list[first + before] = (uint16_t)d;               // first + before < total <= 256
-        __syncthreads();
-        total = __builtin_amdgcn_readfirstlane(total);             // the same in every lane: a scalar loop bound
+        const uint32_t total = brush_chunk_list(dabs, n, base, tx0, ty0, tx1, ty1, list, wave_total);
         for (uint32_t e = 0; e < total; e++) {
-            uint32_t di = __builtin_amdgcn_readfirstlane((uint32_t)list[e]);
-            di = di < n ? di : n - 1;
-            const BrushDab b = dabs[di];
+            const BrushDab b = dabs[brush_chunk_entry(list, e, n)];
             float f;
             if (inside && brush_weight(b, x, y, &f)) {
                 touched = true;
@@ -121,7 +104,6 @@ __global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, i
 // host side
 // ---------------------------------------------------------------------------------------
 static bool host_finite(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
-static dim3 tiles_32x8(const DirtyRect& r) { return dim3((unsigned)((r.x1 - r.x0 + 31) / 32), (unsigned)((r.y1 - r.y0 + 7) / 8)); }
 
 void vr_brush_release(vr_terrain* t)
 {
@@ -129,11 +111,13 @@ void vr_brush_release(vr_terrain* t)
     if (t->h_brush_dabs) { (void)hipHostFree(t->h_brush_dabs); t->h_brush_dabs = nullptr; }
     (void)hipFree(t->d_brush_dabs); t->d_brush_dabs = nullptr;
     (void)hipFree(t->d_brush_snap); t->d_brush_snap = nullptr; t->brush_snap_bytes = 0;
+    (void)hipFree(t->d_erode_mask); (void)hipFree(t->d_erode_state[0]); (void)hipFree(t->d_erode_state[1]);
+    t->d_erode_mask = t->d_erode_state[0] = t->d_erode_state[1] = nullptr; t->erode_plane_bytes = 0;
     t->brush_pending = false;
 }
 
 // the previous stroke's kernel has passed: the pinned dabs, their device copy and the snapshot are free again
-static int brush_consumed(vr_terrain* t)
+int vr_brush_consumed(vr_terrain* t)
 {
     if (!t->brush_pending) return VR_OK;
     VR_HIP(hipEventSynchronize(t->ev_brush));
@@ -142,7 +126,7 @@ static int brush_consumed(vr_terrain* t)
 }
 
 // Everything a stroke needs, before anything is launched: a refusal leaves the terrain as it was.
-static int brush_reserve(vr_terrain* t, size_t snap_bytes)
+int vr_brush_reserve(vr_terrain* t, size_t snap_bytes)
 {
     constexpr size_t dab_bytes = (size_t)VR_MAX_BRUSH_DABS * sizeof(BrushDab);
     if (!t->ev_brush) VR_HIP(hipEventCreateWithFlags(&t->ev_brush, hipEventDisableTiming));
@@ -158,12 +142,45 @@ static int brush_reserve(vr_terrain* t, size_t snap_bytes)
     if (snap_bytes > t->brush_snap_bytes) {
         size_t want = t->brush_snap_bytes ? t->brush_snap_bytes * 2 : (size_t)1 << 16;
         while (want < snap_bytes) want *= 2;
-        const auto idle = [t]() -> int { return brush_consumed(t); };
+        const auto idle = [t]() -> int { return vr_brush_consumed(t); };
         int rc = vr_grow(&t->d_brush_snap, &t->brush_snap_bytes, want, idle);
         if (rc == VR_ERR_OUT_OF_MEMORY && want > snap_bytes) rc = vr_grow(&t->d_brush_snap, &t->brush_snap_bytes, snap_bytes, idle);
         if (rc) { if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain brush: %zu bytes for the snapshot", snap_bytes); return rc; }
     }
     return VR_OK;
+}
+
+// the dab checks of a stroke of `op` (erosion's strengths are opacities: it passes VR_BRUSH_FLATTEN)
+int vr_brush_check_dabs(const vr_brush_dab* dabs, uint32_t n, int op)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const vr_brush_dab& d = dabs[i];
+        VR_REQUIRE(host_finite(d.x) && host_finite(d.z) && host_finite(d.radius) && host_finite(d.hardness) && host_finite(d.strength), "a dab holds a NaN or an infinity");
+        VR_REQUIRE(d.radius > 0.0f, "radius must be positive");
+        VR_REQUIRE(d.hardness >= 0.0f && d.hardness < 1.0f, "hardness outside [0, 1)");
+        if (op == VR_BRUSH_RAISE) VR_REQUIRE(fabsf(d.strength) <= 255.0f, "RAISE: |strength| above 255");
+        else VR_REQUIRE(d.strength >= 0.0f && d.strength <= 1.0f, "opacity outside [0, 1]");
+    }
+    return VR_OK;
+}
+
+// The dabs that meet the map, in order, prepared for the map `tex`, into t->brush_prepared, and the hull of their spans - on the
+// host alone (the vector keeps its room from stroke to stroke).
+DirtyRect vr_brush_prepare_dabs(vr_terrain* t, const DevTex& tex, const vr_brush_dab* dabs, uint32_t n)
+{
+    std::vector<BrushDab>& prepared = t->brush_prepared;
+    prepared.clear();
+    prepared.reserve(VR_MAX_BRUSH_DABS);
+    DirtySpan hx, hy;
+    for (uint32_t i = 0; i < n; i++) {
+        const vr_brush_dab& d = dabs[i];
+        const BrushDab b = brush_prepare(d.x, d.z, d.radius, d.hardness, d.strength, t->p.world_size, tex.w0, tex.h0);
+        if (brush_dab_empty(b)) continue;
+        DirtySpan sx, sy; sx.lo = b.x0; sx.hi = b.x1; sy.lo = b.y0; sy.hi = b.y1;
+        hx = dirty_hull(hx, sx); hy = dirty_hull(hy, sy);
+        prepared.push_back(b);
+    }
+    return dirty_rect(hx, hy);
 }
 
 extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* stroke, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4])
@@ -185,31 +202,11 @@ extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* str
         VR_REQUIRE(stroke->channel_mask >= 1u && stroke->channel_mask <= 15u, "channel_mask must be 1 .. 15");
         for (int c = 0; c < 4; c++) VR_REQUIRE(stroke->color[c] >= 0.0f && stroke->color[c] <= 255.0f, "color outside [0, 255]");
     }
-    for (uint32_t i = 0; i < n; i++) {
-        const vr_brush_dab& d = dabs[i];
-        VR_REQUIRE(host_finite(d.x) && host_finite(d.z) && host_finite(d.radius) && host_finite(d.hardness) && host_finite(d.strength), "a dab holds a NaN or an infinity");
-        VR_REQUIRE(d.radius > 0.0f, "radius must be positive");
-        VR_REQUIRE(d.hardness >= 0.0f && d.hardness < 1.0f, "hardness outside [0, 1)");
-        if (op == VR_BRUSH_RAISE) VR_REQUIRE(fabsf(d.strength) <= 255.0f, "RAISE: |strength| above 255");
-        else VR_REQUIRE(d.strength >= 0.0f && d.strength <= 1.0f, "opacity outside [0, 1]");
-    }
+    { const int rc = vr_brush_check_dabs(dabs, n, op); if (rc) return rc; }
     const int which = op == VR_BRUSH_PAINT ? 1 : 0;
     const DevTex& tex = which == 0 ? t->height : t->albedo;
-    // The dabs that meet the map, in order, prepared for the map the stroke addresses, and the hull of their spans - still on the
-    // host alone (the vector keeps its room from stroke to stroke).
-    std::vector<BrushDab>& prepared = t->brush_prepared;
-    prepared.clear();
-    prepared.reserve(VR_MAX_BRUSH_DABS);
-    DirtySpan hx, hy;
-    for (uint32_t i = 0; i < n; i++) {
-        const vr_brush_dab& d = dabs[i];
-        const BrushDab b = brush_prepare(d.x, d.z, d.radius, d.hardness, d.strength, t->p.world_size, tex.w0, tex.h0);
-        if (brush_dab_empty(b)) continue;
-        DirtySpan sx, sy; sx.lo = b.x0; sx.hi = b.x1; sy.lo = b.y0; sy.hi = b.y1;
-        hx = dirty_hull(hx, sx); hy = dirty_hull(hy, sy);
-        prepared.push_back(b);
-    }
-    const DirtyRect dirty = dirty_rect(hx, hy);
+    const DirtyRect dirty = vr_brush_prepare_dabs(t, tex, dabs, n);
+    const std::vector<BrushDab>& prepared = t->brush_prepared;
     if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
     if (prepared.empty()) return VR_OK;                            // n == 0, or every dab misses the map: nothing is launched
 
@@ -218,9 +215,9 @@ extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* str
     // SMOOTH reads the rectangle grown by one texel, clamped to the map
     DirtyRect sr = dirty;
     if (op == VR_BRUSH_SMOOTH) sr = dirty_rect(dirty_clip(DirtySpan{ dirty.x0 - 1, dirty.x1 + 1 }, tex.w0), dirty_clip(DirtySpan{ dirty.y0 - 1, dirty.y1 + 1 }, tex.h0));
-    { const int rc = brush_reserve(t, op == VR_BRUSH_SMOOTH ? (size_t)(sr.x1 - sr.x0) * (size_t)(sr.y1 - sr.y0) : 0); if (rc) return rc; }
+    { const int rc = vr_brush_reserve(t, op == VR_BRUSH_SMOOTH ? (size_t)(sr.x1 - sr.x0) * (size_t)(sr.y1 - sr.y0) : 0); if (rc) return rc; }
     // the one wait on the host: only where the previous stroke has not been consumed yet
-    { const int rc = brush_consumed(t); if (rc) return rc; }
+    { const int rc = vr_brush_consumed(t); if (rc) return rc; }
     const uint32_t nd = (uint32_t)prepared.size();
     memcpy(t->h_brush_dabs, prepared.data(), (size_t)nd * sizeof(BrushDab));
 

@@ -1,0 +1,44 @@
+// Device code the kernels that walk a dab list share (k_brush in vr_brush.hip, k_erode_begin in vr_erode.hip): a 256-thread
+// workgroup per 32 x 8 tile of the rectangle, one texel per lane, the list walked in chunks of 256 dabs.
+#pragma once
+#include "vr_internal.h"
+#include "vr_dirty.h"
+#include "vr_brush.h"
+
+constexpr int kBrushTileW = 32, kBrushTileH = 8, kBrushChunk = 256;
+
+__device__ __forceinline__ int brush_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+inline dim3 tiles_32x8(const DirtyRect& r) { return dim3((unsigned)((r.x1 - r.x0 + kBrushTileW - 1) / kBrushTileW), (unsigned)((r.y1 - r.y0 + kBrushTileH - 1) / kBrushTileH)); }
+
+// One chunk of the list: lane d tests dab base + d's span against the tile [tx0, tx1) x [ty0, ty1), and the survivors are
+// compacted IN LIST ORDER into `list` (ballot + popcount prefix inside a wave, the four waves' totals through `wave_total`).
+// Returns how many there are, the same in every lane (a scalar loop bound).  Every lane of the workgroup calls it (two barriers
+// inside); the caller puts one more barrier behind its use of `list`, in front of the next chunk.
+__device__ __forceinline__ uint32_t brush_chunk_list(const BrushDab* __restrict__ dabs, uint32_t n, uint32_t base, int tx0, int ty0, int tx1, int ty1,
+                                                     uint16_t (&list)[kBrushChunk], uint32_t (&wave_total)[4])
+{
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t d = base + (uint32_t)tid;
+    bool hit = false;
+    if (d < n) {
+        const BrushDab& b = dabs[d];
+        hit = b.x0 < tx1 && b.x1 > tx0 && b.y0 < ty1 && b.y1 > ty0;
+    }
+    const unsigned long long m = __ballot(hit);
+    const uint32_t before = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t first = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const uint32_t c = wave_total[k]; first += k < wave ? c : 0u; total += c; }
+    if (hit) list[first + before] = (uint16_t)d;               // first + before < total <= 256
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(total);
+}
+
+// entry e of the chunk's list: the dab's index, wave-uniform and inside the list whatever LDS held
+__device__ __forceinline__ uint32_t brush_chunk_entry(const uint16_t (&list)[kBrushChunk], uint32_t e, uint32_t n)
+{
+    const uint32_t di = __builtin_amdgcn_readfirstlane((uint32_t)list[e]);
+    return di < n ? di : n - 1;
+}

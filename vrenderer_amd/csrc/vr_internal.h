@@ -397,6 +397,10 @@ struct vr_terrain {
     BrushDab* h_brush_dabs = nullptr; BrushDab* d_brush_dabs = nullptr;
     void* d_brush_snap = nullptr; size_t brush_snap_bytes = 0;
     hipEvent_t ev_brush = nullptr; bool brush_pending = false;
+    // Erosion (vr_erode.hip): the mask and the two state planes, fp32, of the largest rectangle so far (erode_plane_bytes each).
+    // Their one reader is the erosion's kernels, which run in front of the same event: an erode shares the brush's dab buffers
+    // and its consumed-event protocol, so strokes and erodes of one terrain order against each other whichever stream they ran on.
+    float* d_erode_mask = nullptr; float* d_erode_state[2] = { nullptr, nullptr }; size_t erode_plane_bytes = 0;
     // History (vr_history.hip): the journal's bookkeeping (vr_history.h) over a table of kHistoryMaxRecords records and one device
     // arena, both from vr_terrain_history_enable on, and the event behind the latest journal kernel with the stream it ran on - a
     // journal kernel on another stream waits for it (the rule of ev_pyramid / pyramid_stream).
@@ -407,7 +411,16 @@ struct vr_terrain {
     hipEvent_t ev_history = nullptr; hipStream_t history_stream = nullptr; bool history_queued = false;
 };
 void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
-void vr_brush_release(vr_terrain* t);      // the brush's memory and event (vr_brush.hip)
+void vr_brush_release(vr_terrain* t);      // the brush's and the erosion's memory and their event (vr_brush.hip)
+// What vr_terrain_brush and vr_terrain_erode share (vr_brush.hip).  check_dabs: the dab refusals of a stroke of `op` (an opacity
+// op for the erosion).  prepare_dabs: the dabs that meet the map `tex`, in order, into t->brush_prepared; returns the hull of their
+// spans.  reserve: the event, the pinned and the device dab list and `snap_bytes` of snapshot, before anything is launched.
+// consumed: the one wait on the host - the kernels in front of the latest record of ev_brush have passed.
+struct DirtyRect;
+int vr_brush_check_dabs(const vr_brush_dab* dabs, uint32_t n, int op);
+DirtyRect vr_brush_prepare_dabs(vr_terrain* t, const DevTex& tex, const vr_brush_dab* dabs, uint32_t n);
+int vr_brush_reserve(vr_terrain* t, size_t snap_bytes);
+int vr_brush_consumed(vr_terrain* t);
 void vr_history_release(vr_terrain* t);    // the journal's arena and event; history is off afterwards (vr_history.hip)
 // In front of a write of the rectangle `dirty` of level 0 (inside vr_derive_level0_write's write_level0, so behind its waits): with
 // history on, a record is appended and the kernel that captures the rectangle is queued on `s`.  Synchronises nothing; with

@@ -529,6 +529,26 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_brush(self.handle, C.byref(stroke), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_brush")
         return tuple(int(v) for v in rect)
 
+    def Erode(self, dabs, iterations, talus, rate):
+        """vr_terrain_erode: `iterations` sweeps of thermal erosion on level 0 of the heightmap under the mask the dabs form (rows as
+        for Brush, strength an opacity in [0, 1]; their order does not matter), computed on the device; stream-ordered, nothing is
+        synchronised.  `talus`: the height difference per texel, in heightmap steps, that stays (0 .. 255; x sqrt 2 on the diagonals);
+        `rate`: the share of the excess moved per sweep and neighbour, 0 < rate <= 0.125.  Returns (x, y, w, h) of the level-0
+        rectangle the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
+        a = np.asarray(dabs, np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 5)
+        assert a.ndim == 2 and a.shape[1] in (5, 8)
+        if a.shape[1] == 5:
+            full = np.zeros((a.shape[0], 8), np.float32)
+            full[:, :5] = a
+            a = full
+        a = np.ascontiguousarray(a)
+        params = capi.ErodeParams(iterations=int(iterations), talus=float(talus), rate=float(rate))
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_erode(self.handle, C.byref(params), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_erode")
+        return tuple(int(v) for v in rect)
+
     def EnableHistory(self, budget_bytes):
         """vr_terrain_history_enable: a device arena of budget_bytes in which every Edit and Brush from now on first records the
         rectangle it is about to write; 0 switches history off and frees the arena; another budget drops all steps."""
