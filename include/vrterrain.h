@@ -183,7 +183,7 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
  * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
  * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
- * vr_terrain_edit / _brush / _erode / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * vr_terrain_edit / _brush / _erode / _erode_hydraulic / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
  * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
  * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
  * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
@@ -320,13 +320,47 @@ typedef struct vr_erode_params { int32_t iterations; float talus; float rate; in
 VR_API int vr_terrain_erode(vr_terrain* t, const vr_erode_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
 /* test helper: {tile width, tile height, sweeps per launch, 0} of this build's erosion kernel */
 VR_API int vr_debug_erode_config(int32_t out[4]);
-/* History: undo and redo of vr_terrain_edit, vr_terrain_brush and vr_terrain_erode, kept on the device.  Off by default: every call then queues
+/* Hydraulic erosion of level 0 of the heightmap under a brush mask - water that runs downhill, dissolves the terrain where it runs
+ * fast and lays the load down where it slows: gullies and fans, which the talus relaxation of vr_terrain_erode cannot make.  It is
+ * computed on the device from the map as it is there and followed by the refresh vr_terrain_edit does: afterwards the terrain is the
+ * one vr_terrain_create builds from the eroded map.  The mask m is vr_terrain_erode's (per texel the largest weight * strength of the
+ * dabs that cover it, strength an opacity in [0, 1]).  A texel carries three fp32 values: h, the terrain in heightmap steps (the
+ * stored byte to begin with), d, the water depth (rain * m to begin with), and s, the suspended sediment (0 to begin with).  They
+ * are advanced `iterations` times, every texel of a sweep from the sweep before.  For each of the four axis neighbours n inside the
+ * map, in the order (0,-1) (-1,0) (1,0) (0,1) of (dx, dy), with w = min(m, m_n) > 0: the end with the higher surface S = h + d
+ * gives the share phi = min(flow * (S_high - S_low), 0.25) * w of its water, q = phi * d, and of its sediment, phi * s, to the
+ * other - both ends compute the same amounts, bit for bit; `out` is the water the texel gave.  Then d and s are clamped at 0, the
+ * capacity is C = capacity * out, and a texel with s < C dissolves e = dissolve * (C - s) * m of its terrain (h -= e, s += e) while
+ * one with s >= C deposits g = deposit * (s - C) (h += g, s -= g); the water becomes d * (1 - evaporation) + rain * m.  After the
+ * last sweep a texel with a positive mask is stored as the nearest byte of min(max(h + s, 0), 255) - what is still suspended
+ * settles where it is; a texel with mask 0 keeps its byte (it is not written).  rain = 0 or capacity = 0 leaves the map as it is.
+ * The arithmetic is defined bit for bit in vrenderer_amd/csrc/vr_hydro.h, without a division or a square root;
+ * the result does not depend on how the device divides the work.
+ * out_rect, `dabs`, the stream order and what the host waits for are vr_terrain_brush's: the call synchronises nothing, and
+ * strokes and erosions of both kinds of one terrain are ordered against each other.  With history on, one call is one record.
+ * n == 0, or dabs that all miss the map, is VR_OK and launches nothing.  The device advances several sweeps per launch: a call
+ * costs about iterations / 4 short kernels on top of the refresh.
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the terrain untouched: NULL t or p, NULL dabs with
+ * n > 0; n > VR_MAX_BRUSH_DABS; iterations < 1 or > VR_HYDRO_MAX_ITERATIONS; a parameter NaN or infinite; rain outside [0, 16];
+ * flow <= 0 or > 1; capacity outside [0, 64]; dissolve, deposit or evaporation outside [0, 1]; a non-zero reserved word; the dab
+ * refusals of vr_terrain_brush with an opacity for a strength.  The memory a call needs - seven fp32 planes of the rectangle's
+ * size, kept with the terrain and counted under scratch by vr_terrain_memory_bytes - is reserved before anything is launched
+ * (VR_ERR_OUT_OF_MEMORY leaves the terrain as it was).  Timing: as for vr_terrain_edit; the erosion kernels themselves are untimed. */
+#define VR_HYDRO_MAX_ITERATIONS 1024
+typedef struct vr_hydro_params { int32_t iterations; float rain, flow, capacity, dissolve, deposit, evaporation; int32_t reserved; } vr_hydro_params; /* 32 B */
+VR_API int vr_terrain_erode_hydraulic(vr_terrain* t, const vr_hydro_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
+/* test helper: {tile width, tile height, sweeps per launch, 0} of this build's hydraulic kernel */
+VR_API int vr_debug_hydro_config(int32_t out[4]);
+/* measurement helper, process-wide: later calls advance `sweeps` (1 .. the build's figure; 0 = that figure again) sweeps per
+ * launch.  The bytes are the same; only the number of launches changes.  VR_ERR_INVALID_ARGUMENT outside that range. */
+VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps);
+/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
  * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
  *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
  *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
  *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
  *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
- *   records               with history on, every vr_terrain_edit, _brush and _erode that writes (not w == 0, n == 0 or a stroke
+ *   records               with history on, every vr_terrain_edit, _brush, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
  *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
  *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
  *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no

@@ -226,7 +226,17 @@ namespace vRenderer
             p.iterations = iterations; p.talus = talus; p.rate = rate;
             return Check(vr_terrain_erode(m_Terrain, &p, dabs, n, outRect), "vr_terrain_erode");
         }
-        // vr_terrain_history_*: undo and redo of Edit, Brush and Erode on the device.  EnableHistory(bytes) sets the arena (0: off);
+        // vr_terrain_erode_hydraulic: `iterations` sweeps of hydraulic erosion of the heightmap's level 0 under the mask the n dabs form
+        // (as for Erode): water rains on the mask, runs downhill, dissolves terrain where it runs and deposits where it slows.  rain
+        // 0 .. 16 per sweep, flow in (0, 1], capacity 0 .. 64, dissolve, deposit and evaporation in [0, 1].  Stream-ordered like Brush.
+        bool ErodeHydraulic(const vr_brush_dab* dabs, uint32_t n, int32_t iterations, float rain, float flow, float capacity, float dissolve, float deposit,
+                            float evaporation, int32_t outRect[4] = nullptr)
+        {
+            vr_hydro_params p = {};
+            p.iterations = iterations; p.rain = rain; p.flow = flow; p.capacity = capacity; p.dissolve = dissolve; p.deposit = deposit; p.evaporation = evaporation;
+            return Check(vr_terrain_erode_hydraulic(m_Terrain, &p, dabs, n, outRect), "vr_terrain_erode_hydraulic");
+        }
+        // vr_terrain_history_*: undo and redo of Edit, Brush, Erode and ErodeHydraulic on the device.  EnableHistory(bytes) sets the arena (0: off);
         // CommitHistory closes the open step (mouse-up); Undo / Redo return whether a step was applied (*applied).
         bool EnableHistory(size_t budgetBytes) { return Check(vr_terrain_history_enable(m_Terrain, budgetBytes), "vr_terrain_history_enable"); }
         bool CommitHistory() { return Check(vr_terrain_history_commit(m_Terrain), "vr_terrain_history_commit"); }

@@ -41,6 +41,7 @@ VR_BRUSH_SMOOTH = 2
 VR_BRUSH_PAINT = 3
 VR_HISTORY_MAX_RECORDS = 4096
 VR_ERODE_MAX_ITERATIONS = 1024
+VR_HYDRO_MAX_ITERATIONS = 1024
 
 
 class TerrainParams(C.Structure):
@@ -171,6 +172,12 @@ class ErodeParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("talus", C.c_float), ("rate", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
+class HydroParams(C.Structure):
+    """vr_hydro_params: sweeps, rain per sweep (0 .. 16), flow in (0, 1], capacity (0 .. 64), dissolve, deposit, evaporation in [0, 1]."""
+    _fields_ = [("iterations", C.c_int32), ("rain", C.c_float), ("flow", C.c_float), ("capacity", C.c_float), ("dissolve", C.c_float),
+                ("deposit", C.c_float), ("evaporation", C.c_float), ("reserved", C.c_int32)]
+
+
 class HistoryStatus(C.Structure):
     """vr_history_status: what undo / redo can apply now, the open step, the steps lost to the budget, the arena's bytes."""
     _fields_ = [("undo_steps", C.c_uint32), ("redo_steps", C.c_uint32), ("open_records", C.c_uint32), ("dropped_steps", C.c_uint32),
@@ -179,7 +186,7 @@ class HistoryStatus(C.Structure):
 
 assert C.sizeof(HistoryStatus) == 32
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
-assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32 and C.sizeof(ErodeParams) == 32
+assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32 and C.sizeof(ErodeParams) == 32 and C.sizeof(HydroParams) == 32
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -204,6 +211,7 @@ EXPORTS = [
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
     "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush", "vr_terrain_erode", "vr_debug_erode_config",
+    "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
 ]
 
@@ -330,6 +338,9 @@ def load_library():
         "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_erode": (C.c_int, [vp, P(ErodeParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_debug_erode_config": (C.c_int, [P(C.c_int32)]),
+        "vr_terrain_erode_hydraulic": (C.c_int, [vp, P(HydroParams), vp, C.c_uint32, P(C.c_int32)]),
+        "vr_debug_hydro_config": (C.c_int, [P(C.c_int32)]),
+        "vr_debug_hydro_sweeps_per_launch": (C.c_int, [C.c_int32]),
         "vr_terrain_history_enable": (C.c_int, [vp, C.c_size_t]),
         "vr_terrain_history_commit": (C.c_int, [vp]),
         "vr_terrain_undo": (C.c_int, [vp, P(C.c_int32)]),

@@ -113,6 +113,7 @@ void vr_brush_release(vr_terrain* t)
     (void)hipFree(t->d_brush_snap); t->d_brush_snap = nullptr; t->brush_snap_bytes = 0;
     (void)hipFree(t->d_erode_mask); (void)hipFree(t->d_erode_state[0]); (void)hipFree(t->d_erode_state[1]);
     t->d_erode_mask = t->d_erode_state[0] = t->d_erode_state[1] = nullptr; t->erode_plane_bytes = 0;
+    (void)hipFree(t->d_hydro); t->d_hydro = nullptr; t->hydro_plane_bytes = 0;
     t->brush_pending = false;
 }
 

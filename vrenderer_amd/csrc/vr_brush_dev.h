@@ -1,9 +1,10 @@
-// Device code the kernels that walk a dab list share (k_brush in vr_brush.hip, k_erode_begin in vr_erode.hip): a 256-thread
-// workgroup per 32 x 8 tile of the rectangle, one texel per lane, the list walked in chunks of 256 dabs.
+// Device code the kernels that walk a dab list share (k_brush in vr_brush.hip, k_erode_begin in vr_erode.hip, k_hydro_begin in
+// vr_hydro.hip): a 256-thread workgroup per 32 x 8 tile of the rectangle, one texel per lane, the list walked in chunks of 256 dabs.
 #pragma once
 #include "vr_internal.h"
 #include "vr_dirty.h"
 #include "vr_brush.h"
+#include "vr_erode.h"
 
 constexpr int kBrushTileW = 32, kBrushTileH = 8, kBrushChunk = 256;
 
@@ -41,4 +42,22 @@ __device__ __forceinline__ uint32_t brush_chunk_entry(const uint16_t (&list)[kBr
 {
     const uint32_t di = __builtin_amdgcn_readfirstlane((uint32_t)list[e]);
     return di < n ? di : n - 1;
+}
+
+// The erosions' mask (vr_erode.h) of the lane's texel (x, y) under the whole list, for the tile [tx0, tx1) x [ty0, ty1).  Every lane
+// of the workgroup calls it and stays to the end (barriers inside); a lane whose texel is not `inside` the tile gets 0.
+__device__ __forceinline__ float brush_tile_mask(const BrushDab* __restrict__ dabs, uint32_t n, int tx0, int ty0, int tx1, int ty1, int x, int y, bool inside,
+                                                 uint16_t (&list)[kBrushChunk], uint32_t (&wave_total)[4])
+{
+    float m = 0.0f;
+    for (uint32_t base = 0; base < n; base += kBrushChunk) {       // (n is a kernel argument: the trip count is uniform)
+        const uint32_t total = brush_chunk_list(dabs, n, base, tx0, ty0, tx1, ty1, list, wave_total);
+        for (uint32_t e = 0; e < total; e++) {
+            const BrushDab b = dabs[brush_chunk_entry(list, e, n)];
+            float f;
+            if (inside && brush_weight(b, x, y, &f)) m = erode_mask_max(m, f, b.strength);
+        }
+        __syncthreads();                                           // the next chunk overwrites list and wave_total
+    }
+    return m;
 }

@@ -45,16 +45,7 @@ __global__ __launch_bounds__(256) void k_erode_begin(const uint8_t* __restrict__
     // every lane stays to the end; one outside the rectangle works on the clamped texel and writes nothing
     const int cx = brush_clampi(x, r.x0, r.x1 - 1), cy = brush_clampi(y, r.y0, r.y1 - 1);
     const float h = (float)map[(size_t)brush_clampi(cy, 0, h0 - 1) * (size_t)w0 + (size_t)brush_clampi(cx, 0, w0 - 1)];
-    float m = 0.0f;
-    for (uint32_t base = 0; base < n; base += kBrushChunk) {       // (n is a kernel argument: the trip count is uniform)
-        const uint32_t total = brush_chunk_list(dabs, n, base, tx0, ty0, tx1, ty1, list, wave_total);
-        for (uint32_t e = 0; e < total; e++) {
-            const BrushDab b = dabs[brush_chunk_entry(list, e, n)];
-            float f;
-            if (inside && brush_weight(b, x, y, &f)) m = erode_mask_max(m, f, b.strength);
-        }
-        __syncthreads();                                           // the next chunk overwrites list and wave_total
-    }
+    const float m = brush_tile_mask(dabs, n, tx0, ty0, tx1, ty1, x, y, inside, list, wave_total);
     if (!inside) return;
     const size_t at = (size_t)(y - r.y0) * (size_t)(r.x1 - r.x0) + (size_t)(x - r.x0);
     mask[at] = m;

@@ -401,6 +401,9 @@ struct vr_terrain {
     // Their one reader is the erosion's kernels, which run in front of the same event: an erode shares the brush's dab buffers
     // and its consumed-event protocol, so strokes and erodes of one terrain order against each other whichever stream they ran on.
     float* d_erode_mask = nullptr; float* d_erode_state[2] = { nullptr, nullptr }; size_t erode_plane_bytes = 0;
+    // Hydraulic erosion (vr_hydro.hip): one block of seven fp32 planes - the mask and two sets of terrain, water and sediment - of the
+    // largest rectangle so far (hydro_plane_bytes each), under the same event and protocol as the planes above.
+    float* d_hydro = nullptr; size_t hydro_plane_bytes = 0;
     // History (vr_history.hip): the journal's bookkeeping (vr_history.h) over a table of kHistoryMaxRecords records and one device
     // arena, both from vr_terrain_history_enable on, and the event behind the latest journal kernel with the stream it ran on - a
     // journal kernel on another stream waits for it (the rule of ev_pyramid / pyramid_stream).
@@ -411,8 +414,8 @@ struct vr_terrain {
     hipEvent_t ev_history = nullptr; hipStream_t history_stream = nullptr; bool history_queued = false;
 };
 void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
-void vr_brush_release(vr_terrain* t);      // the brush's and the erosion's memory and their event (vr_brush.hip)
-// What vr_terrain_brush and vr_terrain_erode share (vr_brush.hip).  check_dabs: the dab refusals of a stroke of `op` (an opacity
+void vr_brush_release(vr_terrain* t);      // the brush's and the erosions' memory and their event (vr_brush.hip)
+// What vr_terrain_brush, vr_terrain_erode and vr_terrain_erode_hydraulic share (vr_brush.hip).  check_dabs: the dab refusals of a stroke of `op` (an opacity
 // op for the erosion).  prepare_dabs: the dabs that meet the map `tex`, in order, into t->brush_prepared; returns the hull of their
 // spans.  reserve: the event, the pinned and the device dab list and `snap_bytes` of snapshot, before anything is launched.
 // consumed: the one wait on the host - the kernels in front of the latest record of ev_brush have passed.

@@ -549,6 +549,28 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_erode(self.handle, C.byref(params), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_erode")
         return tuple(int(v) for v in rect)
 
+    def ErodeHydraulic(self, dabs, iterations, rain, flow, capacity, dissolve, deposit, evaporation):
+        """vr_terrain_erode_hydraulic: `iterations` sweeps of hydraulic erosion on level 0 of the heightmap under the mask the dabs form
+        (rows as for Erode), computed on the device; stream-ordered, nothing is synchronised.  `rain`: water added per sweep where the
+        mask is 1 (0 .. 16); `flow`: the share of a surface difference that runs off per sweep, 0 < flow <= 1; `capacity`: sediment
+        carried per unit of water given (0 .. 64); `dissolve`, `deposit`: the shares of the gap to the capacity taken up or laid down
+        per sweep; `evaporation`: the share of the water lost per sweep (each 0 .. 1).  Returns (x, y, w, h) of the level-0 rectangle
+        the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
+        a = np.asarray(dabs, np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 5)
+        assert a.ndim == 2 and a.shape[1] in (5, 8)
+        if a.shape[1] == 5:
+            full = np.zeros((a.shape[0], 8), np.float32)
+            full[:, :5] = a
+            a = full
+        a = np.ascontiguousarray(a)
+        params = capi.HydroParams(iterations=int(iterations), rain=float(rain), flow=float(flow), capacity=float(capacity), dissolve=float(dissolve),
+                                  deposit=float(deposit), evaporation=float(evaporation))
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_erode_hydraulic(self.handle, C.byref(params), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_erode_hydraulic")
+        return tuple(int(v) for v in rect)
+
     def EnableHistory(self, budget_bytes):
         """vr_terrain_history_enable: a device arena of budget_bytes in which every Edit and Brush from now on first records the
         rectangle it is about to write; 0 switches history off and frees the arena; another budget drops all steps."""
