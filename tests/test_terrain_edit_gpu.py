@@ -109,6 +109,30 @@ def _assert_chains_equal(a, b, what):
             assert np.array_equal(x, y), f"{what}: {which} level {l} differs in {(x != y).sum()} bytes, first {np.argwhere(x != y)[:4].tolist()}"
 
 
+def _assert_terrains_equal(sc, a, b, what):
+    """Everything the library exposes of terrains A and B of scene `sc`: every mip level, node heights and selections, every G-buffer
+    plane for cameras 0 and 5, 1024 sampled heights with normals, 64 ray hits."""
+    _assert_chains_equal(a, b, what)
+    surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
+    nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
+    ha, hb = a.node_heights(0, nodes), b.node_heights(0, nodes)
+    assert np.array_equal(ha.view(np.uint32), hb.view(np.uint32)), f"{what}: {(ha.view(np.uint32) != hb.view(np.uint32)).any(1).sum()} of {nodes} nodes differ"
+    for cam in (0, 5):
+        v = sc.view(cam)
+        na, ia, insta = a.NodeSelect(v, sc.mh)
+        nb, ib, instb = b.NodeSelect(v, sc.mh)
+        assert na == nb and na > 0 and np.array_equal(ia, ib) and np.array_equal(insta, instb), (what, cam, na, nb)
+        _assert_frames_equal(_render(sc, a, cam), _render(sc, b, cam), f"{what}, camera {cam}")
+    pts = qc.uniform_points(sc.world, 1024)
+    (h1, n1), (h2, n2) = a.SampleHeights(pts, sc.mh, normals=True), b.SampleHeights(pts, sc.mh, normals=True)
+    assert np.array_equal(h1.view(np.uint32), h2.view(np.uint32)) and np.array_equal(n1.view(np.uint32), n2.view(np.uint32))
+    surf = Surface64(b.download_mip("height", 0), b.download_mip("height", 1), sc.world, sc.mh)
+    o, d, tm = qc.make_rays(surf, sc.world, n=64)
+    ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
+    assert ra.tobytes() == rb.tobytes(), f"{what}: {(ra != rb).sum()} of {len(ra)} hits differ"
+    assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
+
+
 def _render(sc, tp, cam, part=None, **rpkw):
     rt = vr.RenderTargets(sc.ctx).Init(W, H)
     if not rpkw.get("assume_cleared"):

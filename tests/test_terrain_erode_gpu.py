@@ -10,9 +10,7 @@ import pytest
 from vrenderer_amd import capi
 from tests import brush_model as bm
 from tests import erode_model as em
-from tests import queries_common as qc
 from tests import test_terrain_edit_gpu as te
-from tests.f64_queries import Surface64
 from tests.test_terrain_brush_gpu import assert_bytes, dab, five_dabs, level0, world_of
 
 pytestmark = pytest.mark.gpu
@@ -125,25 +123,7 @@ def test_the_terrain_is_the_one_created_from_the_eroded_map(scenes, name):
     a = sc.terrain(sc.hm, sc.al)
     a.Erode(dabs, ITER, TALUS, RATE)
     b = sc.terrain(hm, sc.al)
-    te._assert_chains_equal(a, b, name)
-    surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
-    nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
-    ha, hb = a.node_heights(0, nodes), b.node_heights(0, nodes)
-    assert np.array_equal(ha.view(np.uint32), hb.view(np.uint32)), f"{name}: {(ha.view(np.uint32) != hb.view(np.uint32)).any(1).sum()} of {nodes} nodes differ"
-    for cam in (0, 5):
-        v = sc.view(cam)
-        na, ia, insta = a.NodeSelect(v, sc.mh)
-        nb, ib, instb = b.NodeSelect(v, sc.mh)
-        assert na == nb and na > 0 and np.array_equal(ia, ib) and np.array_equal(insta, instb), (name, cam, na, nb)
-        te._assert_frames_equal(te._render(sc, a, cam), te._render(sc, b, cam), f"{name}, camera {cam}")
-    pts = qc.uniform_points(sc.world, 1024)
-    (h1, n1), (h2, n2) = a.SampleHeights(pts, sc.mh, normals=True), b.SampleHeights(pts, sc.mh, normals=True)
-    assert np.array_equal(h1.view(np.uint32), h2.view(np.uint32)) and np.array_equal(n1.view(np.uint32), n2.view(np.uint32))
-    surf = Surface64(b.download_mip("height", 0), b.download_mip("height", 1), sc.world, sc.mh)
-    o, d, tm = qc.make_rays(surf, sc.world, n=64)
-    ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
-    assert ra.tobytes() == rb.tobytes(), f"{name}: {(ra != rb).sum()} of {len(ra)} hits differ"
-    assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
+    te._assert_terrains_equal(sc, a, b, name)
     a.close(); b.close()
 
 

@@ -103,17 +103,13 @@ __global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, i
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-static bool host_finite(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
-
 void vr_brush_release(vr_terrain* t)
 {
     if (t->ev_brush) { (void)hipEventSynchronize(t->ev_brush); (void)hipEventDestroy(t->ev_brush); t->ev_brush = nullptr; }
     if (t->h_brush_dabs) { (void)hipHostFree(t->h_brush_dabs); t->h_brush_dabs = nullptr; }
     (void)hipFree(t->d_brush_dabs); t->d_brush_dabs = nullptr;
     (void)hipFree(t->d_brush_snap); t->d_brush_snap = nullptr; t->brush_snap_bytes = 0;
-    (void)hipFree(t->d_erode_mask); (void)hipFree(t->d_erode_state[0]); (void)hipFree(t->d_erode_state[1]);
-    t->d_erode_mask = t->d_erode_state[0] = t->d_erode_state[1] = nullptr; t->erode_plane_bytes = 0;
-    (void)hipFree(t->d_hydro); t->d_hydro = nullptr; t->hydro_plane_bytes = 0;
+    (void)hipFree(t->d_erode); t->d_erode = nullptr; t->erode_bytes = 0;
     t->brush_pending = false;
 }
 
@@ -140,15 +136,23 @@ int vr_brush_reserve(vr_terrain* t, size_t snap_bytes)
         if (!vr_dev_alloc(&p, dab_bytes)) { vr_set_error("terrain brush: %zu bytes for the dab list", dab_bytes); return VR_ERR_OUT_OF_MEMORY; }
         t->d_brush_dabs = (BrushDab*)p;
     }
-    if (snap_bytes > t->brush_snap_bytes) {
-        size_t want = t->brush_snap_bytes ? t->brush_snap_bytes * 2 : (size_t)1 << 16;
-        while (want < snap_bytes) want *= 2;
-        const auto idle = [t]() -> int { return vr_brush_consumed(t); };
-        int rc = vr_grow(&t->d_brush_snap, &t->brush_snap_bytes, want, idle);
-        if (rc == VR_ERR_OUT_OF_MEMORY && want > snap_bytes) rc = vr_grow(&t->d_brush_snap, &t->brush_snap_bytes, snap_bytes, idle);
-        if (rc) { if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain brush: %zu bytes for the snapshot", snap_bytes); return rc; }
-    }
-    return VR_OK;
+    const int rc = vr_brush_grow(t, &t->d_brush_snap, &t->brush_snap_bytes, snap_bytes);
+    if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain brush: %zu bytes for the snapshot", snap_bytes);
+    return rc;
+}
+
+// A buffer whose one reader runs in front of ev_brush holds `bytes`: grown from 64 KiB by doubling - to exactly `bytes` where the
+// doubled size does not fit - and the old block freed behind vr_brush_consumed.  A refusal leaves the terrain as it was; the
+// caller words VR_ERR_OUT_OF_MEMORY's message.
+int vr_brush_grow(vr_terrain* t, void** ptr, size_t* capacity, size_t bytes)
+{
+    if (bytes <= *capacity) return VR_OK;
+    size_t want = *capacity ? *capacity * 2 : (size_t)1 << 16;
+    while (want < bytes) want *= 2;
+    const auto idle = [t]() -> int { return vr_brush_consumed(t); };
+    int rc = vr_grow(ptr, capacity, want, idle);
+    if (rc == VR_ERR_OUT_OF_MEMORY && want > bytes) rc = vr_grow(ptr, capacity, bytes, idle);
+    return rc;
 }
 
 // the dab checks of a stroke of `op` (erosion's strengths are opacities: it passes VR_BRUSH_FLATTEN)
@@ -203,48 +207,30 @@ extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* str
         VR_REQUIRE(stroke->channel_mask >= 1u && stroke->channel_mask <= 15u, "channel_mask must be 1 .. 15");
         for (int c = 0; c < 4; c++) VR_REQUIRE(stroke->color[c] >= 0.0f && stroke->color[c] <= 255.0f, "color outside [0, 255]");
     }
-    { const int rc = vr_brush_check_dabs(dabs, n, op); if (rc) return rc; }
     const int which = op == VR_BRUSH_PAINT ? 1 : 0;
     const DevTex& tex = which == 0 ? t->height : t->albedo;
-    const DirtyRect dirty = vr_brush_prepare_dabs(t, tex, dabs, n);
-    const std::vector<BrushDab>& prepared = t->brush_prepared;
-    if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
-    if (prepared.empty()) return VR_OK;                            // n == 0, or every dab misses the map: nothing is launched
-
-    vr_context* ctx = t->ctx;
-    VR_HIP(hipSetDevice(ctx->device));
-    // SMOOTH reads the rectangle grown by one texel, clamped to the map
-    DirtyRect sr = dirty;
-    if (op == VR_BRUSH_SMOOTH) sr = dirty_rect(dirty_clip(DirtySpan{ dirty.x0 - 1, dirty.x1 + 1 }, tex.w0), dirty_clip(DirtySpan{ dirty.y0 - 1, dirty.y1 + 1 }, tex.h0));
-    { const int rc = vr_brush_reserve(t, op == VR_BRUSH_SMOOTH ? (size_t)(sr.x1 - sr.x0) * (size_t)(sr.y1 - sr.y0) : 0); if (rc) return rc; }
-    // the one wait on the host: only where the previous stroke has not been consumed yet
-    { const int rc = vr_brush_consumed(t); if (rc) return rc; }
-    const uint32_t nd = (uint32_t)prepared.size();
-    memcpy(t->h_brush_dabs, prepared.data(), (size_t)nd * sizeof(BrushDab));
-
     BrushArgs a; memset(&a, 0, sizeof(a));
     a.target = stroke->target; a.channel_mask = stroke->channel_mask;
     for (int c = 0; c < 4; c++) a.color[c] = stroke->color[c];
-    void* mem = const_cast<uint8_t*>(tex.base);
-    const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t s) -> int {
-        { const int hrc = vr_history_capture(t, which, dirty, s); if (hrc) return hrc; }       // history on: the rectangle as it is, first
-        VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)nd * sizeof(BrushDab), hipMemcpyHostToDevice, s));
-        const uint8_t* snap = (const uint8_t*)t->d_brush_snap;
-        const dim3 grid = tiles_32x8(dirty);
-        switch (op) {
-        case VR_BRUSH_RAISE: hipLaunchKernelGGL(k_brush<kBrushRaise>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
-        case VR_BRUSH_FLATTEN: hipLaunchKernelGGL(k_brush<kBrushFlatten>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
-        case VR_BRUSH_SMOOTH:
-            hipLaunchKernelGGL(k_brush_snapshot, tiles_32x8(sr), dim3(256), 0, s, (const uint8_t*)mem, tex.w0, (uint8_t*)t->d_brush_snap, sr);
-            hipLaunchKernelGGL(k_brush<kBrushSmooth>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
-        default: hipLaunchKernelGGL(k_brush<kBrushPaint>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
-        }
-        VR_HIP(hipGetLastError());
-        VR_HIP(hipEventRecord(t->ev_brush, s));
-        t->brush_pending = true;
-        return VR_OK;
-    });
-    if (rc) return rc;
-    if (out_rect) { out_rect[0] = dirty.x0; out_rect[1] = dirty.y0; out_rect[2] = dirty.x1 - dirty.x0; out_rect[3] = dirty.y1 - dirty.y0; }
-    return VR_OK;
+    DirtyRect sr;                                                  // SMOOTH reads the rectangle grown by one texel, clamped to the map
+    return vr_brush_call(t, which, dabs, n, op, out_rect,
+        [&](const DirtyRect& dirty) -> int {
+            sr = dirty;
+            if (op == VR_BRUSH_SMOOTH) sr = dirty_rect(dirty_clip(DirtySpan{ dirty.x0 - 1, dirty.x1 + 1 }, tex.w0), dirty_clip(DirtySpan{ dirty.y0 - 1, dirty.y1 + 1 }, tex.h0));
+            return vr_brush_reserve(t, op == VR_BRUSH_SMOOTH ? (size_t)(sr.x1 - sr.x0) * (size_t)(sr.y1 - sr.y0) : 0);
+        },
+        [&](hipStream_t s, const DirtyRect& dirty, uint32_t nd) -> int {
+            void* mem = const_cast<uint8_t*>(tex.base);
+            const uint8_t* snap = (const uint8_t*)t->d_brush_snap;
+            const dim3 grid = tiles_32x8(dirty);
+            switch (op) {
+            case VR_BRUSH_RAISE: hipLaunchKernelGGL(k_brush<kBrushRaise>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+            case VR_BRUSH_FLATTEN: hipLaunchKernelGGL(k_brush<kBrushFlatten>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+            case VR_BRUSH_SMOOTH:
+                hipLaunchKernelGGL(k_brush_snapshot, tiles_32x8(sr), dim3(256), 0, s, (const uint8_t*)mem, tex.w0, (uint8_t*)t->d_brush_snap, sr);
+                hipLaunchKernelGGL(k_brush<kBrushSmooth>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+            default: hipLaunchKernelGGL(k_brush<kBrushPaint>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+            }
+            return VR_OK;
+        });
 }

@@ -1,10 +1,12 @@
-// Device code the kernels that walk a dab list share (k_brush in vr_brush.hip, k_erode_begin in vr_erode.hip, k_hydro_begin in
-// vr_hydro.hip): a 256-thread workgroup per 32 x 8 tile of the rectangle, one texel per lane, the list walked in chunks of 256 dabs.
+// Device code the kernels that walk a dab list share (k_brush in vr_brush.hip, k_sweep_begin in vr_erode.hip): a 256-thread
+// workgroup per 32 x 8 tile of the rectangle, one texel per lane, the list walked in chunks of 256 dabs.
 #pragma once
 #include "vr_internal.h"
 #include "vr_dirty.h"
 #include "vr_brush.h"
 #include "vr_erode.h"
+
+#include <string.h>
 
 constexpr int kBrushTileW = 32, kBrushTileH = 8, kBrushChunk = 256;
 
@@ -60,4 +62,38 @@ __device__ __forceinline__ float brush_tile_mask(const BrushDab* __restrict__ da
         __syncthreads();                                           // the next chunk overwrites list and wave_total
     }
     return m;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+// A stroke's or an erosion's path behind its entry point's own argument checks: the dabs checked (as a stroke of `op`) and prepared
+// for map `which`; nothing at all for an empty list; then reserve(rectangle) - everything the launches need, before anything is
+// launched - the one wait on the host, the pinned list, and inside vr_derive_level0_write the history capture, the upload,
+// launch(stream, rectangle, dabs) and the event the next call waits for.
+template <class Reserve, class Launch>
+int vr_brush_call(vr_terrain* t, int which, const vr_brush_dab* dabs, uint32_t n, int op, int32_t out_rect[4], Reserve&& reserve, Launch&& launch)
+{
+    { const int rc = vr_brush_check_dabs(dabs, n, op); if (rc) return rc; }
+    const DirtyRect dirty = vr_brush_prepare_dabs(t, which == 0 ? t->height : t->albedo, dabs, n);
+    const std::vector<BrushDab>& prepared = t->brush_prepared;
+    if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
+    if (prepared.empty()) return VR_OK;                            // n == 0, or every dab misses the map: nothing is launched
+
+    VR_HIP(hipSetDevice(t->ctx->device));
+    { const int rc = reserve(dirty); if (rc) return rc; }
+    // the one wait on the host: only where the previous stroke or erosion has not been consumed yet
+    { const int rc = vr_brush_consumed(t); if (rc) return rc; }
+    const uint32_t nd = (uint32_t)prepared.size();
+    memcpy(t->h_brush_dabs, prepared.data(), (size_t)nd * sizeof(BrushDab));
+    const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t s) -> int {
+        { const int hrc = vr_history_capture(t, which, dirty, s); if (hrc) return hrc; }       // history on: the rectangle as it is, first
+        VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)nd * sizeof(BrushDab), hipMemcpyHostToDevice, s));
+        { const int lrc = launch(s, dirty, nd); if (lrc) return lrc; }
+        VR_HIP(hipGetLastError());
+        VR_HIP(hipEventRecord(t->ev_brush, s));
+        t->brush_pending = true;
+        return VR_OK;
+    });
+    if (rc) return rc;
+    if (out_rect) { out_rect[0] = dirty.x0; out_rect[1] = dirty.y0; out_rect[2] = dirty.x1 - dirty.x0; out_rect[3] = dirty.y1 - dirty.y0; }
+    return VR_OK;
 }

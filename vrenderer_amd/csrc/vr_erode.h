@@ -1,4 +1,4 @@
-// Thermal (talus) erosion of level 0 of the heightmap under a brush mask (vr_terrain_erode, vr_erode.hip): the definition, for the
+// Thermal (talus) erosion of level 0 of the heightmap under a brush mask (vr_terrain_erode; its kernels: vr_erode.hip): the definition, for the
 // device and for the host.  Plain C++17, no HIP types: the host compiles this header alone (tests/host/erode_check.cpp).
 //
 // As in vr_brush.h everything a texel sees is fp32, evaluated in the written order with no contraction, and uses +, -, *,
@@ -83,6 +83,23 @@ VR_ERODE_FN uint8_t erode_byte(float h)
     return (uint8_t)floorf(c + 0.5f);
 }
 
+// The mask of every texel of rect = {x0, y0, x1, y1} under the prepared dabs (none empty), into a plane of the rectangle's size: the
+// serial evaluators' first step, vr_hydro.h's as well.
+inline void erode_serial_mask(const BrushDab* dabs, size_t n, const int rect[4], float* mask)
+{
+    const int rw = rect[2] - rect[0];
+    for (int y = rect[1]; y < rect[3]; y++)
+        for (int x = rect[0]; x < rect[2]; x++) {
+            float m = 0.0f;
+            for (size_t d = 0; d < n; d++) {
+                float f;
+                if (x < dabs[d].x0 || x >= dabs[d].x1 || y < dabs[d].y0 || y >= dabs[d].y1 || !brush_weight(dabs[d], x, y, &f)) continue;
+                m = erode_mask_max(m, f, dabs[d].strength);
+            }
+            mask[(size_t)(y - rect[1]) * rw + (x - rect[0])] = m;
+        }
+}
+
 // The whole operation over a host array.  map: w0 x h0 bytes, changed in place; dabs: the prepared dabs that met the map (none
 // empty); rect = {x0, y0, x1, y1}: the hull of their spans; mask, a, b: room for (x1 - x0) * (y1 - y0) floats each.
 inline void erode_serial(uint8_t* map, int w0, int h0, const BrushDab* dabs, size_t n, const int rect[4], int iterations, float talus,
@@ -90,18 +107,9 @@ inline void erode_serial(uint8_t* map, int w0, int h0, const BrushDab* dabs, siz
 {
     const int x0 = rect[0], y0 = rect[1], rw = rect[2] - rect[0], rh = rect[3] - rect[1];
     if (rw <= 0 || rh <= 0) return;
+    erode_serial_mask(dabs, n, rect, mask);
     for (int j = 0; j < rh; j++)
-        for (int i = 0; i < rw; i++) {
-            const int x = x0 + i, y = y0 + j;
-            float m = 0.0f;
-            for (size_t d = 0; d < n; d++) {
-                float f;
-                if (x < dabs[d].x0 || x >= dabs[d].x1 || y < dabs[d].y0 || y >= dabs[d].y1 || !brush_weight(dabs[d], x, y, &f)) continue;
-                m = erode_mask_max(m, f, dabs[d].strength);
-            }
-            mask[(size_t)j * rw + i] = m;
-            a[(size_t)j * rw + i] = (float)map[(size_t)y * w0 + x];
-        }
+        for (int i = 0; i < rw; i++) a[(size_t)j * rw + i] = (float)map[(size_t)(y0 + j) * w0 + (x0 + i)];
     static const int ndx[8] = { -1, 0, 1, -1, 1, -1, 0, 1 }, ndy[8] = { -1, -1, -1, 0, 0, 1, 1, 1 };
     const float T[2] = { talus, erode_diagonal_talus(talus) };
     float* cur = a; float* nxt = b;

@@ -1,39 +1,73 @@
-// vr_terrain_erode: thermal (talus) erosion of level 0 of the heightmap under a brush mask, on the device, followed by the refresh
-// vr_terrain_edit does (vr_derive_level0_write).  The definition, texel by texel, is vr_erode.h; this file holds nothing of it but
-// the order in which the header's functions are called.  DESIGN.md 4u.
+// vr_terrain_erode and vr_terrain_erode_hydraulic: thermal (talus) and hydraulic erosion of level 0 of the heightmap under a brush
+// mask, on the device, followed by the refresh vr_terrain_edit does (vr_derive_level0_write).  The definitions, texel by texel, are
+// vr_erode.h and vr_hydro.h; this file holds nothing of them but the order in which the headers' functions are called.  The kernels
+// are written once, over a model type (the models: 4u, 4v):
 //
-//   k_erode_begin   one 256-thread workgroup per 32 x 8 tile of the rectangle, one texel per lane, the dab list walked the way
-//                   k_brush walks it (vr_brush_dev.h): the mask (fp32) and the state (byte -> fp32) into planes of the rectangle's size
-//   k_erode_steps   the hot path, temporally blocked: a workgroup of 768 lanes loads an 80 x 40 tile of state and mask plus a halo of kErodeK = 8
-//                   texels into LDS (96 x 56 cells), runs up to kErodeK sweeps there - ping-pong in LDS, one barrier per sweep, the
-//                   valid region one ring smaller after each - and stores the tile to the other state plane.  One launch advances
-//                   kErodeK iterations: a call of N iterations is ceil(N / kErodeK) launches, the last with the remainder.  Cells
-//                   beyond the rectangle load as mask 0 / state 0 and are never stored.
-//   k_erode_end     clamp, round and store the byte where the mask is positive
+//   k_sweep_begin   one 256-thread workgroup per 32 x 8 tile of the rectangle, one texel per lane, the dab list walked the way
+//                   k_brush walks it (vr_brush_dev.h): the mask (fp32) and the model's F state fields into planes of the rectangle's size
+//   k_sweep_steps   the hot path, temporally blocked: a workgroup loads a tile of the F fields and the mask plus a halo of K texels
+//                   into LDS (2F + 1 planes: the fields twice, the mask once), runs up to K sweeps there - ping-pong in LDS, one
+//                   barrier per sweep, the valid region one ring smaller after each - and stores the tile's fields to the other set
+//                   of planes.  A lane sweeps a strip: a column of the model's strip height, by the model's strip body.  A call of N
+//                   iterations is ceil(N / K) launches, the last with the remainder.  Cells beyond the rectangle load as zeros
+//                   (mask 0: no edge reaches them) and are never stored.
+//   k_sweep_end     the model's byte where the mask is positive
 //
-// Every cell of a sweep is erode_edge over the previous sweep's values in the header's order, so the bits depend neither on the tile
-// nor on kErodeK.  The kernels are untimed, like the brush's.
+// In memory: one block (vr_terrain::d_erode) of the mask plane and two sets of F planes, `plane` floats apart.  Every cell of a sweep
+// is the model's header functions over the previous sweep's values in the header's order, so the bits depend neither on the tile nor
+// on the sweeps per launch.  The kernels are untimed, like the brush's.
+//
+// A model supplies: kTileW, kTileH, kK, kStrip, kFields, kThreads; Const, the call's constants (trivially copyable); begin(byte,
+// mask, k, f[F]), a lane's initial fields; end(state, plane, at), the byte of texel `at`; and its strip body, which stands in
+// k_sweep_steps' one `if constexpr` over the model, in the kernel's own text (a call costs the thermal kernel registers).
 #include "vr_internal.h"
 #include "vr_dirty.h"
-#include "vr_erode.h"
+#include "vr_hydro.h"
 #include "vr_brush_dev.h"
 
-#include <string.h>
+#include <type_traits>
 
-constexpr int kErodeTileW = 80, kErodeTileH = 40, kErodeK = 8;
-constexpr int kErodeThreads = 768;                               // of k_erode_steps: one strip per lane (672 strips); 256 and 1024 were slower
-constexpr int kErodeStrip = 8;                                   // a lane sweeps a column of this many cells, its 3 x 3 window in registers
-constexpr int kErodeRW = kErodeTileW + 2 * kErodeK, kErodeRH = kErodeTileH + 2 * kErodeK;
-constexpr int kErodeCells = kErodeRW * kErodeRH, kErodeStrips = kErodeRW * (kErodeRH / kErodeStrip);
-// A wave's 64 lanes take 64 consecutive strips: consecutive columns, and - the row length being a multiple of the 32 banks a
-// 4-byte access sees - consecutive banks across the end of a row of strips as well, so every row access is conflict-free.
-static_assert(kErodeRW % 32 == 0 && kErodeRH % kErodeStrip == 0, "k_erode_steps' LDS layout");
-static_assert(kErodeCells * 12 <= 65536 && 2 * kErodeCells * 12 <= 160 * 1024, "state x 2 + mask: two workgroups per CU");
-static_assert(kErodeK >= 4, "a launch advances at least four iterations");
+template <class M> struct Sweep {
+    static constexpr int kRW = M::kTileW + 2 * M::kK, kRH = M::kTileH + 2 * M::kK;                 // the LDS image: the tile and its halo
+    static constexpr int kCells = kRW * kRH, kStrips = kRW * (kRH / M::kStrip);
+    static constexpr int kPlanes = 2 * M::kFields + 1;                                           // in LDS: fields x 2 + mask; in memory: mask + fields x 2
+    static constexpr int kLds = kCells * kPlanes * (int)sizeof(float);
+    // A wave's 64 lanes take 64 consecutive strips: consecutive columns, and - the row length being a multiple of the 32 banks a
+    // 4-byte access sees - consecutive banks across the end of a row of strips as well, so every row access is conflict-free, in
+    // every plane (a plane is a whole number of rows).
+    static_assert(kRW % 32 == 0 && kRH % M::kStrip == 0, "k_sweep_steps' LDS layout");
+    static_assert(M::kThreads % 64 == 0 && M::kThreads <= 1024 && kCells % M::kThreads == 0, "whole waves, a whole number of cells per lane");
+    static_assert(M::kK >= 1 && 2 * M::kK < kRH, "a tile remains inside the halo");
+    static_assert(2 * kLds <= 160 * 1024, "two workgroups per CU");
+};
 
-// `map`: level 0 of the heightmap; `r`: the rectangle, inside the map; `dabs`: n of them, none empty; mask, state: planes of r's size
-__global__ __launch_bounds__(256) void k_erode_begin(const uint8_t* __restrict__ map, int w0, int h0, DirtyRect r, const BrushDab* __restrict__ dabs, uint32_t n,
-                                                     float* __restrict__ mask, float* __restrict__ state)
+struct Thermal {
+    static constexpr int kTileW = 80, kTileH = 40, kK = 8, kFields = 1;
+    static constexpr int kStrip = 8;                               // a lane sweeps a column of this many cells, its 3 x 3 window in registers
+    static constexpr int kThreads = 768;                           // one strip per lane (672 strips); 256 and 1024 were slower
+    struct Const { float talus, talus_d, rate; };                  // talus_d: the diagonals' talus
+    static __device__ __forceinline__ void begin(float byte, float, const Const&, float (&f)[1]) { f[0] = byte; }
+    static __device__ __forceinline__ uint8_t end(const float* __restrict__ st, size_t, size_t at) { return erode_byte(st[at]); }
+};
+static_assert(Sweep<Thermal>::kLds == 64512 && Sweep<Thermal>::kLds <= 65536, "state x 2 + mask of 96 x 56 cells: two workgroups per CU");
+static_assert(Thermal::kK >= 4, "a launch advances at least four iterations");
+
+struct Hydraulic {
+    static constexpr int kTileW = 56, kTileH = 36, kK = 4, kFields = 3;                           // the fields: h, d, s
+    static constexpr int kStrip = 4;                               // a lane sweeps a column of this many cells, the column's three rows in registers
+    static constexpr int kThreads = 704;                           // one strip per lane, 11 waves: a wave takes one whole row of the image
+    using Const = HydroConst;
+    static __device__ __forceinline__ void begin(float byte, float m, const Const& k, float (&f)[3]) { f[0] = byte; f[1] = hydro_rain(k.rain, m); f[2] = 0.0f; }
+    static __device__ __forceinline__ uint8_t end(const float* __restrict__ st, size_t plane, size_t at) { return hydro_byte(st[at], st[2 * plane + at]); }
+};
+static_assert(Hydraulic::kThreads == Sweep<Hydraulic>::kStrips, "one strip per lane");
+static_assert(Sweep<Hydraulic>::kLds == 78848, "seven planes of 64 x 44 cells: two workgroups per CU");
+
+// `map`: level 0 of the heightmap; `r`: the rectangle, inside the map; `dabs`: n of them, none empty; mask: a plane of r's size;
+// state: F of them, `plane` floats apart
+template <class M>
+__global__ __launch_bounds__(256) void k_sweep_begin(const uint8_t* __restrict__ map, int w0, int h0, DirtyRect r, const BrushDab* __restrict__ dabs, uint32_t n,
+                                                     typename M::Const k, float* __restrict__ mask, float* __restrict__ state, size_t plane)
 {
     __shared__ uint16_t list[kBrushChunk];
     __shared__ uint32_t wave_total[4];
@@ -48,112 +82,182 @@ __global__ __launch_bounds__(256) void k_erode_begin(const uint8_t* __restrict__
     const float m = brush_tile_mask(dabs, n, tx0, ty0, tx1, ty1, x, y, inside, list, wave_total);
     if (!inside) return;
     const size_t at = (size_t)(y - r.y0) * (size_t)(r.x1 - r.x0) + (size_t)(x - r.x0);
+    float f[M::kFields];
+    M::begin(h, m, k, f);
     mask[at] = m;
-    state[at] = h;
+#pragma unroll
+    for (int i = 0; i < M::kFields; i++) state[(size_t)i * plane + at] = f[i];
 }
 
-// src, dst, mask: rw x rh planes; steps: 1 .. kErodeK sweeps; talus_d: the diagonals' talus
-__global__ __launch_bounds__(kErodeThreads) void k_erode_steps(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ mask, int rw, int rh,
-                                                     int steps, float talus, float talus_d, float rate)
+// src, dst: F planes of rw x rh cells each, `plane` floats apart; mask: one; steps: 1 .. K sweeps
+template <class M>
+__global__ __launch_bounds__(M::kThreads) void k_sweep_steps(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ mask, size_t plane,
+                                                             int rw, int rh, int steps, typename M::Const k)
 {
-    __shared__ float s_m[kErodeCells];
-    __shared__ float s_h[2][kErodeCells];
+    using S = Sweep<M>;
+    constexpr int F = M::kFields, kRW = S::kRW, kRH = S::kRH;
+    __shared__ float s_m[S::kCells];
+    __shared__ float s_f[2][F * S::kCells];                       // a set: the F planes one after the other
     const int tid = (int)threadIdx.x;
-    const int ox = (int)blockIdx.x * kErodeTileW - kErodeK, oy = (int)blockIdx.y * kErodeTileH - kErodeK;     // the LDS image's origin in the plane
-    for (int i = tid; i < kErodeCells; i += kErodeThreads) {
-        const int ly = i / kErodeRW, lx = i - ly * kErodeRW;
+    const int ox = (int)blockIdx.x * M::kTileW - M::kK, oy = (int)blockIdx.y * M::kTileH - M::kK;   // the LDS image's origin in the plane
+    for (int i = tid; i < S::kCells; i += M::kThreads) {
+        const int ly = i / S::kRW, lx = i - ly * S::kRW;
         const int x = ox + lx, y = oy + ly;
         const bool in = x >= 0 && x < rw && y >= 0 && y < rh;
         const size_t at = (size_t)brush_clampi(y, 0, rh - 1) * (size_t)rw + (size_t)brush_clampi(x, 0, rw - 1);
-        const float h = src[at], m = mask[at];
-        s_h[0][i] = in ? h : 0.0f;
+        float v[F];
+#pragma unroll
+        for (int f = 0; f < F; f++) v[f] = src[(size_t)f * plane + at];
+        const float m = mask[at];
+#pragma unroll
+        for (int f = 0; f < F; f++) s_f[0][f * S::kCells + i] = in ? v[f] : 0.0f;
         s_m[i] = in ? m : 0.0f;
     }
-    steps = brush_clampi(steps, 0, kErodeK);                       // (a kernel argument: uniform) more sweeps than the halo holds would read stale rings
+    steps = brush_clampi(steps, 0, M::kK);                         // (a kernel argument: uniform) more sweeps than the halo holds would read stale rings
     __syncthreads();
     int cur = 0;
     // Sweep s leaves the cells at least s rings inside the image valid; it reads ring s - 1 and inwards of the sweep before.
     for (int s = 1; s <= steps; s++) {
-        const float* __restrict__ hin = s_h[cur];
-        float* __restrict__ hout = s_h[cur ^ 1];
-        for (int idx = tid; idx < kErodeStrips; idx += kErodeThreads) {
-            const int sy = idx / kErodeRW, lx = idx - sy * kErodeRW, y0 = sy * kErodeStrip;
-            if (lx < s || lx >= kErodeRW - s || y0 + kErodeStrip <= s || y0 >= kErodeRH - s) continue;      // nothing of this strip is valid after the sweep
-            const int xl = lx - 1, xr = lx + 1;                    // 1 <= s <= lx < kErodeRW - s: both inside the row
-            // rows a (above), c (the cell's) and b (below), three columns each; a row index is clamped before it addresses LDS
-            const int ra = brush_clampi(y0 - 1, 0, kErodeRH - 1) * kErodeRW, rc = y0 * kErodeRW;
-            float ha0 = hin[ra + xl], ha1 = hin[ra + lx], ha2 = hin[ra + xr], ma0 = s_m[ra + xl], ma1 = s_m[ra + lx], ma2 = s_m[ra + xr];
-            float hc0 = hin[rc + xl], hc1 = hin[rc + lx], hc2 = hin[rc + xr], mc0 = s_m[rc + xl], mc1 = s_m[rc + lx], mc2 = s_m[rc + xr];
+        const float* __restrict__ hin = s_f[cur];
+        float* __restrict__ hout = s_f[cur ^ 1];
+        for (int idx = tid; idx < S::kStrips; idx += M::kThreads) {
+            const int sy = idx / S::kRW, lx = idx - sy * S::kRW, y0 = sy * M::kStrip;
+            if (lx < s || lx >= S::kRW - s || y0 + M::kStrip <= s || y0 >= S::kRH - s) continue;    // nothing of this strip is valid after the sweep
+            // The model's strip body: sweep s of the strip whose column is lx and whose first row is y0, from hin to hout.  It stands
+            // here, not behind a call: routed through a function of the model, forced inline or not, the unchanged thermal body took
+            // 76 - 79 VGPRs instead of 74.
+            if constexpr (std::is_same<M, Thermal>::value) {
+                const float talus = k.talus, talus_d = k.talus_d, rate = k.rate;
+                const int xl = lx - 1, xr = lx + 1;                        // 1 <= s <= lx < kRW - s: both inside the row
+                // rows a (above), c (the cell's) and b (below), three columns each; a row index is clamped before it addresses LDS
+                const int ra = brush_clampi(y0 - 1, 0, kRH - 1) * kRW, rc = y0 * kRW;
+                float ha0 = hin[ra + xl], ha1 = hin[ra + lx], ha2 = hin[ra + xr], ma0 = s_m[ra + xl], ma1 = s_m[ra + lx], ma2 = s_m[ra + xr];
+                float hc0 = hin[rc + xl], hc1 = hin[rc + lx], hc2 = hin[rc + xr], mc0 = s_m[rc + xl], mc1 = s_m[rc + lx], mc2 = s_m[rc + xr];
 #pragma unroll
-            for (int r = 0; r < kErodeStrip; r++) {
-                const int ly = y0 + r;
-                const int rb = brush_clampi(ly + 1, 0, kErodeRH - 1) * kErodeRW;
-                const float hb0 = hin[rb + xl], hb1 = hin[rb + lx], hb2 = hin[rb + xr], mb0 = s_m[rb + xl], mb1 = s_m[rb + lx], mb2 = s_m[rb + xr];
-                if (ly >= s && ly < kErodeRH - s) {
-                    float acc = 0.0f;
-                    acc = erode_edge(acc, hc1, ha0, mc1, ma0, talus_d, rate);
-                    acc = erode_edge(acc, hc1, ha1, mc1, ma1, talus, rate);
-                    acc = erode_edge(acc, hc1, ha2, mc1, ma2, talus_d, rate);
-                    acc = erode_edge(acc, hc1, hc0, mc1, mc0, talus, rate);
-                    acc = erode_edge(acc, hc1, hc2, mc1, mc2, talus, rate);
-                    acc = erode_edge(acc, hc1, hb0, mc1, mb0, talus_d, rate);
-                    acc = erode_edge(acc, hc1, hb1, mc1, mb1, talus, rate);
-                    acc = erode_edge(acc, hc1, hb2, mc1, mb2, talus_d, rate);
-                    hout[ly * kErodeRW + lx] = hc1 + acc;
+                for (int r = 0; r < M::kStrip; r++) {
+                    const int ly = y0 + r;
+                    const int rb = brush_clampi(ly + 1, 0, kRH - 1) * kRW;
+                    const float hb0 = hin[rb + xl], hb1 = hin[rb + lx], hb2 = hin[rb + xr], mb0 = s_m[rb + xl], mb1 = s_m[rb + lx], mb2 = s_m[rb + xr];
+                    if (ly >= s && ly < kRH - s) {
+                        float acc = 0.0f;
+                        acc = erode_edge(acc, hc1, ha0, mc1, ma0, talus_d, rate);
+                        acc = erode_edge(acc, hc1, ha1, mc1, ma1, talus, rate);
+                        acc = erode_edge(acc, hc1, ha2, mc1, ma2, talus_d, rate);
+                        acc = erode_edge(acc, hc1, hc0, mc1, mc0, talus, rate);
+                        acc = erode_edge(acc, hc1, hc2, mc1, mc2, talus, rate);
+                        acc = erode_edge(acc, hc1, hb0, mc1, mb0, talus_d, rate);
+                        acc = erode_edge(acc, hc1, hb1, mc1, mb1, talus, rate);
+                        acc = erode_edge(acc, hc1, hb2, mc1, mb2, talus_d, rate);
+                        hout[ly * kRW + lx] = hc1 + acc;
+                    }
+                    ha0 = hc0; ha1 = hc1; ha2 = hc2; ma0 = mc0; ma1 = mc1; ma2 = mc2;
+                    hc0 = hb0; hc1 = hb1; hc2 = hb2; mc0 = mb0; mc1 = mb1; mc2 = mb2;
                 }
-                ha0 = hc0; ha1 = hc1; ha2 = hc2; ma0 = mc0; ma1 = mc1; ma2 = mc2;
-                hc0 = hb0; hc1 = hb1; hc2 = hb2; mc0 = mb0; mc1 = mb1; mc2 = mb2;
+            } else {
+                static_assert(std::is_same<M, Thermal>::value || std::is_same<M, Hydraulic>::value, "a new model brings its strip body here");
+                const float* __restrict__ din = hin + S::kCells;
+                const float* __restrict__ sdin = hin + 2 * S::kCells;
+                float* __restrict__ dout = hout + S::kCells;
+                float* __restrict__ sout = hout + 2 * S::kCells;
+                const int xl = lx - 1, xr = lx + 1;                        // 1 <= s <= lx < kRW - s: both inside the row
+                // the column's rows a (above) and c (the cell's); a row index is clamped before it addresses LDS
+                const int ra = brush_clampi(y0 - 1, 0, kRH - 1) * kRW + lx, rc = y0 * kRW + lx;
+                float ha = hin[ra], da = din[ra], sa = sdin[ra], ma = s_m[ra];
+                float hc = hin[rc], dc = din[rc], sc = sdin[rc], mc = s_m[rc];
+#pragma unroll
+                for (int r = 0; r < M::kStrip; r++) {
+                    const int ly = y0 + r, row = ly * kRW;
+                    const int rb = brush_clampi(ly + 1, 0, kRH - 1) * kRW + lx;
+                    const float hb = hin[rb], db = din[rb], sb = sdin[rb], mb = s_m[rb];
+                    if (ly >= s && ly < kRH - s) {
+                        HydroAcc acc = { 0.0f, 0.0f, 0.0f };
+                        hydro_edge(acc, hc, dc, sc, mc, ha, da, sa, ma, k.flow);                                                                    // (0, -1)
+                        hydro_edge(acc, hc, dc, sc, mc, hin[row + xl], din[row + xl], sdin[row + xl], s_m[row + xl], k.flow);                        // (-1, 0)
+                        hydro_edge(acc, hc, dc, sc, mc, hin[row + xr], din[row + xr], sdin[row + xr], s_m[row + xr], k.flow);                        // (1, 0)
+                        hydro_edge(acc, hc, dc, sc, mc, hb, db, sb, mb, k.flow);                                                                    // (0, 1)
+                        float h1, d1, s1;
+                        hydro_cell(hc, dc, sc, mc, acc, k, &h1, &d1, &s1);
+                        hout[row + lx] = h1; dout[row + lx] = d1; sout[row + lx] = s1;
+                    }
+                    ha = hc; da = dc; sa = sc; ma = mc;
+                    hc = hb; dc = db; sc = sb; mc = mb;
+                }
             }
         }
         __syncthreads();                                           // every lane arrives: the loop bounds are uniform
         cur ^= 1;
     }
-    const float* __restrict__ hfin = s_h[cur];
-    for (int i = tid; i < kErodeTileW * kErodeTileH; i += kErodeThreads) {
-        const int ty = i / kErodeTileW, tx = i - ty * kErodeTileW;
-        const int x = (int)blockIdx.x * kErodeTileW + tx, y = (int)blockIdx.y * kErodeTileH + ty;
-        if (x < rw && y < rh) dst[(size_t)y * (size_t)rw + (size_t)x] = hfin[(ty + kErodeK) * kErodeRW + (tx + kErodeK)];
+#pragma unroll
+    for (int f = 0; f < F; f++) {
+        const float* __restrict__ fin = s_f[cur] + f * S::kCells;
+        for (int i = tid; i < M::kTileW * M::kTileH; i += M::kThreads) {
+            const int ty = i / M::kTileW, tx = i - ty * M::kTileW;
+            const int x = (int)blockIdx.x * M::kTileW + tx, y = (int)blockIdx.y * M::kTileH + ty;
+            if (x < rw && y < rh) dst[(size_t)f * plane + (size_t)y * (size_t)rw + (size_t)x] = fin[(ty + M::kK) * S::kRW + (tx + M::kK)];
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void k_erode_end(uint8_t* __restrict__ map, int w0, DirtyRect r, const float* __restrict__ mask, const float* __restrict__ state)
+template <class M>
+__global__ __launch_bounds__(256) void k_sweep_end(uint8_t* __restrict__ map, int w0, DirtyRect r, const float* __restrict__ mask, const float* __restrict__ state, size_t plane)
 {
     const int x = r.x0 + (int)blockIdx.x * kBrushTileW + ((int)threadIdx.x & 31), y = r.y0 + (int)blockIdx.y * kBrushTileH + ((int)threadIdx.x >> 5);
     if (x >= r.x1 || y >= r.y1) return;
     const size_t at = (size_t)(y - r.y0) * (size_t)(r.x1 - r.x0) + (size_t)(x - r.x0);
-    if (mask[at] > 0.0f) map[(size_t)y * (size_t)w0 + (size_t)x] = erode_byte(state[at]);
+    if (mask[at] > 0.0f) map[(size_t)y * (size_t)w0 + (size_t)x] = M::end(state, plane, at);
 }
 
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-static bool host_finite(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
+// sweeps per hydraulic step launch: the build's K unless the measurement tool asked for fewer (the bytes are the same)
+static int g_hydro_sweeps = Hydraulic::kK;
 
-extern "C" VR_API int vr_debug_erode_config(int32_t out[4])
+template <class M> static int sweep_config(int32_t out[4])
 {
     VR_REQUIRE(out != nullptr, "out is NULL");
-    out[0] = kErodeTileW; out[1] = kErodeTileH; out[2] = kErodeK; out[3] = 0;
+    out[0] = M::kTileW; out[1] = M::kTileH; out[2] = M::kK; out[3] = 0;
+    return VR_OK;
+}
+extern "C" VR_API int vr_debug_erode_config(int32_t out[4]) { return sweep_config<Thermal>(out); }
+extern "C" VR_API int vr_debug_hydro_config(int32_t out[4]) { return sweep_config<Hydraulic>(out); }
+
+extern "C" VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps)
+{
+    VR_REQUIRE(sweeps >= 0 && sweeps <= Hydraulic::kK, "sweeps outside 0 .. the build's sweeps per launch");
+    g_hydro_sweeps = sweeps ? sweeps : Hydraulic::kK;
     return VR_OK;
 }
 
-// The three planes hold `plane_bytes` each, before anything is launched: all three or none (a refusal leaves the terrain as it was).
-static int erode_reserve(vr_terrain* t, size_t plane_bytes)
+// One call of the model M behind its entry point's own checks (vr_brush_call, vr_brush_dev.h): the block's 2F + 1 planes of the
+// rectangle reserved, then begin, ceil(iterations / per_launch) step launches and end.
+template <class M>
+static int sweep_call(vr_terrain* t, const char* who, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4], int iterations, int per_launch, const typename M::Const& k)
 {
-    if (plane_bytes <= t->erode_plane_bytes) return VR_OK;
-    size_t want = t->erode_plane_bytes ? t->erode_plane_bytes * 2 : (size_t)1 << 16;
-    while (want < plane_bytes) want *= 2;
-    const auto idle = [t]() -> int { return vr_brush_consumed(t); };
-    void** const slots[3] = { (void**)&t->d_erode_mask, (void**)&t->d_erode_state[0], (void**)&t->d_erode_state[1] };
-    const auto grow = [&](size_t bytes) -> int {
-        const size_t sizes[3] = { bytes, bytes, bytes };
-        const int rc = vr_grow_group(slots, sizes, idle);
-        if (!rc) t->erode_plane_bytes = bytes;
-        return rc;
-    };
-    int rc = grow(want);
-    if (rc == VR_ERR_OUT_OF_MEMORY && want > plane_bytes) rc = grow(plane_bytes);
-    if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain erode: 3 x %zu bytes for the mask and state planes", plane_bytes);
-    return rc;
+    size_t plane = 0;                                              // floats from one plane to the next: the rectangle's, rounded up to 256 bytes
+    return vr_brush_call(t, 0, dabs, n, VR_BRUSH_FLATTEN, out_rect,                              // strength is an opacity
+        [&](const DirtyRect& r) -> int {
+            plane = ((size_t)(r.x1 - r.x0) * (size_t)(r.y1 - r.y0) + 63) & ~(size_t)63;
+            { const int rc = vr_brush_reserve(t, 0); if (rc) return rc; }
+            const int rc = vr_brush_grow(t, &t->d_erode, &t->erode_bytes, plane * sizeof(float) * Sweep<M>::kPlanes);
+            if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain %s: %d x %zu bytes for the mask and state planes", who, Sweep<M>::kPlanes, plane * sizeof(float));
+            return rc;
+        },
+        [&](hipStream_t s, const DirtyRect& r, uint32_t nd) -> int {
+            const int rw = r.x1 - r.x0, rh = r.y1 - r.y0;
+            // the block: the mask, then two sets of F planes
+            float* const d_mask = (float*)t->d_erode;
+            float* const d_set[2] = { d_mask + plane, d_mask + (1 + M::kFields) * plane };
+            hipLaunchKernelGGL(k_sweep_begin<M>, tiles_32x8(r), dim3(256), 0, s, (const uint8_t*)t->height.base, t->height.w0, t->height.h0, r, t->d_brush_dabs, nd, k, d_mask, d_set[0], plane);
+            const dim3 grid((unsigned)((rw + M::kTileW - 1) / M::kTileW), (unsigned)((rh + M::kTileH - 1) / M::kTileH));
+            int cur = 0;
+            for (int done = 0; done < iterations; done += per_launch, cur ^= 1) {
+                const int steps = iterations - done < per_launch ? iterations - done : per_launch;
+                hipLaunchKernelGGL(k_sweep_steps<M>, grid, dim3(M::kThreads), 0, s, (const float*)d_set[cur], d_set[cur ^ 1], (const float*)d_mask, plane, rw, rh, steps, k);
+            }
+            hipLaunchKernelGGL(k_sweep_end<M>, tiles_32x8(r), dim3(256), 0, s, const_cast<uint8_t*>(t->height.base), t->height.w0, r, (const float*)d_mask, (const float*)d_set[cur], plane);
+            return VR_OK;
+        });
 }
 
 extern "C" VR_API int vr_terrain_erode(vr_terrain* t, const vr_erode_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4])
@@ -170,45 +274,29 @@ extern "C" VR_API int vr_terrain_erode(vr_terrain* t, const vr_erode_params* p, 
     VR_REQUIRE(p->talus >= 0.0f && p->talus <= 255.0f, "talus outside [0, 255]");
     VR_REQUIRE(p->rate > 0.0f && p->rate <= 0.125f, "rate outside (0, 0.125]");
     for (int i = 0; i < 5; i++) VR_REQUIRE(p->reserved[i] == 0, "reserved must be zero");
-    { const int rc = vr_brush_check_dabs(dabs, n, VR_BRUSH_FLATTEN); if (rc) return rc; }        // strength is an opacity
-    const DevTex& tex = t->height;
-    const DirtyRect dirty = vr_brush_prepare_dabs(t, tex, dabs, n);
-    const std::vector<BrushDab>& prepared = t->brush_prepared;
-    if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
-    if (prepared.empty()) return VR_OK;                            // n == 0, or every dab misses the map: nothing is launched
+    const Thermal::Const k = { p->talus, erode_diagonal_talus(p->talus), p->rate };
+    return sweep_call<Thermal>(t, "erode", dabs, n, out_rect, p->iterations, Thermal::kK, k);
+}
 
-    vr_context* ctx = t->ctx;
-    VR_HIP(hipSetDevice(ctx->device));
-    const int rw = dirty.x1 - dirty.x0, rh = dirty.y1 - dirty.y0;
-    // everything is reserved before anything is launched
-    { const int rc = vr_brush_reserve(t, 0); if (rc) return rc; }
-    { const int rc = erode_reserve(t, (size_t)rw * (size_t)rh * sizeof(float)); if (rc) return rc; }
-    // the one wait on the host: only where the previous stroke or erode has not been consumed yet
-    { const int rc = vr_brush_consumed(t); if (rc) return rc; }
-    const uint32_t nd = (uint32_t)prepared.size();
-    memcpy(t->h_brush_dabs, prepared.data(), (size_t)nd * sizeof(BrushDab));
-
-    const int iterations = p->iterations;
-    const float talus = p->talus, talus_d = erode_diagonal_talus(p->talus), rate = p->rate;
-    uint8_t* mem = const_cast<uint8_t*>(tex.base);
-    const int rc = vr_derive_level0_write(t, 0, dirty, [&](hipStream_t s) -> int {
-        { const int hrc = vr_history_capture(t, 0, dirty, s); if (hrc) return hrc; }           // history on: the rectangle as it is, first
-        VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)nd * sizeof(BrushDab), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_erode_begin, tiles_32x8(dirty), dim3(256), 0, s, (const uint8_t*)mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, t->d_erode_mask, t->d_erode_state[0]);
-        const dim3 grid((unsigned)((rw + kErodeTileW - 1) / kErodeTileW), (unsigned)((rh + kErodeTileH - 1) / kErodeTileH));
-        int cur = 0;
-        for (int done = 0; done < iterations; done += kErodeK, cur ^= 1) {
-            const int steps = iterations - done < kErodeK ? iterations - done : kErodeK;
-            hipLaunchKernelGGL(k_erode_steps, grid, dim3(kErodeThreads), 0, s, (const float*)t->d_erode_state[cur], t->d_erode_state[cur ^ 1], (const float*)t->d_erode_mask, rw, rh,
-                               steps, talus, talus_d, rate);
-        }
-        hipLaunchKernelGGL(k_erode_end, tiles_32x8(dirty), dim3(256), 0, s, mem, tex.w0, dirty, (const float*)t->d_erode_mask, (const float*)t->d_erode_state[cur]);
-        VR_HIP(hipGetLastError());
-        VR_HIP(hipEventRecord(t->ev_brush, s));
-        t->brush_pending = true;
-        return VR_OK;
-    });
-    if (rc) return rc;
-    if (out_rect) { out_rect[0] = dirty.x0; out_rect[1] = dirty.y0; out_rect[2] = dirty.x1 - dirty.x0; out_rect[3] = dirty.y1 - dirty.y0; }
-    return VR_OK;
+extern "C" VR_API int vr_terrain_erode_hydraulic(vr_terrain* t, const vr_hydro_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4])
+{
+    static_assert(sizeof(vr_hydro_params) == 32, "vr_hydro_params layout");
+    static_assert(VR_HYDRO_MAX_ITERATIONS == kHydroMaxIterations, "vr_hydro.h's limit");
+    // the argument checks come before any use of the device (and leave the terrain alone)
+    VR_REQUIRE(t != nullptr, "terrain is NULL");
+    VR_REQUIRE(p != nullptr, "params is NULL");
+    VR_REQUIRE(dabs != nullptr || n == 0, "dabs is NULL with n > 0");
+    VR_REQUIRE(n <= VR_MAX_BRUSH_DABS, "more than VR_MAX_BRUSH_DABS dabs");
+    VR_REQUIRE(p->iterations >= 1 && p->iterations <= VR_HYDRO_MAX_ITERATIONS, "iterations outside 1 .. VR_HYDRO_MAX_ITERATIONS");
+    VR_REQUIRE(host_finite(p->rain) && host_finite(p->flow) && host_finite(p->capacity) && host_finite(p->dissolve) && host_finite(p->deposit) && host_finite(p->evaporation),
+               "a parameter is NaN or infinite");
+    VR_REQUIRE(p->rain >= 0.0f && p->rain <= 16.0f, "rain outside [0, 16]");
+    VR_REQUIRE(p->flow > 0.0f && p->flow <= 1.0f, "flow outside (0, 1]");
+    VR_REQUIRE(p->capacity >= 0.0f && p->capacity <= 64.0f, "capacity outside [0, 64]");
+    VR_REQUIRE(p->dissolve >= 0.0f && p->dissolve <= 1.0f, "dissolve outside [0, 1]");
+    VR_REQUIRE(p->deposit >= 0.0f && p->deposit <= 1.0f, "deposit outside [0, 1]");
+    VR_REQUIRE(p->evaporation >= 0.0f && p->evaporation <= 1.0f, "evaporation outside [0, 1]");
+    VR_REQUIRE(p->reserved == 0, "reserved must be zero");
+    const HydroConst k = { p->rain, p->flow, p->capacity, p->dissolve, p->deposit, hydro_keep(p->evaporation) };
+    return sweep_call<Hydraulic>(t, "erode_hydraulic", dabs, n, out_rect, p->iterations, g_hydro_sweeps, k);
 }

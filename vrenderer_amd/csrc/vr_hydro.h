@@ -1,4 +1,4 @@
-// Hydraulic erosion of level 0 of the heightmap under a brush mask (vr_terrain_erode_hydraulic, vr_hydro.hip): the definition, for
+// Hydraulic erosion of level 0 of the heightmap under a brush mask (vr_terrain_erode_hydraulic; its kernels: vr_erode.hip): the definition, for
 // the device and for the host.  Plain C++17, no HIP types: the host compiles this header alone (tests/host/hydro_check.cpp).
 //
 // As in vr_erode.h everything a texel sees is fp32, evaluated in the written order with no contraction, and uses +, -, *,
@@ -153,19 +153,12 @@ inline bool hydro_serial(uint8_t* map, int w0, int h0, const BrushDab* dabs, siz
     const int x0 = rect[0], y0 = rect[1], rw = rect[2] - rect[0], rh = rect[3] - rect[1];
     if (rw <= 0 || rh <= 0) return true;
     const size_t cells = (size_t)rw * (size_t)rh;
+    erode_serial_mask(dabs, n, rect, mask);
     for (int j = 0; j < rh; j++)
         for (int i = 0; i < rw; i++) {
-            const int x = x0 + i, y = y0 + j;
-            float m = 0.0f;
-            for (size_t d = 0; d < n; d++) {
-                float f;
-                if (x < dabs[d].x0 || x >= dabs[d].x1 || y < dabs[d].y0 || y >= dabs[d].y1 || !brush_weight(dabs[d], x, y, &f)) continue;
-                m = erode_mask_max(m, f, dabs[d].strength);
-            }
             const size_t at = (size_t)j * rw + i;
-            mask[at] = m;
-            a[at] = (float)map[(size_t)y * w0 + x];
-            a[cells + at] = hydro_rain(k.rain, m);
+            a[at] = (float)map[(size_t)(y0 + j) * w0 + (x0 + i)];
+            a[cells + at] = hydro_rain(k.rain, mask[at]);
             a[2 * cells + at] = 0.0f;
         }
     static const int ndx[4] = { 0, -1, 1, 0 }, ndy[4] = { -1, 0, 0, 1 };

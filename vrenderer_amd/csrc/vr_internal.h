@@ -32,6 +32,7 @@ void vr_set_error(const char* fmt, ...);
     } while (0)
 #define VR_REQUIRE(cond, msg)                                                         \
     do { if (!(cond)) { vr_set_error("%s:%d: %s", __FILE__, __LINE__, msg); return VR_ERR_INVALID_ARGUMENT; } } while (0)
+inline bool host_finite(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }    // of an argument: neither a NaN nor an infinity
 
 // ---- device buffers that grow (vr_devbuf.h) ----------------------------------------
 // Every buffer that a larger one replaces while the library runs goes through these: the new block is allocated first, `quiesce`
@@ -397,13 +398,11 @@ struct vr_terrain {
     BrushDab* h_brush_dabs = nullptr; BrushDab* d_brush_dabs = nullptr;
     void* d_brush_snap = nullptr; size_t brush_snap_bytes = 0;
     hipEvent_t ev_brush = nullptr; bool brush_pending = false;
-    // Erosion (vr_erode.hip): the mask and the two state planes, fp32, of the largest rectangle so far (erode_plane_bytes each).
-    // Their one reader is the erosion's kernels, which run in front of the same event: an erode shares the brush's dab buffers
-    // and its consumed-event protocol, so strokes and erodes of one terrain order against each other whichever stream they ran on.
-    float* d_erode_mask = nullptr; float* d_erode_state[2] = { nullptr, nullptr }; size_t erode_plane_bytes = 0;
-    // Hydraulic erosion (vr_hydro.hip): one block of seven fp32 planes - the mask and two sets of terrain, water and sediment - of the
-    // largest rectangle so far (hydro_plane_bytes each), under the same event and protocol as the planes above.
-    float* d_hydro = nullptr; size_t hydro_plane_bytes = 0;
+    // Erosion, thermal and hydraulic (vr_erode.hip): one block of fp32 planes - the mask and two sets of the model's state fields,
+    // three planes or seven - of the largest call so far.  Its one reader is the erosion's kernels, which run in front of the same
+    // event: an erosion shares the brush's dab buffers and its consumed-event protocol, so strokes and erosions of one terrain
+    // order against each other, and one erosion against the next one's growth of the block, whichever stream they ran on.
+    void* d_erode = nullptr; size_t erode_bytes = 0;
     // History (vr_history.hip): the journal's bookkeeping (vr_history.h) over a table of kHistoryMaxRecords records and one device
     // arena, both from vr_terrain_history_enable on, and the event behind the latest journal kernel with the stream it ran on - a
     // journal kernel on another stream waits for it (the rule of ev_pyramid / pyramid_stream).
@@ -418,8 +417,11 @@ void vr_brush_release(vr_terrain* t);      // the brush's and the erosions' memo
 // What vr_terrain_brush, vr_terrain_erode and vr_terrain_erode_hydraulic share (vr_brush.hip).  check_dabs: the dab refusals of a stroke of `op` (an opacity
 // op for the erosion).  prepare_dabs: the dabs that meet the map `tex`, in order, into t->brush_prepared; returns the hull of their
 // spans.  reserve: the event, the pinned and the device dab list and `snap_bytes` of snapshot, before anything is launched.
-// consumed: the one wait on the host - the kernels in front of the latest record of ev_brush have passed.
+// grow: one of the buffers read in front of ev_brush to `bytes`.  consumed: the one wait on the host - the kernels in front of
+// the latest record of ev_brush have passed.  (vr_brush_call, the whole path from the dab checks to the recorded event around the
+// caller's reserve step and launches, is a template: vr_brush_dev.h.)
 struct DirtyRect;
+int vr_brush_grow(vr_terrain* t, void** ptr, size_t* capacity, size_t bytes);
 int vr_brush_check_dabs(const vr_brush_dab* dabs, uint32_t n, int op);
 DirtyRect vr_brush_prepare_dabs(vr_terrain* t, const DevTex& tex, const vr_brush_dab* dabs, uint32_t n);
 int vr_brush_reserve(vr_terrain* t, size_t snap_bytes);

@@ -315,7 +315,6 @@ __global__ __launch_bounds__(256) void k_query_rays(DevTex hm, QueryArgs a, PyrD
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-static bool host_finite(float x) { return x == x && fabsf(x) <= 3.402823466e38f; }
 
 static int grid_for(uint32_t n)
 {

@@ -774,6 +774,6 @@ extern "C" VR_API int vr_terrain_memory_bytes(const vr_terrain* t, uint64_t out[
         const uint64_t surfaces = (uint64_t)(t->surfaces_per_side * t->surfaces_per_side);
         heights = nodes * surfaces * sizeof(float2) + (t->d_minmax ? nodes * surfaces * sizeof(uchar2) : 0);
     }
-    out[0] = t->bytes_textures + t->pyramid_bytes; out[1] = t->bytes_scratch + tiles + t->query_stage_bytes + t->brush_snap_bytes + 3 * (uint64_t)t->erode_plane_bytes + 7 * (uint64_t)t->hydro_plane_bytes + (t->d_brush_dabs ? (uint64_t)VR_MAX_BRUSH_DABS * sizeof(BrushDab) : 0) + t->history.budget; out[2] = heights; out[3] = out[0] + out[1] + out[2];
+    out[0] = t->bytes_textures + t->pyramid_bytes; out[1] = t->bytes_scratch + tiles + t->query_stage_bytes + t->brush_snap_bytes + t->erode_bytes + (t->d_brush_dabs ? (uint64_t)VR_MAX_BRUSH_DABS * sizeof(BrushDab) : 0) + t->history.budget; out[2] = heights; out[3] = out[0] + out[1] + out[2];
     return VR_OK;
 }
