@@ -320,6 +320,15 @@ typedef struct vr_erode_params { int32_t iterations; float talus; float rate; in
 VR_API int vr_terrain_erode(vr_terrain* t, const vr_erode_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
 /* test helper: {tile width, tile height, sweeps per launch, 0} of this build's erosion kernel */
 VR_API int vr_debug_erode_config(int32_t out[4]);
+/* test helper: the fp32 planes the last vr_terrain_erode or vr_terrain_erode_hydraulic of this terrain left on the device, before
+ * the final rounding to bytes.  out_rect receives the call's {x, y, w, h}, *out_fields its model's state fields (1: h; 3: h, d, s),
+ * and `out` (1 + fields) planes of w * h floats each, row-major: the mask, then the fields.  The copy runs on the context's stream
+ * behind the erosion, on whichever stream that ran, and the entry returns when it has completed.  out == NULL with
+ * capacity_floats == 0 is a size query: the rectangle and the field count only.  A refused erosion call leaves the record of the
+ * call before it; a call that launched nothing (n == 0, or dabs that all miss the map) clears it.  With no record: VR_OK,
+ * *out_fields == 0, a zero rectangle, `out` untouched.  VR_ERR_INVALID_ARGUMENT, with nothing written: NULL t, out_rect or
+ * out_fields; NULL out with a capacity; a capacity below (1 + fields) * w * h. */
+VR_API int vr_debug_terrain_sweep_state(vr_terrain* t, int32_t out_rect[4], int32_t* out_fields, float* out, size_t capacity_floats);
 /* Hydraulic erosion of level 0 of the heightmap under a brush mask - water that runs downhill, dissolves the terrain where it runs
  * fast and lays the load down where it slows: gullies and fans, which the talus relaxation of vr_terrain_erode cannot make.  It is
  * computed on the device from the map as it is there and followed by the refresh vr_terrain_edit does: afterwards the terrain is the

@@ -54,12 +54,13 @@ def _shifted(a, dx, dy, fill):
     return out
 
 
-def sweep(h, m, talus, rate):
-    """One iteration over the whole map: float32 (h0, w0) -> float32 (h0, w0)."""
+def sweep(h, m, talus, rate, neighbours=NEIGHBOURS):
+    """One iteration over the whole map: float32 (h0, w0) -> float32 (h0, w0).  (`neighbours`: another order is another operation -
+    the sensitivity checks of tests/erosion_state.py pass one to show that a test can tell.)"""
     talus, rate = F(talus), F(rate)
     diagonal = F(talus * F(1.41421354))
     acc = np.zeros_like(h)
-    for dx, dy in NEIGHBOURS:
+    for dx, dy in neighbours:
         T = diagonal if dx and dy else talus
         hn, mn = _shifted(h, dx, dy, F(0)), _shifted(m, dx, dy, F(0))        # outside the map: mask 0, no edge
         w = np.minimum(m, mn)
@@ -73,11 +74,18 @@ def sweep(h, m, talus, rate):
     return (h + acc).astype(F)
 
 
-def erode(texels, dabs, world_size, iterations, talus, rate):
-    """`iterations` sweeps on a copy of `texels` ((h, w) uint8) -> (new texels, rect)."""
+def state(texels, dabs, world_size, iterations, talus, rate, neighbours=NEIGHBOURS):
+    """(h, mask, rect) after `iterations` sweeps: the fp32 plane before the final rounding."""
     m, rect = mask_of(texels.shape, dabs, world_size)
     h = texels.astype(F)
-    for _ in range(int(iterations)):
-        h = sweep(h, m, talus, rate)
+    with np.errstate(under="ignore"):
+        for _ in range(int(iterations)):
+            h = sweep(h, m, talus, rate, neighbours)
+    return h, m, rect
+
+
+def erode(texels, dabs, world_size, iterations, talus, rate):
+    """`iterations` sweeps on a copy of `texels` ((h, w) uint8) -> (new texels, rect)."""
+    h, m, rect = state(texels, dabs, world_size, iterations, talus, rate)
     stored = np.floor(np.minimum(np.maximum(h, F(0)), F(255)) + F(0.5)).astype(np.uint8)
     return np.where(m > F(0), stored, texels).astype(np.uint8), rect

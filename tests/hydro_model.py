@@ -25,13 +25,14 @@ F = np.float32
 NEIGHBOURS = ((0, -1), (-1, 0), (1, 0), (0, 1))
 
 
-def sweep(h, d, s, m, rain, flow, capacity, dissolve, deposit, keep):
-    """One sweep over the whole map: float32 (h0, w0) planes -> (h', d', s')."""
+def sweep(h, d, s, m, rain, flow, capacity, dissolve, deposit, keep, neighbours=NEIGHBOURS):
+    """One sweep over the whole map: float32 (h0, w0) planes -> (h', d', s').  (`neighbours`: another order is another operation - the
+    sensitivity checks of tests/erosion_state.py pass one to show that a test can tell.)"""
     rain, flow, capacity, dissolve, deposit, keep = F(rain), F(flow), F(capacity), F(dissolve), F(deposit), F(keep)
     zero, quarter = F(0), F(0.25)
     dd, ds, out = np.zeros_like(h), np.zeros_like(h), np.zeros_like(h)
     S = h + d
-    for dx, dy in NEIGHBOURS:
+    for dx, dy in neighbours:
         hn, dn, sn, mn = (_shifted(a, dx, dy, zero) for a in (h, d, s, m))   # outside the map: mask 0, no edge
         w = np.where(m < mn, m, mn)
         live = w > zero
@@ -59,16 +60,17 @@ def sweep(h, d, s, m, rain, flow, capacity, dissolve, deposit, keep):
     return h2, d2, s2
 
 
-def state(texels, dabs, world_size, iterations, rain, flow, capacity, dissolve, deposit, evaporation):
-    """(h, d, s, mask, rect) after `iterations` sweeps: the fp32 planes before the final rounding."""
+def state(texels, dabs, world_size, iterations, rain, flow, capacity, dissolve, deposit, evaporation, neighbours=NEIGHBOURS, keep=None):
+    """(h, d, s, mask, rect) after `iterations` sweeps: the fp32 planes before the final rounding.  (`keep`: another value than
+    1 - evaporation, for the sensitivity checks only.)"""
     m, rect = mask_of(texels.shape, dabs, world_size)
-    keep = F(F(1.0) - F(evaporation))
+    keep = F(F(1.0) - F(evaporation)) if keep is None else F(keep)
     h = texels.astype(F)
     d = (F(rain) * m).astype(F)
     s = np.zeros_like(h)
     with np.errstate(under="ignore"):
         for _ in range(int(iterations)):
-            h, d, s = sweep(h, d, s, m, rain, flow, capacity, dissolve, deposit, keep)
+            h, d, s = sweep(h, d, s, m, rain, flow, capacity, dissolve, deposit, keep, neighbours)
     return h, d, s, m, rect
 
 

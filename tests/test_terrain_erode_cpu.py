@@ -194,3 +194,81 @@ def test_a_spike_spreads_to_its_eight_neighbours():
     assert out[8, 8] < 220
     ring = [(8 + dy, 8 + dx) for dx, dy in em.NEIGHBOURS]
     assert all(out[p] > 20 for p in ring)
+
+
+# ---- the fp32 state and its read-back (tests/erosion_state.py, tests/test_terrain_erosion_state_gpu.py) ---------------------------------
+def test_the_state_read_back_is_declared_exported_and_refuses_null(product_lib):
+    header = open(os.path.join(ROOT, "include", "vrterrain.h")).read()
+    assert re.search(r"VR_API\s+int\s+vr_debug_terrain_sweep_state\s*\(\s*vr_terrain\*\s*t,\s*int32_t out_rect\[4\],\s*int32_t\*\s*out_fields,"
+                     r"\s*float\*\s*out,\s*size_t capacity_floats\)", header)
+    assert "vr_debug_terrain_sweep_state" in capi.EXPORTS and len(product_lib.vr_debug_terrain_sweep_state.argtypes) == 5
+    fake = C.create_string_buffer(1 << 16)                          # stands in for a terrain; a refused call does not read it
+    t = C.cast(fake, C.c_void_p)
+    rect, fields, out = (C.c_int32 * 4)(-1, -1, -1, -1), C.c_int32(-1), (C.c_float * 4)(5, 5, 5, 5)
+    fn = product_lib.vr_debug_terrain_sweep_state
+    assert fn(None, rect, C.byref(fields), out, 4) == capi.VR_ERR_INVALID_ARGUMENT
+    assert fn(t, None, C.byref(fields), out, 4) == capi.VR_ERR_INVALID_ARGUMENT
+    assert fn(t, rect, None, out, 4) == capi.VR_ERR_INVALID_ARGUMENT
+    assert fn(None, rect, C.byref(fields), None, 0) == capi.VR_ERR_INVALID_ARGUMENT
+    assert list(rect) == [-1] * 4 and fields.value == -1 and list(out) == [5.0] * 4 and bytes(fake) == bytes(1 << 16)
+
+
+@pytest.mark.parametrize("size", SIZES[2:])
+def test_state_gives_the_bytes_of_erode(size):
+    """erode_model.state: the plane that erode() rounds - its bytes, its mask and its rectangle - and tests/erosion_state.py's view of it."""
+    from tests import erosion_state as es
+    h, w = size
+    rng = np.random.default_rng(7 * h + w)
+    texels = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    dabs = seeded_dabs(rng, h, w)
+    mask, rect = em.mask_of(texels.shape, dabs, WORLD)
+    for iterations, talus, rate in ((1, 0.0, 0.125), (2, 0.7, 0.1), (33, 3.0, 0.03)):
+        plane, m, r = em.state(texels, dabs, WORLD, iterations, talus, rate)
+        want, want_rect = em.erode(texels, dabs, WORLD, iterations, talus, rate)
+        assert plane.dtype == np.float32 and plane.shape == texels.shape and np.array_equal(m, mask) and tuple(r) == tuple(rect) == tuple(want_rect)
+        stored = np.floor(np.clip(plane.astype(np.float64), 0.0, 255.0) + 0.5).astype(np.uint8)       # (exact in double)
+        assert np.array_equal(np.where(mask > 0, stored, texels), want)
+        assert np.array_equal(plane[mask == 0], texels[mask == 0].astype(np.float32))
+        step = texels.astype(np.float32)
+        for _ in range(iterations):
+            step = em.sweep(step, mask, talus, rate)
+        assert np.array_equal(step.view(np.uint32), plane.view(np.uint32))
+        view = es.state("thermal", texels, dabs, WORLD, iterations, (talus, rate))
+        assert np.array_equal(view["bytes"], want) and view["rect"] == tuple(want_rect) and np.array_equal(es.bits(view["planes"][0]), es.bits(plane))
+    assert (want != texels).sum() >= 30
+
+
+def test_every_state_case_can_tell_a_wrong_order(oracle, product_lib):
+    """The cases of tests/test_terrain_erosion_state_gpu.py on scenes made by the oracle's synthetic heightmaps: each is sensitive - the
+    model with two neighbours exchanged differs in at least 30 fp32 cells of the final state - every wrong variant of DESIGN.md 4w's
+    table changes the state of every case, and the corner and clamp cases show what they are there for.  (About 10 s of numpy.)"""
+    from tests import erosion_state as es
+    config = {}
+    for kind, fn in (("thermal", product_lib.vr_debug_erode_config), ("hydraulic", product_lib.vr_debug_hydro_config)):
+        cfg = (C.c_int32 * 4)()
+        assert fn(cfg) == capi.VR_OK
+        config[kind] = (cfg[0], cfg[1], cfg[2])
+    maps = es.scene_maps(oracle.synth_heightmap)
+    cases = es.suite_cases(maps, config)
+    assert len(cases) >= 6 + 20 + 4 + 2 + 1
+    for name, kind, texels, dabs, world, iterations, params in cases:
+        right = es.state(kind, texels, dabs, world, iterations, params)
+        assert es.assert_sensitive(kind, texels, dabs, world, iterations, params, right) >= es.SENSITIVE
+        if name.startswith(("scene", "borders", "1024")):
+            for variant in es.wrong_variants(kind, params):
+                cells, _ = es.sensitivity(kind, texels, dabs, world, iterations, params, right, variant)
+                assert cells >= 1, (name, kind, iterations, variant)
+        if name.startswith("borders"):
+            assert es.changes_on_both_sides_of_every_border(texels.astype(np.float32), right["planes"][0], *config[kind][:2]), (name, kind, iterations)
+    texels, world = maps["fast64"]
+    dabs = np.float32([es.dab(texels.shape, world, 30.0, 28.0, 6.0, 0.0, 1.0)])
+    for corner, (params, holds) in es.HYDRO_CORNERS.items():
+        holds(es.state("hydraulic", texels, dabs, world, 2 * config["hydraulic"][2] + 1, params), texels)
+    for corner, (params, prepare, holds) in es.THERMAL_CORNERS.items():
+        holds(es.state("thermal", prepare(texels), dabs, world, 2 * config["thermal"][2] + 1, params), prepare(texels))
+    texels, dabs, n, params = es.clamp_case(64.0)
+    want = es.state("hydraulic", texels, dabs, 64.0, n, params)
+    masked = want["mask"] > 0
+    assert (masked & (want["settled"] < 0)).sum() >= 10 and (masked & (want["settled"] > 255)).sum() >= 10
+    for name, (dabs, intended) in es.rect_dabs(maps["odd"][1]).items():
+        assert es.state("thermal", maps["odd"][0], dabs, maps["odd"][1], 1, es.THERMAL)["rect"] == intended, name

@@ -211,7 +211,7 @@ EXPORTS = [
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
     "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush", "vr_terrain_erode", "vr_debug_erode_config",
-    "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch",
+    "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
 ]
 
@@ -341,6 +341,7 @@ def load_library():
         "vr_terrain_erode_hydraulic": (C.c_int, [vp, P(HydroParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_debug_hydro_config": (C.c_int, [P(C.c_int32)]),
         "vr_debug_hydro_sweeps_per_launch": (C.c_int, [C.c_int32]),
+        "vr_debug_terrain_sweep_state": (C.c_int, [vp, P(C.c_int32), P(C.c_int32), vp, C.c_size_t]),
         "vr_terrain_history_enable": (C.c_int, [vp, C.c_size_t]),
         "vr_terrain_history_commit": (C.c_int, [vp]),
         "vr_terrain_undo": (C.c_int, [vp, P(C.c_int32)]),

@@ -109,7 +109,7 @@ void vr_brush_release(vr_terrain* t)
     if (t->h_brush_dabs) { (void)hipHostFree(t->h_brush_dabs); t->h_brush_dabs = nullptr; }
     (void)hipFree(t->d_brush_dabs); t->d_brush_dabs = nullptr;
     (void)hipFree(t->d_brush_snap); t->d_brush_snap = nullptr; t->brush_snap_bytes = 0;
-    (void)hipFree(t->d_erode); t->d_erode = nullptr; t->erode_bytes = 0;
+    (void)hipFree(t->d_erode); t->d_erode = nullptr; t->erode_bytes = 0; t->erode_last = {};
     t->brush_pending = false;
 }
 

@@ -230,17 +230,19 @@ extern "C" VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps)
 }
 
 // One call of the model M behind its entry point's own checks (vr_brush_call, vr_brush_dev.h): the block's 2F + 1 planes of the
-// rectangle reserved, then begin, ceil(iterations / per_launch) step launches and end.
+// rectangle reserved, then begin, ceil(iterations / per_launch) step launches and end.  What the launches left is recorded on the
+// terrain for vr_debug_terrain_sweep_state: a refused call leaves the record as it was, a call whose dabs all miss clears it.
 template <class M>
 static int sweep_call(vr_terrain* t, const char* who, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4], int iterations, int per_launch, const typename M::Const& k)
 {
     size_t plane = 0;                                              // floats from one plane to the next: the rectangle's, rounded up to 256 bytes
-    return vr_brush_call(t, 0, dabs, n, VR_BRUSH_FLATTEN, out_rect,                              // strength is an opacity
+    const int call_rc = vr_brush_call(t, 0, dabs, n, VR_BRUSH_FLATTEN, out_rect,                              // strength is an opacity
         [&](const DirtyRect& r) -> int {
             plane = ((size_t)(r.x1 - r.x0) * (size_t)(r.y1 - r.y0) + 63) & ~(size_t)63;
             { const int rc = vr_brush_reserve(t, 0); if (rc) return rc; }
             const int rc = vr_brush_grow(t, &t->d_erode, &t->erode_bytes, plane * sizeof(float) * Sweep<M>::kPlanes);
             if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain %s: %d x %zu bytes for the mask and state planes", who, Sweep<M>::kPlanes, plane * sizeof(float));
+            if (rc == VR_OK) t->erode_last = {};                   // past the last refusal: the block is this call's from here on
             return rc;
         },
         [&](hipStream_t s, const DirtyRect& r, uint32_t nd) -> int {
@@ -256,8 +258,40 @@ static int sweep_call(vr_terrain* t, const char* who, const vr_brush_dab* dabs, 
                 hipLaunchKernelGGL(k_sweep_steps<M>, grid, dim3(M::kThreads), 0, s, (const float*)d_set[cur], d_set[cur ^ 1], (const float*)d_mask, plane, rw, rh, steps, k);
             }
             hipLaunchKernelGGL(k_sweep_end<M>, tiles_32x8(r), dim3(256), 0, s, const_cast<uint8_t*>(t->height.base), t->height.w0, r, (const float*)d_mask, (const float*)d_set[cur], plane);
+            t->erode_last.x = r.x0; t->erode_last.y = r.y0; t->erode_last.w = rw; t->erode_last.h = rh;
+            t->erode_last.fields = M::kFields; t->erode_last.set = cur; t->erode_last.plane = plane;
             return VR_OK;
         });
+    if (call_rc == VR_OK && t->brush_prepared.empty()) t->erode_last = {};                      // n == 0, or every dab misses the map
+    return call_rc;
+}
+
+// The planes the last erosion call left: the mask, then the F fields of the set its last step launch wrote, each packed to rw * rh
+// floats.  The copy runs on the context's stream behind the erosion's event (the call may have run on another stream) and the
+// entry returns when it has completed, as a query's download does.
+extern "C" VR_API int vr_debug_terrain_sweep_state(vr_terrain* t, int32_t out_rect[4], int32_t* out_fields, float* out, size_t capacity_floats)
+{
+    VR_REQUIRE(t != nullptr, "terrain is NULL");
+    VR_REQUIRE(out_rect != nullptr && out_fields != nullptr, "out_rect or out_fields is NULL");
+    const vr_terrain::ErodeRecord rec = t->erode_last;
+    const size_t cells = (size_t)rec.w * (size_t)rec.h, need = (size_t)(1 + rec.fields) * cells;
+    if (!(out == nullptr && capacity_floats == 0)) {
+        VR_REQUIRE(out != nullptr, "out is NULL with a capacity");
+        VR_REQUIRE(rec.fields == 0 || capacity_floats >= need, "capacity below (1 + fields) * w * h floats");
+    }
+    out_rect[0] = rec.x; out_rect[1] = rec.y; out_rect[2] = rec.w; out_rect[3] = rec.h;
+    *out_fields = rec.fields;
+    if (out == nullptr || rec.fields == 0) return VR_OK;
+    VR_HIP(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    if (t->ev_brush) VR_HIP(hipStreamWaitEvent(s, t->ev_brush, 0));
+    const float* const d_mask = (const float*)t->d_erode;
+    const float* const d_set = d_mask + (size_t)(1 + rec.set * rec.fields) * rec.plane;
+    VR_HIP(hipMemcpyAsync(out, d_mask, cells * sizeof(float), hipMemcpyDeviceToHost, s));
+    for (int f = 0; f < rec.fields; f++)
+        VR_HIP(hipMemcpyAsync(out + (size_t)(1 + f) * cells, d_set + (size_t)f * rec.plane, cells * sizeof(float), hipMemcpyDeviceToHost, s));
+    VR_HIP(hipStreamSynchronize(s));
+    return VR_OK;
 }
 
 extern "C" VR_API int vr_terrain_erode(vr_terrain* t, const vr_erode_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4])

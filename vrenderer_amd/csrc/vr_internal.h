@@ -403,6 +403,9 @@ struct vr_terrain {
     // event: an erosion shares the brush's dab buffers and its consumed-event protocol, so strokes and erosions of one terrain
     // order against each other, and one erosion against the next one's growth of the block, whichever stream they ran on.
     void* d_erode = nullptr; size_t erode_bytes = 0;
+    // What the last erosion call that launched left in the block, for vr_debug_terrain_sweep_state (host side only): the rectangle,
+    // the model's field count (0: no record), the floats from one plane to the next and which of the two sets holds the final state.
+    struct ErodeRecord { int x = 0, y = 0, w = 0, h = 0, fields = 0, set = 0; size_t plane = 0; } erode_last;
     // History (vr_history.hip): the journal's bookkeeping (vr_history.h) over a table of kHistoryMaxRecords records and one device
     // arena, both from vr_terrain_history_enable on, and the event behind the latest journal kernel with the stream it ran on - a
     // journal kernel on another stream waits for it (the rule of ev_pyramid / pyramid_stream).

@@ -571,6 +571,20 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_erode_hydraulic(self.handle, C.byref(params), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_erode_hydraulic")
         return tuple(int(v) for v in rect)
 
+    def ErosionState(self):
+        """vr_debug_terrain_sweep_state (test helper): what the last Erode or ErodeHydraulic of this terrain left on the device before
+        the final rounding - ((x, y, w, h), mask, [planes]), float32 arrays of shape (h, w): one plane (h) after Erode, three (h, d,
+        s) after ErodeHydraulic.  ((0, 0, 0, 0), None, []) when there is no such call, or the last one launched nothing."""
+        rect, fields = (C.c_int32 * 4)(), C.c_int32()
+        check(self.ctx.lib.vr_debug_terrain_sweep_state(self.handle, rect, C.byref(fields), None, 0), "vr_debug_terrain_sweep_state")
+        if fields.value == 0:
+            return tuple(int(v) for v in rect), None, []
+        w, h = int(rect[2]), int(rect[3])
+        out = np.empty((1 + fields.value, h, w), np.float32)
+        check(self.ctx.lib.vr_debug_terrain_sweep_state(self.handle, rect, C.byref(fields), _vp(out), out.size), "vr_debug_terrain_sweep_state")
+        assert (int(rect[2]), int(rect[3]), fields.value) == (w, h, out.shape[0] - 1)
+        return tuple(int(v) for v in rect), out[0], [out[1 + f] for f in range(fields.value)]
+
     def EnableHistory(self, budget_bytes):
         """vr_terrain_history_enable: a device arena of budget_bytes in which every Edit and Brush from now on first records the
         rectangle it is about to write; 0 switches history off and frees the arena; another budget drops all steps."""
