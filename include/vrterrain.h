@@ -148,6 +148,9 @@ typedef struct vr_image    vr_image;    /* RGBA16F image in device memory       
 /* nvrhi::IDevice + the single command list (main.cpp:57-61, Renderer.cpp:48). */
 VR_API int  vr_context_create(int device_ordinal, vr_context** out);
 VR_API void vr_context_destroy(vr_context* ctx);
+/* What the host owes: the new stream runs behind the work the library queued on the old one (a wait for an event recorded
+ * there, or a synchronise).  This orders everything a terrain keeps on the context's stream alone: the maps, their chains and
+ * tables, the query pyramid, the history journal, the brush and erosion buffers, and device-pointer queries not yet waited for. */
 VR_API int  vr_context_set_stream(vr_context* ctx, void* hip_stream);
 VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submit + wait */
 /* Options.  VR_OPT_ASYNC_GEOMETRY (default 1): vr_terrain_render runs its view-dependent geometry

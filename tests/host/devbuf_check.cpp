@@ -1,10 +1,14 @@
-// Check of vr_devbuf_grow / vr_devbuf_grow_group (vrenderer_amd/csrc/vr_devbuf.h) with a counting allocator over malloc: for a
-// single buffer and for groups of 1..15, from empty, from full and from mixed slots, with the k-th allocation failing for
-// every k (and for none), and with a quiesce hook that refuses.
+// Check of vr_devbuf_grow / vr_devbuf_grow_group / vr_devbuf_reserve (vrenderer_amd/csrc/vr_devbuf.h) with a counting allocator
+// over malloc: for a single buffer and for groups of 1..15, from empty, from full and from mixed slots, with the k-th allocation
+// failing for every k (and for none), and with a quiesce hook that refuses; for the reserve, with an allocator that grants
+// everything, one that refuses whatever is larger than the request (the doubled size), and one that refuses everything.
 //   failure: every pointer and capacity bit-identical to before, the live blocks are the blocks live before (nothing leaked,
 //            nothing freed), quiesce not called (or, where it refused, called once and nothing freed but the new blocks);
 //   success: every old block freed exactly once and behind quiesce, quiesce called once if an old block existed and never
 //            otherwise, every slot holds a live block of the size asked for, the capacity equals the request.
+//   reserve: the capacity it reaches is the policy's - the smallest of 64 KiB, 128 KiB, .. (from empty) or of twice, four times, ..
+//            the old capacity that holds the request; exactly the request where that is refused; otherwise as a failure above,
+//            with one allocation tried per size and quiesce never asked twice.
 // Plain C++17, no GPU: g++ -std=c++17 -Wall -Werror -I vrenderer_amd/csrc tests/host/devbuf_check.cpp
 #include "vr_devbuf.h"
 
@@ -22,13 +26,15 @@ static long cases = 0, failures = 0;
 static std::map<void*, size_t> live;            // block -> its size
 static std::vector<void*> freed;                // every release, in order
 static long alloc_calls = 0, fail_at = 0;       // the fail_at-th allocation from now fails (0: none)
+static size_t refuse_above = 0;                 // every allocation larger than this fails (0: no limit)
+static bool refuse_all = false;
 static long quiesce_calls = 0;
 static size_t frees_at_quiesce = 0;             // releases seen when quiesce ran
 static int quiesce_result = 0;
 
 static bool test_alloc(void** out, size_t bytes)
 {
-    if (++alloc_calls == fail_at) return false;
+    if (++alloc_calls == fail_at || refuse_all || (refuse_above && bytes > refuse_above)) return false;
     *out = std::malloc(bytes ? bytes : 1);
     live[*out] = bytes;
     return true;
@@ -145,9 +151,56 @@ static void single_cases()
                 }
 }
 
+// mode: 0 = every size granted, 1 = only what is no larger than the request, 2 = nothing
+static void reserve_cases()
+{
+    char what[80];
+    const size_t have[4] = { 0, 100, 1 << 16, 3 << 16 }, ask[5] = { 1, 1 << 16, (1 << 16) + 1, 200000, 1 << 20 };
+    for (size_t h : have)
+        for (size_t a : ask)
+            for (int quiesce_rc = 0; quiesce_rc <= 7; quiesce_rc += 7)
+                for (int mode = 0; mode < 3; mode++) {
+                    std::snprintf(what, sizeof(what), "reserve have=%zu ask=%zu mode=%d quiesce=%d", h, a, mode, quiesce_rc);
+                    cases++;
+                    void* ptr = h ? old_block(h) : nullptr;
+                    void* const before = ptr;
+                    size_t cap = h;
+                    const std::map<void*, size_t> live_before = live;
+                    reset(0, quiesce_rc);
+                    refuse_above = mode == 1 ? a : 0; refuse_all = mode == 2;
+                    const int rc = vr_devbuf_reserve(&ptr, &cap, a, test_alloc, test_release, test_quiesce);
+                    refuse_above = 0; refuse_all = false;
+                    size_t doubled = h ? h * 2 : (size_t)1 << 16;          // the policy, written out again
+                    while (doubled < a) doubled *= 2;
+                    const bool exact = mode == 1 && doubled > a;            // the doubled size is refused, the request granted
+                    const bool refused = mode != 2 && h != 0 && quiesce_rc != 0;
+                    if (a <= h) {
+                        CHECK(rc == 0 && alloc_calls == 0 && quiesce_calls == 0 && freed.empty());
+                        CHECK(ptr == before && cap == h && live == live_before);
+                    } else if (mode == 2 || refused) {
+                        CHECK(rc == (mode == 2 ? kDevBufNoMemory : quiesce_rc));
+                        CHECK(ptr == before && cap == h && live == live_before);
+                        CHECK(alloc_calls == (mode == 2 ? (doubled > a ? 2 : 1) : (exact ? 2 : 1)));      // one try per size, none behind a refusing quiesce
+                        CHECK(quiesce_calls == (refused ? 1 : 0));
+                        CHECK(freed.size() == (size_t)(refused ? 1 : 0));
+                        for (void* p : freed) CHECK(live_before.count(p) == 0);
+                    } else {
+                        CHECK(rc == 0);
+                        CHECK(cap == (exact ? a : doubled));
+                        CHECK(alloc_calls == (exact ? 2 : 1));
+                        CHECK(ptr != nullptr && ptr != before && live.count(ptr) == 1 && live[ptr] == cap);
+                        CHECK(quiesce_calls == (h ? 1 : 0) && frees_at_quiesce == 0);
+                        CHECK(freed.size() == (size_t)(h ? 1 : 0) && (!h || (freed[0] == before && live.count(before) == 0)));
+                        CHECK(live.size() == live_before.size() + (h ? 0 : 1));
+                    }
+                    while (!live.empty()) { std::free(live.begin()->first); live.erase(live.begin()); }
+                }
+}
+
 int main()
 {
     single_cases();
+    reserve_cases();
     group_cases<15>();
     std::printf("devbuf: %ld cases, %ld failures\n", cases, failures);
     return failures ? EXIT_FAILURE : EXIT_SUCCESS;

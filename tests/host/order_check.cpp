@@ -8,15 +8,20 @@
 //  (b) HAPPENS-BEFORE MODEL of HIP's stream semantics: one vector clock per stream; a record snapshots the stream's clock into the
 //      event, a wait joins it, a dispatch-stamped event is a snapshot right behind its launch; a host-side synchronise joins the
 //      stream's (event's) clock into everything queued later.  Every kernel that touches a set's selection, a set's vertices and
-//      bins, the node heights or an HDR image registers a read or a write; a conflicting pair (write/write, read/write) that the
-//      clocks do not order is a failure.  The protocol must pass; where the plain transcription does not, that is a finding
+//      bins, the node heights, an HDR image, one of the two maps (level 0, chain and tables), the query pyramid, the journal's
+//      arena, the brush buffers or the query staging registers a read or a write; a conflicting pair (write/write, read/write)
+//      that the clocks do not order is a failure, and so is memory the host frees or rewrites (host_touch) while something it has
+//      not waited for may still use it.  The protocol must pass; where the plain transcription does not, that is a finding
 //      about the parent, and one of the intended differences must be what repairs it.
+//      The editing path (edit, brush / erode, undo / redo, history_enable, queries, sweep_state) is transcribed from commit 605778b,
+//      the last one with its three private event records; the numbers beside it are that commit's lines.
 //  (c) every sequence up to kExhaustive calls, then a fixed-seed random sample of longer ones.
 // What the model is not: the HIP runtime (it assumes the documented semantics of the two calls), or the 64-entry ring the
 // stamped events of ordinary runs come from (every stamped launch gets a fresh event here).
 //   order_check                 the check; prints sequences and failures
 //   order_check --drop-each     is the model alive?  The transcription (intended differences on) loses one wait site at a time;
-//                               prints for each site in how many sequences (b) reports it
+//                               prints for each site in how many sequences (b) reports it, and for a site that no sequence
+//                               reports the reason it orders nothing (dead_reason) - a site with neither fails the run
 // Plain C++17, no GPU: g++ -std=c++17 -Wall -Werror -I vrenderer_amd/csrc tests/host/order_check.cpp
 #include "vr_order.h"
 
@@ -29,16 +34,18 @@
 // ---- the world: trace, clocks, accesses -----------------------------------------------------------
 enum Stream { S_NONE = 0, G0, G1, M0, M1, TM, N_STREAMS };       // two geometry streams, the context's (a host may switch), the tone mapper's
 static const char* const kStreamName[N_STREAMS] = { "-", "geo0", "geo1", "main0", "main1", "tonemap" };
-enum Res { SEL0, SEL1, SEL2, GEO0, GEO1, GEO2, HEIGHTS, IMG0, IMG1, N_RES };
+// (a map: its level 0, its mip chain and its tables; the brush buffers: dab lists, snapshot and the erosions' block)
+enum Res { SEL0, SEL1, SEL2, GEO0, GEO1, GEO2, HEIGHTS, IMG0, IMG1, HMAP, AMAP, PYRAMID, JOURNAL, BRUSHBUF, STAGE, N_RES };
 static const char* const kResName[N_RES] = { "selection 0", "selection 1", "selection 2", "verts+bins 0", "verts+bins 1", "verts+bins 2",
-                                             "node heights", "image 0", "image 1" };
+                                             "node heights", "image 0", "image 1", "heightmap", "albedo", "query pyramid", "journal arena",
+                                             "brush buffers", "query staging" };
 // own events (0 = none); stamped events follow
-enum { EV_GEO_DONE = 1, EV_RASTER_DONE = 4, EV_SEL_READ = 7, EV_MAIN_DEP = 10, EV_SEL_COPY, EV_RASTER_BEGIN, EV_WRITTEN, EV_READ_DONE = 15, EV_FIRST_STAMPED = 17,
+enum { EV_GEO_DONE = 1, EV_RASTER_DONE = 4, EV_SEL_READ = 7, EV_MAIN_DEP = 10, EV_SEL_COPY, EV_RASTER_BEGIN, EV_WRITTEN, EV_READ_DONE = 15, EV_PYRAMID = 17, EV_JOURNAL, EV_BRUSH, EV_FIRST_STAMPED,
        N_EVENTS = 96 };
 typedef std::array<uint32_t, N_STREAMS> Clock;
 static void join(Clock& a, const Clock& b) { for (int i = 0; i < N_STREAMS; i++) if (b[i] > a[i]) a[i] = b[i]; }
 
-struct Op { uint8_t wait, stream; uint16_t event; };
+struct Op { uint8_t wait, stream; uint16_t event; };              // wait: 0 record, 1 wait, 2 the host's synchronise (no stream)
 struct World {
     std::vector<Op> trace;
     Clock clk[N_STREAMS], host, ev[N_EVENTS];
@@ -46,7 +53,7 @@ struct World {
     int next_event;
     struct Acc { Clock c; int stream; };
     Acc last_write[N_RES]; bool has_write[N_RES];
-    Acc reads[N_RES][64]; int n_reads[N_RES];
+    Acc reads[N_RES][128]; int n_reads[N_RES];
     int unordered;                   // conflicting pairs the clocks do not order (+ waits on an event never recorded)
     std::string first;
     int drop_site;                   // the transcription's wait site that is left out (0: none)
@@ -72,6 +79,16 @@ struct World {
     int stamp(int s) { const int e = next_event++; ev[e] = clk[s]; ev_recorded[e] = true; return e; }     // right behind the kernel just queued
     void sync_stream(int s) { join(host, clk[s]); }
     void sync_event(int e) { join(host, ev[e]); }
+    int sync(int e) { sync_event(e); trace.push_back({ 2, 0, (uint16_t)e }); return 0; }                  // a side resource's order_side_idle
+    void host_touch(int r)                                       // the host frees the resource's memory, or writes pinned memory that queued work reads
+    {
+        auto check = [&](const Acc& a, const char* kind) {
+            if (a.c[a.stream] > host[a.stream]) fail(std::string(kResName[r]) + ": " + kind + " on " + kStreamName[a.stream] + " not waited for by the host");
+        };
+        if (has_write[r]) check(last_write[r], "write");
+        for (int i = 0; i < n_reads[r]; i++) check(reads[r][i], "read");
+        n_reads[r] = 0; has_write[r] = false;
+    }
     void host_orders(int later, int earlier) { join(clk[later], clk[earlier]); }      // what a host owes when it moves work to another stream
     void fail(const std::string& what) { if (!unordered++) first = what; }
     void access(int r, bool write, int s)                        // by the kernel just queued on s
@@ -85,11 +102,12 @@ struct World {
         if (write) {
             for (int i = 0; i < n_reads[r]; i++) check(reads[r][i], "read");
             n_reads[r] = 0; has_write[r] = true; last_write[r] = { now, s };
-        } else if (n_reads[r] < 64) reads[r][n_reads[r]++] = { now, s };
+        } else if (n_reads[r] < 128) reads[r][n_reads[r]++] = { now, s };
         else fail("too many reads between two writes for the model");
     }
 };
-struct Ops { World* w; int record(int e, int s) const { return w->record(e, s); } int wait(int s, int e) const { return w->wait(s, e); } };
+struct Ops { World* w; int record(int e, int s) const { return w->record(e, s); } int wait(int s, int e) const { return w->wait(s, e); }
+             int sync(int e) const { return w->sync(e); } };
 
 // ---- what the .hip files decide (the same for both protocols): the context and the terrain's set bookkeeping ---------------
 struct Host {
@@ -105,6 +123,10 @@ struct Host {
     int prep_view[3] = { 0, 0, 0 }; uint64_t prep_serial[3] = { 0, 0, 0 }, prep_counter = 0;
     int cur = 0, frame_no = 0;
     unsigned geo_turn = 0;
+    // the editing path: the pyramid exists (d_pyramid), history is on, the steps that can be undone / redone (the map of each),
+    // an erosion has left its planes (vr_terrain::erode_last)
+    bool pyramid_built = false, history_on = false, sweep_left = false;
+    std::vector<int> undo, redo;
     int pick_set() const              // vr_terrain_pick_set
     {
         int best = -1;
@@ -136,14 +158,31 @@ struct Intended {
     bool own_stop;          // vr_frame_submit waits for the lighting pass's OWN stop event, or records; never ctx->last_stop
     bool heights_behind;    // the node-height update runs behind every chain queued so far (found by (b): see main)
     bool common_order;      // vr_terrain_select queues its waits in launch_geometry's order (the permitted reorder)
+    bool sweep_dead_wait;   // vr_debug_terrain_sweep_state does not wait for the erosion's event on the stream that recorded it (a dead wait)
 };
 enum Site { W_LG_CHAIN = 1, W_LG_SEL_READ, W_LG_RASTER, W_LG_MAIN_DEP, W_LG_SEL_COPY, W_PREP_HINT, W_PREP_NOW, W_TILE_CHAIN, W_KEEP_READER, W_AHEAD,
-            W_SEL_MAIN_DEP, W_SEL_CHAIN, W_SEL_SEL_READ, W_SEL_RASTER, W_FRAME_READER, W_FRAME_WRITTEN, W_HEIGHTS_CHAIN, N_SITES };
+            W_SEL_MAIN_DEP, W_SEL_CHAIN, W_SEL_SEL_READ, W_SEL_RASTER, W_FRAME_READER, W_FRAME_WRITTEN, W_HEIGHTS_CHAIN,
+            W_MAPS_CHAIN, W_MAPS_RASTER, W_PYR_CAST, W_PYR_WRITE, W_JOURNAL, S_JOURNAL_IDLE, S_BRUSH_IDLE, W_SWEEP, W_SWEEP_DEAD, N_SITES };
 static const char* const kSiteName[N_SITES] = { "", "launch_geometry: previous chain", "launch_geometry: lock_view copy out of the set", "launch_geometry: tile pass",
     "launch_geometry: main dependency", "launch_geometry: lock_view source complete", "prepare: start hint", "prepare: context's stream waits now",
     "tile pass: chain", "fused tile pass: image's reader", "tile pass: deferred waits of sets prepared ahead", "select: main dependency", "select: previous chain",
     "select: lock_view copy out of the set", "select: tile pass", "frame: image's reader", "frame: tone-map stage behind the writer",
-    "heights: chains queued so far (intended difference)" };
+    "heights: chains queued so far (intended difference)",
+    "level-0 write: chains queued so far", "level-0 write: tile passes", "cast_rays: pyramid's last writer", "level-0 write: pyramid's last user",
+    "journal kernel: the journal's last kernel", "history_enable: host waits for the journal", "brush / erode: host waits for the previous one",
+    "sweep_state: the erosion on another stream", "sweep_state: the erosion on this stream (dropped: intended difference)" };
+// Sites that (b) is expected NOT to report, and why.  All but the first order work on the context's stream of before a set_stream
+// against work on the stream of after it, which the host has ordered already ("what the host owes", SET_STREAM below).
+static const char* dead_reason(int site)
+{
+    switch (site) {
+    case W_PREP_HINT: return "a hint: it says when a prepared chain becomes runnable, it orders nothing";
+    case W_MAPS_RASTER: case W_PYR_CAST: case W_PYR_WRITE: case W_JOURNAL: case W_SWEEP:
+        return "both sides ran on the context's stream, and the host orders the new stream behind the old one at set_stream";
+    case W_SWEEP_DEAD: return "a wait on the stream that recorded the event";
+    default: return nullptr;
+    }
+}
 
 struct Parent {
     World& w; Host& h; Intended in;
@@ -157,8 +196,15 @@ struct Parent {
         for (int i = 0; i < 3; i++) { sets[i].ev_geo_done = EV_GEO_DONE + i; sets[i].ev_raster_done = EV_RASTER_DONE + i; sets[i].ev_sel_read = EV_SEL_READ + i; }
         for (int i = 0; i < 2; i++) { img[i].ev_written = EV_WRITTEN + i; img[i].ev_read_done = EV_READ_DONE + i; }
     }
+    // the editing path's three private records (vr_internal.h of the parent: ev_pyramid / pyramid_stream with d_pyramid as the flag,
+    // ev_history / history_stream / history_queued, ev_brush / brush_pending)
+    int ev_pyramid = EV_PYRAMID, pyramid_stream = 0;
+    int ev_history = EV_JOURNAL, history_stream = 0; bool history_queued = false;
+    int ev_brush = 0; bool brush_pending = false;
+    int brush_stream = 0;   // (no field of the parent: what Intended::sweep_dead_wait needs to tell the dead wait from the live one)
     void R(int e, int s) { w.record(e, s); }
     void W(int site, int s, int e) { if (site != w.drop_site) w.wait(s, e); }
+    void S(int site, int e) { if (site != w.drop_site) w.sync(e); }
     int stream(int gi) const { return sets[gi].stream; }
 
     void begin_chain(int gi)                                  // launch_geometry, vr_raster.hip
@@ -253,6 +299,53 @@ struct Parent {
         /* 456 */ R(ev_main_dep, h.main);
         /* 457 */ for (Set& g : sets) g.main_dep_pending = true;
     }
+    void maps_begin()                                         // vr_derive_level0_write, vr_derive.hip (the header's two steps, flat)
+    {
+        /* 230 */ for (Set& g : sets) if (g.geo_recorded) W(W_MAPS_CHAIN, h.main, g.ev_geo_done);
+        /* 231 */ for (Set& g : sets) if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == h.ev_epoch)) W(W_MAPS_RASTER, h.main, g.raster_done);
+    }
+    void maps_end() { /* 260 */ heights_end(); }
+    void pyramid_begin(bool write)
+    {
+        const int s = h.main;
+        if (!write) { /* vr_query.hip 368 */ if (s != pyramid_stream) W(W_PYR_CAST, s, ev_pyramid); }
+        else { /* vr_derive.hip 248 */ if (s != pyramid_stream) W(W_PYR_WRITE, s, ev_pyramid); }
+    }
+    void pyramid_end()
+    {
+        /* vr_query.hip 385 / vr_derive.hip 256 */ R(ev_pyramid, h.main);
+        /* 390 / 257 */ pyramid_stream = h.main;
+    }
+    void journal_begin() { /* vr_history.hip 80 */ if (history_queued && h.main != history_stream) W(W_JOURNAL, h.main, ev_history); }
+    void journal_end()
+    {
+        /* 91 */ R(ev_history, h.main);
+        /* 92 */ history_stream = h.main; history_queued = true;
+    }
+    void journal_idle()                                       // history_idle
+    {
+        /* 106 */ if (history_queued) S(S_JOURNAL_IDLE, ev_history);
+        /* 107 */ history_queued = false;
+    }
+    void brush_idle()                                         // vr_brush_consumed, vr_brush.hip
+    {
+        /* 129 */ ev_brush = EV_BRUSH;                        // (vr_brush_reserve, in front of it)
+        /* 119 */ if (!brush_pending) return;
+        /* 120 */ S(S_BRUSH_IDLE, ev_brush);
+        /* 121 */ brush_pending = false;
+    }
+    void brush_end()                                          // vr_brush_call, vr_brush_dev.h
+    {
+        /* 92 */ R(ev_brush, h.main);
+        /* 93 */ brush_pending = true;
+        brush_stream = h.main;
+    }
+    void sweep_begin()                                        // vr_debug_terrain_sweep_state, vr_erode.hip
+    {
+        if (!in.sweep_dead_wait) {
+        /* 287 */ if (ev_brush) W(brush_pending && brush_stream != h.main ? W_SWEEP : W_SWEEP_DEAD, h.main, ev_brush);
+        } else if (brush_pending && brush_stream != h.main) W(W_SWEEP, h.main, ev_brush);
+    }
     void light_writer_begins(int im)                          // vr_frame_submit, vr_frame.hip
     {
         /* 38 */ if (img[im].read_pending) { W(W_FRAME_READER, h.main, img[im].ev_read_done); img[im].read_pending = false; }
@@ -279,8 +372,10 @@ struct Parent {
 struct Protocol {
     World& w; Host& h; Ops ops;
     OrderTerrain<int> t; OrderSet<int, int> sets[3]; OrderImage<int> img[2];
+    OrderSide<int, int> pyramid, journal, brush;
     Protocol(World& w_, Host& h_) : w(w_), h(h_), ops{ &w_ }
     {
+        pyramid.ev = EV_PYRAMID; journal.ev = EV_JOURNAL; brush.ev = EV_BRUSH;
         t.ev_changed = EV_MAIN_DEP; t.ev_sel_ready = EV_SEL_COPY; t.hint.own = EV_RASTER_BEGIN;
         for (int i = 0; i < 3; i++) { sets[i].stream = G0; sets[i].chain.own = EV_GEO_DONE + i; sets[i].tile_pass.own = EV_RASTER_DONE + i;
                                       sets[i].sel_read.ev = EV_SEL_READ + i; sets[i].main_dep.ev = t.ev_changed; }
@@ -308,6 +403,20 @@ struct Protocol {
     void select_end(int gi) { order_end_chain(sets[gi], ops); }
     void heights_begin() { OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] }; order_terrain_changing(all, ops, h.main); }
     void heights_end() { OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] }; order_terrain_changed(t, all, ops, h.main); }
+    void maps_begin()
+    {
+        OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] };
+        order_terrain_changing(all, ops, h.main); order_terrain_tables_changing(all, ops, h.main, h.ev_epoch);
+    }
+    void maps_end() { heights_end(); }
+    void pyramid_begin(bool) { order_side_begin(pyramid, ops, h.main); }
+    void pyramid_end() { order_side_end(pyramid, ops, h.main); }
+    void journal_begin() { order_side_begin(journal, ops, h.main); }
+    void journal_end() { order_side_end(journal, ops, h.main); }
+    void journal_idle() { order_side_idle(journal, ops); }
+    void brush_idle() { order_side_idle(brush, ops); }
+    void brush_end() { order_side_end(brush, ops, h.main); }
+    void sweep_begin() { order_side_begin(brush, ops, h.main); }
     void light_writer_begins(int im) { order_image_writer_begins(img[im], ops, h.main); }
     void image_written(int im, bool fused, int fused_stop, int light_stop, int reader)
     { order_image_written(img[im], ops, h.main, reader, fused ? fused_stop : light_stop, h.ev_epoch); }
@@ -316,11 +425,14 @@ struct Protocol {
 
 // ---- the API calls: what the .hip files do around the ordering steps, with the kernels' accesses ------------------------------
 enum Call { RENDER0, RENDER1, RENDER2, PREPARE0, PREPARE1, PREPARE2, RENDER_LOCKED, SELECT, HEIGHTS_UPDATE, SET_STREAM, ASYNC_TOGGLE, DISPATCH_TOGGLE,
-            FUSION_TOGGLE, NOT_STAMPED_1ST, NOT_STAMPED_2ND, TIMING_ON, TIMING_OFF, SUBMIT_A_CROSS, SUBMIT_A_SAME, SUBMIT_B_CROSS, SUBMIT_B_SAME, N_CALLS };
+            FUSION_TOGGLE, NOT_STAMPED_1ST, NOT_STAMPED_2ND, TIMING_ON, TIMING_OFF, SUBMIT_A_CROSS, SUBMIT_A_SAME, SUBMIT_B_CROSS, SUBMIT_B_SAME,
+            EDIT_HOST, EDIT_DEVICE, EDIT_ALBEDO_DEVICE, BRUSH, UNDO_REDO, HISTORY_ENABLE, CAST_HOST, CAST_DEVICE, QUERY_DEVICE, SWEEP_STATE, N_CALLS };
 static const char* const kCallName[N_CALLS] = { "render(0)", "render(1)", "render(2)", "prepare(0)", "prepare(1)", "prepare(2)", "render(lock_view)", "select",
     "update_heights", "set_stream", "async_geometry^", "dispatch_events^", "frame_fusion^", "next launch not stamped", "launch after next not stamped",
     "timing_enable(2)", "timing_enable(0)/collect", "submit(image A, tone mapper on another stream)", "submit(image A, same stream)",
-    "submit(image B, another stream)", "submit(image B, same stream)" };
+    "submit(image B, another stream)", "submit(image B, same stream)",
+    "edit(heightmap, host pointer)", "edit(heightmap, device pointer)", "edit(albedo, device pointer)", "brush/erode", "undo/redo", "history_enable",
+    "cast_rays(host pointers)", "cast_rays(device pointers)", "query_heights(device pointers)", "sweep_state" };
 
 template <class P> struct Driver {
     World& w; Host& h; P& p;
@@ -333,7 +445,7 @@ template <class P> struct Driver {
             p.copy_selection(gi, sel, [&]() { w.kernel(gs); w.access(SEL0 + sel, false, gs); w.access(SEL0 + gi, true, gs); });
             h.have_selection[gi] = true;
         }
-        w.kernel(gs); w.access(SEL0 + gi, false, gs); w.access(GEO0 + gi, true, gs);
+        w.kernel(gs); w.access(SEL0 + gi, false, gs); w.access(HMAP, false, gs); w.access(GEO0 + gi, true, gs);      // (the vertex stage samples the heightmap)
         p.end_chain(gi);
     }
     void prepare(int view)                                    // vr_terrain_prepare
@@ -360,6 +472,7 @@ template <class P> struct Driver {
         if (keep_image >= 0) p.keep_writer_begins(keep_image);
         const int pass_stop = h.stop_of(h.stamped_launch(w));
         w.access(SEL0 + gi, false, h.main); w.access(GEO0 + gi, false, h.main);
+        w.access(HMAP, false, h.main); w.access(AMAP, false, h.main);                                                    // (both maps' tables)
         if (keep_image >= 0) w.access(IMG0 + keep_image, true, h.main);
         p.tile_pass_launched(gi, pass_stop);
         return pass_stop;
@@ -380,6 +493,90 @@ template <class P> struct Driver {
         p.heights_begin();
         w.kernel(h.main); w.access(HEIGHTS, true, h.main);
         p.heights_end();
+    }
+    // ---- the editing path.  Every kernel runs on the context's stream.  Not modelled: a refusal; a growth of the staging or of a
+    // brush buffer (its quiesce is the stream synchronise / the order_side_idle that the call makes anyway); a pending G-buffer frame.
+    template <class Write> void level0_write(int which, Write&& write)      // vr_derive_level0_write
+    {
+        const int s = h.main, map = which ? AMAP : HMAP;
+        p.maps_begin();
+        for (bool& b : h.prepared) b = false;
+        write();
+        w.kernel(s); w.access(map, true, s);                                // levels 1 .. and the tables
+        if (which == 0) { w.kernel(s); w.access(HMAP, false, s); w.access(HEIGHTS, true, s); }
+        if (which == 0 && h.pyramid_built) {
+            p.pyramid_begin(true);
+            w.kernel(s); w.access(HMAP, false, s); w.access(PYRAMID, true, s);
+            p.pyramid_end();
+        }
+        p.maps_end();
+    }
+    void capture(int which)                                   // vr_history_capture: every call is one committed step here
+    {
+        if (!h.history_on) return;
+        const int s = h.main;
+        p.journal_begin();
+        w.kernel(s); w.access(which ? AMAP : HMAP, false, s); w.access(JOURNAL, true, s);
+        p.journal_end();
+        h.undo.push_back(which); h.redo.clear();
+    }
+    void edit(int which, bool host_pointer)                   // vr_terrain_edit
+    {
+        const int s = h.main;
+        level0_write(which, [&]() {
+            capture(which);
+            if (host_pointer) { w.kernel(s); w.access(STAGE, true, s); }
+            w.kernel(s); if (host_pointer) w.access(STAGE, false, s); w.access(which ? AMAP : HMAP, true, s);
+        });
+        if (host_pointer) w.sync_stream(s);
+    }
+    void brush()                                              // vr_brush_call: vr_terrain_brush (a sculpting op), vr_terrain_erode, _erode_hydraulic
+    {
+        const int s = h.main;
+        p.brush_idle();
+        w.host_touch(BRUSHBUF);                               // the pinned dab list is written; a buffer that grows is freed
+        level0_write(0, [&]() {
+            capture(0);
+            w.kernel(s); w.access(BRUSHBUF, true, s);         // the upload, the snapshot, the block's planes
+            w.kernel(s); w.access(BRUSHBUF, false, s); w.access(HMAP, true, s);
+            p.brush_end();
+        });
+        h.sweep_left = true;
+    }
+    void undo_redo()                                          // history_apply: undo if there is a step to undo, else redo
+    {
+        const bool undo = !h.undo.empty();
+        if (!undo && h.redo.empty()) return;                  // queues nothing
+        std::vector<int>& from = undo ? h.undo : h.redo;
+        const int which = from.back(), s = h.main;
+        from.pop_back(); (undo ? h.redo : h.undo).push_back(which);
+        level0_write(which, [&]() {
+            p.journal_begin();
+            w.kernel(s); w.access(JOURNAL, true, s); w.access(which ? AMAP : HMAP, true, s);
+            p.journal_end();
+        });
+    }
+    void history_enable()                                     // vr_terrain_history_enable with another budget: a new arena replaces the old one
+    {
+        if (h.history_on) { p.journal_idle(); w.host_touch(JOURNAL); }
+        h.history_on = true; h.undo.clear(); h.redo.clear();
+    }
+    void cast(bool host_pointers)                             // vr_terrain_cast_rays; the first one builds the pyramid (ensure_pyramid)
+    {
+        const int s = h.main;
+        if (h.pyramid_built) p.pyramid_begin(false);
+        else { w.kernel(s); w.access(HMAP, false, s); w.access(PYRAMID, true, s); p.pyramid_end(); h.pyramid_built = true; }
+        if (host_pointers) { w.kernel(s); w.access(STAGE, true, s); }
+        w.kernel(s); w.access(HMAP, false, s); w.access(PYRAMID, false, s);
+        if (host_pointers) { w.access(STAGE, true, s); w.kernel(s); w.access(STAGE, false, s); w.sync_stream(s); }
+    }
+    void query_device() { w.kernel(h.main); w.access(HMAP, false, h.main); }      // vr_terrain_query_heights, nothing waited for
+    void sweep_state()                                        // vr_debug_terrain_sweep_state
+    {
+        if (!h.sweep_left) return;
+        p.sweep_begin();
+        w.kernel(h.main); w.access(BRUSHBUF, false, h.main);
+        w.sync_stream(h.main);
     }
     void timing(int level)                                    // vr_timing_enable / vr_timing_collect (vr_host.hip:216-218, timing_reset)
     {
@@ -428,6 +625,16 @@ template <class P> struct Driver {
         case SUBMIT_A_SAME: submit(0, false); break;
         case SUBMIT_B_CROSS: submit(1, true); break;
         case SUBMIT_B_SAME: submit(1, false); break;
+        case EDIT_HOST: edit(0, true); break;
+        case EDIT_DEVICE: edit(0, false); break;
+        case EDIT_ALBEDO_DEVICE: edit(1, false); break;
+        case BRUSH: brush(); break;
+        case UNDO_REDO: undo_redo(); break;
+        case HISTORY_ENABLE: history_enable(); break;
+        case CAST_HOST: cast(true); break;
+        case CAST_DEVICE: cast(false); break;
+        case QUERY_DEVICE: query_device(); break;
+        case SWEEP_STATE: sweep_state(); break;
         }
         if (h.launched) h.not_stamped = 0;                    // the marker covers the next call that launches, no more
     }
@@ -454,19 +661,19 @@ static std::string show(const int* seq, int n) { std::string s; for (int i = 0; 
 static std::string show(const std::vector<Op>& t)
 {
     std::string s;
-    for (const Op& o : t) { char b[64]; snprintf(b, sizeof(b), " %s(%s,e%d)", o.wait ? "wait" : "record", kStreamName[o.stream], o.event); s += b; }
+    for (const Op& o : t) { char b[64]; snprintf(b, sizeof(b), " %s(%s,e%d)", o.wait == 2 ? "sync" : o.wait ? "wait" : "record", kStreamName[o.stream], o.event); s += b; }
     return s;
 }
 
 // ---- (c) the sequences ------------------------------------------------------------------------------------
 constexpr int kExhaustive = 4, kRandom = 200000, kRandomMax = 14;
-static const Intended kPlain = { false, false, false }, kAll = { true, true, true };
+static const Intended kPlain = { false, false, false, false }, kAll = { true, true, true, true };
 static long sequences = 0, failures = 0;
 // the parent's own unordered pairs, by the one intended difference that repairs them
 struct Finding { const char* name; Intended only; long count; int shortest[kRandomMax], shortest_n; std::string pair; };
 static Finding findings[2] = {
-    { "vr_frame_submit took ctx->last_stop for a lighting pass that was not stamped", { true, false, false }, 0, {}, 0, "" },
-    { "the node-height update did not wait for chains that still read the heights", { false, true, false }, 0, {}, 0, "" },
+    { "vr_frame_submit took ctx->last_stop for a lighting pass that was not stamped", { true, false, false, false }, 0, {}, 0, "" },
+    { "the node-height update did not wait for chains that still read the heights", { false, true, false, false }, 0, {}, 0, "" },
 };
 static long drop_reported[N_SITES];
 
@@ -488,7 +695,7 @@ static void check(const int* seq, int n)
             explained = true; f.count++;
             if (!f.shortest_n || n < f.shortest_n) { f.shortest_n = n; memcpy(f.shortest, seq, n * sizeof(int)); f.pair = plain.first; }
         }
-        if (!explained && run_parent(seq, n, { true, true, false }, 0).unordered) {
+        if (!explained && run_parent(seq, n, { true, true, false, false }, 0).unordered) {
             if (failures++ < 10) printf("FAIL (b) parent, not repaired by the intended differences: %s\n    %s\n", show(seq, n).c_str(), plain.first.c_str());
         }
     }
@@ -496,7 +703,9 @@ static void check(const int* seq, int n)
 static void check_drops(const int* seq, int n)
 {
     sequences++;
-    for (int site = 1; site < N_SITES; site++) if (run_parent(seq, n, kAll, site).unordered) drop_reported[site]++;
+    // (the dead wait that Intended::sweep_dead_wait drops exists only with that switch off)
+    static const Intended kWithDead = { true, true, true, false };
+    for (int site = 1; site < N_SITES; site++) if (run_parent(seq, n, site == W_SWEEP_DEAD ? kWithDead : kAll, site).unordered) drop_reported[site]++;
 }
 
 template <class F> static void all_sequences(int longest, long random, F&& f)
@@ -532,10 +741,11 @@ int main(int argc, char** argv)
         printf("%ld sequences, the transcription (intended differences on) less one wait site at a time:\n", sequences);
         int reported = 0, bad = 0;
         for (int site = 1; site < N_SITES; site++) {
-            printf("  %-60s %s (%ld sequences)\n", kSiteName[site], drop_reported[site] ? "reported" : "NOT reported", drop_reported[site]);
+            printf("  %-72s %s (%ld sequences)\n", kSiteName[site], drop_reported[site] ? "reported" : "NOT reported", drop_reported[site]);
+            if (!drop_reported[site] && dead_reason(site)) printf("      orders nothing: %s\n", dead_reason(site));
             reported += drop_reported[site] != 0;
-            // the start hint orders nothing: it only says when a prepared chain becomes runnable.  Every other wait is needed somewhere.
-            bad += (drop_reported[site] != 0) == (site == W_PREP_HINT);
+            // every wait is needed somewhere, or is named with the reason it orders nothing
+            bad += (drop_reported[site] != 0) == (dead_reason(site) != nullptr);
         }
         printf("%d of %d wait sites reported, %d unexpected\n", reported, N_SITES - 1, bad);
         return bad ? 1 : 0;
@@ -550,6 +760,7 @@ int main(int argc, char** argv)
         printf("finding: %s: %ld sequences; shortest: %s\n    %s\n", f.name, f.count, show(f.shortest, f.shortest_n).c_str(), f.pair.c_str());
         if (!f.count) { failures++; printf("FAIL: the finding was not seen\n"); }
     }
+    printf("dead wait dropped: vr_debug_terrain_sweep_state waits for the erosion only where it ran on another stream (Intended::sweep_dead_wait)\n");
     printf("permitted reorder: vr_terrain_select queues the main-dependency wait last, as launch_geometry does (Intended::common_order)\n");
     printf("%ld sequences (all up to %d calls of %d, %d random up to %d), %ld failures\n", sequences, kExhaustive, (int)N_CALLS, kRandom, kRandomMax, failures);
     return failures ? 1 : 0;

@@ -192,22 +192,27 @@ def test_raster_plan_matches_the_transcribed_decisions_and_invariants(tmp_path):
 
 def test_devbuf_grow_is_all_or_nothing_at_every_failure_position(tmp_path):
     """vr_devbuf.h compiles without HIP; a single grow and group grows of 1..15 buffers keep every pointer, capacity and live
-    block on a failure at any allocation (or a refusing quiesce) and free each old block once, behind quiesce, on success
+    block on a failure at any allocation (or a refusing quiesce) and free each old block once, behind quiesce, on success; the
+    reserve reaches the doubling policy's capacity, or exactly the request where the doubled size is refused
     (tests/host/devbuf_check.cpp)."""
     exe = build_host_check(tmp_path, "devbuf_check")
     r = run_host_check(exe)
-    assert "1152 cases" in r.stdout, r.stdout[-400:]            # single: 3 x 6 x 2 x 2; groups: 4 patterns x 2 x (N + 1), N = 1..15
+    # single: 3 x 6 x 2 x 2; groups: 4 patterns x 2 x (N + 1), N = 1..15; reserve: 4 x 5 x 2 x 3 allocators = 120
+    assert "1272 cases" in r.stdout, r.stdout[-400:]
 
 
 def test_stream_order_matches_the_transcribed_protocol_and_the_happens_before_model(tmp_path):
     """vr_order.h compiles without HIP.  Over every sequence of up to four API calls and a fixed sample of longer ones
     (tests/host/order_check.cpp) the protocol queues the records and waits the ordering code it replaced queued, apart from the
-    intended differences the program names, and no two conflicting accesses to a geometry set, the node heights or an HDR image
-    are left unordered by the streams' vector clocks; a transcription that loses any one wait but the start hint's is reported."""
+    intended differences the program names, and no two conflicting accesses to a geometry set, the node heights, an HDR image,
+    a map, the query pyramid, the journal's arena, the brush buffers or the query staging are left unordered by the streams'
+    vector clocks (or, where the host frees or rewrites memory, by what the host waited for); a transcription that loses any one
+    wait is reported, but for the seven the program names with the reason each orders nothing.  The ten calls of the editing
+    path run to the same exhaustive depth as the others: the program takes 2.5 s where the parent's took 1.3 s."""
     exe = build_host_check(tmp_path, "order_check")
     r = run_host_check(exe)
-    assert "404204 sequences" in r.stdout, r.stdout[-400:]      # 21 + 21^2 + 21^3 + 21^4 of 21 calls, 200000 random
-    run_host_check(exe, "--drop-each", expect="16 of 17 wait sites reported")
+    assert "1154304 sequences" in r.stdout, r.stdout[-400:]     # 31 + 31^2 + 31^3 + 31^4 of 31 calls (21 + the editing path's 10), 200000 random
+    run_host_check(exe, "--drop-each", expect="19 of 26 wait sites reported")      # 17 + 9 sites; 16 + 3 reported
 
 
 def test_scratch_policy_matches_the_transcribed_code_and_its_invariants(tmp_path):

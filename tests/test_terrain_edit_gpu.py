@@ -389,3 +389,92 @@ def test_refusals_leave_the_terrain_alone(scenes):
         assert np.array_equal(a.download_mip(wh, l), want), (wh, l)
     _assert_frames_equal(_render(sc, a, 0), frame, "after the refusals")
     a.close()
+
+
+def test_side_resources_follow_the_context_across_two_streams(scenes, gpu_ctx):
+    """The query pyramid, the journal and the brush buffers (vr_order.h's side resources) with the context moved between two streams
+    and the host paying only what vr_context_set_stream asks of it - the new stream waits for the old one, nothing is synchronised.
+    256 rays with host pointers on stream A (which builds the pyramid); on B a RAISE stroke with history on, then the rays through
+    device pointers; back on A an undo, the rays again; on B a thermal erosion, and its planes read back on A.  The hits after each
+    step are those of a fresh terrain created from the model's map for that step, byte for byte, level 0 is the model's, and the
+    erosion's planes are the model's.  Checked first, on the references alone: the stroke changes at least 30 texels and at least 10
+    rays hit another cell (or stop hitting) because of it - else a stale pyramid or map could not show."""
+    import torch
+    from tests import brush_model as bm
+    from tests import erosion_state as es
+    from tests.test_terrain_brush_gpu import assert_bytes, five_dabs, level0, world_of
+    from tests.test_terrain_erosion_state_gpu import ITER, assert_state, model
+    sc = scenes["fast64"]
+    S, mh = world_of(sc), sc.mh
+    stroke = five_dabs(sc.hm.shape, S, bm.RAISE)
+    m1, _ = bm.stroke(sc.hm, bm.RAISE, stroke, S)
+    mask = es.five_dabs(sc.hm.shape, S)
+    eroded = model("thermal", sc.hm, mask, S, ITER, es.PARAMS["thermal"])
+    assert (m1 != sc.hm).sum() >= 30
+
+    def fresh_hits(hm, rays):
+        b = sc.terrain(hm, sc.al, cast=False, render=False)
+        try:
+            return b.cast_ray_array(rays, mh)
+        finally:
+            b.close()
+
+    b0 = sc.terrain(sc.hm, sc.al, cast=False, render=False)
+    surf = Surface64(b0.download_mip("height", 0), b0.download_mip("height", 1), sc.world, mh)
+    b0.close()
+    o, d, tm = qc.make_rays(surf, sc.world, n=256)
+    rays = np.zeros(256, vr.RAY_DTYPE)
+    rays["origin"], rays["dir"], rays["t_max"] = o, d, tm
+    ref0, ref1, ref2 = fresh_hits(sc.hm, rays), fresh_hits(m1, rays), fresh_hits(eroded["bytes"], rays)
+
+    def cells(hits):
+        xz = np.floor((hits["position"][:, [0, 2]].astype(np.float64) / S + 0.5) * sc.hm.shape[1]).astype(np.int64)
+        return np.where((hits["status"] == capi.VR_RAY_HIT)[:, None], xz, -1)
+
+    moved = (cells(ref0) != cells(ref1)).any(1).sum()
+    print(f"stroke: {(m1 != sc.hm).sum()} texels changed, {moved} of 256 rays hit another cell")
+    assert moved >= 10, moved
+
+    dev = f"cuda:{gpu_ctx.device}"
+    d_rays = torch.from_numpy(rays.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_hits = [torch.zeros(256 * 32, dtype=torch.uint8, device=dev) for _ in range(2)]
+    a = sc.terrain(sc.hm, sc.al, cast=False, render=False)
+    a.EnableHistory(1 << 20)
+    gpu_ctx.synchronize()
+    torch.cuda.synchronize()
+    A, B = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def cast_on_device(out):
+        capi.check(gpu_ctx.lib.vr_terrain_cast_rays(a.handle, C.c_void_p(d_rays.data_ptr()), 256, mh, C.c_void_p(out.data_ptr()), 1), "vr_terrain_cast_rays")
+
+    try:
+        gpu_ctx.set_stream(A.cuda_stream)
+        assert a.cast_ray_array(rays, mh).tobytes() == ref0.tobytes(), "1. host pointers on A (the pyramid's build)"
+        B.wait_stream(A)
+        gpu_ctx.set_stream(B.cuda_stream)
+        a.Brush("raise", stroke)
+        a.CommitHistory()
+        cast_on_device(d_hits[0])
+        A.wait_stream(B)
+        gpu_ctx.set_stream(A.cuda_stream)
+        assert a.Undo()
+        cast_on_device(d_hits[1])
+        gpu_ctx.synchronize()
+        assert d_hits[0].cpu().numpy().tobytes() == ref1.tobytes(), "4. device pointers on B behind the stroke"
+        assert d_hits[1].cpu().numpy().tobytes() == ref0.tobytes(), "7. device pointers on A behind the undo"
+        assert a.cast_ray_array(rays, mh).tobytes() == ref0.tobytes(), "7. host pointers on A behind the undo"
+        assert_bytes(level0(a, "height"), sc.hm, "level 0 behind the undo")
+        assert a.Redo()
+        assert_bytes(level0(a, "height"), m1, "level 0 behind the redo")
+        assert a.Undo()
+        B.wait_stream(A)
+        gpu_ctx.set_stream(B.cuda_stream)
+        assert a.Erode(mask, ITER, *es.PARAMS["thermal"]) == eroded["rect"]
+        A.wait_stream(B)
+        gpu_ctx.set_stream(A.cuda_stream)
+        assert_state(a, eroded, "8. sweep_state on A behind an erode on B")
+        assert a.cast_ray_array(rays, mh).tobytes() == ref2.tobytes(), "8. host pointers on A behind the erode"
+    finally:
+        torch.cuda.synchronize()
+        gpu_ctx.set_stream(0)
+        a.close()

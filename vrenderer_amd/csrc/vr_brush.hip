@@ -105,28 +105,23 @@ __global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, i
 // ---------------------------------------------------------------------------------------
 void vr_brush_release(vr_terrain* t)
 {
-    if (t->ev_brush) { (void)hipEventSynchronize(t->ev_brush); (void)hipEventDestroy(t->ev_brush); t->ev_brush = nullptr; }
+    (void)vr_brush_consumed(t);
+    if (t->ord_brush.ev) (void)hipEventDestroy(t->ord_brush.ev);
+    t->ord_brush = VrOrderSide();
     if (t->h_brush_dabs) { (void)hipHostFree(t->h_brush_dabs); t->h_brush_dabs = nullptr; }
     (void)hipFree(t->d_brush_dabs); t->d_brush_dabs = nullptr;
     (void)hipFree(t->d_brush_snap); t->d_brush_snap = nullptr; t->brush_snap_bytes = 0;
     (void)hipFree(t->d_erode); t->d_erode = nullptr; t->erode_bytes = 0; t->erode_last = {};
-    t->brush_pending = false;
 }
 
 // the previous stroke's kernel has passed: the pinned dabs, their device copy and the snapshot are free again
-int vr_brush_consumed(vr_terrain* t)
-{
-    if (!t->brush_pending) return VR_OK;
-    VR_HIP(hipEventSynchronize(t->ev_brush));
-    t->brush_pending = false;
-    return VR_OK;
-}
+int vr_brush_consumed(vr_terrain* t) { return order_side_idle(t->ord_brush, VrOrderOps()); }
 
 // Everything a stroke needs, before anything is launched: a refusal leaves the terrain as it was.
 int vr_brush_reserve(vr_terrain* t, size_t snap_bytes)
 {
     constexpr size_t dab_bytes = (size_t)VR_MAX_BRUSH_DABS * sizeof(BrushDab);
-    if (!t->ev_brush) VR_HIP(hipEventCreateWithFlags(&t->ev_brush, hipEventDisableTiming));
+    if (!t->ord_brush.ev) VR_HIP(hipEventCreateWithFlags(&t->ord_brush.ev, hipEventDisableTiming));
     if (!t->h_brush_dabs) {
         const hipError_t e = hipHostMalloc((void**)&t->h_brush_dabs, dab_bytes, hipHostMallocDefault);
         if (e != hipSuccess) { (void)hipGetLastError(); t->h_brush_dabs = nullptr; vr_set_error("terrain brush: %zu bytes of pinned memory: %s", dab_bytes, hipGetErrorString(e)); return VR_ERR_OUT_OF_MEMORY; }
@@ -141,18 +136,11 @@ int vr_brush_reserve(vr_terrain* t, size_t snap_bytes)
     return rc;
 }
 
-// A buffer whose one reader runs in front of ev_brush holds `bytes`: grown from 64 KiB by doubling - to exactly `bytes` where the
-// doubled size does not fit - and the old block freed behind vr_brush_consumed.  A refusal leaves the terrain as it was; the
-// caller words VR_ERR_OUT_OF_MEMORY's message.
+// A buffer whose one reader runs in front of ord_brush's event holds `bytes` (vr_reserve), the old block freed behind
+// vr_brush_consumed.  A refusal leaves the terrain as it was; the caller words VR_ERR_OUT_OF_MEMORY's message.
 int vr_brush_grow(vr_terrain* t, void** ptr, size_t* capacity, size_t bytes)
 {
-    if (bytes <= *capacity) return VR_OK;
-    size_t want = *capacity ? *capacity * 2 : (size_t)1 << 16;
-    while (want < bytes) want *= 2;
-    const auto idle = [t]() -> int { return vr_brush_consumed(t); };
-    int rc = vr_grow(ptr, capacity, want, idle);
-    if (rc == VR_ERR_OUT_OF_MEMORY && want > bytes) rc = vr_grow(ptr, capacity, bytes, idle);
-    return rc;
+    return vr_reserve(ptr, capacity, bytes, [t]() -> int { return vr_brush_consumed(t); });
 }
 
 // the dab checks of a stroke of `op` (erosion's strengths are opacities: it passes VR_BRUSH_FLATTEN)

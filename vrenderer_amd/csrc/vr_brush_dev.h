@@ -68,7 +68,7 @@ __device__ __forceinline__ float brush_tile_mask(const BrushDab* __restrict__ da
 // A stroke's or an erosion's path behind its entry point's own argument checks: the dabs checked (as a stroke of `op`) and prepared
 // for map `which`; nothing at all for an empty list; then reserve(rectangle) - everything the launches need, before anything is
 // launched - the one wait on the host, the pinned list, and inside vr_derive_level0_write the history capture, the upload,
-// launch(stream, rectangle, dabs) and the event the next call waits for.
+// launch(stream, rectangle, dabs) and order_side_end of the brush's buffers, whose order_side_idle the next call takes.
 template <class Reserve, class Launch>
 int vr_brush_call(vr_terrain* t, int which, const vr_brush_dab* dabs, uint32_t n, int op, int32_t out_rect[4], Reserve&& reserve, Launch&& launch)
 {
@@ -89,9 +89,7 @@ int vr_brush_call(vr_terrain* t, int which, const vr_brush_dab* dabs, uint32_t n
         VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)nd * sizeof(BrushDab), hipMemcpyHostToDevice, s));
         { const int lrc = launch(s, dirty, nd); if (lrc) return lrc; }
         VR_HIP(hipGetLastError());
-        VR_HIP(hipEventRecord(t->ev_brush, s));
-        t->brush_pending = true;
-        return VR_OK;
+        return order_side_end(t->ord_brush, VrOrderOps(), s);
     });
     if (rc) return rc;
     if (out_rect) { out_rect[0] = dirty.x0; out_rect[1] = dirty.y0; out_rect[2] = dirty.x1 - dirty.x0; out_rect[3] = dirty.y1 - dirty.y0; }

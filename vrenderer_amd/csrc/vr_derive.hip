@@ -245,7 +245,7 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
         VR_HIP(hipGetLastError());
     }
     if (which == 0 && t->d_pyramid) {                       // a ray cast has built it
-        if (s != t->pyramid_stream) VR_HIP(hipStreamWaitEvent(s, t->ev_pyramid, 0));     // the host changed the context's stream since the build
+        { const int rc = order_side_begin(t->ord_pyramid, VrOrderOps(), s); if (rc) return rc; }
         const DirtyRect l1 = tex.levels > 1 ? dirty_rect(dirty_mip_next(dirty_x(dirty), dirty_level_size(tex.w0, 1)), dirty_mip_next(dirty_y(dirty), dirty_level_size(tex.h0, 1)))
                                             : dirty;
         {
@@ -253,8 +253,7 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
             vr_derive_pyramid(tex, vr_pyramid_desc(t, nullptr), t->d_pyramid, dirty, l1, s);
         }
         VR_HIP(hipGetLastError());
-        VR_HIP(hipEventRecord(t->ev_pyramid, s));
-        t->pyramid_stream = s;
+        { const int rc = order_side_end(t->ord_pyramid, VrOrderOps(), s); if (rc) return rc; }
     }
     // every set's next chain runs behind the write
     { const int rc = order_terrain_changed(t->ord, ord_sets, VrOrderOps(), s); if (rc) return rc; }

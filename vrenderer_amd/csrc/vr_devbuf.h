@@ -8,7 +8,7 @@
 //                                               stream synchronisations); called at most once, in front of the first release
 //                                               and only if there is an old block; its non-zero result ends the call
 //
-// Both return 0, kDevBufNoMemory, or what quiesce returned; unless they return 0, every pointer and capacity is what it was
+// All three return 0, kDevBufNoMemory, or what quiesce returned; unless they return 0, every pointer and capacity is what it was
 // and no block has been gained or lost.  During a growth the old and the new blocks exist side by side.
 #pragma once
 
@@ -47,5 +47,18 @@ int vr_devbuf_grow(void** ptr, size_t* capacity, size_t bytes, Alloc&& alloc, Re
     const size_t want[1] = { bytes };
     const int rc = vr_devbuf_grow_group(slot, want, alloc, release, quiesce);
     if (!rc) *capacity = bytes;
+    return rc;
+}
+
+// One buffer that only ever grows, to at least `bytes`: from 64 KiB by doubling, and to exactly `bytes` where the allocator refuses
+// the doubled size.  (quiesce runs at most once: a refused allocation never reaches it.)
+template <class Alloc, class Release, class Quiesce>
+int vr_devbuf_reserve(void** ptr, size_t* capacity, size_t bytes, Alloc&& alloc, Release&& release, Quiesce&& quiesce)
+{
+    if (bytes <= *capacity) return 0;
+    size_t want = *capacity ? *capacity * 2 : (size_t)1 << 16;
+    while (want < bytes) want *= 2;
+    int rc = vr_devbuf_grow(ptr, capacity, want, alloc, release, quiesce);
+    if (rc == kDevBufNoMemory && want > bytes) rc = vr_devbuf_grow(ptr, capacity, bytes, alloc, release, quiesce);
     return rc;
 }

@@ -284,7 +284,7 @@ extern "C" VR_API int vr_debug_terrain_sweep_state(vr_terrain* t, int32_t out_re
     if (out == nullptr || rec.fields == 0) return VR_OK;
     VR_HIP(hipSetDevice(t->ctx->device));
     hipStream_t s = t->ctx->stream;
-    if (t->ev_brush) VR_HIP(hipStreamWaitEvent(s, t->ev_brush, 0));
+    { const int rc = order_side_begin(t->ord_brush, VrOrderOps(), s); if (rc) return rc; }
     const float* const d_mask = (const float*)t->d_erode;
     const float* const d_set = d_mask + (size_t)(1 + rec.set * rec.fields) * rec.plane;
     VR_HIP(hipMemcpyAsync(out, d_mask, cells * sizeof(float), hipMemcpyDeviceToHost, s));

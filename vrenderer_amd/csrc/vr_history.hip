@@ -72,12 +72,11 @@ static HistoryMove history_move_of(const vr_terrain* t, const HistoryRecord& e)
 // one lane per chunk: at most 2^26 texels x 4 bytes / 16 + one chunk per row = 2^24 + 2^14 lanes, 65600 workgroups
 static dim3 history_grid(const HistoryMove& m) { return dim3((unsigned)(((uint64_t)m.rows * m.chunks + 255) / 256)); }
 
-// One journal kernel on `s`: behind the journal's last kernel if that ran on another stream (the rule of ev_pyramid /
-// pyramid_stream), and the event moved behind this one.
+// One journal kernel on `s`, between the journal's order_side_begin and order_side_end.
 template <bool SWAP>
 static int history_queue(vr_terrain* t, const HistoryRecord& e, hipStream_t s)
 {
-    if (t->history_queued && s != t->history_stream) VR_HIP(hipStreamWaitEvent(s, t->ev_history, 0));
+    { const int rc = order_side_begin(t->ord_journal, VrOrderOps(), s); if (rc) return rc; }
     const HistoryMove m = history_move_of(t, e);
     const dim3 grid = history_grid(m);
     if (SWAP) {
@@ -88,9 +87,7 @@ static int history_queue(vr_terrain* t, const HistoryRecord& e, hipStream_t s)
         else hipLaunchKernelGGL(k_history_capture<uint32_t>, grid, dim3(256), 0, s, m);
     }
     VR_HIP(hipGetLastError());
-    VR_HIP(hipEventRecord(t->ev_history, s));
-    t->history_stream = s; t->history_queued = true;
-    return VR_OK;
+    return order_side_end(t->ord_journal, VrOrderOps(), s);
 }
 
 int vr_history_capture(vr_terrain* t, int which, const DirtyRect& dirty, hipStream_t s)
@@ -100,18 +97,11 @@ int vr_history_capture(vr_terrain* t, int which, const DirtyRect& dirty, hipStre
     return history_queue<false>(t, e, s);
 }
 
-// nothing queued can still touch the arena
-static int history_idle(vr_terrain* t)
-{
-    if (t->history_queued) VR_HIP(hipEventSynchronize(t->ev_history));
-    t->history_queued = false;
-    return VR_OK;
-}
-
 void vr_history_release(vr_terrain* t)
 {
-    (void)history_idle(t);
-    if (t->ev_history) { (void)hipEventDestroy(t->ev_history); t->ev_history = nullptr; }
+    (void)order_side_idle(t->ord_journal, VrOrderOps());
+    if (t->ord_journal.ev) (void)hipEventDestroy(t->ord_journal.ev);
+    t->ord_journal = VrOrderSide();
     (void)hipFree(t->d_history); t->d_history = nullptr;
     history_reset(t->history, 0, nullptr, 0);
 }
@@ -127,10 +117,10 @@ extern "C" VR_API int vr_terrain_history_enable(vr_terrain* t, size_t budget_byt
     // everything the journal will ever need, before the old arena goes: the record table, the event, then the arena itself
     try { t->history_table.resize(kHistoryMaxRecords); }
     catch (const std::bad_alloc&) { vr_set_error("terrain history: %zu bytes for the record table", (size_t)kHistoryMaxRecords * sizeof(HistoryRecord)); return VR_ERR_OUT_OF_MEMORY; }
-    if (!t->ev_history) VR_HIP(hipEventCreateWithFlags(&t->ev_history, hipEventDisableTiming));
+    if (!t->ord_journal.ev) VR_HIP(hipEventCreateWithFlags(&t->ord_journal.ev, hipEventDisableTiming));
     void** const slot[1] = { (void**)&t->d_history };
     const size_t want[1] = { budget_bytes };
-    const int rc = vr_grow_group(slot, want, [t]() -> int { return history_idle(t); });
+    const int rc = vr_grow_group(slot, want, [t]() -> int { return order_side_idle(t->ord_journal, VrOrderOps()); });
     if (rc) { if (rc == VR_ERR_OUT_OF_MEMORY) vr_set_error("terrain history: %zu bytes for the arena", budget_bytes); return rc; }
     history_reset(t->history, budget_bytes, t->history_table.data(), kHistoryMaxRecords);
     return VR_OK;

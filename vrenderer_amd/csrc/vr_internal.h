@@ -45,14 +45,19 @@ template <class T, class Quiesce> int vr_grow(T** ptr, size_t* capacity_bytes, s
 { return vr_grow_code(vr_devbuf_grow((void**)ptr, capacity_bytes, bytes, vr_dev_alloc, vr_dev_free, quiesce)); }
 template <size_t N, class Quiesce> int vr_grow_group(void** const (&slot)[N], const size_t (&bytes)[N], Quiesce&& quiesce)
 { return vr_grow_code(vr_devbuf_grow_group(slot, bytes, vr_dev_alloc, vr_dev_free, quiesce)); }
+// a buffer that follows the largest request so far: from 64 KiB by doubling (vr_devbuf_reserve)
+template <class T, class Quiesce> int vr_reserve(T** ptr, size_t* capacity_bytes, size_t bytes, Quiesce&& quiesce)
+{ return vr_grow_code(vr_devbuf_reserve((void**)ptr, capacity_bytes, bytes, vr_dev_alloc, vr_dev_free, quiesce)); }
 
 // ---- cross-stream order (vr_order.h) -----------------------------------------------------
-// The protocol's two operations on HIP's streams and events; its steps return what these return.
+// The protocol's three operations on HIP's streams and events; its steps return what these return.
 struct VrOrderOps {
     int record(hipEvent_t e, hipStream_t s) const { VR_HIP(hipEventRecord(e, s)); return VR_OK; }
     int wait(hipStream_t s, hipEvent_t e) const { VR_HIP(hipStreamWaitEvent(s, e, 0)); return VR_OK; }
+    int sync(hipEvent_t e) const { VR_HIP(hipEventSynchronize(e)); return VR_OK; }
 };
 using VrOrderSet = OrderSet<hipStream_t, hipEvent_t>;
+using VrOrderSide = OrderSide<hipStream_t, hipEvent_t>;
 
 // ---- geometry constants -----------------------------------------------------------
 constexpr int kGrid = 32;                    // GRID_SIZE (TerrainPass.h:28)
@@ -384,44 +389,43 @@ struct vr_terrain {
     // stream and overlap whatever the context's stream is doing (the lighting pass of the previous frame,
     // or - after vr_terrain_prepare - its tile pass); the tile pass on the context's stream waits for them.
     OrderTerrain<hipEvent_t> ord;          // vr_order.h
+    // The three side resources (vr_order.h: order_side_begin / _end / _idle) - the only ordering state of the pyramid, of the
+    // journal's arena and of the brush's and the erosions' buffers.  Each event is made with its resource and destroyed with it.
+    VrOrderSide ord_pyramid, ord_journal, ord_brush;
     // Terrain queries (vr_query.hip): the min / max pyramid over the surface, built by the first ray cast on the context's stream and
     // kept until vr_terrain_destroy, and the staging memory of the host-pointer mode (grown by doubling).
     uchar2* d_pyramid = nullptr; uint64_t pyramid_bytes = 0;
-    hipEvent_t ev_pyramid = nullptr; hipStream_t pyramid_stream = nullptr;     // the build; a cast on another stream waits for it
     void* d_query_stage = nullptr; size_t query_stage_bytes = 0;
     // Brush strokes (vr_brush.hip): the prepared dabs of the latest stroke in pinned host memory and their copy on the device
-    // (VR_MAX_BRUSH_DABS each, from the first stroke on), SMOOTH's snapshot of the map (grown to the largest rectangle so far),
-    // and the event behind the latest stroke's kernel - the one reader of all three.  vr_terrain_brush synchronises nothing, so
-    // this memory is its own and not d_query_stage, whose users leave it idle when they return: the next stroke waits on the
-    // host for the event where the previous stroke has not been consumed yet, whichever stream that one ran on.
+    // (VR_MAX_BRUSH_DABS each, from the first stroke on) and SMOOTH's snapshot of the map (grown to the largest rectangle so far);
+    // ord_brush's event lies behind the latest stroke's kernel - the one reader of all three.  vr_terrain_brush synchronises
+    // nothing, so this memory is its own and not d_query_stage, whose users leave it idle when they return: the next stroke
+    // takes order_side_idle where the previous stroke has not been consumed yet, whichever stream that one ran on.
     std::vector<BrushDab> brush_prepared;       // a stroke's dabs as they are prepared, before anything touches the device
     BrushDab* h_brush_dabs = nullptr; BrushDab* d_brush_dabs = nullptr;
     void* d_brush_snap = nullptr; size_t brush_snap_bytes = 0;
-    hipEvent_t ev_brush = nullptr; bool brush_pending = false;
     // Erosion, thermal and hydraulic (vr_erode.hip): one block of fp32 planes - the mask and two sets of the model's state fields,
-    // three planes or seven - of the largest call so far.  Its one reader is the erosion's kernels, which run in front of the same
-    // event: an erosion shares the brush's dab buffers and its consumed-event protocol, so strokes and erosions of one terrain
+    // three planes or seven - of the largest call so far.  Its one reader is the erosion's kernels, which run in front of
+    // ord_brush's event: an erosion shares the brush's dab buffers and its side resource, so strokes and erosions of one terrain
     // order against each other, and one erosion against the next one's growth of the block, whichever stream they ran on.
     void* d_erode = nullptr; size_t erode_bytes = 0;
     // What the last erosion call that launched left in the block, for vr_debug_terrain_sweep_state (host side only): the rectangle,
     // the model's field count (0: no record), the floats from one plane to the next and which of the two sets holds the final state.
     struct ErodeRecord { int x = 0, y = 0, w = 0, h = 0, fields = 0, set = 0; size_t plane = 0; } erode_last;
     // History (vr_history.hip): the journal's bookkeeping (vr_history.h) over a table of kHistoryMaxRecords records and one device
-    // arena, both from vr_terrain_history_enable on, and the event behind the latest journal kernel with the stream it ran on - a
-    // journal kernel on another stream waits for it (the rule of ev_pyramid / pyramid_stream).
+    // arena, both from vr_terrain_history_enable on; ord_journal's event lies behind the latest journal kernel.
     vr_gbuffer* pending_target = nullptr;       // the (at most one) G-buffer whose colour planes wait for a frame of this terrain
     HistoryState history;
     std::vector<HistoryRecord> history_table;
     uint8_t* d_history = nullptr;
-    hipEvent_t ev_history = nullptr; hipStream_t history_stream = nullptr; bool history_queued = false;
 };
 void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
 void vr_brush_release(vr_terrain* t);      // the brush's and the erosions' memory and their event (vr_brush.hip)
 // What vr_terrain_brush, vr_terrain_erode and vr_terrain_erode_hydraulic share (vr_brush.hip).  check_dabs: the dab refusals of a stroke of `op` (an opacity
 // op for the erosion).  prepare_dabs: the dabs that meet the map `tex`, in order, into t->brush_prepared; returns the hull of their
 // spans.  reserve: the event, the pinned and the device dab list and `snap_bytes` of snapshot, before anything is launched.
-// grow: one of the buffers read in front of ev_brush to `bytes`.  consumed: the one wait on the host - the kernels in front of
-// the latest record of ev_brush have passed.  (vr_brush_call, the whole path from the dab checks to the recorded event around the
+// grow: one of the buffers read in front of ord_brush's event to `bytes` (vr_reserve).  consumed: order_side_idle(ord_brush), the
+// one wait on the host.  (vr_brush_call, the whole path from the dab checks to the recorded event around the
 // caller's reserve step and launches, is a template: vr_brush_dev.h.)
 struct DirtyRect;
 int vr_brush_grow(vr_terrain* t, void** ptr, size_t* capacity, size_t bytes);

@@ -1,10 +1,11 @@
 // Who waits for whom between a terrain's two geometry streams, the context's stream and a tone mapper's stream.  Plain C++17:
 // no HIP, no library types - a CPU program replays every short sequence of API calls against a transcription of the code this
 // replaced and against a happens-before model of the streams (tests/host/order_check.cpp).  Stream and Event are opaque
-// handles (Event{} = none); every operation on them goes through the caller's `ops` (vr_internal.h wraps HIP's two calls):
+// handles (Event{} = none); every operation on them goes through the caller's `ops` (vr_internal.h wraps HIP's three calls):
 //
 //   ops.record(event, stream) -> int      the event completes once everything queued on the stream so far has
 //   ops.wait(stream, event)   -> int      what is queued on the stream from now on runs behind the event's last record
+//   ops.sync(event)           -> int      the HOST waits for the event's last record (the side resources alone, below)
 //
 // A non-zero result ends the step and is returned; 0 otherwise.
 //
@@ -41,6 +42,16 @@
 //   order_image_writer_begins / _written / _reader_done
 //                           the pass that writes an image waits for the stage that still reads it; the stage on another stream
 //                           waits for the pass's own stop event (or an explicit record); the image remembers the stage.
+//
+// SIDE RESOURCES.  Memory a terrain keeps beside its maps, whose kernels all run on the context's stream of the moment - the
+// query pyramid, the history journal's arena, the brush's and the erosions' buffers (dab lists, snapshot, block of planes).  One
+// event and the stream of its last record each (OrderSide); three steps:
+//
+//   order_side_begin        in front of a kernel that touches the resource: behind its last user if that ran on another stream
+//                           (the host changed the context's stream in between; on the same stream the stream orders it)
+//   order_side_end          behind the kernel: the event moves there
+//   order_side_idle         the one wait on the HOST: nothing queued can still touch the resource - in front of a free or a
+//                           growth, or of the host's next write into pinned memory a queued copy reads
 #pragma once
 
 #include <stddef.h>
@@ -226,4 +237,26 @@ int order_image_written(OrderImage<Event>& im, const Ops& ops, Stream writer, St
 template <class Stream, class Event, class Ops> int order_image_reader_done(OrderImage<Event>& im, const Ops& ops, Stream reader)
 {
     return order_pending_record(im.read_done, ops, reader);
+}
+
+template <class Stream, class Event> struct OrderSide {
+    Event ev{};              // created and destroyed by the owner of the resource
+    Stream stream{};         // where `ev` was last recorded
+    bool queued = false;     // a record of `ev` that the host has not waited for
+};
+template <class Stream, class Event, class Ops> int order_side_begin(const OrderSide<Stream, Event>& r, const Ops& ops, Stream s)
+{
+    return r.queued && s != r.stream ? ops.wait(s, r.ev) : 0;
+}
+template <class Stream, class Event, class Ops> int order_side_end(OrderSide<Stream, Event>& r, const Ops& ops, Stream s)
+{
+    VR_ORDER_TRY(ops.record(r.ev, s));
+    r.stream = s; r.queued = true;
+    return 0;
+}
+template <class Stream, class Event, class Ops> int order_side_idle(OrderSide<Stream, Event>& r, const Ops& ops)
+{
+    if (r.queued) VR_ORDER_TRY(ops.sync(r.ev));
+    r.queued = false;
+    return 0;
 }

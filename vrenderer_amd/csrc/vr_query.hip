@@ -325,20 +325,16 @@ static int grid_for(uint32_t n)
 // staging of the host-pointer mode: kept with the terrain, grown by doubling
 int vr_query_reserve_stage(vr_terrain* t, size_t bytes)
 {
-    if (bytes <= t->query_stage_bytes) return VR_OK;
-    size_t want = t->query_stage_bytes ? t->query_stage_bytes * 2 : (size_t)1 << 16;
-    while (want < bytes) want *= 2;
-    const auto idle = [t]() -> int { VR_HIP(hipStreamSynchronize(t->ctx->stream)); return VR_OK; };
-    int rc = vr_grow(&t->d_query_stage, &t->query_stage_bytes, want, idle);
-    if (rc == VR_ERR_OUT_OF_MEMORY && want > bytes) rc = vr_grow(&t->d_query_stage, &t->query_stage_bytes, bytes, idle);
-    return rc;                                                           // (on failure the terrain keeps what it had)
+    // (its users leave it idle when they return: only what the caller has queued since can still be running)
+    return vr_reserve(&t->d_query_stage, &t->query_stage_bytes, bytes, [t]() -> int { VR_HIP(hipStreamSynchronize(t->ctx->stream)); return VR_OK; });
 }
 
 void vr_query_release(vr_terrain* t)
 {
     (void)hipFree(t->d_query_stage); t->d_query_stage = nullptr; t->query_stage_bytes = 0;
     (void)hipFree(t->d_pyramid); t->d_pyramid = nullptr; t->pyramid_bytes = 0;
-    if (t->ev_pyramid) { (void)hipEventDestroy(t->ev_pyramid); t->ev_pyramid = nullptr; }
+    if (t->ord_pyramid.ev) (void)hipEventDestroy(t->ord_pyramid.ev);
+    t->ord_pyramid = VrOrderSide();
 }
 
 PyrDesc vr_pyramid_desc(const vr_terrain* t, size_t* cells)
@@ -364,10 +360,7 @@ static int ensure_pyramid(vr_terrain* t, PyrDesc* out)
     size_t cells = 0;
     *out = vr_pyramid_desc(t, &cells);
     hipStream_t s = t->ctx->stream;
-    if (t->d_pyramid) {
-        if (s != t->pyramid_stream) VR_HIP(hipStreamWaitEvent(s, t->ev_pyramid, 0));     // the host changed the context's stream since
-        return VR_OK;
-    }
+    if (t->d_pyramid) return order_side_begin(t->ord_pyramid, VrOrderOps(), s);
     VR_REQUIRE(((t->height.w0 + 1) >> (kPyrMaxLevels - 1)) <= 1 && ((t->height.h0 + 1) >> (kPyrMaxLevels - 1)) <= 1, "heightmap too large for the query pyramid");
     uchar2* p = nullptr;
     hipEvent_t ev = nullptr;
@@ -382,12 +375,13 @@ static int ensure_pyramid(vr_terrain* t, PyrDesc* out)
         vr_derive_pyramid(t->height, *out, p, dirty_whole(w0, h0), dirty_whole(dirty_level_size(w0, lv1), dirty_level_size(h0, lv1)), s);
     }
     const hipError_t le = hipGetLastError();
-    if (le != hipSuccess || hipEventRecord(ev, s) != hipSuccess) {
+    VrOrderSide built; built.ev = ev;
+    if (le != hipSuccess || order_side_end(built, VrOrderOps(), s) != VR_OK) {
         (void)hipStreamSynchronize(s); (void)hipFree(p); (void)hipEventDestroy(ev);
         vr_set_error("terrain query: building the bound pyramid: %s", hipGetErrorString(le));
         return VR_ERR_HIP;
     }
-    t->d_pyramid = p; t->pyramid_bytes = cells * sizeof(uchar2); t->ev_pyramid = ev; t->pyramid_stream = s;
+    t->d_pyramid = p; t->pyramid_bytes = cells * sizeof(uchar2); t->ord_pyramid = built;
     return VR_OK;
 }
 
