@@ -494,6 +494,17 @@ VR_API int vr_terrain_query_heights(vr_terrain* t, const float* xz, uint32_t n, 
  * has a hard iteration cap, and a ray that reaches it returns VR_RAY_STEP_LIMIT. */
 VR_API int vr_terrain_cast_rays(vr_terrain* t, const vr_ray* rays, uint32_t n, float max_height,
                                 vr_ray_hit* hits, int device_pointers);
+/* test helper: the min / max pyramid vr_terrain_cast_rays walks, as it is on the device.  *out_levels receives the number of levels,
+ * out_dims the cells per level - {cw, ch} of level l at out_dims[2 l], out_dims[2 l + 1], zeros beyond the last level - and `out` the
+ * levels in order, cw * ch pairs of bytes (lo, hi) each, row-major: level 0 has (w0 + 1) x (h0 + 1) cells, cell (ix, iz) bounding the
+ * surface over the texel-centre interval [ix - 1, ix] x [iz - 1, iz] by lo / 255 <= H / max_height <= hi / 255; every further level is
+ * the min / max of 2 x 2 cells of the one below, (c + 1) / 2 cells a side, down to 1 x 1.  The copy runs on the context's stream
+ * behind the pyramid's last writer (the first cast, or the refresh of an edit, a stroke, an erosion, an undo or a redo, on whichever
+ * stream that ran) and the entry returns when it has completed.  out == NULL with capacity_bytes == 0 is a size query: the levels and
+ * their cells only.  On a terrain on which no ray has been cast there is no pyramid and none is built: VR_OK, *out_levels == 0, zero
+ * out_dims, `out` untouched.  VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with nothing written: NULL t,
+ * out_levels or out_dims; NULL out with a capacity; a capacity below 2 bytes per cell of all levels together. */
+VR_API int vr_debug_terrain_query_pyramid(vr_terrain* t, int32_t* out_levels, int32_t out_dims[2 * 16], uint8_t* out, size_t capacity_bytes);
 /* Host only (picking; QuadTree.h:84 is what the reference would have called with it): the ray through the centre of pixel
  * (px, py) of view's viewport - screen point (px + 0.5, py + 0.5); fractional px, py are allowed.  The two ends are the
  * points world_to_clip sends to (x, y, 0) and (x, y, 1), solved in double (the inverse of the matrix a renderer projects with;

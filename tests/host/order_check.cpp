@@ -14,7 +14,8 @@
 //      not waited for may still use it.  The protocol must pass; where the plain transcription does not, that is a finding
 //      about the parent, and one of the intended differences must be what repairs it.
 //      The editing path (edit, brush / erode, undo / redo, history_enable, queries, sweep_state) is transcribed from commit 605778b,
-//      the last one with its three private event records; the numbers beside it are that commit's lines.
+//      the last one with its three private event records; the numbers beside it are that commit's lines.  The pyramid's read-back
+//      (vr_debug_terrain_query_pyramid) is younger than that commit: a reader of the pyramid, it is given the wait of the cast's walk.
 //  (c) every sequence up to kExhaustive calls, then a fixed-seed random sample of longer ones.
 // What the model is not: the HIP runtime (it assumes the documented semantics of the two calls), or the 64-entry ring the
 // stamped events of ordinary runs come from (every stamped launch gets a fresh event here).
@@ -426,13 +427,13 @@ struct Protocol {
 // ---- the API calls: what the .hip files do around the ordering steps, with the kernels' accesses ------------------------------
 enum Call { RENDER0, RENDER1, RENDER2, PREPARE0, PREPARE1, PREPARE2, RENDER_LOCKED, SELECT, HEIGHTS_UPDATE, SET_STREAM, ASYNC_TOGGLE, DISPATCH_TOGGLE,
             FUSION_TOGGLE, NOT_STAMPED_1ST, NOT_STAMPED_2ND, TIMING_ON, TIMING_OFF, SUBMIT_A_CROSS, SUBMIT_A_SAME, SUBMIT_B_CROSS, SUBMIT_B_SAME,
-            EDIT_HOST, EDIT_DEVICE, EDIT_ALBEDO_DEVICE, BRUSH, UNDO_REDO, HISTORY_ENABLE, CAST_HOST, CAST_DEVICE, QUERY_DEVICE, SWEEP_STATE, N_CALLS };
+            EDIT_HOST, EDIT_DEVICE, EDIT_ALBEDO_DEVICE, BRUSH, UNDO_REDO, HISTORY_ENABLE, CAST_HOST, CAST_DEVICE, QUERY_DEVICE, SWEEP_STATE, QUERY_PYRAMID, N_CALLS };
 static const char* const kCallName[N_CALLS] = { "render(0)", "render(1)", "render(2)", "prepare(0)", "prepare(1)", "prepare(2)", "render(lock_view)", "select",
     "update_heights", "set_stream", "async_geometry^", "dispatch_events^", "frame_fusion^", "next launch not stamped", "launch after next not stamped",
     "timing_enable(2)", "timing_enable(0)/collect", "submit(image A, tone mapper on another stream)", "submit(image A, same stream)",
     "submit(image B, another stream)", "submit(image B, same stream)",
     "edit(heightmap, host pointer)", "edit(heightmap, device pointer)", "edit(albedo, device pointer)", "brush/erode", "undo/redo", "history_enable",
-    "cast_rays(host pointers)", "cast_rays(device pointers)", "query_heights(device pointers)", "sweep_state" };
+    "cast_rays(host pointers)", "cast_rays(device pointers)", "query_heights(device pointers)", "sweep_state", "query_pyramid" };
 
 template <class P> struct Driver {
     World& w; Host& h; P& p;
@@ -578,6 +579,13 @@ template <class P> struct Driver {
         w.kernel(h.main); w.access(BRUSHBUF, false, h.main);
         w.sync_stream(h.main);
     }
+    void query_pyramid()                                      // vr_debug_terrain_query_pyramid: builds nothing; the copy is a reader, like the walk
+    {
+        if (!h.pyramid_built) return;
+        p.pyramid_begin(false);
+        w.kernel(h.main); w.access(PYRAMID, false, h.main);
+        w.sync_stream(h.main);
+    }
     void timing(int level)                                    // vr_timing_enable / vr_timing_collect (vr_host.hip:216-218, timing_reset)
     {
         w.sync_stream(h.main);
@@ -635,6 +643,7 @@ template <class P> struct Driver {
         case CAST_DEVICE: cast(false); break;
         case QUERY_DEVICE: query_device(); break;
         case SWEEP_STATE: sweep_state(); break;
+        case QUERY_PYRAMID: query_pyramid(); break;
         }
         if (h.launched) h.not_stamped = 0;                    // the marker covers the next call that launches, no more
     }

@@ -207,11 +207,12 @@ def test_stream_order_matches_the_transcribed_protocol_and_the_happens_before_mo
     intended differences the program names, and no two conflicting accesses to a geometry set, the node heights, an HDR image,
     a map, the query pyramid, the journal's arena, the brush buffers or the query staging are left unordered by the streams'
     vector clocks (or, where the host frees or rewrites memory, by what the host waited for); a transcription that loses any one
-    wait is reported, but for the seven the program names with the reason each orders nothing.  The ten calls of the editing
-    path run to the same exhaustive depth as the others: the program takes 2.5 s where the parent's took 1.3 s."""
+    wait is reported, but for the seven the program names with the reason each orders nothing.  The eleven calls of the editing
+    path (the pyramid's read-back, a reader of the pyramid, is the youngest) run to the same exhaustive depth as the others: the
+    program takes about 3 s."""
     exe = build_host_check(tmp_path, "order_check")
     r = run_host_check(exe)
-    assert "1154304 sequences" in r.stdout, r.stdout[-400:]     # 31 + 31^2 + 31^3 + 31^4 of 31 calls (21 + the editing path's 10), 200000 random
+    assert "1282400 sequences" in r.stdout, r.stdout[-400:]     # 32 + 32^2 + 32^3 + 32^4 of 32 calls (21 + the editing path's 11), 200000 random
     run_host_check(exe, "--drop-each", expect="19 of 26 wait sites reported")      # 17 + 9 sites; 16 + 3 reported
 
 

@@ -2,13 +2,16 @@
 device, the host-only pixel ray, and self-checks of the float64 model the GPU tests measure against."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
+import pytest
 
 import vrenderer_amd as vr
 from vrenderer_amd import capi
 from tests.common import CAMERAS, params, scaled_camera
+from tests import pyramid_model as pm
 from tests import queries_common as qc
 from tests.f64_queries import HIT, MISS, Surface64
 
@@ -138,3 +141,101 @@ def test_seeds_keep_the_shares_the_gpu_tests_rely_on(oracle, product_lib):
     assert m["grazing"].mean() <= 0.03, m["grazing"].mean()
     assert 0.3 < (m["status"] == HIT).mean() < 0.9
     ot.close()
+
+
+# ---- the query pyramid's read-back and its model (tests/pyramid_model.py, tests/test_query_pyramid_gpu.py) -----------------------------
+PYRAMID_SHAPES = [(1, 1), (5, 5), (7, 2), (2, 7), (33, 17), (67, 45), (64, 64)]
+
+
+def _random_pair(w, h):
+    return pm.chain_pair(np.random.default_rng(100 + 131 * w + h).integers(0, 256, (h, w), dtype=np.uint8))
+
+
+def test_the_pyramid_read_back_is_declared_exported_and_refuses_null(product_lib):
+    header = open(os.path.join(ROOT, "include", "vrterrain.h")).read()
+    assert re.search(r"VR_API\s+int\s+vr_debug_terrain_query_pyramid\s*\(\s*vr_terrain\*\s*t,\s*int32_t\*\s*out_levels,\s*int32_t out_dims\[2 \* 16\],"
+                     r"\s*uint8_t\*\s*out,\s*size_t capacity_bytes\)", header)
+    assert "vr_debug_terrain_query_pyramid" in capi.EXPORTS and len(product_lib.vr_debug_terrain_query_pyramid.argtypes) == 5
+    fake = C.create_string_buffer(1 << 16)                          # stands in for a terrain on which no ray was cast
+    t = C.cast(fake, C.c_void_p)
+    levels, dims, out = C.c_int32(-1), (C.c_int32 * 32)(*([-1] * 32)), (C.c_uint8 * 4)(5, 5, 5, 5)
+    fn = product_lib.vr_debug_terrain_query_pyramid
+    inv = capi.VR_ERR_INVALID_ARGUMENT
+    assert fn(None, C.byref(levels), dims, out, 4) == inv and fn(None, C.byref(levels), dims, None, 0) == inv
+    assert fn(t, None, dims, out, 4) == inv and fn(t, C.byref(levels), None, out, 4) == inv
+    assert fn(t, C.byref(levels), dims, None, 4) == inv and b"capacity" in product_lib.vr_last_error()
+    assert levels.value == -1 and list(dims) == [-1] * 32 and list(out) == [5] * 4 and bytes(fake) == bytes(1 << 16)
+    # no pyramid: the description says so, nothing is built and the device is not touched (there is none here)
+    assert fn(t, C.byref(levels), dims, None, 0) == capi.VR_OK and levels.value == 0 and list(dims) == [0] * 32
+    levels.value = -1
+    assert fn(t, C.byref(levels), dims, out, 4) == capi.VR_OK and levels.value == 0 and list(out) == [5] * 4 and bytes(fake) == bytes(1 << 16)
+
+
+@pytest.mark.parametrize("shape", PYRAMID_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_pyramid_model_bounds_the_surface(shape):
+    """3a.  Random bytes, the chain of the box-filter model, Surface64(l0, l1, 64, 1).  At every leaf cell's points (texel-centre
+    offsets 0, 1/4, 1/2, 3/4, 1 per axis and the cell's level-1 footprint cuts) lo / 255 - 2^-14 <= H <= hi / 255 + 2^-14: the slack is
+    the walk's own (slack_mh of k_query_rays), the bound the walk assumes.  Measured here: the worst excess over [lo, hi] / 255 itself
+    is 3.3e-16 (67x45; float64 rounding of H), against 6.1e-5 of slack.  Every level above is the min / max of its children, so it
+    bounds what they bound; its shape is (c + 1) // 2 per side down to 1 x 1."""
+    w, h = shape
+    l0, l1 = _random_pair(w, h)
+    lv = pm.levels(l0, l1)
+    x, z = pm.cell_points(w, h, l1.shape[1], l1.shape[0], 64.0)
+    e = pm.excess(lv[0], Surface64(l0, l1, 64.0, 1.0).H(x, z))
+    print(f"\n{w}x{h}: {x.size} points, worst excess over [lo, hi] / 255 = {e:.3e} (slack {pm.SLACK:.3e})")
+    assert e <= pm.SLACK, e
+    assert lv[0].shape == (h + 1, w + 1, 2) and lv[-1].shape == (1, 1, 2) and all(a.dtype == np.uint8 for a in lv)
+    for c, p in zip(lv, lv[1:]):
+        ch, cw = c.shape[:2]
+        assert p.shape == ((ch + 1) // 2, (cw + 1) // 2, 2)
+        for pz in range(p.shape[0]):
+            for px in range(p.shape[1]):
+                kids = c[2 * pz:2 * pz + 2, 2 * px:2 * px + 2]
+                assert p[pz, px, 0] == kids[..., 0].min() and p[pz, px, 1] == kids[..., 1].max()
+    assert (lv[0][..., 0] <= lv[0][..., 1]).all()
+
+
+def test_planted_faults_in_the_model_are_told_apart():
+    """The tests see what they are meant to see: a leaf that swaps lo and hi, or rounds hi down (no + 9), leaves the bound of 3a by
+    more than the slack on every shape but 1 x 1 and differs from the true model there; an up cell that uses 2 p + 1 without the
+    clamp differs from the true model in some level of every ragged shape - 5x5, 7x2, 2x7, 33x17, 67x45 and 64x64 (65 cells a side) -
+    so the byte comparison of the device test tells it apart."""
+    for w, h in PYRAMID_SHAPES[1:]:
+        l0, l1 = _random_pair(w, h)
+        true = pm.levels(l0, l1)
+        x, z = pm.cell_points(w, h, l1.shape[1], l1.shape[0], 64.0)
+        hv = Surface64(l0, l1, 64.0, 1.0).H(x, z)
+        for fault in pm.FAULTS:
+            bad = pm.levels(l0, l1, fault)
+            assert any(not np.array_equal(a, b) for a, b in zip(true, bad)), (w, h, fault)
+            if fault.startswith("leaf"):
+                assert pm.excess(bad[0], hv) > 10 * pm.SLACK, (w, h, fault)
+                assert not np.array_equal(true[0], bad[0])
+            else:
+                assert np.array_equal(true[0], bad[0])
+
+
+@pytest.mark.parametrize("shape", [(67, 45), (64, 64)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_refresh_cases_move_the_model(oracle, shape):
+    """3b.  On the model alone, for the edits of the device test (pyramid_model.refresh_edits on the scene's heights clipped to
+    20 .. 230): one texel raised to 255 changes hi at EVERY level up to the top cell, one texel lowered to 0 changes lo at every level -
+    so a refresh that stops one level early, or that can only grow a bound, leaves bytes that differ - and the restored map gives the
+    original pyramid.  Each edit changes at least one leaf cell, the column, the row and the rectangle at least 30."""
+    w, h = shape
+    hm = pm.clipped(np.ascontiguousarray(oracle.synth_heightmap(max(w, h))[:h, :w]))
+    assert hm.min() >= 20 and hm.max() <= 230
+    base = pm.levels(*pm.chain_pair(hm))
+    for name, x, y, ew, eh in pm.refresh_edits(w, h):
+        assert 0 <= x and x + ew <= w and 0 <= y and y + eh <= h, name
+        for value, plane in ((255, 1), (0, 0)):
+            e = hm.copy()
+            e[y:y + eh, x:x + ew] = value
+            lv = pm.levels(*pm.chain_pair(e))
+            assert len(lv) == len(base)
+            for l, (a, b) in enumerate(zip(base, lv)):
+                assert (a[..., plane] != b[..., plane]).any(), f"{name} -> {value}: level {l} of {len(lv)} does not move"
+            changed = int((base[0] != lv[0]).any(-1).sum())
+            assert changed >= (30 if ew * eh > 1 else 1), (name, value, changed)
+            e[y:y + eh, x:x + ew] = hm[y:y + eh, x:x + ew]
+            assert all(np.array_equal(a, b) for a, b in zip(base, pm.levels(*pm.chain_pair(e))))

@@ -15,6 +15,7 @@ import vrenderer_amd as vr
 from vrenderer_amd import capi
 from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
 from tests.fusion_common import PLANES, download_frame
+from tests import pyramid_model as pm
 from tests import queries_common as qc
 from tests.f64_queries import Surface64
 
@@ -111,7 +112,8 @@ def _assert_chains_equal(a, b, what):
 
 def _assert_terrains_equal(sc, a, b, what):
     """Everything the library exposes of terrains A and B of scene `sc`: every mip level, node heights and selections, every G-buffer
-    plane for cameras 0 and 5, 1024 sampled heights with normals, 64 ray hits."""
+    plane for cameras 0 and 5, 1024 sampled heights with normals, 64 ray hits, then the query pyramid itself and 64 hits under a negative
+    max_height (_assert_pyramids_equal)."""
     _assert_chains_equal(a, b, what)
     surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
     nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
@@ -130,6 +132,27 @@ def _assert_terrains_equal(sc, a, b, what):
     o, d, tm = qc.make_rays(surf, sc.world, n=64)
     ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
     assert ra.tobytes() == rb.tobytes(), f"{what}: {(ra != rb).sum()} of {len(ra)} hits differ"
+    assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
+    _assert_pyramids_equal(sc, a, b, what)
+
+
+def _assert_pyramids_equal(sc, a, b, what):
+    """What the rays above cannot show.  The query pyramids of A and B (both have cast by now) are equal level by level, and equal to
+    tests/pyramid_model.py's of B's maps, byte for byte: a bound left too loose by a refresh only makes a walk longer.  And 64 rays
+    built for max_height = -sc.mh are cast with it - the one sign under which the walk reads the lo plane: the same bytes from A and B."""
+    pa, pb = a.QueryPyramid(), b.QueryPyramid()
+    assert pa is not None and pb is not None and len(pa) == len(pb), what
+    l0 = b.download_mip("height", 0)
+    model = pm.levels(l0, b.download_mip("height", 1) if b.mip_levels("height") > 1 else l0)
+    assert len(pb) == len(model), (what, len(pb), len(model))
+    for l, (x, y, m) in enumerate(zip(pa, pb, model)):
+        assert x.shape == y.shape == m.shape, (what, l, x.shape, y.shape, m.shape)
+        assert np.array_equal(x, y), f"{what}: pyramid level {l}: {(x != y).any(-1).sum()} cells of A differ from B's, first {np.argwhere((x != y).any(-1))[:4].tolist()}"
+        assert np.array_equal(y, m), f"{what}: pyramid level {l}: {(y != m).any(-1).sum()} cells differ from the model, first {np.argwhere((y != m).any(-1))[:4].tolist()}"
+    below = Surface64(l0, b.download_mip("height", 1) if b.mip_levels("height") > 1 else l0, sc.world, -sc.mh)
+    o, d, tm = qc.make_rays(below, sc.world, n=64)
+    ra, rb = a.CastRays(o, d, tm, -sc.mh), b.CastRays(o, d, tm, -sc.mh)
+    assert ra.tobytes() == rb.tobytes(), f"{what}: {(ra != rb).sum()} of {len(ra)} hits differ under max_height = {-sc.mh}"
     assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
 
 
@@ -256,6 +279,7 @@ def test_queries(scenes, name, cast_first):
     ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
     assert ra.tobytes() == rb.tobytes(), f"{name}: {(ra != rb).sum()} of {len(ra)} hits differ"
     assert (ra["status"] == capi.VR_RAY_HIT).mean() > 0.2
+    _assert_pyramids_equal(sc, a, b, f"{name}, cast before the edits: {cast_first}")
     a.close(); b.close()
 
 

@@ -457,6 +457,35 @@ extern "C" VR_API int vr_terrain_cast_rays(vr_terrain* t, const vr_ray* rays, ui
     return VR_OK;
 }
 
+// The pyramid as it is on the device: every level in order, cw * ch pairs (lo, hi) each, as PyrDesc lays them out.  The copy runs on
+// the context's stream behind the pyramid's last writer, as a ray cast's kernel does (the refresh of an edit may have run on another
+// stream), and the entry returns when it has completed, as a query's download does.  No kernel, and nothing is built: a terrain on
+// which no ray was cast has no pyramid to show.
+extern "C" VR_API int vr_debug_terrain_query_pyramid(vr_terrain* t, int32_t* out_levels, int32_t out_dims[2 * 16], uint8_t* out, size_t capacity_bytes)
+{
+    static_assert(kPyrMaxLevels == 16, "out_dims of the header");
+    VR_REQUIRE(t != nullptr, "terrain is NULL");
+    VR_REQUIRE(out_levels != nullptr && out_dims != nullptr, "out_levels or out_dims is NULL");
+    size_t cells = 0;
+    PyrDesc pd; memset(&pd, 0, sizeof(pd));
+    if (t->d_pyramid) pd = vr_pyramid_desc(t, &cells);
+    if (!(out == nullptr && capacity_bytes == 0)) {
+        VR_REQUIRE(out != nullptr, "out is NULL with a capacity");
+        VR_REQUIRE(capacity_bytes >= cells * sizeof(uchar2), "capacity below 2 bytes per cell of every level");
+    }
+    *out_levels = pd.levels;
+    for (int l = 0, w = pd.cw, h = pd.ch; l < kPyrMaxLevels; l++, w = (w + 1) / 2, h = (h + 1) / 2) {
+        out_dims[2 * l] = l < pd.levels ? w : 0; out_dims[2 * l + 1] = l < pd.levels ? h : 0;
+    }
+    if (out == nullptr || pd.levels == 0) return VR_OK;
+    VR_HIP(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    { const int rc = order_side_begin(t->ord_pyramid, VrOrderOps(), s); if (rc) return rc; }
+    VR_HIP(hipMemcpyAsync(out, t->d_pyramid, cells * sizeof(uchar2), hipMemcpyDeviceToHost, s));
+    VR_HIP(hipStreamSynchronize(s));
+    return VR_OK;
+}
+
 // ---- vr_view_pixel_ray (host only) ---------------------------------------------------------------------
 // The world point that world_to_clip sends to NDC (x, y, z): clip_j - ndc_j clip_w = 0 for j = x, y, z is a 3 x 3 linear system
 // in the point.  It is solved in double against world_to_clip - the matrix a renderer projects with - because the fp32

@@ -491,6 +491,24 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_cast_rays(self.handle, _vp(rays), rays.shape[0], max_height, _vp(hits), 0), "vr_terrain_cast_rays")
         return hits
 
+    def QueryPyramid(self):
+        """vr_debug_terrain_query_pyramid (test helper): the min / max pyramid CastRays walks, as it is on the device - a list of
+        uint8 arrays of shape (ch, cw, 2), one per level, [..., 0] = lo and [..., 1] = hi.  None before the first cast of this
+        terrain (nothing is built)."""
+        levels, dims = C.c_int32(), (C.c_int32 * 32)()
+        check(self.ctx.lib.vr_debug_terrain_query_pyramid(self.handle, C.byref(levels), dims, None, 0), "vr_debug_terrain_query_pyramid")
+        if levels.value == 0:
+            return None
+        shapes = [(int(dims[2 * l + 1]), int(dims[2 * l])) for l in range(levels.value)]
+        out = np.empty(2 * sum(h * w for h, w in shapes), np.uint8)
+        check(self.ctx.lib.vr_debug_terrain_query_pyramid(self.handle, C.byref(levels), dims, _vp(out), out.size), "vr_debug_terrain_query_pyramid")
+        assert [(int(dims[2 * l + 1]), int(dims[2 * l])) for l in range(levels.value)] == shapes
+        at, res = 0, []
+        for h, w in shapes:
+            res.append(out[at:at + 2 * h * w].reshape(h, w, 2))
+            at += 2 * h * w
+        return res
+
     def Edit(self, which, x, y, texels=None, device_ptr=None, w=None, h=None, pitch=0):
         """vr_terrain_edit: replaces a sub-rectangle of level 0 of the heightmap (which = 'height' / 0) or the albedo ('albedo' / 1)
         at (x, y) in place; afterwards the terrain is the one Init would build from the edited arrays.  With device_ptr=None,
