@@ -17,8 +17,11 @@
 //      the last one with its three private event records; the numbers beside it are that commit's lines.  The pyramid's read-back
 //      (vr_debug_terrain_query_pyramid) is younger than that commit: a reader of the pyramid, it is given the wait of the cast's walk.
 //  (c) every sequence up to kExhaustive calls, then a fixed-seed random sample of longer ones.
-// What the model is not: the HIP runtime (it assumes the documented semantics of the two calls), or the 64-entry ring the
-// stamped events of ordinary runs come from (every stamped launch gets a fresh event here).
+//      The stamped launches take their events from the real supplier (vr_events.h) with a ring of FOUR events, two launches, so
+//      slots are reissued inside the short sequences; a re-stamped event is what it is - a wait on it orders against the new
+//      occupant only - and every re-stamp must come behind the event's previous occupant (the rule vr_events.h states for a wait
+//      on a ring handle that is no longer live).
+// What the model is not: the HIP runtime (it assumes the documented semantics of the two calls).
 //   order_check                 the check; prints sequences and failures
 //   order_check --drop-each     is the model alive?  The transcription (intended differences on) loses one wait site at a time;
 //                               prints for each site in how many sequences (b) reports it, and for a site that no sequence
@@ -42,7 +45,7 @@ static const char* const kResName[N_RES] = { "selection 0", "selection 1", "sele
                                              "brush buffers", "query staging" };
 // own events (0 = none); stamped events follow
 enum { EV_GEO_DONE = 1, EV_RASTER_DONE = 4, EV_SEL_READ = 7, EV_MAIN_DEP = 10, EV_SEL_COPY, EV_RASTER_BEGIN, EV_WRITTEN, EV_READ_DONE = 15, EV_PYRAMID = 17, EV_JOURNAL, EV_BRUSH, EV_FIRST_STAMPED,
-       N_EVENTS = 96 };
+       N_EVENTS = 128 };
 typedef std::array<uint32_t, N_STREAMS> Clock;
 static void join(Clock& a, const Clock& b) { for (int i = 0; i < N_STREAMS; i++) if (b[i] > a[i]) a[i] = b[i]; }
 
@@ -77,7 +80,12 @@ struct World {
         return 0;
     }
     void kernel(int s) { op_on(s); clk[s][s]++; }
-    int stamp(int s) { const int e = next_event++; ev[e] = clk[s]; ev_recorded[e] = true; return e; }     // right behind the kernel just queued
+    static bool behind(const Clock& a, const Clock& b) { for (int i = 0; i < N_STREAMS; i++) if (a[i] > b[i]) return false; return true; }
+    void stamp(int e, int s)                                     // by the dispatch: right behind the kernel just queued
+    {
+        if (ev_recorded[e] && !behind(ev[e], clk[s])) fail("an event re-stamped for a launch that is not ordered behind its previous occupant");
+        ev[e] = clk[s]; ev_recorded[e] = true;
+    }
     void sync_stream(int s) { join(host, clk[s]); }
     void sync_event(int e) { join(host, ev[e]); }
     int sync(int e) { sync_event(e); trace.push_back({ 2, 0, (uint16_t)e }); return 0; }                  // a side resource's order_side_idle
@@ -113,12 +121,20 @@ struct Ops { World* w; int record(int e, int s) const { return w->record(e, s); 
 // ---- what the .hip files decide (the same for both protocols): the context and the terrain's set bookkeeping ---------------
 struct Host {
     int main = M0;
-    bool async_geometry = true, dispatch_events = true, frame_fusion = true;
-    int timing = 0;                   // 0 or 2 (level 2: only the stamped launches are timed; level 1 synchronises more)
-    uint64_t ev_epoch = 1;
-    int last_stop = 0;
-    std::vector<int> pooled_end;      // stop events taken from the timing pool since it was last recycled
-    unsigned not_stamped = 0;         // bit k: the k-th stamped launch from now gets no events (the ring or pool gave none)
+    bool async_geometry = true, frame_fusion = true;
+    // the real supplier, small: a ring of two launches, no events made ahead (timing level 0 or 2: only the stamped launches are
+    // timed; level 1 synchronises more)
+    EventSupply<int> events;
+    struct EvOps { World* w; const Host* h;
+        bool create(int* e) const { if (h->fail_create || w->next_event >= N_EVENTS) return false; *e = w->next_event++; return true; }
+        void destroy(int) const {}
+        void record(int e, int s) const { w->record(e, s); }
+        int sync_stream(int s) const { w->sync_stream(s); return 0; }
+        int sync_event(int e) const { w->sync_event(e); return 0; }
+        int elapsed(float*, int, int) const { return 0; } };
+    Host() { events.ring_size = 4; events.precreate[1] = events.precreate[2] = 0; }
+    unsigned not_stamped = 0;         // bit k: the k-th stamped launch from now gets no events if it has to create one (the only way to get none)
+    bool fail_create = false;
     bool launched = false;
     bool prepared[3] = { false, false, false }, have_selection[3] = { false, false, false };
     int prep_view[3] = { 0, 0, 0 }; uint64_t prep_serial[3] = { 0, 0, 0 }, prep_counter = 0;
@@ -138,19 +154,20 @@ struct Host {
         }
         return best;
     }
-    // VrKernelScope(attach) + VR_LAUNCH_TIMED on the context's stream: the kernel, and its stop event if the dispatch stamped one
-    int stamped_launch(World& w)
+    // VrKernelScope(by_dispatch) + launch on the context's stream: the kernel, and VrKernelScope::stop
+    EventRef<int> stamped_launch(World& w)
     {
-        const bool events = (timing != 0 || dispatch_events) && !(not_stamped & 1u);
+        const EvOps ops{ &w, this };
+        fail_create = (not_stamped & 1u) != 0;
         not_stamped >>= 1; launched = true;
+        EventPair<int, int> pair = events_take(events, ops, 0, main, true);
+        fail_create = false;
         w.kernel(main);
-        if (!events) return 0;
-        const int e1 = w.stamp(main);
-        if (timing) pooled_end.push_back(e1);
-        last_stop = e1;
-        return e1;
+        if (pair.stamps()) { w.stamp(pair.begin, main); w.stamp(pair.end, main); events_launched(events, pair, main); }
+        const EventRef<int> stop = events_stop(events, pair);
+        events_release(events, ops, pair);
+        return stop;
     }
-    int stop_of(int e1) const { return dispatch_events ? e1 : 0; }      // VrKernelScope::stop
 };
 static const int kGeo[2] = { G0, G1 };
 
@@ -160,6 +177,8 @@ struct Intended {
     bool heights_behind;    // the node-height update runs behind every chain queued so far (found by (b): see main)
     bool common_order;      // vr_terrain_select queues its waits in launch_geometry's order (the permitted reorder)
     bool sweep_dead_wait;   // vr_debug_terrain_sweep_state does not wait for the erosion's event on the stream that recorded it (a dead wait)
+    bool ring_handles;      // a mark that holds a RING event is not dropped when the timing epoch advances: its handle is live until the slot
+                            // is reissued (vr_events.h) - a wait more, for a launch the recycler's synchronise has seen complete
 };
 enum Site { W_LG_CHAIN = 1, W_LG_SEL_READ, W_LG_RASTER, W_LG_MAIN_DEP, W_LG_SEL_COPY, W_PREP_HINT, W_PREP_NOW, W_TILE_CHAIN, W_KEEP_READER, W_AHEAD,
             W_SEL_MAIN_DEP, W_SEL_CHAIN, W_SEL_SEL_READ, W_SEL_RASTER, W_FRAME_READER, W_FRAME_WRITTEN, W_HEIGHTS_CHAIN,
@@ -187,10 +206,10 @@ static const char* dead_reason(int site)
 
 struct Parent {
     World& w; Host& h; Intended in;
-    struct Set { int ev_geo_done, ev_raster_done, raster_done = 0; uint64_t raster_done_epoch = 0; bool raster_recorded = false, geo_recorded = false;
+    struct Set { int ev_geo_done, ev_raster_done, raster_done = 0; uint64_t raster_done_epoch = 0; bool raster_recorded = false, geo_recorded = false, raster_ring = false;
                  int ev_sel_read; bool sel_read_pending = false, main_waited = false; int main_wait_stream = 0, stream = G0; bool main_dep_pending = false; } sets[3];
     int ev_sel_copy = EV_SEL_COPY, ev_main_dep = EV_MAIN_DEP, ev_raster_begin = EV_RASTER_BEGIN;
-    bool raster_begin_recorded = false; int start_hint = 0; uint64_t start_hint_epoch = 0;
+    bool raster_begin_recorded = false, start_hint_ring = false; int start_hint = 0; uint64_t start_hint_epoch = 0;
     struct Image { int ev_written, ev_read_done; bool read_pending = false; } img[2];
     Parent(World& w_, Host& h_, Intended in_) : w(w_), h(h_), in(in_)
     {
@@ -207,6 +226,7 @@ struct Parent {
     void W(int site, int s, int e) { if (site != w.drop_site) w.wait(s, e); }
     void S(int site, int e) { if (site != w.drop_site) w.sync(e); }
     int stream(int gi) const { return sets[gi].stream; }
+    bool epoch_ok(uint64_t epoch, bool ring) const { return epoch == 0 || epoch == h.events.epoch || (in.ring_handles && ring); }
 
     void begin_chain(int gi)                                  // launch_geometry, vr_raster.hip
     {
@@ -220,7 +240,7 @@ struct Parent {
                    }
         /* 1795 */ if (g.geo_recorded) W(W_LG_CHAIN, gs, g.ev_geo_done);
         /* 1796 */ if (g.sel_read_pending) { W(W_LG_SEL_READ, gs, g.ev_sel_read); g.sel_read_pending = false; }
-        /* 1798 */ if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == h.ev_epoch)) W(W_LG_RASTER, gs, g.raster_done);
+        /* 1798 */ if (g.raster_recorded && epoch_ok(g.raster_done_epoch, g.raster_ring)) W(W_LG_RASTER, gs, g.raster_done);
         /* 1799 */ if (g.main_dep_pending) { W(W_LG_MAIN_DEP, gs, ev_main_dep); g.main_dep_pending = false; }
     }
     template <class Copy> void copy_selection(int gi, int from, Copy&& copy)
@@ -240,7 +260,7 @@ struct Parent {
     }
     void prepare_start()                                      // vr_terrain_prepare
     {
-        /* 1925 */ if (raster_begin_recorded && (start_hint_epoch == 0 || start_hint_epoch == h.ev_epoch))
+        /* 1925 */ if (raster_begin_recorded && epoch_ok(start_hint_epoch, start_hint_ring))
         /* 1926 */     W(W_PREP_HINT, kGeo[h.geo_turn & 1u], start_hint);
     }
     void prepare_wait(int gi)
@@ -256,17 +276,18 @@ struct Parent {
         Set& g = sets[gi]; const int s = h.main;
         /* 2040 */ if (!(use_prepared && g.main_waited && g.main_wait_stream == s)) W(W_TILE_CHAIN, s, g.ev_geo_done);
         /* 2041 */ g.main_waited = false;
-        /* 2045 */ if (h.dispatch_events && h.last_stop) { start_hint = h.last_stop; start_hint_epoch = h.ev_epoch; raster_begin_recorded = true; }
+        /* 2045 */ if (h.events.dispatch_events && h.events.last_stop.ev) { start_hint = h.events.last_stop.ev; start_hint_epoch = h.events.epoch; raster_begin_recorded = true; }
         /* 2046 */ else { R(ev_raster_begin, s); start_hint = ev_raster_begin; start_hint_epoch = 0; raster_begin_recorded = true; }
+        start_hint_ring = start_hint_epoch && h.events.last_stop.slot != 0;
     }
     void keep_writer_begins(int im)
     {
         /* 2057 */ if (img[im].read_pending) { W(W_KEEP_READER, h.main, img[im].ev_read_done); img[im].read_pending = false; }
     }
-    void tile_pass_launched(int gi, int pass_stop)            // pass_stop: 2075
+    void tile_pass_launched(int gi, EventRef<int> stop)       // pass_stop: 2075
     {
-        Set& g = sets[gi]; const int s = h.main;
-        /* 2078 */ if (pass_stop) { g.raster_done = pass_stop; g.raster_done_epoch = h.ev_epoch; }
+        Set& g = sets[gi]; const int s = h.main, pass_stop = stop.ev;
+        /* 2078 */ if (pass_stop) { g.raster_done = pass_stop; g.raster_done_epoch = h.events.epoch; g.raster_ring = stop.slot != 0; }
         /* 2079 */ else { R(g.ev_raster_done, s); g.raster_done = g.ev_raster_done; g.raster_done_epoch = 0; }
         /* 2080 */ g.raster_recorded = true;
         /* 2082 */ for (int pi = 0; pi < 3; pi++) { Set& p = sets[pi];
@@ -280,7 +301,7 @@ struct Parent {
         /* 751 */ if (g.main_dep_pending) { W(W_SEL_MAIN_DEP, g.stream, ev_main_dep); g.main_dep_pending = false; }
         /* 753 */ if (g.geo_recorded) W(W_SEL_CHAIN, g.stream, g.ev_geo_done);
         /* 754 */ if (g.sel_read_pending) { W(W_SEL_SEL_READ, g.stream, g.ev_sel_read); g.sel_read_pending = false; }
-        /* 755 */ if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == h.ev_epoch)) W(W_SEL_RASTER, g.stream, g.raster_done);
+        /* 755 */ if (g.raster_recorded && epoch_ok(g.raster_done_epoch, g.raster_ring)) W(W_SEL_RASTER, g.stream, g.raster_done);
         if (in.common_order)                                  // the same waits; the main dependency last, as launch_geometry has it
         /* 751 */ if (g.main_dep_pending) { W(W_SEL_MAIN_DEP, g.stream, ev_main_dep); g.main_dep_pending = false; }
     }
@@ -303,7 +324,7 @@ struct Parent {
     void maps_begin()                                         // vr_derive_level0_write, vr_derive.hip (the header's two steps, flat)
     {
         /* 230 */ for (Set& g : sets) if (g.geo_recorded) W(W_MAPS_CHAIN, h.main, g.ev_geo_done);
-        /* 231 */ for (Set& g : sets) if (g.raster_recorded && (g.raster_done_epoch == 0 || g.raster_done_epoch == h.ev_epoch)) W(W_MAPS_RASTER, h.main, g.raster_done);
+        /* 231 */ for (Set& g : sets) if (g.raster_recorded && epoch_ok(g.raster_done_epoch, g.raster_ring)) W(W_MAPS_RASTER, h.main, g.raster_done);
     }
     void maps_end() { /* 260 */ heights_end(); }
     void pyramid_begin(bool write)
@@ -351,11 +372,11 @@ struct Parent {
     {
         /* 38 */ if (img[im].read_pending) { W(W_FRAME_READER, h.main, img[im].ev_read_done); img[im].read_pending = false; }
     }
-    void image_written(int im, bool fused, int fused_stop, int light_stop, int reader)
+    void image_written(int im, bool fused, EventRef<int> fused_stop, EventRef<int> light_stop, int reader)
     {
         Image* hdr = &img[im];
-        /* 55 */ int done = fused ? fused_stop : (h.dispatch_events && h.last_stop) ? h.last_stop : 0;
-        if (in.own_stop && !fused) done = light_stop;
+        /* 55 */ int done = fused ? fused_stop.ev : (h.events.dispatch_events && h.events.last_stop.ev) ? h.events.last_stop.ev : 0;
+        if (in.own_stop && !fused) done = light_stop.ev;
         /* 56 */ if (!done) {
         /* 58 */     R(hdr->ev_written, h.main);
         /* 59 */     done = hdr->ev_written;
@@ -383,31 +404,31 @@ struct Protocol {
         for (int i = 0; i < 2; i++) { img[i].written.own = EV_WRITTEN + i; img[i].read_done.ev = EV_READ_DONE + i; }
     }
     int stream(int gi) const { return sets[gi].stream; }
-    void begin_chain(int gi) { order_begin_chain(t, sets[gi], ops, kGeo, h.geo_turn, h.main, !h.async_geometry, h.ev_epoch); }
+    void begin_chain(int gi) { order_begin_chain(t, sets[gi], ops, kGeo, h.geo_turn, h.main, !h.async_geometry, h.events); }
     template <class Copy> void copy_selection(int gi, int from, Copy&& copy) { order_copy_selection(t, sets[gi], sets[from], ops, [&]() -> int { copy(); return 0; }); }
     void end_chain(int gi) { order_end_chain(sets[gi], ops); }
-    void prepare_start() { order_prepare_start(t, ops, kGeo, h.geo_turn, h.ev_epoch); }
+    void prepare_start() { order_prepare_start(t, ops, kGeo, h.geo_turn, h.events); }
     void prepare_wait(int gi)
     {
         bool other_prepared = false;
         for (int p = 0; p < 3; p++) other_prepared |= (p != gi) && h.prepared[p];
         order_prepare_wait(sets[gi], ops, h.main, other_prepared);
     }
-    void tile_pass_begin(int gi, bool use_prepared) { order_tile_pass_begin(t, sets[gi], ops, h.main, use_prepared, h.dispatch_events ? h.last_stop : 0, h.ev_epoch); }
+    void tile_pass_begin(int gi, bool use_prepared) { order_tile_pass_begin(t, sets[gi], ops, h.main, use_prepared, events_start_hint(h.events)); }
     void keep_writer_begins(int im) { order_image_writer_begins(img[im], ops, h.main); }
-    void tile_pass_launched(int gi, int pass_stop)
+    void tile_pass_launched(int gi, EventRef<int> pass_stop)
     {
-        order_tile_pass_launched(sets[gi], ops, h.main, pass_stop, h.ev_epoch);
+        order_tile_pass_launched(sets[gi], ops, h.main, pass_stop);
         for (int p = 0; p < 3; p++) if (p != gi && h.prepared[p]) order_wait_ahead(sets[p], ops, h.main);
     }
-    void select_begin(int gi) { order_begin_chain(t, sets[gi], ops, kGeo, h.geo_turn, h.main, false, h.ev_epoch); }
+    void select_begin(int gi) { order_begin_chain(t, sets[gi], ops, kGeo, h.geo_turn, h.main, false, h.events); }
     void select_end(int gi) { order_end_chain(sets[gi], ops); }
     void heights_begin() { OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] }; order_terrain_changing(all, ops, h.main); }
     void heights_end() { OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] }; order_terrain_changed(t, all, ops, h.main); }
     void maps_begin()
     {
         OrderSet<int, int>* const all[3] = { &sets[0], &sets[1], &sets[2] };
-        order_terrain_changing(all, ops, h.main); order_terrain_tables_changing(all, ops, h.main, h.ev_epoch);
+        order_terrain_changing(all, ops, h.main); order_terrain_tables_changing(all, ops, h.main, h.events);
     }
     void maps_end() { heights_end(); }
     void pyramid_begin(bool) { order_side_begin(pyramid, ops, h.main); }
@@ -419,21 +440,21 @@ struct Protocol {
     void brush_end() { order_side_end(brush, ops, h.main); }
     void sweep_begin() { order_side_begin(brush, ops, h.main); }
     void light_writer_begins(int im) { order_image_writer_begins(img[im], ops, h.main); }
-    void image_written(int im, bool fused, int fused_stop, int light_stop, int reader)
-    { order_image_written(img[im], ops, h.main, reader, fused ? fused_stop : light_stop, h.ev_epoch); }
+    void image_written(int im, bool fused, EventRef<int> fused_stop, EventRef<int> light_stop, int reader)
+    { order_image_written(img[im], ops, h.main, reader, fused ? fused_stop : light_stop, h.events); }
     void reader_done(int im, int reader) { order_image_reader_done(img[im], ops, reader); }
 };
 
 // ---- the API calls: what the .hip files do around the ordering steps, with the kernels' accesses ------------------------------
 enum Call { RENDER0, RENDER1, RENDER2, PREPARE0, PREPARE1, PREPARE2, RENDER_LOCKED, SELECT, HEIGHTS_UPDATE, SET_STREAM, ASYNC_TOGGLE, DISPATCH_TOGGLE,
             FUSION_TOGGLE, NOT_STAMPED_1ST, NOT_STAMPED_2ND, TIMING_ON, TIMING_OFF, SUBMIT_A_CROSS, SUBMIT_A_SAME, SUBMIT_B_CROSS, SUBMIT_B_SAME,
-            EDIT_HOST, EDIT_DEVICE, EDIT_ALBEDO_DEVICE, BRUSH, UNDO_REDO, HISTORY_ENABLE, CAST_HOST, CAST_DEVICE, QUERY_DEVICE, SWEEP_STATE, QUERY_PYRAMID, N_CALLS };
+            EDIT_HOST, EDIT_DEVICE, EDIT_ALBEDO_DEVICE, BRUSH, UNDO_REDO, HISTORY_ENABLE, CAST_HOST, CAST_DEVICE, QUERY_DEVICE, SWEEP_STATE, QUERY_PYRAMID, OTHER_TERRAIN_FRAME, N_CALLS };
 static const char* const kCallName[N_CALLS] = { "render(0)", "render(1)", "render(2)", "prepare(0)", "prepare(1)", "prepare(2)", "render(lock_view)", "select",
     "update_heights", "set_stream", "async_geometry^", "dispatch_events^", "frame_fusion^", "next launch not stamped", "launch after next not stamped",
     "timing_enable(2)", "timing_enable(0)/collect", "submit(image A, tone mapper on another stream)", "submit(image A, same stream)",
     "submit(image B, another stream)", "submit(image B, same stream)",
     "edit(heightmap, host pointer)", "edit(heightmap, device pointer)", "edit(albedo, device pointer)", "brush/erode", "undo/redo", "history_enable",
-    "cast_rays(host pointers)", "cast_rays(device pointers)", "query_heights(device pointers)", "sweep_state", "query_pyramid" };
+    "cast_rays(host pointers)", "cast_rays(device pointers)", "query_heights(device pointers)", "sweep_state", "query_pyramid", "frame of another terrain" };
 
 template <class P> struct Driver {
     World& w; Host& h; P& p;
@@ -459,7 +480,7 @@ template <class P> struct Driver {
         p.prepare_wait(gi);
         h.prepared[gi] = true; h.prep_view[gi] = view; h.prep_serial[gi] = ++h.prep_counter;
     }
-    int render(int view, bool lock, int keep_image)           // terrain_render_impl; returns the pass's stop event (keep: the fused launch's)
+    EventRef<int> render(int view, bool lock, int keep_image) // terrain_render_impl; returns the pass's stop event (keep: the fused launch's)
     {
         int gi = -1;
         if (!lock) for (int i = 0; i < 3; i++) if (i != h.cur && h.prepared[i] && h.prep_view[i] == view) { gi = i; break; }
@@ -471,7 +492,7 @@ template <class P> struct Driver {
         h.cur = gi;
         p.tile_pass_begin(gi, use_prepared);
         if (keep_image >= 0) p.keep_writer_begins(keep_image);
-        const int pass_stop = h.stop_of(h.stamped_launch(w));
+        const EventRef<int> pass_stop = h.stamped_launch(w);
         w.access(SEL0 + gi, false, h.main); w.access(GEO0 + gi, false, h.main);
         w.access(HMAP, false, h.main); w.access(AMAP, false, h.main);                                                    // (both maps' tables)
         if (keep_image >= 0) w.access(IMG0 + keep_image, true, h.main);
@@ -586,23 +607,20 @@ template <class P> struct Driver {
         w.kernel(h.main); w.access(PYRAMID, false, h.main);
         w.sync_stream(h.main);
     }
-    void timing(int level)                                    // vr_timing_enable / vr_timing_collect (vr_host.hip:216-218, timing_reset)
-    {
-        w.sync_stream(h.main);
-        for (int e : h.pooled_end) w.sync_event(e);
-        h.ev_epoch++; h.last_stop = 0; h.pooled_end.clear();
-        h.timing = level;
-    }
+    void timing(int level) { events_timing_enable(h.events, Host::EvOps{ &w, &h }, h.main, level); }      // vr_timing_enable / vr_timing_collect
+    // a frame of ANOTHER terrain of the same context, unfused: its tile pass and its lighting pass take ring slots (all four of this
+    // ring) and touch nothing of this terrain's; its chains run on its own geometry streams
+    void other_terrain_frame() { h.stamped_launch(w); h.stamped_launch(w); }
     void submit(int im, bool tm_cross)                        // vr_frame_submit: view n, the next two prepared ahead
     {
         const int view = h.frame_no % 3;
         const bool fused = h.frame_fusion;                    // (where the tile pass's G-buffer-keeping flavour applies)
-        const int fused_stop = render(view, false, fused ? im : -1);
+        const EventRef<int> fused_stop = render(view, false, fused ? im : -1);
         prepare((view + 1) % 3); prepare((view + 2) % 3);
-        int light_stop = 0;
+        EventRef<int> light_stop;
         if (!fused) {
             p.light_writer_begins(im);
-            light_stop = h.stop_of(h.stamped_launch(w));
+            light_stop = h.stamped_launch(w);
             w.access(IMG0 + im, true, h.main);
         }
         const int reader = tm_cross ? TM : h.main;
@@ -623,7 +641,7 @@ template <class P> struct Driver {
         case HEIGHTS_UPDATE: update_heights(); break;
         case SET_STREAM: { const int to = h.main == M0 ? M1 : M0; w.host_orders(to, h.main); h.main = to; } break;     // (test_context_stream_changed_...: "what the host owes")
         case ASYNC_TOGGLE: h.async_geometry = !h.async_geometry; break;
-        case DISPATCH_TOGGLE: w.sync_stream(h.main); h.dispatch_events = !h.dispatch_events; h.last_stop = 0; break;   // vr_context_set_option
+        case DISPATCH_TOGGLE: events_set_dispatch(h.events, Host::EvOps{ &w, &h }, h.main, !h.events.dispatch_events); break;   // vr_context_set_option
         case FUSION_TOGGLE: h.frame_fusion = !h.frame_fusion; break;
         case NOT_STAMPED_1ST: h.not_stamped = 1u; break;
         case NOT_STAMPED_2ND: h.not_stamped = 2u; break;
@@ -644,6 +662,7 @@ template <class P> struct Driver {
         case QUERY_DEVICE: query_device(); break;
         case SWEEP_STATE: sweep_state(); break;
         case QUERY_PYRAMID: query_pyramid(); break;
+        case OTHER_TERRAIN_FRAME: other_terrain_frame(); break;
         }
         if (h.launched) h.not_stamped = 0;                    // the marker covers the next call that launches, no more
     }
@@ -676,13 +695,13 @@ static std::string show(const std::vector<Op>& t)
 
 // ---- (c) the sequences ------------------------------------------------------------------------------------
 constexpr int kExhaustive = 4, kRandom = 200000, kRandomMax = 14;
-static const Intended kPlain = { false, false, false, false }, kAll = { true, true, true, true };
+static const Intended kPlain = { false, false, false, false, false }, kAll = { true, true, true, true, true };
 static long sequences = 0, failures = 0;
 // the parent's own unordered pairs, by the one intended difference that repairs them
 struct Finding { const char* name; Intended only; long count; int shortest[kRandomMax], shortest_n; std::string pair; };
 static Finding findings[2] = {
-    { "vr_frame_submit took ctx->last_stop for a lighting pass that was not stamped", { true, false, false, false }, 0, {}, 0, "" },
-    { "the node-height update did not wait for chains that still read the heights", { false, true, false, false }, 0, {}, 0, "" },
+    { "vr_frame_submit took ctx->last_stop for a lighting pass that was not stamped", { true, false, false, false, false }, 0, {}, 0, "" },
+    { "the node-height update did not wait for chains that still read the heights", { false, true, false, false, false }, 0, {}, 0, "" },
 };
 static long drop_reported[N_SITES];
 
@@ -704,7 +723,7 @@ static void check(const int* seq, int n)
             explained = true; f.count++;
             if (!f.shortest_n || n < f.shortest_n) { f.shortest_n = n; memcpy(f.shortest, seq, n * sizeof(int)); f.pair = plain.first; }
         }
-        if (!explained && run_parent(seq, n, { true, true, false, false }, 0).unordered) {
+        if (!explained && run_parent(seq, n, { true, true, false, false, false }, 0).unordered) {
             if (failures++ < 10) printf("FAIL (b) parent, not repaired by the intended differences: %s\n    %s\n", show(seq, n).c_str(), plain.first.c_str());
         }
     }
@@ -713,7 +732,7 @@ static void check_drops(const int* seq, int n)
 {
     sequences++;
     // (the dead wait that Intended::sweep_dead_wait drops exists only with that switch off)
-    static const Intended kWithDead = { true, true, true, false };
+    static const Intended kWithDead = { true, true, true, false, true };
     for (int site = 1; site < N_SITES; site++) if (run_parent(seq, n, site == W_SWEEP_DEAD ? kWithDead : kAll, site).unordered) drop_reported[site]++;
 }
 
@@ -743,6 +762,26 @@ static void known(const char* what, std::vector<int> seq)
     if (!plain.unordered || now.unordered) { failures++; printf("FAIL: expected the parent unordered and the protocol ordered\n"); }
 }
 
+// The rule of vr_events.h for a ring handle that is no longer live, pinned: set 1's tile pass is stamped on main0; the context moves
+// to main1, where another terrain's frame takes all four slots; two renders later set 1's next chain waits on the mark - for the
+// slot's new occupant, stamped on ANOTHER stream, and that orders the chain behind the tile pass all the same.
+static void pinned_ring_reuse()
+{
+    const std::vector<int> seq = { RENDER0, SET_STREAM, OTHER_TERRAIN_FRAME, RENDER1, RENDER2 };
+    g_world.reset(0);
+    Host h; Protocol p(g_world, h); Driver<Protocol> d{ g_world, h, p };
+    for (size_t i = 0; i + 1 < seq.size(); i++) d.call(seq[i]);
+    const EventRef<int> mark = p.sets[1].tile_pass.at;
+    const bool stale = mark.slot != 0 && !events_live(h.events, mark) && events_wait_needed(h.events, mark);
+    const size_t before = g_world.trace.size();
+    d.call(seq.back());
+    bool waited = false;
+    for (size_t i = before; i < g_world.trace.size(); i++) waited |= g_world.trace[i].wait == 1 && g_world.trace[i].event == mark.ev && g_world.trace[i].stream == p.stream(1);
+    printf("pinned: a wait on a reissued ring slot is a wait for its new occupant, queued behind the old one\n    %s\n    handle %s, %s, %s\n",
+           show(seq.data(), (int)seq.size()).c_str(), stale ? "no longer live" : "LIVE", waited ? "waited for" : "NOT waited for", g_world.unordered ? g_world.first.c_str() : "ordered");
+    if (!stale || !waited || g_world.unordered) { failures++; printf("FAIL: expected a stale ring handle, a wait on it and no unordered pair\n"); }
+}
+
 int main(int argc, char** argv)
 {
     if (argc > 1 && !strcmp(argv[1], "--drop-each")) {
@@ -764,12 +803,14 @@ int main(int argc, char** argv)
     known(findings[0].name, { FUSION_TOGGLE, NOT_STAMPED_2ND, SUBMIT_A_CROSS });
     // intended difference 2 (found by (b)): a select's chain is consumed by nothing on the context's stream, which then rewrites the heights
     known(findings[1].name, { SELECT, HEIGHTS_UPDATE });
+    pinned_ring_reuse();
     all_sequences(kExhaustive, kRandom, check);
     for (const Finding& f : findings) {
         printf("finding: %s: %ld sequences; shortest: %s\n    %s\n", f.name, f.count, show(f.shortest, f.shortest_n).c_str(), f.pair.c_str());
         if (!f.count) { failures++; printf("FAIL: the finding was not seen\n"); }
     }
     printf("dead wait dropped: vr_debug_terrain_sweep_state waits for the erosion only where it ran on another stream (Intended::sweep_dead_wait)\n");
+    printf("wait kept: a mark that holds a ring event outlives a recycled timing epoch; its launch is complete by then (Intended::ring_handles)\n");
     printf("permitted reorder: vr_terrain_select queues the main-dependency wait last, as launch_geometry does (Intended::common_order)\n");
     printf("%ld sequences (all up to %d calls of %d, %d random up to %d), %ld failures\n", sequences, kExhaustive, (int)N_CALLS, kRandom, kRandomMax, failures);
     return failures ? 1 : 0;

@@ -209,11 +209,27 @@ def test_stream_order_matches_the_transcribed_protocol_and_the_happens_before_mo
     vector clocks (or, where the host frees or rewrites memory, by what the host waited for); a transcription that loses any one
     wait is reported, but for the seven the program names with the reason each orders nothing.  The eleven calls of the editing
     path (the pyramid's read-back, a reader of the pyramid, is the youngest) run to the same exhaustive depth as the others: the
-    program takes about 3 s."""
+    program takes about 4 s.  The stamped launches take their events from vr_events.h with a ring of four, and a frame of another
+    terrain is one of the calls: slots are reissued inside the sequences, every re-stamp must come behind the event's previous
+    occupant, and one pinned sequence waits on a reissued slot across a stream change.  No wait site was added for it."""
     exe = build_host_check(tmp_path, "order_check")
     r = run_host_check(exe)
-    assert "1282400 sequences" in r.stdout, r.stdout[-400:]     # 32 + 32^2 + 32^3 + 32^4 of 32 calls (21 + the editing path's 11), 200000 random
+    # 33 + 33^2 + 33^3 + 33^4 of 33 calls (21 + the editing path's 11 + another terrain's frame), 200000 random
+    assert "1422980 sequences" in r.stdout, r.stdout[-400:]
+    assert "handle no longer live, waited for, ordered" in r.stdout, r.stdout[-4000:]
     run_host_check(exe, "--drop-each", expect="19 of 26 wait sites reported")      # 17 + 9 sites; 16 + 3 reported
+
+
+def test_event_supply_keeps_its_invariants_over_random_transitions(tmp_path):
+    """vr_events.h compiles without HIP.  Against a counting fake of its ops, over random sequences of its transitions
+    (tests/host/events_check.cpp), no event is in two places at once, every event created is destroyed exactly once, a scope
+    that ends without a launch leaves no never-recorded pair, a failed creation leaves the launch unstamped, collect returns
+    exactly the pairs committed since the last recycle (and recycles when a query fails), and a handle is live exactly until
+    its pool epoch passes or its ring slot is reissued; once more under the address and undefined-behaviour sanitizers."""
+    r = run_host_check(build_host_check(tmp_path, "events_check"))
+    assert "20000 cases" in r.stdout, r.stdout[-400:]
+    san = build_host_check(tmp_path, "events_check", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "events_check_san")
+    run_host_check(san)
 
 
 def test_scratch_policy_matches_the_transcribed_code_and_its_invariants(tmp_path):

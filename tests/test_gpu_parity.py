@@ -1362,6 +1362,88 @@ def test_marks_of_a_recycled_timing_epoch_are_not_waited_for(scene256, oracle, g
         rt.close()
 
 
+def test_marks_that_outlive_the_event_ring_wait_for_the_new_occupants(scene256, oracle, gpu_ctx):
+    """Timing off, VR_OPT_DISPATCH_EVENTS on: the stamped events come from the context's ring of 64, two per launch.  Between
+    two uses of terrain A's geometry sets a second terrain renders 40 frames - every slot is reissued at least once, half of
+    them after vr_context_set_stream to another stream - so A's tile-pass marks and the start hint of a chain prepared before
+    those frames hold handles that are no longer live: a wait on one is a wait for the slot's new occupant (vr_events.h).
+    Nothing hangs, and every downloaded frame's five planes equal the oracle's, A's on either stream and B's last ones.
+    This cannot detect a race: a download synchronises.  A missing wait is what tests/host/order_check.cpp finds."""
+    import torch
+    ot, tp = scene256["ot"], scene256["tp"]
+    tp_b = vr.TerrainPass(gpu_ctx, params(256)).Init(scene256["h"], scene256["a"])
+    w, h = 320, 180
+    rp = vr.default_render_params(400.0, assume_cleared=1)
+    rt, rt_b = vr.RenderTargets(gpu_ctx).Init(w, h), vr.RenderTargets(gpu_ctx).Init(w, h)
+    views, want = [], []
+    for cam in (CAMERAS[0], CAMERAS[3], CAMERAS[5], CAMERAS[1]):
+        v = vr.make_view(*scaled_camera(cam, 256), w, h)
+        gb = oracle.GBufferHost(w, h)
+        gb.clear(); ot.render(v, gb, rp)
+        views.append(v); want.append(gb)
+
+    def check(targets, k, what):
+        planes = {p: targets.download(p) for p in ("depth", "diffuse", "specular", "normals", "emissive")}
+        _assert_gbuffer_equal(want[k], planes, what)
+
+    gpu_ctx.timing_enable(0)
+    gpu_ctx.set_dispatch_events(True)
+    gpu_ctx.synchronize()                                 # (the new targets' clears ran on the stream the context had until now)
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    try:
+        gpu_ctx.set_stream(sa.cuda_stream)
+        tp.Render(views[0], views[0], rt, rp); check(rt, 0, "A, first frame")
+        tp.Prepare(views[1], rt, rp)                      # consumed behind B's frames: its start hint is A's tile pass
+        for k in range(20):
+            tp_b.Render(views[k % 4], views[k % 4], rt_b, rp)
+        check(rt_b, 19 % 4, "B, frame 20 on the first stream")
+        sb.wait_stream(sa)                                # what the host owes when it moves the context to another stream
+        gpu_ctx.set_stream(sb.cuda_stream)
+        for k in range(20, 40):
+            tp_b.Render(views[k % 4], views[k % 4], rt_b, rp)
+        check(rt_b, 39 % 4, "B, frame 40 on the second stream")
+        tp.Render(views[1], views[1], rt, rp); check(rt, 1, "A on the second stream, prepared before the ring wrapped")
+        sa.wait_stream(sb)
+        gpu_ctx.set_stream(sa.cuda_stream)
+        tp.Render(views[2], views[2], rt, rp); check(rt, 2, "A on the first stream, into a set whose tile-pass mark predates the wrap")
+        sb.wait_stream(sa)
+        gpu_ctx.set_stream(sb.cuda_stream)
+        tp.Render(views[3], views[3], rt, rp); check(rt, 3, "A on the second stream, the third set")
+    finally:
+        torch.cuda.synchronize()
+        gpu_ctx.set_stream(0)
+        for o in (rt_b, rt, tp_b):
+            o.close()
+
+
+@pytest.mark.parametrize("fusion", [True, False])
+def test_timing_level_2_counts_the_stamped_launches_alone(scene256, gpu_ctx, fusion):
+    """vr_timing_collect at level 2 over 8 frames of Frame.submit: one tile pass per frame - the fused variant where the frame
+    is one kernel - one lighting launch per unfused frame, and nothing for the small kernels, whose launches are not stamped.
+    (bench.py reports these counts and sums.)"""
+    tp = scene256["tp"]
+    w, h = 320, 180
+    views = [vr.make_view(*scaled_camera(CAMERAS[k], 256), w, h) for k in (0, 1, 5, 3, 0, 6, 1, 5)]
+    rp = vr.default_render_params(400.0, assume_cleared=1)
+    rt = vr.RenderTargets(gpu_ctx).Init(w, h)
+    hdrs = [vr.HdrImage(gpu_ctx, w, h) for _ in range(2)]
+    fr = vr.Frame(tp, rt, rp, [vr.reference_sun()], AMBIENT_TOP, AMBIENT_BOTTOM)
+    gpu_ctx.synchronize()
+    gpu_ctx.set_frame_fusion(fusion)
+    try:
+        gpu_ctx.timing_enable(2)
+        for i, v in enumerate(views):
+            fr.submit(v, hdrs[i % 2], views[i + 1:i + 3])
+        got = {name: n for name, (_, n) in gpu_ctx.timing_collect().items()}
+        assert got == ({"k_raster (fused with lighting)": 8} if fusion else {"k_raster": 8, "k_deferred": 8})
+        assert gpu_ctx.timing_collect() == {}, "collect did not reset"
+    finally:
+        gpu_ctx.timing_enable(0)
+        gpu_ctx.set_frame_fusion(True)
+        for o in hdrs + [rt]:
+            o.close()
+
+
 def test_region_tracking_never_changes_the_gbuffer(scene256, oracle, gpu_ctx):
     """VR_OPT_PLANE_TRACKING per region (8 rows x 32 pixels): a sky region known to hold the clear values is not written by a
     pass over a 'cleared' target, a terrain region known to hold the specular constant keeps that plane.  Through a history of

@@ -744,7 +744,7 @@ static_assert(sizeof(kStreamKernels) / sizeof(kStreamKernels[0]) == LV_HINTED_RO
 
 // The streaming pass: vr_deferred_light, vr_deferred_light_shadowed.
 // *stop: the stop event this call's own launch was stamped with (NULL: not stamped, or nothing was launched)
-static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightCall& c, hipEvent_t* stop)
+static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightCall& c, VrEventRef* stop)
 {
     PlaneHints hints;                                         // (a reader: a pending clear happens now)
     { const int rc = vr_gbuffer_plane_hints(gb, ctx->stream, &hints); if (rc) return rc; }
@@ -754,9 +754,9 @@ static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightC
         const int32_t* owned = c.pt ? c.pt->d_owned_tiles : nullptr;
         VrKernelScope ks(ctx, VR_K_DEFERRED, ctx->stream, true);
 #define VR_LIGHT_ARGS c.a, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut
-        if (plan.shade == LV_SCALAR) VR_LAUNCH_TIMED(ks, k_deferred_scalar, dim3(plan.shade_grid), dim3(256), ctx->stream, VR_LIGHT_ARGS, c.sh, c.in.shadow ? 1 : 0);
-        else if (plan.shade < LV_HINTED_ROW) VR_LAUNCH_TIMED(ks, kStreamKernels[plan.shade - LV_STREAM_ROW], dim3(plan.shade_grid), dim3(256), ctx->stream, VR_LIGHT_ARGS, owned, c.sh);
-        else VR_LAUNCH_TIMED(ks, kHintedKernels[plan.shade - LV_HINTED_ROW], dim3(plan.shade_grid), dim3(256), ctx->stream, VR_LIGHT_ARGS, owned, c.sh, hints);
+        if (plan.shade == LV_SCALAR) ks.launch(k_deferred_scalar, dim3(plan.shade_grid), dim3(256), VR_LIGHT_ARGS, c.sh, c.in.shadow ? 1 : 0);
+        else if (plan.shade < LV_HINTED_ROW) ks.launch(kStreamKernels[plan.shade - LV_STREAM_ROW], dim3(plan.shade_grid), dim3(256), VR_LIGHT_ARGS, owned, c.sh);
+        else ks.launch(kHintedKernels[plan.shade - LV_HINTED_ROW], dim3(plan.shade_grid), dim3(256), VR_LIGHT_ARGS, owned, c.sh, hints);
 #undef VR_LIGHT_ARGS
         *stop = ks.stop();
     }
@@ -766,7 +766,7 @@ static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightC
 
 // Both tiled entry points: vr_deferred_light_tiled, vr_deferred_light_tiled_ex (what either can get: vr_light_plan.h).
 // The list is in ctx->h_lights (vr_light_check); c.a has no light in it: the kernels read d_lights.
-static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, LightCall& c, hipEvent_t* stop)
+static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, LightCall& c, VrEventRef* stop)
 {
     // (the buffers below grow through vr_grow: a growth that fails leaves the old buffer, its capacity and - d_lights - its contents)
     const auto idle = [ctx]() -> int { VR_HIP(hipStreamSynchronize(ctx->stream)); return VR_OK; };
@@ -800,11 +800,11 @@ static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, 
     // pass's, so its stop event serves as the next frame's geometry start hint (vr_terrain_prepare)
     if (plan.launch) {
         const int32_t* owned = c.pt ? c.pt->d_owned_tiles : nullptr;
-        { VrKernelScope kc(ctx, VR_K_LIGHT_CULL);
+        { VrKernelScope kc(ctx, VR_K_LIGHT_CULL, ctx->stream);
           hipLaunchKernelGGL(kCullKernels[plan.cull], dim3(plan.cull_grid), dim3(256), 0, ctx->stream, c.a, ctx->d_lights, c.in.num_lights, gb->depth, (const uint2*)gb->normals,
                              plan.macro_x, owned, ctx->d_light_lists, plan.list_stride, plan.tiles32_x, plan.tiles32_y, ctx->d_flags, ctx->d_macro_scratch, gb->d_ranges); }
         VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
-        VR_LAUNCH_TIMED(ks, kTiledKernels[plan.shade - LV_TILED_ROW], dim3(plan.shade_grid), dim3(256), ctx->stream, c.a, ctx->d_lights, gb->depth, gb->diffuse, gb->specular,
+        ks.launch(kTiledKernels[plan.shade - LV_TILED_ROW], dim3(plan.shade_grid), dim3(256), c.a, ctx->d_lights, gb->depth, gb->diffuse, gb->specular,
                         gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, owned, ctx->d_light_lists, plan.list_stride, plan.tiles32_x, hints, c.sh);
         *stop = ks.stop();
     }
@@ -870,10 +870,10 @@ int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gb
 }
 
 // ---- nothing refuses an argument from here on.  The arguments are those vr_light_check took; *stop = the stop event the
-// pass's own launch was stamped with (NULL: not stamped, or nothing was launched).
-int vr_light_queue(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall& c, hipEvent_t* stop)
+// pass's own launch was stamped with (none: not stamped, or nothing was launched).
+int vr_light_queue(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall& c, VrEventRef* stop)
 {
-    *stop = nullptr;
+    *stop = {};
     VR_HIP(hipSetDevice(ctx->device));
     if (part) { const int rc = vr_partition_tables(ctx, gb->w, gb->h, part, &c.pt); if (rc) return rc; }      // (a cache hit)
     if (c.in.shadow) {                                        // the map made real (a pending clear is written)
@@ -887,7 +887,7 @@ static int light_pass(vr_context* ctx, LightEntry entry, const vr_view* view, vr
                       const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow)
 {
     LightCall c;
-    hipEvent_t stop;
+    VrEventRef stop;
     const int rc = vr_light_check(ctx, entry, view, gb, lights, num_lights, amb_top, amb_bottom, hdr, part, shadow, &c);
     return rc ? rc : vr_light_queue(ctx, gb, hdr, part, shadow, c, &stop);
 }
@@ -977,7 +977,7 @@ extern "C" VR_API int vr_frame_detile(vr_context* ctx, const void* gathered, int
     { int rc = vr_partition_slot_tables(ctx, frame->w, frame->h, world, &pt); if (rc) return rc; }
     const size_t pairs = (size_t)frame->w * frame->h / 2;
     const int tiles_x = (frame->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
-    VrKernelScope ks(ctx, VR_K_DETILE);
+    VrKernelScope ks(ctx, VR_K_DETILE, ctx->stream);
     hipLaunchKernelGGL(k_detile, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)gathered,
                        (uint4*)frame->data, frame->w, frame->h, tiles_x, pt->d_tile_slot);
     VR_HIP(hipGetLastError());

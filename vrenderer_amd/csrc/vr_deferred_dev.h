@@ -261,7 +261,7 @@ struct LightCall { LightPlanIn in; DeferredArgs a; ShadowArgs sh; const PartTabl
 int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
                    const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
                    const vr_shadow_binding* shadow, LightCall* call);
-int vr_light_queue(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall& c, hipEvent_t* stop);
+int vr_light_queue(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall& c, VrEventRef* stop);
 
 __device__ __forceinline__ float shadow_factor(const DeferredArgs& a, const ShadowArgs& s, int px, int py, float depth)
 {

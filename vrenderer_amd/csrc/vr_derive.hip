@@ -228,7 +228,7 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
     static_assert(kGeoSets == 3, "the list below");
     VrOrderSet* const ord_sets[kGeoSets] = { &t->sets[0].ord, &t->sets[1].ord, &t->sets[2].ord };
     { const int rc = order_terrain_changing(ord_sets, VrOrderOps(), s); if (rc) return rc; }
-    { const int rc = order_terrain_tables_changing(ord_sets, VrOrderOps(), s, ctx->ev_epoch); if (rc) return rc; }
+    { const int rc = order_terrain_tables_changing(ord_sets, VrOrderOps(), s, ctx->events); if (rc) return rc; }
     // geometry built from the old map is stale, whichever map it was (one rule); selections and lock_view stay as they are
     for (GeoSet& g : t->sets) g.prepared = false;
 
@@ -236,7 +236,7 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
     vr_derive_chain(ctx, const_cast<uint8_t*>(tex.base), lay, tex.w0, tex.h0, tex.levels, which == 0 ? 1 : 4, dirty);
     VR_HIP(hipGetLastError());
     if (which == 0 && t->height_loaded && t->d_node_heights) {
-        VrKernelScope ks(ctx, VR_K_NODE_HEIGHTS);
+        VrKernelScope ks(ctx, VR_K_NODE_HEIGHTS, ctx->stream);
         for (int surf = 0; surf < t->surfaces_per_side * t->surfaces_per_side; surf++) {
             const NodeSurface ns = vr_node_surface(t, surf);
             if (ns.dyadic) vr_derive_node_heights(t, surf, ns, dirty);
@@ -249,7 +249,7 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
         const DirtyRect l1 = tex.levels > 1 ? dirty_rect(dirty_mip_next(dirty_x(dirty), dirty_level_size(tex.w0, 1)), dirty_mip_next(dirty_y(dirty), dirty_level_size(tex.h0, 1)))
                                             : dirty;
         {
-            VrKernelScope ks(ctx, VR_K_QUERY_PYRAMID);
+            VrKernelScope ks(ctx, VR_K_QUERY_PYRAMID, ctx->stream);
             vr_derive_pyramid(tex, vr_pyramid_desc(t, nullptr), t->d_pyramid, dirty, l1, s);
         }
         VR_HIP(hipGetLastError());

@@ -41,7 +41,7 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     // lighting pass of a whole frame; everything else is decided in vr_terrain_render_keep, in front of the launch): the frame is
     // then one kernel, and what the G-buffer, its plane states and HdrColor hold afterwards is what the two passes leave.
     bool fused = false;
-    hipEvent_t fused_stop = nullptr;
+    VrEventRef fused_stop;
     int earlier;
     if (ctx->frame_fusion && !f->tiled && !f->shadow && !f->part)
         earlier = vr_terrain_render_keep(t, f->view, gb, f->render, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, &fused, &fused_stop);
@@ -54,7 +54,7 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     // written_stop: the stop event of the pass that writes the image - the fused tile pass's or the lighting pass's OWN, handed out
     // by the launch (vr_terrain_prepare has run since: the context's last stamped launch need not be that one)
     const VrOrderOps ops;
-    hipEvent_t written_stop = fused_stop;
+    VrEventRef written_stop = fused_stop;
     if (!fused) {
         if ((rc = order_image_writer_begins(hdr->ord, ops, ctx->stream))) return rc;
         if ((rc = vr_light_queue(ctx, gb, hdr, f->part, f->shadow, lc, &written_stop))) return rc;
@@ -66,8 +66,8 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     const bool cross = tc->stream != ctx->stream;
     if (cross) {
         // behind the pass that wrote the image: its dispatch-stamped stop event when there is one, else an explicit record
-        if (!written_stop && !hdr->ord.written.own) VR_HIP(hipEventCreateWithFlags(&hdr->ord.written.own, hipEventDisableTiming));
-        if ((rc = order_image_written(hdr->ord, ops, ctx->stream, tc->stream, written_stop, ctx->ev_epoch))) return rc;
+        if (!written_stop.ev && !hdr->ord.written.own) VR_HIP(hipEventCreateWithFlags(&hdr->ord.written.own, hipEventDisableTiming));
+        if ((rc = order_image_written(hdr->ord, ops, ctx->stream, tc->stream, written_stop, ctx->events))) return rc;
     }
     if ((rc = vr_tonemap_stage(f->tonemap, tmc, true))) return rc;
     if (cross) {

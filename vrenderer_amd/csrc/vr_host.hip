@@ -35,7 +35,29 @@ extern "C" VR_API uint32_t vr_build_experiments(void) { return kExpMask; }
 // ---- sRGB tables (SRGBA8 fetch / render-target conversion) -------------------------
 static double srgb_eotf(double c) { return c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4); }
 
-static void timing_reset(vr_context* c);
+// ---- launch events (vr_events.h decides; this is the HIP work it names) ---------------------------
+// Events that order device work against device work (and time kernels) need no system-scope fence: nothing here hands data
+// to the host through them - downloads go through stream synchronisation.  Without the flag every stamped event ends its
+// kernel with a release to system scope (a write-back of the caches) in front of the next dispatch.
+static unsigned vr_event_flags()
+{
+    static const unsigned flags = getenv("VR_EVENT_SYSTEM_FENCE") ? hipEventDefault : hipEventDisableSystemFence;
+    return flags;
+}
+namespace {
+struct VrEventOps {
+    bool create(hipEvent_t* e) const { return hipEventCreateWithFlags(e, vr_event_flags()) == hipSuccess; }
+    void destroy(hipEvent_t e) const { (void)hipEventDestroy(e); }
+    void record(hipEvent_t e, hipStream_t s) const { (void)hipEventRecord(e, s); }
+    int sync_stream(hipStream_t s) const { VR_HIP(hipStreamSynchronize(s)); return VR_OK; }
+    int sync_event(hipEvent_t e) const { return check(hipEventSynchronize(e)); }
+    int elapsed(float* ms, hipEvent_t a, hipEvent_t b) const { return check(hipEventElapsedTime(ms, a, b)); }
+    static int check(hipError_t e) { if (e != hipSuccess) vr_set_error("vr_timing_collect: %s", hipGetErrorString(e)); return e == hipSuccess ? VR_OK : VR_ERR_HIP; }
+};
+}
+VrKernelScope::VrKernelScope(vr_context* ctx, int id, hipStream_t stream, bool by_dispatch)
+    : c(ctx), pair(events_take(ctx->events, VrEventOps(), id, stream, by_dispatch)) {}
+VrKernelScope::~VrKernelScope() { events_release(c->events, VrEventOps(), pair); }
 
 // ---- context ----------------------------------------------------------------------
 extern "C" VR_API int vr_context_create(int device, vr_context** out)
@@ -97,10 +119,8 @@ extern "C" VR_API void vr_context_destroy(vr_context* c)
         (void)hipFree(pt->d_owned_tiles); (void)hipFree(pt->d_tile_slot); (void)hipFree(pt->d_raster_tiles);
         delete pt;
     }
-    timing_reset(c);
+    events_destroy(c->events, VrEventOps());
     if (c->ev_sysfence) (void)hipEventDestroy(c->ev_sysfence);
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_ring) (void)hipEventDestroy(e);
     delete c;
 }
 
@@ -124,7 +144,7 @@ extern "C" VR_API int vr_context_set_option(vr_context* c, int option, int value
         VR_REQUIRE(value == 0 || value == 32 || value == 64, "VR_OPT_RASTER_TILE: 0 (by size), 32 or 64");
         c->raster_tile_force = value == 32 ? 5 : value == 64 ? 6 : 0;
     }
-    else { VR_HIP(hipStreamSynchronize(c->stream)); c->dispatch_events = value != 0; c->last_stop = nullptr; }
+    else return events_set_dispatch(c->events, VrEventOps(), c->stream, value != 0);
     return VR_OK;
 }
 
@@ -136,127 +156,26 @@ extern "C" VR_API int vr_context_synchronize(vr_context* c)
 }
 
 // ---- per-kernel timing ---------------------------------------------------------------
-// Events that order device work against device work (and time kernels) need no system-scope fence: nothing here hands data
-// to the host through them - downloads go through stream synchronisation.  Without the flag every stamped event ends its
-// kernel with a release to system scope (a write-back of the caches) in front of the next dispatch.
-static unsigned vr_event_flags()
-{
-    static const unsigned flags = getenv("VR_EVENT_SYSTEM_FENCE") ? hipEventDefault : hipEventDisableSystemFence;
-    return flags;
-}
-static hipEvent_t take_event(vr_context* c)
-{
-    hipEvent_t e = nullptr;
-    if (!c->ev_pool.empty()) { e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
-    if (hipEventCreateWithFlags(&e, vr_event_flags()) != hipSuccess) return nullptr;
-    return e;
-}
-VrKernelScope::VrKernelScope(vr_context* ctx, int id) : VrKernelScope(ctx, id, ctx->stream) {}
-VrKernelScope::VrKernelScope(vr_context* ctx, int id, hipStream_t stream) : VrKernelScope(ctx, id, stream, false) {}
-static hipEvent_t ring_event(vr_context* c)
-{
-    constexpr size_t kRing = 64;          // far more than the launches a later wait can still refer to
-    if (c->ev_ring.size() < kRing) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreateWithFlags(&e, vr_event_flags()) != hipSuccess) return nullptr;
-        c->ev_ring.push_back(e);
-        return e;
-    }
-    hipEvent_t e = c->ev_ring[c->ev_ring_pos];
-    c->ev_ring_pos = (c->ev_ring_pos + 1) % kRing;
-    return e;
-}
-VrKernelScope::VrKernelScope(vr_context* ctx, int id_, hipStream_t stream, bool attach_) : c(ctx), st(stream), attach(attach_), id(id_)
-{
-    // level 2: only the launches whose events are stamped by the dispatch itself (the tile pass, the lighting passes): timing
-    // them costs the host nothing, while two hipEventRecord calls around each of a frame's dozen small kernels make a loop
-    // with a ~110 us frame period host-bound
-    if (c->timing == 1 || (c->timing == 2 && attach)) {
-        e0 = take_event(c); e1 = take_event(c);
-        if (!e0 || !e1) {
-            if (e0) c->ev_pool.push_back(e0);
-            if (e1) c->ev_pool.push_back(e1);
-            e0 = e1 = nullptr; return;
-        }
-        pooled = true;
-        if (!attach) { (void)hipEventRecord(e0, st); commit(); }
-    } else if (attach && c->dispatch_events) {
-        e0 = ring_event(c); e1 = ring_event(c);
-        if (!e0 || !e1) e0 = e1 = nullptr;
-    }
-}
-void VrKernelScope::commit()
-{
-    if (committed || !pooled || !e0 || !e1) return;
-    c->ev_begin.push_back(e0); c->ev_end.push_back(e1); c->ev_id.push_back(id);
-    committed = true;
-}
-void VrKernelScope::launched()
-{
-    commit();
-    stamped = true;
-    if (st == c->stream) c->last_stop = e1;
-}
-VrKernelScope::~VrKernelScope()
-{
-    if (!e0 || !e1 || !pooled) return;
-    if (!attach) (void)hipEventRecord(e1, st);
-    else if (!committed) { c->ev_pool.push_back(e0); c->ev_pool.push_back(e1); }
-}
-
-static void timing_reset(vr_context* c)
-{
-    c->ev_epoch++;                     // every handle to a pooled event taken before this point is stale now
-    c->last_stop = nullptr;
-    for (hipEvent_t e : c->ev_begin) c->ev_pool.push_back(e);
-    for (hipEvent_t e : c->ev_end) c->ev_pool.push_back(e);
-    c->ev_begin.clear(); c->ev_end.clear(); c->ev_id.clear();
-}
 extern "C" VR_API int vr_timing_enable(vr_context* c, int enable)
 {
     VR_REQUIRE(c != nullptr, "ctx is NULL");
     VR_HIP(hipSetDevice(c->device));
-    VR_HIP(hipStreamSynchronize(c->stream));
-    // pairs recorded on a terrain's geometry stream may still be pending: wait for each before its events are recycled
-    for (hipEvent_t e : c->ev_end) (void)hipEventSynchronize(e);
-    timing_reset(c);
-    c->timing = enable < 0 ? 0 : (enable > 2 ? 1 : enable);
-    // events for the launches to come are made HERE, not one by one inside the host's frame loop (hipEventCreate per stamped
-    // launch was ~20 us of a rank's ~100 us of host time per frame): enough for a few hundred frames, more are made on demand
-    if (c->timing) {
-        const size_t want = c->timing == 1 ? 8192 : 2048;
-        while (c->ev_pool.size() < want) {
-            hipEvent_t e = nullptr;
-            if (hipEventCreateWithFlags(&e, vr_event_flags()) != hipSuccess) break;
-            c->ev_pool.push_back(e);
-        }
-    }
-    return VR_OK;
+    return events_timing_enable(c->events, VrEventOps(), c->stream, enable);
 }
 extern "C" VR_API int vr_timing_collect(vr_context* c, float ms_sum[VR_K_COUNT], int32_t launches[VR_K_COUNT])
 {
     VR_REQUIRE(c && ms_sum && launches, "NULL argument");
     VR_HIP(hipSetDevice(c->device));
-    VR_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < VR_K_COUNT; i++) { ms_sum[i] = 0.0f; launches[i] = 0; }
-    int rc = VR_OK;
-    for (size_t i = 0; i < c->ev_id.size(); i++) {
-        float ms = 0.0f;
-        hipError_t e = hipEventSynchronize(c->ev_end[i]);      // may have been recorded on a terrain's geometry stream
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev_begin[i], c->ev_end[i]);
-        if (e != hipSuccess) { vr_set_error("vr_timing_collect: %s", hipGetErrorString(e)); rc = VR_ERR_HIP; continue; }
-        ms_sum[c->ev_id[i]] += ms; launches[c->ev_id[i]]++;
-    }
-    timing_reset(c);                                     // also on the error path: a bad pair must not persist
-    return rc;
+    return events_collect(c->events, VrEventOps(), c->stream, ms_sum, launches, VR_K_COUNT);
 }
 extern "C" VR_API int vr_timing_kernel_count(void) { return VR_K_COUNT; }
 extern "C" VR_API const char* vr_kernel_name(int id)
 {
-    static const char* names[VR_K_COUNT] = { "k_select", "k_vertex", "k_setup", "k_clip", "k_scan", "k_fill", "k_raster",
+    static const char* names[] = { "k_select", "k_vertex", "k_setup", "k_clip", "k_scan", "k_fill", "k_raster",
                                               "k_deferred", "k_detile", "k_fill_u32 (clear)", "k_deferred_tiled", "k_node_heights (all levels)",
                                               "k_tm_histogram", "k_tm_exposure", "k_tonemap", "k_detile_ldr", "k_raster (depth only)", "k_light_cull",
                                               "k_raster (fused with lighting)", "k_query_heights", "k_query_rays", "k_query_pyramid (all levels)" };
+    static_assert(sizeof(names) / sizeof(names[0]) == VR_K_COUNT, "one name per kernel id");
     return (id >= 0 && id < VR_K_COUNT) ? names[id] : "?";
 }
 

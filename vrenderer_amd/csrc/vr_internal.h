@@ -58,6 +58,7 @@ struct VrOrderOps {
 };
 using VrOrderSet = OrderSet<hipStream_t, hipEvent_t>;
 using VrOrderSide = OrderSide<hipStream_t, hipEvent_t>;
+using VrEventRef = EventRef<hipEvent_t>;
 
 // ---- geometry constants -----------------------------------------------------------
 constexpr int kGrid = 32;                    // GRID_SIZE (TerrainPass.h:28)
@@ -212,56 +213,36 @@ struct vr_context {
     bool frame_fusion = true;      // VR_OPT_FRAME_FUSION: vr_frame_submit shades in the tile pass where its G-buffer-keeping flavour applies
     bool gbuffer_lazy = true;      // VR_OPT_GBUFFER_LAZY: a fused frame leaves its colour planes to their first reader (vr_gbuffer_state.h)
     int raster_tile_force = 0;     // VR_OPT_RASTER_TILE: 0 = by size (vr_raster_tile_shift), 5 / 6 = 32- / 64-pixel raster tiles
-    // VR_OPT_DISPATCH_EVENTS: the tile pass and the lighting pass are launched with hipExtLaunchKernelGGL, whose start/stop
-    // events are stamped by the dispatch itself; the stop events double as the cross-stream dependencies (tile pass done ->
-    // its geometry set is free; lighting pass done -> the next frame's geometry may start), so no event-record packets
-    // sit between the two big kernels of a frame.  Outside timing runs the events come from this ring.
-    bool dispatch_events = true;
-    std::vector<hipEvent_t> ev_ring; size_t ev_ring_pos = 0;
-    // Stop event of the most recent dispatch-stamped launch on `stream`.  Read for ONE thing: the start hint of the next
-    // prepared chain (order_tile_pass_begin), where a wrong event costs time and not correctness.  It says nothing about which
-    // launch it belongs to: a pass that others must wait for hands out its own stop event (VrKernelScope::stop).
-    hipEvent_t last_stop = nullptr;
-    // Advanced whenever the timing pool is recycled (vr_timing_enable / vr_timing_collect, both of which synchronise the stream
-    // first): a mark that holds a stamped event of an older epoch counts as complete (OrderMark, vr_order.h).
-    uint64_t ev_epoch = 1;
+    // Start / stop events of the launches (vr_events.h): the timing level and pool, VR_OPT_DISPATCH_EVENTS and the ring the stamped
+    // events of ordinary runs come from, the pairs vr_timing_collect reads.  Only vr_host.hip changes it, through that header's transitions.
+    EventSupply<hipEvent_t> events;
     // light list of vr_deferred_light_tiled
     DevLight* d_lights = nullptr; size_t light_bytes = 0; std::vector<DevLight> h_lights, h_lights_on_device;   // (the list d_lights holds)
     uint32_t* d_macro_scratch = nullptr; size_t macro_scratch_bytes = 0;   // per macro tile: lights touching its box (k_light_cull's first stage)
     uint32_t* d_light_lists = nullptr; size_t light_list_bytes = 0;    // per 32x32 light tile: count + light indices (k_light_cull)
     uint32_t* d_flags = nullptr;
     int list_stride = 0, list_tiles_x = 0, list_tiles_y = 0;   // layout of d_light_lists as the last tiled pass left it (vr_debug_tile_light_list)
-    // per-kernel timing (vr_timing_*): event pairs recorded on `stream`
-    int timing = 0;                      // 0 off, 1 every kernel (two event records each), 2 only the launches whose events the dispatch stamps
-    std::vector<hipEvent_t> ev_pool;     // reusable events
-    std::vector<hipEvent_t> ev_begin, ev_end;
-    std::vector<int> ev_id;
 };
 
-// Records a begin/end event pair around one kernel launch when timing is enabled.
-struct VrKernelScope {
-    vr_context* c; hipEvent_t e0 = nullptr, e1 = nullptr; hipStream_t st = nullptr; bool attach = false; int id = 0; bool committed = false;
-    bool pooled = false;            // the pair came from the timing pool (else from the context's ring: dependencies only)
-    VrKernelScope(vr_context* ctx, int id);                       // on the context's stream
-    VrKernelScope(vr_context* ctx, int id, hipStream_t stream);   // on another stream of the same device
-    // attach = true: the events are not recorded as separate stream operations; the launch passes them to
-    // hipExtLaunchKernelGGL (VR_LAUNCH_TIMED), which stamps them from the dispatch itself - no extra packets between
-    // two dependent kernels on the stream
-    VrKernelScope(vr_context* ctx, int id, hipStream_t stream, bool attach);
-    // the pair enters the context's list only once something will stamp it (attach = true: after the launch was issued;
-    // a scope that returns early without launching hands its events back instead of leaving a never-recorded pair)
-    void commit();
-    void launched();                // the dispatch that stamps the pair has been issued
-    bool stamped = false;
-    // this launch's own stop event where such events serve as dependencies (VR_OPT_DISPATCH_EVENTS); NULL: not stamped, or no launch
-    hipEvent_t stop() const { return stamped && c->dispatch_events ? e1 : nullptr; }
+// One kernel launch's event pair, when it gets one (events_take): RAII over vr_events.h's transitions.
+// by_dispatch: the events are not recorded as separate stream operations; the launch passes them to hipExtLaunchKernelGGL
+// (launch), which stamps them from the dispatch itself.
+class VrKernelScope {
+    vr_context* c; EventPair<hipEvent_t, hipStream_t> pair;
+public:
+    VrKernelScope(vr_context* ctx, int id, hipStream_t stream, bool by_dispatch = false);
+    VrKernelScope(const VrKernelScope&) = delete;
+    // the launch of a scope created with by_dispatch = true, on the scope's stream
+    template <class Kernel, class... Args> void launch(Kernel kernel, dim3 grid, dim3 block, const Args&... args)
+    {
+        if (pair.stamps()) {
+            hipExtLaunchKernelGGL(kernel, grid, block, 0, pair.stream, pair.begin, pair.end, 0, args...);
+            events_launched(c->events, pair, c->stream);
+        } else hipLaunchKernelGGL(kernel, grid, block, 0, pair.stream, args...);
+    }
+    VrEventRef stop() const { return events_stop(c->events, pair); }      // this launch's own stop event as a dependency; none: not stamped, or no launch
     ~VrKernelScope();
 };
-// launch under a scope created with attach = true
-#define VR_LAUNCH_TIMED(scope, kernel, grid, block, stream, ...) do { \
-        if ((scope).e0 && (scope).e1) { hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, (scope).e0, (scope).e1, 0, __VA_ARGS__); (scope).launched(); } \
-        else hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__); } while (0)
-
 struct vr_gbuffer {
     vr_context* ctx;
     int w, h;
@@ -486,7 +467,7 @@ int vr_terrain_frame_scratch(vr_terrain* t, bool report, const std::function<int
 // or NULL) and is exactly vr_terrain_render where it does not
 int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
                            int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
-                           bool* fused, hipEvent_t* fused_stop);
+                           bool* fused, VrEventRef* fused_stop);
 // the lighting passes as vr_frame_submit queues them: vr_light_check, vr_light_queue (vr_deferred_dev.h)
 // The tone-map stage (vr_tonemap.hip): the steps of `steps` (TmStep, vr_tonemap_plan.h) in their order - reset, histogram, all-reduce
 // over `comm`, exposure, render - behind every refusal of every one of them; queue = false: the refusals alone.  `frame`:

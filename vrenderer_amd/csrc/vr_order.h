@@ -54,38 +54,38 @@
 //                           growth, or of the host's next write into pinned memory a queued copy reads
 #pragma once
 
+#include "vr_events.h"
+
 #include <stddef.h>
 #include <stdint.h>
 
 #define VR_ORDER_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
-// A point on a stream that others may wait for: the stop event a launch's dispatch stamped, taken in timing epoch `epoch` (handles
-// to such events are only good until the context recycles its pool, which synchronises the stream first: a mark of an older
-// epoch counts as complete - the event may since have been re-recorded for an unrelated kernel), or this mark's own event,
-// recorded explicitly (epoch 0: always valid).  Unset until the first of either.
+// A point on a stream that others may wait for: the stop event a launch's dispatch stamped, as the handle vr_events.h gave out
+// for it (such a handle denotes its launch only until the event's source reissues it; what a wait does afterwards is that
+// header's rule, events_wait_needed), or this mark's own event, recorded explicitly (always valid).  Unset until the first of either.
 template <class Event> struct OrderMark {
     Event own{};             // created and destroyed by the owner of the mark
-    Event at{};
-    uint64_t epoch = 0;
+    EventRef<Event> at;
     bool set = false;
 };
-template <class Event> void order_mark_stamped(OrderMark<Event>& m, Event stop, uint64_t epoch) { m.at = stop; m.epoch = epoch; m.set = true; }
+template <class Event> void order_mark_stamped(OrderMark<Event>& m, const EventRef<Event>& stop) { m.at = stop; m.set = true; }
 template <class Event, class Stream, class Ops> int order_mark_record(OrderMark<Event>& m, const Ops& ops, Stream s)
 {
     VR_ORDER_TRY(ops.record(m.own, s));
-    m.at = m.own; m.epoch = 0; m.set = true;
+    m.at = { m.own, 0, 0 }; m.set = true;
     return 0;
 }
 // the stamped stop event if there is one, else a record
-template <class Event, class Stream, class Ops> int order_mark_here(OrderMark<Event>& m, const Ops& ops, Stream s, Event stop, uint64_t epoch)
+template <class Event, class Stream, class Ops> int order_mark_here(OrderMark<Event>& m, const Ops& ops, Stream s, const EventRef<Event>& stop)
 {
-    if (stop != Event{}) { order_mark_stamped(m, stop, epoch); return 0; }
+    if (stop.ev != Event{}) { order_mark_stamped(m, stop); return 0; }
     return order_mark_record(m, ops, s);
 }
-template <class Event, class Stream, class Ops> int order_mark_wait(const OrderMark<Event>& m, const Ops& ops, Stream s, uint64_t epoch_now)
+template <class Event, class Stream, class Ops> int order_mark_wait(const OrderMark<Event>& m, const Ops& ops, Stream s, const EventSupply<Event>& events)
 {
-    if (!m.set || (m.epoch != 0 && m.epoch != epoch_now)) return 0;
-    return ops.wait(s, m.at);
+    if (!m.set || !events_wait_needed(events, m.at)) return 0;
+    return ops.wait(s, m.at.ev);
 }
 
 // A reader that nobody has waited for yet.
@@ -130,7 +130,7 @@ template <class Event> struct OrderImage {
 // yet - ScratchState::pending - would be waited for here, too.)
 template <class Stream, class Event, class Ops>
 int order_begin_chain(OrderTerrain<Event>& t, OrderSet<Stream, Event>& g, const Ops& ops, const Stream (&geo_streams)[2], unsigned& turn,
-                      Stream main, bool single_stream, uint64_t epoch_now)
+                      Stream main, bool single_stream, const EventSupply<Event>& events)
 {
     g.stream = geo_streams[turn++ & 1u];
     g.main_waited = false;
@@ -138,9 +138,9 @@ int order_begin_chain(OrderTerrain<Event>& t, OrderSet<Stream, Event>& g, const 
         VR_ORDER_TRY(ops.record(t.ev_changed, main));
         g.main_dep.pending = true;
     }
-    VR_ORDER_TRY(order_mark_wait(g.chain, ops, g.stream, epoch_now));
+    VR_ORDER_TRY(order_mark_wait(g.chain, ops, g.stream, events));
     VR_ORDER_TRY(order_pending_wait(g.sel_read, ops, g.stream));
-    VR_ORDER_TRY(order_mark_wait(g.tile_pass, ops, g.stream, epoch_now));
+    VR_ORDER_TRY(order_mark_wait(g.tile_pass, ops, g.stream, events));
     return order_pending_wait(g.main_dep, ops, g.stream);
 }
 
@@ -161,9 +161,9 @@ template <class Stream, class Event, class Ops> int order_end_chain(OrderSet<Str
 
 // in front of order_begin_chain: on the stream it takes next
 template <class Stream, class Event, class Ops>
-int order_prepare_start(const OrderTerrain<Event>& t, const Ops& ops, const Stream (&geo_streams)[2], unsigned turn, uint64_t epoch_now)
+int order_prepare_start(const OrderTerrain<Event>& t, const Ops& ops, const Stream (&geo_streams)[2], unsigned turn, const EventSupply<Event>& events)
 {
-    return order_mark_wait(t.hint, ops, geo_streams[turn & 1u], epoch_now);
+    return order_mark_wait(t.hint, ops, geo_streams[turn & 1u], events);
 }
 template <class Stream, class Event, class Ops>
 int order_prepare_wait(OrderSet<Stream, Event>& g, const Ops& ops, Stream main, bool other_prepared)
@@ -175,21 +175,20 @@ int order_prepare_wait(OrderSet<Stream, Event>& g, const Ops& ops, Stream main, 
     return 0;
 }
 
-// `prepared`: the set's chain was built ahead by vr_terrain_prepare; `last_stop`: the stop event of the most recent stamped
-// launch on the stream if such events serve as dependencies (VR_OPT_DISPATCH_EVENTS) and there is one, else Event{}
+// `prepared`: the set's chain was built ahead by vr_terrain_prepare; `hint`: events_start_hint - the stop event of the most recent
+// stamped launch on the stream if such events serve as dependencies (VR_OPT_DISPATCH_EVENTS) and there is one, else none
 template <class Stream, class Event, class Ops>
-int order_tile_pass_begin(OrderTerrain<Event>& t, OrderSet<Stream, Event>& g, const Ops& ops, Stream main, bool prepared, Event last_stop,
-                          uint64_t epoch_now)
+int order_tile_pass_begin(OrderTerrain<Event>& t, OrderSet<Stream, Event>& g, const Ops& ops, Stream main, bool prepared, const EventRef<Event>& hint)
 {
     if (!(prepared && g.main_waited && g.main_wait_stream == main)) VR_ORDER_TRY(ops.wait(main, g.chain.own));
     g.main_waited = false;
-    return order_mark_here(t.hint, ops, main, last_stop, epoch_now);
+    return order_mark_here(t.hint, ops, main, hint);
 }
-// `stop`: the pass's own dispatch-stamped stop event, Event{} if it was not stamped (or nothing was launched)
+// `stop`: the pass's own dispatch-stamped stop event (events_stop), none if it was not stamped (or nothing was launched)
 template <class Stream, class Event, class Ops>
-int order_tile_pass_launched(OrderSet<Stream, Event>& g, const Ops& ops, Stream main, Event stop, uint64_t epoch_now)
+int order_tile_pass_launched(OrderSet<Stream, Event>& g, const Ops& ops, Stream main, const EventRef<Event>& stop)
 {
-    return order_mark_here(g.tile_pass, ops, main, stop, epoch_now);
+    return order_mark_here(g.tile_pass, ops, main, stop);
 }
 // for every OTHER set that holds a prepared frame, behind the tile pass
 template <class Stream, class Event, class Ops> int order_wait_ahead(OrderSet<Stream, Event>& p, const Ops& ops, Stream main)
@@ -203,7 +202,7 @@ template <class Stream, class Event, class Ops> int order_wait_ahead(OrderSet<St
 template <class Stream, class Event, class Ops, size_t N>
 int order_terrain_changing(OrderSet<Stream, Event>* const (&sets)[N], const Ops& ops, Stream main)
 {
-    for (OrderSet<Stream, Event>* g : sets) VR_ORDER_TRY(order_mark_wait(g->chain, ops, main, 0));
+    for (OrderSet<Stream, Event>* g : sets) if (g->chain.set) VR_ORDER_TRY(ops.wait(main, g->chain.own));
     return 0;
 }
 template <class Stream, class Event, class Ops, size_t N>
@@ -217,9 +216,9 @@ int order_terrain_changed(OrderTerrain<Event>& t, OrderSet<Stream, Event>* const
 // A write of the maps' tables on the context's stream (vr_terrain_edit), next to order_terrain_changing: behind every set's tile
 // pass, which reads them - on whatever stream the context had when that pass was queued.
 template <class Stream, class Event, class Ops, size_t N>
-int order_terrain_tables_changing(OrderSet<Stream, Event>* const (&sets)[N], const Ops& ops, Stream main, uint64_t epoch_now)
+int order_terrain_tables_changing(OrderSet<Stream, Event>* const (&sets)[N], const Ops& ops, Stream main, const EventSupply<Event>& events)
 {
-    for (OrderSet<Stream, Event>* g : sets) VR_ORDER_TRY(order_mark_wait(g->tile_pass, ops, main, epoch_now));
+    for (OrderSet<Stream, Event>* g : sets) VR_ORDER_TRY(order_mark_wait(g->tile_pass, ops, main, events));
     return 0;
 }
 
@@ -229,10 +228,10 @@ template <class Stream, class Event, class Ops> int order_image_writer_begins(Or
 }
 // the writing pass has been launched on `writer` and a stage on ANOTHER stream reads next; `stop` as in order_tile_pass_launched
 template <class Stream, class Event, class Ops>
-int order_image_written(OrderImage<Event>& im, const Ops& ops, Stream writer, Stream reader, Event stop, uint64_t epoch_now)
+int order_image_written(OrderImage<Event>& im, const Ops& ops, Stream writer, Stream reader, const EventRef<Event>& stop, const EventSupply<Event>& events)
 {
-    VR_ORDER_TRY(order_mark_here(im.written, ops, writer, stop, epoch_now));
-    return order_mark_wait(im.written, ops, reader, epoch_now);
+    VR_ORDER_TRY(order_mark_here(im.written, ops, writer, stop));
+    return order_mark_wait(im.written, ops, reader, events);
 }
 template <class Stream, class Event, class Ops> int order_image_reader_done(OrderImage<Event>& im, const Ops& ops, Stream reader)
 {

@@ -370,7 +370,7 @@ static int ensure_pyramid(vr_terrain* t, PyrDesc* out)
         if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipFree(p); vr_set_error("terrain query: hipEventCreate failed"); return VR_ERR_HIP; }
     }
     {
-        VrKernelScope ks(t->ctx, VR_K_QUERY_PYRAMID);
+        VrKernelScope ks(t->ctx, VR_K_QUERY_PYRAMID, t->ctx->stream);
         const int w0 = t->height.w0, h0 = t->height.h0, lv1 = t->height.levels > 1 ? 1 : 0;
         vr_derive_pyramid(t->height, *out, p, dirty_whole(w0, h0), dirty_whole(dirty_level_size(w0, lv1), dirty_level_size(h0, lv1)), s);
     }
@@ -409,7 +409,7 @@ extern "C" VR_API int vr_terrain_query_heights(vr_terrain* t, const float* xz, u
         VR_HIP(hipMemcpyAsync(base, xz, b_xz, hipMemcpyHostToDevice, s));
     }
     {
-        VrKernelScope ks(t->ctx, VR_K_QUERY_HEIGHTS);
+        VrKernelScope ks(t->ctx, VR_K_QUERY_HEIGHTS, t->ctx->stream);
         hipLaunchKernelGGL(k_query_heights, dim3(grid_for(n)), dim3(256), 0, s, t->height, a, d_xz, n, d_h, d_n);
     }
     VR_HIP(hipGetLastError());
@@ -446,7 +446,7 @@ extern "C" VR_API int vr_terrain_cast_rays(vr_terrain* t, const vr_ray* rays, ui
     a.step_cap = 4 * (t->height.w0 + t->height.h0) + 64 * pd.levels;
     if (!device_pointers) VR_HIP(hipMemcpyAsync((void*)d_rays, rays, b, hipMemcpyHostToDevice, s));
     {
-        VrKernelScope ks(t->ctx, VR_K_QUERY_RAYS);
+        VrKernelScope ks(t->ctx, VR_K_QUERY_RAYS, t->ctx->stream);
         hipLaunchKernelGGL(k_query_rays, dim3(grid_for(n)), dim3(256), 0, s, t->height, a, pd, (const uchar2*)t->d_pyramid, d_rays, n, d_hits);
     }
     VR_HIP(hipGetLastError());

@@ -1807,7 +1807,7 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
     const VrOrderOps ops;
     int rc;
     // this chain's stream, behind whatever still uses the set (single-stream mode: behind everything queued so far)
-    if ((rc = order_begin_chain(t->ord, g.ord, ops, t->geo_streams, t->geo_turn, ctx->stream, !ctx->async_geometry, ctx->ev_epoch))) return rc;
+    if ((rc = order_begin_chain(t->ord, g.ord, ops, t->geo_streams, t->geo_turn, ctx->stream, !ctx->async_geometry, ctx->events))) return rc;
     hipStream_t s = ctx->stream, gs = g.ord.stream;
     if (selection_from == nullptr) {                                   // TerrainPass.cpp:173-190
         if ((rc = vr_select_launch(t, g, view, rp->max_height, gs))) return rc;
@@ -1929,7 +1929,7 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
     // with the previous frame's lighting pass (bandwidth-bound) instead of with a tile pass (which leaves
     // half of every CU's wave slots free).  (Measured again in round 2, 8K: geometry under the tile pass 483 + 211 us,
     // frame 0.715 ms; geometry under the lighting pass 462 + 239 us, frame 0.723 ms.)
-    if ((rc = order_prepare_start(t->ord, VrOrderOps(), t->geo_streams, t->geo_turn, t->ctx->ev_epoch))) return rc;
+    if ((rc = order_prepare_start(t->ord, VrOrderOps(), t->geo_streams, t->geo_turn, t->ctx->events))) return rc;
     if ((rc = launch_geometry(t, g, nullptr, view, rp, a, pt))) return rc;
     // Where the context's stream waits for this chain.  Never in front of the tile pass that consumes it (the lighting pass ->
     // tile pass boundary then holds no cross-stream wait) and never earlier than it has to:
@@ -1952,7 +1952,7 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
 // leave everything the unfused pair leaves; where it does not apply the call queues exactly the unfused tile pass and reports
 // "not fused".  stop_out: the fused launch's own dispatch-stamped stop event (NULL: the launch was not stamped).
 struct LitRequest { const vr_light* lights; int32_t num_lights; const float* amb_top; const float* amb_bottom; vr_image* hdr;
-                    bool keep; hipEvent_t* stop_out; };
+                    bool keep; VrEventRef* stop_out; };
 // The facts raster_plan() decides on.  Whether a lit request's light list is the lighting pass's plain case is one of them:
 // the list goes through vr_deferred_make_args here (*la, *lights_rc).
 static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view, const vr_gbuffer* gb, const vr_render_params* rp,
@@ -2060,9 +2060,9 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     // the tile pass consumes verts + bins; vr_terrain_prepare's start hint: with dispatch-stamped events the stop event of whatever
     // ran last on the stream (the previous frame's lighting pass)
     const VrOrderOps ops;
-    if ((rc = order_tile_pass_begin(t->ord, g.ord, ops, s, use_prepared, ctx->dispatch_events ? ctx->last_stop : nullptr, ctx->ev_epoch))) return rc;
+    if ((rc = order_tile_pass_begin(t->ord, g.ord, ops, s, use_prepared, events_start_hint(ctx->events)))) return rc;
     const uint32_t spec_const = vr_specular_constant(ctx);               // terrain_ps.hlsl:76 -> SRGBA8
-    hipEvent_t pass_stop = nullptr;
+    VrEventRef pass_stop;
     if (grid > 0) {
         // a depth-only tile pass (the shadow map's) is timed under its own id: it is an order of magnitude shorter than the
         // G-buffer pass and must not be averaged with it
@@ -2096,13 +2096,13 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
                            (const uint4*)g.d_recs, t->scratch_tris(), g.d_tile_cursor, g.d_tile_offset, g.d_bin_entries, tiles, g.d_counters + C_CLASS0, \
                            gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, ctx->d_srgb_thr, ctx->d_enc_tab, spec_const, plan.ranges ? gb->d_ranges : (uint2*)nullptr, region
         const RasterKernel k = raster_kernel(plan.variant);
-        if (k.lit) VR_LAUNCH_TIMED(ks, k.lit, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, la);
-        else VR_LAUNCH_TIMED(ks, k.plain, dim3(grid), dim3(kRT), s, VR_RASTER_ARGS, LitNone());
+        if (k.lit) ks.launch(k.lit, dim3(grid), dim3(kRT), VR_RASTER_ARGS, la);
+        else ks.launch(k.plain, dim3(grid), dim3(kRT), VR_RASTER_ARGS, LitNone());
 #undef VR_RASTER_ARGS
         pass_stop = ks.stop();                                                // stamped by the dispatch: complete when the tile pass is
         if (plan.keep && lit_req->stop_out) *lit_req->stop_out = pass_stop;
     }
-    if ((rc = order_tile_pass_launched(g.ord, ops, s, pass_stop, ctx->ev_epoch))) return rc;
+    if ((rc = order_tile_pass_launched(g.ord, ops, s, pass_stop))) return rc;
     // chains prepared further ahead whose wait vr_terrain_prepare left for later: behind this tile pass
     for (GeoSet& p : t->sets)
         if (&p != &g && p.prepared && (rc = order_wait_ahead(p.ord, ops, s))) return rc;
@@ -2169,11 +2169,11 @@ int vr_terrain_materialise_pending(vr_terrain* t) { return t->pending_target ? v
 // queues the lighting pass itself otherwise)
 int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
                            int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
-                           bool* fused, hipEvent_t* fused_stop)
+                           bool* fused, VrEventRef* fused_stop)
 {
     const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, true, fused_stop };
     int earlier = VR_OK;
-    *fused = false; *fused_stop = nullptr;
+    *fused = false; *fused_stop = {};
     const int rc = terrain_render_impl(t, view, gb, rp, nullptr, &req, fused, &earlier, render_mode_of(t->ctx));
     return rc ? rc : earlier;
 }

@@ -430,7 +430,7 @@ extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
     static_assert(kGeoSets == 3, "the list below");
     VrOrderSet* const ord_sets[kGeoSets] = { &t->sets[0].ord, &t->sets[1].ord, &t->sets[2].ord };
     { const int rc = order_terrain_changing(ord_sets, VrOrderOps(), t->ctx->stream); if (rc) return rc; }
-    VrKernelScope ks(t->ctx, VR_K_NODE_HEIGHTS);
+    VrKernelScope ks(t->ctx, VR_K_NODE_HEIGHTS, t->ctx->stream);
     for (int surf = 0; surf < num_surfaces; surf++) { const int rc = vr_node_heights_surface(t, surf, vr_node_surface(t, surf)); if (rc) return rc; }
     VR_HIP(hipGetLastError());
     { const int rc = order_terrain_changed(t->ord, ord_sets, VrOrderOps(), t->ctx->stream); if (rc) return rc; }
@@ -699,7 +699,7 @@ extern "C" VR_API int vr_terrain_select(vr_terrain* t, const vr_view* view, floa
     const int gi = vr_terrain_pick_set(t);                         // a set no tile pass in flight is reading
     GeoSet& g = t->sets[gi];
     // (not part of a frame: never behind the context's stream as a whole, whatever VR_OPT_ASYNC_GEOMETRY says)
-    int rc = order_begin_chain(t->ord, g.ord, VrOrderOps(), t->geo_streams, t->geo_turn, t->ctx->stream, false, t->ctx->ev_epoch);
+    int rc = order_begin_chain(t->ord, g.ord, VrOrderOps(), t->geo_streams, t->geo_turn, t->ctx->stream, false, t->ctx->events);
     if (rc) return rc;
     g.prepared = false;
     if ((rc = vr_select_launch(t, g, view, max_height, g.ord.stream))) return rc;

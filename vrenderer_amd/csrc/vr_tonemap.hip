@@ -430,7 +430,7 @@ int vr_tonemap_stage(vr_tonemap* tm, const TmStageCall& c, bool queue)
     const int32_t* owned = pt ? pt->d_owned_tiles : nullptr;
     if (c.steps & TM_RESET) VR_HIP(hipMemsetAsync(tm->d_hist, 0, sizeof(uint32_t) * VR_TONEMAP_BINS, ctx->stream));
     if (c.steps & TM_HISTOGRAM) {
-        VrKernelScope ks(ctx, VR_K_TM_HISTOGRAM);
+        VrKernelScope ks(ctx, VR_K_TM_HISTOGRAM, ctx->stream);
         if (plan.launch && plan.family == TM_SCALAR) hipLaunchKernelGGL(k_tm_histogram_scalar, dim3(plan.hist_grid), dim3(256), 0, ctx->stream, a, (const uint2*)hdr->data, tm->d_hist);
         else if (plan.launch) hipLaunchKernelGGL(kHistKernels[plan.family], dim3(plan.hist_grid), dim3(256), 0, ctx->stream, a, (const void*)hdr->data, owned, plan.blocks, tm->d_hist);
         VR_HIP(hipGetLastError());
@@ -439,14 +439,14 @@ int vr_tonemap_stage(vr_tonemap* tm, const TmStageCall& c, bool queue)
     if (c.steps & TM_EXPOSURE) {
         const float k_up = (float)(1.0 - exp(-(double)c.frame_time * (double)p->eye_adaptation_speed_up));
         const float k_down = (float)(1.0 - exp(-(double)c.frame_time * (double)p->eye_adaptation_speed_down));
-        VrKernelScope ks(ctx, VR_K_TM_EXPOSURE);
+        VrKernelScope ks(ctx, VR_K_TM_EXPOSURE, ctx->stream);
         hipLaunchKernelGGL(k_tm_exposure, dim3(1), dim3(256), 0, ctx->stream, (const uint32_t*)tm->d_hist, tm->d_exposure, a.scale, a.bias,
                            p->histogram_low_percentile, p->histogram_high_percentile, p->min_log_luminance, p->min_adapted_luminance,
                            p->max_adapted_luminance, k_up, k_down, p->eye_adaptation_speed_up > 0.0f ? 1 : 0, p->eye_adaptation_speed_down > 0.0f ? 1 : 0);
         VR_HIP(hipGetLastError());
     }
     if (c.steps & TM_RENDER) {
-        VrKernelScope ks(ctx, VR_K_TONEMAP);
+        VrKernelScope ks(ctx, VR_K_TONEMAP, ctx->stream);
         if (plan.launch && plan.family == TM_SCALAR) hipLaunchKernelGGL(k_tonemap_scalar, dim3(plan.map_grid), dim3(256), 0, ctx->stream, a, (const uint2*)hdr->data,
                                                                         (const float*)tm->d_exposure, (uint32_t*)c.ldr, ctx->d_srgb_thr, ctx->d_enc_tab);
         else if (plan.launch) hipLaunchKernelGGL(kMapKernels[plan.family], dim3(plan.map_grid), dim3(256), 0, ctx->stream, a, (const void*)hdr->data, owned,
@@ -517,7 +517,7 @@ extern "C" VR_API int vr_frame_detile_ldr(vr_context* ctx, const void* gathered,
     const PartTables* pt = nullptr;
     { int rc = vr_partition_slot_tables(ctx, w, h, world, &pt); if (rc) return rc; }
     const size_t quads = (size_t)w * h / 4;
-    VrKernelScope ks(ctx, VR_K_DETILE_LDR);
+    VrKernelScope ks(ctx, VR_K_DETILE_LDR, ctx->stream);
     hipLaunchKernelGGL(k_detile_ldr, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, ctx->stream, (const uint8_t*)gathered,
                        (uint4*)frame, w, h, (w + VR_OWNER_TILE - 1) / VR_OWNER_TILE, pt->d_tile_slot);
     VR_HIP(hipGetLastError());
