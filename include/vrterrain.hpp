@@ -217,6 +217,17 @@ namespace vRenderer
         {
             return Check(vr_terrain_brush(m_Terrain, &stroke, dabs, n, outRect), "vr_terrain_brush");
         }
+        // vr_terrain_texture: level 0 of the albedo painted by rule from the heightmap's shape - numLayers altitude and slope layers,
+        // applied in order - under the mask the n dabs form (as for Erode, prepared for the albedo), or over the whole map
+        // (wholeMap: dabs == nullptr, n == 0); computed on the device, stream-ordered like Brush, nothing is synchronised, and
+        // `layers` and `dabs` are free again when the call returns.  maxHeight: the world height of byte 255.  outRect as for Brush.
+        bool Texture(const vr_texture_layer* layers, int32_t numLayers, float maxHeight, const vr_brush_dab* dabs, uint32_t n, bool wholeMap = false,
+                     int32_t outRect[4] = nullptr)
+        {
+            vr_texture_params p = {};
+            p.num_layers = numLayers; p.flags = wholeMap ? (uint32_t)VR_TEXTURE_WHOLE_MAP : 0u; p.max_height = maxHeight;
+            return Check(vr_terrain_texture(m_Terrain, &p, layers, dabs, n, outRect), "vr_terrain_texture");
+        }
         // vr_terrain_erode: `iterations` sweeps of thermal erosion of the heightmap's level 0 under the mask the n dabs form (strength =
         // opacity; their order does not matter), computed on the device; stream-ordered like Brush, nothing is synchronised.
         // talus: the height step per texel that stays, in heightmap steps; rate: 0 < rate <= 0.125.  outRect as for Brush.

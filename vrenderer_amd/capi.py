@@ -41,6 +41,8 @@ VR_BRUSH_SMOOTH = 2
 VR_BRUSH_PAINT = 3
 VR_HISTORY_MAX_RECORDS = 4096
 VR_ERODE_MAX_ITERATIONS = 1024
+VR_TEXTURE_MAX_LAYERS = 8
+VR_TEXTURE_WHOLE_MAP = 1
 VR_HYDRO_MAX_ITERATIONS = 1024
 
 
@@ -178,6 +180,18 @@ class HydroParams(C.Structure):
                 ("deposit", C.c_float), ("evaporation", C.c_float), ("reserved", C.c_int32)]
 
 
+class TextureLayer(C.Structure):
+    """vr_texture_layer: a colour (stored encoding, 0 .. 255) and an opacity, weighed by an altitude band in world units of height and
+    a slope band in degrees (0 <= lo <= hi <= 89), each faded over `fade` outside its ends (vr_terrain_texture)."""
+    _fields_ = [("color", C.c_float * 4), ("opacity", C.c_float), ("alt_lo", C.c_float), ("alt_hi", C.c_float), ("alt_fade", C.c_float),
+                ("slope_lo", C.c_float), ("slope_hi", C.c_float), ("slope_fade", C.c_float), ("channel_mask", C.c_uint32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class TextureParams(C.Structure):
+    _fields_ = [("num_layers", C.c_int32), ("flags", C.c_uint32), ("max_height", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
 class HistoryStatus(C.Structure):
     """vr_history_status: what undo / redo can apply now, the open step, the steps lost to the budget, the arena's bytes."""
     _fields_ = [("undo_steps", C.c_uint32), ("redo_steps", C.c_uint32), ("open_records", C.c_uint32), ("dropped_steps", C.c_uint32),
@@ -187,6 +201,7 @@ class HistoryStatus(C.Structure):
 assert C.sizeof(HistoryStatus) == 32
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32 and C.sizeof(ErodeParams) == 32 and C.sizeof(HydroParams) == 32
+assert C.sizeof(TextureLayer) == 64 and C.sizeof(TextureParams) == 32
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -210,7 +225,7 @@ EXPORTS = [
     "vr_tonemap_default_params", "vr_tonemap_create", "vr_tonemap_destroy", "vr_tonemap_reset_exposure", "vr_tonemap_reset_histogram",
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
-    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_debug_terrain_query_pyramid", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush", "vr_terrain_erode", "vr_debug_erode_config",
+    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_debug_terrain_query_pyramid", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush", "vr_terrain_texture", "vr_terrain_erode", "vr_debug_erode_config",
     "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
 ]
@@ -337,6 +352,7 @@ def load_library():
         "vr_view_pixel_ray": (C.c_int, [P(View), C.c_float, C.c_float, P(Ray)]),
         "vr_terrain_edit": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int]),
         "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),
+        "vr_terrain_texture": (C.c_int, [vp, P(TextureParams), vp, vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_erode": (C.c_int, [vp, P(ErodeParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_debug_erode_config": (C.c_int, [P(C.c_int32)]),
         "vr_terrain_erode_hydraulic": (C.c_int, [vp, P(HydroParams), vp, C.c_uint32, P(C.c_int32)]),

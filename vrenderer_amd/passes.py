@@ -547,6 +547,39 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_brush(self.handle, C.byref(stroke), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_brush")
         return tuple(int(v) for v in rect)
 
+    def Texture(self, layers, dabs=None, max_height=400.0, whole_map=False):
+        """vr_terrain_texture: level 0 of the albedo painted by rule from the heightmap's shape, computed on the device; stream-ordered,
+        nothing is synchronised.  `layers`: 1 .. 8 of them, applied in order - dicts with the keys color (four stored bytes' worth,
+        0 .. 255), opacity, alt_lo, alt_hi, alt_fade (world units of height), slope_lo, slope_hi, slope_fade (degrees) and
+        channel_mask (default 0xF), or rows of those twelve numbers in that order.  `dabs`: rows as for Erode (strength an opacity),
+        prepared for the albedo map; their mask limits the call.  whole_map=True takes no dabs: mask 1 on every texel.
+        `max_height`: the world height of byte 255.  Returns (x, y, w, h) of the level-0 rectangle of the albedo the call treated as
+        dirty, (0, 0, 0, 0) when no dab meets the map."""
+        arr = (capi.TextureLayer * max(len(layers), 1))()
+        for dst, l in zip(arr, layers):
+            if not isinstance(l, dict):
+                row = [float(v) for v in l]
+                l = dict(color=row[0:4], opacity=row[4], alt_lo=row[5], alt_hi=row[6], alt_fade=row[7], slope_lo=row[8], slope_hi=row[9],
+                         slope_fade=row[10], channel_mask=int(row[11]))
+            dst.color[:] = [float(c) for c in l["color"]]
+            dst.opacity = float(l["opacity"])
+            dst.alt_lo, dst.alt_hi, dst.alt_fade = float(l["alt_lo"]), float(l["alt_hi"]), float(l["alt_fade"])
+            dst.slope_lo, dst.slope_hi, dst.slope_fade = float(l["slope_lo"]), float(l["slope_hi"]), float(l["slope_fade"])
+            dst.channel_mask = int(l.get("channel_mask", 0xF))
+        a = np.asarray(dabs if dabs is not None else np.zeros((0, 5), np.float32), np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 5)
+        assert a.ndim == 2 and a.shape[1] in (5, 8)
+        if a.shape[1] == 5:
+            full = np.zeros((a.shape[0], 8), np.float32)
+            full[:, :5] = a
+            a = full
+        a = np.ascontiguousarray(a)
+        params = capi.TextureParams(num_layers=len(layers), flags=capi.VR_TEXTURE_WHOLE_MAP if whole_map else 0, max_height=float(max_height))
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_texture(self.handle, C.byref(params), arr, _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_texture")
+        return tuple(int(v) for v in rect)
+
     def Erode(self, dabs, iterations, talus, rate):
         """vr_terrain_erode: `iterations` sweeps of thermal erosion on level 0 of the heightmap under the mask the dabs form (rows as
         for Brush, strength an opacity in [0, 1]; their order does not matter), computed on the device; stream-ordered, nothing is
