@@ -543,6 +543,21 @@ VR_API int vr_terrain_cast_rays(vr_terrain* t, const vr_ray* rays, uint32_t n, f
  * out_dims, `out` untouched.  VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with nothing written: NULL t,
  * out_levels or out_dims; NULL out with a capacity; a capacity below 2 bytes per cell of all levels together. */
 VR_API int vr_debug_terrain_query_pyramid(vr_terrain* t, int32_t* out_levels, int32_t out_dims[2 * 16], uint8_t* out, size_t capacity_bytes);
+/* test helper: one level of one decoded table of a map - what every tile pass and every height query reads instead of the mip chain -
+ * as it is on the device.  which: 0 heightmap, 1 albedo.  Level l of a w0 x h0 map has w = max(1, w0 >> l) by h = max(1, h0 >> l) texels;
+ * t(x, y) = (float)byte / 255.0f of the clamp-addressed texel (min(max(x, 0), w - 1), min(max(y, 0), h - 1)), lin() the sRGB decode:
+ *   VR_DEBUG_TABLE_QUAD   heightmap  (w + 2) x (h + 2) uint32   entry (ix, iy): bytes (ix-1, iy-1) | (ix, iy-1) << 8 | (ix-1, iy) << 16 | (ix, iy) << 24
+ *   VR_DEBUG_TABLE_QUADF  heightmap  (w + 2) x (h + 2) float[4] (t00, t10 - t00, t01, t11 - t01) of the same four texels
+ *   VR_DEBUG_TABLE_FAST   both       (w + 3) x (h + 3) float[4] heightmap: as QUADF; albedo: (lin r, lin g, lin b, 0) of texel (ix-1, iy-1)
+ *   VR_DEBUG_TABLE_RGBF   albedo     w x h float[4]             (lin r, lin g, lin b, 0) of texel (ix, iy)
+ * out_dims receives {entries per row, rows} and `out` the entries, row-major and densely packed (padding between levels is never shown).
+ * The copy runs on the context's stream - behind the tables' last writer as a tile pass's read of them is - and the entry returns when
+ * it has completed; no kernel is launched and nothing is built.  out == NULL with capacity_bytes == 0 is a size query.  A table the map
+ * does not have (QUAD / QUADF of the albedo, RGBF of the heightmap) or a level beyond the chain: VR_OK, zero out_dims, `out` untouched.
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with nothing written: NULL t or out_dims; which not 0 or 1; an
+ * unknown table; a negative level; NULL out with a capacity; a capacity below the level's entries. */
+enum { VR_DEBUG_TABLE_QUAD = 0, VR_DEBUG_TABLE_QUADF = 1, VR_DEBUG_TABLE_FAST = 2, VR_DEBUG_TABLE_RGBF = 3 };
+VR_API int vr_debug_terrain_tables(vr_terrain* t, int which, int table, int32_t level, int32_t out_dims[2], void* out, size_t capacity_bytes);
 /* Host only (picking; QuadTree.h:84 is what the reference would have called with it): the ray through the centre of pixel
  * (px, py) of view's viewport - screen point (px + 0.5, py + 0.5); fractional px, py are allowed.  The two ends are the
  * points world_to_clip sends to (x, y, 0) and (x, y, 1), solved in double (the inverse of the matrix a renderer projects with;

@@ -35,6 +35,36 @@ def test_library_exports_every_declared_symbol(product_lib):
         assert hasattr(product_lib, name), name
 
 
+def test_the_tables_read_back_is_declared_exported_and_refuses_before_the_device(product_lib):
+    """vr_debug_terrain_tables: the header's signature and table ids, capi's export and argtypes, and every argument refusal - each
+    comes before any use of the device (there is none here) and leaves out_dims, `out` and the terrain as they were.  A terrain with
+    no chain (zeroed memory stands in for it) has no level 0: VR_OK, zero out_dims, `out` untouched."""
+    header = open(os.path.join(ROOT, "include", "vrterrain.h")).read()
+    assert re.search(r"VR_API\s+int\s+vr_debug_terrain_tables\s*\(\s*vr_terrain\*\s*t,\s*int which,\s*int table,\s*int32_t level,\s*int32_t out_dims\[2\],"
+                     r"\s*void\*\s*out,\s*size_t capacity_bytes\)", header)
+    assert re.search(r"enum\s*\{\s*VR_DEBUG_TABLE_QUAD = 0,\s*VR_DEBUG_TABLE_QUADF = 1,\s*VR_DEBUG_TABLE_FAST = 2,\s*VR_DEBUG_TABLE_RGBF = 3\s*\}", header)
+    assert (capi.VR_DEBUG_TABLE_QUAD, capi.VR_DEBUG_TABLE_QUADF, capi.VR_DEBUG_TABLE_FAST, capi.VR_DEBUG_TABLE_RGBF) == (0, 1, 2, 3)
+    fn = product_lib.vr_debug_terrain_tables
+    assert "vr_debug_terrain_tables" in capi.EXPORTS and fn.restype is C.c_int
+    assert list(fn.argtypes) == [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_size_t]
+    fake = C.create_string_buffer(1 << 20)
+    t = C.cast(fake, C.c_void_p)
+    dims, out = (C.c_int32 * 2)(-1, -1), (C.c_uint8 * 16)(*([5] * 16))
+    inv = capi.VR_ERR_INVALID_ARGUMENT
+    for args in ((None, 0, 2, 0, dims, out, 16), (None, 0, 2, 0, dims, None, 0), (t, 2, 2, 0, dims, out, 16), (t, -1, 2, 0, dims, out, 16),
+                 (t, 0, 4, 0, dims, out, 16), (t, 0, -1, 0, dims, out, 16), (t, 1, 2, -1, dims, out, 16), (t, 0, 0, 0, None, out, 16),
+                 (t, 0, 0, 0, dims, None, 16)):
+        assert fn(*args) == inv, args[1:4]
+    assert b"capacity" in product_lib.vr_last_error()
+    assert list(dims) == [-1, -1] and list(out) == [5] * 16 and bytes(fake) == bytes(1 << 20)
+    for which in (0, 1):
+        for table in range(4):
+            for args in ((None, 0), (out, 16)):
+                dims[0] = dims[1] = -1
+                assert fn(t, which, table, 0, dims, *args) == capi.VR_OK and list(dims) == [0, 0], (which, table)
+    assert list(out) == [5] * 16 and bytes(fake) == bytes(1 << 20)
+
+
 def test_struct_layouts_match_header():
     assert C.sizeof(capi.Instance) == 112 and C.sizeof(capi.Light) == 64
     assert C.sizeof(capi.TerrainParams) == 40 and C.sizeof(capi.RenderParams) == 32

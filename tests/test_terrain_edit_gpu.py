@@ -17,6 +17,7 @@ from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_ca
 from tests.fusion_common import PLANES, download_frame
 from tests import pyramid_model as pm
 from tests import queries_common as qc
+from tests import tables_model as tm
 from tests.f64_queries import Surface64
 
 pytestmark = pytest.mark.gpu
@@ -113,8 +114,9 @@ def _assert_chains_equal(a, b, what):
 def _assert_terrains_equal(sc, a, b, what):
     """Everything the library exposes of terrains A and B of scene `sc`: every mip level, node heights and selections, every G-buffer
     plane for cameras 0 and 5, 1024 sampled heights with normals, 64 ray hits, then the query pyramid itself and 64 hits under a negative
-    max_height (_assert_pyramids_equal)."""
+    max_height (_assert_pyramids_equal), and the decoded tables themselves (_assert_tables_equal)."""
     _assert_chains_equal(a, b, what)
+    _assert_tables_equal(a, b, what)
     surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
     nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
     ha, hb = a.node_heights(0, nodes), b.node_heights(0, nodes)
@@ -134,6 +136,14 @@ def _assert_terrains_equal(sc, a, b, what):
     assert ra.tobytes() == rb.tobytes(), f"{what}: {(ra != rb).sum()} of {len(ra)} hits differ"
     assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
     _assert_pyramids_equal(sc, a, b, what)
+
+
+def _assert_tables_equal(a, b, what):
+    """What frames and samples cannot show: they read only the entries some pixel or point selects, of the one raster variant the pair of
+    maps takes.  Every decoded table (quad, quadf, fast; fast, rgbf) of every level of both maps of A equals B's and equals
+    tests/tables_model.py's of the device's own level, bit for bit."""
+    ta = tm.assert_tables_are_the_model(a, f"{what}: A")
+    tm.assert_tables_equal(ta, tm.assert_tables_are_the_model(b, f"{what}: B"), f"{what}: A's tables against B's")
 
 
 def _assert_pyramids_equal(sc, a, b, what):
@@ -217,6 +227,7 @@ def test_every_gbuffer_plane(scenes, oracle, name):
     a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
     _edit_some(sc, a, maps)
     b = sc.terrain(maps.hm, maps.al)
+    _assert_tables_equal(a, b, name)
     covered = 0
     for cam in RENDER_CAMERAS:
         for what, kw, part in (("fill", dict(assume_cleared=1), None), ("wireframe", dict(wireframe=1), None),
@@ -280,6 +291,7 @@ def test_queries(scenes, name, cast_first):
     assert ra.tobytes() == rb.tobytes(), f"{name}: {(ra != rb).sum()} of {len(ra)} hits differ"
     assert (ra["status"] == capi.VR_RAY_HIT).mean() > 0.2
     _assert_pyramids_equal(sc, a, b, f"{name}, cast before the edits: {cast_first}")
+    _assert_tables_equal(a, b, f"{name}, cast before the edits: {cast_first}")
     a.close(); b.close()
 
 

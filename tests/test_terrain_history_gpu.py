@@ -19,7 +19,7 @@ from tests import test_terrain_brush_gpu as tb
 from tests.f64_queries import Surface64
 from tests.fusion_common import PLANES
 from tests.host_check import build_host_check
-from tests.test_terrain_edit_gpu import SCENES, Scene, _assert_chains_equal, _assert_frames_equal, _assert_pyramids_equal, _bits, _render, _submit_frames
+from tests.test_terrain_edit_gpu import SCENES, Scene, _assert_chains_equal, _assert_frames_equal, _assert_pyramids_equal, _assert_tables_equal, _bits, _render, _submit_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -48,8 +48,9 @@ def _assert_maps(tp, hm, al, what):
 
 def _assert_terrains_equal(sc, a, b, what):
     """Every mip level of both maps, the node heights, sampled heights with normals, ray hits, every G-buffer plane of a frame, the
-    query pyramid and the hits under a negative max_height."""
+    query pyramid and the hits under a negative max_height, the decoded tables of both maps."""
     _assert_chains_equal(a, b, what)
+    _assert_tables_equal(a, b, what)
     surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
     nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
     ha, hb = a.node_heights(0, nodes).view(np.uint32), b.node_heights(0, nodes).view(np.uint32)

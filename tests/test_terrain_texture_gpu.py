@@ -62,7 +62,9 @@ def test_bytes_equal_the_model_under_five_dabs(scenes, name):
     assert rect == tuple(want_rect), (rect, want_rect)
     assert_bytes(level0(a, "albedo"), want, f"{name}, texture under five dabs")
     assert_bytes(level0(a, "height"), sc.hm, f"{name}, texture: the heightmap")
-    a.close()
+    b = sc.terrain(sc.hm, want, cast=False, render=False)
+    te._assert_tables_equal(a, b, f"{name}, texture under five dabs")
+    a.close(); b.close()
 
 
 @pytest.mark.parametrize("name", tc.SCENES)
@@ -79,6 +81,7 @@ def test_bytes_equal_the_model_over_the_whole_map(scenes, name):
     assert_bytes(level0(a, "height"), sc.hm, f"{name}, texture: the heightmap")
     b = sc.terrain(sc.hm, want, cast=False, render=False)
     te._assert_chains_equal(a, b, f"{name}, texture over the whole map")
+    te._assert_tables_equal(a, b, f"{name}, texture over the whole map")
     a.close(); b.close()
 
 

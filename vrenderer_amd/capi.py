@@ -44,6 +44,10 @@ VR_ERODE_MAX_ITERATIONS = 1024
 VR_TEXTURE_MAX_LAYERS = 8
 VR_TEXTURE_WHOLE_MAP = 1
 VR_HYDRO_MAX_ITERATIONS = 1024
+VR_DEBUG_TABLE_QUAD = 0
+VR_DEBUG_TABLE_QUADF = 1
+VR_DEBUG_TABLE_FAST = 2
+VR_DEBUG_TABLE_RGBF = 3
 
 
 class TerrainParams(C.Structure):
@@ -225,7 +229,7 @@ EXPORTS = [
     "vr_tonemap_default_params", "vr_tonemap_create", "vr_tonemap_destroy", "vr_tonemap_reset_exposure", "vr_tonemap_reset_histogram",
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
-    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_debug_terrain_query_pyramid", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush", "vr_terrain_texture", "vr_terrain_erode", "vr_debug_erode_config",
+    "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_debug_terrain_query_pyramid", "vr_debug_terrain_tables", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush", "vr_terrain_texture", "vr_terrain_erode", "vr_debug_erode_config",
     "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
 ]
@@ -349,6 +353,7 @@ def load_library():
         "vr_terrain_query_heights": (C.c_int, [vp, vp, C.c_uint32, C.c_float, vp, vp, C.c_int]),
         "vr_terrain_cast_rays": (C.c_int, [vp, vp, C.c_uint32, C.c_float, vp, C.c_int]),
         "vr_debug_terrain_query_pyramid": (C.c_int, [vp, P(C.c_int32), P(C.c_int32), vp, C.c_size_t]),
+        "vr_debug_terrain_tables": (C.c_int, [vp, C.c_int, C.c_int, C.c_int32, P(C.c_int32), vp, C.c_size_t]),
         "vr_view_pixel_ray": (C.c_int, [P(View), C.c_float, C.c_float, P(Ray)]),
         "vr_terrain_edit": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int]),
         "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),

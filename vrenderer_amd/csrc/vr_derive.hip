@@ -302,3 +302,42 @@ extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32
     if (!device_pointer) VR_HIP(hipStreamSynchronize(s));        // the caller's host memory has been consumed
     return VR_OK;
 }
+
+// One level of one decoded table as it is on the device, densely packed as the kernels above lay it out: `cols` entries per row,
+// `rows` rows, from the offsets of the terrain's own TexLayout (rgbf: level l begins at float4 off[l] / 4; the 256-byte padding
+// between two levels is never decoded and never shown).  No kernel, and nothing is built.  The copy is a reader of the map's tables
+// on the context's stream with no wait of its own, as a tile pass's and a height query's reads of them are (vr_order.h orders the
+// maps' writers against the geometry chains and the tile passes of other streams; on the context's stream the stream orders a
+// reader behind the writer, and across vr_context_set_stream the host's obligation does), and the entry returns when it has completed.
+extern "C" VR_API int vr_debug_terrain_tables(vr_terrain* t, int which, int table, int32_t level, int32_t out_dims[2], void* out, size_t capacity_bytes)
+{
+    VR_REQUIRE(t != nullptr, "terrain is NULL");
+    VR_REQUIRE(which == 0 || which == 1, "which must be 0 (heightmap) or 1 (albedo)");
+    VR_REQUIRE(table == VR_DEBUG_TABLE_QUAD || table == VR_DEBUG_TABLE_QUADF || table == VR_DEBUG_TABLE_FAST || table == VR_DEBUG_TABLE_RGBF, "unknown table");
+    VR_REQUIRE(level >= 0, "negative level");
+    VR_REQUIRE(out_dims != nullptr, "out_dims is NULL");
+    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const TexLayout& lay = which == 0 ? t->height_layout : t->albedo_layout;
+    const bool has = table == VR_DEBUG_TABLE_FAST || (table == VR_DEBUG_TABLE_RGBF ? which == 1 : which == 0);
+    int cols = 0, rows = 0;
+    size_t at = 0, entry = 16;
+    if (has && tex.base != nullptr && level < tex.levels) {
+        const int lw = dirty_level_size(tex.w0, level), lh = dirty_level_size(tex.h0, level);
+        if (table == VR_DEBUG_TABLE_QUAD) { cols = lw + 2; rows = lh + 2; entry = 4; at = lay.quad_at + (size_t)lay.qoff[level] * 4; }
+        else if (table == VR_DEBUG_TABLE_QUADF) { cols = lw + 2; rows = lh + 2; at = lay.quadf_at + (size_t)lay.qoff[level] * 16; }
+        else if (table == VR_DEBUG_TABLE_FAST) { cols = lw + 3; rows = lh + 3; at = lay.fast_at + (size_t)lay.fast_entry[level] * 16; }
+        else { cols = lw; rows = lh; at = lay.rgbf_at + (size_t)(lay.off[level] / 4) * 16; }
+    }
+    const size_t bytes = (size_t)cols * (size_t)rows * entry;
+    if (!(out == nullptr && capacity_bytes == 0)) {
+        VR_REQUIRE(out != nullptr, "out is NULL with a capacity");
+        VR_REQUIRE(capacity_bytes >= bytes, "capacity below the level's entries");
+    }
+    out_dims[0] = cols; out_dims[1] = rows;
+    if (out == nullptr || bytes == 0) return VR_OK;
+    VR_HIP(hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    VR_HIP(hipMemcpyAsync(out, tex.base + at, bytes, hipMemcpyDeviceToHost, s));
+    VR_HIP(hipStreamSynchronize(s));
+    return VR_OK;
+}

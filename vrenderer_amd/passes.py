@@ -509,6 +509,28 @@ class TerrainPass:
             at += 2 * h * w
         return res
 
+    def Tables(self, which):
+        """vr_debug_terrain_tables (test helper): the decoded tables of the heightmap (which = 'height' / 0) or the albedo ('albedo' / 1)
+        as they are on the device - a list with one dict per mip level, holding the tables the map has: 'quad' uint32 (h + 2, w + 2),
+        'quadf' float32 (h + 2, w + 2, 4) and 'fast' float32 (h + 3, w + 3, 4) for the heightmap; 'fast' and 'rgbf' float32 (h, w, 4)
+        for the albedo."""
+        idx = 0 if which in ("height", 0) else 1
+        fn, dims, res = self.ctx.lib.vr_debug_terrain_tables, (C.c_int32 * 2)(), []
+        ids = (("quad", capi.VR_DEBUG_TABLE_QUAD), ("quadf", capi.VR_DEBUG_TABLE_QUADF), ("fast", capi.VR_DEBUG_TABLE_FAST), ("rgbf", capi.VR_DEBUG_TABLE_RGBF))
+        for level in range(self.mip_levels("height" if idx == 0 else "albedo")):
+            lv = {}
+            for name, table in ids:
+                check(fn(self.handle, idx, table, level, dims, None, 0), "vr_debug_terrain_tables")
+                cols, rows = int(dims[0]), int(dims[1])
+                if cols == 0 or rows == 0:
+                    continue
+                out = np.empty((rows, cols) if name == "quad" else (rows, cols, 4), np.uint32 if name == "quad" else np.float32)
+                check(fn(self.handle, idx, table, level, dims, _vp(out), out.nbytes), "vr_debug_terrain_tables")
+                assert (int(dims[0]), int(dims[1])) == (cols, rows)
+                lv[name] = out
+            res.append(lv)
+        return res
+
     def Edit(self, which, x, y, texels=None, device_ptr=None, w=None, h=None, pitch=0):
         """vr_terrain_edit: replaces a sub-rectangle of level 0 of the heightmap (which = 'height' / 0) or the albedo ('albedo' / 1)
         at (x, y) in place; afterwards the terrain is the one Init would build from the edited arrays.  With device_ptr=None,
