@@ -26,7 +26,10 @@
 //   order_check --drop-each     is the model alive?  The transcription (intended differences on) loses one wait site at a time;
 //                               prints for each site in how many sequences (b) reports it, and for a site that no sequence
 //                               reports the reason it orders nothing (dead_reason) - a site with neither fails the run
+// Which set a call gets is not this program's: Host keeps a GeoSlots<int> (the key: a view's number) and the calls below go through
+// the transitions of vr_geosets.h as the .hip files do; tests/host/geosets_check.cpp holds that header to the code it replaced.
 // Plain C++17, no GPU: g++ -std=c++17 -Wall -Werror -I vrenderer_amd/csrc tests/host/order_check.cpp
+#include "vr_geosets.h"
 #include "vr_order.h"
 
 #include <array>
@@ -118,7 +121,7 @@ struct World {
 struct Ops { World* w; int record(int e, int s) const { return w->record(e, s); } int wait(int s, int e) const { return w->wait(s, e); }
              int sync(int e) const { return w->sync(e); } };
 
-// ---- what the .hip files decide (the same for both protocols): the context and the terrain's set bookkeeping ---------------
+// ---- what the .hip files decide (the same for both protocols): the context and the terrain's slot policy (vr_geosets.h) ------
 struct Host {
     int main = M0;
     bool async_geometry = true, frame_fusion = true;
@@ -136,24 +139,13 @@ struct Host {
     unsigned not_stamped = 0;         // bit k: the k-th stamped launch from now gets no events if it has to create one (the only way to get none)
     bool fail_create = false;
     bool launched = false;
-    bool prepared[3] = { false, false, false }, have_selection[3] = { false, false, false };
-    int prep_view[3] = { 0, 0, 0 }; uint64_t prep_serial[3] = { 0, 0, 0 }, prep_counter = 0;
-    int cur = 0, frame_no = 0;
+    GeoSlots<int> slots;              // vr_terrain::slots
+    int frame_no = 0;
     unsigned geo_turn = 0;
     // the editing path: the pyramid exists (d_pyramid), history is on, the steps that can be undone / redone (the map of each),
     // an erosion has left its planes (vr_terrain::erode_last)
     bool pyramid_built = false, history_on = false, sweep_left = false;
     std::vector<int> undo, redo;
-    int pick_set() const              // vr_terrain_pick_set
-    {
-        int best = -1;
-        for (int i = 0; i < 3; i++) {
-            if (i == cur) continue;
-            if (!prepared[i]) return i;
-            if (best < 0 || prep_serial[i] < prep_serial[best]) best = i;
-        }
-        return best;
-    }
     // VrKernelScope(by_dispatch) + launch on the context's stream: the kernel, and VrKernelScope::stop
     EventRef<int> stamped_launch(World& w)
     {
@@ -266,8 +258,7 @@ struct Parent {
     void prepare_wait(int gi)
     {
         Set& g = sets[gi];
-        /* 1936 */ bool other_prepared = false;
-        /* 1937 */ for (int p = 0; p < 3; p++) other_prepared |= (p != gi) && h.prepared[p];
+        /* 1936-1937 */ const bool other_prepared = geoslots_other_prepared(h.slots, gi);
         /* 1938 */ if (other_prepared) g.main_waited = false;
         /* 1939 */ else { W(W_PREP_NOW, h.main, g.ev_geo_done); g.main_waited = true; g.main_wait_stream = h.main; }
     }
@@ -291,7 +282,7 @@ struct Parent {
         /* 2079 */ else { R(g.ev_raster_done, s); g.raster_done = g.ev_raster_done; g.raster_done_epoch = 0; }
         /* 2080 */ g.raster_recorded = true;
         /* 2082 */ for (int pi = 0; pi < 3; pi++) { Set& p = sets[pi];
-        /* 2083 */     if (pi != gi && h.prepared[pi] && !(p.main_waited && p.main_wait_stream == s) && p.geo_recorded) { W(W_AHEAD, s, p.ev_geo_done); p.main_waited = true; p.main_wait_stream = s; } }
+        /* 2083 */     if (pi != gi && h.slots.slot[pi].prepared && !(p.main_waited && p.main_wait_stream == s) && p.geo_recorded) { W(W_AHEAD, s, p.ev_geo_done); p.main_waited = true; p.main_wait_stream = s; } }
     }
     void select_begin(int gi)                                 // vr_terrain_select, vr_select.hip
     {
@@ -408,18 +399,13 @@ struct Protocol {
     template <class Copy> void copy_selection(int gi, int from, Copy&& copy) { order_copy_selection(t, sets[gi], sets[from], ops, [&]() -> int { copy(); return 0; }); }
     void end_chain(int gi) { order_end_chain(sets[gi], ops); }
     void prepare_start() { order_prepare_start(t, ops, kGeo, h.geo_turn, h.events); }
-    void prepare_wait(int gi)
-    {
-        bool other_prepared = false;
-        for (int p = 0; p < 3; p++) other_prepared |= (p != gi) && h.prepared[p];
-        order_prepare_wait(sets[gi], ops, h.main, other_prepared);
-    }
+    void prepare_wait(int gi) { order_prepare_wait(sets[gi], ops, h.main, geoslots_other_prepared(h.slots, gi)); }
     void tile_pass_begin(int gi, bool use_prepared) { order_tile_pass_begin(t, sets[gi], ops, h.main, use_prepared, events_start_hint(h.events)); }
     void keep_writer_begins(int im) { order_image_writer_begins(img[im], ops, h.main); }
     void tile_pass_launched(int gi, EventRef<int> pass_stop)
     {
         order_tile_pass_launched(sets[gi], ops, h.main, pass_stop);
-        for (int p = 0; p < 3; p++) if (p != gi && h.prepared[p]) order_wait_ahead(sets[p], ops, h.main);
+        for (int p = 0; p < 3; p++) if (p != gi && h.slots.slot[p].prepared) order_wait_ahead(sets[p], ops, h.main);
     }
     void select_begin(int gi) { order_begin_chain(t, sets[gi], ops, kGeo, h.geo_turn, h.main, false, h.events); }
     void select_end(int gi) { order_end_chain(sets[gi], ops); }
@@ -462,34 +448,32 @@ template <class P> struct Driver {
     {
         p.begin_chain(gi);
         const int gs = p.stream(gi);
-        if (sel < 0) { w.kernel(gs); w.access(HEIGHTS, false, gs); w.access(SEL0 + gi, true, gs); h.have_selection[gi] = true; }
+        if (sel < 0) { w.kernel(gs); w.access(HEIGHTS, false, gs); w.access(SEL0 + gi, true, gs); geoslots_selected(h.slots, gi); }
         else if (sel != gi) {
             p.copy_selection(gi, sel, [&]() { w.kernel(gs); w.access(SEL0 + sel, false, gs); w.access(SEL0 + gi, true, gs); });
-            h.have_selection[gi] = true;
+            geoslots_selected(h.slots, gi);
         }
         w.kernel(gs); w.access(SEL0 + gi, false, gs); w.access(HMAP, false, gs); w.access(GEO0 + gi, true, gs);      // (the vertex stage samples the heightmap)
         p.end_chain(gi);
     }
     void prepare(int view)                                    // vr_terrain_prepare
     {
-        for (int i = 0; i < 3; i++) if (h.prepared[i] && h.prep_view[i] == view) return;
-        const int gi = h.pick_set();
-        h.prepared[gi] = false;
+        if (geoslots_find(h.slots, view) >= 0) return;
+        const int gi = geoslots_pick(h.slots);
+        geoslots_claim(h.slots, gi);
         p.prepare_start();
         geometry(gi, -1);
         p.prepare_wait(gi);
-        h.prepared[gi] = true; h.prep_view[gi] = view; h.prep_serial[gi] = ++h.prep_counter;
+        geoslots_prepared(h.slots, gi, view);
     }
     EventRef<int> render(int view, bool lock, int keep_image) // terrain_render_impl; returns the pass's stop event (keep: the fused launch's)
     {
-        int gi = -1;
-        if (!lock) for (int i = 0; i < 3; i++) if (i != h.cur && h.prepared[i] && h.prep_view[i] == view) { gi = i; break; }
+        int gi = lock ? -1 : geoslots_find(h.slots, view);
         const bool use_prepared = gi >= 0;
-        if (!use_prepared) gi = h.pick_set();
-        const int last = h.cur;
-        h.prepared[gi] = false;
-        if (!use_prepared) geometry(gi, (lock && h.have_selection[last]) ? last : -1);
-        h.cur = gi;
+        if (!use_prepared) gi = geoslots_pick(h.slots);
+        geoslots_claim(h.slots, gi);
+        if (!use_prepared) geometry(gi, geoslots_selection_source(h.slots, lock));
+        geoslots_current(h.slots, gi);
         p.tile_pass_begin(gi, use_prepared);
         if (keep_image >= 0) p.keep_writer_begins(keep_image);
         const EventRef<int> pass_stop = h.stamped_launch(w);
@@ -501,17 +485,17 @@ template <class P> struct Driver {
     }
     void select()                                             // vr_terrain_select (asynchronous form)
     {
-        const int gi = h.pick_set();
+        const int gi = geoslots_pick(h.slots);
         p.select_begin(gi);
-        h.prepared[gi] = false;
+        geoslots_claim(h.slots, gi);
         const int gs = p.stream(gi);
-        w.kernel(gs); w.access(HEIGHTS, false, gs); w.access(SEL0 + gi, true, gs); h.have_selection[gi] = true;
+        w.kernel(gs); w.access(HEIGHTS, false, gs); w.access(SEL0 + gi, true, gs); geoslots_selected(h.slots, gi);
         p.select_end(gi);
-        h.cur = gi;
+        geoslots_current(h.slots, gi);
     }
     void update_heights()                                     // vr_terrain_update_heights
     {
-        for (bool& b : h.prepared) b = false;
+        geoslots_invalidate(h.slots);
         p.heights_begin();
         w.kernel(h.main); w.access(HEIGHTS, true, h.main);
         p.heights_end();
@@ -522,7 +506,7 @@ template <class P> struct Driver {
     {
         const int s = h.main, map = which ? AMAP : HMAP;
         p.maps_begin();
-        for (bool& b : h.prepared) b = false;
+        geoslots_invalidate(h.slots);
         write();
         w.kernel(s); w.access(map, true, s);                                // levels 1 .. and the tables
         if (which == 0) { w.kernel(s); w.access(HMAP, false, s); w.access(HEIGHTS, true, s); }

@@ -183,6 +183,21 @@ def test_product_build_has_no_experiment_switch():
     assert not any(x.startswith("-DVR_") for x in flags), flags
 
 
+def test_geometry_slot_policy_lives_in_its_header_alone():
+    """Which geometry set a call gets is vr_geosets.h's: no other file under csrc names the fields and functions it replaced, and
+    the .hip files and vr_internal.h reach vr_terrain::slots through its transitions - they read its fields and assign none."""
+    csrc = os.path.join(ROOT, "vrenderer_amd", "csrc")
+    write = re.compile(r"(\+\+|--)\s*[\w\->.]*\bslots\.|\bslots\.(cur|counter|slot\[[^\]]*\]\.\w+)\s*(=(?!=)|\+\+|--|[-+|&^]=)")
+    for f in sorted(os.listdir(csrc)):
+        if f == "vr_geosets.h":
+            continue
+        text = open(os.path.join(csrc, f), errors="ignore").read()
+        for gone in ("prep_serial", "prep_counter", "prepared_matches", "vr_terrain_pick_set"):
+            assert gone not in text, f"{f}: {gone} belongs to vr_geosets.h"
+        assert not re.search(r"\.prepared\s*=(?!=)", text), f"{f}: a prepared frame is given up through geoslots_claim / geoslots_invalidate"
+        assert not write.search(text), f"{f}: {write.search(text).group(0)!r} writes the slot state past vr_geosets.h"
+
+
 def test_pack_detile_roundtrip_numpy():
     rng = np.random.default_rng(3)
     for (w, h, world) in ((300, 260, 3), (512, 256, 2), (130, 70, 8)):
@@ -285,6 +300,22 @@ def test_gbuffer_state_matches_the_transcribed_code_and_the_memory_model(tmp_pat
     # 2089 + 2089^2 of all events, 57 + .. + 57^4 of the smaller set, 200000 random
     assert "15310510 sequences" in r.stdout, r.stdout[-400:]
     run_host_check(exe, "--break-each", expect="15 of 15 weakenings reported")
+
+
+def test_geometry_slot_policy_matches_the_transcribed_code_and_its_invariants(tmp_path):
+    """vr_geosets.h compiles without HIP.  Over every sequence of up to four events and a fixed sample of longer ones
+    (tests/host/geosets_check.cpp: prepares, renders with and without lock_view, selects, invalidations and materialising passes
+    over six keys, any fallible step of any of them refused) its transitions choose the sets, answer and leave the state of the
+    code they replaced in vr_raster.hip, vr_select.hip and vr_derive.hip, and keep the invariants the program names - the current
+    set is never prepared, the pick is never the current set, a selection is never lost, a materialising pass leaves the current
+    set alone; each rule weakened in turn is reported; once more under the address and undefined-behaviour sanitizers."""
+    exe = build_host_check(tmp_path, "geosets_check")
+    r = run_host_check(exe)
+    # 32 + 32^2 + 32^3 + 32^4 of 32 events (4 x 6 keys, select, invalidate, 6 failing steps), 200000 random
+    assert "1282400 sequences" in r.stdout, r.stdout[-400:]
+    run_host_check(exe, "--break-each", expect="8 of 8 weakenings reported")
+    san = build_host_check(tmp_path, "geosets_check", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "geosets_check_san")
+    run_host_check(san)
 
 
 def _build_allgather_example(tmpdir):

@@ -311,3 +311,31 @@ def test_a_second_terrain_takes_over_the_target(fx):
         _both(fx, w, h, script)
     finally:
         other.close()
+
+
+def test_a_materialising_pass_borrows_a_set_while_two_frames_are_prepared(fx):
+    """A fused frame nobody has looked at, two frames prepared ahead for two other views, then the first reader: the materialising
+    pass needs a geometry set while both sets other than the current one hold a prepared frame, so it takes the older one's
+    (vr_geosets.h: the borrowed pass) and must leave the current set and the younger frame alone.  The two prepared views are then
+    rendered - one from its prepared set, one built again - and a lock_view render reuses the last selection; every plane behind
+    every step is the eager world's."""
+    w, h = 320, 180
+    v = _views(w, h)
+
+    def script(sc, lazy):
+        out = {}
+        assert PLAIN not in sc.submit(v[0])
+        sc.tp.Prepare(v[1], sc.rt, sc.rp)
+        sc.tp.Prepare(v[2], sc.rt, sc.rp)
+        out["first"], r = _timed(sc.ctx, lambda: sc.rt.download("diffuse").copy())
+        assert (PLAIN in r) == bool(lazy), sorted(r)                             # the materialising pass, with two sets prepared
+        out["the frame"] = _capture(sc.rt, sc.hdr)
+        for i in (1, 2):
+            sc.tp.Render(v[i], v[i], sc.rt, sc.rp)
+            out[f"prepared view {i}"] = _capture(sc.rt, sc.hdr)
+        sc.rp.lock_view = 1
+        sc.tp.Render(v[0], v[0], sc.rt, sc.rp)
+        out["lock_view"] = _capture(sc.rt, sc.hdr)
+        return out
+    want, _ = _both(fx, w, h, script)
+    assert not np.array_equal(want["prepared view 1"]["depth"], want["prepared view 2"]["depth"])

@@ -230,7 +230,7 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
     { const int rc = order_terrain_changing(ord_sets, VrOrderOps(), s); if (rc) return rc; }
     { const int rc = order_terrain_tables_changing(ord_sets, VrOrderOps(), s, ctx->events); if (rc) return rc; }
     // geometry built from the old map is stale, whichever map it was (one rule); selections and lock_view stay as they are
-    for (GeoSet& g : t->sets) g.prepared = false;
+    geoslots_invalidate(t->slots);
 
     { const int rc = write_level0(s); if (rc) return rc; }
     vr_derive_chain(ctx, const_cast<uint8_t*>(tex.base), lay, tex.w0, tex.h0, tex.levels, which == 0 ? 1 : 4, dirty);

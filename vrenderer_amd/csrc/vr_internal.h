@@ -14,6 +14,7 @@
 #include "vr_brush.h"
 #include "vr_devbuf.h"
 #include "vr_gbuffer_state.h"
+#include "vr_geosets.h"
 #include "vr_history.h"
 #include "vr_light_plan.h"
 #include "vr_order.h"
@@ -305,8 +306,8 @@ struct vr_ldr_image {
 };
 
 // Everything one frame's geometry stages produce and its tile pass consumes.  Three sets rotate: the tile pass of
-// frame N reads one while the geometry of frames N+1 and N+2 is built in the other two (vr_terrain_prepare).
-constexpr int kGeoSets = 3;
+// frame N reads one while the geometry of frames N+1 and N+2 is built in the other two (vr_terrain_prepare).  Which set a call
+// gets - current, prepared, holding a selection - is vr_terrain::slots (vr_geosets.h); a GeoSet is the memory and its order.
 static_assert(kGeoSets == kScratchSets, "ScratchState::pending has one flag per geometry set");
 struct GeoSet {
     uint32_t* d_node_ids = nullptr;      // select outputs
@@ -326,12 +327,7 @@ struct GeoSet {
     TileEntry* d_bin_entries = nullptr;   // ScratchState::bin_capacity entries of 64 B (k_fill)
     int scratch_tiles = 0;
     int last_tiles = 0;                  // raster tiles of the target the last chain was built for (the stride of d_tile_order's class regions)
-    bool have_selection = false;
     VrOrderSet ord;                      // the set's stream, marks and pending readers (vr_order.h)
-    // vr_terrain_prepare: geometry already built for exactly these inputs
-    bool prepared = false;
-    uint64_t prep_serial = 0;            // order of the vr_terrain_prepare calls (the oldest prepared set is evicted first)
-    vr_view prep_view; vr_render_params prep_rp; int prep_w = 0, prep_h = 0, prep_rank = 0, prep_world = 0, prep_tile_shift = 0;
 };
 
 struct vr_terrain {
@@ -353,8 +349,7 @@ struct vr_terrain {
     uint32_t* h_status = nullptr;          // kGeoSets x kStatusWords, hipHostMalloc (mapped)
     uint32_t* d_status = nullptr;          // the device's view of it
     GeoSet sets[kGeoSets];
-    int cur = 0;                            // set of the most recent select / render
-    uint64_t prep_counter = 0;
+    GeoSlots<GeoKey> slots;                 // the current set, the prepared frames, the selections (vr_geosets.h)
     // Two geometry streams, taken in turns by successive chains.  Not one per set: HIP multiplexes streams onto 4 hardware
     // queues by default (GPU_MAX_HW_QUEUES), and a frame loop with an exchange stage already uses 2-3 of its own; streams
     // that share a queue serialise (measured: a fifth stream cost the N = 8 rank emulation 0.23 -> 0.39 ms per frame).
@@ -456,7 +451,6 @@ vr_context* vr_tonemap_context(vr_tonemap* tm);
 int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, int texel_bytes,
                           DevTex* out, uint8_t** out_mem, uint64_t* out_bytes = nullptr, TexLayout* layout = nullptr);
 int vr_select_launch(vr_terrain* t, GeoSet& g, const vr_view* view, float max_height, hipStream_t stream);
-int vr_terrain_pick_set(vr_terrain* t);
 // In front of a frame's geometry (vr_terrain_prepare, the tile pass; vr_select.hip).  Completed chains' status words are read (no
 // wait) and the scratch grows if due; with `report` a completed frame's device-side condition comes back once, in *earlier - it
 // does not stop the frame.  Then target(&tiles) - the call site's RasterArgs, which read the capacities - says how many raster tiles

@@ -1821,7 +1821,7 @@ static int launch_geometry(vr_terrain* t, GeoSet& g, GeoSet* selection_from, con
             return VR_OK;
         });
         if (rc) return rc;
-        g.have_selection = true;
+        geoslots_selected(t->slots, (int)(&g - t->sets));
     }
     const int n_tiles = a.rtx * a.rty;
     if (n_tiles > g.scratch_tiles) {
@@ -1890,13 +1890,6 @@ static RasterKernel raster_kernel(RasterVariant v)
     return { nullptr, k_raster<false, 64, RM_FAST, false, true, true> };
 }
 
-static bool prepared_matches(const GeoSet& g, const vr_view* view, const vr_render_params* rp, int w, int h, const RasterArgs& a)
-{
-    return memcmp(&g.prep_view, view, sizeof(vr_view)) == 0 && g.prep_rp.max_height == rp->max_height && g.prep_rp.depth_only == rp->depth_only
-        && !g.prep_rp.wireframe == !rp->wireframe && g.prep_w == w && g.prep_h == h && g.prep_rank == a.rank && g.prep_world == a.world
-        && g.prep_tile_shift == a.tile_shift;      // (VR_OPT_RASTER_TILE may have changed in between: the bins are per tile size)
-}
-
 static int check_render_inputs(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp)
 {
     VR_REQUIRE(t && view && gb && rp, "NULL argument");
@@ -1920,10 +1913,11 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
     const PartTables* pt = nullptr;       // this rank's raster tiles; unused (NULL) for the whole frame
     if (a.world > 1 && (rc = vr_partition_tables(t->ctx, gb->w, gb->h, part, &pt))) return rc;
     // already prepared for exactly these inputs (a caller may name the same future frame twice): nothing to do
-    for (GeoSet& p : t->sets)
-        if (p.prepared && prepared_matches(p, view, rp, gb->w, gb->h, a)) return VR_OK;
-    GeoSet& g = t->sets[vr_terrain_pick_set(t)];
-    g.prepared = false;
+    const GeoKey key = geo_key(*view, *rp, gb->w, gb->h, a.rank, a.world, a.tile_shift);
+    if (geoslots_find(t->slots, key) >= 0) return VR_OK;
+    const int gi = geoslots_pick(t->slots);
+    GeoSet& g = t->sets[gi];
+    geoslots_claim(t->slots, gi);
     // Start when the context's stream starts the tile pass queued last: the host runs frames ahead of the
     // device, and without this the geometry would become runnable one pass earlier and share the device
     // with the previous frame's lighting pass (bandwidth-bound) instead of with a tile pass (which leaves
@@ -1939,11 +1933,8 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
     //     pass (vr_terrain_render queues it), a whole frame later.  Below 8K a chain under load (~0.2 ms) outlasts the tile
     //     pass it starts under (4K: 0.15 ms), and a wait in front of the current lighting pass stalled every frame by the
     //     difference (4K: 0.28 -> 0.22 ms per frame without it).
-    bool other_prepared = false;
-    for (const GeoSet& p : t->sets) other_prepared |= (&p != &g) && p.prepared;
-    if ((rc = order_prepare_wait(g.ord, VrOrderOps(), t->ctx->stream, other_prepared))) return rc;
-    g.prepared = true; g.prep_view = *view; g.prep_rp = *rp; g.prep_w = gb->w; g.prep_h = gb->h; g.prep_rank = a.rank; g.prep_world = a.world; g.prep_tile_shift = a.tile_shift;
-    g.prep_serial = ++t->prep_counter;
+    if ((rc = order_prepare_wait(g.ord, VrOrderOps(), t->ctx->stream, geoslots_other_prepared(t->slots, gi)))) return rc;
+    geoslots_prepared(t->slots, gi, key);
     return VR_OK;
 }
 
@@ -2043,20 +2034,16 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     if (plan.materialise_first && (rc = vr_gbuffer_materialise(gb, s))) return rc;
 
     // a set prepared for exactly this frame, else a free one (the oldest prepared set is given up if all are taken)
-    int gi = -1;
-    if (!rp->lock_view)
-        for (int i = 0; i < kGeoSets; i++)
-            if (i != t->cur && t->sets[i].prepared && prepared_matches(t->sets[i], view, rp, gb->w, gb->h, a)) { gi = i; break; }
+    int gi = rp->lock_view ? -1 : geoslots_find(t->slots, geo_key(*view, *rp, gb->w, gb->h, a.rank, a.world, a.tile_shift));
     const bool use_prepared = gi >= 0;
-    if (!use_prepared) gi = vr_terrain_pick_set(t);
+    if (!use_prepared) gi = geoslots_pick(t->slots);
     GeoSet& g = t->sets[gi];
-    GeoSet& last = t->sets[t->cur];
-    g.prepared = false;
+    geoslots_claim(t->slots, gi);
     if (!use_prepared) {
-        GeoSet* sel = (rp->lock_view && last.have_selection) ? &last : nullptr;
-        if ((rc = launch_geometry(t, g, sel, view, rp, a, pt))) return rc;
+        const int from = geoslots_selection_source(t->slots, rp->lock_view != 0);
+        if ((rc = launch_geometry(t, g, from >= 0 ? &t->sets[from] : nullptr, view, rp, a, pt))) return rc;
     }
-    t->cur = gi;
+    geoslots_current(t->slots, gi);
     // the tile pass consumes verts + bins; vr_terrain_prepare's start hint: with dispatch-stamped events the stop event of whatever
     // ran last on the stream (the previous frame's lighting pass)
     const VrOrderOps ops;
@@ -2104,8 +2091,8 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
     }
     if ((rc = order_tile_pass_launched(g.ord, ops, s, pass_stop))) return rc;
     // chains prepared further ahead whose wait vr_terrain_prepare left for later: behind this tile pass
-    for (GeoSet& p : t->sets)
-        if (&p != &g && p.prepared && (rc = order_wait_ahead(p.ord, ops, s))) return rc;
+    for (int i = 0; i < kGeoSets; i++)
+        if (i != gi && t->slots.slot[i].prepared && (rc = order_wait_ahead(t->sets[i].ord, ops, s))) return rc;
     VR_HIP(hipGetLastError());
     if (earlier_out) *earlier_out = earlier;
     return VR_OK;
@@ -2154,10 +2141,9 @@ int vr_gbuffer_materialise_planes(vr_gbuffer* gb)
 {
     if (!gb->st.planes_pending) return VR_OK;
     vr_terrain* t = gb->pending.terrain;
-    const int cur = t->cur;
     const RenderMode recorded = { 5, true, true };
-    const int rc = terrain_render_impl(t, &gb->pending.view, gb, &gb->pending.rp, nullptr, nullptr, nullptr, nullptr, recorded);
-    t->cur = cur;
+    int rc;
+    { const GeoBorrow<GeoKey> borrowed(t->slots); rc = terrain_render_impl(t, &gb->pending.view, gb, &gb->pending.rp, nullptr, nullptr, nullptr, nullptr, recorded); }
     if (rc) return rc;                     // (before the plan was applied: still pending)
     gb->st = gbs_planes_materialised(gb->st);
     vr_gbuffer_record_settle(gb);
@@ -2182,7 +2168,7 @@ extern "C" VR_API int vr_debug_tile_order(vr_terrain* t, int32_t* out_tiles, uin
 {
     VR_REQUIRE(t && out_tiles && out_bin_lengths && out_count && capacity >= 0, "bad arguments");
     VR_HIP(hipSetDevice(t->ctx->device));
-    const GeoSet& g = t->sets[t->cur];
+    const GeoSet& g = t->sets[t->slots.cur];
     VR_HIP(hipStreamSynchronize(g.ord.stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     *out_count = 0;

@@ -35,7 +35,7 @@ constexpr uint32_t kStTooMany = 1u;        // more than max_instances nodes sele
 constexpr uint32_t kStListFull = 2u;       // a work list (frontier, clipper, bins) was full: triangles or nodes were dropped
 constexpr uint32_t kStScratchShort = 4u;   // more nodes than the scratch held (and no more than max_instances)
 
-constexpr int kScratchSets = 3;            // == kGeoSets (vr_internal.h)
+constexpr int kScratchSets = 3;            // == kGeoSets (vr_geosets.h)
 
 struct ScratchState {
     int cap_instances = 0;                 // nodes the scratch holds (<= max_instances)

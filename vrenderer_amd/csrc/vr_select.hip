@@ -271,7 +271,7 @@ int vr_select_launch(vr_terrain* t, GeoSet& g, const vr_view* view, float max_he
     hipLaunchKernelGGL(k_select, dim3(1), dim3(kSelThreads), 0, stream, a, g.d_node_ids, g.d_instances, g.d_counters,
                        (const float2*)t->d_node_heights, g.d_sel_scratch);
     VR_HIP(hipGetLastError());
-    g.have_selection = true;
+    geoslots_selected(t->slots, (int)(&g - t->sets));
     return VR_OK;
 }
 
@@ -418,7 +418,7 @@ extern "C" VR_API int vr_terrain_update_heights(vr_terrain* t, int enable)
     VR_REQUIRE(t != nullptr, "terrain is NULL");
     VR_HIP(hipSetDevice(t->ctx->device));
     { const int rc = vr_terrain_materialise_pending(t); if (rc) return rc; }      // (a recorded frame selects with the bounds of now)
-    for (GeoSet& g : t->sets) g.prepared = false;          // geometry prepared with the old bounds is stale
+    geoslots_invalidate(t->slots);                         // geometry prepared with the old bounds is stale
     if (!enable) { t->height_loaded = false; return VR_OK; }
     const uint64_t nodes = nodes_per_surface(t);
     const int num_surfaces = t->surfaces_per_side * t->surfaces_per_side;
@@ -482,7 +482,7 @@ static int alloc_scratch(vr_terrain* t, int cap, size_t bin_want)
     });
     if (rc) return rc;
     scratch_allocated(t->scratch, cap, bins, bin_want); t->bytes_scratch = total;
-    for (GeoSet& g : t->sets) g.prepared = false;    // geometry built for the old buffers is gone (a selection lives in the fixed part: kept)
+    geoslots_invalidate(t->slots);                   // geometry built for the old buffers is gone (a selection lives in the fixed part: kept)
     return VR_OK;
 }
 
@@ -659,12 +659,12 @@ extern "C" VR_API int vr_terrain_download_mip(vr_terrain* t, int which, int leve
 static int read_counters(vr_terrain* t, uint32_t* count, bool selection_only = false)
 {
     uint32_t c[kStatusWords] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream)); // selection and bins are produced on the set's geometry stream
-    VR_HIP(hipMemcpyAsync(c, t->sets[t->cur].d_counters, sizeof(c), hipMemcpyDeviceToHost, t->ctx->stream));
+    VR_HIP(hipStreamSynchronize(t->sets[t->slots.cur].ord.stream)); // selection and bins are produced on the set's geometry stream
+    VR_HIP(hipMemcpyAsync(c, t->sets[t->slots.cur].d_counters, sizeof(c), hipMemcpyDeviceToHost, t->ctx->stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
     if (count) *count = selection_only ? c[C_SELECTED] : c[C_COUNT];   // NodeSelect's list is complete up to max_instances whatever the scratch holds
     ScratchState& s = t->scratch;
-    const ScratchRead r = scratch_read(s, t->cur, c, selection_only);
+    const ScratchRead r = scratch_read(s, t->slots.cur, c, selection_only);
     if (r.poll) (void)terrain_poll(t, false);
     if (r.drop_report) (void)scratch_take_report(s);
     if (r.kind == SCRATCH_READ_TOO_MANY) vr_set_error("more than max_instances nodes selected (TerrainPass.cpp:238 assert)");
@@ -672,19 +672,6 @@ static int read_counters(vr_terrain* t, uint32_t* count, bool selection_only = f
     else if (r.kind == SCRATCH_READ_SHORT) vr_set_error("the frame selected more nodes than the scratch held (drawn without the excess); the scratch has been grown to %d nodes - render again",
                                                         s.cap_instances);
     return r.code;
-}
-
-// The set the next select / geometry build goes to: never the current one (a tile pass may be reading it and lock_view
-// copies its selection); among the others one that holds no prepared frame, else the one prepared longest ago.
-int vr_terrain_pick_set(vr_terrain* t)
-{
-    int best = -1;
-    for (int i = 0; i < kGeoSets; i++) {
-        if (i == t->cur) continue;
-        if (!t->sets[i].prepared) return i;
-        if (best < 0 || t->sets[i].prep_serial < t->sets[best].prep_serial) best = i;
-    }
-    return best;
 }
 
 extern "C" VR_API int vr_terrain_select(vr_terrain* t, const vr_view* view, float max_height, uint32_t* node_ids,
@@ -696,15 +683,15 @@ extern "C" VR_API int vr_terrain_select(vr_terrain* t, const vr_view* view, floa
     { const int prc = terrain_poll(t, false); if (prc) return prc; }
     // the selection buffers are consumed by geometry-stream kernels: order this launch behind them and
     // behind whatever the context's stream did to the terrain (heights)
-    const int gi = vr_terrain_pick_set(t);                         // a set no tile pass in flight is reading
+    const int gi = geoslots_pick(t->slots);                        // a set no tile pass in flight is reading
     GeoSet& g = t->sets[gi];
     // (not part of a frame: never behind the context's stream as a whole, whatever VR_OPT_ASYNC_GEOMETRY says)
     int rc = order_begin_chain(t->ord, g.ord, VrOrderOps(), t->geo_streams, t->geo_turn, t->ctx->stream, false, t->ctx->events);
     if (rc) return rc;
-    g.prepared = false;
+    geoslots_claim(t->slots, gi);
     if ((rc = vr_select_launch(t, g, view, max_height, g.ord.stream))) return rc;
     if ((rc = order_end_chain(g.ord, VrOrderOps()))) return rc;           // this select is the set's latest writer
-    t->cur = gi;
+    geoslots_current(t->slots, gi);
     if (!node_ids && !instances && !count) return VR_OK;       // stays asynchronous
     uint32_t n = 0;
     rc = read_counters(t, &n, true);
@@ -718,7 +705,7 @@ extern "C" VR_API int vr_terrain_num_chunks(vr_terrain* t, uint32_t* count)
 {
     VR_REQUIRE(t && count, "NULL argument");
     VR_HIP(hipSetDevice(t->ctx->device));
-    if (!t->sets[t->cur].have_selection) { *count = 0; return VR_OK; }
+    if (!t->slots.slot[t->slots.cur].have_selection) { *count = 0; return VR_OK; }
     return read_counters(t, count);
 }
 
@@ -726,9 +713,9 @@ extern "C" VR_API int vr_debug_render_stats(vr_terrain* t, uint32_t out[8])
 {
     VR_REQUIRE(t && out, "NULL argument");
     VR_HIP(hipSetDevice(t->ctx->device));
-    VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream));
+    VR_HIP(hipStreamSynchronize(t->sets[t->slots.cur].ord.stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
-    const GeoSet& g = t->sets[t->cur];
+    const GeoSet& g = t->sets[t->slots.cur];
     VR_HIP(hipMemcpy(out, g.d_counters, (C_BINTOTAL + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
 #ifdef VR_SELECT_PROFILE
     { unsigned long long ts[4]; VR_HIP(hipMemcpy(ts, g.d_sel_scratch + 2 * (kFrontierCap - kFrontLds) + kSelectedCap - 8, sizeof(ts), hipMemcpyDeviceToHost));
@@ -748,9 +735,9 @@ extern "C" VR_API int vr_debug_download_vertices(vr_terrain* t, uint32_t first, 
 {
     VR_REQUIRE(t && out, "NULL argument");
     VR_HIP(hipSetDevice(t->ctx->device));
-    VR_HIP(hipStreamSynchronize(t->sets[t->cur].ord.stream));
+    VR_HIP(hipStreamSynchronize(t->sets[t->slots.cur].ord.stream));
     VR_HIP(hipStreamSynchronize(t->ctx->stream));
-    const GeoSet& g = t->sets[t->cur];
+    const GeoSet& g = t->sets[t->slots.cur];
     uint32_t n = 0;
     VR_HIP(hipMemcpy(&n, g.d_counters + C_COUNT, sizeof(uint32_t), hipMemcpyDeviceToHost));
     VR_REQUIRE((uint64_t)first + count <= (uint64_t)n * kVertsPerInst, "vertex range exceeds the last draw's instances");
