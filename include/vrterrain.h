@@ -186,7 +186,7 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
  * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
  * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
- * vr_terrain_edit / _brush / _texture / _erode / _erode_hydraulic / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
  * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
  * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
  * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
@@ -334,6 +334,69 @@ typedef struct vr_texture_layer {      /* 64 B */
 typedef struct vr_texture_params { int32_t num_layers; uint32_t flags; float max_height; int32_t reserved[5]; } vr_texture_params; /* 32 B */
 VR_API int vr_terrain_texture(vr_terrain* t, const vr_texture_params* p, const vr_texture_layer* layers,
                               const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
+/* Stamps: a prepared patch - a mountain, a crater, a scanned tile, an albedo decal - kept in device memory and set into level 0 of a
+ * map at a position, size and angle, with a blend rule.  A vr_stamp is w x h texels, 1 .. 4096 per side, of one of the maps' formats:
+ * VR_STAMP_R8 (the heightmap's, = which 0) or VR_STAMP_SRGBA8 (the albedo's, = which 1).  It belongs to the context it was created
+ * on, may be stamped on any terrain of that context any number of times, and is destroyed before the context.
+ *   vr_stamp_create        copies w x h texels (rows row_pitch_bytes apart; 0 = tightly packed).  device_pointer = 0: `texels` is host
+ *                          memory and the call returns once it has been consumed (it synchronises the stream, as a host-pointer
+ *                          vr_terrain_edit does).  device_pointer = 1: `texels` is device memory, aligned like vr_terrain_edit's; the
+ *                          copy is stream-ordered on the context's stream, nothing is synchronised, and the caller keeps `texels`
+ *                          alive and unchanged until the stream has passed it.
+ *   vr_stamp_from_terrain  the w x h texels at (x, y) of level 0 of the terrain's heightmap (which = 0) or albedo (1) as they are on
+ *                          the device - the clone tool's source: a device copy on the context's stream, behind the map's last
+ *                          writer; nothing is synchronised and the map never visits the host.
+ *   vr_stamp_destroy       waits on the host until nothing queued can still touch the stamp, then frees it.  NULL is allowed.
+ *   vr_stamp_info          format and size (each pointer may be NULL).
+ *   vr_stamp_download      test / IO helper, synchronous: the w * h texels, tightly packed, into `host` (bytes >= their size).
+ * vr_terrain_stamp sets the stamp into level 0 of map `which`, computed on the device from the map as it is there, followed by the
+ * refresh vr_terrain_edit does: afterwards the terrain is the one vr_terrain_create builds from the stamped maps.  The stamp's centre
+ * lies at world (x, z); its own u axis points along (cos rotation, sin rotation) in world (x, z) and is size_x world units long, its
+ * v axis along (-sin, cos), size_z long.  Every map texel whose centre lies inside that rectangle is covered: it samples the stamp
+ * bilinearly (clamp addressing), s' = s * gain + offset in stored units, and weighs a = wf * opacity, where wf falls from 1 to 0 by
+ * a smoothstep over the outer `feather` share of each half-extent (0 = a hard edge) and, with VR_STAMP_USE_ALPHA, a is scaled by the
+ * stamp's sampled alpha / 255.  Per channel c of channel_mask (as PAINT's; an R8 map has the one channel, mask 1):
+ *   VR_STAMP_BLEND  value_c += a * (s'_c - value_c)
+ *   VR_STAMP_ADD    value_c += a * s'_c                  VR_STAMP_SUB  value_c -= a * s'_c
+ *   VR_STAMP_MAX    value_c += a * (max(value_c, s'_c) - value_c)       VR_STAMP_MIN likewise with min
+ * clamped to [0, 255] and rounded to the nearest byte once.  A texel that is not covered is not written; a covered one with a == 0
+ * keeps its byte.  The arithmetic is defined bit for bit in vrenderer_amd/csrc/vr_stamp.h, without a division or
+ * trigonometry on the device.  Sampling is bilinear only: a stamp minified by more than about 2 aliases, and filtering it first is
+ * the caller's business.
+ * out_rect (may be NULL) receives {x, y, w, h} of the level-0 rectangle the call treated as dirty - the hull of the stamp's corners
+ * grown by one texel, clipped to the map; no texel outside it changes - or {0, 0, 0, 0} when the stamp misses the map, which is VR_OK
+ * and launches nothing.  The call is stream-ordered on the context's stream like a device-pointer edit and synchronises nothing; it
+ * is ordered against every other user of the stamp, whichever stream that ran on.  With history on, one call is one record.
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with nothing touched: a NULL handle, pointer or `out`; a
+ * format that is not VR_STAMP_R8 / _SRGBA8 or differs from `which`; a stamp of another context; a side outside 1 .. 4096; a
+ * rectangle not wholly inside level 0; a pitch smaller than a row, or a device pointer or pitch not aligned to the texel; a NaN or an
+ * infinity in a field; size_x or size_z <= 0; opacity or feather outside [0, 1]; |gain| > 256; |offset| > 255; an unknown op or flag;
+ * VR_STAMP_USE_ALPHA on R8; a channel_mask of 0 or above 15, or other than 1 on R8; a non-zero reserved word.  Memory is reserved
+ * before anything is launched (VR_ERR_OUT_OF_MEMORY leaves everything as it was).  Timing: as for vr_terrain_edit; the stamp kernel
+ * itself is untimed. */
+typedef struct vr_stamp vr_stamp;      /* a patch in device memory, owned by a context */
+enum { VR_STAMP_R8 = 0, VR_STAMP_SRGBA8 = 1 };          /* = the `which` of the map it can be stamped on */
+VR_API int  vr_stamp_create(vr_context* ctx, int format, int32_t w, int32_t h, const void* texels, size_t row_pitch_bytes,
+                            int device_pointer, vr_stamp** out);
+VR_API int  vr_stamp_from_terrain(vr_terrain* t, int which, int32_t x, int32_t y, int32_t w, int32_t h, vr_stamp** out);
+VR_API void vr_stamp_destroy(vr_stamp* stamp);
+VR_API int  vr_stamp_info(const vr_stamp* stamp, int32_t* format, int32_t* w, int32_t* h);
+VR_API int  vr_stamp_download(vr_stamp* stamp, void* host, size_t bytes);
+enum { VR_STAMP_BLEND = 0, VR_STAMP_ADD = 1, VR_STAMP_SUB = 2, VR_STAMP_MAX = 3, VR_STAMP_MIN = 4 };
+enum { VR_STAMP_USE_ALPHA = 1 };       /* SRGBA8 only: the stamp's alpha scales the weight */
+typedef struct vr_stamp_params {       /* 64 B */
+    float x, z;                        /* centre, world units */
+    float size_x, size_z;              /* world extent of the stamp along its own axes, > 0 */
+    float rotation;                    /* radians about y */
+    float opacity;                     /* [0, 1] */
+    float feather;                     /* [0, 1]: share of each half-extent over which the weight falls to 0 at the border; 0 = hard edge */
+    float gain, offset;                /* s' = s * gain + offset, in stored units; |gain| <= 256, |offset| <= 255 */
+    int32_t op;                        /* VR_STAMP_BLEND .. VR_STAMP_MIN */
+    uint32_t channel_mask;             /* 1 .. 15, like PAINT's; 1 on R8 */
+    uint32_t flags;                    /* VR_STAMP_USE_ALPHA */
+    int32_t reserved[4];               /* zero */
+} vr_stamp_params;
+VR_API int vr_terrain_stamp(vr_terrain* t, int which, vr_stamp* stamp, const vr_stamp_params* params, int32_t out_rect[4]);
 /* Thermal (talus) erosion of level 0 of the heightmap under a brush mask, computed on the device from the map as it is there and
  * followed by the refresh vr_terrain_edit does: afterwards the terrain is the one vr_terrain_create builds from the eroded map.
  * The dabs are those of a stroke on the heightmap, their strength an opacity in [0, 1]; they form a mask, per texel the largest
@@ -404,13 +467,13 @@ VR_API int vr_debug_hydro_config(int32_t out[4]);
 /* measurement helper, process-wide: later calls advance `sweeps` (1 .. the build's figure; 0 = that figure again) sweeps per
  * launch.  The bytes are the same; only the number of launches changes.  VR_ERR_INVALID_ARGUMENT outside that range. */
 VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps);
-/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
+/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
  * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
  *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
  *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
  *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
  *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
- *   records               with history on, every vr_terrain_edit, _brush, _texture, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
+ *   records               with history on, every vr_terrain_edit, _brush, _texture, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
  *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
  *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
  *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no

@@ -98,6 +98,30 @@ namespace vRenderer
         int Height() const { return m_Height; }
     };
 
+    // A stamp (vr_stamp): a patch of R8 (heightmap) or SRGBA8 (albedo) texels in device memory, owned by a device, for
+    // TerrainPass::Stamp.  Destroyed before its device.
+    class Stamp
+    {
+        vr_stamp* m_Stamp = nullptr;
+    public:
+        Stamp() = default;
+        ~Stamp() { vr_stamp_destroy(m_Stamp); }
+        Stamp(const Stamp&) = delete;
+        Stamp& operator=(const Stamp&) = delete;
+        // vr_stamp_create: w x h texels of `format` (VR_STAMP_R8 / VR_STAMP_SRGBA8), rows rowPitchBytes apart (0 = tightly packed);
+        // from host memory the call returns once it has been consumed, from device memory the copy is stream-ordered.
+        bool Create(Device& device, int format, int32_t w, int32_t h, const void* texels, size_t rowPitchBytes = 0, bool devicePointer = false)
+        {
+            vr_stamp_destroy(m_Stamp); m_Stamp = nullptr;
+            return Check(vr_stamp_create(device.Get(), format, w, h, texels, rowPitchBytes, devicePointer ? 1 : 0, &m_Stamp), "vr_stamp_create");
+        }
+        // takes ownership of a stamp made elsewhere (TerrainPass::CaptureStamp)
+        void Reset(vr_stamp* stamp = nullptr) { vr_stamp_destroy(m_Stamp); m_Stamp = stamp; }
+        bool Info(int32_t& format, int32_t& w, int32_t& h) const { return Check(vr_stamp_info(m_Stamp, &format, &w, &h), "vr_stamp_info"); }
+        bool Download(void* host, size_t bytes) const { return Check(vr_stamp_download(m_Stamp, host, bytes), "vr_stamp_download"); }
+        vr_stamp* Get() const { return m_Stamp; }
+    };
+
     class TerrainPass;
 
     // QuadTree (QuadTree.h:64-127).  The tree itself is implicit on the device; this object is the
@@ -227,6 +251,21 @@ namespace vRenderer
             vr_texture_params p = {};
             p.num_layers = numLayers; p.flags = wholeMap ? (uint32_t)VR_TEXTURE_WHOLE_MAP : 0u; p.max_height = maxHeight;
             return Check(vr_terrain_texture(m_Terrain, &p, layers, dabs, n, outRect), "vr_terrain_texture");
+        }
+        // vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap (which = 0) or the albedo (1) as they are on the
+        // device, into `out` - the clone tool's source; a device copy on the context's stream, nothing is synchronised.
+        bool CaptureStamp(int which, int32_t x, int32_t y, int32_t w, int32_t h, vRenderer::Stamp& out)
+        {
+            vr_stamp* s = nullptr;
+            const bool ok = Check(vr_stamp_from_terrain(m_Terrain, which, x, y, w, h, &s), "vr_stamp_from_terrain");
+            out.Reset(s);
+            return ok;
+        }
+        // vr_terrain_stamp: `stamp` set into level 0 of map `which` at params' position, size and angle with its blend rule, computed
+        // on the device; stream-ordered like Brush, nothing is synchronised.  outRect as for Brush.
+        bool Stamp(int which, const vRenderer::Stamp& stamp, const vr_stamp_params& params, int32_t outRect[4] = nullptr)
+        {
+            return Check(vr_terrain_stamp(m_Terrain, which, stamp.Get(), &params, outRect), "vr_terrain_stamp");
         }
         // vr_terrain_erode: `iterations` sweeps of thermal erosion of the heightmap's level 0 under the mask the n dabs form (strength =
         // opacity; their order does not matter), computed on the device; stream-ordered like Brush, nothing is synchronised.

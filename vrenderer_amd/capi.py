@@ -44,6 +44,15 @@ VR_ERODE_MAX_ITERATIONS = 1024
 VR_TEXTURE_MAX_LAYERS = 8
 VR_TEXTURE_WHOLE_MAP = 1
 VR_HYDRO_MAX_ITERATIONS = 1024
+VR_STAMP_R8 = 0
+VR_STAMP_SRGBA8 = 1
+VR_STAMP_BLEND = 0
+VR_STAMP_ADD = 1
+VR_STAMP_SUB = 2
+VR_STAMP_MAX = 3
+VR_STAMP_MIN = 4
+VR_STAMP_USE_ALPHA = 1
+VR_STAMP_MAX_SIDE = 4096
 VR_DEBUG_TABLE_QUAD = 0
 VR_DEBUG_TABLE_QUADF = 1
 VR_DEBUG_TABLE_FAST = 2
@@ -196,6 +205,14 @@ class TextureParams(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("flags", C.c_uint32), ("max_height", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
+class StampParams(C.Structure):
+    """vr_stamp_params: where a stamp lands (centre, extent along its own axes, rotation about y), how it weighs (opacity, feather,
+    VR_STAMP_USE_ALPHA) and what it does (s' = s * gain + offset, op, channel_mask) - vr_terrain_stamp."""
+    _fields_ = [("x", C.c_float), ("z", C.c_float), ("size_x", C.c_float), ("size_z", C.c_float), ("rotation", C.c_float), ("opacity", C.c_float),
+                ("feather", C.c_float), ("gain", C.c_float), ("offset", C.c_float), ("op", C.c_int32), ("channel_mask", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_int32 * 4)]
+
+
 class HistoryStatus(C.Structure):
     """vr_history_status: what undo / redo can apply now, the open step, the steps lost to the budget, the arena's bytes."""
     _fields_ = [("undo_steps", C.c_uint32), ("redo_steps", C.c_uint32), ("open_records", C.c_uint32), ("dropped_steps", C.c_uint32),
@@ -206,6 +223,7 @@ assert C.sizeof(HistoryStatus) == 32
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32 and C.sizeof(ErodeParams) == 32 and C.sizeof(HydroParams) == 32
 assert C.sizeof(TextureLayer) == 64 and C.sizeof(TextureParams) == 32
+assert C.sizeof(StampParams) == 64
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -232,6 +250,7 @@ EXPORTS = [
     "vr_terrain_query_heights", "vr_terrain_cast_rays", "vr_debug_terrain_query_pyramid", "vr_debug_terrain_tables", "vr_view_pixel_ray", "vr_terrain_edit", "vr_terrain_brush", "vr_terrain_texture", "vr_terrain_erode", "vr_debug_erode_config",
     "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
+    "vr_stamp_create", "vr_stamp_from_terrain", "vr_stamp_destroy", "vr_stamp_info", "vr_stamp_download", "vr_terrain_stamp",
 ]
 
 _lib = None
@@ -369,6 +388,12 @@ def load_library():
         "vr_terrain_undo": (C.c_int, [vp, P(C.c_int32)]),
         "vr_terrain_redo": (C.c_int, [vp, P(C.c_int32)]),
         "vr_terrain_history_status": (C.c_int, [vp, P(HistoryStatus)]),
+        "vr_stamp_create": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int, P(vp)]),
+        "vr_stamp_from_terrain": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(vp)]),
+        "vr_stamp_destroy": (None, [vp]),
+        "vr_stamp_info": (C.c_int, [vp, P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
+        "vr_stamp_download": (C.c_int, [vp, vp, C.c_size_t]),
+        "vr_terrain_stamp": (C.c_int, [vp, C.c_int, vp, P(StampParams), P(C.c_int32)]),
     }
     for name in EXPORTS:
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -252,6 +252,47 @@ class HdrImage:
             self.handle = None
 
 
+class Stamp:
+    """vr_stamp: a patch of texels in device memory, owned by a context, for TerrainPass.Stamp.  `texels`: uint8 (h, w) makes an R8
+    stamp (for the heightmap), uint8 (h, w, 4) an SRGBA8 one (for the albedo); the call returns once the array has been consumed.
+    With device_ptr (a raw device pointer to w x h texels of `fmt` = 'height' / 'albedo', rows `pitch` bytes apart, 0 = tightly
+    packed) the copy is stream-ordered and the memory must stay as it is until the stream has passed it.  1 .. 4096 texels per side."""
+
+    def __init__(self, ctx, texels=None, device_ptr=None, fmt=None, w=None, h=None, pitch=0, handle=None):
+        self.ctx = ctx
+        if handle is not None:
+            self.handle = handle
+            return
+        out = C.c_void_p()
+        if device_ptr is None:
+            a = np.ascontiguousarray(texels, np.uint8)
+            assert a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 4)
+            fid = capi.VR_STAMP_R8 if a.ndim == 2 else capi.VR_STAMP_SRGBA8
+            check(ctx.lib.vr_stamp_create(ctx.handle, fid, a.shape[1], a.shape[0], _vp(a), 0, 0, C.byref(out)), "vr_stamp_create")
+        else:
+            fid = {"height": capi.VR_STAMP_R8, "albedo": capi.VR_STAMP_SRGBA8}.get(fmt, fmt)
+            check(ctx.lib.vr_stamp_create(ctx.handle, fid, w, h, C.c_void_p(device_ptr), pitch, 1, C.byref(out)), "vr_stamp_create")
+        self.handle = out
+
+    def info(self):
+        """(format, w, h): format is capi.VR_STAMP_R8 or capi.VR_STAMP_SRGBA8."""
+        f, w, h = C.c_int32(), C.c_int32(), C.c_int32()
+        check(self.ctx.lib.vr_stamp_info(self.handle, C.byref(f), C.byref(w), C.byref(h)), "vr_stamp_info")
+        return f.value, w.value, h.value
+
+    def download(self):
+        """vr_stamp_download (synchronous): uint8 (h, w) of an R8 stamp, (h, w, 4) of an SRGBA8 one."""
+        f, w, h = self.info()
+        out = np.empty((h, w) if f == capi.VR_STAMP_R8 else (h, w, 4), np.uint8)
+        check(self.ctx.lib.vr_stamp_download(self.handle, _vp(out), out.nbytes), "vr_stamp_download")
+        return out
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.vr_stamp_destroy(self.handle)
+            self.handle = None
+
+
 class LdrImage:
     """LdrColor, SRGBA8_UNORM (Renderer.h:81-92): a vr_ldr_image of width*height*4 bytes of device memory, or the
     packed RGB8 tiles of one rank when used as a multi-GPU send buffer (capacity_bytes)."""
@@ -600,6 +641,32 @@ class TerrainPass:
         params = capi.TextureParams(num_layers=len(layers), flags=capi.VR_TEXTURE_WHOLE_MAP if whole_map else 0, max_height=float(max_height))
         rect = (C.c_int32 * 4)()
         check(self.ctx.lib.vr_terrain_texture(self.handle, C.byref(params), arr, _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_texture")
+        return tuple(int(v) for v in rect)
+
+    def CaptureStamp(self, which, x, y, w, h):
+        """vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap ('height' / 0) or the albedo ('albedo' / 1) as
+        they are on the device, as a Stamp - the clone tool's source; a device copy on the context's stream, nothing is synchronised."""
+        idx = {"height": 0, "albedo": 1}.get(which, which)
+        out = C.c_void_p()
+        check(self.ctx.lib.vr_stamp_from_terrain(self.handle, idx, x, y, w, h, C.byref(out)), "vr_stamp_from_terrain")
+        return Stamp(self.ctx, handle=out)
+
+    def Stamp(self, which, stamp, x, z, size_x, size_z, rotation=0.0, opacity=1.0, feather=0.0, gain=1.0, offset=0.0, op="blend", channels=None,
+              use_alpha=False):
+        """vr_terrain_stamp: `stamp` set into level 0 of the heightmap ('height' / 0) or the albedo ('albedo' / 1), computed on the
+        device; stream-ordered, nothing is synchronised.  (x, z): the centre in world units; size_x, size_z: the stamp's world extent
+        along its own axes; rotation: radians about y; opacity and feather in [0, 1]; the sample is s * gain + offset in stored units;
+        op: 'blend', 'add', 'sub', 'max', 'min' or capi.VR_STAMP_*; channels: the channel mask (default: 1 for the heightmap, 0xF for
+        the albedo); use_alpha: the stamp's alpha scales the weight (albedo only).  Returns (x, y, w, h) of the level-0 rectangle the
+        call treated as dirty, (0, 0, 0, 0) when the stamp misses the map."""
+        idx = {"height": 0, "albedo": 1}.get(which, which)
+        oid = {"blend": capi.VR_STAMP_BLEND, "add": capi.VR_STAMP_ADD, "sub": capi.VR_STAMP_SUB, "max": capi.VR_STAMP_MAX, "min": capi.VR_STAMP_MIN}.get(op, op)
+        p = capi.StampParams(x=float(x), z=float(z), size_x=float(size_x), size_z=float(size_z), rotation=float(rotation), opacity=float(opacity),
+                             feather=float(feather), gain=float(gain), offset=float(offset), op=int(oid),
+                             channel_mask=int(channels) if channels is not None else (1 if idx == 0 else 0xF),
+                             flags=capi.VR_STAMP_USE_ALPHA if use_alpha else 0)
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_stamp(self.handle, idx, stamp.handle, C.byref(p), rect), "vr_terrain_stamp")
         return tuple(int(v) for v in rect)
 
     def Erode(self, dabs, iterations, talus, rate):
