@@ -186,7 +186,7 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
  * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
  * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
- * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _noise / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
  * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
  * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
  * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
@@ -334,6 +334,64 @@ typedef struct vr_texture_layer {      /* 64 B */
 typedef struct vr_texture_params { int32_t num_layers; uint32_t flags; float max_height; int32_t reserved[5]; } vr_texture_params; /* 32 B */
 VR_API int vr_terrain_texture(vr_terrain* t, const vr_texture_params* p, const vr_texture_layer* layers,
                               const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
+/* Procedural noise on level 0 of the heightmap (which = 0) or the albedo (1) - roughen a plateau, break up a smooth flank, speckle
+ * an albedo, or make a fractal base terrain on a flat map - under a brush mask or over the whole map, computed on the device from
+ * the map as it is there and followed by the refresh vr_terrain_edit does: afterwards the terrain is the one vr_terrain_create
+ * builds from the noised maps.  The noise lives in world space: octave o (0 .. octaves - 1) is a lattice of frequency *
+ * lacunarity^o cells per world unit over the world position plus (offset_x, offset_z), so the same parameters give the same
+ * landscape on maps of different resolution.  Each lattice corner is hashed with seed + o; a texel's centre falls into a cell at
+ * (tx, tz) and is interpolated with the quintic fade t^3 (t (6 t - 15) + 10):
+ *   VR_NOISE_VALUE     the corner's value is the hash's top 24 bits in [-1, 1); n = the faded bilinear interpolation
+ *   VR_NOISE_GRADIENT  the corner takes one of eight unit gradients (four axis directions, four diagonals) by three hash bits; n =
+ *                      the faded interpolation of the gradients' dot products with the offsets to the corners, times sqrt 2
+ * Either n lies in [-1, 1].  The octaves are summed in ascending order with the weights a_o = gain^o / sum of gain^k, which sum to 1:
+ *   VR_NOISE_FBM     f += a_o * n_o
+ *   VR_NOISE_BILLOW  f += a_o * (2 |n_o| - 1)
+ *   VR_NOISE_RIDGED  f += a_o * (1 - 2 |n_o|)
+ * so f lies in [-1, 1].  Per channel c of channel_mask (as PAINT's; the heightmap has the one channel, mask 1; every selected
+ * channel of an albedo texel receives the same f):
+ *   VR_NOISE_ADD    value_c += m * (amplitude * f)                           amplitude signed, in stored units, |amplitude| <= 255
+ *   VR_NOISE_BLEND  value_c += m * ((base + amplitude * f) - value_c)        base in [0, 255]
+ * clamped to [0, 255] and rounded to the nearest byte once.  m is the mask of vr_terrain_erode (below) of the dabs, prepared for map
+ * `which` with their strength an opacity - per texel the largest weight * strength, so their order does not matter - or 1 on every
+ * texel with VR_NOISE_WHOLE_MAP, which needs dabs == NULL and n == 0 and whose rectangle is the whole map.  A texel with mask 0 is not
+ * written.  A texel is a function of its own byte, its position, the parameters and its mask alone.  The arithmetic is defined bit for
+ * bit in vrenderer_amd/csrc/vr_noise.h, without a division, a power or anything transcendental on the device.
+ * out_rect, `dabs`, the stream order and what the host waits for are vr_terrain_brush's: the call synchronises nothing, and is
+ * ordered against the strokes and erosions of the terrain.  With history on, one call is one record.  n == 0 without the flag, or
+ * dabs that all miss the map, is VR_OK and launches nothing.
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the terrain untouched: NULL t or p; `which` not 0 or 1;
+ * octaves outside 1 .. VR_NOISE_MAX_OCTAVES; an unknown basis, fractal, op or flag bit; VR_NOISE_WHOLE_MAP together with dabs; NULL
+ * dabs with n > 0; n > VR_MAX_BRUSH_DABS; a NaN or an infinity in a field; frequency <= 0; lacunarity outside [1, 4]; gain outside
+ * [0, 1]; |amplitude| > 255; base outside [0, 255]; a channel_mask of 0 or above 15, or other than 1 on the heightmap; a non-zero
+ * reserved word; the dab refusals of vr_terrain_brush with an opacity for a strength.  One more refusal needs the map's size and is
+ * checked behind those, before anything is queued: an octave whose lattice coordinate - (texel centre's world position + offset) *
+ * frequency * lacunarity^o - reaches 2^22 in magnitude at one of the map's four corners.  Below that bound the cell index is an
+ * exact int32 and the position inside the cell keeps at least a bit of fraction; beyond it the noise would be meaningless, not
+ * merely coarse.  The memory a call needs is reserved before anything is launched (VR_ERR_OUT_OF_MEMORY leaves the terrain as it
+ * was).  Timing: as for vr_terrain_edit; the noise kernel itself is untimed. */
+#define VR_NOISE_MAX_OCTAVES 12
+enum { VR_NOISE_VALUE = 0, VR_NOISE_GRADIENT = 1 };
+enum { VR_NOISE_FBM = 0, VR_NOISE_BILLOW = 1, VR_NOISE_RIDGED = 2 };
+enum { VR_NOISE_ADD = 0, VR_NOISE_BLEND = 1 };
+enum { VR_NOISE_WHOLE_MAP = 1 };
+typedef struct vr_noise_params {       /* 64 B */
+    float frequency;                   /* lattice cells per world unit of octave 0, > 0 */
+    float offset_x, offset_z;          /* added to the world position: the lattice origin lies at world (-offset_x, -offset_z) */
+    float lacunarity;                  /* frequency ratio of successive octaves, [1, 4] */
+    float gain;                        /* weight ratio of successive octaves, [0, 1] */
+    float amplitude;                   /* stored units, signed, |amplitude| <= 255 */
+    float base;                        /* BLEND's level, [0, 255] */
+    uint32_t seed;
+    int32_t octaves;                   /* 1 .. VR_NOISE_MAX_OCTAVES */
+    int32_t basis;                     /* VR_NOISE_VALUE, VR_NOISE_GRADIENT */
+    int32_t fractal;                   /* VR_NOISE_FBM, VR_NOISE_BILLOW, VR_NOISE_RIDGED */
+    int32_t op;                        /* VR_NOISE_ADD, VR_NOISE_BLEND */
+    uint32_t channel_mask;             /* 1 .. 15, like PAINT's; 1 on the heightmap */
+    uint32_t flags;                    /* VR_NOISE_WHOLE_MAP */
+    int32_t reserved[2];               /* zero */
+} vr_noise_params;
+VR_API int vr_terrain_noise(vr_terrain* t, int which, const vr_noise_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
 /* Stamps: a prepared patch - a mountain, a crater, a scanned tile, an albedo decal - kept in device memory and set into level 0 of a
  * map at a position, size and angle, with a blend rule.  A vr_stamp is w x h texels, 1 .. 4096 per side, of one of the maps' formats:
  * VR_STAMP_R8 (the heightmap's, = which 0) or VR_STAMP_SRGBA8 (the albedo's, = which 1).  It belongs to the context it was created
@@ -467,13 +525,13 @@ VR_API int vr_debug_hydro_config(int32_t out[4]);
 /* measurement helper, process-wide: later calls advance `sweeps` (1 .. the build's figure; 0 = that figure again) sweeps per
  * launch.  The bytes are the same; only the number of launches changes.  VR_ERR_INVALID_ARGUMENT outside that range. */
 VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps);
-/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
+/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_noise, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
  * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
  *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
  *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
  *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
  *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
- *   records               with history on, every vr_terrain_edit, _brush, _texture, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
+ *   records               with history on, every vr_terrain_edit, _brush, _texture, _noise, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
  *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
  *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
  *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no

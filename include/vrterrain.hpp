@@ -252,6 +252,17 @@ namespace vRenderer
             p.num_layers = numLayers; p.flags = wholeMap ? (uint32_t)VR_TEXTURE_WHOLE_MAP : 0u; p.max_height = maxHeight;
             return Check(vr_terrain_texture(m_Terrain, &p, layers, dabs, n, outRect), "vr_terrain_texture");
         }
+        // vr_terrain_noise: fractal value or gradient noise (params: frequency, offset, lacunarity, gain, octaves, seed, basis, fractal)
+        // added to or blended into level 0 of the heightmap (which = 0) or the albedo (1) under the mask the n dabs form (as for
+        // Erode, prepared for that map), or over the whole map (wholeMap: dabs == nullptr, n == 0; sets VR_NOISE_WHOLE_MAP in a copy
+        // of params); computed on the device, stream-ordered like Brush, nothing is synchronised, and `dabs` is free again when the
+        // call returns.  outRect as for Brush.
+        bool Noise(int which, const vr_noise_params& params, const vr_brush_dab* dabs, uint32_t n, bool wholeMap = false, int32_t outRect[4] = nullptr)
+        {
+            vr_noise_params p = params;
+            if (wholeMap) p.flags |= (uint32_t)VR_NOISE_WHOLE_MAP;
+            return Check(vr_terrain_noise(m_Terrain, which, &p, dabs, n, outRect), "vr_terrain_noise");
+        }
         // vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap (which = 0) or the albedo (1) as they are on the
         // device, into `out` - the clone tool's source; a device copy on the context's stream, nothing is synchronised.
         bool CaptureStamp(int which, int32_t x, int32_t y, int32_t w, int32_t h, vRenderer::Stamp& out)

@@ -44,6 +44,15 @@ VR_ERODE_MAX_ITERATIONS = 1024
 VR_TEXTURE_MAX_LAYERS = 8
 VR_TEXTURE_WHOLE_MAP = 1
 VR_HYDRO_MAX_ITERATIONS = 1024
+VR_NOISE_MAX_OCTAVES = 12
+VR_NOISE_VALUE = 0
+VR_NOISE_GRADIENT = 1
+VR_NOISE_FBM = 0
+VR_NOISE_BILLOW = 1
+VR_NOISE_RIDGED = 2
+VR_NOISE_ADD = 0
+VR_NOISE_BLEND = 1
+VR_NOISE_WHOLE_MAP = 1
 VR_STAMP_R8 = 0
 VR_STAMP_SRGBA8 = 1
 VR_STAMP_BLEND = 0
@@ -205,6 +214,15 @@ class TextureParams(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("flags", C.c_uint32), ("max_height", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
+class NoiseParams(C.Structure):
+    """vr_noise_params: the lattice (frequency in cells per world unit, offset added to the world position, lacunarity, gain, octaves,
+    seed), what it is made of (basis, fractal) and what it does (amplitude and base in stored units, op, channel_mask) -
+    vr_terrain_noise."""
+    _fields_ = [("frequency", C.c_float), ("offset_x", C.c_float), ("offset_z", C.c_float), ("lacunarity", C.c_float), ("gain", C.c_float),
+                ("amplitude", C.c_float), ("base", C.c_float), ("seed", C.c_uint32), ("octaves", C.c_int32), ("basis", C.c_int32),
+                ("fractal", C.c_int32), ("op", C.c_int32), ("channel_mask", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
 class StampParams(C.Structure):
     """vr_stamp_params: where a stamp lands (centre, extent along its own axes, rotation about y), how it weighs (opacity, feather,
     VR_STAMP_USE_ALPHA) and what it does (s' = s * gain + offset, op, channel_mask) - vr_terrain_stamp."""
@@ -224,6 +242,7 @@ assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32 and C.sizeof(ErodeParams) == 32 and C.sizeof(HydroParams) == 32
 assert C.sizeof(TextureLayer) == 64 and C.sizeof(TextureParams) == 32
 assert C.sizeof(StampParams) == 64
+assert C.sizeof(NoiseParams) == 64
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -251,6 +270,7 @@ EXPORTS = [
     "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
     "vr_stamp_create", "vr_stamp_from_terrain", "vr_stamp_destroy", "vr_stamp_info", "vr_stamp_download", "vr_terrain_stamp",
+    "vr_terrain_noise",
 ]
 
 _lib = None
@@ -377,6 +397,7 @@ def load_library():
         "vr_terrain_edit": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int]),
         "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_texture": (C.c_int, [vp, P(TextureParams), vp, vp, C.c_uint32, P(C.c_int32)]),
+        "vr_terrain_noise": (C.c_int, [vp, C.c_int, P(NoiseParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_erode": (C.c_int, [vp, P(ErodeParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_debug_erode_config": (C.c_int, [P(C.c_int32)]),
         "vr_terrain_erode_hydraulic": (C.c_int, [vp, P(HydroParams), vp, C.c_uint32, P(C.c_int32)]),

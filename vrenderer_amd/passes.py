@@ -643,6 +643,36 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_texture(self.handle, C.byref(params), arr, _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_texture")
         return tuple(int(v) for v in rect)
 
+    def Noise(self, which, frequency, amplitude, octaves=6, lacunarity=2.0, gain=0.5, offset=(0.0, 0.0), seed=0, basis="gradient", fractal="fbm",
+              op="add", base=0.0, channels=None, dabs=None, whole_map=False):
+        """vr_terrain_noise: fractal noise added to ('add') or blended into ('blend', about `base`) level 0 of the heightmap ('height' /
+        0) or the albedo ('albedo' / 1), computed on the device; stream-ordered, nothing is synchronised.  `frequency`: lattice cells
+        per world unit of the first octave; `offset`: added to the world position; `octaves` (1 .. 12), `lacunarity` (1 .. 4), `gain`
+        (0 .. 1): the fractal; `basis`: 'value', 'gradient' or capi.VR_NOISE_*; `fractal`: 'fbm', 'billow', 'ridged'; `amplitude` and
+        `base` in stored units; `channels`: the channel mask (default: 1 for the heightmap, 0xF for the albedo).  `dabs`: rows as for
+        Erode (strength an opacity), prepared for that map; their mask limits the call.  whole_map=True takes no dabs: mask 1 on every
+        texel.  Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
+        idx = {"height": 0, "albedo": 1}.get(which, which)
+        a = np.asarray(dabs if dabs is not None else np.zeros((0, 5), np.float32), np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 5)
+        assert a.ndim == 2 and a.shape[1] in (5, 8)
+        if a.shape[1] == 5:
+            full = np.zeros((a.shape[0], 8), np.float32)
+            full[:, :5] = a
+            a = full
+        a = np.ascontiguousarray(a)
+        p = capi.NoiseParams(frequency=float(frequency), offset_x=float(offset[0]), offset_z=float(offset[1]), lacunarity=float(lacunarity), gain=float(gain),
+                             amplitude=float(amplitude), base=float(base), seed=int(seed) & 0xFFFFFFFF, octaves=int(octaves),
+                             basis={"value": capi.VR_NOISE_VALUE, "gradient": capi.VR_NOISE_GRADIENT}.get(basis, basis),
+                             fractal={"fbm": capi.VR_NOISE_FBM, "billow": capi.VR_NOISE_BILLOW, "ridged": capi.VR_NOISE_RIDGED}.get(fractal, fractal),
+                             op={"add": capi.VR_NOISE_ADD, "blend": capi.VR_NOISE_BLEND}.get(op, op),
+                             channel_mask=int(channels) if channels is not None else (1 if idx == 0 else 0xF),
+                             flags=capi.VR_NOISE_WHOLE_MAP if whole_map else 0)
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_noise(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_noise")
+        return tuple(int(v) for v in rect)
+
     def CaptureStamp(self, which, x, y, w, h):
         """vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap ('height' / 0) or the albedo ('albedo' / 1) as
         they are on the device, as a Stamp - the clone tool's source; a device copy on the context's stream, nothing is synchronised."""
