@@ -233,8 +233,11 @@ VR_API void vr_render_default_params(vr_render_params* out);
  * bytes (decoded with sRGB=true, Renderer.cpp:55).  Both are copied to the device
  * and mip chains are generated there (Donut TextureCache mip generation).
  * Limits: each texture at most 16384 texels on a side and 2^26 texels in all (8192 x 8192): the tile pass
- * reads decoded copies (16 B per texel / footprint, x 4/3 for the mips) through 32-bit offsets.  Device memory
- * held by a terrain: vr_terrain_memory_bytes(). */
+ * reads decoded copies (16 B per texel / footprint, x 4/3 for the mips) through 32-bit offsets.  The albedo has
+ * one such table more, the sRGB8 codes of every bilinear footprint packed into 16 B, which the fused frame kernel
+ * reads instead of the decoded texels: +90 MB per 2048 x 2048 terrain, and the steady-state frame then touches
+ * 180 MB of tables (90 of height footprints, 90 of packed albedo footprints) through a quarter of the albedo
+ * fetches.  Device memory held by a terrain: vr_terrain_memory_bytes(). */
 VR_API int  vr_terrain_create(vr_context* ctx, const vr_terrain_params* params,
                               const uint8_t* height_r8, int32_t hm_w, int32_t hm_h,
                               const uint8_t* albedo_srgba8, int32_t al_w, int32_t al_h,
@@ -671,6 +674,8 @@ VR_API int vr_debug_terrain_query_pyramid(vr_terrain* t, int32_t* out_levels, in
  *   VR_DEBUG_TABLE_QUADF  heightmap  (w + 2) x (h + 2) float[4] (t00, t10 - t00, t01, t11 - t01) of the same four texels
  *   VR_DEBUG_TABLE_FAST   both       (w + 3) x (h + 3) float[4] heightmap: as QUADF; albedo: (lin r, lin g, lin b, 0) of texel (ix-1, iy-1)
  *   VR_DEBUG_TABLE_RGBF   albedo     w x h float[4]             (lin r, lin g, lin b, 0) of texel (ix, iy)
+ *   VR_DEBUG_TABLE_PACK   albedo     (w + 3) x (h + 3) uint32[4] the sRGB8 codes of the footprint (ix-1, iy-1) (ix, iy-1) (ix-1, iy) (ix, iy), a dword
+ *                                                               per texel: r << 2 | g << 12 | b << 22 (what the fused tile pass reads instead of FAST)
  * out_dims receives {entries per row, rows} and `out` the entries, row-major and densely packed (padding between levels is never shown).
  * The copy runs on the context's stream - behind the tables' last writer as a tile pass's read of them is - and the entry returns when
  * it has completed; no kernel is launched and nothing is built.  out == NULL with capacity_bytes == 0 is a size query.  A table the map
@@ -678,6 +683,7 @@ VR_API int vr_debug_terrain_query_pyramid(vr_terrain* t, int32_t* out_levels, in
  * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with nothing written: NULL t or out_dims; which not 0 or 1; an
  * unknown table; a negative level; NULL out with a capacity; a capacity below the level's entries. */
 enum { VR_DEBUG_TABLE_QUAD = 0, VR_DEBUG_TABLE_QUADF = 1, VR_DEBUG_TABLE_FAST = 2, VR_DEBUG_TABLE_RGBF = 3 };
+enum { VR_DEBUG_TABLE_PACK = 5 };     /* (4 is no table: it stays the unknown id the entry refuses) */
 VR_API int vr_debug_terrain_tables(vr_terrain* t, int which, int table, int32_t level, int32_t out_dims[2], void* out, size_t capacity_bytes);
 /* Host only (picking; QuadTree.h:84 is what the reference would have called with it): the ray through the centre of pixel
  * (px, py) of view's viewport - screen point (px + 0.5, py + 0.5); fractional px, py are allowed.  The two ends are the

@@ -66,6 +66,7 @@ VR_DEBUG_TABLE_QUAD = 0
 VR_DEBUG_TABLE_QUADF = 1
 VR_DEBUG_TABLE_FAST = 2
 VR_DEBUG_TABLE_RGBF = 3
+VR_DEBUG_TABLE_PACK = 5
 
 
 class TerrainParams(C.Structure):

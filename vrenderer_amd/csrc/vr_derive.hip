@@ -22,6 +22,7 @@
 #include "vr_internal.h"
 #include "vr_terrain_dev.h"
 #include "vr_dirty.h"
+#include "vr_packed.h"
 
 #include <string.h>
 
@@ -51,8 +52,9 @@ __global__ __launch_bounds__(256) void k_derive_mip_srgba8(const uint32_t* __res
     vr_mip_srgba8_texel(src, sw, sh, dst, dw, x, y, lut, thr);
 }
 
-// One level's share of the tables launch.  `entries`: the dirty entries of the level's fast table, which the workgroups tile
-// (32 x 8 each, `blocks_x` per row, the level's first is `first_block`).  `inner`: R8 - the dirty entries of quad / quadf (same
+// One level's share of the tables launch.  `entries`: the dirty entries of the level's fast table - of an SRGBA8 map: of its pack
+// table, which has the same indexing and whose span holds fast's (one entry more in front; that one is rewritten with what it held)
+// - which the workgroups tile (32 x 8 each, `blocks_x` per row, the level's first is `first_block`).  `inner`: R8 - the dirty entries of quad / quadf (same
 // indexing, one entry less per side); SRGBA8 - the dirty texels of the chain, for rgbf (entry (ix, iy) is texel (ix-1, iy-1)).
 struct DeriveLevel {
     uint32_t chain_off;        // bytes into the chain
@@ -89,12 +91,15 @@ __global__ __launch_bounds__(256) void k_derive_tables_r8(DeriveTables d, const 
 // (rgbf holds a float4 per dword of the chain, the padding between two 256-byte-aligned levels included; only texels are ever
 // decoded, and the tile pass - its one reader - clamps every index into its level)
 __global__ __launch_bounds__(256) void k_derive_tables_srgba8(DeriveTables d, const uint8_t* __restrict__ chain, const float* __restrict__ lut,
-                                                               float4* __restrict__ fast, float* __restrict__ rgbf)
+                                                               float4* __restrict__ fast, float* __restrict__ rgbf, uint4* __restrict__ pack)
 {
     int l, ix, iy;
     if (!derive_tables_entry(d, l, ix, iy)) return;
     const DeriveLevel& e = d.lv[l];
     vr_fast_srgba8_entry((const uint32_t*)(chain + e.chain_off), e.w, e.h, lut, fast + e.fast_off, ix, iy);
+    uint32_t pk[4];
+    vr_packed_entry((const uint32_t*)(chain + e.chain_off), e.w, e.h, ix, iy, pk);
+    pack[(size_t)e.fast_off + (size_t)iy * (e.w + 3) + ix] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
     const int x = ix - 1, y = iy - 1;
     if (x >= e.inner.x0 && x < e.inner.x1 && y >= e.inner.y0 && y < e.inner.y1)
         vr_rgbf_texel((const uint32_t*)chain, (size_t)(e.chain_off / 4) + (size_t)y * e.w + x, lut, rgbf);
@@ -156,7 +161,7 @@ void vr_derive_chain(vr_context* ctx, uint8_t* mem, const TexLayout& lay, int w0
             e.entries = dirty_rect(dirty_fast_r8_entries(cx, lw), dirty_fast_r8_entries(cy, lh));
             e.inner = dirty_rect(dirty_quad_entries(cx, lw), dirty_quad_entries(cy, lh));
         } else {
-            e.entries = dirty_rect(dirty_fast_srgba8_entries(cx, lw), dirty_fast_srgba8_entries(cy, lh));
+            e.entries = dirty_rect(dirty_pack_srgba8_entries(cx, lw), dirty_pack_srgba8_entries(cy, lh));
             e.inner = chain[l];
         }
         e.first_block = blocks;
@@ -173,7 +178,8 @@ void vr_derive_chain(vr_context* ctx, uint8_t* mem, const TexLayout& lay, int w0
     }
     if (r8) hipLaunchKernelGGL(k_derive_tables_r8, dim3(blocks), dim3(256), 0, s, dt, mem, (uint32_t*)(mem + lay.quad_at), (float4*)(mem + lay.quadf_at),
                                (float4*)(mem + lay.fast_at));
-    else hipLaunchKernelGGL(k_derive_tables_srgba8, dim3(blocks), dim3(256), 0, s, dt, mem, ctx->d_srgb_lut, (float4*)(mem + lay.fast_at), (float*)(mem + lay.rgbf_at));
+    else hipLaunchKernelGGL(k_derive_tables_srgba8, dim3(blocks), dim3(256), 0, s, dt, mem, ctx->d_srgb_lut, (float4*)(mem + lay.fast_at), (float*)(mem + lay.rgbf_at),
+                            (uint4*)(mem + lay.pack_at));
 }
 
 void vr_derive_node_heights(vr_terrain* t, int surf, const NodeSurface& ns, const DirtyRect& dirty)
@@ -313,12 +319,13 @@ extern "C" VR_API int vr_debug_terrain_tables(vr_terrain* t, int which, int tabl
 {
     VR_REQUIRE(t != nullptr, "terrain is NULL");
     VR_REQUIRE(which == 0 || which == 1, "which must be 0 (heightmap) or 1 (albedo)");
-    VR_REQUIRE(table == VR_DEBUG_TABLE_QUAD || table == VR_DEBUG_TABLE_QUADF || table == VR_DEBUG_TABLE_FAST || table == VR_DEBUG_TABLE_RGBF, "unknown table");
+    VR_REQUIRE(table == VR_DEBUG_TABLE_QUAD || table == VR_DEBUG_TABLE_QUADF || table == VR_DEBUG_TABLE_FAST || table == VR_DEBUG_TABLE_RGBF
+               || table == VR_DEBUG_TABLE_PACK, "unknown table");
     VR_REQUIRE(level >= 0, "negative level");
     VR_REQUIRE(out_dims != nullptr, "out_dims is NULL");
     const DevTex& tex = which == 0 ? t->height : t->albedo;
     const TexLayout& lay = which == 0 ? t->height_layout : t->albedo_layout;
-    const bool has = table == VR_DEBUG_TABLE_FAST || (table == VR_DEBUG_TABLE_RGBF ? which == 1 : which == 0);
+    const bool has = table == VR_DEBUG_TABLE_FAST || (table == VR_DEBUG_TABLE_RGBF || table == VR_DEBUG_TABLE_PACK ? which == 1 : which == 0);
     int cols = 0, rows = 0;
     size_t at = 0, entry = 16;
     if (has && tex.base != nullptr && level < tex.levels) {
@@ -326,6 +333,7 @@ extern "C" VR_API int vr_debug_terrain_tables(vr_terrain* t, int which, int tabl
         if (table == VR_DEBUG_TABLE_QUAD) { cols = lw + 2; rows = lh + 2; entry = 4; at = lay.quad_at + (size_t)lay.qoff[level] * 4; }
         else if (table == VR_DEBUG_TABLE_QUADF) { cols = lw + 2; rows = lh + 2; at = lay.quadf_at + (size_t)lay.qoff[level] * 16; }
         else if (table == VR_DEBUG_TABLE_FAST) { cols = lw + 3; rows = lh + 3; at = lay.fast_at + (size_t)lay.fast_entry[level] * 16; }
+        else if (table == VR_DEBUG_TABLE_PACK) { cols = lw + 3; rows = lh + 3; at = lay.pack_at + (size_t)lay.fast_entry[level] * 16; }
         else { cols = lw; rows = lh; at = lay.rgbf_at + (size_t)(lay.off[level] / 4) * 16; }
     }
     const size_t bytes = (size_t)cols * (size_t)rows * entry;

@@ -16,6 +16,7 @@
 //                    quad, quadf  (w + 2 entries)  k = 0, 1
 //                    fast, R8     (w + 3 entries)  k = 0, 1
 //                    fast, SRGBA8 (w + 3 entries)  k = 0
+//                    pack, SRGBA8 (w + 3 entries)  k = 0, 1      (a whole footprint per entry: vr_packed.h)
 //                  so texels [x0, x1) dirty the entries [x0 + 1 - k1, x1 + 1 - k0); a span that touches texel 0 also dirties
 //                  every entry in front (they clamp to it), one that touches texel w - 1 every entry behind.  rgbf is indexed
 //                  like the chain.
@@ -83,6 +84,7 @@ inline DirtySpan dirty_entries(DirtySpan s, int w, int tw, int k0, int k1)
 inline DirtySpan dirty_quad_entries(DirtySpan s, int w) { return dirty_entries(s, w, w + 2, 0, 1); }          // quad and quadf
 inline DirtySpan dirty_fast_r8_entries(DirtySpan s, int w) { return dirty_entries(s, w, w + 3, 0, 1); }
 inline DirtySpan dirty_fast_srgba8_entries(DirtySpan s, int w) { return dirty_entries(s, w, w + 3, 0, 0); }
+inline DirtySpan dirty_pack_srgba8_entries(DirtySpan s, int w) { return dirty_entries(s, w, w + 3, 0, 1); }    // holds fast's span: one entry more in front
 
 // ---- node heights (mip-style path) ----
 // `origin`: first texel of the surface's root on this axis, `s`: texels per leaf node, `n`: leaf nodes per side

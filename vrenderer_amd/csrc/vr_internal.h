@@ -136,6 +136,9 @@ struct TexLayout {
     uint32_t qoff[kMaxLevels];         // entries into quad / quadf (R8 only)
     uint32_t fast_entry[kMaxLevels];   // entries into fast
     size_t quad_at, quadf_at, rgbf_at, fast_at;     // bytes from the chain's first to each table (0: the texture has none)
+    // SRGBA8 only: the packed footprint table of the fused tile pass (vr_packed.h) - entry for entry where `fast` has its own
+    // (fast_entry, fast_lv and DevTex::fast_bytes hold for both), so it is not part of DevTex: the fused launch is handed the pointer
+    size_t pack_at;
 };
 
 // Per-light constants the deferred kernel reads (host precomputes the half-angle terms).
@@ -433,7 +436,7 @@ int vr_node_heights_surface(vr_terrain* t, int surf, const NodeSurface& ns);    
 // terrain passes the whole map, vr_terrain_edit what it replaced.  The three queue launches and report nothing: hipGetLastError
 // afterwards.
 struct DirtyRect;
-// levels 1 .. of the chain at `mem` and the texture's tables (quad, quadf, fast of an R8 map; fast, rgbf of an SRGBA8 one), on the context's stream
+// levels 1 .. of the chain at `mem` and the texture's tables (quad, quadf, fast of an R8 map; fast, rgbf, pack of an SRGBA8 one), on the context's stream
 void vr_derive_chain(vr_context* ctx, uint8_t* mem, const TexLayout& lay, int w0, int h0, int levels, int texel_bytes, const DirtyRect& dirty);
 // the node heights of one surface on the mip-style path (ns.dyadic; d_node_heights and d_minmax exist), on the context's stream
 void vr_derive_node_heights(vr_terrain* t, int surf, const NodeSurface& ns, const DirtyRect& dirty);

@@ -30,6 +30,7 @@
 #include "vr_deferred_dev.h"
 #include "vr_terrain_surface.h"
 #include "vr_experiments.h"
+#include "vr_packed.h"
 #include <type_traits>
 
 #include <stdlib.h>
@@ -925,6 +926,8 @@ extern "C" VR_API int vr_debug_raster_prof(unsigned long long out[16], int reset
 //   - heights and albedo are read from the clamp-padded tables of DevTex::fast: one set of byte offsets serves the four
 //     height taps and the albedo footprint, built from three row products and fast adds; no clamp, no shift - an index
 //     is scaled by 16 as a FLOAT (exact) before its conversion, right / lower neighbours are immediate offsets;
+//     the fused flavours read the albedo footprint as ONE entry of packed sRGB8 codes at the same offset and decode it through
+//     the LUT they hold in LDS (PACKED below; vr_packed.h) - the same floats, a quarter of the albedo fetches;
 //   - what a pixel needs of a mip level (table offset, row bytes, float sizes) is one 16-byte LDS read;
 //   - the implicit LOD has no compare / select (oracle: lod_from_derivs), its clamp is one v_med3;
 //   - no range check in front of the short reciprocal: a pixel inside its triangle interpolates 1/w between its vertices'.
@@ -950,6 +953,9 @@ struct FastTaps { u32x4 e0, e1, e2, e3, p00, p10, p01, p11; float fxa, fxb, fx0,
 #define FAST_AXIS_INSIDE(f_, i_, t_, n_, scale_) do { const float x_ = __builtin_fmaf((t_), (n_), -0.5f); const float xf_ = floorf(x_); (f_) = x_ - xf_; \
                                                        (i_) = (int)(xf_ * (scale_)); } while (0)
 
+// PACKED (the fused flavours): rc is the albedo's packed footprint table (vr_packed.h) - same offsets, and the entry at a00 holds the
+// codes of all four texels: one fetch instead of four, four data registers held across the wait instead of sixteen.
+template <bool PACKED>
 __device__ __forceinline__ FastTaps issue_level_fast(__amdgpu_buffer_rsrc_t rq, __amdgpu_buffer_rsrc_t rc, const uint4* __restrict__ s_lv, int lvl16,
                                                      float ua, float ub, float va, float vb, float u0, float v0)
 {
@@ -967,6 +973,7 @@ __device__ __forceinline__ FastTaps issue_level_fast(__amdgpu_buffer_rsrc_t rq, 
     t.e0 = LD(rq, row0 + (uint32_t)xa);
     if (!kExpOneHeight) { t.e1 = LD(rq, row0 + (uint32_t)xb); t.e2 = LD(rq, rowa + (uint32_t)x0); t.e3 = LD(rq, rowb + (uint32_t)x0); }
     t.p00 = LD(rc, a00);
+    if (PACKED) { if (kExpOneHeight) { t.e1 = t.e0; t.e2 = t.e0; t.e3 = t.e0; } return t; }
     if (!(kExpOneHeight || kExpOneAlbedo)) { t.p10 = LD(rc, a00 + 16u); t.p01 = LD(rc, a01); t.p11 = LD(rc, a01 + 16u); }
     if (kExpOneHeight) { t.e1 = t.e0; t.e2 = t.e0; t.e3 = t.e0; }
     if (kExpOneHeight || kExpOneAlbedo) { t.p10 = t.p00; t.p01 = t.p00; t.p11 = t.p00; }
@@ -974,7 +981,10 @@ __device__ __forceinline__ FastTaps issue_level_fast(__amdgpu_buffer_rsrc_t rq, 
     return t;
 }
 
-__device__ __forceinline__ void filter_level_fast(const FastTaps& t, float hgt[4], float col[3])
+// PACKED: the footprint's twelve codes go through `lut`, the sRGB8 -> linear table in LDS (the context's own, which the float table
+// was decoded with: the same twelve floats), a field of the entry being the byte offset of its float; then the same expressions.
+template <bool PACKED>
+__device__ __forceinline__ void filter_level_fast(const FastTaps& t, const float* __restrict__ lut, float hgt[4], float col[3])
 {
 #define QF(e, fx, fy) ({ const float top_ = __builtin_fmaf(__uint_as_float((e).y), (fx), __uint_as_float((e).x)), \
                                      bot_ = __builtin_fmaf(__uint_as_float((e).w), (fx), __uint_as_float((e).z)); \
@@ -983,14 +993,21 @@ __device__ __forceinline__ void filter_level_fast(const FastTaps& t, float hgt[4
 #undef QF
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const float t00 = __uint_as_float(t.p00[k]), t10 = __uint_as_float(t.p10[k]), t01 = __uint_as_float(t.p01[k]), t11 = __uint_as_float(t.p11[k]);
+        float t00, t10, t01, t11;
+        if (PACKED) {
+#define LUT(w_) (*reinterpret_cast<const float*>(reinterpret_cast<const char*>(lut) + vr_packed_lut_offset((w_), k)))
+            t00 = LUT(t.p00.x); t10 = LUT(t.p00.y); t01 = LUT(t.p00.z); t11 = LUT(t.p00.w);
+#undef LUT
+        } else { t00 = __uint_as_float(t.p00[k]); t10 = __uint_as_float(t.p10[k]); t01 = __uint_as_float(t.p01[k]); t11 = __uint_as_float(t.p11[k]); }
         const float top = __builtin_fmaf(t10 - t00, t.fx0, t00), bot = __builtin_fmaf(t11 - t01, t.fx0, t01);
         col[k] = __builtin_fmaf(bot - top, t.fy0, top);
     }
 }
 
+template <bool PACKED>
 __device__ __forceinline__ void pixel_shader_fast(const RasterArgs& a, __amdgpu_buffer_rsrc_t rq, __amdgpu_buffer_rsrc_t rc,
-                                                  const float* __restrict__ thr, const uint8_t* __restrict__ enc, const uint4* __restrict__ s_lv, const Attr& p,
+                                                  const float* __restrict__ thr, const uint8_t* __restrict__ enc, const uint4* __restrict__ s_lv,
+                                                  const float* __restrict__ s_lut, const Attr& p,
                                                   uint32_t& diffuse, uint32_t& n01, uint32_t& n23 VR_PROF_PARAM)
 {
     const float half_ws = a.world_size * 0.5f, iws = a.inv_world_size;
@@ -1004,11 +1021,11 @@ __device__ __forceinline__ void pixel_shader_fast(const RasterArgs& a, __amdgpu_
     const float ua = u + offset, ub = u + (-offset), va = v + offset, vb = v + (-offset);
     float hgt[4], col[3];
     {
-        const FastTaps t0 = issue_level_fast(rq, rc, s_lv, l16, ua, ub, va, vb, u, v);
+        const FastTaps t0 = issue_level_fast<PACKED>(rq, rc, s_lv, l16, ua, ub, va, vb, u, v);
         VR_PROF_MARK(10);
         VR_PROF_DRAIN;
         VR_PROF_MARK(11);
-        filter_level_fast(t0, hgt, col);
+        filter_level_fast<PACKED>(t0, s_lut, hgt, col);
         VR_PROF_MARK(12);
     }
     // Wave-uniform branch (ballot): where every pixel of the wave is magnified (LOD 0 - the near half of an 8K frame)
@@ -1019,8 +1036,8 @@ __device__ __forceinline__ void pixel_shader_fast(const RasterArgs& a, __amdgpu_
         float xa = ua, xb = ub, ya = va, yb = vb, x0 = u, y0 = v;
         asm volatile("" : "+v"(xa), "+v"(xb), "+v"(ya), "+v"(yb), "+v"(x0), "+v"(y0));
         float g[4], cb[3];
-        const FastTaps t1 = issue_level_fast(rq, rc, s_lv, l16b, xa, xb, ya, yb, x0, y0);
-        filter_level_fast(t1, g, cb);
+        const FastTaps t1 = issue_level_fast<PACKED>(rq, rc, s_lv, l16b, xa, xb, ya, yb, x0, y0);
+        filter_level_fast<PACKED>(t1, s_lut, g, cb);
         // fma(b - a, f, a): with f == 0 this is a exactly (b - a is finite), as the oracle's "f > 0" branch leaves it
 #pragma unroll
         for (int k = 0; k < 4; k++) hgt[k] = __builtin_fmaf(g[k] - hgt[k], frac, hgt[k]);
@@ -1218,6 +1235,7 @@ enum { RM_GENERIC = 0, RM_FAST = 1, RM_DEPTH = 2 };
 struct LitArgs {
     DeferredArgs da;                   // the lighting pass's constants
     const float* lut_g;                // sRGB8 -> linear (256 floats)
+    const uint4* al_pack;              // the albedo's packed footprint table (vr_packed.h; TexLayout::pack_at): the fused flavours' albedo source
     uint2* hdr;                        // HdrColor, row-major RGBA16F - or, with a partition, this rank's packed RGB16F tiles
     const int32_t* tile_slot;          // partition: owner tile -> rank * max_owned + local index (NULL: whole frame, row-major)
     int slot_base, owner_tiles_x;
@@ -1497,7 +1515,10 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? (TILE == 
     const bool depth_only = DEPTH || (!FAST && a.depth_only != 0);
     const __amdgpu_buffer_rsrc_t rq = FAST ? __builtin_amdgcn_make_buffer_rsrc((void*)hm.fast, (short)0, (int)hm.fast_bytes, 0x00020000)
                                            : __builtin_amdgcn_make_buffer_rsrc((void*)hm.quadf, (short)0, (int)(hm.quad_bytes * 4u), 0x00020000);
-    __amdgpu_buffer_rsrc_t rc = FAST ? __builtin_amdgcn_make_buffer_rsrc((void*)al.fast, (short)0, (int)al.fast_bytes, 0x00020000)
+    // (the fused flavours read the packed footprints: entry for entry the float table's layout, fast_bytes long)
+    const void* al_fast = al.fast;
+    if constexpr (LIT) al_fast = lit.al_pack;
+    __amdgpu_buffer_rsrc_t rc = FAST ? __builtin_amdgcn_make_buffer_rsrc((void*)al_fast, (short)0, (int)al.fast_bytes, 0x00020000)
                                      : __builtin_amdgcn_make_buffer_rsrc((void*)al.rgbf, (short)0, (int)(al.chain_bytes * 4u), 0x00020000);
     // fused flavours: the descriptor stays formed.  Its fourth dword is the same constant as rq's; seeing that, the compiler kept one
     // copy, and under the resolve's scalar register pressure restored rc from spill lanes, replaced that dword and wrote rc back in
@@ -1686,7 +1707,7 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? (TILE == 
                     p.dwxdy = __builtin_fmaf(-p.wx, qy, nxy) * r; p.dwzdy = __builtin_fmaf(-p.wz, qy, nzy) * r;
                 }
                 VR_PROF_MARK(9);
-                if (FAST) pixel_shader_fast(a, rq, rc, thr, enc, s_lv, p, dif, nn0, nn1 VR_PROF_ARG);
+                if (FAST) pixel_shader_fast<LIT>(a, rq, rc, thr, enc, s_lv, s_lut, p, dif, nn0, nn1 VR_PROF_ARG);
                 else pixel_shader<false, false>(a, hm, al, rq, rc, thr, enc, s_qoff, s_aoff, p, dif, nn0, nn1);
             }
             if constexpr (LIT) {
@@ -2058,6 +2079,7 @@ static int terrain_render_impl(vr_terrain* t, const vr_view* view, vr_gbuffer* g
         if (lit && plan.fast && !plan.ranges) VR_REQUIRE(in.viewport_full, "view viewport must cover the G-buffer");
         if (plan.fuse) {
             la.lut_g = ctx->d_srgb_lut; la.hdr = (uint2*)lit_req->hdr->data;
+            la.al_pack = (const uint4*)(t->albedo.base + t->albedo_layout.pack_at);
             // whoever still reads the image this pass overwrites (vr_frame_submit: the tone-map stage of two frames ago, on another stream)
             if (plan.keep) { if ((rc = order_image_writer_begins(lit_req->hdr->ord, ops, s))) return rc; }
             else if (pt) {

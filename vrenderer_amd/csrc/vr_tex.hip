@@ -50,6 +50,7 @@ int vr_tex_upload_and_mip(vr_context* ctx, const uint8_t* host, int w, int h, in
     if (tb == 4) { lay.rgbf_at = total = align256(total); total += chain_bytes / 4 * 16; }   // a float4 per dword of the chain
     const size_t fastlv_off = total = align256(total); total += sizeof(fast_lv);
     lay.fast_at = total = align256(total); total += fast_bytes;
+    if (tb == 4) { lay.pack_at = total = align256(total); total += fast_bytes; }    // the packed footprints (vr_packed.h): entry for entry like fast
     // every table is read through its own buffer resource with 32-bit byte offsets: each must stay below 2 GB
     VR_REQUIRE(quad_dwords * sizeof(float4) < ((size_t)1 << 31) && chain_bytes * 4 < ((size_t)1 << 31) && fast_bytes < ((size_t)1 << 31),
                "texture too large");

@@ -572,6 +572,18 @@ class TerrainPass:
             res.append(lv)
         return res
 
+    def PackedTables(self):
+        """vr_debug_terrain_tables, VR_DEBUG_TABLE_PACK (test helper): the albedo's packed footprint table - what the fused tile
+        pass reads instead of 'fast' - as it is on the device: one uint32 array (h + 3, w + 3, 4) per mip level, a dword per texel of
+        the footprint (ix-1, iy-1) (ix, iy-1) (ix-1, iy) (ix, iy), each r << 2 | g << 12 | b << 22."""
+        fn, dims, res = self.ctx.lib.vr_debug_terrain_tables, (C.c_int32 * 2)(), []
+        for level in range(self.mip_levels("albedo")):
+            check(fn(self.handle, 1, capi.VR_DEBUG_TABLE_PACK, level, dims, None, 0), "vr_debug_terrain_tables")
+            out = np.empty((int(dims[1]), int(dims[0]), 4), np.uint32)
+            check(fn(self.handle, 1, capi.VR_DEBUG_TABLE_PACK, level, dims, _vp(out), out.nbytes), "vr_debug_terrain_tables")
+            res.append(out)
+        return res
+
     def Edit(self, which, x, y, texels=None, device_ptr=None, w=None, h=None, pitch=0):
         """vr_terrain_edit: replaces a sub-rectangle of level 0 of the heightmap (which = 'height' / 0) or the albedo ('albedo' / 1)
         at (x, y) in place; afterwards the terrain is the one Init would build from the edited arrays.  With device_ptr=None,
