@@ -116,6 +116,9 @@ typedef struct vr_light {
     float   inner_angle, outer_angle;
     float   out_of_bounds_shadow;
 } vr_light;
+/* Every float field a light's type reads must be finite (directional: direction, color, intensity, angular size,
+ * out_of_bounds_shadow; point: position, color, intensity, 1/range, radius; spot: a point light's and direction, inner_angle,
+ * outer_angle): every entry that takes lights refuses a NaN or an infinity with VR_ERR_INVALID_ARGUMENT and names the field. */
 
 /* G-buffer planes (Donut GBufferRenderTargets formats; 28 B/pixel, row-major):
  *   depth    float32                 (cleared to 1.0)
@@ -731,6 +734,15 @@ VR_API int  vr_image_download(vr_image* img, void* host, size_t bytes);
 VR_API int  vr_image_upload(vr_image* img, const void* host, size_t bytes);
 
 /* ---- deferred lighting --------------------------------------------------------- */
+/* The domain of the lighting entries (vr_deferred_light, _shadowed, _tiled, _tiled_ex, vr_terrain_render_lit, vr_frame_submit):
+ *  - a NaN or an infinity in view->clip_to_world, view->camera_pos, an ambient channel or a light field its type reads is
+ *    refused (VR_ERR_INVALID_ARGUMENT, the field named) before anything is queued: nothing the call touches changes;
+ *  - finite inputs under which a cleared texel (sky) is not guaranteed to shade to +0 - a clip_to_world that sends depth 1 to
+ *    w = 0 (an infinite far plane), a light on the far plane, intensity / color / ambient beyond 2^40, a source radius or a spot
+ *    cone below 2^-20 ... - are accepted by vr_deferred_light[_shadowed] and vr_frame_submit, which then shade EVERY texel
+ *    (no plane-state shortcut, no fused frame: same results, the speed of the plain pass); vr_deferred_light_tiled[_ex] and
+ *    vr_terrain_render_lit, whose kernels give a sky texel +0 unshaded, refuse them with VR_ERR_INVALID_ARGUMENT.
+ * The bounds: vrenderer_amd/csrc/vr_light_domain.h. */
 /* DeferredLightingPass::Render(cmd, view, Inputs{GBuffer, ambientColorTop/Bottom,
  * lights, output}) (Renderer.cpp:417-428).  `part` NULL = whole frame, output
  * row-major; otherwise only owned tiles are shaded and written to `hdr_out` as a
@@ -971,6 +983,13 @@ VR_API int vr_debug_tile_order(vr_terrain* t, int32_t* out_tiles, uint32_t* out_
  * lighting pass - either entry point - left for the 32x32 light tile (tile_x, tile_y).  *out_count = the length of the list; the
  * first min(*out_count, capacity) indices go to `out`.  A pass over a partition writes its own tiles' lists only.  Synchronises. */
 VR_API int vr_debug_tile_light_list(vr_context* ctx, int32_t tile_x, int32_t tile_y, uint32_t* out, int32_t capacity, int32_t* out_count);
+/* Test helpers.  vr_debug_light_domain: what the lighting entries make of a set of inputs, without a context or a device - *refused
+ * and *sky_is_zero as 0 / 1, in `why` the field or the first bound that failed.  vr_debug_light_variant: which instantiation of the
+ * shading kernel (and, of a tiled pass, of the culling kernel) this context's last lighting pass launched, as vr_light_plan.h numbers them; -1: none. */
+VR_API int vr_debug_light_domain(const vr_view* view, int32_t w, int32_t h, const vr_light* lights, int32_t num_lights,
+                                 const float ambient_top[3], const float ambient_bottom[3], int32_t* refused,
+                                 int32_t* sky_is_zero, char* why, int32_t why_capacity);
+VR_API int vr_debug_light_variant(vr_context* ctx, int32_t* shade, int32_t* cull);
 /* Device memory a terrain holds, in bytes: out[0] textures (chains + decoded tables, and the query pyramid once a ray was cast), out[1] per-frame geometry scratch
  * (three rotating sets: instances, vertices, triangle records, bins - sized for params->max_instances) plus the staging
  * memory of host-pointer queries, out[2] node heights (after vr_terrain_update_heights), out[3] the sum. */

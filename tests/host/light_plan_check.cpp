@@ -3,7 +3,11 @@
 //  (a) a flat transcription of the ternaries and launch sites deferred_light and deferred_light_tiled held before the plan
 //      existed (commit 012f361, vrenderer_amd/csrc/vr_deferred.hip; line numbers are that file's), written as that code wrote
 //      them and not as the header structures them - this is the specification;
-//  (b) invariants that hold whatever the transcription says, against a table of what each variant has compiled in.
+//  (b) invariants that hold whatever the transcription says, against a table of what each variant has compiled in;
+//  (c) the rule that is younger than that code, over the same inputs with sky_not_zero set (vr_light_domain.h could not show that
+//      a cleared texel shades to +0): the tiled entry points are refused (light_sky_ok), the streaming pass gets the plan of the
+//      same call with nothing known about the planes - k_deferred_stream or k_deferred_scalar, never k_deferred.  (a) and (b) run
+//      with the flag clear, where the plan is the transcription's.
 // Plain C++17, no GPU: g++ -std=c++17 -Wall -Werror -I vrenderer_amd/csrc tests/host/light_plan_check.cpp
 #include "vr_light_plan.h"
 
@@ -112,8 +116,8 @@ static long failures = 0;
 static void fail(const LightPlanIn& in, const char* what)
 {
     if (failures++ < 20)
-        std::printf("FAIL %s: entry %d packed %d width_mult4 %d shadow %d extra %d cone %d hinted %d ranges_usable %d lights %d %dx%d owned %d\n",
-                    what, (int)in.entry, in.packed, in.width_mult4, in.shadow, in.extra, in.cone, in.hinted, in.ranges_usable, in.num_lights,
+        std::printf("FAIL %s: entry %d packed %d width_mult4 %d shadow %d extra %d cone %d hinted %d ranges_usable %d sky_not_zero %d lights %d %dx%d owned %d\n",
+                    what, (int)in.entry, in.packed, in.width_mult4, in.shadow, in.extra, in.cone, in.hinted, in.ranges_usable, in.sky_not_zero, in.num_lights,
                     in.w, in.h, in.num_owned);
 }
 #define CHECK(cond) do { if (!(cond)) fail(in, #cond); } while (0)
@@ -207,6 +211,37 @@ int main()
                             }
                         }
                     }
+    // (c)
+    long sky_cases = 0, sky_refused = 0;
+    for (int entry = LIGHT_STREAM; entry <= LIGHT_TILED_EX; entry++)
+        for (unsigned bits = 0; bits < (1u << 7); bits++)
+            for (int li = 0; li < 5; li++)
+                for (int owned = 0; owned <= 1; owned++)
+                    for (int si = 0; si < 3; si++) {
+                        LightPlanIn in{};
+                        unsigned b = bits;
+                        auto next = [&b]() { const bool v = b & 1u; b >>= 1; return v; };
+                        in.entry = (LightEntry)entry;
+                        in.packed = next(); in.width_mult4 = next(); in.shadow = next(); in.extra = next(); in.cone = next();
+                        in.hinted = next(); in.ranges_usable = next();
+                        in.num_lights = kLights[li]; in.num_owned = owned;
+                        const int* size = in.width_mult4 ? kSizes4[si] : kSizesOdd[si];
+                        in.w = size[0]; in.h = size[1];
+                        LightPlanIn safe = in;
+                        CHECK(light_sky_ok(safe));
+                        in.sky_not_zero = true;
+                        CHECK(light_width_ok(in) == light_width_ok(safe));
+                        if (!light_width_ok(in)) continue;
+                        sky_cases++;
+                        CHECK(light_sky_ok(in) == (in.entry == LIGHT_STREAM));
+                        if (!light_sky_ok(in)) { sky_refused++; continue; }        // (the plan is asked for accepted calls only)
+                        const LightPlan p = light_plan(in);
+                        safe.hinted = false;
+                        CHECK(same_plan(p, light_plan(safe)));
+                        CHECK((int)p.shade >= 0 && p.shade < LV_COUNT);
+                        if ((int)p.shade >= 0 && p.shade < LV_COUNT) CHECK(kFlags[p.shade].family == F_STREAM || kFlags[p.shade].family == F_SCALAR);
+                    }
+    std::printf("light_plan: outside sky_is_zero: %ld accepted widths (%ld refused: the tiled entry points)\n", sky_cases, sky_refused);
     for (int v = 0; v < LV_COUNT; v++)
         if (!reached[v]) { std::printf("FAIL shading variant %d is never chosen\n", v); failures++; }
     for (int c = 0; c < LC_COUNT; c++)

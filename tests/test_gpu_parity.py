@@ -2321,7 +2321,19 @@ def test_deferred_fuzz_random_gbuffer_and_lights(scene256, oracle, gpu_ctx):
         for k, arr in (("depth", gb.depth), ("diffuse", gb.diffuse), ("specular", gb.specular), ("normals", gb.normals), ("emissive", gb.emissive)):
             rt.upload(k, arr)
         dl.Render(v, rt, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
-        got = oracle.half_to_float(hdr.download()).astype(np.float64)[..., :3]
+        tracked = hdr.download().copy()
+        # the same planes with the plane tracking off (the kernel that shades every texel, cleared rows included): the same bits
+        gpu_ctx.set_plane_tracking(False)
+        try:
+            rt2 = vr.RenderTargets(gpu_ctx).Init(w, h)
+            for k, arr in (("depth", gb.depth), ("diffuse", gb.diffuse), ("specular", gb.specular), ("normals", gb.normals), ("emissive", gb.emissive)):
+                rt2.upload(k, arr)
+            dl.Render(v, rt2, lights, AMBIENT_TOP, AMBIENT_BOTTOM, hdr)
+            rt2.close()
+        finally:
+            gpu_ctx.set_plane_tracking(True)
+        assert np.array_equal(tracked.view(np.uint8), hdr.download().view(np.uint8)), f"trial {trial}: tracked and untracked HdrColor differ"
+        got = oracle.half_to_float(tracked).astype(np.float64)[..., :3]
         ref = oracle.deferred(v, gb, lights, AMBIENT_TOP, AMBIENT_BOTTOM, f32=True).astype(np.float64)[..., :3]
         assert np.isfinite(got).all() and np.isfinite(ref).all(), trial
         # half rounding is 4.9e-4 relative; GGX highlights at low roughness are ill-conditioned in fp32 (dd = NdotH^2 (a2-1) + 1

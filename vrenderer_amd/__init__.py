@@ -9,4 +9,4 @@ from .capi import (Instance, Light, Partition, Ray, RayHit, RenderParams, Shadow
                    VR_LIGHT_DIRECTIONAL, VR_LIGHT_POINT, VR_LIGHT_SPOT, VR_MAX_LODS, VR_OWNER_TILE, load_library)
 from .passes import (CascadedShadowMap, Context, DeferredLightingPass, Frame, HdrImage, LdrImage, Stamp, default_shadow_params, RenderTargets, TerrainPass, TiledDeferredLightingPass,  # noqa: F401
                      ToneMappingPass, default_render_params, default_terrain_params, default_tonemap_params, directional_light, make_view,
-                     RAY_DTYPE, RAY_HIT_DTYPE, light_array, pixel_ray, point_light, reference_sun, spot_light, synth_albedo, synth_heightmap, synthetic_point_lights)
+                     RAY_DTYPE, RAY_HIT_DTYPE, light_array, light_domain, pixel_ray, point_light, reference_sun, spot_light, synth_albedo, synth_heightmap, synthetic_point_lights)

@@ -263,7 +263,7 @@ EXPORTS = [
     "vr_gbuffer_download", "vr_gbuffer_upload", "vr_image_create", "vr_image_destroy",
     "vr_image_device_ptr", "vr_image_download", "vr_image_upload", "vr_ldr_image_create", "vr_ldr_image_destroy", "vr_ldr_image_device_ptr", "vr_ldr_image_capacity", "vr_ldr_image_download", "vr_ldr_image_upload", "vr_deferred_light", "vr_deferred_light_tiled", "vr_deferred_tiled_status", "vr_partition_num_tiles",
     "vr_partition_packed_bytes", "vr_partition_prepare", "vr_frame_detile",
-    "vr_shadow_default_params", "vr_shadow_view_setup", "vr_deferred_light_shadowed", "vr_deferred_light_tiled_ex", "vr_debug_tile_light_list",
+    "vr_shadow_default_params", "vr_shadow_view_setup", "vr_deferred_light_shadowed", "vr_deferred_light_tiled_ex", "vr_debug_tile_light_list", "vr_debug_light_domain", "vr_debug_light_variant",
     "vr_tonemap_default_params", "vr_tonemap_create", "vr_tonemap_destroy", "vr_tonemap_reset_exposure", "vr_tonemap_reset_histogram",
     "vr_tonemap_add_frame_to_histogram", "vr_tonemap_histogram_device_ptr", "vr_tonemap_compute_exposure", "vr_tonemap_render",
     "vr_tonemap_simple_render", "vr_tonemap_download", "vr_partition_packed_bytes_ldr", "vr_frame_detile_ldr", "vr_frame_submit", "vr_frame_allgather", "vr_frame_allgather_tiles", "vr_frame_allgather_ldr", "vr_tonemap_allreduce_histogram", "vr_synth_heightmap", "vr_synth_albedo", "vr_debug_srgb_encode", "vr_debug_fastmath_check", "vr_debug_render_stats", "vr_debug_tile_order", "vr_debug_download_vertices", "vr_terrain_memory_bytes",
@@ -369,6 +369,8 @@ def load_library():
         "vr_deferred_light_tiled_ex": (C.c_int, [vp, P(View), vp, P(Light), C.c_int32, P(C.c_float), P(C.c_float),
                                                  vp, P(Partition), P(ShadowBinding)]),
         "vr_debug_tile_light_list": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int32, P(C.c_int32)]),
+        "vr_debug_light_variant": (C.c_int, [vp, P(C.c_int32), P(C.c_int32)]),
+        "vr_debug_light_domain": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, P(C.c_int32), P(C.c_int32), C.c_char_p, C.c_int32]),
         "vr_tonemap_default_params": (None, [P(TonemapParams)]),
         "vr_tonemap_create": (C.c_int, [vp, P(vp)]),
         "vr_tonemap_destroy": (None, [vp]),

@@ -19,6 +19,7 @@
 #include "vr_tex_dev.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include "vr_deferred_dev.h"
@@ -180,8 +181,8 @@ __global__ __launch_bounds__(256, VR_DEFERRED_WAVES) void k_deferred(DeferredArg
     // shade: with albedo, F0, occlusion, the normal and the emissive term all zero every product of the model below is a
     // (finite) factor times zero - the radiance is +0 in every channel, which is what the loop would store.  (Wave-uniform.)
     // "Finite" is the one assumption: a light with non-finite parameters, or a clip-to-world matrix that sends the far plane to
-    // w = 0, would make the loop produce NaN for such a texel where this stores 0 - inputs this path does not see (the host
-    // builds both from a camera and a light list it has validated).
+    // w = 0, would make the loop produce NaN for such a texel where this stores 0 - inputs this path does not see
+    // (vr_light_domain.h: non-finite values are refused, and outside sky_is_zero the plan launches k_deferred_stream instead).
     {
         const uint32_t any = (dzu.x ^ 0x3f800000u) | (dzu.y ^ 0x3f800000u) | (dzu.z ^ 0x3f800000u) | (dzu.w ^ 0x3f800000u)
                            | df.x | df.y | df.z | df.w | sp.x | sp.y | sp.z | sp.w | n0.x | n0.y | n0.z | n0.w | n1.x | n1.y | n1.z | n1.w
@@ -754,6 +755,7 @@ static int deferred_light(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, LightC
         const int32_t* owned = c.pt ? c.pt->d_owned_tiles : nullptr;
         VrKernelScope ks(ctx, VR_K_DEFERRED, ctx->stream, true);
 #define VR_LIGHT_ARGS c.a, gb->depth, gb->diffuse, gb->specular, gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut
+        ctx->last_light_variant = (int)plan.shade;
         if (plan.shade == LV_SCALAR) ks.launch(k_deferred_scalar, dim3(plan.shade_grid), dim3(256), VR_LIGHT_ARGS, c.sh, c.in.shadow ? 1 : 0);
         else if (plan.shade < LV_HINTED_ROW) ks.launch(kStreamKernels[plan.shade - LV_STREAM_ROW], dim3(plan.shade_grid), dim3(256), VR_LIGHT_ARGS, owned, c.sh);
         else ks.launch(kHintedKernels[plan.shade - LV_HINTED_ROW], dim3(plan.shade_grid), dim3(256), VR_LIGHT_ARGS, owned, c.sh, hints);
@@ -804,6 +806,7 @@ static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, 
           hipLaunchKernelGGL(kCullKernels[plan.cull], dim3(plan.cull_grid), dim3(256), 0, ctx->stream, c.a, ctx->d_lights, c.in.num_lights, gb->depth, (const uint2*)gb->normals,
                              plan.macro_x, owned, ctx->d_light_lists, plan.list_stride, plan.tiles32_x, plan.tiles32_y, ctx->d_flags, ctx->d_macro_scratch, gb->d_ranges); }
         VrKernelScope ks(ctx, VR_K_DEFERRED_TILED, ctx->stream, true);
+        ctx->last_light_variant = (int)plan.shade; ctx->last_light_cull = (int)plan.cull;
         ks.launch(kTiledKernels[plan.shade - LV_TILED_ROW], dim3(plan.shade_grid), dim3(256), c.a, ctx->d_lights, gb->depth, gb->diffuse, gb->specular,
                         gb->normals, gb->emissive, (uint2*)hdr->data, ctx->d_srgb_lut, owned, ctx->d_light_lists, plan.list_stride, plan.tiles32_x, hints, c.sh);
         *stop = ks.stop();
@@ -819,6 +822,32 @@ static int deferred_light_tiled(vr_context* ctx, vr_gbuffer* gb, vr_image* hdr, 
 // continue: the device, the shadow map and the G-buffer made real, the tiled pass's buffers and its light upload, the depth
 // ranges consumed, the launches.  A refused call leaves no trace.  The entry points call the halves back to back;
 // vr_frame_submit checks in front of its tile pass and queues behind it.
+// The refusal half of vr_light_domain.h, the same from every entry that takes lights or a view for shading; *dom: the whole answer.
+static_assert(kDomDirectional == VR_LIGHT_DIRECTIONAL && kDomSpot == VR_LIGHT_SPOT && kDomPoint == VR_LIGHT_POINT, "vr_light_domain.h");
+int vr_light_domain_check(const vr_view* view, int w, int h, const vr_light* lights, int32_t num_lights, const float amb_top[3],
+                          const float amb_bottom[3], LightDomain* dom)
+{
+    *dom = light_domain(view->clip_to_world, view->camera_pos, w, h, amb_top, amb_bottom, lights, num_lights);
+    if (dom->refuse) {
+        if (dom->light >= 0) vr_set_error("%s:%d: lights[%d]: %s is NaN or infinite", __FILE__, __LINE__, dom->light, dom->field);
+        else vr_set_error("%s:%d: %s holds a NaN or an infinity", __FILE__, __LINE__, dom->field);
+        return VR_ERR_INVALID_ARGUMENT;
+    }
+    return VR_OK;
+}
+
+// Test helper: the whole answer, without a context or a device.  *refused and
+// *sky_is_zero as 0 / 1; why: the field or the first bound that failed ("" where neither applies), NUL-terminated within why_capacity.
+extern "C" VR_API int vr_debug_light_domain(const vr_view* view, int32_t w, int32_t h, const vr_light* lights, int32_t num_lights, const float amb_top[3],
+                                             const float amb_bottom[3], int32_t* refused, int32_t* sky_is_zero, char* why, int32_t why_capacity)
+{
+    VR_REQUIRE(view && amb_top && amb_bottom && refused && sky_is_zero && num_lights >= 0 && (num_lights == 0 || lights) && (why_capacity <= 0 || why), "NULL argument");
+    const LightDomain d = light_domain(view->clip_to_world, view->camera_pos, w, h, amb_top, amb_bottom, lights, num_lights);
+    *refused = d.refuse ? 1 : 0; *sky_is_zero = d.sky_is_zero ? 1 : 0;
+    if (why_capacity > 0) snprintf(why, (size_t)why_capacity, "%s", d.why ? d.why : "");
+    return VR_OK;
+}
+
 int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
                    const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part, const vr_shadow_binding* shadow, LightCall* call)
 {
@@ -837,6 +866,10 @@ int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gb
         VR_REQUIRE(shadow->shadow_map->ctx->device == ctx->device, "shadow map lives on another device");
     }
     VR_REQUIRE(view->viewport_w == gb->w && view->viewport_h == gb->h && view->viewport_x == 0 && view->viewport_y == 0, "view viewport must cover the G-buffer");
+    // the model's domain (vr_light_domain.h): no NaN and no infinity reaches a kernel; whether the kernels that do not shade a
+    // cleared texel may run is the plan's to decide, except that the tiled pass has no other kernel
+    LightDomain dom;
+    { const int rc = vr_light_domain_check(view, gb->w, gb->h, lights, num_lights, amb_top, amb_bottom, &dom); if (rc) return rc; }
     LightCall& c = *call;
     c = LightCall{};
     LightPlanIn& in = c.in;       // extra: spot or spherical lights in the list; cone (LIGHT_TILED_EX): spot lights whose cone is culled
@@ -860,6 +893,12 @@ int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gb
     in.width_mult4 = gb->w % 4 == 0; in.shadow = shadow != nullptr; in.num_lights = num_lights; in.w = gb->w; in.h = gb->h;
     VR_REQUIRE(light_width_ok(in), tiled ? "the tiled pass needs a frame width that is a multiple of 4" : "partitioned frames need a width that is a multiple of 4");
     if (in.packed) c.a.tiles_x = (gb->w + VR_OWNER_TILE - 1) / VR_OWNER_TILE;
+    in.sky_not_zero = !dom.sky_is_zero;
+    if (!light_sky_ok(in)) {
+        vr_set_error("%s:%d: a cleared texel is not guaranteed to shade to +0 (%s, light %d) and the tiled pass gives it no light: use vr_deferred_light",
+                     __FILE__, __LINE__, dom.why, dom.light);
+        return VR_ERR_INVALID_ARGUMENT;
+    }
     if (shadow) {                                             // the kernels' constants (the map itself: vr_light_queue)
         ShadowArgs& sh = c.sh;
         for (int i = 0; i < 16; i++) sh.w2c[i] = shadow->light_view->world_to_clip[i];
@@ -925,6 +964,14 @@ extern "C" VR_API int vr_debug_tile_light_list(vr_context* ctx, int32_t tile_x, 
     *out_count = (int32_t)n;
     const uint32_t m = n < (uint32_t)capacity ? n : (uint32_t)capacity;
     if (m) VR_HIP(hipMemcpy(out, list + 1, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return VR_OK;
+}
+
+// Test helper: the LightVariant (and, of a tiled pass, the LightCull) of vr_light_plan.h that this context's last lighting pass launched; -1: none.
+extern "C" VR_API int vr_debug_light_variant(vr_context* ctx, int32_t* shade, int32_t* cull)
+{
+    VR_REQUIRE(ctx && shade && cull, "NULL argument");
+    *shade = ctx->last_light_variant; *cull = ctx->last_light_cull;
     return VR_OK;
 }
 

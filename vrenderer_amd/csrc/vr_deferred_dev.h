@@ -258,6 +258,8 @@ struct ShadowArgs {
 // A lighting pass between its two halves (vr_deferred.hip): vr_light_check fills it behind every refusal - the call's facts for
 // the plan, the kernels' constants - and vr_light_queue adds what only exists then: the rank's tables, the shadow map's plane.
 struct LightCall { LightPlanIn in; DeferredArgs a; ShadowArgs sh; const PartTables* pt; };
+int vr_light_domain_check(const vr_view* view, int w, int h, const vr_light* lights, int32_t num_lights, const float amb_top[3],
+                          const float amb_bottom[3], LightDomain* dom);                            // (vr_deferred.hip; vr_light_domain.h)
 int vr_light_check(vr_context* ctx, LightEntry entry, const vr_view* view, vr_gbuffer* gb, const vr_light* lights, int32_t num_lights,
                    const float amb_top[3], const float amb_bottom[3], vr_image* hdr, const vr_partition* part,
                    const vr_shadow_binding* shadow, LightCall* call);

@@ -40,11 +40,13 @@ extern "C" VR_API int vr_frame_submit(vr_terrain* t, vr_gbuffer* gb, const vr_fr
     // Under VR_OPT_FRAME_FUSION the tile pass shades as well where its G-buffer-keeping flavour applies (the plain streaming
     // lighting pass of a whole frame; everything else is decided in vr_terrain_render_keep, in front of the launch): the frame is
     // then one kernel, and what the G-buffer, its plane states and HdrColor hold afterwards is what the two passes leave.
+    // Outside sky_is_zero (vr_light_domain.h) nothing fuses: the resolve would store +0 for a sky pixel that the model does not
+    // shade to +0 there, so the frame is the unfused pair, whose lighting pass is then k_deferred_stream (vr_light_plan.h).
     bool fused = false;
     VrEventRef fused_stop;
     int earlier;
     if (ctx->frame_fusion && !f->tiled && !f->shadow && !f->part)
-        earlier = vr_terrain_render_keep(t, f->view, gb, f->render, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, &fused, &fused_stop);
+        earlier = vr_terrain_render_keep(t, f->view, gb, f->render, f->lights, f->num_lights, f->ambient_top, f->ambient_bottom, hdr, !lc.in.sky_not_zero, &fused, &fused_stop);
     else earlier = vr_terrain_render(t, f->view, f->view, gb, f->render, f->part);
     if (earlier != VR_OK && earlier != VR_ERR_TOO_MANY_INSTANCES && earlier != VR_ERR_OVERFLOW) return earlier;
     for (int k = 0; k < 2; k++)

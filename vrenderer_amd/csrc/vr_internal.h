@@ -17,6 +17,7 @@
 #include "vr_geosets.h"
 #include "vr_history.h"
 #include "vr_light_plan.h"
+#include "vr_light_domain.h"
 #include "vr_order.h"
 #include "vr_scratch.h"
 #include "vr_tonemap_plan.h"
@@ -225,6 +226,7 @@ struct vr_context {
     uint32_t* d_macro_scratch = nullptr; size_t macro_scratch_bytes = 0;   // per macro tile: lights touching its box (k_light_cull's first stage)
     uint32_t* d_light_lists = nullptr; size_t light_list_bytes = 0;    // per 32x32 light tile: count + light indices (k_light_cull)
     uint32_t* d_flags = nullptr;
+    int last_light_variant = -1, last_light_cull = -1;          // what the last lighting pass launched (vr_debug_light_variant)
     int list_stride = 0, list_tiles_x = 0, list_tiles_y = 0;   // layout of d_light_lists as the last tiled pass left it (vr_debug_tile_light_list)
 };
 
@@ -461,10 +463,10 @@ int vr_select_launch(vr_terrain* t, GeoSet& g, const vr_view* view, float max_he
 int vr_terrain_frame_scratch(vr_terrain* t, bool report, const std::function<int(size_t* tiles)>& target, int* earlier, uint32_t* bin_capacity);
 // vr_frame_submit's tile pass under VR_OPT_FRAME_FUSION (vr_raster.hip): vr_terrain_render of the whole frame that also shades
 // into hdr_out where the G-buffer-keeping fused flavour applies (*fused; *fused_stop = that launch's dispatch-stamped stop event
-// or NULL) and is exactly vr_terrain_render where it does not
+// or NULL) and is exactly vr_terrain_render where it does not - as wherever sky_is_zero (vr_light_domain.h, from vr_light_check) is false
 int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
                            int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
-                           bool* fused, VrEventRef* fused_stop);
+                           bool sky_is_zero, bool* fused, VrEventRef* fused_stop);
 // the lighting passes as vr_frame_submit queues them: vr_light_check, vr_light_queue (vr_deferred_dev.h)
 // The tone-map stage (vr_tonemap.hip): the steps of `steps` (TmStep, vr_tonemap_plan.h) in their order - reset, histogram, all-reduce
 // over `comm`, exposure, render - behind every refusal of every one of them; queue = false: the refusals alone.  `frame`:

@@ -4,7 +4,8 @@
 // the facts behind its refusals; deferred_light and deferred_light_tiled ask light_plan() and launch what it names.
 //
 // The streaming pass: k_deferred, which asks first what it need not read, where the plane-state tracking knows something (hinted),
-// else the pure stream k_deferred_stream (the question costs that case 10 us: 221 vs 210 us at 8K).  A shadow binding compiles in
+// else the pure stream k_deferred_stream (the question costs that case 10 us: 221 vs 210 us at 8K) - also where the call's inputs are
+// outside sky_is_zero (vr_light_domain.h): k_deferred stores +0 for a cleared texel without shading it.  A shadow binding compiles in
 // EXTRA as well: shade_pixel<EXTRA, SHADOW> exists as <false, false>, <true, false>, <true, true>.  A width that is no multiple
 // of 4 runs k_deferred_scalar, whole frames only: every light type compiled in, the shadow term a run-time argument.
 // The tiled pass: EXTRA and SHADOW are independent (a shadowed sun over plain point lights stages no TiledExtra); CONE only where
@@ -43,6 +44,7 @@ struct LightPlanIn {
     bool extra, cone;              // a spot or spherical light is in the list; a spot light has cone_cos > 0 (cone_cull_terms)
     bool hinted;                   // PlaneHints: a region array, or the emissive plane known zero (the streaming pass's question)
     bool ranges_usable;            // the G-buffer's depth ranges are VALID for this split
+    bool sky_not_zero;             // vr_light_domain.h: sky_is_zero could NOT be shown - a cleared texel may shade to something but +0 (false: every shortcut holds)
     int num_lights, w, h, num_owned;       // (num_owned: owner tiles of this rank, packed)
 };
 struct LightPlan {
@@ -59,6 +61,12 @@ struct LightPlan {
 // whole-frame streaming pass has a kernel for anything else.  light_plan() is asked for accepted widths only.
 inline bool light_width_ok(const LightPlanIn& in) { return in.width_mult4 || (in.entry == LIGHT_STREAM && !in.packed); }
 
+// Outside sky_is_zero only a kernel that shades every texel may run: k_deferred_stream and k_deferred_scalar.  k_deferred stores +0
+// for a wave of cleared texels and k_deferred_tiled gives its background pixels no light, whatever the host knows - so the
+// streaming pass drops the question (hinted) and the tiled entry points, which have no such kernel (and take up to 65536 lights
+// where the streaming pass takes 16), refuse.  light_plan() is asked for accepted calls only.
+inline bool light_sky_ok(const LightPlanIn& in) { return !in.sky_not_zero || in.entry == LIGHT_STREAM; }
+
 inline LightPlan light_plan(const LightPlanIn& in)
 {
     LightPlan p{};
@@ -70,7 +78,7 @@ inline LightPlan light_plan(const LightPlanIn& in)
     if (in.entry == LIGHT_STREAM) {
         // packed: a block = 8 rows of an owner tile; row-major: 256 quads, or 256 pixels of the scalar kernel
         p.shade_grid = in.packed ? (unsigned)in.num_owned * 16u : (unsigned)(((in.width_mult4 ? npx / 4 : npx) + 255) / 256);
-        p.shade = !in.width_mult4 ? LV_SCALAR : (LightVariant)((in.hinted ? LV_HINTED_ROW : LV_STREAM_ROW) + (in.packed ? 3 : 0) + (shadow ? 2 : extra ? 1 : 0));
+        p.shade = !in.width_mult4 ? LV_SCALAR : (LightVariant)((in.hinted && !in.sky_not_zero ? LV_HINTED_ROW : LV_STREAM_ROW) + (in.packed ? 3 : 0) + (shadow ? 2 : extra ? 1 : 0));
         return p;
     }
     p.shade = (LightVariant)((in.packed ? LV_TILED_PACKED : LV_TILED_ROW) + (extra ? 1 : 0) + (shadow ? 2 : 0));

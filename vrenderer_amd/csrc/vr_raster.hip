@@ -1714,7 +1714,7 @@ __global__ __launch_bounds__(kRT, (KEEP ? VR_RASTER_WAVES_KEEP : LIT ? (TILE == 
                 // the pixel as the lighting pass would read it back from the G-buffer: the encoded texel (a cleared one where nothing
                 // was drawn), the same decode, the same shading, the same half conversion
                 // (a wave of uncovered pixels - cleared texels - shades to +0 in every channel: vr_deferred.hip, k_deferred; wave-uniform.
-                // The same assumption - finite light and matrix inputs - holds lane by lane: an uncovered pixel of a mixed wave is
+                // The same assumption - sky_is_zero of vr_light_domain.h, without which no pass fuses - holds lane by lane: an uncovered pixel of a mixed wave is
                 // given the +0 the model arrives at on a cleared texel.  Every lane whose shading is kept is then a terrain pixel:
                 // the TERRAIN flavour of the model, the specular word's decode from `known`, vr_terrain_surface.h's roughness.)
                 float lrgb[3] = { 0.0f, 0.0f, 0.0f };
@@ -1964,7 +1964,8 @@ extern "C" VR_API int vr_terrain_prepare(vr_terrain* t, const vr_view* view, vr_
 // leave everything the unfused pair leaves; where it does not apply the call queues exactly the unfused tile pass and reports
 // "not fused".  stop_out: the fused launch's own dispatch-stamped stop event (NULL: the launch was not stamped).
 struct LitRequest { const vr_light* lights; int32_t num_lights; const float* amb_top; const float* amb_bottom; vr_image* hdr;
-                    bool keep; VrEventRef* stop_out; };
+                    bool keep; VrEventRef* stop_out;
+                    bool sky_is_zero; };       // vr_light_domain.h's answer for these inputs (the caller has asked, and refused what it refuses)
 // The facts raster_plan() decides on.  Whether a lit request's light list is the lighting pass's plain case is one of them:
 // the list goes through vr_deferred_make_args here (*la, *lights_rc).
 static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view, const vr_gbuffer* gb, const vr_render_params* rp,
@@ -1998,7 +1999,7 @@ static RasterPlanIn raster_plan_inputs(const vr_terrain* t, const vr_view* view,
             bool extra = false;
             memset(la, 0, sizeof(*la));
             *lights_rc = vr_deferred_make_args(view, gb->w, gb->h, lit_req->lights, lit_req->num_lights, lit_req->amb_top, lit_req->amb_bottom, &la->da, &extra);
-            in.lit_plain = *lights_rc == VR_OK && !extra;
+            in.lit_plain = *lights_rc == VR_OK && !extra && lit_req->sky_is_zero;      // (the resolve gives an uncovered pixel +0 unshaded)
         }
     }
     return in;
@@ -2134,7 +2135,8 @@ extern "C" VR_API int vr_terrain_render(vr_terrain* t, const vr_view* view, cons
 // not written (they keep what they held).  Bit-identical HdrColor and depth to vr_terrain_render(assume_cleared = 1) +
 // vr_deferred_light on the same inputs.  The fused kernel exists for the reference's case (the conditions of the tile pass's
 // fast variant, up to 16 directional / punctual point lights, no shadow term); anything else runs the two passes one after the
-// other inside this call - same result, no saving.
+// other inside this call - same result, no saving - except inputs outside sky_is_zero (vr_light_domain.h), which are refused:
+// the call is a request for the kernel that does not shade sky, and the caller is told to queue the pair.
 extern "C" VR_API int vr_terrain_render_lit(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp,
                                              const vr_partition* part, const vr_light* lights, int32_t num_lights,
                                              const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out)
@@ -2143,10 +2145,24 @@ extern "C" VR_API int vr_terrain_render_lit(vr_terrain* t, const vr_view* view, 
     VR_REQUIRE(rp->assume_cleared && !rp->depth_only && !rp->wireframe && !rp->depth_ranges,
                "vr_terrain_render_lit draws into a cleared target (assume_cleared = 1), shaded fill mode, no depth ranges");
     VR_REQUIRE(num_lights >= 0 && num_lights <= kMaxLights && (num_lights == 0 || lights), "at most 16 lights (terrain_cb.h:15)");
-    const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, false, nullptr };
+    int rc;
+    // the model's domain, in front of every effect: the fused resolve stores +0 for an uncovered pixel without shading it, and
+    // this call is an explicit request for that kernel - outside sky_is_zero it refuses where vr_frame_submit falls back
+    VR_REQUIRE(gb->w > 0 && gb->h > 0, "empty G-buffer");
+    LightDomain dom;
+    if ((rc = vr_light_domain_check(view, gb->w, gb->h, lights, num_lights, ambient_top, ambient_bottom, &dom))) return rc;
+    // (a list the lighting pass refuses for itself - an unknown type, a cone inside out - goes on and is refused where, and with
+    // the words with which, it always was)
+    DeferredArgs probe; bool probe_extra;                     // (on this path only)
+    if (!dom.sky_is_zero && vr_deferred_make_args(view, gb->w, gb->h, lights, num_lights, ambient_top, ambient_bottom, &probe, &probe_extra) == VR_OK) {
+        vr_set_error("%s:%d: a cleared texel is not guaranteed to shade to +0 (%s, light %d) and the fused pass does not shade it: use vr_terrain_render + vr_deferred_light",
+                     __FILE__, __LINE__, dom.why, dom.light);
+        return VR_ERR_INVALID_ARGUMENT;
+    }
+    const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, false, nullptr, dom.sky_is_zero };
     bool fused = false;
     int earlier = VR_OK;
-    int rc = terrain_render_impl(t, view, gb, rp, part, &req, &fused, &earlier, render_mode_of(t->ctx));
+    rc = terrain_render_impl(t, view, gb, rp, part, &req, &fused, &earlier, render_mode_of(t->ctx));
     if (rc) return rc;
     if (!fused && (rc = vr_deferred_light(t->ctx, view, gb, lights, num_lights, ambient_top, ambient_bottom, hdr_out, part))) return rc;     // the unfused pair
     return earlier;
@@ -2177,9 +2193,9 @@ int vr_terrain_materialise_pending(vr_terrain* t) { return t->pending_target ? v
 // queues the lighting pass itself otherwise)
 int vr_terrain_render_keep(vr_terrain* t, const vr_view* view, vr_gbuffer* gb, const vr_render_params* rp, const vr_light* lights,
                            int32_t num_lights, const float ambient_top[3], const float ambient_bottom[3], vr_image* hdr_out,
-                           bool* fused, VrEventRef* fused_stop)
+                           bool sky_is_zero, bool* fused, VrEventRef* fused_stop)
 {
-    const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, true, fused_stop };
+    const LitRequest req = { lights, num_lights, ambient_top, ambient_bottom, hdr_out, true, fused_stop, sky_is_zero };
     int earlier = VR_OK;
     *fused = false; *fused_stop = {};
     const int rc = terrain_render_impl(t, view, gb, rp, nullptr, &req, fused, &earlier, render_mode_of(t->ctx));

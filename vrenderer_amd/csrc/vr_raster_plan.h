@@ -46,7 +46,7 @@ struct RasterPlanIn {
     bool width_mult4;
     RasterRequest request;
     bool lit_inputs_ok;            // KEEP: pointers, light count and device (LIT: its entry point has refused anything else)
-    bool lit_plain;                // vr_deferred_make_args took the light list, without `extra` lights
+    bool lit_plain;                // vr_deferred_make_args took the light list, without `extra` lights, inside sky_is_zero (vr_light_domain.h)
     bool hdr_fits;                 // KEEP: the frame fits the image (LIT: the host refuses an image too small)
     bool lazy_ok;                  // KEEP: the colour planes may stay pending (gbs_lazy_allowed)
 };

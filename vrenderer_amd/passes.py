@@ -78,6 +78,12 @@ class Context:
         """Tile pass / lighting pass launched with dispatch-stamped events that double as cross-stream dependencies (default on)."""
         check(self.lib.vr_context_set_option(self.handle, capi.VR_OPT_DISPATCH_EVENTS, int(enable)), "vr_context_set_option")
 
+    def last_light_variant(self):
+        """(shade, cull): the LightVariant / LightCull of vr_light_plan.h that this context's last lighting pass launched (test helper)."""
+        shade, cull = C.c_int32(), C.c_int32()
+        check(self.lib.vr_debug_light_variant(self.handle, C.byref(shade), C.byref(cull)), "vr_debug_light_variant")
+        return shade.value, cull.value
+
     def timing_enable(self, enable=True):
         """0 / False: off; 1 / True: events around every kernel; 2: only the tile pass and the lighting passes (no host cost)."""
         check(self.lib.vr_timing_enable(self.handle, int(enable)), "vr_timing_enable")
@@ -935,6 +941,15 @@ class Frame:
         rc = self._submit(self.tp.handle, self.rt.handle, C.byref(d))
         if rc:
             check(rc, "vr_frame_submit")
+
+
+def light_domain(view, width, height, lights, ambient_top, ambient_bottom):
+    """vr_debug_light_domain: dict(refused, sky_is_zero, why) - what every lighting entry point will make of these inputs (test helper; no device)."""
+    refused, sky = C.c_int32(), C.c_int32()
+    why = C.create_string_buffer(160)
+    check(capi.load_library().vr_debug_light_domain(C.byref(view), width, height, light_array(lights), len(lights), _f3(ambient_top), _f3(ambient_bottom),
+                                                    C.byref(refused), C.byref(sky), why, len(why)), "vr_debug_light_domain")
+    return dict(refused=bool(refused.value), sky_is_zero=bool(sky.value), why=why.value.decode())
 
 
 def light_array(lights):
