@@ -1,22 +1,14 @@
-// vr_terrain_brush: a stroke - an ordered list of dabs - applied to level 0 of a map on the device by one kernel, followed by the
-// refresh vr_terrain_edit does (vr_derive_level0_write).  The definition of a stroke, texel by texel, is vr_brush.h; this file
-// holds nothing of it but the order in which the header's functions are called.
+// vr_terrain_brush: a stroke - an ordered list of dabs - applied to level 0 of a map on the device by one kernel, through
+// vr_brush_call (vr_level0.h).  The definition of a stroke, texel by texel, is vr_brush.h; this file holds nothing of it but the
+// order in which the header's functions are called.
 //
 //   k_brush_snapshot   SMOOTH only: the stroke's rectangle grown by one texel (clamped) out of the map, so that the 3 x 3 means
 //                      are those of the map before the stroke whatever order the tiles run in
-//   k_brush<op>        one 256-thread workgroup per 32 x 8 tile of the stroke's rectangle, one texel per lane.  The dab list is
-//                      walked in chunks of 256: lane d tests dab d's span against the tile, the survivors are compacted IN LIST
-//                      ORDER into an LDS index list (ballot + popcount prefix inside a wave, the four waves' totals through LDS),
-//                      then every lane applies the listed dabs in order.  A texel no dab covers is not written.  (The chunk walk
-//                      is vr_brush_dev.h's, shared with vr_erode.hip's mask kernel.)
+//   k_brush<op>        the tile frame and the chunk walk of vr_brush_dev.h; every lane applies the chunk's listed dabs in list
+//                      order.  A texel no dab covers is not written.
 //
 // The kernel is untimed, like the mip and table kernels; the node-height and pyramid work counts where the edit's does.
-#include "vr_internal.h"
-#include "vr_dirty.h"
-#include "vr_brush.h"
-#include "vr_brush_dev.h"
-
-#include <string.h>
+#include "vr_level0.h"
 
 struct BrushArgs {
     float target;               // FLATTEN
@@ -24,9 +16,9 @@ struct BrushArgs {
     uint32_t channel_mask;      // PAINT
 };
 
-__global__ __launch_bounds__(256) void k_brush_snapshot(const uint8_t* __restrict__ map, int w0, uint8_t* __restrict__ snap, DirtyRect sr)
+__global__ __launch_bounds__(kBrushThreads) void k_brush_snapshot(const uint8_t* __restrict__ map, int w0, uint8_t* __restrict__ snap, DirtyRect sr)
 {
-    const int x = sr.x0 + blockIdx.x * 32 + (threadIdx.x & 31), y = sr.y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x = brush_tile_x(sr.x0) + brush_lane_x(), y = brush_tile_y(sr.y0) + brush_lane_y();
     if (x >= sr.x1 || y >= sr.y1) return;
     snap[(size_t)(y - sr.y0) * (size_t)(sr.x1 - sr.x0) + (size_t)(x - sr.x0)] = map[(size_t)y * w0 + x];
 }
@@ -34,20 +26,15 @@ __global__ __launch_bounds__(256) void k_brush_snapshot(const uint8_t* __restric
 // `map`: level 0 (R8: bytes, SRGBA8: dwords), w0 x h0; `r`: the stroke's rectangle, inside the map; `dabs`: n of them, none empty;
 // `snap`: SMOOTH's snapshot of the rectangle `sr`
 template <int OP>
-__global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, int h0, DirtyRect r, const BrushDab* __restrict__ dabs, uint32_t n,
-                                               BrushArgs a, const uint8_t* __restrict__ snap, DirtyRect sr)
+__global__ __launch_bounds__(kBrushThreads) void k_brush(void* __restrict__ map, int w0, int h0, DirtyRect r, const BrushDab* __restrict__ dabs, uint32_t n,
+                                                         BrushArgs a, const uint8_t* __restrict__ snap, DirtyRect sr)
 {
     constexpr int NC = OP == kBrushPaint ? 4 : 1;
     __shared__ uint16_t list[kBrushChunk];  // the chunk's dabs that meet this tile, in list order
     __shared__ uint32_t wave_total[4];
-    const int tid = (int)threadIdx.x;
-    const int tx0 = r.x0 + (int)blockIdx.x * 32, ty0 = r.y0 + (int)blockIdx.y * 8;
-    const int tx1 = tx0 + 32 < r.x1 ? tx0 + 32 : r.x1, ty1 = ty0 + 8 < r.y1 ? ty0 + 8 : r.y1;
-    const int x = tx0 + (tid & 31), y = ty0 + (tid >> 5);
-    const bool inside = x < tx1 && y < ty1;
-    // every lane stays to the end (the ballots and barriers below want whole waves); one outside the rectangle works on the
-    // clamped texel and writes nothing
-    const size_t at = (size_t)brush_clampi(y, 0, h0 - 1) * (size_t)w0 + (size_t)brush_clampi(x, 0, w0 - 1);
+    const BrushTile tile = brush_tile(r);
+    const int x = tile.x, y = tile.y;
+    const size_t at = (size_t)tile.cy(h0) * (size_t)w0 + (size_t)tile.cx(w0);
     float val[NC];
     uint32_t stored;
     if (OP == kBrushPaint) {
@@ -72,12 +59,12 @@ __global__ __launch_bounds__(256) void k_brush(void* __restrict__ map, int w0, i
         mean = brush_mean9(sum);
     }
     bool touched = false;
-    for (uint32_t base = 0; base < n; base += 256) {               // (n is a kernel argument: the trip count is uniform)
-        const uint32_t total = brush_chunk_list(dabs, n, base, tx0, ty0, tx1, ty1, list, wave_total);
+    for (uint32_t base = 0; base < n; base += kBrushChunk) {       // (n is a kernel argument: the trip count is uniform)
+        const uint32_t total = brush_chunk_list(dabs, n, base, tile, list, wave_total);
         for (uint32_t e = 0; e < total; e++) {
             const BrushDab b = dabs[brush_chunk_entry(list, e, n)];
             float f;
-            if (inside && brush_weight(b, x, y, &f)) {
+            if (tile.inside && brush_weight(b, x, y, &f)) {
                 touched = true;
                 if (OP == kBrushRaise) val[0] = brush_raise(val[0], f, b.strength);
                 else if (OP == kBrushFlatten) val[0] = brush_blend(val[0], f, b.strength, a.target);
@@ -196,7 +183,7 @@ extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* str
         for (int c = 0; c < 4; c++) VR_REQUIRE(stroke->color[c] >= 0.0f && stroke->color[c] <= 255.0f, "color outside [0, 255]");
     }
     const int which = op == VR_BRUSH_PAINT ? 1 : 0;
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, which);
     BrushArgs a; memset(&a, 0, sizeof(a));
     a.target = stroke->target; a.channel_mask = stroke->channel_mask;
     for (int c = 0; c < 4; c++) a.color[c] = stroke->color[c];
@@ -210,14 +197,14 @@ extern "C" VR_API int vr_terrain_brush(vr_terrain* t, const vr_brush_stroke* str
         [&](hipStream_t s, const DirtyRect& dirty, uint32_t nd) -> int {
             void* mem = const_cast<uint8_t*>(tex.base);
             const uint8_t* snap = (const uint8_t*)t->d_brush_snap;
-            const dim3 grid = tiles_32x8(dirty);
+            const dim3 grid = tiles_32x8(dirty), block(kBrushThreads);
             switch (op) {
-            case VR_BRUSH_RAISE: hipLaunchKernelGGL(k_brush<kBrushRaise>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
-            case VR_BRUSH_FLATTEN: hipLaunchKernelGGL(k_brush<kBrushFlatten>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+            case VR_BRUSH_RAISE: hipLaunchKernelGGL(k_brush<kBrushRaise>, grid, block, 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+            case VR_BRUSH_FLATTEN: hipLaunchKernelGGL(k_brush<kBrushFlatten>, grid, block, 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
             case VR_BRUSH_SMOOTH:
-                hipLaunchKernelGGL(k_brush_snapshot, tiles_32x8(sr), dim3(256), 0, s, (const uint8_t*)mem, tex.w0, (uint8_t*)t->d_brush_snap, sr);
-                hipLaunchKernelGGL(k_brush<kBrushSmooth>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
-            default: hipLaunchKernelGGL(k_brush<kBrushPaint>, grid, dim3(256), 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+                hipLaunchKernelGGL(k_brush_snapshot, tiles_32x8(sr), block, 0, s, (const uint8_t*)mem, tex.w0, (uint8_t*)t->d_brush_snap, sr);
+                hipLaunchKernelGGL(k_brush<kBrushSmooth>, grid, block, 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
+            default: hipLaunchKernelGGL(k_brush<kBrushPaint>, grid, block, 0, s, mem, tex.w0, tex.h0, dirty, t->d_brush_dabs, nd, a, snap, sr); break;
             }
             return VR_OK;
         });

@@ -4,9 +4,10 @@
 //   create   vr_tex_upload_and_mip, vr_node_heights_surface, the first ray cast's pyramid: the rectangle is the whole map
 //   edit     vr_terrain_edit (below): a sub-rectangle of level 0 is replaced in place and everything is brought up to date inside
 //            the dirty rectangle of each structure, so that the terrain is the one vr_terrain_create builds from the edited arrays
-//   brush    vr_terrain_brush (vr_brush.hip): a kernel rewrites texels of level 0 inside a stroke's bounding rectangle; the same
-//            refresh follows.  Edit and brush share vr_derive_level0_write: the waits in front of the write, the write itself
-//            (the caller's), the chain and the tables, the node heights, the pyramid, the order mark behind.
+//   write    every other writer of level 0 (brush, erosion, texture, stamp, noise: vr_level0.h; undo and redo: vr_history.hip): a
+//            kernel rewrites texels inside a rectangle; the same refresh follows.  They share vr_derive_level0_write: the waits
+//            in front of the write, the write itself (the caller's), the chain and the tables, the node heights, the pyramid, the
+//            order mark behind.
 //
 // Every rectangle comes from vr_dirty.h (the whole map dirties the whole of every structure: tests/host/dirty_check.cpp); every
 // element is computed by the expressions of vr_terrain_dev.h.  Grids are sized from the rectangle, never from the map.
@@ -19,24 +20,21 @@
 //                                          (timed as VR_K_NODE_HEIGHTS); a surface off the mip-style path runs its whole
 //                                          reduction (vr_select.hip), on an edit again
 //   query pyramid     k_derive_pyramid_*   once a ray cast asks for it (timed as VR_K_QUERY_PYRAMID)                       vr_derive_pyramid
-#include "vr_internal.h"
+#include "vr_level0.h"
 #include "vr_terrain_dev.h"
-#include "vr_dirty.h"
 #include "vr_packed.h"
-
-#include <string.h>
 
 template <class T>
 __global__ __launch_bounds__(256) void k_derive_copy(const uint8_t* __restrict__ src, size_t src_pitch, T* __restrict__ dst, int dst_w, DirtyRect r)
 {
-    const int x = r.x0 + blockIdx.x * 32 + (threadIdx.x & 31), y = r.y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x = brush_tile_x(r.x0) + brush_lane_x(), y = brush_tile_y(r.y0) + brush_lane_y();
     if (x >= r.x1 || y >= r.y1) return;
     dst[(size_t)y * dst_w + x] = reinterpret_cast<const T*>(src + (size_t)(y - r.y0) * src_pitch)[x - r.x0];
 }
 
 __global__ __launch_bounds__(256) void k_derive_mip_r8(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, DirtyRect r)
 {
-    const int x = r.x0 + blockIdx.x * 32 + (threadIdx.x & 31), y = r.y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x = brush_tile_x(r.x0) + brush_lane_x(), y = brush_tile_y(r.y0) + brush_lane_y();
     if (x >= r.x1 || y >= r.y1) return;
     vr_mip_r8_texel(src, sw, sh, dst, dw, x, y);
 }
@@ -47,7 +45,7 @@ __global__ __launch_bounds__(256) void k_derive_mip_srgba8(const uint32_t* __res
     __shared__ float thr[256];
     lut[threadIdx.x] = lut_g[threadIdx.x]; thr[threadIdx.x] = thr_g[threadIdx.x];
     __syncthreads();
-    const int x = r.x0 + blockIdx.x * 32 + (threadIdx.x & 31), y = r.y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x = brush_tile_x(r.x0) + brush_lane_x(), y = brush_tile_y(r.y0) + brush_lane_y();
     if (x >= r.x1 || y >= r.y1) return;
     vr_mip_srgba8_texel(src, sw, sh, dst, dw, x, y, lut, thr);
 }
@@ -71,8 +69,9 @@ __device__ __forceinline__ bool derive_tables_entry(const DeriveTables& d, int& 
     l = 0;
     while (l + 1 < d.levels && blockIdx.x >= d.lv[l + 1].first_block) l++;
     const uint32_t b = blockIdx.x - d.lv[l].first_block;
-    ix = d.lv[l].entries.x0 + (int)(b % (uint32_t)d.lv[l].blocks_x) * 32 + (int)(threadIdx.x & 31);
-    iy = d.lv[l].entries.y0 + (int)(b / (uint32_t)d.lv[l].blocks_x) * 8 + (int)(threadIdx.x >> 5);
+    // (tiles_32x8's tiles of the level's entries, the workgroups of all levels numbered in one row: not blockIdx's tile)
+    ix = d.lv[l].entries.x0 + (int)(b % (uint32_t)d.lv[l].blocks_x) * kBrushTileW + (int)(threadIdx.x % kBrushTileW);
+    iy = d.lv[l].entries.y0 + (int)(b / (uint32_t)d.lv[l].blocks_x) * kBrushTileH + (int)(threadIdx.x / kBrushTileW);
     return ix < d.lv[l].entries.x1 && iy < d.lv[l].entries.y1;
 }
 __global__ __launch_bounds__(256) void k_derive_tables_r8(DeriveTables d, const uint8_t* __restrict__ chain, uint32_t* __restrict__ quad,
@@ -136,7 +135,6 @@ __global__ __launch_bounds__(256) void k_derive_pyramid_up(const uchar2* __restr
 // host side: the three functions queue launches on the context's stream and report nothing; whoever calls them asks
 // hipGetLastError afterwards
 // ---------------------------------------------------------------------------------------
-static dim3 tiles_32x8(const DirtyRect& r) { return dim3((unsigned)((r.x1 - r.x0 + 31) / 32), (unsigned)((r.y1 - r.y0 + 7) / 8)); }
 static dim3 tiles_64x4(const DirtyRect& r) { return dim3((unsigned)((r.x1 - r.x0 + 63) / 64), (unsigned)((r.y1 - r.y0 + 3) / 4)); }
 // one lane per node: at most 4^num_lods / 256 workgroups, 65536 at VR_MAX_LODS - far below the 2^31 - 1 a grid's x may hold
 static unsigned blocks_of(const DirtyRect& r) { return (unsigned)(((uint64_t)(r.x1 - r.x0) * (uint64_t)(r.y1 - r.y0) + 255) / 256); }
@@ -225,8 +223,8 @@ int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, con
 {
     vr_context* ctx = t->ctx;
     hipStream_t s = ctx->stream;
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
-    const TexLayout& lay = which == 0 ? t->height_layout : t->albedo_layout;
+    const DevTex& tex = vr_terrain_map(t, which);
+    const TexLayout& lay = vr_terrain_layout(t, which);
     // a frame recorded for a target's pending colour planes draws the map as it is now
     { const int rc = vr_terrain_materialise_pending(t); if (rc) return rc; }
     // before the first write: behind every chain queued so far (its vertex stage reads the heightmap) and behind every tile pass
@@ -273,7 +271,7 @@ extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32
     VR_REQUIRE(t != nullptr, "terrain is NULL");
     VR_REQUIRE(which == 0 || which == 1, "which must be 0 (heightmap) or 1 (albedo)");
     VR_REQUIRE(x >= 0 && y >= 0 && w >= 0 && h >= 0, "negative coordinate or extent");
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, which);
     const size_t tb = which == 0 ? 1 : 4;
     VR_REQUIRE((int64_t)x + w <= tex.w0 && (int64_t)y + h <= tex.h0, "the rectangle is not inside level 0");
     if (w == 0 || h == 0) return VR_OK;
@@ -281,9 +279,7 @@ extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32
     VR_REQUIRE(row_pitch_bytes == 0 || row_pitch_bytes >= (size_t)w * tb, "row pitch smaller than a row");
     VR_REQUIRE(!device_pointer || (((uintptr_t)texels | row_pitch_bytes) & (tb - 1)) == 0, "device pointer and pitch must be aligned to the texel size");
     const size_t row = (size_t)w * tb, pitch = row_pitch_bytes ? row_pitch_bytes : row;
-    vr_context* ctx = t->ctx;
-    VR_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    VR_HIP(hipSetDevice(t->ctx->device));
     // staging of the host-pointer mode: reserved before anything is launched (a refusal leaves the terrain as it was)
     const uint8_t* src = (const uint8_t*)texels; size_t src_pitch = pitch;
     if (!device_pointer) {
@@ -294,8 +290,7 @@ extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32
     DirtyRect dirty; dirty.x0 = x; dirty.y0 = y; dirty.x1 = x + w; dirty.y1 = y + h;
     uint8_t* mem = const_cast<uint8_t*>(tex.base);
     // the host's texels into the staging memory, then one strided copy into level 0; everything else is the shared path
-    const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t st) -> int {
-        { const int hrc = vr_history_capture(t, which, dirty, st); if (hrc) return hrc; }      // history on: the rectangle as it is, first
+    const int rc = vr_level0_call(t, which, dirty, nullptr, [&](hipStream_t st) -> int {
         if (!device_pointer) {
             if (pitch == row) VR_HIP(hipMemcpyAsync(t->d_query_stage, texels, row * (size_t)h, hipMemcpyHostToDevice, st));
             else VR_HIP(hipMemcpy2DAsync(t->d_query_stage, row, texels, pitch, row, (size_t)h, hipMemcpyHostToDevice, st));
@@ -305,7 +300,7 @@ extern "C" VR_API int vr_terrain_edit(vr_terrain* t, int which, int32_t x, int32
         return VR_OK;
     });
     if (rc) return rc;
-    if (!device_pointer) VR_HIP(hipStreamSynchronize(s));        // the caller's host memory has been consumed
+    if (!device_pointer) VR_HIP(hipStreamSynchronize(t->ctx->stream));      // the caller's host memory has been consumed
     return VR_OK;
 }
 
@@ -323,8 +318,8 @@ extern "C" VR_API int vr_debug_terrain_tables(vr_terrain* t, int which, int tabl
                || table == VR_DEBUG_TABLE_PACK, "unknown table");
     VR_REQUIRE(level >= 0, "negative level");
     VR_REQUIRE(out_dims != nullptr, "out_dims is NULL");
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
-    const TexLayout& lay = which == 0 ? t->height_layout : t->albedo_layout;
+    const DevTex& tex = vr_terrain_map(t, which);
+    const TexLayout& lay = vr_terrain_layout(t, which);
     const bool has = table == VR_DEBUG_TABLE_FAST || (table == VR_DEBUG_TABLE_RGBF || table == VR_DEBUG_TABLE_PACK ? which == 1 : which == 0);
     int cols = 0, rows = 0;
     size_t at = 0, entry = 16;

@@ -1,10 +1,9 @@
 // vr_terrain_erode and vr_terrain_erode_hydraulic: thermal (talus) and hydraulic erosion of level 0 of the heightmap under a brush
-// mask, on the device, followed by the refresh vr_terrain_edit does (vr_derive_level0_write).  The definitions, texel by texel, are
+// mask, on the device, through vr_brush_call (vr_level0.h).  The definitions, texel by texel, are
 // vr_erode.h and vr_hydro.h; this file holds nothing of them but the order in which the headers' functions are called.  The kernels
 // are written once, over a model type (the models: 4u, 4v):
 //
-//   k_sweep_begin   one 256-thread workgroup per 32 x 8 tile of the rectangle, one texel per lane, the dab list walked the way
-//                   k_brush walks it (vr_brush_dev.h): the mask (fp32) and the model's F state fields into planes of the rectangle's size
+//   k_sweep_begin   the tile frame and brush_tile_mask of vr_brush_dev.h: the mask (fp32) and the model's F state fields into planes of the rectangle's size
 //   k_sweep_steps   the hot path, temporally blocked: a workgroup loads a tile of the F fields and the mask plus a halo of K texels
 //                   into LDS (2F + 1 planes: the fields twice, the mask once), runs up to K sweeps there - ping-pong in LDS, one
 //                   barrier per sweep, the valid region one ring smaller after each - and stores the tile's fields to the other set
@@ -20,10 +19,8 @@
 // A model supplies: kTileW, kTileH, kK, kStrip, kFields, kThreads; Const, the call's constants (trivially copyable); begin(byte,
 // mask, k, f[F]), a lane's initial fields; end(state, plane, at), the byte of texel `at`; and its strip body, which stands in
 // k_sweep_steps' one `if constexpr` over the model, in the kernel's own text (a call costs the thermal kernel registers).
-#include "vr_internal.h"
-#include "vr_dirty.h"
+#include "vr_level0.h"
 #include "vr_hydro.h"
-#include "vr_brush_dev.h"
 
 #include <type_traits>
 
@@ -71,16 +68,13 @@ __global__ __launch_bounds__(256) void k_sweep_begin(const uint8_t* __restrict__
 {
     __shared__ uint16_t list[kBrushChunk];
     __shared__ uint32_t wave_total[4];
-    const int tid = (int)threadIdx.x;
-    const int tx0 = r.x0 + (int)blockIdx.x * kBrushTileW, ty0 = r.y0 + (int)blockIdx.y * kBrushTileH;
-    const int tx1 = tx0 + kBrushTileW < r.x1 ? tx0 + kBrushTileW : r.x1, ty1 = ty0 + kBrushTileH < r.y1 ? ty0 + kBrushTileH : r.y1;
-    const int x = tx0 + (tid & 31), y = ty0 + (tid >> 5);
-    const bool inside = x < tx1 && y < ty1;
-    // every lane stays to the end; one outside the rectangle works on the clamped texel and writes nothing
+    const BrushTile tile = brush_tile(r);
+    const int x = tile.x, y = tile.y;
+    // every lane stays to the end; one outside the rectangle works on the rectangle's nearest texel (not the map's: no tile.cx, tile.cy)
     const int cx = brush_clampi(x, r.x0, r.x1 - 1), cy = brush_clampi(y, r.y0, r.y1 - 1);
     const float h = (float)map[(size_t)brush_clampi(cy, 0, h0 - 1) * (size_t)w0 + (size_t)brush_clampi(cx, 0, w0 - 1)];
-    const float m = brush_tile_mask(dabs, n, tx0, ty0, tx1, ty1, x, y, inside, list, wave_total);
-    if (!inside) return;
+    const float m = brush_tile_mask(dabs, n, tile, list, wave_total);
+    if (!tile.inside) return;
     const size_t at = (size_t)(y - r.y0) * (size_t)(r.x1 - r.x0) + (size_t)(x - r.x0);
     float f[M::kFields];
     M::begin(h, m, k, f);
@@ -201,7 +195,7 @@ __global__ __launch_bounds__(M::kThreads) void k_sweep_steps(const float* __rest
 template <class M>
 __global__ __launch_bounds__(256) void k_sweep_end(uint8_t* __restrict__ map, int w0, DirtyRect r, const float* __restrict__ mask, const float* __restrict__ state, size_t plane)
 {
-    const int x = r.x0 + (int)blockIdx.x * kBrushTileW + ((int)threadIdx.x & 31), y = r.y0 + (int)blockIdx.y * kBrushTileH + ((int)threadIdx.x >> 5);
+    const int x = brush_tile_x(r.x0) + brush_lane_x(), y = brush_tile_y(r.y0) + brush_lane_y();
     if (x >= r.x1 || y >= r.y1) return;
     const size_t at = (size_t)(y - r.y0) * (size_t)(r.x1 - r.x0) + (size_t)(x - r.x0);
     if (mask[at] > 0.0f) map[(size_t)y * (size_t)w0 + (size_t)x] = M::end(state, plane, at);
@@ -229,7 +223,7 @@ extern "C" VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps)
     return VR_OK;
 }
 
-// One call of the model M behind its entry point's own checks (vr_brush_call, vr_brush_dev.h): the block's 2F + 1 planes of the
+// One call of the model M behind its entry point's own checks (vr_brush_call, vr_level0.h): the block's 2F + 1 planes of the
 // rectangle reserved, then begin, ceil(iterations / per_launch) step launches and end.  What the launches left is recorded on the
 // terrain for vr_debug_terrain_sweep_state: a refused call leaves the record as it was, a call whose dabs all miss clears it.
 template <class M>

@@ -2,7 +2,7 @@
 // is given up when the budget is short is vr_history.h; this file holds the arena, the two kernels that move a rectangle between
 // a map and its record, the event behind them and the entry points.
 //
-//   k_history_capture<T>   map -> record, queued by vr_terrain_edit and vr_terrain_brush in front of their write of level 0
+//   k_history_capture<T>   map -> record, queued by vr_level0_call (vr_level0.h) in front of every edit's write of level 0
 //   k_history_swap<T>      map <-> record, queued by undo and redo as the write of vr_derive_level0_write, whose refresh follows
 //
 // Both are one launch per record, one lane per 16-byte chunk of a record row (pitch / 16 chunks per row, rows x chunks lanes in
@@ -60,7 +60,7 @@ template <class T> __global__ __launch_bounds__(256) void k_history_swap(History
 // ---------------------------------------------------------------------------------------
 static HistoryMove history_move_of(const vr_terrain* t, const HistoryRecord& e)
 {
-    const DevTex& tex = e.which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, e.which);
     HistoryMove m;
     m.map_pitch = (uint64_t)tex.w0 * e.texel_bytes;
     m.map = const_cast<uint8_t*>(tex.base) + (size_t)e.r.y0 * m.map_pitch + (size_t)e.r.x0 * e.texel_bytes;
@@ -152,6 +152,7 @@ static int history_apply(vr_terrain* t, bool undo, int32_t* applied)
     VR_HIP(hipSetDevice(t->ctx->device));
     for (uint64_t k = 0; k < hi - lo; k++) {
         const HistoryRecord e = history_at(t->history, undo ? hi - 1 - k : lo + k);
+        // (not vr_level0_call: applying a record captures nothing, so the write is the swap alone)
         const int rc = vr_derive_level0_write(t, e.which, e.r, [&](hipStream_t s) -> int { return history_queue<true>(t, e, s); });
         if (rc) return rc;
     }

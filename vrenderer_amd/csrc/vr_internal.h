@@ -400,6 +400,9 @@ struct vr_terrain {
     std::vector<HistoryRecord> history_table;
     uint8_t* d_history = nullptr;
 };
+// the map `which` names (0: the heightmap, 1: the albedo) and its layout
+inline const DevTex& vr_terrain_map(const vr_terrain* t, int which) { return which == 0 ? t->height : t->albedo; }
+inline const TexLayout& vr_terrain_layout(const vr_terrain* t, int which) { return which == 0 ? t->height_layout : t->albedo_layout; }
 void vr_query_release(vr_terrain* t);      // frees the above (vr_query.hip)
 void vr_brush_release(vr_terrain* t);      // the brush's and the erosions' memory and their event (vr_brush.hip)
 // What vr_terrain_brush, vr_terrain_erode and vr_terrain_erode_hydraulic share (vr_brush.hip).  check_dabs: the dab refusals of a stroke of `op` (an opacity
@@ -407,7 +410,7 @@ void vr_brush_release(vr_terrain* t);      // the brush's and the erosions' memo
 // spans.  reserve: the event, the pinned and the device dab list and `snap_bytes` of snapshot, before anything is launched.
 // grow: one of the buffers read in front of ord_brush's event to `bytes` (vr_reserve).  consumed: order_side_idle(ord_brush), the
 // one wait on the host.  (vr_brush_call, the whole path from the dab checks to the recorded event around the
-// caller's reserve step and launches, is a template: vr_brush_dev.h.)
+// caller's reserve step and launches, is a template: vr_level0.h.)
 struct DirtyRect;
 int vr_brush_grow(vr_terrain* t, void** ptr, size_t* capacity, size_t bytes);
 int vr_brush_check_dabs(const vr_brush_dab* dabs, uint32_t n, int op);
@@ -417,7 +420,7 @@ int vr_brush_consumed(vr_terrain* t);
 void vr_history_release(vr_terrain* t);    // the journal's arena and event; history is off afterwards (vr_history.hip)
 // In front of a write of the rectangle `dirty` of level 0 (inside vr_derive_level0_write's write_level0, so behind its waits): with
 // history on, a record is appended and the kernel that captures the rectangle is queued on `s`.  Synchronises nothing; with
-// history off it does nothing at all.
+// history off it does nothing at all.  Its one caller is vr_level0_call (vr_level0.h).
 int vr_history_capture(vr_terrain* t, int which, const DirtyRect& dirty, hipStream_t s);
 // the staging memory holds at least `bytes` (grown by doubling; on failure the terrain keeps what it had); whoever uses it
 // synchronises the context's stream before it returns
@@ -445,7 +448,7 @@ void vr_derive_node_heights(vr_terrain* t, int surf, const NodeSurface& ns, cons
 // the query pyramid at `pyramid`; l0, l1: the rectangle in levels 0 and 1 of the heightmap (a one-level chain: l1 = l0)
 void vr_derive_pyramid(const DevTex& hm, const PyrDesc& pd, uchar2* pyramid, const DirtyRect& l0, const DirtyRect& l1, hipStream_t s);
 // A write of the rectangle `dirty` of level 0 of a map (which: 0 heightmap, 1 albedo) and everything that follows from it, on the
-// context's stream - the one path of vr_terrain_edit and vr_terrain_brush: the write waits behind every chain and tile pass queued
+// context's stream - the one path of vr_level0_call (vr_level0.h: every edit) and of undo and redo: the write waits behind every chain and tile pass queued
 // so far, prepared geometry is dropped, write_level0(stream) queues the write itself, then the chain and the tables, the node
 // heights and the query pyramid are brought up to date inside their dirty rectangles and every set's next chain runs behind it.
 int vr_derive_level0_write(vr_terrain* t, int which, const DirtyRect& dirty, const std::function<int(hipStream_t)>& write_level0);

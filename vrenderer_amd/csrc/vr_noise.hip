@@ -1,26 +1,18 @@
 // vr_terrain_noise: fractal value or gradient noise added to or blended into level 0 of a map - under a brush mask or over the whole
-// map - by one kernel, followed by the refresh vr_terrain_edit does (vr_derive_level0_write).  The definition, texel by texel, is
-// vr_noise.h; this file holds nothing of it.
+// map - by one kernel, through vr_mask_call (vr_level0.h).  The definition, texel by texel, is vr_noise.h; this file holds nothing of it.
 //
-//   k_noise<T, WHOLE>   T = uint8_t (the heightmap) or uchar4 (the albedo).  One 256-thread workgroup per 32 x 8 tile of the
-//                       rectangle, one texel per lane.  The mask is brush_tile_mask's (vr_brush_dev.h: the erosions' mask, the dab
-//                       list walked in chunks of 256); WHOLE has mask 1 on every texel, walks no list and takes no dab buffer.  The
+//   k_noise<T, WHOLE>   T = uint8_t (the heightmap) or uchar4 (the albedo).  The tile frame of vr_brush_dev.h; the mask is its
+//                       brush_tile_mask's, and WHOLE has mask 1 on every texel, walks no list and takes no dab buffer.  The
 //                       prepared per-octave constants are one kernel argument: wave-uniform, read by scalar loads.  The octave
 //                       loop is bounded by the constant 12 and left at the call's count; basis and fractal are uniform branches.
-//                       No lane leaves before the last barrier; every index is clamped before it addresses memory; a lane outside
-//                       the rectangle or with mask 0 stores nothing.  The cost is arithmetic - octaves x four lattice hashes per
+//                       A lane with mask 0 stores nothing.  The cost is arithmetic - octaves x four lattice hashes per
 //                       texel - and no texel reads any memory but its own byte.
 //                       A variant for the whole R8 map with four texels per lane, one dword load and store, was measured against
 //                       this kernel and not kept (profiles/terrain_noise_variants.txt).
 //
 // The kernel is untimed, like the brush kernel.
-#include "vr_internal.h"
-#include "vr_dirty.h"
-#include "vr_brush.h"
-#include "vr_brush_dev.h"
+#include "vr_level0.h"
 #include "vr_noise.h"
-
-#include <string.h>
 
 // `map`: level 0 of the map, w0 x h0; `r`: the call's rectangle, inside the map; `dabs`: n of them, prepared for the map, none empty
 // (WHOLE: none at all)
@@ -29,17 +21,12 @@ __global__ __launch_bounds__(256) void k_noise(T* __restrict__ map, int w0, int 
 {
     __shared__ uint16_t list[kBrushChunk];  // the chunk's dabs that meet this tile
     __shared__ uint32_t wave_total[4];
-    const int tid = (int)threadIdx.x;
-    const int tx0 = r.x0 + (int)blockIdx.x * kBrushTileW, ty0 = r.y0 + (int)blockIdx.y * kBrushTileH;
-    const int tx1 = tx0 + kBrushTileW < r.x1 ? tx0 + kBrushTileW : r.x1, ty1 = ty0 + kBrushTileH < r.y1 ? ty0 + kBrushTileH : r.y1;
-    const int x = tx0 + (tid & 31), y = ty0 + (tid >> 5);
-    const bool inside = x < tx1 && y < ty1;
-    // every lane stays to the last barrier; one outside the rectangle works on the clamped texel and writes nothing
-    const int cx = brush_clampi(x, 0, w0 - 1), cy = brush_clampi(y, 0, h0 - 1);
+    const BrushTile tile = brush_tile(r);
+    const int cx = tile.cx(w0), cy = tile.cy(h0);
     float m;
-    if constexpr (WHOLE) m = inside ? 1.0f : 0.0f;
-    else m = brush_tile_mask(dabs, n, tx0, ty0, tx1, ty1, x, y, inside, list, wave_total);
-    if (!(inside && m > 0.0f)) return;                             // behind the last barrier
+    if constexpr (WHOLE) m = tile.inside ? 1.0f : 0.0f;
+    else m = brush_tile_mask(dabs, n, tile, list, wave_total);
+    if (!(tile.inside && m > 0.0f)) return;                        // behind the last barrier
     const float f = noise_fractal(k, cx, cy);
     const size_t at = (size_t)cy * (size_t)w0 + (size_t)cx;
     if constexpr (sizeof(T) == 4) {
@@ -60,7 +47,7 @@ __global__ __launch_bounds__(256) void k_noise(T* __restrict__ map, int w0, int 
 // k_noise over the rectangle `r` on `s`; dabs == nullptr: the whole-map variant
 static void noise_launch(vr_terrain* t, int which, hipStream_t s, const DirtyRect& r, const BrushDab* dabs, uint32_t nd, const NoiseConst& k)
 {
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, which);
     uint8_t* mem = const_cast<uint8_t*>(tex.base);
     const dim3 grid = tiles_32x8(r);
     if (which == 0) {
@@ -104,7 +91,7 @@ extern "C" VR_API int vr_terrain_noise(vr_terrain* t, int which, const vr_noise_
     for (int i = 0; i < 2; i++) VR_REQUIRE(p->reserved[i] == 0, "reserved must be zero");
     if (!whole) { const int rc = vr_brush_check_dabs(dabs, n, VR_BRUSH_FLATTEN); if (rc) return rc; }       // strength is an opacity
     // the handle is looked into from here on
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, which);
     NoiseDesc d;
     d.frequency = p->frequency; d.offset_x = p->offset_x; d.offset_z = p->offset_z; d.lacunarity = p->lacunarity; d.gain = p->gain;
     d.amplitude = p->amplitude; d.base = p->base; d.seed = p->seed; d.octaves = p->octaves; d.basis = p->basis; d.fractal = p->fractal; d.op = p->op;
@@ -112,21 +99,8 @@ extern "C" VR_API int vr_terrain_noise(vr_terrain* t, int which, const vr_noise_
     const NoiseConst k = noise_prepare(d, t->p.world_size, tex.w0, tex.h0);
     // the one refusal that needs the map's size: what keeps (int32_t)floorf(u) defined and u - floorf(u) meaningful (vr_noise.h)
     VR_REQUIRE(noise_in_range(k, tex.w0, tex.h0), "a lattice coordinate reaches 2^22 on this map: lower frequency, lacunarity, octaves or the offset");
-    if (!whole)
-        return vr_brush_call(t, which, dabs, n, VR_BRUSH_FLATTEN, out_rect,
-            [&](const DirtyRect&) -> int { return vr_brush_reserve(t, 0); },                     // nothing beyond the dab list
-            [&](hipStream_t s, const DirtyRect& dirty, uint32_t nd) -> int { noise_launch(t, which, s, dirty, t->d_brush_dabs, nd, k); return VR_OK; });
-    // the whole map: the same write path with the full rectangle; no dab list, so ord_brush's buffers are not touched
-    if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
-    VR_HIP(hipSetDevice(t->ctx->device));
-    DirtyRect dirty; dirty.x0 = 0; dirty.y0 = 0; dirty.x1 = tex.w0; dirty.y1 = tex.h0;
-    const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t s) -> int {
-        { const int hrc = vr_history_capture(t, which, dirty, s); if (hrc) return hrc; }           // history on: the map as it is, first
-        noise_launch(t, which, s, dirty, nullptr, 0, k);
-        VR_HIP(hipGetLastError());
+    return vr_mask_call(t, which, whole, dabs, n, out_rect, [&](hipStream_t s, const DirtyRect& dirty, const BrushDab* d_dabs, uint32_t nd) -> int {
+        noise_launch(t, which, s, dirty, d_dabs, nd, k);
         return VR_OK;
     });
-    if (rc) return rc;
-    if (out_rect) { out_rect[0] = 0; out_rect[1] = 0; out_rect[2] = dirty.x1; out_rect[3] = dirty.y1; }
-    return VR_OK;
 }

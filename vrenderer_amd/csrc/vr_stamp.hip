@@ -1,9 +1,9 @@
 // Stamps: a patch of R8 or SRGBA8 texels kept in device memory (vr_stamp_create, vr_stamp_from_terrain) and set into level 0 of a
-// map at a position, size and angle with a blend rule (vr_terrain_stamp) by one kernel, followed by the refresh vr_terrain_edit does
-// (vr_derive_level0_write).  The definition, texel by texel, is vr_stamp.h; this file holds nothing of it.
+// map at a position, size and angle with a blend rule (vr_terrain_stamp) by one kernel, through vr_level0_call (vr_level0.h).  The
+// definition, texel by texel, is vr_stamp.h; this file holds nothing of it.
 //
 //   k_stamp_copy<T>            the pitched copies: the caller's device memory into a new stamp, a rectangle of a map's level 0 into one
-//   k_stamp<FORMAT>            one 256-thread workgroup per 32 x 8 tile of the call's rectangle, one texel per lane.  The prepared
+//   k_stamp<FORMAT>            the barrier-free tile frame of vr_brush_dev.h over the call's rectangle.  The prepared
 //                              constants are one kernel argument: wave-uniform, read by scalar loads.  A texel reads a 2 x 2
 //                              footprint of the stamp straight from memory, through the caches.  A variant that first loaded the
 //                              tile's footprint in stamp space into LDS was built and measured against this one: it beat it at no
@@ -15,14 +15,10 @@
 //
 // A stamp is a side resource (vr_order.h): one OrderSide, order_side_begin / _end round every kernel and copy that reads or writes
 // it, order_side_idle in front of its free.  The kernels are untimed, like the brush kernel.
-#include "vr_internal.h"
-#include "vr_dirty.h"
-#include "vr_brush.h"
-#include "vr_brush_dev.h"
+#include "vr_level0.h"
 #include "vr_stamp.h"
 
 #include <new>
-#include <string.h>
 
 struct vr_stamp {
     vr_context* ctx;            // first, like vr_terrain's: the refusals compare the two
@@ -34,7 +30,7 @@ struct vr_stamp {
 template <class T>
 __global__ __launch_bounds__(256) void k_stamp_copy(const uint8_t* __restrict__ src, size_t src_pitch, T* __restrict__ dst, int w, int h)
 {
-    const int x = (int)blockIdx.x * kBrushTileW + ((int)threadIdx.x & 31), y = (int)blockIdx.y * kBrushTileH + ((int)threadIdx.x >> 5);
+    const int x = brush_tile_x(0) + brush_lane_x(), y = brush_tile_y(0) + brush_lane_y();
     if (x >= w || y >= h) return;
     dst[(size_t)y * (size_t)w + (size_t)x] = ((const T*)(src + (size_t)y * src_pitch))[x];
 }
@@ -54,8 +50,7 @@ __global__ __launch_bounds__(256) void k_stamp(void* __restrict__ map, int w0, i
 {
     using T = typename StampTexel<FORMAT>::type;
     constexpr int NC = FORMAT == kStampSrgba8 ? 4 : 1;
-    const int tid = (int)threadIdx.x;
-    const int x = r.x0 + (int)blockIdx.x * kBrushTileW + (tid & 31), y = r.y0 + (int)blockIdx.y * kBrushTileH + (tid >> 5);
+    const int x = brush_tile_x(r.x0) + brush_lane_x(), y = brush_tile_y(r.y0) + brush_lane_y();
     if (x >= r.x1 || y >= r.y1) return;                            // (no barrier anywhere below)
     const int cx = brush_clampi(x, 0, w0 - 1), cy = brush_clampi(y, 0, h0 - 1);
     StampFetch<FORMAT> fetch;
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(256) void k_stamp(void* __restrict__ map, int w0, i
 // host side
 // ---------------------------------------------------------------------------------------
 static size_t stamp_texel_bytes(int format) { return format == VR_STAMP_SRGBA8 ? 4 : 1; }
-static dim3 stamp_tiles(int w, int h) { return dim3((unsigned)((w + kBrushTileW - 1) / kBrushTileW), (unsigned)((h + kBrushTileH - 1) / kBrushTileH)); }
+static dim3 stamp_tiles(int w, int h) { return tiles_32x8(dirty_whole(w, h)); }
 
 // a stamp of `format`, w x h, its memory and its event; everything or nothing
 static int stamp_new(vr_context* ctx, int format, int w, int h, vr_stamp** out)
@@ -155,7 +150,7 @@ extern "C" VR_API int vr_stamp_from_terrain(vr_terrain* t, int which, int32_t x,
     VR_REQUIRE(which == 0 || which == 1, "which must be 0 (heightmap) or 1 (albedo)");
     VR_REQUIRE(w >= 1 && w <= kStampMaxSide && h >= 1 && h <= kStampMaxSide, "a stamp has 1 .. 4096 texels per side");
     VR_REQUIRE(x >= 0 && y >= 0, "negative coordinate");
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, which);
     VR_REQUIRE((int64_t)x + w <= tex.w0 && (int64_t)y + h <= tex.h0, "the rectangle is not inside level 0");
     vr_context* ctx = t->ctx;
     VR_HIP(hipSetDevice(ctx->device));
@@ -203,7 +198,7 @@ extern "C" VR_API int vr_stamp_download(vr_stamp* st, void* host, size_t bytes)
 // k_stamp over the rectangle `r` on `s`
 static void stamp_launch(vr_terrain* t, int which, hipStream_t s, const DirtyRect& r, const vr_stamp* st, const StampConst& k)
 {
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, which);
     void* mem = const_cast<uint8_t*>(tex.base);
     if (which == 0) hipLaunchKernelGGL(k_stamp<kStampR8>, tiles_32x8(r), dim3(256), 0, s, mem, tex.w0, tex.h0, r, (const void*)st->d_texels, k);
     else hipLaunchKernelGGL(k_stamp<kStampSrgba8>, tiles_32x8(r), dim3(256), 0, s, mem, tex.w0, tex.h0, r, (const void*)st->d_texels, k);
@@ -235,24 +230,17 @@ extern "C" VR_API int vr_terrain_stamp(vr_terrain* t, int which, vr_stamp* st, c
     VR_REQUIRE(p->channel_mask >= 1u && p->channel_mask <= 15u, "channel_mask must be 1 .. 15");
     VR_REQUIRE(which == 1 || p->channel_mask == 1u, "an R8 map has channel_mask 1");
     for (int i = 0; i < 4; i++) VR_REQUIRE(p->reserved[i] == 0, "reserved must be zero");
-    const DevTex& tex = which == 0 ? t->height : t->albedo;
+    const DevTex& tex = vr_terrain_map(t, which);
     StampDesc d;
     d.x = p->x; d.z = p->z; d.size_x = p->size_x; d.size_z = p->size_z; d.rotation = p->rotation; d.opacity = p->opacity; d.feather = p->feather;
     d.gain = p->gain; d.offset = p->offset; d.op = p->op; d.channel_mask = p->channel_mask; d.flags = p->flags;
     DirtyRect dirty;
     const StampConst k = stamp_prepare(d, t->p.world_size, tex.w0, tex.h0, st->w, st->h, &dirty);
-    if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
-    if (dirty_empty(dirty)) return VR_OK;                          // the stamp misses the map: nothing is launched
-    VR_HIP(hipSetDevice(t->ctx->device));
-    // the same write path as a whole-map vr_terrain_texture; the call needs no memory beyond the history's own record
-    const int rc = vr_derive_level0_write(t, which, dirty, [&](hipStream_t s) -> int {
-        { const int hrc = vr_history_capture(t, which, dirty, s); if (hrc) return hrc; }           // history on: the rectangle as it is, first
+    // a stamp that misses the map launches nothing; the call needs no memory beyond the history's own record
+    return vr_level0_call(t, which, dirty, out_rect, [&](hipStream_t s) -> int {
         { const int orc = order_side_begin(st->ord, VrOrderOps(), s); if (orc) return orc; }
         stamp_launch(t, which, s, dirty, st, k);
         VR_HIP(hipGetLastError());
         return order_side_end(st->ord, VrOrderOps(), s);
     });
-    if (rc) return rc;
-    if (out_rect) { out_rect[0] = dirty.x0; out_rect[1] = dirty.y0; out_rect[2] = dirty.x1 - dirty.x0; out_rect[3] = dirty.y1 - dirty.y0; }
-    return VR_OK;
 }

@@ -1,9 +1,8 @@
 // vr_terrain_texture: level 0 of the albedo painted by rule from the heightmap's shape - altitude and slope layers under a brush mask
-// or over the whole map - by one kernel, followed by the refresh vr_terrain_edit does (vr_derive_level0_write).  The definition,
-// texel by texel, is vr_texture.h; this file holds nothing of it but where the height bytes come from.
+// or over the whole map - by one kernel, through vr_mask_call (vr_level0.h).  The definition, texel by texel, is vr_texture.h; this
+// file holds nothing of it but where the height bytes come from.
 //
-//   k_texture<STAGED, WHOLE>   one 256-thread workgroup per 32 x 8 tile of the albedo rectangle, one texel per lane.  The mask is
-//                              brush_tile_mask's (vr_brush_dev.h: the erosions' mask, the dab list walked in chunks of 256); WHOLE
+//   k_texture<STAGED, WHOLE>   the tile frame of vr_brush_dev.h over the albedo rectangle; the mask is its brush_tile_mask's, and WHOLE
 //                              has mask 1 on every texel, walks no list and takes no dab buffer.  The prepared layers (at most 8)
 //                              and the call's four constants are one kernel argument: wave-uniform, read by scalar loads.
 //                              A texel reads a 4 x 4 footprint of height bytes through HeightFetch.  STAGED: the tile's footprint
@@ -11,17 +10,12 @@
 //                              texel's sample point, clamped at the map's edge - is loaded into LDS once, row by row by consecutive
 //                              lanes; the host chooses it where that is at most 4 KiB.  Otherwise (a heightmap much finer than the
 //                              albedo: the lanes' footprints hardly overlap) the lanes read memory directly.  The arithmetic is one
-//                              body and the bytes are the same.  No lane leaves before the last barrier; every index is clamped
-//                              before it addresses memory; a lane outside the rectangle or with mask 0 stores nothing.
+//                              body and the bytes are the same.  Every index is clamped before it addresses memory; a lane with
+//                              mask 0 stores nothing.
 //
 // The kernel is untimed, like the brush kernel.
-#include "vr_internal.h"
-#include "vr_dirty.h"
-#include "vr_brush.h"
-#include "vr_brush_dev.h"
+#include "vr_level0.h"
 #include "vr_texture.h"
-
-#include <string.h>
 
 constexpr int kTextureFootBytes = 4096;
 
@@ -54,22 +48,17 @@ __global__ __launch_bounds__(256) void k_texture(uchar4* __restrict__ albedo, in
     __shared__ uint8_t foot[STAGED ? kTextureFootBytes : 4];
     __shared__ uint16_t list[kBrushChunk];  // the chunk's dabs that meet this tile
     __shared__ uint32_t wave_total[4];
-    const int tid = (int)threadIdx.x;
-    const int tx0 = r.x0 + (int)blockIdx.x * kBrushTileW, ty0 = r.y0 + (int)blockIdx.y * kBrushTileH;
-    const int tx1 = tx0 + kBrushTileW < r.x1 ? tx0 + kBrushTileW : r.x1, ty1 = ty0 + kBrushTileH < r.y1 ? ty0 + kBrushTileH : r.y1;
-    const int x = tx0 + (tid & 31), y = ty0 + (tid >> 5);
-    const bool inside = x < tx1 && y < ty1;
-    // every lane stays to the last barrier; one outside the rectangle works on the clamped texel and writes nothing
-    const int cx = brush_clampi(x, 0, wa - 1), cy = brush_clampi(y, 0, ha - 1);
+    const BrushTile tile = brush_tile(r);
+    const int cx = tile.cx(wa), cy = tile.cy(ha);
     HeightFetch<STAGED> fetch;
     if constexpr (STAGED) {
         // the sample points grow with the texel index: the tile's first texel has the smallest i0 and j0
         int a0, a1, b0, b1; float ta, tb;
-        texture_axis(brush_clampi(tx0, 0, wa - 1), k.rx, w0, &a0, &a1, &ta);
-        texture_axis(brush_clampi(ty0, 0, ha - 1), k.rz, h0, &b0, &b1, &tb);
+        texture_axis(brush_clampi(tile.tx0, 0, wa - 1), k.rx, w0, &a0, &a1, &ta);
+        texture_axis(brush_clampi(tile.ty0, 0, ha - 1), k.rz, h0, &b0, &b1, &tb);
         const int ox = a0 - 1, oy = b0 - 1;
         const int cells = fw * fh < kTextureFootBytes ? fw * fh : kTextureFootBytes;
-        for (int at = tid; at < cells; at += 256) {
+        for (int at = (int)threadIdx.x; at < cells; at += kBrushThreads) {
             const int ly = at / fw, lx = at - ly * fw;
             foot[at] = height[(size_t)brush_clampi(oy + ly, 0, h0 - 1) * (size_t)w0 + (size_t)brush_clampi(ox + lx, 0, w0 - 1)];
         }
@@ -79,9 +68,9 @@ __global__ __launch_bounds__(256) void k_texture(uchar4* __restrict__ albedo, in
         fetch.height = height; fetch.w0 = w0;
     }
     float m;
-    if constexpr (WHOLE) m = inside ? 1.0f : 0.0f;
-    else m = brush_tile_mask(dabs, n, tx0, ty0, tx1, ty1, x, y, inside, list, wave_total);
-    if (!(inside && m > 0.0f)) return;                             // behind the last barrier
+    if constexpr (WHOLE) m = tile.inside ? 1.0f : 0.0f;
+    else m = brush_tile_mask(dabs, n, tile, list, wave_total);
+    if (!(tile.inside && m > 0.0f)) return;                        // behind the last barrier
     float h, s2;
     texture_sample(k, fetch, w0, h0, cx, cy, &h, &s2);
     const size_t at = (size_t)cy * (size_t)wa + (size_t)cx;
@@ -153,21 +142,8 @@ extern "C" VR_API int vr_terrain_texture(vr_terrain* t, const vr_texture_params*
     if (!whole) { const int rc = vr_brush_check_dabs(dabs, n, VR_BRUSH_FLATTEN); if (rc) return rc; }       // strength is an opacity
     // the layer list is consumed here, on the host: the kernel takes the prepared layers by value
     const TextureConst k = texture_prepare(desc, p->num_layers, p->max_height, t->p.world_size, t->height.w0, t->height.h0, t->albedo.w0, t->albedo.h0);
-    if (!whole)
-        return vr_brush_call(t, 1, dabs, n, VR_BRUSH_FLATTEN, out_rect,
-            [&](const DirtyRect&) -> int { return vr_brush_reserve(t, 0); },                     // nothing beyond the dab list
-            [&](hipStream_t s, const DirtyRect& dirty, uint32_t nd) -> int { texture_launch(t, s, dirty, t->d_brush_dabs, nd, k); return VR_OK; });
-    // the whole map: the same write path with the full rectangle; no dab list, so ord_brush's buffers are not touched
-    if (out_rect) { out_rect[0] = out_rect[1] = out_rect[2] = out_rect[3] = 0; }
-    VR_HIP(hipSetDevice(t->ctx->device));
-    DirtyRect dirty; dirty.x0 = 0; dirty.y0 = 0; dirty.x1 = t->albedo.w0; dirty.y1 = t->albedo.h0;
-    const int rc = vr_derive_level0_write(t, 1, dirty, [&](hipStream_t s) -> int {
-        { const int hrc = vr_history_capture(t, 1, dirty, s); if (hrc) return hrc; }               // history on: the map as it is, first
-        texture_launch(t, s, dirty, nullptr, 0, k);
-        VR_HIP(hipGetLastError());
+    return vr_mask_call(t, 1, whole, dabs, n, out_rect, [&](hipStream_t s, const DirtyRect& dirty, const BrushDab* d_dabs, uint32_t nd) -> int {
+        texture_launch(t, s, dirty, d_dabs, nd, k);
         return VR_OK;
     });
-    if (rc) return rc;
-    if (out_rect) { out_rect[0] = 0; out_rect[1] = 0; out_rect[2] = dirty.x1; out_rect[3] = dirty.y1; }
-    return VR_OK;
 }
