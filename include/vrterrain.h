@@ -189,7 +189,7 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
  * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
  * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
- * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _noise / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _noise / _path / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
  * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
  * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
  * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
@@ -398,6 +398,45 @@ typedef struct vr_noise_params {       /* 64 B */
     int32_t reserved[2];               /* zero */
 } vr_noise_params;
 VR_API int vr_terrain_noise(vr_terrain* t, int which, const vr_noise_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
+/* A path on level 0 of the heightmap (which = 0: LEVEL, CUT, FILL) or the albedo (1: PAINT) - a road, a railway embankment, a river
+ * bed, a dam, a piste, a painted track: a corridor of half-width `radius` world units along the polyline through `points`, computed on
+ * the device from the map as it is there and followed by the refresh vr_terrain_edit does: afterwards the terrain is the one
+ * vr_terrain_create builds from the map with the path in it.  `points` are world (x, z), as for dabs, each with the target `height` in
+ * stored heightmap units ([0, 255], like FLATTEN's target; PAINT ignores it).  n points make n - 1 segments, or n with VR_PATH_CLOSED
+ * (the last point joined to the first; needs n >= 3); n == 1 is a single disc, and a repeated point makes a zero-length segment, a
+ * disc too - it is legal.  Across the path the weight is a dab's: with q = (distance to the polyline / radius)^2 it is 1 out to
+ * q <= hardness^2 and the dab's smoothstep to 0 at q = 1.  Per texel the NEAREST segment counts - the one with the smallest q, of equal
+ * ones the first in the list - with its parameter t in [0, 1] and the target = height_a + t * (height_b - height_a); with
+ * a = weight * opacity the texel's value (the stored byte; four for the albedo) changes ONCE, however many segments pass nearby and
+ * however the path bends - no beads, no joints applied twice:
+ *   VR_PATH_LEVEL  value += a * (target - value)
+ *   VR_PATH_CUT    value += a * (min(value, target) - value)       only lowers: a river bed, a cutting
+ *   VR_PATH_FILL   value += a * (max(value, target) - value)       only raises: an embankment, a dam
+ *   VR_PATH_PAINT  per channel c of channel_mask (as vr_terrain_brush's PAINT): value_c += a * (color[c] - value_c)
+ * clamped to [0, 255] and rounded to the nearest byte once.  LEVEL, CUT and FILL need which = 0 and channel_mask == 1, PAINT which = 1.
+ * A texel farther than `radius` from every segment is not written.  A texel is a function of its own byte, its position and the call
+ * alone.  The arithmetic is defined bit for bit in vrenderer_amd/csrc/vr_path.h, without a division, a square root or
+ * trigonometry on the device.
+ * out_rect, the stream order and what the host waits for are vr_terrain_brush's: the call synchronises nothing, is ordered against
+ * the strokes, erosions and the other writers of the terrain, and `points` is host memory that may be reused as soon as the call
+ * returns.  With history on, one call is one record.  n == 0, or a path that misses the map, is VR_OK and launches nothing.
+ * Not here: a width per point; splines (the caller tessellates - a point every few texels of a curve is plenty, and VR_MAX_PATH_POINTS
+ * of them fit a call); heights snapped to the ground (vr_terrain_query_heights gives them, one call before); both maps in one call
+ * (a road and its paint are two calls with the same points).
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the terrain untouched: NULL t or p; NULL points with
+ * n > 0; n > VR_MAX_PATH_POINTS; `which` not 0 or 1; an unknown op, or one that does not fit the map; unknown flag bits;
+ * VR_PATH_CLOSED with n < 3; a NaN or an infinity anywhere; radius <= 0; hardness outside [0, 1); opacity outside [0, 1]; a height or
+ * a color outside [0, 255]; a channel_mask of 0 or above 15, or other than 1 on the heightmap; a non-zero reserved word, a point's
+ * included.  The memory a call needs is reserved before anything is launched (VR_ERR_OUT_OF_MEMORY leaves the terrain as it was).
+ * Timing: as for vr_terrain_edit; the path kernel itself is untimed. */
+#define VR_MAX_PATH_POINTS 4096
+enum { VR_PATH_LEVEL = 0, VR_PATH_CUT = 1, VR_PATH_FILL = 2, VR_PATH_PAINT = 3 };
+enum { VR_PATH_CLOSED = 1 };
+typedef struct vr_path_point  { float x, z, height, reserved; } vr_path_point;             /* 16 B */
+typedef struct vr_path_params { int32_t op; uint32_t channel_mask; float radius, hardness, opacity;
+                                float color[4]; uint32_t flags; int32_t reserved[6]; } vr_path_params; /* 64 B */
+VR_API int vr_terrain_path(vr_terrain* t, int which, const vr_path_params* p,
+                           const vr_path_point* points, uint32_t n, int32_t out_rect[4]);
 /* Stamps: a prepared patch - a mountain, a crater, a scanned tile, an albedo decal - kept in device memory and set into level 0 of a
  * map at a position, size and angle, with a blend rule.  A vr_stamp is w x h texels, 1 .. 4096 per side, of one of the maps' formats:
  * VR_STAMP_R8 (the heightmap's, = which 0) or VR_STAMP_SRGBA8 (the albedo's, = which 1).  It belongs to the context it was created
@@ -531,13 +570,13 @@ VR_API int vr_debug_hydro_config(int32_t out[4]);
 /* measurement helper, process-wide: later calls advance `sweeps` (1 .. the build's figure; 0 = that figure again) sweeps per
  * launch.  The bytes are the same; only the number of launches changes.  VR_ERR_INVALID_ARGUMENT outside that range. */
 VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps);
-/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_noise, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
+/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_noise, vr_terrain_path, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
  * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
  *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
  *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
  *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
  *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
- *   records               with history on, every vr_terrain_edit, _brush, _texture, _noise, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
+ *   records               with history on, every vr_terrain_edit, _brush, _texture, _noise, _path, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
  *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
  *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
  *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no

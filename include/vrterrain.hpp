@@ -263,6 +263,17 @@ namespace vRenderer
             if (wholeMap) p.flags |= (uint32_t)VR_NOISE_WHOLE_MAP;
             return Check(vr_terrain_noise(m_Terrain, which, &p, dabs, n, outRect), "vr_terrain_noise");
         }
+        // vr_terrain_path: a corridor of half-width params.radius along the polyline through `points` (world x, z and a target height in
+        // stored units each) - LEVEL, CUT or FILL on the heightmap (which = 0), PAINT on the albedo (1); every texel takes its weight and
+        // its target from the nearest segment and changes once.  closed: the last point is joined to the first (sets VR_PATH_CLOSED in a
+        // copy of params).  Computed on the device, stream-ordered like Brush, nothing is synchronised, and `points` is free again when
+        // the call returns.  outRect as for Brush.
+        bool Path(int which, const vr_path_params& params, const vr_path_point* points, uint32_t n, bool closed = false, int32_t outRect[4] = nullptr)
+        {
+            vr_path_params p = params;
+            if (closed) p.flags |= (uint32_t)VR_PATH_CLOSED;
+            return Check(vr_terrain_path(m_Terrain, which, &p, points, n, outRect), "vr_terrain_path");
+        }
         // vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap (which = 0) or the albedo (1) as they are on the
         // device, into `out` - the clone tool's source; a device copy on the context's stream, nothing is synchronised.
         bool CaptureStamp(int which, int32_t x, int32_t y, int32_t w, int32_t h, vRenderer::Stamp& out)

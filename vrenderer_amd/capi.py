@@ -53,6 +53,12 @@ VR_NOISE_RIDGED = 2
 VR_NOISE_ADD = 0
 VR_NOISE_BLEND = 1
 VR_NOISE_WHOLE_MAP = 1
+VR_MAX_PATH_POINTS = 4096
+VR_PATH_LEVEL = 0
+VR_PATH_CUT = 1
+VR_PATH_FILL = 2
+VR_PATH_PAINT = 3
+VR_PATH_CLOSED = 1
 VR_STAMP_R8 = 0
 VR_STAMP_SRGBA8 = 1
 VR_STAMP_BLEND = 0
@@ -224,6 +230,18 @@ class NoiseParams(C.Structure):
                 ("fractal", C.c_int32), ("op", C.c_int32), ("channel_mask", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_int32 * 2)]
 
 
+class PathPoint(C.Structure):
+    """vr_path_point: a control point of a path - world (x, z) and the target height there in stored units, 0 .. 255 (vr_terrain_path)."""
+    _fields_ = [("x", C.c_float), ("z", C.c_float), ("height", C.c_float), ("reserved", C.c_float)]
+
+
+class PathParams(C.Structure):
+    """vr_path_params: what a path does (op, channel_mask, color), its profile (radius in world units, hardness, opacity) and
+    VR_PATH_CLOSED - vr_terrain_path."""
+    _fields_ = [("op", C.c_int32), ("channel_mask", C.c_uint32), ("radius", C.c_float), ("hardness", C.c_float), ("opacity", C.c_float),
+                ("color", C.c_float * 4), ("flags", C.c_uint32), ("reserved", C.c_int32 * 6)]
+
+
 class StampParams(C.Structure):
     """vr_stamp_params: where a stamp lands (centre, extent along its own axes, rotation about y), how it weighs (opacity, feather,
     VR_STAMP_USE_ALPHA) and what it does (s' = s * gain + offset, op, channel_mask) - vr_terrain_stamp."""
@@ -244,6 +262,7 @@ assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32 and C.sizeof(Ero
 assert C.sizeof(TextureLayer) == 64 and C.sizeof(TextureParams) == 32
 assert C.sizeof(StampParams) == 64
 assert C.sizeof(NoiseParams) == 64
+assert C.sizeof(PathPoint) == 16 and C.sizeof(PathParams) == 64
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -271,7 +290,7 @@ EXPORTS = [
     "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
     "vr_stamp_create", "vr_stamp_from_terrain", "vr_stamp_destroy", "vr_stamp_info", "vr_stamp_download", "vr_terrain_stamp",
-    "vr_terrain_noise",
+    "vr_terrain_noise", "vr_terrain_path",
 ]
 
 _lib = None
@@ -401,6 +420,7 @@ def load_library():
         "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_texture": (C.c_int, [vp, P(TextureParams), vp, vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_noise": (C.c_int, [vp, C.c_int, P(NoiseParams), vp, C.c_uint32, P(C.c_int32)]),
+        "vr_terrain_path": (C.c_int, [vp, C.c_int, P(PathParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_erode": (C.c_int, [vp, P(ErodeParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_debug_erode_config": (C.c_int, [P(C.c_int32)]),
         "vr_terrain_erode_hydraulic": (C.c_int, [vp, P(HydroParams), vp, C.c_uint32, P(C.c_int32)]),

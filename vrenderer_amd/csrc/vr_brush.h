@@ -70,6 +70,21 @@ inline void brush_span(float c, float s, int n, int32_t* lo, int32_t* hi)
 
 VR_BRUSH_FN bool brush_weight(const BrushDab& d, int i, int j, float* f);
 
+// The weight's tail, on q = (distance / radius)^2 however it was measured (a dab's disc here, a path's corridor in vr_path.h).
+// false: outside, !(q < 1); true: *f is 1 out to q <= h2, then the smoothstep of (1 - q) * k.
+VR_BRUSH_FN bool brush_falloff(float q, float h2, float k, float* f)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (!(q < 1.0f)) return false;
+    if (q <= h2) { *f = 1.0f; return true; }
+    const float t = (1.0f - q) * k;
+    const float tt = t * t, s = 3.0f - 2.0f * t;
+    *f = tt * s;
+    return true;
+}
+
 // (x, z, radius, hardness, strength) of a w0 x h0 map that spans `world_size`; the caller has checked the ranges
 inline BrushDab brush_prepare(float x, float z, float radius, float hardness, float strength, float world_size, int w0, int h0)
 {
@@ -107,12 +122,7 @@ VR_BRUSH_FN bool brush_weight(const BrushDab& d, int i, int j, float* f)
     const float v = ((float)j - d.cz) * d.sz;
     const float uu = u * u, vv = v * v;
     const float q = uu + vv;
-    if (!(q < 1.0f)) return false;
-    if (q <= d.h2) { *f = 1.0f; return true; }
-    const float t = (1.0f - q) * d.k;
-    const float tt = t * t, s = 3.0f - 2.0f * t;
-    *f = tt * s;
-    return true;
+    return brush_falloff(q, d.h2, d.k, f);
 }
 
 VR_BRUSH_FN float brush_clamp(float val) { return fminf(fmaxf(val, 0.0f), 255.0f); }

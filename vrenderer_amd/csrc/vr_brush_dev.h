@@ -47,15 +47,17 @@ __device__ __forceinline__ BrushTile brush_tile(const DirtyRect& r)
 // One chunk of the list: lane d tests dab base + d's span against the tile, and the survivors are compacted IN LIST ORDER into `list`
 // (ballot + popcount prefix inside a wave, the four waves' totals through `wave_total`).  Returns how many there are, the same in
 // every lane (a scalar loop bound).  Every lane of the workgroup calls it (two barriers inside); the caller puts one more barrier
-// behind its use of `list`, in front of the next chunk.
-__device__ __forceinline__ uint32_t brush_chunk_list(const BrushDab* __restrict__ dabs, uint32_t n, uint32_t base, const BrushTile& t,
+// behind its use of `list`, in front of the next chunk.  The element is a BrushDab or anything else that carries a span [x0, x1) x
+// [y0, y1) (vr_path.h's PathSeg): there is the one walk.
+template <class Elem>
+__device__ __forceinline__ uint32_t brush_chunk_list(const Elem* __restrict__ dabs, uint32_t n, uint32_t base, const BrushTile& t,
                                                      uint16_t (&list)[kBrushChunk], uint32_t (&wave_total)[4])
 {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t d = base + (uint32_t)tid;
     bool hit = false;
     if (d < n) {
-        const BrushDab& b = dabs[d];
+        const Elem& b = dabs[d];
         hit = b.x0 < t.tx1 && b.x1 > t.tx0 && b.y0 < t.ty1 && b.y1 > t.ty0;
     }
     const unsigned long long m = __ballot(hit);

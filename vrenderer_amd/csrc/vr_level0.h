@@ -1,5 +1,5 @@
 // The host's call frame of every entry point that writes level 0 of a terrain map on the device (edit, brush, both erosions, texture,
-// stamp, noise), behind the entry point's own argument checks.  The ordering rules live here and nowhere else: a refusal comes before
+// stamp, noise, path), behind the entry point's own argument checks.  The ordering rules live here and nowhere else: a refusal comes before
 // any effect, the history capture is first on the stream, hipGetLastError follows the launches, out_rect is zeroed past the last
 // argument refusal and filled on success only.  The kernels' side of it is vr_brush_dev.h; DESIGN.md 4aa.
 #pragma once
@@ -32,31 +32,39 @@ int vr_level0_call(vr_terrain* t, int which, const DirtyRect& dirty, int32_t out
     return rc;
 }
 
-// A stroke's or an erosion's call: the dabs checked (as a stroke of `op`) and prepared for map `which`; nothing at all where none meets
-// the map; then reserve(rectangle) - everything the launches need, before anything is launched - the one wait on the host, the pinned
-// list, and as the write the upload, launch(stream, rectangle, count) and order_side_end of the brush's buffers, whose
-// order_side_idle the next call takes.
+// A call whose kernel walks a prepared list - dabs, or a path's segments (vr_path.h) - that travels in the terrain's brush list buffers:
+// `count` elements at `prepared`, of BrushDab's size, prepared on the host for map `which`, and the hull `dirty` of their spans.
+// Nothing at all where the list is empty; then reserve(rectangle) - everything the launches need, before anything is launched - the
+// one wait on the host, the pinned list, and as the write the upload, launch(stream, rectangle, count) and order_side_end of the
+// brush's buffers, whose order_side_idle the next call takes.
+template <class Elem, class Reserve, class Launch>
+int vr_list_call(vr_terrain* t, int which, const DirtyRect& dirty, const Elem* prepared, uint32_t count, int32_t out_rect[4], Reserve&& reserve, Launch&& launch)
+{
+    static_assert(sizeof(Elem) == sizeof(BrushDab), "the list travels in h_brush_dabs / d_brush_dabs");
+    level0_out_rect(out_rect, DirtyRect());
+    if (count == 0) return VR_OK;                                  // n == 0, or every element misses the map: nothing is launched
+
+    VR_HIP(hipSetDevice(t->ctx->device));
+    { const int rc = reserve(dirty); if (rc) return rc; }
+    // the one wait on the host: only where the previous stroke, erosion or path has not been consumed yet
+    { const int rc = vr_brush_consumed(t); if (rc) return rc; }
+    memcpy(t->h_brush_dabs, prepared, (size_t)count * sizeof(BrushDab));
+    return vr_level0_call(t, which, dirty, out_rect, [&](hipStream_t s) -> int {
+        VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)count * sizeof(BrushDab), hipMemcpyHostToDevice, s));
+        { const int lrc = launch(s, dirty, count); if (lrc) return lrc; }
+        VR_HIP(hipGetLastError());
+        return order_side_end(t->ord_brush, VrOrderOps(), s);
+    });
+}
+
+// A stroke's or an erosion's call: the dabs checked (as a stroke of `op`) and prepared for map `which`, then vr_list_call.
 template <class Reserve, class Launch>
 int vr_brush_call(vr_terrain* t, int which, const vr_brush_dab* dabs, uint32_t n, int op, int32_t out_rect[4], Reserve&& reserve, Launch&& launch)
 {
     { const int rc = vr_brush_check_dabs(dabs, n, op); if (rc) return rc; }
     const DirtyRect dirty = vr_brush_prepare_dabs(t, vr_terrain_map(t, which), dabs, n);
     const std::vector<BrushDab>& prepared = t->brush_prepared;
-    level0_out_rect(out_rect, DirtyRect());
-    if (prepared.empty()) return VR_OK;                            // n == 0, or every dab misses the map: nothing is launched
-
-    VR_HIP(hipSetDevice(t->ctx->device));
-    { const int rc = reserve(dirty); if (rc) return rc; }
-    // the one wait on the host: only where the previous stroke or erosion has not been consumed yet
-    { const int rc = vr_brush_consumed(t); if (rc) return rc; }
-    const uint32_t nd = (uint32_t)prepared.size();
-    memcpy(t->h_brush_dabs, prepared.data(), (size_t)nd * sizeof(BrushDab));
-    return vr_level0_call(t, which, dirty, out_rect, [&](hipStream_t s) -> int {
-        VR_HIP(hipMemcpyAsync(t->d_brush_dabs, t->h_brush_dabs, (size_t)nd * sizeof(BrushDab), hipMemcpyHostToDevice, s));
-        { const int lrc = launch(s, dirty, nd); if (lrc) return lrc; }
-        VR_HIP(hipGetLastError());
-        return order_side_end(t->ord_brush, VrOrderOps(), s);
-    });
+    return vr_list_call(t, which, dirty, prepared.data(), (uint32_t)prepared.size(), out_rect, reserve, launch);
 }
 
 // An operation under the erosions' mask of a dab list (strength is an opacity), or - `whole` - over the whole map with no list, when

@@ -691,6 +691,33 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_noise(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_noise")
         return tuple(int(v) for v in rect)
 
+    def Path(self, which, points, radius, hardness=0.0, opacity=1.0, op="level", color=None, channels=None, closed=False):
+        """vr_terrain_path: a corridor of half-width `radius` world units along the polyline through `points`, on level 0 of the
+        heightmap ('height' / 0: op 'level', 'cut', 'fill' or capi.VR_PATH_*) or the albedo ('albedo' / 1: 'paint'), computed on the
+        device; stream-ordered, nothing is synchronised.  `points`: (n, 3) float32 rows of (x, z, height) - world units and the target
+        in stored units, 0 .. 255 - or (n, 4) rows laid out as the C struct vr_path_point, or (n, 2) rows of (x, z) for 'paint'; the
+        array may be reused as soon as the call returns.  Every texel takes its weight - a dab's profile of `hardness` across the
+        path, times `opacity` - and its target from the nearest segment, and changes once.  `color`: PAINT's four stored bytes'
+        worth; `channels`: the channel mask (default: 1 for the heightmap, 0xF for the albedo); closed=True joins the last point to
+        the first.  Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when the path misses the map."""
+        idx = {"height": 0, "albedo": 1}.get(which, which)
+        a = np.asarray(points, np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 3)
+        assert a.ndim == 2 and a.shape[1] in (2, 3, 4)
+        if a.shape[1] != 4:
+            full = np.zeros((a.shape[0], 4), np.float32)
+            full[:, :a.shape[1]] = a
+            a = full
+        a = np.ascontiguousarray(a)
+        p = capi.PathParams(op={"level": capi.VR_PATH_LEVEL, "cut": capi.VR_PATH_CUT, "fill": capi.VR_PATH_FILL, "paint": capi.VR_PATH_PAINT}.get(op, op),
+                            channel_mask=int(channels) if channels is not None else (1 if idx == 0 else 0xF), radius=float(radius), hardness=float(hardness),
+                            opacity=float(opacity), flags=capi.VR_PATH_CLOSED if closed else 0)
+        p.color[:] = [float(c) for c in (color if color is not None else (0.0, 0.0, 0.0, 0.0))]
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_path(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_path")
+        return tuple(int(v) for v in rect)
+
     def CaptureStamp(self, which, x, y, w, h):
         """vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap ('height' / 0) or the albedo ('albedo' / 1) as
         they are on the device, as a Stamp - the clone tool's source; a device copy on the context's stream, nothing is synchronised."""
