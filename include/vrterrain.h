@@ -189,7 +189,7 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
  * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
  * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
- * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _noise / _path / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _noise / _path / _region / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
  * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
  * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
  * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
@@ -437,6 +437,50 @@ typedef struct vr_path_params { int32_t op; uint32_t channel_mask; float radius,
                                 float color[4]; uint32_t flags; int32_t reserved[6]; } vr_path_params; /* 64 B */
 VR_API int vr_terrain_path(vr_terrain* t, int which, const vr_path_params* p,
                            const vr_path_point* points, uint32_t n, int32_t out_rect[4]);
+/* A region on level 0 of the heightmap (which = 0: LEVEL, CUT, FILL, RAISE) or the albedo (1: PAINT) - a lake bed, a plateau, a
+ * building pad, a quarry, a field, a painted zone: the inside of a polygon, with a feathered outline, computed on the device from the
+ * map as it is there and followed by the refresh vr_terrain_edit does: afterwards the terrain is the one vr_terrain_create builds from
+ * the map with the region in it.  `points` are world (x, z), as for dabs and path points.  They form num_contours closed contours of
+ * contour_counts[c] consecutive points each (at least 3; the counts sum to n; the last point of a contour is joined to its first);
+ * contour_counts == NULL with num_contours == 0 is one contour of all n points.  A texel is inside by the even-odd rule over all edges
+ * of all contours: a second contour inside the first is a hole (an island in a lake), a bow-tie has two lobes.  A vertex or an edge
+ * exactly on a row of texel centres is decided by a half-open rule, so neighbouring polygons that share an edge share no texel.
+ * The weight f of a texel: with q = (distance to the nearest edge / feather)^2 and f0 the dab's smoothstep of hardness 0 - 1 at the
+ * outline, 0 at q = 1 -
+ *   default                     inside f = 1; outside f = f0 where q < 1: the polygon plus a soft skirt, C1 across the outline
+ *   VR_REGION_FEATHER_INSIDE    inside f = 1 - f0 where q < 1, else 1; outside is not written: the feather stays within the outline
+ *   feather == 0                inside f = 1; outside is not written: a hard edge, and no distance is evaluated at all
+ * and with a = f * opacity the texel's value (the stored byte; four for the albedo) changes ONCE:
+ *   VR_REGION_LEVEL  value += a * (target - value)
+ *   VR_REGION_CUT    value += a * (min(value, target) - value)       only lowers: a lake bed, a quarry
+ *   VR_REGION_FILL   value += a * (max(value, target) - value)       only raises: a pad, a plateau
+ *   VR_REGION_RAISE  value += a * target                             target a signed delta in [-255, 255]
+ *   VR_REGION_PAINT  per channel c of channel_mask (as vr_terrain_brush's PAINT): value_c += a * (color[c] - value_c)
+ * clamped to [0, 255] and rounded to the nearest byte once.  The four height ops need which = 0 and channel_mask == 1, PAINT which = 1.
+ * A texel is a function of its own byte, its position and the call alone.  The arithmetic is defined bit for bit in
+ * vrenderer_amd/csrc/vr_region.h, without a division, a square root or trigonometry on the device.
+ * out_rect, the stream order and what the host waits for are vr_terrain_path's: the call synchronises nothing, is ordered against
+ * the strokes, erosions, paths and the other writers of the terrain, and `points` and `contour_counts` are host memory that may be
+ * reused as soon as the call returns.  With history on, one call is one record.  n == 0, or a region that misses the map, is VR_OK
+ * and launches nothing.
+ * Not here: a sloped target plane; per-vertex heights; non-zero winding (even-odd is the one rule); curves (the caller tessellates -
+ * VR_MAX_REGION_POINTS points fit a call); both maps in one call (a pad and its paint are two calls with the same points).
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the terrain untouched: NULL t or p; NULL points with
+ * n > 0; n > VR_MAX_REGION_POINTS; `which` not 0 or 1; an unknown op, or one that does not fit the map; unknown flag bits; a contour
+ * of fewer than 3 points, counts that do not sum to n, num_contours > 0 with NULL counts, or no counts with 0 < n < 3; a NaN or an
+ * infinity anywhere; feather < 0; opacity outside [0, 1]; target outside [0, 255] ([-255, 255] for RAISE); a color outside [0, 255];
+ * a channel_mask of 0 or above 15, or other than 1 on the heightmap; a non-zero reserved word.  The memory a call needs is reserved
+ * before anything is launched (VR_ERR_OUT_OF_MEMORY leaves the terrain as it was).
+ * Timing: as for vr_terrain_edit; the region kernel itself is untimed. */
+#define VR_MAX_REGION_POINTS 4096
+enum { VR_REGION_LEVEL = 0, VR_REGION_CUT = 1, VR_REGION_FILL = 2, VR_REGION_RAISE = 3, VR_REGION_PAINT = 4 };
+enum { VR_REGION_FEATHER_INSIDE = 1 };
+typedef struct vr_region_point  { float x, z; } vr_region_point;                       /*  8 B */
+typedef struct vr_region_params { int32_t op; uint32_t channel_mask; float target, feather, opacity;
+                                  float color[4]; uint32_t flags; int32_t reserved[6]; } vr_region_params; /* 64 B */
+VR_API int vr_terrain_region(vr_terrain* t, int which, const vr_region_params* p,
+                             const vr_region_point* points, uint32_t n,
+                             const uint32_t* contour_counts, uint32_t num_contours, int32_t out_rect[4]);
 /* Stamps: a prepared patch - a mountain, a crater, a scanned tile, an albedo decal - kept in device memory and set into level 0 of a
  * map at a position, size and angle, with a blend rule.  A vr_stamp is w x h texels, 1 .. 4096 per side, of one of the maps' formats:
  * VR_STAMP_R8 (the heightmap's, = which 0) or VR_STAMP_SRGBA8 (the albedo's, = which 1).  It belongs to the context it was created
@@ -570,13 +614,13 @@ VR_API int vr_debug_hydro_config(int32_t out[4]);
 /* measurement helper, process-wide: later calls advance `sweeps` (1 .. the build's figure; 0 = that figure again) sweeps per
  * launch.  The bytes are the same; only the number of launches changes.  VR_ERR_INVALID_ARGUMENT outside that range. */
 VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps);
-/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_noise, vr_terrain_path, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
+/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_noise, vr_terrain_path, vr_terrain_region, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
  * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
  *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
  *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
  *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
  *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
- *   records               with history on, every vr_terrain_edit, _brush, _texture, _noise, _path, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
+ *   records               with history on, every vr_terrain_edit, _brush, _texture, _noise, _path, _region, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
  *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
  *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
  *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no

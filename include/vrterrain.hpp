@@ -274,6 +274,16 @@ namespace vRenderer
             if (closed) p.flags |= (uint32_t)VR_PATH_CLOSED;
             return Check(vr_terrain_path(m_Terrain, which, &p, points, n, outRect), "vr_terrain_path");
         }
+        // vr_terrain_region: the inside of the polygon through `points` (world x, z; contourCounts[c] points per closed contour, or none
+        // for one contour of all n; even-odd, so a contour within another is a hole) - LEVEL, CUT, FILL or RAISE on the heightmap
+        // (which = 0), PAINT on the albedo (1), with a feather of params.feather world units outside the outline, or inside it with
+        // VR_REGION_FEATHER_INSIDE.  Computed on the device, stream-ordered like Path, nothing is synchronised, and `points` is free
+        // again when the call returns.  outRect as for Brush.
+        bool Region(int which, const vr_region_params& params, const vr_region_point* points, uint32_t n, const uint32_t* contourCounts = nullptr,
+                    uint32_t numContours = 0, int32_t outRect[4] = nullptr)
+        {
+            return Check(vr_terrain_region(m_Terrain, which, &params, points, n, contourCounts, numContours, outRect), "vr_terrain_region");
+        }
         // vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap (which = 0) or the albedo (1) as they are on the
         // device, into `out` - the clone tool's source; a device copy on the context's stream, nothing is synchronised.
         bool CaptureStamp(int which, int32_t x, int32_t y, int32_t w, int32_t h, vRenderer::Stamp& out)

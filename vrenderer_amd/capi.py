@@ -59,6 +59,13 @@ VR_PATH_CUT = 1
 VR_PATH_FILL = 2
 VR_PATH_PAINT = 3
 VR_PATH_CLOSED = 1
+VR_MAX_REGION_POINTS = 4096
+VR_REGION_LEVEL = 0
+VR_REGION_CUT = 1
+VR_REGION_FILL = 2
+VR_REGION_RAISE = 3
+VR_REGION_PAINT = 4
+VR_REGION_FEATHER_INSIDE = 1
 VR_STAMP_R8 = 0
 VR_STAMP_SRGBA8 = 1
 VR_STAMP_BLEND = 0
@@ -242,6 +249,18 @@ class PathParams(C.Structure):
                 ("color", C.c_float * 4), ("flags", C.c_uint32), ("reserved", C.c_int32 * 6)]
 
 
+class RegionPoint(C.Structure):
+    """vr_region_point: a vertex of a region's contour - world (x, z) (vr_terrain_region)."""
+    _fields_ = [("x", C.c_float), ("z", C.c_float)]
+
+
+class RegionParams(C.Structure):
+    """vr_region_params: what a region does (op, channel_mask, target, color), its outline (feather in world units,
+    VR_REGION_FEATHER_INSIDE) and its opacity - vr_terrain_region."""
+    _fields_ = [("op", C.c_int32), ("channel_mask", C.c_uint32), ("target", C.c_float), ("feather", C.c_float), ("opacity", C.c_float),
+                ("color", C.c_float * 4), ("flags", C.c_uint32), ("reserved", C.c_int32 * 6)]
+
+
 class StampParams(C.Structure):
     """vr_stamp_params: where a stamp lands (centre, extent along its own axes, rotation about y), how it weighs (opacity, feather,
     VR_STAMP_USE_ALPHA) and what it does (s' = s * gain + offset, op, channel_mask) - vr_terrain_stamp."""
@@ -263,6 +282,7 @@ assert C.sizeof(TextureLayer) == 64 and C.sizeof(TextureParams) == 32
 assert C.sizeof(StampParams) == 64
 assert C.sizeof(NoiseParams) == 64
 assert C.sizeof(PathPoint) == 16 and C.sizeof(PathParams) == 64
+assert C.sizeof(RegionPoint) == 8 and C.sizeof(RegionParams) == 64
 assert C.sizeof(Instance) == 112
 assert C.sizeof(Light) == 64
 assert C.sizeof(FrameDesc) == 160
@@ -290,7 +310,7 @@ EXPORTS = [
     "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
     "vr_stamp_create", "vr_stamp_from_terrain", "vr_stamp_destroy", "vr_stamp_info", "vr_stamp_download", "vr_terrain_stamp",
-    "vr_terrain_noise", "vr_terrain_path",
+    "vr_terrain_noise", "vr_terrain_path", "vr_terrain_region",
 ]
 
 _lib = None
@@ -421,6 +441,7 @@ def load_library():
         "vr_terrain_texture": (C.c_int, [vp, P(TextureParams), vp, vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_noise": (C.c_int, [vp, C.c_int, P(NoiseParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_path": (C.c_int, [vp, C.c_int, P(PathParams), vp, C.c_uint32, P(C.c_int32)]),
+        "vr_terrain_region": (C.c_int, [vp, C.c_int, P(RegionParams), vp, C.c_uint32, P(C.c_uint32), C.c_uint32, P(C.c_int32)]),
         "vr_terrain_erode": (C.c_int, [vp, P(ErodeParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_debug_erode_config": (C.c_int, [P(C.c_int32)]),
         "vr_terrain_erode_hydraulic": (C.c_int, [vp, P(HydroParams), vp, C.c_uint32, P(C.c_int32)]),

@@ -20,6 +20,7 @@
 #include "vr_light_domain.h"
 #include "vr_order.h"
 #include "vr_path.h"
+#include "vr_region.h"
 #include "vr_scratch.h"
 #include "vr_tonemap_plan.h"
 
@@ -387,6 +388,8 @@ struct vr_terrain {
     BrushDab* h_brush_dabs = nullptr; BrushDab* d_brush_dabs = nullptr;
     std::vector<PathPoint> path_points;         // vr_terrain_path: the caller's points and the segments prepared from them (vr_path.h), host
     std::vector<PathSeg> path_prepared;         // memory that keeps its room from call to call; the segments travel in the dab buffers
+    std::vector<RegionVertex> region_verts;     // vr_terrain_region: the vertices and the edges prepared from them (vr_region.h), likewise
+    std::vector<RegionEdge> region_prepared;
     void* d_brush_snap = nullptr; size_t brush_snap_bytes = 0;
     // Erosion, thermal and hydraulic (vr_erode.hip): one block of fp32 planes - the mask and two sets of the model's state fields,
     // three planes or seven - of the largest call so far.  Its one reader is the erosion's kernels, which run in front of

@@ -1,5 +1,5 @@
 // The host's call frame of every entry point that writes level 0 of a terrain map on the device (edit, brush, both erosions, texture,
-// stamp, noise, path), behind the entry point's own argument checks.  The ordering rules live here and nowhere else: a refusal comes before
+// stamp, noise, path, region), behind the entry point's own argument checks.  The ordering rules live here and nowhere else: a refusal comes before
 // any effect, the history capture is first on the stream, hipGetLastError follows the launches, out_rect is zeroed past the last
 // argument refusal and filled on success only.  The kernels' side of it is vr_brush_dev.h; DESIGN.md 4aa.
 #pragma once
@@ -32,7 +32,7 @@ int vr_level0_call(vr_terrain* t, int which, const DirtyRect& dirty, int32_t out
     return rc;
 }
 
-// A call whose kernel walks a prepared list - dabs, or a path's segments (vr_path.h) - that travels in the terrain's brush list buffers:
+// A call whose kernel walks a prepared list - dabs, a path's segments (vr_path.h) or a region's edges (vr_region.h) - that travels in the terrain's brush list buffers:
 // `count` elements at `prepared`, of BrushDab's size, prepared on the host for map `which`, and the hull `dirty` of their spans.
 // Nothing at all where the list is empty; then reserve(rectangle) - everything the launches need, before anything is launched - the
 // one wait on the host, the pinned list, and as the write the upload, launch(stream, rectangle, count) and order_side_end of the

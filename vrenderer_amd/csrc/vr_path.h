@@ -186,25 +186,41 @@ inline void path_prepare(const PathPoint* pts, uint32_t n, bool closed, const Pa
 }
 
 // ---- per texel -----------------------------------------------------------------------------------------------------------
-// texel (i, j) against segment s: q = (distance / radius)^2 and the parameter t of the nearest point, clamped to [0, 1]
-VR_PATH_FN void path_texel(const PathSeg& s, const PathConst& k, int i, int j, float* q, float* t)
+// The chain in its two halves, on plain numbers, so that a region's edge (vr_region.h) runs the same operations: the head gives p,
+// from a to the centre of texel (i, j) in world units; the tail q and t of the point of a + t * d nearest to p.
+VR_PATH_FN void path_offset(float ax, float az, float wx, float wz, int i, int j, float* px, float* pz)
 {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    const float ox = (float)i - s.ax, oz = (float)j - s.az;
-    const float px = ox * k.wx, pz = oz * k.wz;
-    const float m0 = px * s.dx, m1 = pz * s.dz;
+    const float ox = (float)i - ax, oz = (float)j - az;
+    *px = ox * wx;
+    *pz = oz * wz;
+}
+VR_PATH_FN void path_nearest(float px, float pz, float dx, float dz, float inv_len2, float inv_r2, float* q, float* t)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float m0 = px * dx, m1 = pz * dz;
     const float dot = m0 + m1;
-    const float t0 = dot * s.inv_len2;
+    const float t0 = dot * inv_len2;
     const float t1 = t0 < 0.0f ? 0.0f : t0;
     const float tc = t1 > 1.0f ? 1.0f : t1;
-    const float gx = tc * s.dx, gz = tc * s.dz;
+    const float gx = tc * dx, gz = tc * dz;
     const float ex = px - gx, ez = pz - gz;
     const float xx = ex * ex, zz = ez * ez;
     const float d2 = xx + zz;
-    *q = d2 * k.inv_r2;
+    *q = d2 * inv_r2;
     *t = tc;
+}
+
+// texel (i, j) against segment s: q = (distance / radius)^2 and the parameter t of the nearest point, clamped to [0, 1]
+VR_PATH_FN void path_texel(const PathSeg& s, const PathConst& k, int i, int j, float* q, float* t)
+{
+    float px, pz;
+    path_offset(s.ax, s.az, k.wx, k.wz, i, j, &px, &pz);
+    path_nearest(px, pz, s.dx, s.dz, s.inv_len2, k.inv_r2, q, t);
 }
 
 // the target of the winner

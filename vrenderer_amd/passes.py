@@ -718,6 +718,28 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_path(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_path")
         return tuple(int(v) for v in rect)
 
+    def Region(self, which, points, op="level", target=0.0, feather=0.0, opacity=1.0, color=None, channels=None, feather_inside=False, contours=None):
+        """vr_terrain_region: the inside of the polygon through `points`, on level 0 of the heightmap ('height' / 0: op 'level', 'cut',
+        'fill', 'raise' or capi.VR_REGION_*) or the albedo ('albedo' / 1: 'paint'), computed on the device; stream-ordered, nothing is
+        synchronised.  `points`: (n, 2) float32 rows of world (x, z); the array may be reused as soon as the call returns.  `contours`:
+        the number of points of each closed contour, in order (default: one contour of all points); inside is the even-odd rule, so a
+        contour within another is a hole.  `target`: the level in stored units, 0 .. 255 - for 'raise' a signed delta; `feather`: the
+        width in world units of the soft skirt outside the outline - with feather_inside=True of the ramp inside it - 0 for a hard
+        edge; `color`: PAINT's four stored bytes' worth; `channels`: the channel mask (default: 1 for the heightmap, 0xF for the
+        albedo).  Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when the region misses the map."""
+        idx = {"height": 0, "albedo": 1}.get(which, which)
+        a = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 2))
+        p = capi.RegionParams(op={"level": capi.VR_REGION_LEVEL, "cut": capi.VR_REGION_CUT, "fill": capi.VR_REGION_FILL, "raise": capi.VR_REGION_RAISE,
+                                  "paint": capi.VR_REGION_PAINT}.get(op, op),
+                              channel_mask=int(channels) if channels is not None else (1 if idx == 0 else 0xF), target=float(target), feather=float(feather),
+                              opacity=float(opacity), flags=capi.VR_REGION_FEATHER_INSIDE if feather_inside else 0)
+        p.color[:] = [float(c) for c in (color if color is not None else (0.0, 0.0, 0.0, 0.0))]
+        counts = (C.c_uint32 * len(contours))(*[int(c) for c in contours]) if contours is not None and len(contours) else None
+        rect = (C.c_int32 * 4)()
+        check(self.ctx.lib.vr_terrain_region(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], counts, len(counts) if counts is not None else 0,
+                                             rect), "vr_terrain_region")
+        return tuple(int(v) for v in rect)
+
     def CaptureStamp(self, which, x, y, w, h):
         """vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap ('height' / 0) or the albedo ('albedo' / 1) as
         they are on the device, as a Stamp - the clone tool's source; a device copy on the context's stream, nothing is synchronised."""
