@@ -8,8 +8,10 @@ import numpy as np
 
 from tests import erode_model as em
 from tests import hydro_model as hm
+from tests.level0_common import assert_bytes, level0
 
 F = np.float32
+WORLD = 64.0                                                         # of the CPU tests' seeded cases
 FIELDS = {"thermal": ("h",), "hydraulic": ("h", "d", "s")}
 SENSITIVE = 30                                                       # "at least 30 changed", as everywhere in this suite
 # The swap every case is held to before it runs.  (-1,0) and (1,0) stand side by side in the thermal order: exchanging them changes one
@@ -38,6 +40,29 @@ def state(kind, texels, dabs, world, iterations, params, neighbours=None, **wron
         planes, settled = [h, d, s], h + s
     stored = np.floor(np.minimum(np.maximum(settled, F(0)), F(255)) + F(0.5)).astype(np.uint8)
     return dict(rect=tuple(int(v) for v in rect), mask=m, planes=planes, settled=settled, bytes=np.where(m > F(0), stored, texels).astype(np.uint8))
+
+
+ITER = 20
+_MODEL = {}
+
+
+def model(kind, texels, dabs, world, iterations, params):
+    """The model's state, computed once per distinct call and left unchanged."""
+    key = (kind, texels.tobytes(), texels.shape, np.asarray(dabs, F).tobytes(), world, iterations, repr(params))
+    if key not in _MODEL:
+        _MODEL[key] = state(kind, texels, dabs, world, iterations, params)
+    return _MODEL[key]
+
+
+def assert_state(tp, want, what):
+    """The planes the last call left are the model's, bit for bit, inside the model's rectangle; level 0 is the model's bytes."""
+    rect, mask, planes = tp.ErosionState()
+    assert rect == want["rect"], (what, rect, want["rect"])
+    assert len(planes) == len(want["planes"]), (what, len(planes))
+    assert_bits(mask, crop(want["mask"], rect), f"{what}: the mask plane")
+    for name, got, ref in zip("hds", planes, want["planes"]):
+        assert_bits(got, crop(ref, rect), f"{what}: {name}")
+    assert_bytes(level0(tp, "height"), want["bytes"], f"{what}: level 0")
 
 
 def wrong_variants(kind, params):
@@ -108,21 +133,34 @@ PARAMS = {"thermal": THERMAL, "hydraulic": HYDRO}
 
 
 def dab(shape, world, tx, ty, r_tex, hardness, strength):
-    """tests/test_terrain_brush_gpu.py's: centre at texel coordinate (tx, ty), radius r_tex texels of the map's width."""
+    """tests/level0_common.py's: centre at texel coordinate (tx, ty), radius r_tex texels of the map's width."""
     h, w = shape[:2]
     return [(tx + 0.5) / w * world - world / 2, (ty + 0.5) / h * world - world / 2, r_tex * world / w, hardness, strength]
 
 
 def five_dabs(shape, world):
-    """tests/test_terrain_brush_gpu.py's five_dabs with opacities for strengths."""
+    """tests/level0_common.py's five_dabs with opacities for strengths."""
     h, w = shape[:2]
     return np.float32([dab(shape, world, 0.3 * w, 0.4 * h, 12.0, 0.0, 0.6), dab(shape, world, 0.7 * w + 0.37, 0.6 * h + 0.21, 5.5, 0.7, 0.35),
                        dab(shape, world, -0.5, -0.5, 6.0, 0.0, 0.8), dab(shape, world, w + 2.0, 0.5 * h, 4.5, 0.7, 0.5),
                        dab(shape, world, 10.1, 7.2, 0.4, 0.0, 1.0)])
 
 
-def full_mask(world):
-    return np.float32([[0.0, 0.0, 4.0 * world, 0.5, 1.0]])          # mask 1 on every texel
+def full_mask(world=WORLD):
+    return np.float32([[0.0, 0.0, 4.0 * world, 0.5, 1.0]])          # one hard-centred dab far larger than the map: mask 1 everywhere
+
+
+def seeded_dabs(rng, h, w, n=12):
+    """Centres inside and outside the map, radii from under a texel to a third of the map and more, hardness 0 and 0.7."""
+    dabs = np.zeros((n, 5), np.float32)
+    dabs[:, 0:2] = rng.uniform(-0.7 * WORLD, 0.7 * WORLD, (n, 2))
+    dabs[:, 2] = np.exp(rng.uniform(np.log(0.3), np.log(25.0), n)) * WORLD / max(w, h)
+    dabs[:, 3] = rng.choice([0.0, 0.7], n)
+    dabs[:, 4] = rng.uniform(0.0, 1.0, n)
+    dabs[0, 0:2] = (-0.6 * WORLD, 0.1 * WORLD)                       # a centre outside the map that still reaches it
+    dabs[0, 2] = 0.25 * WORLD
+    dabs[1, 2] = 0.4 * WORLD / max(w, h)                             # a sub-texel radius
+    return dabs
 
 
 def soft_mask(world):
@@ -130,7 +168,7 @@ def soft_mask(world):
 
 
 def scene_maps(synth):
-    """name -> (heightmap, world size) of tests/test_terrain_edit_gpu.py's scenes; synth(size): the synthetic heightmap."""
+    """name -> (heightmap, world size) of tests/level0_common.py's scenes; synth(size): the synthetic heightmap."""
     return {"fast64": (synth(64), 64.0), "odd": (np.ascontiguousarray(synth(67)[:45, :67]), 64.0), "multi": (synth(128), 128.0)}
 
 

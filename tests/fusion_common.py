@@ -6,7 +6,7 @@ import contextlib
 import numpy as np
 
 import vrenderer_amd as vr
-from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, packed_hdr, params
+from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, flythrough_camera, packed_hdr, params, scaled_camera
 
 FUSED, LIGHTING = "k_raster (fused with lighting)", "k_deferred"
 PLANES = ("depth", "diffuse", "specular", "normals", "emissive")
@@ -158,3 +158,70 @@ def lit_pair(ctx, tp, v, w, h, lights, part=None):
         return want, render_lit(ctx, tp, v, w, h, lights, part, rt=rt)
     finally:
         rt.close()
+
+
+def views(w, h):
+    """Two flythrough views (terrain under a band of sky) and the top-down camera (no sky at all)."""
+    return [vr.make_view(*scaled_camera(flythrough_camera(0), 256), w, h), vr.make_view(*scaled_camera(CAMERAS[4], 256), w, h),
+            vr.make_view(*scaled_camera(flythrough_camera(5), 256), w, h)]
+
+
+def timed(ctx, fn):
+    ctx.timing_enable(2)
+    try:
+        out = fn()
+        ctx.synchronize()
+        return out, ctx.timing_collect()
+    finally:
+        ctx.timing_enable(0)
+
+
+def capture(rt, hdr):
+    f = {p: rt.download(p).copy() for p in PLANES}
+    f.update(hdr=hdr.download().copy(), census=rt.region_census(), emissive_known_zero=rt.plane_known_zero("emissive"))
+    return f
+
+
+class LazyScene:
+    """Fresh targets and a Frame on the fixture's terrain, with the option set to `lazy`."""
+
+    def __init__(self, fx, lazy, w, h):
+        self.ctx, self.tp, self.w, self.h = fx["ctx"], fx["tp"], w, h
+        self.ctx.set_gbuffer_lazy(lazy)
+        self.rt = vr.RenderTargets(self.ctx).Init(w, h)
+        self.hdr, self.hdr2 = vr.HdrImage(self.ctx, w, h), vr.HdrImage(self.ctx, w, h)
+        self.rp = vr.default_render_params(400.0, assume_cleared=1)
+        self.lights = [vr.reference_sun()]
+        self.fr = vr.Frame(self.tp, self.rt, self.rp, self.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
+
+    def submit(self, v, fused=True):
+        """One frame; returns the names of the stamped kernels it queued."""
+        _, ran = timed(self.ctx, lambda: self.fr.submit(v, self.hdr))
+        assert (FUSED in ran) == fused and (LIGHTING in ran) != fused, sorted(ran)
+        return ran
+
+    def close(self):
+        self.ctx.set_gbuffer_lazy(1)
+        for o in (self.hdr, self.hdr2, self.rt):
+            o.close()
+
+
+def both(fx, w, h, script):
+    """script(scene, lazy) -> dict of results, with the option off and on; the two must agree bit for bit."""
+    outs = []
+    for lazy in (0, 1):
+        sc = LazyScene(fx, lazy, w, h)
+        try:
+            outs.append(script(sc, lazy))
+        finally:
+            sc.close()
+    want, got = outs
+    assert want.keys() == got.keys()
+    for k in want:
+        if isinstance(want[k], dict) and "depth" in want[k]:
+            assert_same_frame(want[k], got[k], f"{w}x{h}, {k}", [q for q in FRAME_KEYS + ("hdr2",) if q in want[k]])
+        elif isinstance(want[k], np.ndarray):
+            assert_same_bits(want[k], got[k], f"{w}x{h}, {k}")
+        else:
+            assert want[k] == got[k], f"{w}x{h}, {k}: {want[k]} != {got[k]}"
+    return want, got

@@ -20,3 +20,23 @@ def run_host_check(exe, *args, timeout=120, expect=" 0 failures", stderr_tail=20
     r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0 and expect in r.stdout, r.stdout[-4000:] + r.stderr[-stderr_tail:]
     return r
+
+
+def build_host_example(tmpdir):
+    exe = os.path.join(str(tmpdir), "frame_example")
+    lib_dir = os.path.join(ROOT, "vrenderer_amd", "lib")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "host", "frame_example.cpp"), "-o", exe,
+           "-L", lib_dir, "-lvrterrain", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    return exe
+
+
+def build_allgather_example(tmpdir):
+    exe = os.path.join(str(tmpdir), "frame_allgather_example")
+    lib_dir = os.path.join(ROOT, "vrenderer_amd", "lib")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
+           os.path.join(ROOT, "tests", "host", "frame_allgather_example.cpp"), "-o", exe,
+           "-L", lib_dir, "-lvrterrain", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-lrccl", "-lpthread"]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    return exe

@@ -12,7 +12,7 @@ import vrenderer_amd as vr
 from vrenderer_amd import capi
 from vrenderer_amd import partition as pt
 from tests.common import DEFAULT_EYE, DEFAULT_TARGET
-from tests.host_check import build_host_check, run_host_check
+from tests.host_check import build_allgather_example, build_host_example, build_host_check, run_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -207,19 +207,9 @@ def test_pack_detile_roundtrip_numpy():
         assert np.array_equal(pt.detile(gathered, w, h, world), frame)
 
 
-def _build_host_example(tmpdir):
-    exe = os.path.join(str(tmpdir), "frame_example")
-    lib_dir = os.path.join(ROOT, "vrenderer_amd", "lib")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "host", "frame_example.cpp"), "-o", exe,
-           "-L", lib_dir, "-lvrterrain", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return exe
-
-
 def test_cpp_host_example_compiles_links_and_fails_soft_without_gpu(product_lib, tmp_path):
     """The header is usable from C++ and the library links; without a device the example reports it."""
-    exe = _build_host_example(tmp_path)
+    exe = build_host_example(tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     if _has_gpu(product_lib):
         assert r.returncode == 0, r.stdout + r.stderr
@@ -318,20 +308,10 @@ def test_geometry_slot_policy_matches_the_transcribed_code_and_its_invariants(tm
     run_host_check(san)
 
 
-def _build_allgather_example(tmpdir):
-    exe = os.path.join(str(tmpdir), "frame_allgather_example")
-    lib_dir = os.path.join(ROOT, "vrenderer_amd", "lib")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-           os.path.join(ROOT, "tests", "host", "frame_allgather_example.cpp"), "-o", exe,
-           "-L", lib_dir, "-lvrterrain", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-lrccl", "-lpthread"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return exe
-
-
 def test_cpp_allgather_example_compiles_and_fails_soft_without_gpu(product_lib, tmp_path):
     """The N-rank C++ host (RCCL communicator + vr_frame_allgather_ldr + vr_tonemap_allreduce_histogram) builds against
     rccl.h and the C ABI; without a device it says so."""
-    exe = _build_allgather_example(tmp_path)
+    exe = build_allgather_example(tmp_path)
     if _has_gpu(product_lib):
         pytest.skip("run by the GPU suite")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)

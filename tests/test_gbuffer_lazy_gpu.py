@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import vrenderer_amd as vr
-from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, flythrough_camera, scaled_camera
-from tests.fusion_common import FRAME_KEYS, FUSED, LIGHTING, PLANES, assert_same_bits, assert_same_frame, terrain_fixture
+from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, flythrough_camera, scaled_camera
+from tests.fusion_common import FUSED, PLANES, LazyScene, assert_same_bits, both, capture, terrain_fixture, timed, views
 
 pytestmark = pytest.mark.gpu
 PLAIN = "k_raster"
@@ -21,79 +21,12 @@ def fx(product_lib):
         yield f
 
 
-def _views(w, h):
-    """Two flythrough views (terrain under a band of sky) and the top-down camera (no sky at all)."""
-    return [vr.make_view(*scaled_camera(flythrough_camera(0), 256), w, h), vr.make_view(*scaled_camera(CAMERAS[4], 256), w, h),
-            vr.make_view(*scaled_camera(flythrough_camera(5), 256), w, h)]
-
-
-def _timed(ctx, fn):
-    ctx.timing_enable(2)
-    try:
-        out = fn()
-        ctx.synchronize()
-        return out, ctx.timing_collect()
-    finally:
-        ctx.timing_enable(0)
-
-
-def _capture(rt, hdr):
-    f = {p: rt.download(p).copy() for p in PLANES}
-    f.update(hdr=hdr.download().copy(), census=rt.region_census(), emissive_known_zero=rt.plane_known_zero("emissive"))
-    return f
-
-
-class Scene:
-    """Fresh targets and a Frame on the fixture's terrain, with the option set to `lazy`."""
-
-    def __init__(self, fx, lazy, w, h):
-        self.ctx, self.tp, self.w, self.h = fx["ctx"], fx["tp"], w, h
-        self.ctx.set_gbuffer_lazy(lazy)
-        self.rt = vr.RenderTargets(self.ctx).Init(w, h)
-        self.hdr, self.hdr2 = vr.HdrImage(self.ctx, w, h), vr.HdrImage(self.ctx, w, h)
-        self.rp = vr.default_render_params(400.0, assume_cleared=1)
-        self.lights = [vr.reference_sun()]
-        self.fr = vr.Frame(self.tp, self.rt, self.rp, self.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
-
-    def submit(self, v, fused=True):
-        """One frame; returns the names of the stamped kernels it queued."""
-        _, ran = _timed(self.ctx, lambda: self.fr.submit(v, self.hdr))
-        assert (FUSED in ran) == fused and (LIGHTING in ran) != fused, sorted(ran)
-        return ran
-
-    def close(self):
-        self.ctx.set_gbuffer_lazy(1)
-        for o in (self.hdr, self.hdr2, self.rt):
-            o.close()
-
-
-def _both(fx, w, h, script):
-    """script(scene) -> dict of results, with the option off and on; the two must agree bit for bit."""
-    outs = []
-    for lazy in (0, 1):
-        sc = Scene(fx, lazy, w, h)
-        try:
-            outs.append(script(sc, lazy))
-        finally:
-            sc.close()
-    want, got = outs
-    assert want.keys() == got.keys()
-    for k in want:
-        if isinstance(want[k], dict) and "depth" in want[k]:
-            assert_same_frame(want[k], got[k], f"{w}x{h}, {k}", [q for q in FRAME_KEYS + ("hdr2",) if q in want[k]])
-        elif isinstance(want[k], np.ndarray):
-            assert_same_bits(want[k], got[k], f"{w}x{h}, {k}")
-        else:
-            assert want[k] == got[k], f"{w}x{h}, {k}: {want[k]} != {got[k]}"
-    return want, got
-
-
 def test_the_views_show_sky_and_no_sky(fx):
     w, h = 96, 64
-    sc = Scene(fx, 0, w, h)
+    sc = LazyScene(fx, 0, w, h)
     try:
         cov = []
-        for v in _views(w, h):
+        for v in views(w, h):
             sc.submit(v)
             cov.append((sc.rt.download("depth") < 1.0).mean())
         assert 0.2 < cov[0] < 1.0 and cov[1] == 1.0 and 0.2 < cov[2] < 1.0, cov
@@ -110,7 +43,7 @@ def test_every_kind_of_reader_finds_the_eager_frame(fx, w, h, reader):
     """Two frames with nobody looking (sky, then no sky), the reader, everything the target holds; then a third frame and all
     of it again.  Lazy: the two frames queue no plain tile pass, the reader queues one, and from then on the target's frames
     keep their G-buffer - the capture behind the third frame queues nothing."""
-    v = _views(w, h)
+    v = views(w, h)
     foreign = np.random.default_rng(7).integers(0, 1 << 32, (h, w), dtype=np.uint64).astype(np.uint32)
 
     def script(sc, lazy):
@@ -131,17 +64,17 @@ def test_every_kind_of_reader_finds_the_eager_frame(fx, w, h, reader):
             else:
                 d = sc.rt.describe()
                 out["first"] = (d.width, d.height)
-        _, r = _timed(sc.ctx, read)
+        _, r = timed(sc.ctx, read)
         assert (PLAIN in r) == bool(lazy), (reader, sorted(r))                   # the one materialisation
-        out["behind the reader"] = _capture(sc.rt, sc.hdr)
+        out["behind the reader"] = capture(sc.rt, sc.hdr)
         if reader == "light":      # the lighting pass over the materialised planes is the fused frame's HdrColor
             assert_same_bits(out["first"], out["behind the reader"]["hdr"], "vr_deferred_light against the fused frame")
         sc.submit(v[2], fused=reader != "describe")      # (the pointers have left the library: the two passes from now on)
-        cap, r = _timed(sc.ctx, lambda: _capture(sc.rt, sc.hdr))
+        cap, r = timed(sc.ctx, lambda: capture(sc.rt, sc.hdr))
         assert PLAIN not in r, f"{reader}: the frame after a materialisation did not keep its G-buffer: {sorted(r)}"
         out["third frame"] = cap
         return out
-    _both(fx, w, h, script)
+    both(fx, w, h, script)
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -149,7 +82,7 @@ def test_every_kind_of_reader_finds_the_eager_frame(fx, w, h, reader):
 def test_an_edit_with_a_frame_pending(fx, w, h, download_first):
     """submit, edit, submit, download: the planes are the second frame's on the edited terrain; with the download between the
     edit and the second submit they are the first frame's on the terrain as it was."""
-    v = _views(w, h)
+    v = views(w, h)
     hm = fx["h"]
     block = np.full((64, 64), 255, np.uint8)
     x0 = y0 = 96
@@ -160,20 +93,20 @@ def test_an_edit_with_a_frame_pending(fx, w, h, download_first):
             sc.submit(v[1])
             sc.tp.Edit("height", x0, y0, block)
             if download_first:
-                out["before the edit"] = _capture(sc.rt, sc.hdr)
+                out["before the edit"] = capture(sc.rt, sc.hdr)
             sc.submit(v[1])
-            out["after the edit"] = _capture(sc.rt, sc.hdr)
+            out["after the edit"] = capture(sc.rt, sc.hdr)
         finally:
             sc.tp.Edit("height", x0, y0, hm[y0:y0 + 64, x0:x0 + 64])
         return out
-    want, _ = _both(fx, w, h, script)
+    want, _ = both(fx, w, h, script)
     if download_first:
         assert not np.array_equal(want["before the edit"]["normals"], want["after the edit"]["normals"]), "the edit is not in view"
 
 
 def test_undo_and_redo_with_a_frame_pending(fx):
     w, h = 96, 64
-    v = _views(w, h)
+    v = views(w, h)
     block = np.full((64, 64), 255, np.uint8)
 
     def script(sc, lazy):
@@ -184,12 +117,12 @@ def test_undo_and_redo_with_a_frame_pending(fx):
             sc.tp.CommitHistory()
             sc.submit(v[1])
             assert sc.tp.Undo() is True
-            out["edited"] = _capture(sc.rt, sc.hdr)          # the frame was submitted on the edited terrain
-            sc = Scene(fx, lazy, w, h)                        # (a fresh target: the first one has given laziness up)
+            out["edited"] = capture(sc.rt, sc.hdr)          # the frame was submitted on the edited terrain
+            sc = LazyScene(fx, lazy, w, h)                        # (a fresh target: the first one has given laziness up)
             try:
                 sc.submit(v[1])
                 assert sc.tp.Redo() is True
-                out["original"] = _capture(sc.rt, sc.hdr)
+                out["original"] = capture(sc.rt, sc.hdr)
             finally:
                 sc.tp.Undo()
                 for o in (sc.hdr, sc.hdr2, sc.rt):
@@ -197,13 +130,13 @@ def test_undo_and_redo_with_a_frame_pending(fx):
         finally:
             sc.tp.EnableHistory(0)
         return out
-    want, _ = _both(fx, w, h, script)
+    want, _ = both(fx, w, h, script)
     assert not np.array_equal(want["edited"]["normals"], want["original"]["normals"])
 
 
 def test_resize_and_clear_with_a_frame_pending(fx):
     w, h = 96, 64
-    v = _views(w, h)
+    v = views(w, h)
 
     def script(sc, lazy):
         out = {}
@@ -218,53 +151,53 @@ def test_resize_and_clear_with_a_frame_pending(fx):
         sc.fr = vr.Frame(sc.tp, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
         sc.submit(v[0])
         sc.rt.Clear()                                         # the clear replaces the frame nobody looked at
-        _, r = _timed(sc.ctx, lambda: out.update(cleared=_capture(sc.rt, sc.hdr)))
+        _, r = timed(sc.ctx, lambda: out.update(cleared=capture(sc.rt, sc.hdr)))
         assert PLAIN not in r, sorted(r)
         assert (out["cleared"]["depth"] == 1.0).all() and not out["cleared"]["diffuse"].any()
         sc.submit(v[1])
         sc.rp.assume_cleared = 0                              # keep-what-is-there over a pending frame: a partial writer
         sc.tp.Render(v[0], v[0], sc.rt, sc.rp)
-        out["kept"] = _capture(sc.rt, sc.hdr)
+        out["kept"] = capture(sc.rt, sc.hdr)
         return out
-    _both(fx, w, h, script)
+    both(fx, w, h, script)
 
 
 def test_a_second_target_on_the_same_terrain(fx):
     """The terrain holds at most one pending target: a lazy frame into a second one produces the first one's planes."""
     w, h = 96, 64
-    v = _views(w, h)
+    v = views(w, h)
 
     def script(sc, lazy):
-        other = Scene(fx, lazy, w, h)
+        other = LazyScene(fx, lazy, w, h)
         try:
             sc.submit(v[0])
             other.submit(v[1])
-            return {"first": _capture(sc.rt, sc.hdr), "second": _capture(other.rt, other.hdr)}
+            return {"first": capture(sc.rt, sc.hdr), "second": capture(other.rt, other.hdr)}
         finally:
             for o in (other.hdr, other.hdr2, other.rt):
                 o.close()
-    _both(fx, w, h, script)
+    both(fx, w, h, script)
 
 
 def test_a_pending_clear_belongs_to_the_frame_that_consumed_it(fx):
     """Clear, a frame without assume_cleared (the frame is that clear), then a keep-what-is-there pass: it keeps the FRAME's
     pixels where it draws nothing, not the clear's - the clear is not pending a second time behind a lazy frame."""
     w, h = 96, 64
-    v = _views(w, h)
+    v = views(w, h)
 
     def script(sc, lazy):
         sc.rp.assume_cleared = 0
         sc.rt.Clear()
         sc.submit(v[1])
         sc.tp.Render(v[0], v[0], sc.rt, sc.rp)
-        out = {"kept": _capture(sc.rt, sc.hdr)}
+        out = {"kept": capture(sc.rt, sc.hdr)}
         sc.rt.Clear()
         sc.submit(v[0])
         sc.rt.Clear()
         sc.submit(v[1])
-        out["second clear"] = _capture(sc.rt, sc.hdr)
+        out["second clear"] = capture(sc.rt, sc.hdr)
         return out
-    want, _ = _both(fx, w, h, script)
+    want, _ = both(fx, w, h, script)
     assert (want["kept"]["depth"] < 1.0).all(), "the top-down frame's pixels were not kept under the sky of the second view"
 
 
@@ -275,13 +208,13 @@ def test_a_second_terrain_takes_over_the_target(fx):
     the target stays lazy until somebody looks."""
     from tests.common import params
     w, h = 96, 64
-    v = _views(w, h)
+    v = views(w, h)
     ctx, hm = fx["ctx"], fx["h"]
     other = vr.TerrainPass(ctx, params(256)).Init(np.ascontiguousarray(hm[::-1]), vr.synth_albedo(ctx, 256, hm))
     block = np.full((64, 64), 255, np.uint8)
 
     def edit_a(sc):
-        _, r = _timed(sc.ctx, lambda: sc.tp.Edit("height", 96, 96, block))
+        _, r = timed(sc.ctx, lambda: sc.tp.Edit("height", 96, 96, block))
         sc.tp.Edit("height", 96, 96, hm[96:160, 96:160])
         return r
 
@@ -289,26 +222,26 @@ def test_a_second_terrain_takes_over_the_target(fx):
         out = {}
         fr_b = vr.Frame(other, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
         sc.submit(v[0])                                       # terrain A
-        _timed(sc.ctx, lambda: fr_b.submit(v[1], sc.hdr))     # terrain B into the same target
+        timed(sc.ctx, lambda: fr_b.submit(v[1], sc.hdr))     # terrain B into the same target
         assert PLAIN not in edit_a(sc), "an edit of the first terrain drew the second terrain's frame"
-        _, r = _timed(sc.ctx, lambda: out.update(b=_capture(sc.rt, sc.hdr)))
+        _, r = timed(sc.ctx, lambda: out.update(b=capture(sc.rt, sc.hdr)))
         assert (PLAIN in r) == bool(lazy), sorted(r)          # B's frame was still pending
         # again on a fresh target, with the resize in between
         sc.rt.Init(w, h)
         sc.fr = vr.Frame(sc.tp, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
         fr_b = vr.Frame(other, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
         sc.submit(v[0])
-        _timed(sc.ctx, lambda: fr_b.submit(v[1], sc.hdr))
+        timed(sc.ctx, lambda: fr_b.submit(v[1], sc.hdr))
         sc.rt.Init(68, 50)                                    # the target goes; neither terrain may still hold it
         assert PLAIN not in edit_a(sc)
-        _, r = _timed(sc.ctx, lambda: other.Edit("height", 96, 96, np.ascontiguousarray(hm[::-1])[96:160, 96:160]))
+        _, r = timed(sc.ctx, lambda: other.Edit("height", 96, 96, np.ascontiguousarray(hm[::-1])[96:160, 96:160]))
         assert PLAIN not in r
         sc.fr = vr.Frame(sc.tp, sc.rt, sc.rp, sc.lights, AMBIENT_TOP, AMBIENT_BOTTOM)
         sc.submit(vr.make_view(*scaled_camera(flythrough_camera(0), 256), 68, 50))
         out["a resized"] = {p: sc.rt.download(p).copy() for p in PLANES}
         return out
     try:
-        _both(fx, w, h, script)
+        both(fx, w, h, script)
     finally:
         other.close()
 
@@ -320,22 +253,22 @@ def test_a_materialising_pass_borrows_a_set_while_two_frames_are_prepared(fx):
     rendered - one from its prepared set, one built again - and a lock_view render reuses the last selection; every plane behind
     every step is the eager world's."""
     w, h = 320, 180
-    v = _views(w, h)
+    v = views(w, h)
 
     def script(sc, lazy):
         out = {}
         assert PLAIN not in sc.submit(v[0])
         sc.tp.Prepare(v[1], sc.rt, sc.rp)
         sc.tp.Prepare(v[2], sc.rt, sc.rp)
-        out["first"], r = _timed(sc.ctx, lambda: sc.rt.download("diffuse").copy())
+        out["first"], r = timed(sc.ctx, lambda: sc.rt.download("diffuse").copy())
         assert (PLAIN in r) == bool(lazy), sorted(r)                             # the materialising pass, with two sets prepared
-        out["the frame"] = _capture(sc.rt, sc.hdr)
+        out["the frame"] = capture(sc.rt, sc.hdr)
         for i in (1, 2):
             sc.tp.Render(v[i], v[i], sc.rt, sc.rp)
-            out[f"prepared view {i}"] = _capture(sc.rt, sc.hdr)
+            out[f"prepared view {i}"] = capture(sc.rt, sc.hdr)
         sc.rp.lock_view = 1
         sc.tp.Render(v[0], v[0], sc.rt, sc.rp)
-        out["lock_view"] = _capture(sc.rt, sc.hdr)
+        out["lock_view"] = capture(sc.rt, sc.hdr)
         return out
-    want, _ = _both(fx, w, h, script)
+    want, _ = both(fx, w, h, script)
     assert not np.array_equal(want["prepared view 1"]["depth"], want["prepared view 2"]["depth"])

@@ -681,8 +681,8 @@ def test_cpp_allgather_example_through_rccl(product_lib, tmp_path):
     world size 1 on a one-GPU box): histogram all-reduce, all-gather of RGB8 tiles, de-tile; the assembled frame equals
     the unsplit one byte for byte."""
     import subprocess
-    from tests.test_abi_cpu import _build_allgather_example
-    exe = _build_allgather_example(tmp_path)
+    from tests.host_check import build_allgather_example
+    exe = build_allgather_example(tmp_path)
     r = subprocess.run([exe, "--require-gpu"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "differing bytes=0" in r.stdout, r.stdout
@@ -691,8 +691,8 @@ def test_cpp_allgather_example_through_rccl(product_lib, tmp_path):
 def test_cpp_host_example(product_lib, tmp_path):
     """The C++ caller of tests/host/frame_example.cpp renders and lights a frame through the C ABI."""
     import subprocess
-    from tests.test_abi_cpu import _build_host_example
-    exe = _build_host_example(tmp_path)
+    from tests.host_check import build_host_example
+    exe = build_host_example(tmp_path)
     r = subprocess.run([exe, "--require-gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "chunks=" in r.stdout

@@ -17,7 +17,7 @@ from tests import pyramid_model as pm
 from tests import queries_common as qc
 from tests.common import params
 from tests.f64_queries import Surface64
-from tests.test_terrain_edit_gpu import Maps, Scene
+from tests.level0_common import Maps, Scene
 
 pytestmark = pytest.mark.gpu
 

@@ -1,73 +1,27 @@
 """GPU tests of vr_terrain_brush.  The stroked map must equal the numpy float32 model (tests/brush_model.py) in every byte - no
 tolerance anywhere: vr_brush.h's arithmetic is IEEE fp32 in a fixed order - and the stroked terrain must be the one created from
-the model's maps.  Scenes and the state under test are those of tests/test_terrain_edit_gpu.py: 64^2 + 64^2, 67x45 height + 33x50
+the model's maps.  Scenes and the state under test are those of tests/level0_common.py: 64^2 + 64^2, 67x45 height + 33x50
 albedo (a dab is an ellipse in texel space) and the 2x2-surface world of 128 on 128^2 maps; frames are 256x144."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import vrenderer_amd as vr
 from vrenderer_amd import capi
 from tests import brush_model as bm
-from tests import test_terrain_edit_gpu as te
+from tests.level0_common import (BRUSH_OPS, SCENES, STROKE_KW, assert_bytes, assert_terrains_equal, check_stroke_preconditions, dab, five_dabs, level0, make_scenes,
+                                 order_dabs, world_of)
 
 pytestmark = pytest.mark.gpu
-
-OPS = {bm.RAISE: "raise", bm.FLATTEN: "flatten", bm.SMOOTH: "smooth", bm.PAINT: "paint"}
 
 
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    return {n: te.Scene(gpu_ctx, n) for n in te.SCENES}
+    return make_scenes(gpu_ctx, SCENES)
 
 
-def world_of(sc):
-    return float(sc.p.world_size)
-
-
-def dab(shape, world, tx, ty, r_tex, hardness, strength):
-    """A dab whose centre is at texel coordinate (tx, ty) of a map of `shape` (texel i has its centre at coordinate i) and whose
-    radius is r_tex texels of the map's width."""
-    h, w = shape[:2]
-    return [(tx + 0.5) / w * world - world / 2, (ty + 0.5) / h * world - world / 2, r_tex * world / w, hardness, strength]
-
-
-def five_dabs(shape, world, op):
-    """Mixed radii (0.4 .. 12 texels), hardness 0 and 0.7, one centre on a map corner, one outside the map that still overlaps it."""
-    h, w = shape[:2]
-    s = {bm.RAISE: (37.3, -21.6, 60.5, 13.2, -90.0), bm.FLATTEN: (0.6, 0.35, 0.8, 0.5, 1.0),
-         bm.SMOOTH: (1.0, 0.6, 0.8, 0.5, 1.0), bm.PAINT: (0.6, 0.35, 0.8, 0.5, 1.0)}[op]
-    return np.float32([dab(shape, world, 0.3 * w, 0.4 * h, 12.0, 0.0, s[0]),
-                       dab(shape, world, 0.7 * w + 0.37, 0.6 * h + 0.21, 5.5, 0.7, s[1]),
-                       dab(shape, world, -0.5, -0.5, 6.0, 0.0, s[2]),                   # the map's corner
-                       dab(shape, world, w + 2.0, 0.5 * h, 4.5, 0.7, s[3]),             # outside, overlapping
-                       dab(shape, world, 10.1, 7.2, 0.4, 0.0, s[4])])                   # one texel
-
-
-STROKE_KW = {bm.RAISE: {}, bm.FLATTEN: dict(target=141.0), bm.SMOOTH: {}, bm.PAINT: dict(color=(200.0, 10.0, 35.5, 99.0), channels=0b0101)}
-
-
-def check_preconditions(before, after, op):
-    """Asserted on the model's output: the stroke can tell a wrong kernel from a right one."""
-    changed = (before != after) if before.ndim == 2 else (before != after).any(-1)
-    assert changed.sum() >= 30, changed.sum()
-    vals = after[changed]
-    assert ((vals > 0) & (vals < 255)).sum() >= 10
-    if op == bm.PAINT:
-        assert np.array_equal(before[..., 1], after[..., 1]) and np.array_equal(before[..., 3], after[..., 3])
-
-
-def level0(tp, which):
-    return tp.download_mip(which, 0)
-
-
-def assert_bytes(got, want, what):
-    assert np.array_equal(got, want), f"{what}: {(got != want).sum()} bytes differ, first {np.argwhere(got != want)[:4].tolist()}"
-
-
-@pytest.mark.parametrize("op", sorted(OPS))
-@pytest.mark.parametrize("name", te.SCENES)
+@pytest.mark.parametrize("op", sorted(BRUSH_OPS))
+@pytest.mark.parametrize("name", SCENES)
 def test_bytes_equal_the_model(scenes, name, op):
     """1. Each op on each scene, a stroke of five dabs: level 0 equals the model in every byte, the other map is untouched, the
     returned rectangle is the model's."""
@@ -76,29 +30,14 @@ def test_bytes_equal_the_model(scenes, name, op):
     before = sc.al if op == bm.PAINT else sc.hm
     dabs = five_dabs(before.shape, world_of(sc), op)
     want, want_rect = bm.stroke(before, op, dabs, world_of(sc), **STROKE_KW[op])
-    check_preconditions(before, want, op)
+    check_stroke_preconditions(before, want, op)
     a = sc.terrain(sc.hm, sc.al, cast=False, render=False)
-    rect = a.Brush(OPS[op], dabs, **STROKE_KW[op])
+    rect = a.Brush(BRUSH_OPS[op], dabs, **STROKE_KW[op])
     assert rect == tuple(want_rect), (rect, want_rect)
-    assert_bytes(level0(a, which), want, f"{name}, {OPS[op]}")
+    assert_bytes(level0(a, which), want, f"{name}, {BRUSH_OPS[op]}")
     other = "height" if which == "albedo" else "albedo"
-    assert_bytes(level0(a, other), sc.hm if other == "height" else sc.al, f"{name}, {OPS[op]}: the other map")
+    assert_bytes(level0(a, other), sc.hm if other == "height" else sc.al, f"{name}, {BRUSH_OPS[op]}: the other map")
     a.close()
-
-
-def order_dabs(shape, world, strengths):
-    """300 dabs: 290 whose spans all meet the 32 x 8 tile at the map's origin, five near the top right corner and five near the
-    left edge further down - so the stroke's rectangle holds tiles no dab meets - and none that reaches the bottom rows."""
-    rows = []
-    for i in range(300):
-        if i % 30 == 7:
-            tx, ty = 57.0 + (i % 4) * 0.5, 4.0
-        elif i % 30 == 19:
-            tx, ty = 4.0, 38.0 + (i % 4) * 0.5
-        else:
-            tx, ty = 8.0 + (i * 7 % 160) * 0.1, 2.0 + (i * 3 % 40) * 0.1
-        rows.append(dab(shape, world, tx, ty, 2.0 + (i % 5) * 0.5, 0.7 if i % 2 else 0.0, strengths[i % len(strengths)]))
-    return np.float32(rows)
 
 
 def test_order_and_chunking(scenes):
@@ -172,7 +111,7 @@ def test_smooth_reads_the_snapshot(scenes):
     a.close()
 
 
-@pytest.mark.parametrize("name", te.SCENES)
+@pytest.mark.parametrize("name", SCENES)
 def test_the_terrain_is_the_one_created_from_the_stroked_maps(scenes, name):
     """5. A (SetHeight on, pyramid built, one frame rendered; then RAISE and PAINT) against B created from the model's maps: every
     mip level, node heights and selections, every G-buffer plane for cameras 0 and 5, sampled heights with normals, 64 ray hits."""
@@ -185,7 +124,7 @@ def test_the_terrain_is_the_one_created_from_the_stroked_maps(scenes, name):
     a.Brush("raise", hd)
     a.Brush("paint", ad, **STROKE_KW[bm.PAINT])
     b = sc.terrain(hm, al)
-    te._assert_terrains_equal(sc, a, b, name)
+    assert_terrains_equal(sc, a, b, name)
     a.close(); b.close()
 
 
@@ -203,8 +142,8 @@ def test_nothing_outside_nothing_on_a_miss(scenes):
         kw = dict(color=(255.0, 255.0, 255.0, 255.0)) if which == "albedo" else dict(target=255.0)
         want, want_rect = bm.stroke(m, op, miss, S, **kw)
         assert tuple(want_rect) == (0, 0, 0, 0) and np.array_equal(want, m)
-        assert a.Brush(OPS[op], miss, **kw) == (0, 0, 0, 0)
-        assert a.Brush(OPS[op], np.zeros((0, 5), np.float32), **kw) == (0, 0, 0, 0)
+        assert a.Brush(BRUSH_OPS[op], miss, **kw) == (0, 0, 0, 0)
+        assert a.Brush(BRUSH_OPS[op], np.zeros((0, 5), np.float32), **kw) == (0, 0, 0, 0)
         assert_bytes(level0(a, which), m, f"{which} after strokes that miss")
     whole = np.float32([[0.3, -0.2, 4.0 * S, 0.5, 30.0]])
     want, want_rect = bm.stroke(sc.hm, bm.RAISE, whole, S)

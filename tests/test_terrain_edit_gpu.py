@@ -3,9 +3,7 @@ arrays.  Terrain A is created from the original maps, put into the state under t
 pyramid exists, one frame rendered) and edited; terrain B is created afresh from the edited arrays.  Everything the library
 exposes is compared bit for bit - no tolerance anywhere: both sides run the same kernels' arithmetic.
 
-Scenes, the smallest at which each mechanism can go wrong: 64^2 + 64^2 (the tile pass's fast variant, the dyadic SetHeight
-path), 67x45 height + 33x50 albedo (odd chains, the clamped last column, the non-dyadic SetHeight path, the general raster
-variant) and a 2x2-surface world of 128 on 128^2 maps (per-surface node bases)."""
+The scenes, the state under test and the comparisons are tests/level0_common.py's."""
 import ctypes as C
 
 import numpy as np
@@ -13,82 +11,20 @@ import pytest
 
 import vrenderer_amd as vr
 from vrenderer_amd import capi
-from tests.common import AMBIENT_BOTTOM, AMBIENT_TOP, CAMERAS, params, scaled_camera
-from tests.fusion_common import PLANES, download_frame
-from tests import pyramid_model as pm
+from tests.fusion_common import PLANES
 from tests import queries_common as qc
-from tests import tables_model as tm
 from tests.f64_queries import Surface64
+from tests.level0_common import (H, SCENES, W, Maps, assert_bytes, assert_chains_equal, assert_frames_equal, assert_pyramids_equal, assert_tables_equal, bits,
+                                 five_dabs, level0, make_scenes, render, submit_frames, world_of)
 
 pytestmark = pytest.mark.gpu
 
-W, H = 256, 144
-SCENES = ("fast64", "odd", "multi")
 RENDER_CAMERAS = (0, 5, 7)
-
-
-def _bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-class Scene:
-    """The original maps of one scene, its terrain parameters and the world size its cameras are scaled to."""
-
-    def __init__(self, ctx, name):
-        self.ctx, self.name = ctx, name
-        if name == "fast64":
-            self.hm = vr.synth_heightmap(ctx, 64)
-            self.al = vr.synth_albedo(ctx, 64, self.hm)
-            self.p, self.world = params(64), 64
-        elif name == "odd":
-            self.hm = np.ascontiguousarray(vr.synth_heightmap(ctx, 67)[:45, :67])
-            h50 = vr.synth_heightmap(ctx, 50)
-            self.al = np.ascontiguousarray(vr.synth_albedo(ctx, 50, h50)[:50, :33])
-            self.p, self.world = params(64), 64
-        else:
-            self.hm = vr.synth_heightmap(ctx, 128)
-            self.al = vr.synth_albedo(ctx, 128, self.hm)
-            self.p, self.world = params(64), 128
-            self.p.world_size = 128.0
-        self.mh = qc.scaled_max_height(self.world)
-
-    def terrain(self, hm, al, cast=True, render=True):
-        """A terrain of (hm, al) in the state under test: node heights on, the pyramid built by one cast, one frame rendered."""
-        tp = vr.TerrainPass(self.ctx, self.p).Init(hm, al)
-        tp.SetHeight(True)
-        if cast:
-            tp.CastRays(np.float32([[0.0, 4.0 * self.mh, 0.0]]), np.float32([[0.1, -1.0, 0.2]]), np.inf, self.mh)
-        if render:
-            rt = vr.RenderTargets(self.ctx).Init(W, H)
-            v = self.view(0)
-            tp.Render(v, v, rt, vr.default_render_params(self.mh))
-            rt.close()
-        return tp
-
-    def view(self, cam, w=W, h=H):
-        eye, tgt = scaled_camera(CAMERAS[cam], self.world)
-        return vr.make_view(eye, tgt, w, h)
-
-
-class Maps:
-    """Host copies of the two maps that follow every edit made to terrain A."""
-
-    def __init__(self, sc):
-        self.hm, self.al = sc.hm.copy(), sc.al.copy()
-
-    def edit(self, tp, which, x, y, texels):
-        tp.Edit(which, x, y, texels)
-        dst = self.hm if which == "height" else self.al
-        dst[y:y + texels.shape[0], x:x + texels.shape[1]] = texels
-
-    def random(self, tp, rng, which, x, y, w, h):
-        shape = (h, w) if which == "height" else (h, w, 4)
-        self.edit(tp, which, x, y, rng.integers(0, 256, shape, dtype=np.uint8))
 
 
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    return {n: Scene(gpu_ctx, n) for n in SCENES}
+    return make_scenes(gpu_ctx, SCENES)
 
 
 def _edit_some(sc, tp, maps, seed=7):
@@ -100,87 +36,6 @@ def _edit_some(sc, tp, maps, seed=7):
         maps.random(tp, rng, which, 3, 5, 7, 9)
         maps.random(tp, rng, which, fw - 6, fh - 4, 6, 4)
         maps.random(tp, rng, which, fw // 2 - 1, 0, 1, fh)
-
-
-def _assert_chains_equal(a, b, what):
-    for which in ("height", "albedo"):
-        n = a.mip_levels(which)
-        assert n == b.mip_levels(which)
-        for l in range(n):
-            x, y = a.download_mip(which, l), b.download_mip(which, l)
-            assert np.array_equal(x, y), f"{what}: {which} level {l} differs in {(x != y).sum()} bytes, first {np.argwhere(x != y)[:4].tolist()}"
-
-
-def _assert_terrains_equal(sc, a, b, what):
-    """Everything the library exposes of terrains A and B of scene `sc`: every mip level, node heights and selections, every G-buffer
-    plane for cameras 0 and 5, 1024 sampled heights with normals, 64 ray hits, then the query pyramid itself and 64 hits under a negative
-    max_height (_assert_pyramids_equal), and the decoded tables themselves (_assert_tables_equal)."""
-    _assert_chains_equal(a, b, what)
-    _assert_tables_equal(a, b, what)
-    surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
-    nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
-    ha, hb = a.node_heights(0, nodes), b.node_heights(0, nodes)
-    assert np.array_equal(ha.view(np.uint32), hb.view(np.uint32)), f"{what}: {(ha.view(np.uint32) != hb.view(np.uint32)).any(1).sum()} of {nodes} nodes differ"
-    for cam in (0, 5):
-        v = sc.view(cam)
-        na, ia, insta = a.NodeSelect(v, sc.mh)
-        nb, ib, instb = b.NodeSelect(v, sc.mh)
-        assert na == nb and na > 0 and np.array_equal(ia, ib) and np.array_equal(insta, instb), (what, cam, na, nb)
-        _assert_frames_equal(_render(sc, a, cam), _render(sc, b, cam), f"{what}, camera {cam}")
-    pts = qc.uniform_points(sc.world, 1024)
-    (h1, n1), (h2, n2) = a.SampleHeights(pts, sc.mh, normals=True), b.SampleHeights(pts, sc.mh, normals=True)
-    assert np.array_equal(h1.view(np.uint32), h2.view(np.uint32)) and np.array_equal(n1.view(np.uint32), n2.view(np.uint32))
-    surf = Surface64(b.download_mip("height", 0), b.download_mip("height", 1), sc.world, sc.mh)
-    o, d, tm = qc.make_rays(surf, sc.world, n=64)
-    ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
-    assert ra.tobytes() == rb.tobytes(), f"{what}: {(ra != rb).sum()} of {len(ra)} hits differ"
-    assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
-    _assert_pyramids_equal(sc, a, b, what)
-
-
-def _assert_tables_equal(a, b, what):
-    """What frames and samples cannot show: they read only the entries some pixel or point selects, of the one raster variant the pair of
-    maps takes.  Every decoded table (quad, quadf, fast; fast, rgbf) of every level of both maps of A equals B's and equals
-    tests/tables_model.py's of the device's own level, bit for bit."""
-    ta = tm.assert_tables_are_the_model(a, f"{what}: A")
-    tm.assert_tables_equal(ta, tm.assert_tables_are_the_model(b, f"{what}: B"), f"{what}: A's tables against B's")
-
-
-def _assert_pyramids_equal(sc, a, b, what):
-    """What the rays above cannot show.  The query pyramids of A and B (both have cast by now) are equal level by level, and equal to
-    tests/pyramid_model.py's of B's maps, byte for byte: a bound left too loose by a refresh only makes a walk longer.  And 64 rays
-    built for max_height = -sc.mh are cast with it - the one sign under which the walk reads the lo plane: the same bytes from A and B."""
-    pa, pb = a.QueryPyramid(), b.QueryPyramid()
-    assert pa is not None and pb is not None and len(pa) == len(pb), what
-    l0 = b.download_mip("height", 0)
-    model = pm.levels(l0, b.download_mip("height", 1) if b.mip_levels("height") > 1 else l0)
-    assert len(pb) == len(model), (what, len(pb), len(model))
-    for l, (x, y, m) in enumerate(zip(pa, pb, model)):
-        assert x.shape == y.shape == m.shape, (what, l, x.shape, y.shape, m.shape)
-        assert np.array_equal(x, y), f"{what}: pyramid level {l}: {(x != y).any(-1).sum()} cells of A differ from B's, first {np.argwhere((x != y).any(-1))[:4].tolist()}"
-        assert np.array_equal(y, m), f"{what}: pyramid level {l}: {(y != m).any(-1).sum()} cells differ from the model, first {np.argwhere((y != m).any(-1))[:4].tolist()}"
-    below = Surface64(l0, b.download_mip("height", 1) if b.mip_levels("height") > 1 else l0, sc.world, -sc.mh)
-    o, d, tm = qc.make_rays(below, sc.world, n=64)
-    ra, rb = a.CastRays(o, d, tm, -sc.mh), b.CastRays(o, d, tm, -sc.mh)
-    assert ra.tobytes() == rb.tobytes(), f"{what}: {(ra != rb).sum()} of {len(ra)} hits differ under max_height = {-sc.mh}"
-    assert (ra["status"] == capi.VR_RAY_HIT).sum() > 0
-
-
-def _render(sc, tp, cam, part=None, **rpkw):
-    rt = vr.RenderTargets(sc.ctx).Init(W, H)
-    if not rpkw.get("assume_cleared"):
-        rt.Clear()
-    v = sc.view(cam)
-    tp.Render(v, v, rt, vr.default_render_params(sc.mh, **rpkw), part)
-    out = {p: rt.download(p).copy() for p in PLANES}
-    rt.close()
-    return out
-
-
-def _assert_frames_equal(a, b, what):
-    for p in PLANES:
-        x, y = _bits(a[p]), _bits(b[p])
-        assert np.array_equal(x, y), f"{what}: {p} differs in {(x != y).sum()} elements, first {np.argwhere(x != y)[:4].tolist()}"
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -207,7 +62,7 @@ def test_every_mip_level_after_every_kind_of_rectangle(scenes, name):
     for what, fn in sequences:
         both(fn)
         b = sc.terrain(maps.hm, maps.al, cast=False, render=False)
-        _assert_chains_equal(a, b, f"{name}, {what}")
+        assert_chains_equal(a, b, f"{name}, {what}")
         b.close()
     for k in range(20):
         which = "height" if k % 2 == 0 else "albedo"
@@ -215,7 +70,7 @@ def test_every_mip_level_after_every_kind_of_rectangle(scenes, name):
         x, y = int(rng.integers(0, fw)), int(rng.integers(0, fh))
         maps.random(a, rng, which, x, y, int(rng.integers(1, fw - x + 1)), int(rng.integers(1, fh - y + 1)))
     b = sc.terrain(maps.hm, maps.al, cast=False, render=False)
-    _assert_chains_equal(a, b, f"{name}, 20 random rectangles")
+    assert_chains_equal(a, b, f"{name}, 20 random rectangles")
     a.close(); b.close()
 
 
@@ -227,13 +82,13 @@ def test_every_gbuffer_plane(scenes, oracle, name):
     a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
     _edit_some(sc, a, maps)
     b = sc.terrain(maps.hm, maps.al)
-    _assert_tables_equal(a, b, name)
+    assert_tables_equal(a, b, name)
     covered = 0
     for cam in RENDER_CAMERAS:
         for what, kw, part in (("fill", dict(assume_cleared=1), None), ("wireframe", dict(wireframe=1), None),
                                ("depth_only", dict(depth_only=1), None), ("rank 1 of 3", {}, vr.Partition(1, 3))):
-            fa, fb = _render(sc, a, cam, part, **kw), _render(sc, b, cam, part, **kw)
-            _assert_frames_equal(fa, fb, f"{name}, camera {cam}, {what}")
+            fa, fb = render(sc, a, cam, part, **kw), render(sc, b, cam, part, **kw)
+            assert_frames_equal(fa, fb, f"{name}, camera {cam}, {what}")
             covered += int((fa["depth"] < 1.0).sum())
     assert covered > 0
     if name == "fast64":
@@ -241,8 +96,8 @@ def test_every_gbuffer_plane(scenes, oracle, name):
         ot.set_height(True)
         gb = oracle.GBufferHost(W, H)
         ot.render(sc.view(0), gb, vr.default_render_params(sc.mh, assume_cleared=1))
-        fa = _render(sc, a, 0, None, assume_cleared=1)
-        _assert_frames_equal(fa, {p: getattr(gb, p) for p in PLANES}, "64^2 against the oracle on the edited arrays")
+        fa = render(sc, a, 0, None, assume_cleared=1)
+        assert_frames_equal(fa, {p: getattr(gb, p) for p in PLANES}, "64^2 against the oracle on the edited arrays")
         assert (fa["depth"] < 1.0).mean() > 0.05
         ot.close()
     a.close(); b.close()
@@ -290,35 +145,9 @@ def test_queries(scenes, name, cast_first):
     ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
     assert ra.tobytes() == rb.tobytes(), f"{name}: {(ra != rb).sum()} of {len(ra)} hits differ"
     assert (ra["status"] == capi.VR_RAY_HIT).mean() > 0.2
-    _assert_pyramids_equal(sc, a, b, f"{name}, cast before the edits: {cast_first}")
-    _assert_tables_equal(a, b, f"{name}, cast before the edits: {cast_first}")
+    assert_pyramids_equal(sc, a, b, f"{name}, cast before the edits: {cast_first}")
+    assert_tables_equal(a, b, f"{name}, cast before the edits: {cast_first}")
     a.close(); b.close()
-
-
-def _submit_frames(sc, tp, views, fusion, edit=None, lock_after=False):
-    """Two vr_frame_submit frames with the next view prepared ahead; `edit` runs between them.  Returns per frame the planes,
-    HdrColor and the selected node ids."""
-    ctx = sc.ctx
-    ctx.set_frame_fusion(fusion)
-    rt, hdr = vr.RenderTargets(ctx).Init(W, H), vr.HdrImage(ctx, W, H)
-    out = []
-    try:
-        for i in range(2):
-            rp = vr.default_render_params(sc.mh, assume_cleared=1, lock_view=1 if (lock_after and i == 1) else 0)
-            fr = vr.Frame(tp, rt, rp, [vr.reference_sun()], AMBIENT_TOP, AMBIENT_BOTTOM)
-            rt.Clear()
-            hdr.upload(np.zeros(W * H * 4, np.uint16))
-            fr.submit(views[i], hdr, views[i + 1:i + 2])
-            ctx.synchronize()
-            f = download_frame(rt, hdr)
-            f["chunks"] = tp.num_chunks()
-            out.append(f)
-            if i == 0 and edit is not None:
-                edit()
-    finally:
-        ctx.set_frame_fusion(1)
-        hdr.close(); rt.close()
-    return out
 
 
 def test_prepared_geometry_is_stale_after_an_edit(scenes):
@@ -337,22 +166,22 @@ def test_prepared_geometry_is_stale_after_an_edit(scenes):
         fa = {p: rt.download(p).copy() for p in PLANES}
         rt.close()
         b = sc.terrain(maps.hm, maps.al)
-        _assert_frames_equal(fa, _render(sc, b, 5, None, assume_cleared=1), f"prepare, {which} edit, render")
+        assert_frames_equal(fa, render(sc, b, 5, None, assume_cleared=1), f"prepare, {which} edit, render")
         a.close(); b.close()
     views = [sc.view(5), sc.view(0), sc.view(0)]
     results = {}
     for fusion in (1, 0):
         a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
         erng = np.random.default_rng(5)
-        fa = _submit_frames(sc, a, views, fusion, edit=lambda: (maps.random(a, erng, "height", 8, 8, 40, 33), maps.random(a, erng, "albedo", 0, 30, 64, 9)))
+        fa = submit_frames(sc, a, views, fusion, edit=lambda: (maps.random(a, erng, "height", 8, 8, 40, 33), maps.random(a, erng, "albedo", 0, 30, 64, 9)))
         b = sc.terrain(maps.hm, maps.al)
-        fb = _submit_frames(sc, b, views, fusion)
+        fb = submit_frames(sc, b, views, fusion)
         for p in PLANES + ("hdr",):
-            assert np.array_equal(_bits(fa[1][p]), _bits(fb[1][p])), f"frame submit, fusion {fusion}: {p} of the frame after the edit differs"
+            assert np.array_equal(bits(fa[1][p]), bits(fb[1][p])), f"frame submit, fusion {fusion}: {p} of the frame after the edit differs"
         results[fusion] = fa
         a.close(); b.close()
     for p in PLANES + ("hdr",):
-        assert np.array_equal(_bits(results[1][1][p]), _bits(results[0][1][p])), f"fused and two-pass frames after the edit differ in {p}"
+        assert np.array_equal(bits(results[1][1][p]), bits(results[0][1][p])), f"fused and two-pass frames after the edit differ in {p}"
     # lock_view: the frame after the edit draws the nodes of the frame before it (a node is named by two opposite corners of its
     # patch: vertices 0 and 1088, which no morph moves)
     a, maps = sc.terrain(sc.hm, sc.al), Maps(sc)
@@ -389,8 +218,8 @@ def test_device_pointer_mode_with_a_wide_pitch(scenes):
         sc.ctx.synchronize()
         rect = host[:, :w * tb]
         b.Edit(which, x, y, rect.copy() if tb == 1 else rect.reshape(h, w, 4).copy())
-    _assert_chains_equal(a, b, "device-pointer mode")
-    _assert_frames_equal(_render(sc, a, 0), _render(sc, b, 0), "device-pointer mode")
+    assert_chains_equal(a, b, "device-pointer mode")
+    assert_frames_equal(render(sc, a, 0), render(sc, b, 0), "device-pointer mode")
     pts = qc.uniform_points(sc.world, 512)
     assert np.array_equal(a.SampleHeights(pts, sc.mh), b.SampleHeights(pts, sc.mh))
     a.close(); b.close()
@@ -404,7 +233,7 @@ def test_refusals_leave_the_terrain_alone(scenes):
     a = sc.terrain(sc.hm, sc.al)
     lib, hnd = sc.ctx.lib, a.handle
     chains = {(wh, l): a.download_mip(wh, l) for wh in ("height", "albedo") for l in range(a.mip_levels(wh))}
-    frame = _render(sc, a, 0)
+    frame = render(sc, a, 0)
     buf = np.full((64, 64, 4), 77, np.uint8)
     p = buf.ctypes.data_as(C.c_void_p)
     dev = torch.full((4096,), 77, dtype=torch.uint8, device=f"cuda:{sc.ctx.device}")
@@ -423,7 +252,7 @@ def test_refusals_leave_the_terrain_alone(scenes):
         assert lib.vr_terrain_edit(hnd, *args) == capi.VR_OK, args
     for (wh, l), want in chains.items():
         assert np.array_equal(a.download_mip(wh, l), want), (wh, l)
-    _assert_frames_equal(_render(sc, a, 0), frame, "after the refusals")
+    assert_frames_equal(render(sc, a, 0), frame, "after the refusals")
     a.close()
 
 
@@ -438,8 +267,7 @@ def test_side_resources_follow_the_context_across_two_streams(scenes, gpu_ctx):
     import torch
     from tests import brush_model as bm
     from tests import erosion_state as es
-    from tests.test_terrain_brush_gpu import assert_bytes, five_dabs, level0, world_of
-    from tests.test_terrain_erosion_state_gpu import ITER, assert_state, model
+    from tests.erosion_state import ITER, assert_state, model
     sc = scenes["fast64"]
     S, mh = world_of(sc), sc.mh
     stroke = five_dabs(sc.hm.shape, S, bm.RAISE)

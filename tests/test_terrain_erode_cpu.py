@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import erode_model as em
+from tests.erosion_state import full_mask, seeded_dabs
 from tests.host_check import build_host_check, run_host_check
 from vrenderer_amd import capi
 
@@ -96,19 +97,6 @@ def test_serial_evaluator_keeps_its_invariants(erode_checks):
         assert "740 calls" in r.stdout, r.stdout[-400:]              # (36 maps + the 61 x 61 one) x 20
 
 
-def seeded_dabs(rng, h, w, n=12):
-    """Centres inside and outside the map, radii from under a texel to a third of the map and more, hardness 0 and 0.7."""
-    dabs = np.zeros((n, 5), np.float32)
-    dabs[:, 0:2] = rng.uniform(-0.7 * WORLD, 0.7 * WORLD, (n, 2))
-    dabs[:, 2] = np.exp(rng.uniform(np.log(0.3), np.log(25.0), n)) * WORLD / max(w, h)
-    dabs[:, 3] = rng.choice([0.0, 0.7], n)
-    dabs[:, 4] = rng.uniform(0.0, 1.0, n)
-    dabs[0, 0:2] = (-0.6 * WORLD, 0.1 * WORLD)                       # a centre outside the map that still reaches it
-    dabs[0, 2] = 0.25 * WORLD
-    dabs[1, 2] = 0.4 * WORLD / max(w, h)                             # a sub-texel radius
-    return dabs
-
-
 def _host_erode(exe, tmp_path, texels, dabs, iterations, talus, rate):
     h, w = texels.shape
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
@@ -144,10 +132,6 @@ def test_header_on_the_host_gives_the_model_s_bytes(erode_checks, tmp_path, size
 
 
 # ---- the model's own properties ---------------------------------------------------------------------------------------------------
-def full_mask(world=WORLD):
-    return np.float32([[0.0, 0.0, 4.0 * world, 0.5, 1.0]])          # one hard-centred dab far larger than the map: mask 1 everywhere
-
-
 def test_zero_mask_and_flat_map_change_nothing():
     rng = np.random.default_rng(11)
     texels = rng.integers(0, 256, (45, 67), dtype=np.uint8)

@@ -1,7 +1,7 @@
 """GPU tests of vr_terrain_erode.  The eroded map must equal the numpy float32 model (tests/erode_model.py) in every byte - no
 tolerance anywhere: vr_erode.h's arithmetic is IEEE fp32 in a fixed order, and a cell is a pure function of the sweep before, so
 neither the tile of the device's kernel nor the number of sweeps it advances per launch may show - and the eroded terrain must be
-the one created from the model's map.  Scenes and the state under test are those of tests/test_terrain_edit_gpu.py."""
+the one created from the model's map.  Scenes and the state under test are those of tests/level0_common.py."""
 import ctypes as C
 
 import numpy as np
@@ -10,8 +10,7 @@ import pytest
 from vrenderer_amd import capi
 from tests import brush_model as bm
 from tests import erode_model as em
-from tests import test_terrain_edit_gpu as te
-from tests.test_terrain_brush_gpu import assert_bytes, dab, five_dabs, level0, world_of
+from tests.level0_common import SCENES, assert_bytes, assert_terrains_equal, borders, dab, five_dabs, full_mask, level0, make_scenes, mask_dabs, world_of
 
 pytestmark = pytest.mark.gpu
 
@@ -20,16 +19,7 @@ ITER, TALUS, RATE = 20, 1.5, 0.125
 
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    return {n: te.Scene(gpu_ctx, n) for n in te.SCENES}
-
-
-def mask_dabs(shape, world):
-    """five_dabs with opacities for strengths: radii 0.4 .. 12 texels, hardness 0 and 0.7, a centre on the map's corner, one outside."""
-    return five_dabs(shape, world, bm.FLATTEN)
-
-
-def full_mask(world):
-    return np.float32([[0.0, 0.0, 4.0 * world, 0.5, 1.0]])          # mask 1 on every texel
+    return make_scenes(gpu_ctx, SCENES)
 
 
 _MODEL = {}
@@ -44,7 +34,7 @@ def model(sc, dabs, iterations, talus=TALUS, rate=RATE, hm=None):
     return _MODEL[key]
 
 
-@pytest.mark.parametrize("name", te.SCENES)
+@pytest.mark.parametrize("name", SCENES)
 def test_bytes_equal_the_model(scenes, name):
     """1. A five-dab mask on each scene: level 0 equals the model in every byte, the albedo is untouched, the rectangle is the model's."""
     sc = scenes[name]
@@ -58,10 +48,6 @@ def test_bytes_equal_the_model(scenes, name):
     assert_bytes(level0(a, "height"), want, f"{name}, erode")
     assert_bytes(level0(a, "albedo"), sc.al, f"{name}, erode: the albedo")
     a.close()
-
-
-def _borders(size, tile):
-    return list(range(tile, size, tile))
 
 
 def _far_from_sources(src, k):
@@ -84,7 +70,7 @@ def test_tile_borders_and_launch_boundaries(scenes, gpu_ctx):
     sc = scenes["multi"]
     size = sc.hm.shape[0]
     assert sc.hm.shape == (size, size)
-    bx, by = _borders(size, tw), _borders(size, th)
+    bx, by = borders(size, tw), borders(size, th)
     assert (len(bx) >= 2 and len(by) >= 1 or len(bx) >= 1 and len(by) >= 2) and size % tw and size % th, (tw, th, size)
     assert min(tw, th) > 2 * (k + 4)                                 # room for the bands between two borders
     dabs = full_mask(world_of(sc))
@@ -113,7 +99,7 @@ def test_tile_borders_and_launch_boundaries(scenes, gpu_ctx):
         a.close()
 
 
-@pytest.mark.parametrize("name", te.SCENES)
+@pytest.mark.parametrize("name", SCENES)
 def test_the_terrain_is_the_one_created_from_the_eroded_map(scenes, name):
     """3. A (SetHeight on, pyramid built, one frame rendered; then eroded) against B created from the model's map: every mip level,
     node heights and selections, every G-buffer plane for cameras 0 and 5, sampled heights with normals, 64 ray hits."""
@@ -123,7 +109,7 @@ def test_the_terrain_is_the_one_created_from_the_eroded_map(scenes, name):
     a = sc.terrain(sc.hm, sc.al)
     a.Erode(dabs, ITER, TALUS, RATE)
     b = sc.terrain(hm, sc.al)
-    te._assert_terrains_equal(sc, a, b, name)
+    assert_terrains_equal(sc, a, b, name)
     a.close(); b.close()
 
 

@@ -7,7 +7,7 @@ bit patterns, cropped to the call's rectangle.  No tolerance anywhere.
 The thermal parameters are not dyadic (tests/erosion_state.py), so the arithmetic rounds; and every case that has the edges for it
 first shows, on the model alone, that it can tell: the model with the first and the last neighbour of its order exchanged differs
 from the right one in at least 30 fp32 cells of the case's final state.  Scenes and helpers are those of
-tests/test_terrain_edit_gpu.py and tests/test_terrain_brush_gpu.py."""
+tests/level0_common.py."""
 import ctypes as C
 
 import numpy as np
@@ -15,19 +15,18 @@ import pytest
 
 from vrenderer_amd import capi
 from tests import erosion_state as es
-from tests import test_terrain_edit_gpu as te
-from tests.test_terrain_brush_gpu import assert_bytes, level0, world_of
+from tests.erosion_state import ITER, assert_state, model
+from tests.level0_common import SCENES, assert_bytes, level0, make_scenes, world_of
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-ITER = 20
 KINDS = ("thermal", "hydraulic")
 
 
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    return {n: te.Scene(gpu_ctx, n) for n in te.SCENES}
+    return make_scenes(gpu_ctx, SCENES)
 
 
 @pytest.fixture(scope="module")
@@ -41,30 +40,8 @@ def config(gpu_ctx):
     return out
 
 
-_MODEL = {}
-
-
-def model(kind, texels, dabs, world, iterations, params):
-    """The model's state, computed once per distinct call and left unchanged."""
-    key = (kind, texels.tobytes(), texels.shape, np.asarray(dabs, F).tobytes(), world, iterations, repr(params))
-    if key not in _MODEL:
-        _MODEL[key] = es.state(kind, texels, dabs, world, iterations, params)
-    return _MODEL[key]
-
-
 def erode(tp, kind, dabs, iterations, params):
     return tp.Erode(dabs, iterations, *params) if kind == "thermal" else tp.ErodeHydraulic(dabs, iterations, **params)
-
-
-def assert_state(tp, want, what):
-    """The planes the last call left are the model's, bit for bit, inside the model's rectangle; level 0 is the model's bytes."""
-    rect, mask, planes = tp.ErosionState()
-    assert rect == want["rect"], (what, rect, want["rect"])
-    assert len(planes) == len(want["planes"]), (what, len(planes))
-    es.assert_bits(mask, es.crop(want["mask"], rect), f"{what}: the mask plane")
-    for name, got, ref in zip("hds", planes, want["planes"]):
-        es.assert_bits(got, es.crop(ref, rect), f"{what}: {name}")
-    assert_bytes(level0(tp, "height"), want["bytes"], f"{what}: level 0")
 
 
 def run_case(sc, kind, texels, dabs, iterations, params, what, sensitive=True):
@@ -83,7 +60,7 @@ def run_case(sc, kind, texels, dabs, iterations, params, what, sensitive=True):
 
 
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("name", te.SCENES)
+@pytest.mark.parametrize("name", SCENES)
 def test_state_on_the_suite_s_scenes(scenes, name, kind):
     """1. The five-dab mask on each scene for 20 iterations: the mask plane is mask_of, h (and d, s) are state(), level 0 is the model's."""
     sc = scenes[name]

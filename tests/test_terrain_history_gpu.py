@@ -1,9 +1,9 @@
 """GPU tests of the terrain history (vr_terrain_history_enable / commit / undo / redo / status).  After an undo or a redo the
 terrain must be the one vr_terrain_create builds from the maps of that point in history; everything is compared bit for bit, with
 no tolerance and no exclusions - the journal moves bytes, and the refresh is the one vr_terrain_edit runs.  Scenes and the state
-under test are those of tests/test_terrain_edit_gpu.py (64^2 + 64^2; 67x45 height + 33x50 albedo, whose row pitches are no
+under test are those of tests/level0_common.py (64^2 + 64^2; 67x45 height + 33x50 albedo, whose row pitches are no
 multiples of 16, so that most rows take the kernels' texel-by-texel path and a few the vector path; 2x2 surfaces on 128^2), the
-strokes those of tests/test_terrain_brush_gpu.py; frames are 256x144."""
+strokes tests/level0_common.py's five_dabs; frames are 256x144."""
 import ctypes as C
 import os
 import subprocess
@@ -15,11 +15,11 @@ import vrenderer_amd as vr
 from vrenderer_amd import capi
 from tests import brush_model as bm
 from tests import queries_common as qc
-from tests import test_terrain_brush_gpu as tb
 from tests.f64_queries import Surface64
 from tests.fusion_common import PLANES
 from tests.host_check import build_host_check
-from tests.test_terrain_edit_gpu import SCENES, Scene, _assert_chains_equal, _assert_frames_equal, _assert_pyramids_equal, _assert_tables_equal, _bits, _render, _submit_frames
+from tests.level0_common import (BRUSH_OPS, SCENES, STROKE_KW, assert_bytes, assert_chains_equal, assert_frames_equal, assert_pyramids_equal, assert_tables_equal, bits,
+                                 check_stroke_preconditions, dab, five_dabs, level0, make_scenes, render, submit_frames, world_of)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +28,7 @@ NODE_HEIGHTS = "k_node_heights (all levels)"
 
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    return {n: Scene(gpu_ctx, n) for n in SCENES}
+    return make_scenes(gpu_ctx, SCENES)
 
 
 @pytest.fixture(scope="module")
@@ -42,15 +42,15 @@ def record_bytes(tmp_path_factory):
 
 
 def _assert_maps(tp, hm, al, what):
-    tb.assert_bytes(tb.level0(tp, "height"), hm, f"{what}: height")
-    tb.assert_bytes(tb.level0(tp, "albedo"), al, f"{what}: albedo")
+    assert_bytes(level0(tp, "height"), hm, f"{what}: height")
+    assert_bytes(level0(tp, "albedo"), al, f"{what}: albedo")
 
 
 def _assert_terrains_equal(sc, a, b, what):
     """Every mip level of both maps, the node heights, sampled heights with normals, ray hits, every G-buffer plane of a frame, the
     query pyramid and the hits under a negative max_height, the decoded tables of both maps."""
-    _assert_chains_equal(a, b, what)
-    _assert_tables_equal(a, b, what)
+    assert_chains_equal(a, b, what)
+    assert_tables_equal(a, b, what)
     surfaces = int(sc.p.world_size / sc.p.surface_size) ** 2
     nodes = (4 ** (a.GetNumLods() + 1) - 1) // 3 * surfaces
     ha, hb = a.node_heights(0, nodes).view(np.uint32), b.node_heights(0, nodes).view(np.uint32)
@@ -62,8 +62,8 @@ def _assert_terrains_equal(sc, a, b, what):
     o, d, tm = qc.make_rays(surf, sc.world, n=64)
     ra, rb = a.CastRays(o, d, tm, sc.mh), b.CastRays(o, d, tm, sc.mh)
     assert ra.tobytes() == rb.tobytes(), f"{what}: {(ra != rb).sum()} of {len(ra)} hits differ"
-    _assert_frames_equal(_render(sc, a, 0), _render(sc, b, 0), what)
-    _assert_pyramids_equal(sc, a, b, what)
+    assert_frames_equal(render(sc, a, 0), render(sc, b, 0), what)
+    assert_pyramids_equal(sc, a, b, what)
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -71,22 +71,22 @@ def test_undo_restores_the_whole_terrain(scenes, name):
     """1. SetHeight on, one ray cast and one frame done first.  Each brush op (five_dabs), commit, undo: the terrain is the one
     created from the original maps - chains, node heights, queries, a frame.  Redo: the one created from the model's stroked maps."""
     sc = scenes[name]
-    S = tb.world_of(sc)
+    S = world_of(sc)
     a, orig = sc.terrain(sc.hm, sc.al), sc.terrain(sc.hm, sc.al)
     a.EnableHistory(1 << 20)
-    for op in sorted(tb.OPS):
+    for op in sorted(BRUSH_OPS):
         before = sc.al if op == bm.PAINT else sc.hm
-        dabs = tb.five_dabs(before.shape, S, op)
-        want, _ = bm.stroke(before, op, dabs, S, **tb.STROKE_KW[op])
-        tb.check_preconditions(before, want, op)
-        a.Brush(tb.OPS[op], dabs, **tb.STROKE_KW[op])
+        dabs = five_dabs(before.shape, S, op)
+        want, _ = bm.stroke(before, op, dabs, S, **STROKE_KW[op])
+        check_stroke_preconditions(before, want, op)
+        a.Brush(BRUSH_OPS[op], dabs, **STROKE_KW[op])
         assert a.HistoryStatus()["open_records"] == 1
         a.CommitHistory()
         assert a.Undo() is True
-        _assert_terrains_equal(sc, a, orig, f"{name}, {tb.OPS[op]}, undo")
+        _assert_terrains_equal(sc, a, orig, f"{name}, {BRUSH_OPS[op]}, undo")
         assert a.Redo() is True
         b = sc.terrain(want if op != bm.PAINT else sc.hm, want if op == bm.PAINT else sc.al)
-        _assert_terrains_equal(sc, a, b, f"{name}, {tb.OPS[op]}, redo")
+        _assert_terrains_equal(sc, a, b, f"{name}, {BRUSH_OPS[op]}, redo")
         b.close()
         assert a.Undo() is True                              # back to the original maps for the next op
     _assert_maps(a, sc.hm, sc.al, f"{name}: after the last undo")
@@ -131,7 +131,7 @@ def test_rectangles_that_stress_the_vector_path(scenes, name):
             _assert_maps(a, edited["height"], edited["albedo"], f"{name}, {which}, {what}: redo")
             cur = edited
     b = sc.terrain(cur["height"], cur["albedo"], cast=False, render=False)
-    _assert_chains_equal(a, b, f"{name}: after all rectangles")
+    assert_chains_equal(a, b, f"{name}: after all rectangles")
     a.close(); b.close()
 
 
@@ -149,17 +149,17 @@ def test_a_step_of_overlapping_records(scenes):
     original maps, one redo the final maps, applied == 1 both times.  A further call returns applied == 0 and queues nothing: the
     timing records are empty, where those of the undo that applied hold the refresh's node-height kernel."""
     sc = scenes["fast64"]
-    S = tb.world_of(sc)
+    S = world_of(sc)
     a = sc.terrain(sc.hm, sc.al)
     a.EnableHistory(1 << 20)
     hm, al = sc.hm, sc.al
     for k, (tx, ty) in enumerate(((20.0, 22.0), (26.5, 25.0), (23.0, 30.0))):
-        dabs = np.float32([tb.dab(hm.shape, S, tx, ty, 9.0, 0.3, 40.0 - 55.0 * (k == 1))])
+        dabs = np.float32([dab(hm.shape, S, tx, ty, 9.0, 0.3, 40.0 - 55.0 * (k == 1))])
         hm, _ = bm.stroke(hm, bm.RAISE, dabs, S)
         a.Brush("raise", dabs)
-    pd = np.float32([tb.dab(al.shape, S, 24.0, 24.0, 10.0, 0.5, 0.8)])
-    al, _ = bm.stroke(al, bm.PAINT, pd, S, **tb.STROKE_KW[bm.PAINT])
-    a.Brush("paint", pd, **tb.STROKE_KW[bm.PAINT])
+    pd = np.float32([dab(al.shape, S, 24.0, 24.0, 10.0, 0.5, 0.8)])
+    al, _ = bm.stroke(al, bm.PAINT, pd, S, **STROKE_KW[bm.PAINT])
+    a.Brush("paint", pd, **STROKE_KW[bm.PAINT])
     patch = np.random.default_rng(3).integers(0, 256, (11, 19), dtype=np.uint8)
     hm = hm.copy(); hm[18:29, 15:34] = patch
     a.Edit("height", 15, 18, patch)
@@ -191,17 +191,17 @@ def test_redo_is_discarded_by_a_new_stroke(scenes):
     """4. Step 1 (RAISE), step 2 (PAINT), undo, a new RAISE stroke: redo_steps == 0 and redo applies nothing.  The two steps that
     remain undo and redo in order."""
     sc = scenes["fast64"]
-    S = tb.world_of(sc)
+    S = world_of(sc)
     a = sc.terrain(sc.hm, sc.al, cast=False, render=False)
     a.EnableHistory(1 << 20)
-    d1, d2 = tb.five_dabs(sc.hm.shape, S, bm.RAISE), tb.five_dabs(sc.al.shape, S, bm.PAINT)
-    d3 = np.float32([tb.dab(sc.hm.shape, S, 40.0, 12.0, 8.0, 0.2, -35.0)])
+    d1, d2 = five_dabs(sc.hm.shape, S, bm.RAISE), five_dabs(sc.al.shape, S, bm.PAINT)
+    d3 = np.float32([dab(sc.hm.shape, S, 40.0, 12.0, 8.0, 0.2, -35.0)])
     hm1, _ = bm.stroke(sc.hm, bm.RAISE, d1, S)
-    al2, _ = bm.stroke(sc.al, bm.PAINT, d2, S, **tb.STROKE_KW[bm.PAINT])
+    al2, _ = bm.stroke(sc.al, bm.PAINT, d2, S, **STROKE_KW[bm.PAINT])
     hm3, _ = bm.stroke(hm1, bm.RAISE, d3, S)
     assert (hm3 != hm1).sum() >= 30
     a.Brush("raise", d1); a.CommitHistory()
-    a.Brush("paint", d2, **tb.STROKE_KW[bm.PAINT]); a.CommitHistory()
+    a.Brush("paint", d2, **STROKE_KW[bm.PAINT]); a.CommitHistory()
     _assert_maps(a, hm1, al2, "two steps")
     assert a.Undo() is True
     st = a.HistoryStatus()
@@ -257,7 +257,7 @@ def test_budget(scenes, record_bytes):
     before = a.HistoryStatus()
     assert before["undo_steps"] == 2
     a.Edit("height", 0, 0, big)
-    tb.assert_bytes(tb.level0(a, "height"), big, "the edit larger than the arena")
+    assert_bytes(level0(a, "height"), big, "the edit larger than the arena")
     st = a.HistoryStatus()
     assert (st["undo_steps"], st["redo_steps"], st["open_records"], st["bytes_used"]) == (0, 0, 0, 0), st
     assert st["dropped_steps"] == before["dropped_steps"] + 2 + 1
@@ -284,9 +284,9 @@ def test_off_means_off(scenes):
     vr_terrain_memory_bytes is what it was before enable-then-disable (and larger by the budget in between).  Argument refusals
     and a refused allocation leave maps, steps and status as they were."""
     sc = scenes["odd"]
-    S = tb.world_of(sc)
+    S = world_of(sc)
     lib = sc.ctx.lib
-    dabs = tb.five_dabs(sc.hm.shape, S, bm.RAISE)
+    dabs = five_dabs(sc.hm.shape, S, bm.RAISE)
     zero = dict(undo_steps=0, redo_steps=0, open_records=0, dropped_steps=0, bytes_used=0, bytes_budget=0)
     a = sc.terrain(sc.hm, sc.al)
     a.Brush("raise", dabs); a.Edit("height", 0, 0, sc.hm)              # the brush's own memory exists from here on
@@ -296,7 +296,7 @@ def test_off_means_off(scenes):
     assert never and a.HistoryStatus() == zero
     assert a.Undo() is False and a.Redo() is False
     a.CommitHistory()
-    hm1 = tb.level0(a, "height")
+    hm1 = level0(a, "height")
     a.EnableHistory(1 << 16)
     assert a.memory_bytes()["total"] == mem["total"] + (1 << 16)
     a.Edit("height", 0, 0, sc.hm)
@@ -314,18 +314,18 @@ def test_off_means_off(scenes):
     finally:
         del os.environ["VR_ALLOC_FAIL_ABOVE"]
     assert a.HistoryStatus() == st
-    tb.assert_bytes(tb.level0(a, "height"), hm1, "after the refusals")
+    assert_bytes(level0(a, "height"), hm1, "after the refusals")
     a.EnableHistory(1 << 16)                                          # the budget it has: the steps stay
     assert a.HistoryStatus() == st
     a.EnableHistory(0)
     assert a.HistoryStatus() == zero and a.memory_bytes() == mem
     assert a.Undo() is False
-    tb.assert_bytes(tb.level0(a, "height"), hm1, "undo with history off")
+    assert_bytes(level0(a, "height"), hm1, "undo with history off")
     a.Edit("height", 0, 0, sc.hm)
     _, after = _timed(sc.ctx, lambda: a.Brush("raise", dabs))
     names = lambda ran: {k: n for k, (ms, n) in ran.items()}
     assert names(never) == names(after) == names(on), (never, on, after)
-    tb.assert_bytes(tb.level0(a, "height"), hm1, "the stroke with history off again")
+    assert_bytes(level0(a, "height"), hm1, "the stroke with history off again")
     a.close()
 
 
@@ -345,18 +345,18 @@ def test_frames_in_flight(scenes):
         a.EnableHistory(1 << 20)
         a.Edit("height", 8, 8, hm[8:41, 8:48]); a.Edit("albedo", 0, 30, al[30:39, 0:64])
         a.CommitHistory()
-        fa = _submit_frames(sc, a, views, fusion, edit=lambda: a.Undo())
+        fa = submit_frames(sc, a, views, fusion, edit=lambda: a.Undo())
         b, e = sc.terrain(sc.hm, sc.al), sc.terrain(hm, al)
-        fb = _submit_frames(sc, b, views, fusion)
-        fr = _submit_frames(sc, a, views, fusion, edit=lambda: a.Redo())     # a is restored here: frame 0 of b, then frame 1 of e
-        fe = _submit_frames(sc, e, views, fusion)
+        fb = submit_frames(sc, b, views, fusion)
+        fr = submit_frames(sc, a, views, fusion, edit=lambda: a.Redo())     # a is restored here: frame 0 of b, then frame 1 of e
+        fe = submit_frames(sc, e, views, fusion)
         for p in PLANES + ("hdr",):
-            assert np.array_equal(_bits(fa[0][p]), _bits(fe[0][p])), f"fusion {fusion}: {p} of the frame before the undo differs"
-            assert np.array_equal(_bits(fa[1][p]), _bits(fb[1][p])), f"fusion {fusion}: {p} of the frame after the undo differs"
-            assert np.array_equal(_bits(fr[0][p]), _bits(fb[0][p])), f"fusion {fusion}: {p} of the frame before the redo differs"
-            assert np.array_equal(_bits(fr[1][p]), _bits(fe[1][p])), f"fusion {fusion}: {p} of the frame after the redo differs"
-        assert (fa[1]["depth"] < 1.0).any() and any(not np.array_equal(_bits(fb[1][p]), _bits(fe[1][p])) for p in PLANES)
+            assert np.array_equal(bits(fa[0][p]), bits(fe[0][p])), f"fusion {fusion}: {p} of the frame before the undo differs"
+            assert np.array_equal(bits(fa[1][p]), bits(fb[1][p])), f"fusion {fusion}: {p} of the frame after the undo differs"
+            assert np.array_equal(bits(fr[0][p]), bits(fb[0][p])), f"fusion {fusion}: {p} of the frame before the redo differs"
+            assert np.array_equal(bits(fr[1][p]), bits(fe[1][p])), f"fusion {fusion}: {p} of the frame after the redo differs"
+        assert (fa[1]["depth"] < 1.0).any() and any(not np.array_equal(bits(fb[1][p]), bits(fe[1][p])) for p in PLANES)
         results[fusion] = fa
         a.close(); b.close(); e.close()
     for p in PLANES + ("hdr",):
-        assert np.array_equal(_bits(results[1][1][p]), _bits(results[0][1][p])), f"fused and two-pass frames after the undo differ in {p}"
+        assert np.array_equal(bits(results[1][1][p]), bits(results[0][1][p])), f"fused and two-pass frames after the undo differ in {p}"

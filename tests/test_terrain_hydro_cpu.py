@@ -13,7 +13,7 @@ import pytest
 
 from tests import hydro_model as hm
 from tests.host_check import build_host_check, run_host_check
-from tests.test_terrain_erode_cpu import full_mask, seeded_dabs
+from tests.erosion_state import full_mask, seeded_dabs
 from vrenderer_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,7 +1,7 @@
 """GPU tests of vr_terrain_erode_hydraulic.  The eroded map must equal the numpy float32 model (tests/hydro_model.py) in every byte -
 no tolerance anywhere: vr_hydro.h's arithmetic is IEEE fp32 in a fixed order, subnormals kept, and a cell is a pure function of the
 sweep before, so neither the tile of the device's kernel nor the number of sweeps it advances per launch may show - and the eroded
-terrain must be the one created from the model's map.  Scenes and helpers are those of tests/test_terrain_erode_gpu.py."""
+terrain must be the one created from the model's map.  Scenes and helpers are those of tests/level0_common.py."""
 import ctypes as C
 
 import numpy as np
@@ -11,9 +11,7 @@ from vrenderer_amd import capi
 from tests import brush_model as bm
 from tests import erode_model as em
 from tests import hydro_model as hm
-from tests import test_terrain_edit_gpu as te
-from tests.test_terrain_brush_gpu import assert_bytes, dab, five_dabs, level0, world_of
-from tests.test_terrain_erode_gpu import _borders, full_mask, mask_dabs
+from tests.level0_common import SCENES, assert_bytes, assert_terrains_equal, borders, dab, five_dabs, full_mask, level0, make_scenes, mask_dabs, world_of
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +24,7 @@ TALUS, RATE = 1.5, 0.125                                             # of the th
 
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    return {n: te.Scene(gpu_ctx, n) for n in te.SCENES}
+    return make_scenes(gpu_ctx, SCENES)
 
 
 _MODEL = {}
@@ -46,7 +44,7 @@ def hydro(tp, dabs, iterations, **kw):
     return tp.ErodeHydraulic(dabs, iterations, **{**P, **kw})
 
 
-@pytest.mark.parametrize("name", te.SCENES)
+@pytest.mark.parametrize("name", SCENES)
 def test_bytes_equal_the_model(scenes, name):
     """1. A five-dab mask on each scene: level 0 equals the model in every byte, the albedo is untouched, the rectangle is the model's."""
     sc = scenes[name]
@@ -83,7 +81,7 @@ def test_tile_borders_and_launch_boundaries(scenes, gpu_ctx):
     sc = scenes["multi"]
     size = sc.hm.shape[0]
     assert sc.hm.shape == (size, size)
-    bx, by = _borders(size, tw), _borders(size, th)
+    bx, by = borders(size, tw), borders(size, th)
     assert len(bx) >= 1 and len(by) >= 1 and len(bx) + len(by) >= 3 and size % tw and size % th, (tw, th, size)
     assert k >= 2
     S = world_of(sc)
@@ -123,7 +121,7 @@ def test_tile_borders_and_launch_boundaries(scenes, gpu_ctx):
         a.close()
 
 
-@pytest.mark.parametrize("name", te.SCENES)
+@pytest.mark.parametrize("name", SCENES)
 def test_the_terrain_is_the_one_created_from_the_eroded_map(scenes, name):
     """3. A (SetHeight on, pyramid built, one frame rendered; then eroded) against B created from the model's map: every mip level,
     node heights and selections, every G-buffer plane for cameras 0 and 5, sampled heights with normals, 64 ray hits."""
@@ -133,7 +131,7 @@ def test_the_terrain_is_the_one_created_from_the_eroded_map(scenes, name):
     a = sc.terrain(sc.hm, sc.al)
     hydro(a, dabs, ITER)
     b = sc.terrain(want, sc.al)
-    te._assert_terrains_equal(sc, a, b, name)
+    assert_terrains_equal(sc, a, b, name)
     a.close(); b.close()
 
 

@@ -1,7 +1,7 @@
 """GPU tests of the stamps.  The stamped map must equal the numpy float32 model (tests/stamp_model.py) in every byte - no tolerance
 anywhere: vr_stamp.h's arithmetic is IEEE fp32 in a fixed order, and a texel is a pure function of its own map texel and the stamp,
 so neither the tile nor the order in which the device visits the texels may show.  Scenes and helpers are those of
-tests/test_terrain_edit_gpu.py; the calls are tests/stamp_cases.py's, whose preconditions are asserted on the model's output (and,
+tests/level0_common.py; the calls are tests/stamp_cases.py's, whose preconditions are asserted on the model's output (and,
 without a device, in tests/test_stamp_model_cpu.py)."""
 import numpy as np
 import pytest
@@ -12,11 +12,9 @@ from tests import erode_model as em
 from tests import queries_common as qc
 from tests import stamp_cases as sc
 from tests import stamp_model as sm
-from tests import test_gbuffer_lazy_gpu as gl
-from tests import test_terrain_edit_gpu as te
 from tests.f64_queries import Surface64
-from tests.fusion_common import terrain_fixture
-from tests.test_terrain_brush_gpu import assert_bytes, five_dabs, level0, world_of
+from tests.fusion_common import both, capture, terrain_fixture, views
+from tests.level0_common import assert_bytes, assert_chains_equal, assert_frames_equal, assert_tables_equal, five_dabs, level0, make_scenes, render, world_of
 from vrenderer_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -25,10 +23,7 @@ OP_NAMES = [n for n, _ in sc.OPS]
 
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    out = {n: te.Scene(gpu_ctx, n) for n in sc.SCENES}
-    for n, s in out.items():
-        assert world_of(s) == sc.WORLD[n]
-    return out
+    return make_scenes(gpu_ctx, sc.SCENES, sc.WORLD)
 
 
 def apply(tp, which, stamp, p):
@@ -56,8 +51,8 @@ def run_calls(s, which, calls, tables=True):
         cur = want
     if tables:
         b = s.terrain(cur, s.al, cast=False, render=False) if which == "height" else s.terrain(s.hm, cur, cast=False, render=False)
-        te._assert_chains_equal(a, b, f"{s.name}, {calls[-1]['name']}")
-        te._assert_tables_equal(a, b, f"{s.name}, {calls[-1]['name']}")
+        assert_chains_equal(a, b, f"{s.name}, {calls[-1]['name']}")
+        assert_tables_equal(a, b, f"{s.name}, {calls[-1]['name']}")
         b.close()
     a.close()
     return cur
@@ -154,10 +149,10 @@ def test_order_with_nothing_between(scenes):
     st = vr.Stamp(s.ctx, call["stamp"])
     a.Erode(mask, 20, 0.5, 0.125)
     assert apply(a, "height", st, call["params"]) == tuple(want_rect)
-    frame = te._render(s, a, 0)
+    frame = render(s, a, 0)
     assert_bytes(level0(a, "height"), want, "erode, stamp")
     b = s.terrain(want, s.al)
-    te._assert_frames_equal(frame, te._render(s, b, 0), "erode, stamp: the frame")
+    assert_frames_equal(frame, render(s, b, 0), "erode, stamp: the frame")
     b.close()
     # brush, capture
     stroke = five_dabs(s.hm.shape, S, bm.RAISE)
@@ -176,7 +171,7 @@ def test_a_stamp_with_a_lazily_fused_frame_pending():
     are those of the eager path (VR_OPT_GBUFFER_LAZY off) - the frame on the terrain as it was; the next frame shows the stamp."""
     w, h = 96, 64
     with terrain_fixture(256) as fx:
-        v = gl._views(w, h)
+        v = views(w, h)
         hm = fx["h"]
         st = vr.Stamp(fx["ctx"], sc.stamp_texels(33, 17))
         p = sc.place(hm.shape, 256.0, 128.0, 128.0, 120.0, 80.0, 30.0, feather=0.5, op=sm.MAX, offset=60.0)
@@ -187,13 +182,13 @@ def test_a_stamp_with_a_lazily_fused_frame_pending():
             try:
                 scn.submit(v[1])
                 apply(scn.tp, "height", st, p)
-                out["before the stamp"] = gl._capture(scn.rt, scn.hdr)
+                out["before the stamp"] = capture(scn.rt, scn.hdr)
                 scn.submit(v[1])
-                out["after the stamp"] = gl._capture(scn.rt, scn.hdr)
+                out["after the stamp"] = capture(scn.rt, scn.hdr)
             finally:
                 scn.tp.Edit("height", 0, 0, hm)
             return out
-        want, _ = gl._both(fx, w, h, script)
+        want, _ = both(fx, w, h, script)
         assert not np.array_equal(want["before the stamp"]["normals"], want["after the stamp"]["normals"]), "the stamp is not in view"
         st.close()
 

@@ -17,7 +17,7 @@ from vrenderer_amd import capi
 from tests import frontend_common as fc
 from tests import tables_model as tm
 from tests.common import params
-from tests.test_terrain_edit_gpu import Maps, Scene
+from tests.level0_common import Maps, Scene
 
 pytestmark = pytest.mark.gpu
 

@@ -1,37 +1,23 @@
 """GPU tests of vr_terrain_texture.  The textured albedo must equal the numpy float32 model (tests/texture_model.py) in every byte - no
 tolerance anywhere: vr_texture.h's arithmetic is IEEE fp32 in a fixed order, and a texel is a pure function of the two maps, so
 neither the tile nor where the kernel reads its height bytes from (LDS or memory) may show.  Scenes and helpers are those of
-tests/test_terrain_edit_gpu.py, with tests/texture_cases.py's two scenes that run the direct-load variant; the preconditions of
+tests/level0_common.py, with tests/texture_cases.py's two scenes that run the direct-load variant; the preconditions of
 every case are asserted on the model's output (and, without a device, in tests/test_terrain_texture_cpu.py)."""
 import numpy as np
 import pytest
 
-import vrenderer_amd as vr
 from tests import erode_model as em
-from tests import queries_common as qc
-from tests import test_terrain_edit_gpu as te
 from tests import texture_cases as tc
-from tests.common import params
-from tests.test_terrain_brush_gpu import assert_bytes, level0, order_dabs, world_of
+from tests.level0_common import assert_bytes, assert_chains_equal, assert_frames_equal, assert_tables_equal, level0, make_scenes, order_dabs, render, world_of
 
 pytestmark = pytest.mark.gpu
 
 
-class ExtraScene(te.Scene):
-    """A scene of tests/texture_cases.py that tests/test_terrain_edit_gpu.py does not have."""
-
-    def __init__(self, ctx, name):
-        self.ctx, self.name = ctx, name
-        self.hm, self.al = tc.scene_maps(name, lambda n: vr.synth_heightmap(ctx, n), lambda n, h: vr.synth_albedo(ctx, n, h))
-        self.p, self.world = params(64), int(tc.WORLD[name])
-        self.mh = qc.scaled_max_height(self.world)
-
-
 @pytest.fixture(scope="module")
 def scenes(gpu_ctx):
-    out = {n: (te.Scene if n in te.SCENES else ExtraScene)(gpu_ctx, n) for n in tc.SCENES}
+    out = make_scenes(gpu_ctx, tc.SCENES, tc.WORLD)
     for n, sc in out.items():
-        assert world_of(sc) == tc.WORLD[n] and sc.mh == tc.max_height(n)
+        assert sc.mh == tc.max_height(n)
         assert tc.staged_footprint(sc.hm.shape, sc.al.shape) == (n not in ("fine", "wide"))
     return out
 
@@ -63,7 +49,7 @@ def test_bytes_equal_the_model_under_five_dabs(scenes, name):
     assert_bytes(level0(a, "albedo"), want, f"{name}, texture under five dabs")
     assert_bytes(level0(a, "height"), sc.hm, f"{name}, texture: the heightmap")
     b = sc.terrain(sc.hm, want, cast=False, render=False)
-    te._assert_tables_equal(a, b, f"{name}, texture under five dabs")
+    assert_tables_equal(a, b, f"{name}, texture under five dabs")
     a.close(); b.close()
 
 
@@ -80,8 +66,8 @@ def test_bytes_equal_the_model_over_the_whole_map(scenes, name):
     assert_bytes(level0(a, "albedo"), want, f"{name}, texture over the whole map")
     assert_bytes(level0(a, "height"), sc.hm, f"{name}, texture: the heightmap")
     b = sc.terrain(sc.hm, want, cast=False, render=False)
-    te._assert_chains_equal(a, b, f"{name}, texture over the whole map")
-    te._assert_tables_equal(a, b, f"{name}, texture over the whole map")
+    assert_chains_equal(a, b, f"{name}, texture over the whole map")
+    assert_tables_equal(a, b, f"{name}, texture over the whole map")
     a.close(); b.close()
 
 
@@ -104,7 +90,7 @@ def test_an_erode_then_a_texture_with_nothing_between(scenes):
     assert_bytes(level0(a, "albedo"), want, "erode, texture")
     assert_bytes(level0(a, "height"), eroded, "erode, texture: the heightmap")
     b = sc.terrain(eroded, want)
-    te._assert_frames_equal(te._render(sc, a, 0), te._render(sc, b, 0), "erode, texture: the frame")
+    assert_frames_equal(render(sc, a, 0), render(sc, b, 0), "erode, texture: the frame")
     a.close(); b.close()
 
 

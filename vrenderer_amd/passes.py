@@ -16,6 +16,32 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _rows(a, short, full):
+    """Rows for a C array of structs `full` floats wide, as a C-contiguous float32 (n, full) array: `a` has rows of `full` columns,
+    which are passed as they are, or of one of the `short` widths, which are padded with zeros; a flat array is rows of short[-1]."""
+    a = np.asarray(a, np.float32)
+    if a.ndim == 1:
+        a = a.reshape(-1, short[-1])
+    assert a.ndim == 2 and a.shape[1] in short + (full,)
+    if a.shape[1] != full:
+        padded = np.zeros((a.shape[0], full), np.float32)
+        padded[:, :a.shape[1]] = a
+        a = padded
+    return np.ascontiguousarray(a)
+
+
+def _map_index(which):
+    return {"height": 0, "albedo": 1}.get(which, which)
+
+
+def _rect():
+    return (C.c_int32 * 4)()
+
+
+def _rect_tuple(rect):
+    return tuple(int(v) for v in rect)
+
+
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
@@ -596,7 +622,7 @@ class TerrainPass:
         `texels` is a numpy array, uint8 (h, w) for the height and uint8 (h, w, 4) for the albedo, and the call returns once it
         has been consumed.  Otherwise device_ptr is a raw device pointer to w x h texels whose rows are `pitch` bytes apart
         (0 = tightly packed); the edit is then stream-ordered and the memory must stay as it is until the stream has passed it."""
-        idx = {"height": 0, "albedo": 1}.get(which, which)
+        idx = _map_index(which)
         if device_ptr is None:
             a = np.ascontiguousarray(texels, np.uint8)
             assert (a.ndim == 2) if idx == 0 else (a.ndim == 3 and a.shape[2] == 4)
@@ -613,20 +639,12 @@ class TerrainPass:
         Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
         idx = {"raise": capi.VR_BRUSH_RAISE, "flatten": capi.VR_BRUSH_FLATTEN, "smooth": capi.VR_BRUSH_SMOOTH,
                "paint": capi.VR_BRUSH_PAINT}.get(op, op)
-        a = np.asarray(dabs, np.float32)
-        if a.ndim == 1:
-            a = a.reshape(-1, 5)
-        assert a.ndim == 2 and a.shape[1] in (5, 8)
-        if a.shape[1] == 5:
-            full = np.zeros((a.shape[0], 8), np.float32)
-            full[:, :5] = a
-            a = full
-        a = np.ascontiguousarray(a)
+        a = _rows(dabs, (5,), 8)
         stroke = capi.BrushStroke(op=idx, channel_mask=channels, target=target)
         stroke.color[:] = [float(c) for c in (color if color is not None else (0.0, 0.0, 0.0, 0.0))]
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_brush(self.handle, C.byref(stroke), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_brush")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def Texture(self, layers, dabs=None, max_height=400.0, whole_map=False):
         """vr_terrain_texture: level 0 of the albedo painted by rule from the heightmap's shape, computed on the device; stream-ordered,
@@ -647,19 +665,11 @@ class TerrainPass:
             dst.alt_lo, dst.alt_hi, dst.alt_fade = float(l["alt_lo"]), float(l["alt_hi"]), float(l["alt_fade"])
             dst.slope_lo, dst.slope_hi, dst.slope_fade = float(l["slope_lo"]), float(l["slope_hi"]), float(l["slope_fade"])
             dst.channel_mask = int(l.get("channel_mask", 0xF))
-        a = np.asarray(dabs if dabs is not None else np.zeros((0, 5), np.float32), np.float32)
-        if a.ndim == 1:
-            a = a.reshape(-1, 5)
-        assert a.ndim == 2 and a.shape[1] in (5, 8)
-        if a.shape[1] == 5:
-            full = np.zeros((a.shape[0], 8), np.float32)
-            full[:, :5] = a
-            a = full
-        a = np.ascontiguousarray(a)
+        a = _rows(dabs if dabs is not None else np.zeros((0, 5), np.float32), (5,), 8)
         params = capi.TextureParams(num_layers=len(layers), flags=capi.VR_TEXTURE_WHOLE_MAP if whole_map else 0, max_height=float(max_height))
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_texture(self.handle, C.byref(params), arr, _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_texture")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def Noise(self, which, frequency, amplitude, octaves=6, lacunarity=2.0, gain=0.5, offset=(0.0, 0.0), seed=0, basis="gradient", fractal="fbm",
               op="add", base=0.0, channels=None, dabs=None, whole_map=False):
@@ -670,16 +680,8 @@ class TerrainPass:
         `base` in stored units; `channels`: the channel mask (default: 1 for the heightmap, 0xF for the albedo).  `dabs`: rows as for
         Erode (strength an opacity), prepared for that map; their mask limits the call.  whole_map=True takes no dabs: mask 1 on every
         texel.  Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
-        idx = {"height": 0, "albedo": 1}.get(which, which)
-        a = np.asarray(dabs if dabs is not None else np.zeros((0, 5), np.float32), np.float32)
-        if a.ndim == 1:
-            a = a.reshape(-1, 5)
-        assert a.ndim == 2 and a.shape[1] in (5, 8)
-        if a.shape[1] == 5:
-            full = np.zeros((a.shape[0], 8), np.float32)
-            full[:, :5] = a
-            a = full
-        a = np.ascontiguousarray(a)
+        idx = _map_index(which)
+        a = _rows(dabs if dabs is not None else np.zeros((0, 5), np.float32), (5,), 8)
         p = capi.NoiseParams(frequency=float(frequency), offset_x=float(offset[0]), offset_z=float(offset[1]), lacunarity=float(lacunarity), gain=float(gain),
                              amplitude=float(amplitude), base=float(base), seed=int(seed) & 0xFFFFFFFF, octaves=int(octaves),
                              basis={"value": capi.VR_NOISE_VALUE, "gradient": capi.VR_NOISE_GRADIENT}.get(basis, basis),
@@ -687,9 +689,9 @@ class TerrainPass:
                              op={"add": capi.VR_NOISE_ADD, "blend": capi.VR_NOISE_BLEND}.get(op, op),
                              channel_mask=int(channels) if channels is not None else (1 if idx == 0 else 0xF),
                              flags=capi.VR_NOISE_WHOLE_MAP if whole_map else 0)
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_noise(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_noise")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def Path(self, which, points, radius, hardness=0.0, opacity=1.0, op="level", color=None, channels=None, closed=False):
         """vr_terrain_path: a corridor of half-width `radius` world units along the polyline through `points`, on level 0 of the
@@ -700,23 +702,15 @@ class TerrainPass:
         path, times `opacity` - and its target from the nearest segment, and changes once.  `color`: PAINT's four stored bytes'
         worth; `channels`: the channel mask (default: 1 for the heightmap, 0xF for the albedo); closed=True joins the last point to
         the first.  Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when the path misses the map."""
-        idx = {"height": 0, "albedo": 1}.get(which, which)
-        a = np.asarray(points, np.float32)
-        if a.ndim == 1:
-            a = a.reshape(-1, 3)
-        assert a.ndim == 2 and a.shape[1] in (2, 3, 4)
-        if a.shape[1] != 4:
-            full = np.zeros((a.shape[0], 4), np.float32)
-            full[:, :a.shape[1]] = a
-            a = full
-        a = np.ascontiguousarray(a)
+        idx = _map_index(which)
+        a = _rows(points, (2, 3), 4)
         p = capi.PathParams(op={"level": capi.VR_PATH_LEVEL, "cut": capi.VR_PATH_CUT, "fill": capi.VR_PATH_FILL, "paint": capi.VR_PATH_PAINT}.get(op, op),
                             channel_mask=int(channels) if channels is not None else (1 if idx == 0 else 0xF), radius=float(radius), hardness=float(hardness),
                             opacity=float(opacity), flags=capi.VR_PATH_CLOSED if closed else 0)
         p.color[:] = [float(c) for c in (color if color is not None else (0.0, 0.0, 0.0, 0.0))]
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_path(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_path")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def Region(self, which, points, op="level", target=0.0, feather=0.0, opacity=1.0, color=None, channels=None, feather_inside=False, contours=None):
         """vr_terrain_region: the inside of the polygon through `points`, on level 0 of the heightmap ('height' / 0: op 'level', 'cut',
@@ -727,7 +721,7 @@ class TerrainPass:
         width in world units of the soft skirt outside the outline - with feather_inside=True of the ramp inside it - 0 for a hard
         edge; `color`: PAINT's four stored bytes' worth; `channels`: the channel mask (default: 1 for the heightmap, 0xF for the
         albedo).  Returns (x, y, w, h) of the level-0 rectangle the call treated as dirty, (0, 0, 0, 0) when the region misses the map."""
-        idx = {"height": 0, "albedo": 1}.get(which, which)
+        idx = _map_index(which)
         a = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 2))
         p = capi.RegionParams(op={"level": capi.VR_REGION_LEVEL, "cut": capi.VR_REGION_CUT, "fill": capi.VR_REGION_FILL, "raise": capi.VR_REGION_RAISE,
                                   "paint": capi.VR_REGION_PAINT}.get(op, op),
@@ -735,15 +729,15 @@ class TerrainPass:
                               opacity=float(opacity), flags=capi.VR_REGION_FEATHER_INSIDE if feather_inside else 0)
         p.color[:] = [float(c) for c in (color if color is not None else (0.0, 0.0, 0.0, 0.0))]
         counts = (C.c_uint32 * len(contours))(*[int(c) for c in contours]) if contours is not None and len(contours) else None
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_region(self.handle, idx, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], counts, len(counts) if counts is not None else 0,
                                              rect), "vr_terrain_region")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def CaptureStamp(self, which, x, y, w, h):
         """vr_stamp_from_terrain: the w x h texels at (x, y) of level 0 of the heightmap ('height' / 0) or the albedo ('albedo' / 1) as
         they are on the device, as a Stamp - the clone tool's source; a device copy on the context's stream, nothing is synchronised."""
-        idx = {"height": 0, "albedo": 1}.get(which, which)
+        idx = _map_index(which)
         out = C.c_void_p()
         check(self.ctx.lib.vr_stamp_from_terrain(self.handle, idx, x, y, w, h, C.byref(out)), "vr_stamp_from_terrain")
         return Stamp(self.ctx, handle=out)
@@ -756,15 +750,15 @@ class TerrainPass:
         op: 'blend', 'add', 'sub', 'max', 'min' or capi.VR_STAMP_*; channels: the channel mask (default: 1 for the heightmap, 0xF for
         the albedo); use_alpha: the stamp's alpha scales the weight (albedo only).  Returns (x, y, w, h) of the level-0 rectangle the
         call treated as dirty, (0, 0, 0, 0) when the stamp misses the map."""
-        idx = {"height": 0, "albedo": 1}.get(which, which)
+        idx = _map_index(which)
         oid = {"blend": capi.VR_STAMP_BLEND, "add": capi.VR_STAMP_ADD, "sub": capi.VR_STAMP_SUB, "max": capi.VR_STAMP_MAX, "min": capi.VR_STAMP_MIN}.get(op, op)
         p = capi.StampParams(x=float(x), z=float(z), size_x=float(size_x), size_z=float(size_z), rotation=float(rotation), opacity=float(opacity),
                              feather=float(feather), gain=float(gain), offset=float(offset), op=int(oid),
                              channel_mask=int(channels) if channels is not None else (1 if idx == 0 else 0xF),
                              flags=capi.VR_STAMP_USE_ALPHA if use_alpha else 0)
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_stamp(self.handle, idx, stamp.handle, C.byref(p), rect), "vr_terrain_stamp")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def Erode(self, dabs, iterations, talus, rate):
         """vr_terrain_erode: `iterations` sweeps of thermal erosion on level 0 of the heightmap under the mask the dabs form (rows as
@@ -772,19 +766,11 @@ class TerrainPass:
         synchronised.  `talus`: the height difference per texel, in heightmap steps, that stays (0 .. 255; x sqrt 2 on the diagonals);
         `rate`: the share of the excess moved per sweep and neighbour, 0 < rate <= 0.125.  Returns (x, y, w, h) of the level-0
         rectangle the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
-        a = np.asarray(dabs, np.float32)
-        if a.ndim == 1:
-            a = a.reshape(-1, 5)
-        assert a.ndim == 2 and a.shape[1] in (5, 8)
-        if a.shape[1] == 5:
-            full = np.zeros((a.shape[0], 8), np.float32)
-            full[:, :5] = a
-            a = full
-        a = np.ascontiguousarray(a)
+        a = _rows(dabs, (5,), 8)
         params = capi.ErodeParams(iterations=int(iterations), talus=float(talus), rate=float(rate))
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_erode(self.handle, C.byref(params), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_erode")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def ErodeHydraulic(self, dabs, iterations, rain, flow, capacity, dissolve, deposit, evaporation):
         """vr_terrain_erode_hydraulic: `iterations` sweeps of hydraulic erosion on level 0 of the heightmap under the mask the dabs form
@@ -793,34 +779,26 @@ class TerrainPass:
         carried per unit of water given (0 .. 64); `dissolve`, `deposit`: the shares of the gap to the capacity taken up or laid down
         per sweep; `evaporation`: the share of the water lost per sweep (each 0 .. 1).  Returns (x, y, w, h) of the level-0 rectangle
         the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
-        a = np.asarray(dabs, np.float32)
-        if a.ndim == 1:
-            a = a.reshape(-1, 5)
-        assert a.ndim == 2 and a.shape[1] in (5, 8)
-        if a.shape[1] == 5:
-            full = np.zeros((a.shape[0], 8), np.float32)
-            full[:, :5] = a
-            a = full
-        a = np.ascontiguousarray(a)
+        a = _rows(dabs, (5,), 8)
         params = capi.HydroParams(iterations=int(iterations), rain=float(rain), flow=float(flow), capacity=float(capacity), dissolve=float(dissolve),
                                   deposit=float(deposit), evaporation=float(evaporation))
-        rect = (C.c_int32 * 4)()
+        rect = _rect()
         check(self.ctx.lib.vr_terrain_erode_hydraulic(self.handle, C.byref(params), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_erode_hydraulic")
-        return tuple(int(v) for v in rect)
+        return _rect_tuple(rect)
 
     def ErosionState(self):
         """vr_debug_terrain_sweep_state (test helper): what the last Erode or ErodeHydraulic of this terrain left on the device before
         the final rounding - ((x, y, w, h), mask, [planes]), float32 arrays of shape (h, w): one plane (h) after Erode, three (h, d,
         s) after ErodeHydraulic.  ((0, 0, 0, 0), None, []) when there is no such call, or the last one launched nothing."""
-        rect, fields = (C.c_int32 * 4)(), C.c_int32()
+        rect, fields = _rect(), C.c_int32()
         check(self.ctx.lib.vr_debug_terrain_sweep_state(self.handle, rect, C.byref(fields), None, 0), "vr_debug_terrain_sweep_state")
         if fields.value == 0:
-            return tuple(int(v) for v in rect), None, []
+            return _rect_tuple(rect), None, []
         w, h = int(rect[2]), int(rect[3])
         out = np.empty((1 + fields.value, h, w), np.float32)
         check(self.ctx.lib.vr_debug_terrain_sweep_state(self.handle, rect, C.byref(fields), _vp(out), out.size), "vr_debug_terrain_sweep_state")
         assert (int(rect[2]), int(rect[3]), fields.value) == (w, h, out.shape[0] - 1)
-        return tuple(int(v) for v in rect), out[0], [out[1 + f] for f in range(fields.value)]
+        return _rect_tuple(rect), out[0], [out[1 + f] for f in range(fields.value)]
 
     def EnableHistory(self, budget_bytes):
         """vr_terrain_history_enable: a device arena of budget_bytes in which every Edit and Brush from now on first records the
