@@ -189,7 +189,7 @@ VR_API int  vr_context_synchronize(vr_context* ctx);          /* Renderer::Submi
  * recorded frame would draw first queues the frame's plain tile pass on the context's stream, so that each of them finds exactly what
  * the eager frame leaves: vr_deferred_light*, vr_gbuffer_download / _upload / _describe / _region_census, a vr_terrain_render* that
  * does not write every pixel of every plane (keep-what-is-there, a partition, depth only, wireframe, vr_terrain_render_lit),
- * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _noise / _path / _region / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
+ * vr_terrain_edit / _brush / _texture / _stamp / _erode / _erode_hydraulic / _noise / _path / _region / _occlusion / _undo / _redo / _update_heights, vr_terrain_destroy.  Its error, if any, is that call's.  The next
  * whole-frame pass over a cleared target, or vr_gbuffer_clear, replaces the record: a frame nobody looked at costs nothing.  Depth is
  * never pending.  The first time a target's planes have to be produced this way ends the laziness for that target for good: a host
  * that reads the G-buffer pays one extra tile pass once and gets the G-buffer-keeping frames from then on.  The record holds the
@@ -340,6 +340,50 @@ typedef struct vr_texture_layer {      /* 64 B */
 typedef struct vr_texture_params { int32_t num_layers; uint32_t flags; float max_height; int32_t reserved[5]; } vr_texture_params; /* 32 B */
 VR_API int vr_terrain_texture(vr_terrain* t, const vr_texture_params* p, const vr_texture_layer* layers,
                               const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
+/* Sky visibility (ambient occlusion, "cavity") baked into level 0 of the albedo by horizon marching - a valley floor darker than a
+ * ridge with the same normal - under a brush mask or over the whole map, computed on the device from both maps as they are there and
+ * followed by the refresh vr_terrain_edit does: afterwards the terrain is the one vr_terrain_create builds from the heightmap and
+ * the new albedo.  The renderer is unchanged: no occlusion reaches shading except through the albedo's bytes.
+ * Each albedo texel stands on the height texel under its centre and marches level 0 of the heightmap from there along `directions`
+ * (4, 8 or 16) fixed directions - steps of (1,0), (2,1), (1,1), (1,2), ... height texels - out to `radius` world units.  A direction
+ * keeps its steepest horizon, the largest rise over distance of the samples inside the map (a sample outside the map is skipped),
+ * as a tangent t >= 0 less `bias`, and sees v = 1 - sin(atan(t)) of the sky, by a 64-interval table over t in [0, 8].  The texel's
+ * visibility is the mean of its directions' and its occlusion o = min((1 - visibility) * gain, 1).
+ *   VR_OCCLUSION_TINT   per channel c of channel_mask value_c += (m * (o * opacity)) * (color[c] - value_c)
+ *   VR_OCCLUSION_STORE  per channel c of channel_mask value_c += (m * opacity) * (255 * (1 - o) - value_c): the visibility as a byte,
+ *                       into a spare channel for instance
+ * clamped to [0, 255] and rounded to the nearest byte.  m is the mask of vr_terrain_texture: the dabs prepared for the albedo with
+ * their strength an opacity, or 1 on every texel with VR_OCCLUSION_WHOLE_MAP, which needs dabs == NULL and n == 0 and whose
+ * rectangle is the whole map.  A texel with mask 0 is not written.  The arithmetic is defined bit for bit in
+ * vrenderer_amd/csrc/vr_occlusion.h, without a division, a square root or trigonometry on the device.
+ * out_rect, `dabs`, the stream order and what the host waits for are vr_terrain_texture's: the call synchronises nothing, and the
+ * heightmap is read behind its last writer.  With history on, one call is one record.  n == 0 without the flag, or dabs that all
+ * miss the map, is VR_OK and launches nothing.
+ * VR_ERR_INVALID_ARGUMENT, checked before the first use of the device, with the terrain and its history untouched: NULL t or p;
+ * unknown flag bits; VR_OCCLUSION_WHOLE_MAP together with dabs; NULL dabs with n > 0; n > VR_MAX_BRUSH_DABS; a non-zero reserved
+ * word; an unknown mode; directions not 4, 8 or 16; a NaN or an infinity in a float; radius <= 0; max_height <= 0; gain outside
+ * [0, 16]; bias outside [0, 8); opacity outside [0, 1]; a color outside [0, 255]; a channel_mask of 0 or above 15; the dab refusals
+ * of vr_terrain_brush with an opacity for a strength; and a radius whose march reaches more than VR_OCCLUSION_MAX_REACH height
+ * texels on either axis in some direction (steps * max(|dx|, |dz|) > 64) - refused, not clamped.  Timing: as for vr_terrain_edit;
+ * the occlusion kernel itself is untimed. */
+#define VR_OCCLUSION_MAX_REACH 64          /* height texels, per axis */
+#define VR_OCCLUSION_TINT  0
+#define VR_OCCLUSION_STORE 1
+#define VR_OCCLUSION_WHOLE_MAP 1u
+typedef struct vr_occlusion_params {       /* 64 B */
+    float    radius;                       /* world units, > 0 */
+    float    max_height;                   /* the world height of byte 255: finite, > 0 (as vr_texture_params) */
+    float    gain;                         /* [0, 16]: occlusion = min((1 - visibility) * gain, 1) */
+    float    bias;                         /* [0, 8): subtracted from every horizon tangent; hides 8-bit terracing */
+    float    opacity;                      /* [0, 1] */
+    float    color[4];                     /* TINT: the shadow colour, stored encoding, [0, 255] */
+    uint32_t channel_mask;                 /* 1 .. 15 */
+    int32_t  directions;                   /* 4, 8 or 16 */
+    uint32_t mode;                         /* VR_OCCLUSION_TINT / _STORE */
+    uint32_t flags;                        /* VR_OCCLUSION_WHOLE_MAP */
+    uint32_t reserved[3];                  /* zero */
+} vr_occlusion_params;
+VR_API int vr_terrain_occlusion(vr_terrain* t, const vr_occlusion_params* p, const vr_brush_dab* dabs, uint32_t n, int32_t out_rect[4]);
 /* Procedural noise on level 0 of the heightmap (which = 0) or the albedo (1) - roughen a plateau, break up a smooth flank, speckle
  * an albedo, or make a fractal base terrain on a flat map - under a brush mask or over the whole map, computed on the device from
  * the map as it is there and followed by the refresh vr_terrain_edit does: afterwards the terrain is the one vr_terrain_create
@@ -614,13 +658,13 @@ VR_API int vr_debug_hydro_config(int32_t out[4]);
 /* measurement helper, process-wide: later calls advance `sweeps` (1 .. the build's figure; 0 = that figure again) sweeps per
  * launch.  The bytes are the same; only the number of launches changes.  VR_ERR_INVALID_ARGUMENT outside that range. */
 VR_API int vr_debug_hydro_sweeps_per_launch(int32_t sweeps);
-/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_noise, vr_terrain_path, vr_terrain_region, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
+/* History: undo and redo of vr_terrain_edit, vr_terrain_brush, vr_terrain_texture, vr_terrain_occlusion, vr_terrain_noise, vr_terrain_path, vr_terrain_region, vr_terrain_stamp, vr_terrain_erode and vr_terrain_erode_hydraulic, kept on the device. Off by default: every call then queues
  * exactly what it queues without it, undo / redo / commit are VR_OK and apply nothing, and the status is all zero.
  *   enable(budget_bytes)  one device arena of that size (vr_terrain_memory_bytes counts it under scratch; vr_terrain_destroy frees
  *                         it) and the host-side table of records, VR_HISTORY_MAX_RECORDS of them - nothing is allocated later.  The
  *                         budget it already has: nothing happens.  Any other budget drops all steps; 0 switches history off and
  *                         frees the arena.  A refusal is VR_ERR_OUT_OF_MEMORY with the terrain and the existing history untouched.
- *   records               with history on, every vr_terrain_edit, _brush, _texture, _noise, _path, _region, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
+ *   records               with history on, every vr_terrain_edit, _brush, _texture, _occlusion, _noise, _path, _region, _stamp, _erode and _erode_hydraulic that writes (not w == 0, n == 0 or a stroke
  *                         that misses the map) first captures its level-0 rectangle as it is, by a kernel on the context's stream
  *                         in front of the write.  Nothing more is synchronised: a stroke with history on still synchronises nothing.
  *   steps                 records join the open step; commit closes it (a drag of many brush calls becomes one undo step; with no

@@ -252,6 +252,17 @@ namespace vRenderer
             p.num_layers = numLayers; p.flags = wholeMap ? (uint32_t)VR_TEXTURE_WHOLE_MAP : 0u; p.max_height = maxHeight;
             return Check(vr_terrain_texture(m_Terrain, &p, layers, dabs, n, outRect), "vr_terrain_texture");
         }
+        // vr_terrain_occlusion: sky visibility baked into level 0 of the albedo by horizon marching over the heightmap (params: radius,
+        // max_height, gain, bias, opacity, color, channel_mask, directions, mode) under the mask the n dabs form (as for Texture,
+        // prepared for the albedo), or over the whole map (wholeMap: dabs == nullptr, n == 0; sets VR_OCCLUSION_WHOLE_MAP in a copy of
+        // params); computed on the device, stream-ordered like Brush, nothing is synchronised, and `dabs` is free again when the call
+        // returns.  outRect as for Brush.
+        bool Occlusion(const vr_occlusion_params& params, const vr_brush_dab* dabs, uint32_t n, bool wholeMap = false, int32_t outRect[4] = nullptr)
+        {
+            vr_occlusion_params p = params;
+            if (wholeMap) p.flags |= (uint32_t)VR_OCCLUSION_WHOLE_MAP;
+            return Check(vr_terrain_occlusion(m_Terrain, &p, dabs, n, outRect), "vr_terrain_occlusion");
+        }
         // vr_terrain_noise: fractal value or gradient noise (params: frequency, offset, lacunarity, gain, octaves, seed, basis, fractal)
         // added to or blended into level 0 of the heightmap (which = 0) or the albedo (1) under the mask the n dabs form (as for
         // Erode, prepared for that map), or over the whole map (wholeMap: dabs == nullptr, n == 0; sets VR_NOISE_WHOLE_MAP in a copy

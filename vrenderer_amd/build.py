@@ -13,7 +13,7 @@ CSRC = os.path.join(_DIR, "csrc")
 LIB_DIR = os.path.join(_DIR, "lib")
 OBJ_DIR = os.path.join(_DIR, "build")
 LIB = os.path.join(LIB_DIR, "libvrterrain.so")
-SOURCES = ["vr_host.hip", "vr_tex.hip", "vr_select.hip", "vr_raster.hip", "vr_deferred.hip", "vr_tonemap.hip", "vr_comm.hip", "vr_frame.hip", "vr_query.hip", "vr_derive.hip", "vr_brush.hip", "vr_history.hip", "vr_erode.hip", "vr_texture.hip", "vr_stamp.hip", "vr_noise.hip", "vr_path.hip", "vr_region.hip"]
+SOURCES = ["vr_host.hip", "vr_tex.hip", "vr_select.hip", "vr_raster.hip", "vr_deferred.hip", "vr_tonemap.hip", "vr_comm.hip", "vr_frame.hip", "vr_query.hip", "vr_derive.hip", "vr_brush.hip", "vr_history.hip", "vr_erode.hip", "vr_texture.hip", "vr_stamp.hip", "vr_noise.hip", "vr_path.hip", "vr_region.hip", "vr_occlusion.hip"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function"]
 

@@ -43,6 +43,9 @@ VR_HISTORY_MAX_RECORDS = 4096
 VR_ERODE_MAX_ITERATIONS = 1024
 VR_TEXTURE_MAX_LAYERS = 8
 VR_TEXTURE_WHOLE_MAP = 1
+VR_OCCLUSION_MAX_REACH = 64
+VR_OCCLUSION_TINT, VR_OCCLUSION_STORE = 0, 1
+VR_OCCLUSION_WHOLE_MAP = 1
 VR_HYDRO_MAX_ITERATIONS = 1024
 VR_NOISE_MAX_OCTAVES = 12
 VR_NOISE_VALUE = 0
@@ -228,6 +231,15 @@ class TextureParams(C.Structure):
     _fields_ = [("num_layers", C.c_int32), ("flags", C.c_uint32), ("max_height", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
+class OcclusionParams(C.Structure):
+    """vr_occlusion_params: how far and along how many directions the horizons are marched (radius in world units, directions 4, 8 or
+    16, max_height), what becomes of them (gain, bias) and what the call does with the occlusion (mode, opacity, color, channel_mask,
+    VR_OCCLUSION_WHOLE_MAP) - vr_terrain_occlusion."""
+    _fields_ = [("radius", C.c_float), ("max_height", C.c_float), ("gain", C.c_float), ("bias", C.c_float), ("opacity", C.c_float),
+                ("color", C.c_float * 4), ("channel_mask", C.c_uint32), ("directions", C.c_int32), ("mode", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
 class NoiseParams(C.Structure):
     """vr_noise_params: the lattice (frequency in cells per world unit, offset added to the world position, lacunarity, gain, octaves,
     seed), what it is made of (basis, fractal) and what it does (amplitude and base in stored units, op, channel_mask) -
@@ -279,6 +291,7 @@ assert C.sizeof(HistoryStatus) == 32
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(BrushDab) == 32 and C.sizeof(BrushStroke) == 32 and C.sizeof(ErodeParams) == 32 and C.sizeof(HydroParams) == 32
 assert C.sizeof(TextureLayer) == 64 and C.sizeof(TextureParams) == 32
+assert C.sizeof(OcclusionParams) == 64
 assert C.sizeof(StampParams) == 64
 assert C.sizeof(NoiseParams) == 64
 assert C.sizeof(PathPoint) == 16 and C.sizeof(PathParams) == 64
@@ -310,7 +323,7 @@ EXPORTS = [
     "vr_terrain_erode_hydraulic", "vr_debug_hydro_config", "vr_debug_hydro_sweeps_per_launch", "vr_debug_terrain_sweep_state",
     "vr_terrain_history_enable", "vr_terrain_history_commit", "vr_terrain_undo", "vr_terrain_redo", "vr_terrain_history_status",
     "vr_stamp_create", "vr_stamp_from_terrain", "vr_stamp_destroy", "vr_stamp_info", "vr_stamp_download", "vr_terrain_stamp",
-    "vr_terrain_noise", "vr_terrain_path", "vr_terrain_region",
+    "vr_terrain_noise", "vr_terrain_path", "vr_terrain_region", "vr_terrain_occlusion",
 ]
 
 _lib = None
@@ -439,6 +452,7 @@ def load_library():
         "vr_terrain_edit": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.c_int]),
         "vr_terrain_brush": (C.c_int, [vp, P(BrushStroke), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_texture": (C.c_int, [vp, P(TextureParams), vp, vp, C.c_uint32, P(C.c_int32)]),
+        "vr_terrain_occlusion": (C.c_int, [vp, P(OcclusionParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_noise": (C.c_int, [vp, C.c_int, P(NoiseParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_path": (C.c_int, [vp, C.c_int, P(PathParams), vp, C.c_uint32, P(C.c_int32)]),
         "vr_terrain_region": (C.c_int, [vp, C.c_int, P(RegionParams), vp, C.c_uint32, P(C.c_uint32), C.c_uint32, P(C.c_int32)]),

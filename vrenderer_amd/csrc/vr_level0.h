@@ -1,5 +1,5 @@
 // The host's call frame of every entry point that writes level 0 of a terrain map on the device (edit, brush, both erosions, texture,
-// stamp, noise, path, region), behind the entry point's own argument checks.  The ordering rules live here and nowhere else: a refusal comes before
+// occlusion, stamp, noise, path, region), behind the entry point's own argument checks.  The ordering rules live here and nowhere else: a refusal comes before
 // any effect, the history capture is first on the stream, hipGetLastError follows the launches, out_rect is zeroed past the last
 // argument refusal and filled on success only.  The kernels' side of it is vr_brush_dev.h; DESIGN.md 4aa.
 #pragma once

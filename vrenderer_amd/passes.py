@@ -671,6 +671,25 @@ class TerrainPass:
         check(self.ctx.lib.vr_terrain_texture(self.handle, C.byref(params), arr, _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_texture")
         return _rect_tuple(rect)
 
+    def Occlusion(self, dabs=None, *, radius, max_height, gain=1.0, bias=0.0, opacity=1.0, color=(0.0, 0.0, 0.0, 255.0), channels=7, directions=16, mode="tint",
+                  whole_map=False):
+        """vr_terrain_occlusion: sky visibility baked into level 0 of the albedo by marching the heightmap along `directions` (4, 8 or
+        16) directions out to `radius` world units, computed on the device; stream-ordered, nothing is synchronised.  `max_height`: the
+        world height of byte 255; occlusion = min((1 - visibility) * gain, 1); `bias` is subtracted from every horizon tangent.
+        mode 'tint' (or capi.VR_OCCLUSION_TINT) blends the channels of `channels` towards `color` (four stored bytes' worth) by
+        occlusion * opacity; 'store' writes the visibility as a byte into them, by `opacity`.  `dabs`: rows as for Erode (strength an
+        opacity), prepared for the albedo map; their mask limits the call.  whole_map=True takes no dabs: mask 1 on every texel.
+        Returns (x, y, w, h) of the level-0 rectangle of the albedo the call treated as dirty, (0, 0, 0, 0) when no dab meets the map."""
+        a = _rows(dabs if dabs is not None else np.zeros((0, 5), np.float32), (5,), 8)
+        p = capi.OcclusionParams(radius=float(radius), max_height=float(max_height), gain=float(gain), bias=float(bias), opacity=float(opacity),
+                                 channel_mask=int(channels), directions=int(directions),
+                                 mode={"tint": capi.VR_OCCLUSION_TINT, "store": capi.VR_OCCLUSION_STORE}.get(mode, mode),
+                                 flags=capi.VR_OCCLUSION_WHOLE_MAP if whole_map else 0)
+        p.color[:] = [float(c) for c in color]
+        rect = _rect()
+        check(self.ctx.lib.vr_terrain_occlusion(self.handle, C.byref(p), _vp(a) if a.shape[0] else None, a.shape[0], rect), "vr_terrain_occlusion")
+        return _rect_tuple(rect)
+
     def Noise(self, which, frequency, amplitude, octaves=6, lacunarity=2.0, gain=0.5, offset=(0.0, 0.0), seed=0, basis="gradient", fractal="fbm",
               op="add", base=0.0, channels=None, dabs=None, whole_map=False):
         """vr_terrain_noise: fractal noise added to ('add') or blended into ('blend', about `base`) level 0 of the heightmap ('height' /
